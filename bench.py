@@ -2,6 +2,18 @@
 """bench.py -- relevance maps/sec for ViT-B/16 224^2 at batch 64 per GPU (BASELINE.json metric; configs[1]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config vit_b16_224 | vit_l16_384 | bert_base_512]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps (every one a replayed HIP graph where the configuration is graphed), writes
+the last step's maps if ``--dump-outputs`` is given and prints the JSON line.  ``--full`` adds everything the headline figure
+does not need: the roofline block (one eager probe step inside the timed region, see below), the fp32-MFMA comparison run,
+the cpu_baseline leg and the parity block.  ``--cpu-baseline``, ``--cpu-maps``, ``--parity`` and ``--no-roofline`` act
+only with ``--full``.
+
+``--dump-outputs DIR`` writes DIR/maps.npy (float32): the maps the timed region ended with, all ranks in global order (the
+gathered maps of the last step; for sweep50k the gathered maps of every step).  Inputs and weights are seeded, so the
+same arguments give the same inputs run after run.  An output above 64 MB is cut to a fixed, seeded sample of rows,
+whose indices go to DIR/maps_rows.npy (float64).
 
 ``--gpus N`` with N > 1 launches N ranks by itself (one process per GPU under ``torch.distributed.run`` on
 127.0.0.1) when it is not already running under a launcher; under one (RANK in the environment, as the driver starts
@@ -13,13 +25,13 @@ SURVEY.md 8f.1 where the shape qualifies, --producers stock for PyTorch everywhe
 chain (LRP.generate_LRP, method "transformer_attribution", start_layer 1 as baselines/ViT/imagenet_seg_eval.py:196 of
 the reference calls it), fp32 end to end.  All blocks are propagated; the only shortcuts are exact or rounding-level
 (DESIGN.md section 3).  Every rank replays its step from a HIP graph captured BEFORE the process group exists (so
-RCCL's threads never see an open capture); ONE step of the timed region runs eagerly with a HIP-event pair around
-every C-ABI call of the relprop path -- the source of the roofline block.
+RCCL's threads never see an open capture); with --full ONE step of the timed region runs eagerly with a HIP-event pair
+around every C-ABI call of the relprop path -- the source of the roofline block.
 
 Weak scaling: every rank runs the same batch size on its own inputs; the only communication is one all_gather (RCCL)
 of the finished maps of the last step, inside the timed region.
 
-The JSON line carries
+The JSON line carries (with --full; null in a plain run)
   roofline      dominant kernel (Linear.relprop C-pass, fp32 MFMA) + ``kernels``: one entry per relprop kernel group
                 with its ALGORITHMIC FLOPs / bytes per launch, the average launch duration from
                 HIP events on the launch stream, and the fraction of the roofline that bounds it
@@ -78,6 +90,8 @@ def _resolve(args):
     args.inflight_auto = args.inflight is None       # resolved in main() once the per-GPU batch is known
     if args.inflight is None:
         args.inflight = 1
+    if not args.full:           # a plain run: the headline figure only
+        args.no_roofline, args.cpu_baseline, args.parity = True, "off", "off"
     return args
 
 
@@ -139,6 +153,13 @@ def parse_args(argv=None):
                     help="tile geometry of the x6 Linear kernels (the maps do not depend on it, bit for bit): auto = 256 x 256 "
                          "tiles wherever the feature counts allow while the step runs concurrent streams (least CU-time per "
                          "launch), else the library's per-launch policy; lib = that policy always; 128 / 256 = pinned")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the roofline block (one eager "
+                         "probe step inside the timed region), the fp32-MFMA comparison run, the cpu_baseline leg and the "
+                         "parity block; a plain run does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the maps the timed region ended with to DIR/maps.npy (float32; a "
+                         "fixed, seeded sample of rows, indices in DIR/maps_rows.npy, where they exceed 64 MB)")
     ap.add_argument("--producers", choices=["stock", "fused"], default="fused",
                     help="fused (default): the attention blocks' forward and attention-gradient backward run on the "
                          "hand-written producer kernels (SURVEY.md 8f.1: head dim 64; N <= 224 one workgroup per head, N <= 640 "
@@ -157,10 +178,13 @@ def _free_port():
 
 def build_once():
     """__graft_entry__.build() under an exclusive file lock: every rank may call it, one compiles, the rest wait and
-    find the library up to date (no process group needed, so it can run before init_process_group)."""
+    find the library up to date (no process group needed, so it can run before init_process_group).  The lock lives in
+    the temporary directory, one per user and tree, so that a checkout the benchmark may not write to still runs."""
+    import hashlib
+    import tempfile
     import __graft_entry__
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    with open(os.path.join(ROOT, "gpurun_out", ".build.lock"), "w") as lock:
+    tag = hashlib.sha1(ROOT.encode()).hexdigest()[:16]
+    with open(os.path.join(tempfile.gettempdir(), f"te_relprop_build_{os.getuid()}_{tag}.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
             __graft_entry__.build()
@@ -718,6 +742,26 @@ def cpu_baseline_parity(args, wl, gpu_maps, ref_maps):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, maps):
+    """--dump-outputs: the maps the timed region ended with as DIR/maps.npy (float32).  Above DUMP_LIMIT_BYTES a fixed,
+    seeded sample of rows is written instead, in ascending order, with their indices in DIR/maps_rows.npy (float64)."""
+    import numpy as np
+    import torch
+    maps = maps.detach().float().cpu().reshape(maps.shape[0], -1)
+    os.makedirs(out_dir, exist_ok=True)
+    row_bytes = maps.shape[1] * 4
+    if maps.numel() * 4 > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // row_bytes
+        rows = torch.randperm(maps.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        maps = maps[rows]
+        np.save(os.path.join(out_dir, "maps_rows.npy"), rows.numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "maps.npy"), maps.numpy())
+    log(f"--dump-outputs: {tuple(maps.shape)} float32 maps written to {out_dir}")
+
+
 # -------------------------------------------------------------------------------------------------------------- main
 def main():
     args = parse_args()
@@ -910,12 +954,14 @@ def main():
     gpu_maps = None if wl.sweep else maps.detach().clone()             # (a graph's static output: kept before anything re-runs)
     assert gathered.shape == ((n_sweep if wl.sweep else world * B), wl.out_cols) and torch.isfinite(gathered).all()
     ops.x6_raise_if_failed(dev)      # sticky device word of every x6 launch of the run (no synchronisation inside a step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered)
 
     # Rounds stay comparable: with the x6 Linear rules the same workload is timed once more on the fp32-MFMA kernels of
-    # csrc/te_linear.hip (own graph capture, one warm-up, the same number of steps); N = 1 only, after the timed region.
+    # csrc/te_linear.hip (own graph capture, one warm-up, the same number of steps); --full, N = 1 only, after the timed region.
     fp32_cmp = {}
     used_graph = graphed is not None or lane_graphs is not None
-    if args.linear == "x6" and world == 1 and not wl.sweep:
+    if args.full and args.linear == "x6" and world == 1 and not wl.sweep:
         lane_graphs = None
         ops.USE_LINEAR_X6 = False
         ops.X6_GEMM = "off"          # the comparison run executes no bf16 MFMA at all: rules AND layer products on fp32 MFMAs
@@ -1016,7 +1062,8 @@ def main():
                                                    else "stock fp32 GEMMs"),
                        **fp32_cmp,
                        "hip_graph": used_graph, "parallelism": f"dp{world} (independent samples, one "
-                                                                      f"all_gather of the maps)"},
+                                                                      f"all_gather of the maps)",
+                       "full": args.full},
         }
         roof = None
         traffic = None

@@ -10,8 +10,8 @@ except Exception as e: print('FAILED', e)"; }
 {
 echo "== pytest: pruning / overlap / tuned gemms / segmentation / sweep"
 python -m pytest tests -q -m gpu -k "batch_equals_singles or pruned or tuned or segmentation or sweep or full_batch" 2>&1 | tail -5
-echo "== bench default"; python bench.py --steps 8 --warmup 2 --cpu-baseline off 2>/dev/null | show
-echo "== bench --prune on"; python bench.py --steps 8 --warmup 2 --cpu-baseline off --prune on 2>/dev/null | show
-echo "== bench --overlap-backward on"; python bench.py --steps 8 --warmup 2 --cpu-baseline off --overlap-backward on 2>/dev/null | show
-echo "== bench --prune on --overlap-backward on"; python bench.py --steps 8 --warmup 2 --cpu-baseline off --prune on --overlap-backward on 2>/dev/null | show
+echo "== bench default"; python bench.py --full --steps 8 --warmup 2 --cpu-baseline off 2>/dev/null | show
+echo "== bench --prune on"; python bench.py --full --steps 8 --warmup 2 --cpu-baseline off --prune on 2>/dev/null | show
+echo "== bench --overlap-backward on"; python bench.py --full --steps 8 --warmup 2 --cpu-baseline off --overlap-backward on 2>/dev/null | show
+echo "== bench --prune on --overlap-backward on"; python bench.py --full --steps 8 --warmup 2 --cpu-baseline off --prune on --overlap-backward on 2>/dev/null | show
 } 2>&1 | tee gpurun_out/trip_f.log

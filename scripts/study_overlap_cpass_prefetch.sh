@@ -13,7 +13,7 @@ TE_CPASS_PF=2 python -m pytest tests/test_gpu_rules.py tests/test_gpu_models.py 
 for ov in off on; do
   for pf in 1 2; do
     echo "== bench overlap=$ov TE_CPASS_PF=$pf"
-    TE_CPASS_PF=$pf python bench.py --steps 8 --warmup 2 --cpu-baseline off --overlap-backward $ov 2>/dev/null | tail -1 | python -c "
+    TE_CPASS_PF=$pf python bench.py --full --steps 8 --warmup 2 --cpu-baseline off --overlap-backward $ov 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('maps/s %.1f  ms/step %.2f  cpass %.1f TF frac %.3f  zfwd %.1f TF' % (d['value'], d['ms_per_step'], r['achieved'], r['frac'], r['zpass']['achieved']))"

@@ -10,16 +10,16 @@ try:
 except Exception as e: print('FAILED', e)"; }
 {
 echo "== default"
-python bench.py --steps 8 --warmup 2 --cpu-baseline off 2>/dev/null | show
+python bench.py --full --steps 8 --warmup 2 --cpu-baseline off 2>/dev/null | show
 echo "== TORCH_BLAS_PREFER_HIPBLASLT=0"
-TORCH_BLAS_PREFER_HIPBLASLT=0 python bench.py --steps 8 --warmup 2 --cpu-baseline off 2>/dev/null | show
+TORCH_BLAS_PREFER_HIPBLASLT=0 python bench.py --full --steps 8 --warmup 2 --cpu-baseline off 2>/dev/null | show
 echo "== TORCH_BLAS_PREFER_HIPBLASLT=1"
-TORCH_BLAS_PREFER_HIPBLASLT=1 python bench.py --steps 8 --warmup 2 --cpu-baseline off 2>/dev/null | show
+TORCH_BLAS_PREFER_HIPBLASLT=1 python bench.py --full --steps 8 --warmup 2 --cpu-baseline off 2>/dev/null | show
 echo "== TunableOp tuning run"
 export PYTORCH_TUNABLEOP_FILENAME=gpurun_out/tunableop_results.csv
 export PYTORCH_TUNABLEOP_MAX_TUNING_DURATION_MS=15 PYTORCH_TUNABLEOP_MAX_WARMUP_DURATION_MS=5
-( time PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=1 timeout 420 python bench.py --steps 3 --warmup 2 --cpu-baseline off --graph off 2>gpurun_out/tunable_tuning.err | show ) 2>&1 | grep -v "^$" | grep -v user | grep -v sys
+( time PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=1 timeout 420 python bench.py --full --steps 3 --warmup 2 --cpu-baseline off --graph off 2>"$(dirname "$PYTORCH_TUNABLEOP_FILENAME")/tunable_tuning.err" | show ) 2>&1 | grep -v "^$" | grep -v user | grep -v sys
 ls -la gpurun_out/tunableop_results*.csv 2>/dev/null; wc -l gpurun_out/tunableop_results*.csv 2>/dev/null
 echo "== TunableOp tuned (no further tuning)"
-PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=0 python bench.py --steps 8 --warmup 2 --cpu-baseline off 2>/dev/null | show
+PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=0 python bench.py --full --steps 8 --warmup 2 --cpu-baseline off 2>/dev/null | show
 } 2>&1 | tee gpurun_out/trip_c.log

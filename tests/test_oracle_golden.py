@@ -138,10 +138,11 @@ def _live_reference():
 
 @pytest.mark.parametrize("seed", [101, 202])
 @pytest.mark.parametrize("variant", ["ours", "lrp"])
-def test_live_reference_vit_vs_oracle(seed, variant):
+def test_live_reference_vit_vs_oracle(seed, variant, monkeypatch):
     """Runs the unmodified reference NOW (not a replayed fixture) on a freshly seeded small ViT and input, extracts the
     tensors its relprop reads, and requires the oracle to reproduce every block's attn_cam and the final map."""
     rh = _live_reference()
+    monkeypatch.setattr(torch.Tensor, "cuda", lambda self, *a, **k: self)    # the generators call .cuda(): stay on the host
     vit = rh.load_reference_vit()
     modname, method = (("ViT_LRP", "transformer_attribution") if variant == "ours" else ("ViT_orig_LRP", "grad"))
     model = vit[modname].VisionTransformer(img_size=32, patch_size=8, embed_dim=64, depth=3, num_heads=4, num_classes=10,
@@ -162,8 +163,9 @@ def test_live_reference_vit_vs_oracle(seed, variant):
 
 
 @pytest.mark.parametrize("seed", [303])
-def test_live_reference_bert_vs_oracle(seed):
+def test_live_reference_bert_vs_oracle(seed, monkeypatch):
     rh = _live_reference()
+    monkeypatch.setattr(torch.Tensor, "cuda", lambda self, *a, **k: self)    # the generators call .cuda(): stay on the host
     bert = rh.load_reference_bert()
     from transformers import BertConfig
     cfg = BertConfig(vocab_size=100, hidden_size=64, num_hidden_layers=3, num_attention_heads=4, intermediate_size=128,
