@@ -35,6 +35,7 @@ extern "C" {
 #endif
 
 typedef void* te_stream_t; /* hipStream_t */
+typedef uint16_t te_bf16_t; /* one bf16 value (the upper half of an fp32) */
 
 enum {
   TE_OK = 0,
@@ -510,6 +511,64 @@ size_t te_perturb_workspace_bytes(int64_t B, int64_t n_steps);
 int te_perturb_f32(const float* vis, const float* data, float* out, int64_t B, int64_t C, int64_t HW,
                    const int64_t* ks, int64_t n_steps, const float* mean, const float* std_, void* ws,
                    size_t ws_bytes, te_stream_t stream);
+
+/* ---- bf16 operands (a bf16 model: model.to(torch.bfloat16)) -----------------------------------------------
+ * The rules of variant "ours", alpha = 1, evaluated in fp32 on the model's own bf16 tensors (te_bf16_t, read exactly:
+ * bf16 -> fp32 is exact).  Relevance operands and outputs, safe_divide, per-sample sums and factors are fp32 as in the
+ * _f32 entry points; the arguments mean what they mean there.  csrc/te_bf16.hip (GEMM-shaped rules, bf16 MFMAs) and
+ * csrc/te_elementwise.hip (streaming rules, the _f32 kernels templated on the operand type).
+ *
+ * Linear.relprop: Z = X+ W+^T + X- W-^T from the bf16 X and W (never from the cached output Y), S = sd(R f, Z) kept as
+ * three bf16 planes, out = X+ (S W+) + X- (S W-).  R [T, r_ld >= out_f] fp32 with the optional per-sample factor
+ * r_scale[(t / rows_per_scale) * r_scale_stride]; X [T, x_ld >= in_f] bf16 (a row stride: cls rows in place); w_planes =
+ * te_linear_bf16_prepare_weights of W [out_f, in_f] bf16 (build once per weight version); out [T, in_f] fp32.
+ * Shapes: te_linear_relprop_bf16_supported (in_f, out_f multiples of 128); TE_ERR_UNSUPPORTED otherwise. */
+int te_linear_relprop_bf16_supported(int64_t T, int64_t in_f, int64_t out_f);
+size_t te_linear_relprop_bf16_workspace_bytes(int64_t T, int64_t in_f, int64_t out_f);
+size_t te_linear_bf16_weight_planes_bytes(int64_t in_f, int64_t out_f);
+int te_linear_bf16_prepare_weights(const te_bf16_t* W, int64_t in_f, int64_t out_f, void* planes, size_t planes_bytes,
+                                   te_stream_t stream);
+int te_linear_relprop_bf16(const float* R, int64_t r_ld, const float* r_scale, int64_t r_scale_stride,
+                           int64_t rows_per_scale, const te_bf16_t* X, int64_t x_ld, const void* w_planes, float* out,
+                           int64_t T, int64_t in_f, int64_t out_f, void* ws, size_t ws_bytes, te_stream_t stream);
+/* The two attention rules with bf16 operands: the argument lists of te_matmul_relprop_av_fwdz_f32 and
+ * te_matmul_relprop_qk_fwd_scaled_f32.  attn, Z (QK) contiguous; q / k / v / Z (AV) strided with a contiguous last dim
+ * (views of the fused qkv activation are read in place).  Z == NULL: recomputed in fp32 from the bf16 operands.
+ * Shapes: te_matmul_relprop_bf16_supported (head dim 64, N <= 1024); variant ours only. */
+int te_matmul_relprop_bf16_supported(int64_t N, int64_t D);
+size_t te_matmul_relprop_av_bf16_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t D);
+size_t te_matmul_relprop_qk_bf16_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t D);
+int te_matmul_relprop_av_bf16(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn,
+                              const te_bf16_t* attn,
+                              const te_bf16_t* v, int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                              const te_bf16_t* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn,
+                              float* cam_attn,
+                              float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn,
+                              int64_t B, int64_t H, int64_t N, int64_t D, float out_scale, int variant,
+                              void* ws, size_t ws_bytes, te_stream_t stream);
+int te_matmul_relprop_qk_bf16(const float* R_nn, const float* r_scale, int64_t r_scale_stride,
+                              const te_bf16_t* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                              const te_bf16_t* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                              const te_bf16_t* Z,
+                              float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn,
+                              float* cam_k, int64_t ck_sb, int64_t ck_sh, int64_t ck_sn,
+                              int64_t B, int64_t H, int64_t N, int64_t D, float out_scale, int variant,
+                              void* ws, size_t ws_bytes, te_stream_t stream);
+/* Streaming rules: the _f32 entry points with bf16 operands X0 / X1 / X / grad (workspaces as there). */
+int te_add_relprop_bf16(const float* R, const te_bf16_t* X0, const te_bf16_t* X1, float* out0, float* out1, int64_t B,
+                        int64_t n, int64_t x1_batch_stride, int variant, void* ws, size_t ws_bytes, te_stream_t stream);
+int te_add_relprop_deferred_bf16(const float* R, const te_bf16_t* X0, const te_bf16_t* X1, float* a, float* b,
+                                 float* fac, int64_t B, int64_t n, int64_t x1_batch_stride, void* ws, size_t ws_bytes,
+                                 te_stream_t stream);
+int te_clone_relprop_bf16(const float* R0, const float* R1, const float* R2, const te_bf16_t* X, float* out, int64_t n,
+                          te_stream_t stream);
+int te_clone_relprop_scaled_bf16(const float* R0, const float* s0, int64_t s0_stride, const float* R1, const float* s1,
+                                 int64_t s1_stride, const float* R2, const float* s2, int64_t s2_stride,
+                                 const te_bf16_t* X, float* out, int64_t B, int64_t n, te_stream_t stream);
+int te_index_select_relprop_bf16(const float* R, const te_bf16_t* X, float* out, int64_t B, int64_t N, int64_t C,
+                                 int64_t index, te_stream_t stream);
+int te_gradcam_headmean_bf16(const te_bf16_t* grad, const float* cam, float* out, int64_t B, int64_t H, int64_t N,
+                             te_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -120,6 +120,25 @@ SIGNATURES = {
     "te_rollout_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "te_rollout_row0_workspace_bytes": (_SZ, [_I64, _I64]),
     "te_rollout_f32": (_I, [_P, _I64, _I64, _I64, _I64, _I, _P, _P, _SZ, _P]),
+    # bf16 operands (csrc/te_bf16.hip, csrc/te_elementwise.hip)
+    "te_linear_relprop_bf16_supported": (_I, [_I64, _I64, _I64]),
+    "te_linear_relprop_bf16_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "te_linear_bf16_weight_planes_bytes": (_SZ, [_I64, _I64]),
+    "te_linear_bf16_prepare_weights": (_I, [_P, _I64, _I64, _P, _SZ, _P]),
+    "te_linear_relprop_bf16": (_I, [_P, _I64, _P, _I64, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
+    "te_matmul_relprop_bf16_supported": (_I, [_I64, _I64]),
+    "te_matmul_relprop_av_bf16_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "te_matmul_relprop_qk_bf16_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "te_matmul_relprop_av_bf16": (_I, [_P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P,
+                                       _I64, _I64, _I64, _I64, _I64, _I64, _I64, _F, _I, _P, _SZ, _P]),
+    "te_matmul_relprop_qk_bf16": (_I, [_P, _P, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _I64, _I64,
+                                       _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _F, _I, _P, _SZ, _P]),
+    "te_add_relprop_bf16": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _P, _SZ, _P]),
+    "te_add_relprop_deferred_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
+    "te_clone_relprop_bf16": (_I, [_P, _P, _P, _P, _P, _I64, _P]),
+    "te_clone_relprop_scaled_bf16": (_I, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _P]),
+    "te_index_select_relprop_bf16": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _P]),
+    "te_gradcam_headmean_bf16": (_I, [_P, _P, _P, _I64, _I64, _I64, _P]),
 }
 
 

@@ -21,24 +21,36 @@ __device__ __forceinline__ V ld(const float* p) { return *reinterpret_cast<const
 template <typename V>
 __device__ __forceinline__ void st(float* p, V v) { *reinterpret_cast<V*>(p) = v; }
 
+// Operand (activation) loads, templated on the operand type TX: fp32 exactly as before, or bf16 (te_bf16_t) widened
+// exactly to fp32 -- a bf16 model's rules read its own bf16 tensors; relevance, sums and outputs stay fp32.
+__device__ __forceinline__ float ldx(const float* p) { return *p; }
+__device__ __forceinline__ float ldx(const te_bf16_t* p) { return __uint_as_float((unsigned)*p << 16); }
+template <typename V>
+__device__ __forceinline__ V ldx4(const float* p) { return ld<V>(p); }
+template <typename V>
+__device__ __forceinline__ V ldx4(const te_bf16_t* p) { return V{ldx(p), ldx(p + 1), ldx(p + 2), ldx(p + 3)}; }
+// host: the vector path needs 16-byte fp32 operands; bf16 operands are read element by element
+static inline bool vec_aligned(const float* p) { return te_aligned16(p); }
+static inline bool vec_aligned(const te_bf16_t*) { return true; }
+
 // ------------------------------------------------------------------------------------------------
 // Add.relprop (modules/layers_ours.py:97-120).  Pass 1: per-(sample, chunk) partial sums.
 // ------------------------------------------------------------------------------------------------
-template <int VEC>
+template <int VEC, typename TX>
 __global__ __launch_bounds__(kThreads) void add_sums_kernel(
-    const float* __restrict__ R, const float* __restrict__ X0, const float* __restrict__ X1,
+    const float* __restrict__ R, const TX* __restrict__ X0, const TX* __restrict__ X1,
     double* __restrict__ partial, int64_t n, int64_t x1_bs, int64_t chunk) {
   __shared__ double smem[3 * (kThreads / 64)];
   const int64_t b = blockIdx.y;
   const int64_t start = (int64_t)blockIdx.x * chunk;
   const int64_t end = min(n, start + chunk);
   const float* r = R + b * n;
-  const float* x0 = X0 + b * n;
-  const float* x1 = X1 + b * x1_bs;
+  const TX* x0 = X0 + b * n;
+  const TX* x1 = X1 + b * x1_bs;
   double sa = 0.0, sb = 0.0, sr = 0.0;
   for (int64_t i = start + (int64_t)threadIdx.x * VEC; i < end; i += (int64_t)kThreads * VEC) {
     if constexpr (VEC == 4) {
-      const f32x4 rv = ld<f32x4>(r + i), av = ld<f32x4>(x0 + i), bv = ld<f32x4>(x1 + i);
+      const f32x4 rv = ld<f32x4>(r + i), av = ldx4<f32x4>(x0 + i), bv = ldx4<f32x4>(x1 + i);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float s = te_sd(rv[e], av[e] + bv[e]);
@@ -47,7 +59,7 @@ __global__ __launch_bounds__(kThreads) void add_sums_kernel(
         sr += (double)rv[e];
       }
     } else {
-      const float rv = r[i], av = x0[i], bv = x1[i];
+      const float rv = r[i], av = ldx(x0 + i), bv = ldx(x1 + i);
       const float s = te_sd(rv, av + bv);
       sa += (double)(av * s);
       sb += (double)(bv * s);
@@ -67,9 +79,9 @@ __global__ __launch_bounds__(kThreads) void add_sums_kernel(
 // per-sample factors are applied by whoever reads them next (Clone / the Linear Z-pass epilogue multiply R by the
 // sample's factor -- the identical fp32 product the apply pass would have stored), so Add.relprop moves its
 // algorithmic 5 n floats per sample exactly once.
-template <int VEC>
+template <int VEC, typename TX>
 __global__ __launch_bounds__(kThreads) void add_deferred_kernel(
-    const float* __restrict__ R, const float* __restrict__ X0, const float* __restrict__ X1,
+    const float* __restrict__ R, const TX* __restrict__ X0, const TX* __restrict__ X1,
     float* __restrict__ a_out, float* __restrict__ b_out, double* __restrict__ partial, int64_t n, int64_t x1_bs,
     int64_t chunk) {
   __shared__ double smem[3 * (kThreads / 64)];
@@ -77,14 +89,14 @@ __global__ __launch_bounds__(kThreads) void add_deferred_kernel(
   const int64_t start = (int64_t)blockIdx.x * chunk;
   const int64_t end = min(n, start + chunk);
   const float* r = R + b * n;
-  const float* x0 = X0 + b * n;
-  const float* x1 = X1 + b * x1_bs;
+  const TX* x0 = X0 + b * n;
+  const TX* x1 = X1 + b * x1_bs;
   float* o0 = a_out + b * n;
   float* o1 = b_out + b * n;
   double sa = 0.0, sb = 0.0, sr = 0.0;
   for (int64_t i = start + (int64_t)threadIdx.x * VEC; i < end; i += (int64_t)kThreads * VEC) {
     if constexpr (VEC == 4) {
-      const f32x4 rv = ld<f32x4>(r + i), av = ld<f32x4>(x0 + i), bv = ld<f32x4>(x1 + i);
+      const f32x4 rv = ld<f32x4>(r + i), av = ldx4<f32x4>(x0 + i), bv = ldx4<f32x4>(x1 + i);
       f32x4 oa, ob;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -98,7 +110,7 @@ __global__ __launch_bounds__(kThreads) void add_deferred_kernel(
       st<f32x4>(o0 + i, oa);
       st<f32x4>(o1 + i, ob);
     } else {
-      const float rv = r[i], av = x0[i], bv = x1[i];
+      const float rv = r[i], av = ldx(x0 + i), bv = ldx(x1 + i);
       const float s = te_sd(rv, av + bv);
       const float a = av * s, bb = bv * s;
       o0[i] = a;
@@ -159,9 +171,9 @@ __global__ __launch_bounds__(64) void add_factors_kernel(const double* __restric
 }
 
 // Pass 2 (ours) / the only pass (lrp): recompute a, b and apply the per-sample factors.
-template <int VEC, bool OURS>
+template <int VEC, bool OURS, typename TX>
 __global__ __launch_bounds__(kThreads) void add_apply_kernel(
-    const float* __restrict__ R, const float* __restrict__ X0, const float* __restrict__ X1,
+    const float* __restrict__ R, const TX* __restrict__ X0, const TX* __restrict__ X1,
     float* __restrict__ out0, float* __restrict__ out1, const double* __restrict__ partial,
     int64_t n, int64_t x1_bs, int64_t chunk) {
   __shared__ float fac[2];
@@ -184,13 +196,13 @@ __global__ __launch_bounds__(kThreads) void add_apply_kernel(
   const int64_t start = (int64_t)blockIdx.x * chunk;
   const int64_t end = min(n, start + chunk);
   const float* r = R + b * n;
-  const float* x0 = X0 + b * n;
-  const float* x1 = X1 + b * x1_bs;
+  const TX* x0 = X0 + b * n;
+  const TX* x1 = X1 + b * x1_bs;
   float* o0 = out0 + b * n;
   float* o1 = out1 + b * n;
   for (int64_t i = start + (int64_t)threadIdx.x * VEC; i < end; i += (int64_t)kThreads * VEC) {
     if constexpr (VEC == 4) {
-      const f32x4 rv = ld<f32x4>(r + i), av = ld<f32x4>(x0 + i), bv = ld<f32x4>(x1 + i);
+      const f32x4 rv = ld<f32x4>(r + i), av = ldx4<f32x4>(x0 + i), bv = ldx4<f32x4>(x1 + i);
       f32x4 oa, ob;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -206,7 +218,7 @@ __global__ __launch_bounds__(kThreads) void add_apply_kernel(
       st<f32x4>(o0 + i, oa);
       st<f32x4>(o1 + i, ob);
     } else {
-      const float rv = r[i], av = x0[i], bv = x1[i];
+      const float rv = r[i], av = ldx(x0 + i), bv = ldx(x1 + i);
       const float s = te_sd(rv, av + bv);
       float a = av * s, bb = bv * s;
       if constexpr (OURS) {
@@ -360,14 +372,14 @@ __global__ __launch_bounds__(kThreads) void addb_apply_kernel(
 // ------------------------------------------------------------------------------------------------
 // Clone.relprop (modules/layers_ours.py:151-169): out = X * (sd(R0,X) + sd(R1,X) [+ sd(R2,X)])
 // ------------------------------------------------------------------------------------------------
-template <int VEC, int NUM>
+template <int VEC, int NUM, typename TX>
 __global__ __launch_bounds__(kThreads) void clone_kernel(
     const float* __restrict__ R0, const float* __restrict__ R1, const float* __restrict__ R2,
-    const float* __restrict__ X, float* __restrict__ out, int64_t n) {
+    const TX* __restrict__ X, float* __restrict__ out, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * kThreads * VEC;
   for (int64_t i = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * VEC; i < n; i += stride) {
     if constexpr (VEC == 4) {
-      const f32x4 x = ld<f32x4>(X + i), a = ld<f32x4>(R0 + i), b = ld<f32x4>(R1 + i);
+      const f32x4 x = ldx4<f32x4>(X + i), a = ld<f32x4>(R0 + i), b = ld<f32x4>(R1 + i);
       f32x4 c = {0.f, 0.f, 0.f, 0.f};
       if constexpr (NUM == 3) c = ld<f32x4>(R2 + i);
       f32x4 o;
@@ -379,7 +391,7 @@ __global__ __launch_bounds__(kThreads) void clone_kernel(
       }
       st<f32x4>(out + i, o);
     } else {
-      const float x = X[i];
+      const float x = ldx(X + i);
       float s = te_sd(R0[i], x) + te_sd(R1[i], x);
       if constexpr (NUM == 3) s = s + te_sd(R2[i], x);
       out[i] = x * s;
@@ -389,23 +401,23 @@ __global__ __launch_bounds__(kThreads) void clone_kernel(
 
 // Clone.relprop whose relevance operands carry a deferred per-sample factor (the unscaled outputs of
 // te_add_relprop_deferred_f32): R_i enters as R_i[e] * s_i[sample]; s_i == NULL means 1.  2-D grid (chunks, samples).
-template <int VEC, int NUM>
+template <int VEC, int NUM, typename TX>
 __global__ __launch_bounds__(kThreads) void clone_scaled_kernel(
     const float* __restrict__ R0, const float* __restrict__ s0, int64_t s0_stride, const float* __restrict__ R1,
     const float* __restrict__ s1, int64_t s1_stride, const float* __restrict__ R2, const float* __restrict__ s2,
-    int64_t s2_stride, const float* __restrict__ X, float* __restrict__ out, int64_t n) {
+    int64_t s2_stride, const TX* __restrict__ X, float* __restrict__ out, int64_t n) {
   const int64_t b = blockIdx.y;
   const float f0 = s0 ? s0[b * s0_stride] : 1.0f, f1 = s1 ? s1[b * s1_stride] : 1.0f;
   const float f2 = (NUM == 3 && s2) ? s2[b * s2_stride] : 1.0f;
   const float* r0 = R0 + b * n;
   const float* r1 = R1 + b * n;
   const float* r2 = (NUM == 3) ? R2 + b * n : nullptr;
-  const float* x_ = X + b * n;
+  const TX* x_ = X + b * n;
   float* o = out + b * n;
   const int64_t stride = (int64_t)gridDim.x * kThreads * VEC;
   for (int64_t i = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * VEC; i < n; i += stride) {
     if constexpr (VEC == 4) {
-      const f32x4 x = ld<f32x4>(x_ + i), a = ld<f32x4>(r0 + i), bq = ld<f32x4>(r1 + i);
+      const f32x4 x = ldx4<f32x4>(x_ + i), a = ld<f32x4>(r0 + i), bq = ld<f32x4>(r1 + i);
       f32x4 c = {0.f, 0.f, 0.f, 0.f};
       if constexpr (NUM == 3) c = ld<f32x4>(r2 + i);
       f32x4 ov;
@@ -418,7 +430,7 @@ __global__ __launch_bounds__(kThreads) void clone_scaled_kernel(
       }
       st<f32x4>(o + i, ov);
     } else {
-      const float x = x_[i];
+      const float x = ldx(x_ + i);
       float s = te_sd(s0 ? r0[i] * f0 : r0[i], x) + te_sd(s1 ? r1[i] * f1 : r1[i], x);
       if constexpr (NUM == 3) s = s + te_sd(s2 ? r2[i] * f2 : r2[i], x);
       o[i] = x * s;
@@ -429,8 +441,9 @@ __global__ __launch_bounds__(kThreads) void clone_scaled_kernel(
 // ------------------------------------------------------------------------------------------------
 // IndexSelect.relprop (modules/layers_ours.py:129-147), dim = 1, single index.
 // ------------------------------------------------------------------------------------------------
+template <typename TX>
 __global__ __launch_bounds__(kThreads) void index_select_kernel(
-    const float* __restrict__ R, const float* __restrict__ X, float* __restrict__ out,
+    const float* __restrict__ R, const TX* __restrict__ X, float* __restrict__ out,
     int64_t B, int64_t N, int64_t C, int64_t index) {
   const int64_t total = B * N * C;
   const int64_t stride = (int64_t)gridDim.x * kThreads;
@@ -440,7 +453,7 @@ __global__ __launch_bounds__(kThreads) void index_select_kernel(
     const int64_t b = i / (C * N);
     float v = 0.0f;
     if (nrow == index) {
-      const float x = X[i];
+      const float x = ldx(X + i);
       v = x * te_sd(R[b * C + c], x);
     }
     out[i] = v;
@@ -452,13 +465,13 @@ __global__ __launch_bounds__(kThreads) void index_select_kernel(
 // (ViT_LRP.py:359-366; ExplanationGenerator.py:49-56).  torch's mean sums heads in order then divides.
 // Per-(b,h) bases are (b*H+h)*N*N elements: only dword-aligned when N*N is odd, hence f32x4_u.
 // ------------------------------------------------------------------------------------------------
-template <int VEC>
+template <int VEC, typename TG>
 __global__ __launch_bounds__(kThreads) void headmean_kernel(
-    const float* __restrict__ grad, const float* __restrict__ cam, float* __restrict__ out,
+    const TG* __restrict__ grad, const float* __restrict__ cam, float* __restrict__ out,
     int64_t H, int64_t NN) {
   const int64_t b = blockIdx.y;
   const float fH = (float)H;
-  const float* g = grad + b * H * NN;
+  const TG* g = grad + b * H * NN;
   const float* c = cam + b * H * NN;
   float* o = out + b * NN;
   const int64_t stride = (int64_t)gridDim.x * kThreads * VEC;
@@ -472,7 +485,7 @@ __global__ __launch_bounds__(kThreads) void headmean_kernel(
         f32x4_u gv[4], cv[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          gv[u] = ld<f32x4_u>(g + (h + u) * NN + e);
+          gv[u] = ldx4<f32x4_u>(g + (h + u) * NN + e);
           cv[u] = ld<f32x4_u>(c + (h + u) * NN + e);
         }
 #pragma unroll
@@ -481,7 +494,7 @@ __global__ __launch_bounds__(kThreads) void headmean_kernel(
           for (int k = 0; k < 4; ++k) acc[k] = acc[k] + fmaxf(gv[u][k] * cv[u][k], 0.0f);
       }
       for (; h < H; ++h) {
-        const f32x4_u gv = ld<f32x4_u>(g + h * NN + e), cv = ld<f32x4_u>(c + h * NN + e);
+        const f32x4_u gv = ldx4<f32x4_u>(g + h * NN + e), cv = ld<f32x4_u>(c + h * NN + e);
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc[k] = acc[k] + fmaxf(gv[k] * cv[k], 0.0f);
       }
@@ -492,7 +505,7 @@ __global__ __launch_bounds__(kThreads) void headmean_kernel(
       const int64_t lim = min(NN, e + VEC);
       for (int64_t ee = e; ee < lim; ++ee) {
         float acc = 0.0f;
-        for (int64_t h = 0; h < H; ++h) acc = acc + fmaxf(g[h * NN + ee] * c[h * NN + ee], 0.0f);
+        for (int64_t h = 0; h < H; ++h) acc = acc + fmaxf(ldx(g + h * NN + ee) * c[h * NN + ee], 0.0f);
         o[ee] = acc / fH;
       }
     }
@@ -503,12 +516,12 @@ __global__ __launch_bounds__(kThreads) void headmean_kernel(
 // (ceil(NN / 1024), B): every block does the same amount of work and the dispatcher back-fills finished blocks
 // (the grid-stride form above gives 6 of 32 blocks per sample a second trip at N = 197).  Heads are still added in
 // index order.
-template <int HMAX>
+template <int HMAX, typename TG>
 __global__ __launch_bounds__(kThreads) void headmean_flat_kernel(
-    const float* __restrict__ grad, const float* __restrict__ cam, float* __restrict__ out, int H, int64_t NN) {
+    const TG* __restrict__ grad, const float* __restrict__ cam, float* __restrict__ out, int H, int64_t NN) {
   const int64_t b = blockIdx.y;
   const float fH = (float)H;
-  const float* g = grad + b * H * NN;
+  const TG* g = grad + b * H * NN;
   const float* c = cam + b * H * NN;
   float* o = out + b * NN;
   const int64_t e = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 4;
@@ -518,7 +531,8 @@ __global__ __launch_bounds__(kThreads) void headmean_flat_kernel(
 #pragma unroll
     for (int h = 0; h < HMAX; ++h)
       if (h < H) {
-        gv[h] = __builtin_nontemporal_load(reinterpret_cast<const f32x4_u*>(g + h * NN + e));
+        if constexpr (sizeof(TG) == 4) gv[h] = __builtin_nontemporal_load(reinterpret_cast<const f32x4_u*>(g + h * NN + e));
+        else gv[h] = ldx4<f32x4_u>(g + h * NN + e);
         cv[h] = __builtin_nontemporal_load(reinterpret_cast<const f32x4_u*>(c + h * NN + e));
       }
     f32x4_u acc = {0.f, 0.f, 0.f, 0.f};
@@ -534,7 +548,7 @@ __global__ __launch_bounds__(kThreads) void headmean_flat_kernel(
   } else {
     for (int64_t ee = e; ee < NN; ++ee) {
       float acc = 0.0f;
-      for (int h = 0; h < H; ++h) acc = acc + fmaxf(g[h * NN + ee] * c[h * NN + ee], 0.0f);
+      for (int h = 0; h < H; ++h) acc = acc + fmaxf(ldx(g + h * NN + ee) * c[h * NN + ee], 0.0f);
       o[ee] = acc / fH;
     }
   }
@@ -558,15 +572,16 @@ extern "C" size_t te_add_relprop_workspace_bytes(int64_t B, int64_t n) {
   return te_align_up((size_t)B * 64 * 3 * sizeof(double), 256);
 }
 
-extern "C" int te_add_relprop_f32(const float* R, const float* X0, const float* X1, float* out0,
-                                  float* out1, int64_t B, int64_t n, int64_t x1_batch_stride,
-                                  int variant, void* ws, size_t ws_bytes, te_stream_t stream_) {
+namespace {
+template <typename TX>
+int add_relprop(const float* R, const TX* X0, const TX* X1, float* out0, float* out1, int64_t B, int64_t n,
+                int64_t x1_batch_stride, int variant, void* ws, size_t ws_bytes, te_stream_t stream_) {
   if (!R || !X0 || !X1 || !out0 || !out1 || B <= 0 || n <= 0) return TE_ERR_INVALID_ARG;
   if (x1_batch_stride != 0 && x1_batch_stride != n) return TE_ERR_INVALID_ARG;
   const int var = variant & 0xff;
   if (var != TE_VARIANT_OURS && var != TE_VARIANT_LRP) return TE_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
-  const bool vec = (n % 4 == 0) && te_aligned16(R) && te_aligned16(X0) && te_aligned16(X1) &&
+  const bool vec = (n % 4 == 0) && te_aligned16(R) && vec_aligned(X0) && vec_aligned(X1) &&
                    te_aligned16(out0) && te_aligned16(out1);
   const int bps = pick_blocks_per_sample(B, n);
   int64_t chunk = te_ceil_div(n, bps);
@@ -596,20 +611,35 @@ extern "C" int te_add_relprop_f32(const float* R, const float* X0, const float* 
   return TE_OK;
 }
 
+}  // namespace
+
+extern "C" int te_add_relprop_f32(const float* R, const float* X0, const float* X1, float* out0,
+                                  float* out1, int64_t B, int64_t n, int64_t x1_batch_stride,
+                                  int variant, void* ws, size_t ws_bytes, te_stream_t stream_) {
+  return add_relprop(R, X0, X1, out0, out1, B, n, x1_batch_stride, variant, ws, ws_bytes, stream_);
+}
+
+extern "C" int te_add_relprop_bf16(const float* R, const te_bf16_t* X0, const te_bf16_t* X1, float* out0, float* out1,
+                                   int64_t B, int64_t n, int64_t x1_batch_stride, int variant, void* ws,
+                                   size_t ws_bytes, te_stream_t stream_) {
+  return add_relprop(R, X0, X1, out0, out1, B, n, x1_batch_stride, variant, ws, ws_bytes, stream_);
+}
+
 // ---- Add with the per-sample rescale deferred to the consumers ---------------------------------------
 extern "C" size_t te_add_relprop_deferred_workspace_bytes(int64_t B, int64_t n) {
   return te_add_relprop_workspace_bytes(B, n);
 }
 
-extern "C" int te_add_relprop_deferred_f32(const float* R, const float* X0, const float* X1, float* a, float* b,
-                                           float* fac, int64_t B, int64_t n, int64_t x1_batch_stride, void* ws,
-                                           size_t ws_bytes, te_stream_t stream_) {
+namespace {
+template <typename TX>
+int add_relprop_deferred(const float* R, const TX* X0, const TX* X1, float* a, float* b, float* fac, int64_t B,
+                         int64_t n, int64_t x1_batch_stride, void* ws, size_t ws_bytes, te_stream_t stream_) {
   if (!R || !X0 || !X1 || !a || !b || !fac || B <= 0 || n <= 0) return TE_ERR_INVALID_ARG;
   if (x1_batch_stride != 0 && x1_batch_stride != n) return TE_ERR_INVALID_ARG;
   if (B > 65535) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_add_relprop_workspace_bytes(B, n)) return TE_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
-  const bool vec = (n % 4 == 0) && te_aligned16(R) && te_aligned16(X0) && te_aligned16(X1) && te_aligned16(a) &&
+  const bool vec = (n % 4 == 0) && te_aligned16(R) && vec_aligned(X0) && vec_aligned(X1) && te_aligned16(a) &&
                    te_aligned16(b);
   const int bps = pick_blocks_per_sample(B, n);      // the same chunking (and fold order) as te_add_relprop_f32
   int64_t chunk = te_ceil_div(n, bps);
@@ -621,6 +651,20 @@ extern "C" int te_add_relprop_deferred_f32(const float* R, const float* X0, cons
   add_factors_kernel<<<dim3((unsigned)B), dim3(64), 0, stream>>>(partial, fac, bps);
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
+}
+
+}  // namespace
+
+extern "C" int te_add_relprop_deferred_f32(const float* R, const float* X0, const float* X1, float* a, float* b,
+                                           float* fac, int64_t B, int64_t n, int64_t x1_batch_stride, void* ws,
+                                           size_t ws_bytes, te_stream_t stream_) {
+  return add_relprop_deferred(R, X0, X1, a, b, fac, B, n, x1_batch_stride, ws, ws_bytes, stream_);
+}
+
+extern "C" int te_add_relprop_deferred_bf16(const float* R, const te_bf16_t* X0, const te_bf16_t* X1, float* a, float* b,
+                                            float* fac, int64_t B, int64_t n, int64_t x1_batch_stride, void* ws,
+                                            size_t ws_bytes, te_stream_t stream_) {
+  return add_relprop_deferred(R, X0, X1, a, b, fac, B, n, x1_batch_stride, ws, ws_bytes, stream_);
 }
 
 // ---- broadcast-mask Add ---------------------------------------------------------------------------
@@ -695,11 +739,13 @@ extern "C" int te_add_bcast_relprop_deferred_f32(const float* R, const float* X0
 }
 
 // ---- Clone ------------------------------------------------------------------------------------------
-extern "C" int te_clone_relprop_f32(const float* R0, const float* R1, const float* R2, const float* X,
-                                    float* out, int64_t n, te_stream_t stream_) {
+namespace {
+template <typename TX>
+int clone_relprop(const float* R0, const float* R1, const float* R2, const TX* X, float* out, int64_t n,
+                  te_stream_t stream_) {
   if (!R0 || !R1 || !X || !out || n <= 0) return TE_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
-  const bool vec = (n % 4 == 0) && te_aligned16(R0) && te_aligned16(R1) && te_aligned16(X) &&
+  const bool vec = (n % 4 == 0) && te_aligned16(R0) && te_aligned16(R1) && vec_aligned(X) &&
                    te_aligned16(out) && (!R2 || te_aligned16(R2));
   const int vecw = vec ? 4 : 1;
   // one float4 per thread (every block the same work, back-filled by the dispatcher) up to 64 K blocks; the
@@ -719,14 +765,14 @@ extern "C" int te_clone_relprop_f32(const float* R0, const float* R1, const floa
   return TE_OK;
 }
 
-extern "C" int te_clone_relprop_scaled_f32(const float* R0, const float* s0, int64_t s0_stride, const float* R1,
-                                           const float* s1, int64_t s1_stride, const float* R2, const float* s2,
-                                           int64_t s2_stride, const float* X, float* out, int64_t B, int64_t n,
-                                           te_stream_t stream_) {
+template <typename TX>
+int clone_relprop_scaled(const float* R0, const float* s0, int64_t s0_stride, const float* R1, const float* s1,
+                         int64_t s1_stride, const float* R2, const float* s2, int64_t s2_stride, const TX* X, float* out,
+                         int64_t B, int64_t n, te_stream_t stream_) {
   if (!R0 || !R1 || !X || !out || B <= 0 || n <= 0) return TE_ERR_INVALID_ARG;
   if (B > 65535) return TE_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
-  const bool vec = (n % 4 == 0) && te_aligned16(R0) && te_aligned16(R1) && te_aligned16(X) && te_aligned16(out) &&
+  const bool vec = (n % 4 == 0) && te_aligned16(R0) && te_aligned16(R1) && vec_aligned(X) && te_aligned16(out) &&
                    (!R2 || te_aligned16(R2));
   const int vecw = vec ? 4 : 1;
   int64_t bx = te_ceil_div(n, (int64_t)kThreads * vecw);       // one float4 per thread
@@ -748,9 +794,37 @@ extern "C" int te_clone_relprop_scaled_f32(const float* R0, const float* s0, int
   return TE_OK;
 }
 
+}  // namespace
+
+extern "C" int te_clone_relprop_f32(const float* R0, const float* R1, const float* R2, const float* X,
+                                    float* out, int64_t n, te_stream_t stream_) {
+  return clone_relprop(R0, R1, R2, X, out, n, stream_);
+}
+
+extern "C" int te_clone_relprop_bf16(const float* R0, const float* R1, const float* R2, const te_bf16_t* X, float* out,
+                                     int64_t n, te_stream_t stream_) {
+  return clone_relprop(R0, R1, R2, X, out, n, stream_);
+}
+
+extern "C" int te_clone_relprop_scaled_f32(const float* R0, const float* s0, int64_t s0_stride, const float* R1,
+                                           const float* s1, int64_t s1_stride, const float* R2, const float* s2,
+                                           int64_t s2_stride, const float* X, float* out, int64_t B, int64_t n,
+                                           te_stream_t stream_) {
+  return clone_relprop_scaled(R0, s0, s0_stride, R1, s1, s1_stride, R2, s2, s2_stride, X, out, B, n, stream_);
+}
+
+extern "C" int te_clone_relprop_scaled_bf16(const float* R0, const float* s0, int64_t s0_stride, const float* R1,
+                                            const float* s1, int64_t s1_stride, const float* R2, const float* s2,
+                                            int64_t s2_stride, const te_bf16_t* X, float* out, int64_t B, int64_t n,
+                                            te_stream_t stream_) {
+  return clone_relprop_scaled(R0, s0, s0_stride, R1, s1, s1_stride, R2, s2, s2_stride, X, out, B, n, stream_);
+}
+
 // ---- IndexSelect ------------------------------------------------------------------------------------
-extern "C" int te_index_select_relprop_f32(const float* R, const float* X, float* out, int64_t B,
-                                           int64_t N, int64_t C, int64_t index, te_stream_t stream_) {
+namespace {
+template <typename TX>
+int index_select_relprop(const float* R, const TX* X, float* out, int64_t B, int64_t N, int64_t C, int64_t index,
+                         te_stream_t stream_) {
   if (!R || !X || !out || B <= 0 || N <= 0 || C <= 0 || index < 0 || index >= N)
     return TE_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
@@ -761,9 +835,23 @@ extern "C" int te_index_select_relprop_f32(const float* R, const float* X, float
   return TE_OK;
 }
 
+}  // namespace
+
+extern "C" int te_index_select_relprop_f32(const float* R, const float* X, float* out, int64_t B,
+                                           int64_t N, int64_t C, int64_t index, te_stream_t stream_) {
+  return index_select_relprop(R, X, out, B, N, C, index, stream_);
+}
+
+extern "C" int te_index_select_relprop_bf16(const float* R, const te_bf16_t* X, float* out, int64_t B, int64_t N,
+                                            int64_t C, int64_t index, te_stream_t stream_) {
+  return index_select_relprop(R, X, out, B, N, C, index, stream_);
+}
+
 // ---- gradient x relevance head mean ----------------------------------------------------------------
-extern "C" int te_gradcam_headmean_f32(const float* grad, const float* cam, float* out, int64_t B,
-                                       int64_t H, int64_t N, te_stream_t stream_) {
+namespace {
+template <typename TG>
+int gradcam_headmean(const TG* grad, const float* cam, float* out, int64_t B, int64_t H, int64_t N,
+                     te_stream_t stream_) {
   if (!grad || !cam || !out || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t NN = N * N;
@@ -790,4 +878,15 @@ extern "C" int te_gradcam_headmean_f32(const float* grad, const float* cam, floa
   headmean_kernel<4><<<dim3((unsigned)bx, (unsigned)B), dim3(kThreads), 0, stream>>>(grad, cam, out, H, NN);
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
+}
+}  // namespace
+
+extern "C" int te_gradcam_headmean_f32(const float* grad, const float* cam, float* out, int64_t B,
+                                       int64_t H, int64_t N, te_stream_t stream_) {
+  return gradcam_headmean(grad, cam, out, B, H, N, stream_);
+}
+
+extern "C" int te_gradcam_headmean_bf16(const te_bf16_t* grad, const float* cam, float* out, int64_t B, int64_t H,
+                                        int64_t N, te_stream_t stream_) {
+  return gradcam_headmean(grad, cam, out, B, H, N, stream_);
 }

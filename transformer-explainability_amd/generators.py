@@ -24,7 +24,9 @@ def _one_hot(output: torch.Tensor, index) -> torch.Tensor:
         idx = idx.reshape(-1).long()
         if idx.numel() == 1 and B > 1:
             idx = idx.expand(B)
-    one_hot = torch.zeros((B, K), dtype=output.dtype, device=output.device)
+    # a bf16 model's relevance is fp32 from the seed on (ops: bf16 operands, fp32 relevance)
+    dtype = torch.float32 if output.dtype == torch.bfloat16 else output.dtype
+    one_hot = torch.zeros((B, K), dtype=dtype, device=output.device)
     one_hot.scatter_(1, idx.view(B, 1), 1.0)
     return one_hot
 

@@ -58,12 +58,43 @@ def _variant(v) -> int:
     return code | (TE_IMPL_SIMPLE if FORCE_SIMPLE else 0)
 
 
+# The dtypes the kernels take: fp32 everywhere; bf16 OPERANDS (activations, weights, attention gradients of a bf16 model)
+# on the rules of a ViT / DeiT explanation (variant ours, alpha = 1), with fp32 relevance (the *_bf16 paths below).
+DTYPES_MSG = ("relprop kernels take float32 tensors, or bfloat16 operands with float32 relevance on the ViT rules of "
+              "variant 'ours' with alpha = 1")
+
+
 def _prep(t: Tensor) -> Tensor:
     if t.dtype != torch.float32:
-        raise _lib.TeError(f"relprop kernels are fp32-only, got {t.dtype}")
+        raise _lib.TeError(f"{DTYPES_MSG}; got {t.dtype} here")
     if not t.is_cuda:
         raise _lib.TeError("relprop kernels need tensors on the MI355X (got a CPU tensor); there is no CPU fallback")
     return t
+
+
+def _is_bf16(t) -> bool:
+    return torch.is_tensor(t) and t.dtype == torch.bfloat16
+
+
+def _prep_bf16(t: Tensor) -> Tensor:
+    if t.dtype != torch.bfloat16:
+        raise _lib.TeError(f"{DTYPES_MSG}; this bf16 rule got a {t.dtype} operand")
+    if not t.is_cuda:
+        raise _lib.TeError("relprop kernels need tensors on the MI355X (got a CPU tensor); there is no CPU fallback")
+    return t
+
+
+def _c16(t: Tensor) -> Tensor:
+    t = _prep_bf16(t)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _bf16_rule(variant, alpha=1.0, what="rule"):
+    """The bf16 paths implement variant ours with alpha = 1 (what LRP.generate_LRP passes); anything else is refused."""
+    var = _variant(variant) & 0xff
+    if var != TE_VARIANT_OURS or alpha != 1:
+        raise _lib.TeError(f"{what} with bf16 operands: only variant 'ours' with alpha = 1 is implemented "
+                           f"(got variant {variant!r}, alpha {alpha}); run the model in float32 for other rules")
 
 
 def _c(t: Tensor) -> Tensor:
@@ -88,7 +119,7 @@ class _on_device:
 
     def __init__(self, t: Tensor):
         global _checked_device
-        _prep(t)
+        _prep_bf16(t) if _is_bf16(t) else _prep(t)
         if not _checked_device:
             _lib.require_device()
             _checked_device = True
@@ -400,7 +431,10 @@ def linear_relprop(R: Tensor, X: Tensor, W: Tensor, alpha: float = 1.0, variant=
     """Linear.relprop: R [..., out], X [..., in], W [out, in] -> [..., in].
     Y [..., out] (optional) is the forward output F.linear(X, W, bias) the rule module cached as self.Y; with it
     (variant ours, alpha = 1) the Z-pass needs one product instead of two.  cache: a dict owned by the layer, where the
-    bf16 operand planes of W are kept between calls (x6_weight_planes)."""
+    bf16 operand planes of W are kept between calls (x6_weight_planes).
+    bf16 X / W (a bf16 model): linear_relprop_bf16."""
+    if _is_bf16(X) or _is_bf16(W):
+        return linear_relprop_bf16(R, X, W, alpha=alpha, variant=variant, cache=cache)
     out_f, in_f = W.shape
     lead = X.shape[:-1]
     R, r_scale = _split_deferred(R)
@@ -559,7 +593,9 @@ def matmul_relprop_av(R: Tensor, attn: Tensor, v: Tensor, out_scale: float = 1.0
     """AV rule.  R, v: [B,H,N,D] (any strides with contiguous D); attn [B,H,N,N].
     Returns (cam_attn [B,H,N,N], cam_v [B,H,N,D]); cam_v is written into `cam_v_out` if given (a
     [B,H,N,D] view, e.g. a slice of the 'b n (qkv h d)' relevance buffer).  z (optional) = attn @ v as the
-    forward pass computed it (self.Y of the product module)."""
+    forward pass computed it (self.Y of the product module).  bf16 attn / v: matmul_relprop_av_bf16."""
+    if _is_bf16(attn) or _is_bf16(v):
+        return matmul_relprop_av_bf16(R, attn, v, out_scale, cam_v_out, variant, z)
     B, H, N, D = v.shape
     zc = None
     z_str = (H * N * D, N * D, D)
@@ -596,7 +632,9 @@ def matmul_relprop_qk(R: Tensor, q: Tensor, k: Tensor, out_scale: float = 1.0,
                       cam_q_out: Optional[Tensor] = None, cam_k_out: Optional[Tensor] = None,
                       variant="ours", z: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """QK rule.  R [B,H,N,N]; q, k [B,H,N,D] -> (cam_q, cam_k) [B,H,N,D].  z (optional) = the UNSCALED q @ k^T as
-    the forward pass computed it (self.Y of the product module)."""
+    the forward pass computed it (self.Y of the product module).  bf16 q / k: matmul_relprop_qk_bf16."""
+    if _is_bf16(q) or _is_bf16(k):
+        return matmul_relprop_qk_bf16(R, q, k, out_scale, cam_q_out, cam_k_out, variant, z)
     B, H, N, D = q.shape
     zc = _cached_z(z, (B, H, N, N))
     q, q_sb, q_sh, q_sn = _bhnd(q)
@@ -897,7 +935,9 @@ def add_relprop(R: Tensor, X0: Tensor, X1: Tensor, variant="ours", deferred: boo
     """Add.relprop with per-sample sums.  dim 0 is the batch.  X1 has X0's shape, or batch 1 (shared by
     all samples), or is the BERT broadcast mask [B,1,1,N] against X0 [B,H,N,N].
     deferred=True (variant ours, same-shape operands): one streaming pass; returns two ``Deferred`` (unscaled tensor +
-    per-sample factor) for clone_relprop / linear_relprop to consume."""
+    per-sample factor) for clone_relprop / linear_relprop to consume.  bf16 X0 / X1: add_relprop_bf16."""
+    if _is_bf16(X0) or _is_bf16(X1):
+        return add_relprop_bf16(R, X0, X1, variant, deferred)
     B = X0.shape[0]
     R, X0 = _c(R), _c(X0)
     n = X0[0].numel()
@@ -949,56 +989,63 @@ def add_relprop(R: Tensor, X0: Tensor, X1: Tensor, variant="ours", deferred: boo
 
 # ---------------------------------------------------------------------------------------- a6
 def clone_relprop(Rs: Sequence, X: Tensor) -> Tensor:
-    """Clone.relprop; relevance operands may be ``Deferred`` (their per-sample factor is applied inside the kernel)."""
+    """Clone.relprop; relevance operands may be ``Deferred`` (their per-sample factor is applied inside the kernel).
+    bf16 X: te_clone_relprop(_scaled)_bf16, fp32 relevance and output."""
     if len(Rs) not in (2, 3):
         raise _lib.TeError(f"Clone.relprop supports 2 or 3 aliases, got {len(Rs)}")
-    X = _c(X)
+    bf = _is_bf16(X)
+    X = _c16(X) if bf else _c(X)
+    sfx = "bf16" if bf else "f32"
     pairs = [_split_deferred(r) for r in Rs]
     Rs = [_c(r) for r, _ in pairs]
     scales = [sc for _, sc in pairs]
     for r in Rs:
         if r.numel() != X.numel():
             raise _lib.TeError("Clone.relprop: relevance / input size mismatch")
-    out = torch.empty_like(X)
-    nb = 4.0 * X.numel() * (len(Rs) + 2)
+    out = torch.empty(X.shape, dtype=torch.float32, device=X.device)
+    nb = 4.0 * X.numel() * (len(Rs) + 1) + X.element_size() * X.numel()
     if any(sc is not None for sc in scales):
         B = X.shape[0]
         sp = [(None, 0) if sc is None else (sc.data_ptr(), sc.stride(0)) for sc in scales] + [(None, 0)]
         with _on_device(X) as lib, _timed("clone", 0.0, nb):
-            _lib.check(lib.te_clone_relprop_scaled_f32(_ptr(Rs[0]), sp[0][0], sp[0][1], _ptr(Rs[1]), sp[1][0], sp[1][1],
-                                                       _ptr(Rs[2]) if len(Rs) == 3 else None, sp[2][0], sp[2][1],
-                                                       _ptr(X), _ptr(out), B, X.numel() // B, _stream(X)),
-                       "te_clone_relprop_scaled_f32")
+            _lib.check(getattr(lib, "te_clone_relprop_scaled_" + sfx)(
+                _ptr(Rs[0]), sp[0][0], sp[0][1], _ptr(Rs[1]), sp[1][0], sp[1][1], _ptr(Rs[2]) if len(Rs) == 3 else None,
+                sp[2][0], sp[2][1], _ptr(X), _ptr(out), B, X.numel() // B, _stream(X)), "te_clone_relprop_scaled_" + sfx)
         return out
     with _on_device(X) as lib, _timed("clone", 0.0, nb):
-        _lib.check(lib.te_clone_relprop_f32(_ptr(Rs[0]), _ptr(Rs[1]), _ptr(Rs[2]) if len(Rs) == 3 else None, _ptr(X),
-                                            _ptr(out), X.numel(), _stream(X)), "te_clone_relprop_f32")
+        _lib.check(getattr(lib, "te_clone_relprop_" + sfx)(_ptr(Rs[0]), _ptr(Rs[1]), _ptr(Rs[2]) if len(Rs) == 3 else None,
+                                                           _ptr(X), _ptr(out), X.numel(), _stream(X)),
+                   "te_clone_relprop_" + sfx)
     return out
 
 
 # ---------------------------------------------------------------------------------------- a7
 def index_select_relprop(R: Tensor, X: Tensor, index: int) -> Tensor:
-    """IndexSelect.relprop for dim=1: R [B,1,C] or [B,C], X [B,N,C] -> [B,N,C]."""
-    X = _c(X)
+    """IndexSelect.relprop for dim=1: R [B,1,C] or [B,C], X [B,N,C] -> [B,N,C] (fp32; X may be bf16)."""
+    bf = _is_bf16(X)
+    X = _c16(X) if bf else _c(X)
     B, N, C = X.shape
     R = _c(R).reshape(B, C)
-    out = torch.empty_like(X)
+    out = torch.empty(X.shape, dtype=torch.float32, device=X.device)
+    sfx = "bf16" if bf else "f32"
     with _on_device(X) as lib:
-        _lib.check(lib.te_index_select_relprop_f32(_ptr(R), _ptr(X), _ptr(out), B, N, C, int(index), _stream(X)),
-                   "te_index_select_relprop_f32")
+        _lib.check(getattr(lib, "te_index_select_relprop_" + sfx)(_ptr(R), _ptr(X), _ptr(out), B, N, C, int(index),
+                                                                   _stream(X)), "te_index_select_relprop_" + sfx)
     return out
 
 
 # ---------------------------------------------------------------------------------------- a10
 def gradcam_headmean(grad: Tensor, cam: Tensor, out: Optional[Tensor] = None) -> Tensor:
-    """grad, cam [B,H,N,N] -> [B,N,N] = mean_h max(grad*cam, 0), per sample."""
-    grad, cam = _c(grad), _c(cam)
+    """grad, cam [B,H,N,N] -> [B,N,N] = mean_h max(grad*cam, 0), per sample (grad may be bf16; cam and out fp32)."""
+    bf = _is_bf16(grad)
+    grad, cam = (_c16(grad) if bf else _c(grad)), _c(cam)
     B, H, N, _ = cam.shape
     if out is None:
         out = torch.empty((B, N, N), dtype=torch.float32, device=cam.device)
-    with _on_device(cam) as lib, _timed("headmean", 0.0, 4.0 * B * (2 * H + 1) * N * N):
-        _lib.check(lib.te_gradcam_headmean_f32(_ptr(grad), _ptr(cam), _ptr(out), B, H, N, _stream(cam)),
-                   "te_gradcam_headmean_f32")
+    sfx = "bf16" if bf else "f32"
+    with _on_device(cam) as lib, _timed("headmean", 0.0, (grad.element_size() + 4.0) * B * H * N * N + 4.0 * B * N * N):
+        _lib.check(getattr(lib, "te_gradcam_headmean_" + sfx)(_ptr(grad), _ptr(cam), _ptr(out), B, H, N, _stream(cam)),
+                   "te_gradcam_headmean_" + sfx)
     return out
 
 
@@ -1104,3 +1151,183 @@ def perturb(vis: Tensor, data: Tensor, ks: Sequence[int], mean: Optional[Sequenc
         _lib.check(lib.te_perturb_f32(_ptr(vis), _ptr(data), _ptr(out), B, C, HW, k_arr, S, m_arr, s_arr, _ptr(ws),
                                       ws.numel(), _stream(data)), "te_perturb_f32")
     return out
+
+
+# ---------------------------------------------------------------------------------------- bf16 operands
+# A bf16 model's rules: the reference's algorithm evaluated in fp32 on the model's own bf16 tensors (read exactly: bf16 ->
+# fp32 is exact).  Relevance, safe_divide, per-sample sums and the rollout stay fp32; Linear's Z is X+ W+^T + X- W-^T from
+# the bf16 X and W (never from the cached bf16 output), the attention rules take Z from the cached bf16 product.  The GEMM-
+# shaped rules run on bf16 MFMAs (csrc/te_bf16.hip); shapes those kernels do not tile take the FP32-UPCAST route: exact fp32
+# copies of the bf16 operands on the fp32 kernels, on the GPU (linear_bf16_route / attention_bf16_route say which).
+def linear_bf16_route(T: int, in_f: int, out_f: int) -> str:
+    """'bf16' (te_linear_relprop_bf16) or 'fp32-upcast' (te_linear_relprop_f32 on fp32 copies of X and W)."""
+    return "bf16" if _lib.load().te_linear_relprop_bf16_supported(int(T), int(in_f), int(out_f)) else "fp32-upcast"
+
+
+def attention_bf16_route(N: int, D: int) -> str:
+    """'bf16' (te_matmul_relprop_av_bf16 / _qk_bf16: head dim 64) or 'fp32-upcast' (the fp32 attention kernels)."""
+    return "bf16" if _lib.load().te_matmul_relprop_bf16_supported(int(N), int(D)) else "fp32-upcast"
+
+
+def bf16_weight_planes(W: Tensor, cache: Optional[dict] = None) -> Tensor:
+    """W+, W- and their transposes for te_linear_relprop_bf16, built once per weight version (cached like
+    x6_weight_planes: keyed on the weight's identity, dropped by x6_invalidate / load_state_dict / .to())."""
+    out_f, in_f = W.shape
+    key = _weight_key(W)
+    if cache is not None:
+        hit = cache.get("bf16_planes")
+        if hit is not None and hit[0] == key:
+            return hit[1]
+    Wc = _c16(W.detach())
+    with _on_device(Wc) as lib:
+        planes = _ws(lib.te_linear_bf16_weight_planes_bytes(in_f, out_f), Wc)
+        _lib.check(lib.te_linear_bf16_prepare_weights(_ptr(Wc), in_f, out_f, _ptr(planes), planes.numel(), _stream(Wc)),
+                   "te_linear_bf16_prepare_weights")
+    if cache is not None:
+        cache["bf16_planes"] = (key, planes)
+    return planes
+
+
+def _rows(X: Tensor, K: int) -> Tuple[Tensor, int]:
+    """[..., K] bf16 activation -> ([T, K] view, row stride), copying only if its rows are not uniformly strided."""
+    X2 = _prep_bf16(X).reshape(-1, K)
+    if X2.stride(1) != 1 or (X2.shape[0] > 1 and X2.stride(0) < K):
+        X2 = X2.contiguous()
+    return X2, (X2.stride(0) if X2.shape[0] > 1 else K)
+
+
+def linear_relprop_bf16(R, X: Tensor, W: Tensor, alpha: float = 1.0, variant="ours",
+                        cache: Optional[dict] = None) -> Tensor:
+    """Linear.relprop of a bf16 layer: R [..., out] fp32 (or ``Deferred``), X [..., in] and W [out, in] bf16 -> fp32
+    [..., in].  X may be a strided view (Block.relprop_cls_only's cls rows are read in place)."""
+    _bf16_rule(variant, alpha, "Linear.relprop")
+    if not (_is_bf16(X) and _is_bf16(W)):
+        raise _lib.TeError(f"Linear.relprop: X ({X.dtype}) and W ({W.dtype}) must both be bf16 on the bf16 path")
+    out_f, in_f = W.shape
+    lead = X.shape[:-1]
+    R, r_scale = _split_deferred(R)
+    Rc = _c(R).reshape(-1, out_f)
+    T = Rc.shape[0]
+    if X.numel() // in_f != T:
+        raise _lib.TeError(f"Linear.relprop: R has {T} rows, X has {X.numel() // in_f}")
+    if linear_bf16_route(T, in_f, out_f) != "bf16":
+        Rd = R if r_scale is None else Deferred(R, r_scale)
+        return linear_relprop(Rd, X.float(), W.detach().float(), alpha=alpha, variant=variant)
+    X2, x_ld = _rows(X, in_f)
+    planes = bf16_weight_planes(W, cache)
+    out = torch.empty((T, in_f), dtype=torch.float32, device=X.device)
+    rs_ptr, rs_stride, rps = None, 0, 1
+    if r_scale is not None:
+        rs_ptr, rs_stride, rps = r_scale.data_ptr(), r_scale.stride(0), T // r_scale.shape[0]
+    gemm = 2.0 * T * in_f * out_f
+    with _on_device(X2) as lib, _timed("linear_bf16", 8.0 * gemm,
+                                       2.0 * T * in_f + 8.0 * in_f * out_f + 4.0 * T * out_f + 6.0 * 2 * T * out_f
+                                       + 2.0 * T * in_f + 4.0 * T * in_f):
+        ws = _ws(lib.te_linear_relprop_bf16_workspace_bytes(T, in_f, out_f), X2)
+        _lib.check(lib.te_linear_relprop_bf16(_ptr(Rc), out_f, rs_ptr, rs_stride, rps, _ptr(X2), x_ld, _ptr(planes),
+                                              _ptr(out), T, in_f, out_f, _ptr(ws), ws.numel(), _stream(X2)),
+                   "te_linear_relprop_bf16")
+    return out.reshape(*lead, in_f)
+
+
+def _bhnd16(t: Tensor) -> Tuple[Tensor, int, int, int]:
+    t = _prep_bf16(t)
+    if t.stride(-1) != 1 or min(t.stride()[:3]) < 0:
+        t = t.contiguous()
+    sb, sh, sn, _ = t.stride()
+    return t, sb, sh, sn
+
+
+def matmul_relprop_av_bf16(R: Tensor, attn: Tensor, v: Tensor, out_scale: float = 1.0,
+                           cam_v_out: Optional[Tensor] = None, variant="ours", z: Optional[Tensor] = None):
+    """AV rule with bf16 attn / v (and bf16 cached product z); R and the results fp32 (matmul_relprop_av)."""
+    _bf16_rule(variant, 1.0, "the attention AV rule")
+    B, H, N, D = v.shape
+    if attention_bf16_route(N, D) != "bf16":
+        return matmul_relprop_av(R, attn.float(), v.float(), out_scale, cam_v_out, variant,
+                                 None if z is None else z.detach().float())
+    zc, z_str = None, (0, 0, 0)
+    if z is not None and USE_FORWARD_PRODUCTS and tuple(z.shape) == (B, H, N, D):
+        zc, zsb, zsh, zsn = _bhnd16(z.detach())
+        z_str = (zsb, zsh, zsn)
+    R, r_sb, r_sh, r_sn = _bhnd(R)
+    v, v_sb, v_sh, v_sn = _bhnd16(v)
+    attn = _c16(attn)
+    cam_attn = torch.empty((B, H, N, N), dtype=torch.float32, device=attn.device)
+    cam_v = cam_v_out if cam_v_out is not None else torch.empty((B, H, N, D), dtype=torch.float32, device=attn.device)
+    if cam_v.stride(-1) != 1 or cam_v.dtype != torch.float32:
+        raise _lib.TeError("cam_v_out must be fp32 with a contiguous last dim")
+    cv_sb, cv_sh, cv_sn, _ = cam_v.stride()
+    with _on_device(attn) as lib, _timed("attention_av_rule_bf16", 12.0 * B * H * N * N * D,
+                                         B * H * (6.0 * N * N + 16.0 * N * D)):
+        ws = _ws(lib.te_matmul_relprop_av_bf16_workspace_bytes(B, H, N, D), attn)
+        _lib.check(lib.te_matmul_relprop_av_bf16(_ptr(R), r_sb, r_sh, r_sn, _ptr(attn), _ptr(v), v_sb, v_sh, v_sn,
+                                                 _ptr(zc), *z_str, _ptr(cam_attn), _ptr(cam_v), cv_sb, cv_sh, cv_sn,
+                                                 B, H, N, D, float(out_scale), _variant(variant), _ptr(ws), ws.numel(),
+                                                 _stream(attn)), "te_matmul_relprop_av_bf16")
+    return cam_attn, cam_v
+
+
+def matmul_relprop_qk_bf16(R, q: Tensor, k: Tensor, out_scale: float = 1.0, cam_q_out: Optional[Tensor] = None,
+                           cam_k_out: Optional[Tensor] = None, variant="ours", z: Optional[Tensor] = None):
+    """QK rule with bf16 q / k (and bf16 cached unscaled product z); R (fp32 or ``Deferred``) and the results fp32."""
+    _bf16_rule(variant, 1.0, "the attention QK rule")
+    B, H, N, D = q.shape
+    if attention_bf16_route(N, D) != "bf16":
+        return matmul_relprop_qk(R, q.float(), k.float(), out_scale, cam_q_out, cam_k_out, variant,
+                                 None if z is None else z.detach().float())
+    zc = None
+    if z is not None and USE_FORWARD_PRODUCTS and tuple(z.shape) == (B, H, N, N):
+        zc = _c16(z.detach())
+    q, q_sb, q_sh, q_sn = _bhnd16(q)
+    k, k_sb, k_sh, k_sn = _bhnd16(k)
+    R, r_scale = _split_deferred(R)
+    R = _c(R)
+    dev = R.device
+    cam_q = cam_q_out if cam_q_out is not None else torch.empty((B, H, N, D), dtype=torch.float32, device=dev)
+    cam_k = cam_k_out if cam_k_out is not None else torch.empty((B, H, N, D), dtype=torch.float32, device=dev)
+    if cam_q.stride(-1) != 1 or cam_k.stride(-1) != 1 or cam_q.dtype != torch.float32 or cam_k.dtype != torch.float32:
+        raise _lib.TeError("cam_q_out / cam_k_out must be fp32 with a contiguous last dim")
+    cq, ck = cam_q.stride(), cam_k.stride()
+    with _on_device(q) as lib, _timed("attention_qk_rule_bf16", 12.0 * B * H * N * N * D,
+                                      B * H * (12.0 * N * N + 12.0 * N * D)):
+        ws = _ws(lib.te_matmul_relprop_qk_bf16_workspace_bytes(B, H, N, D), q)
+        _lib.check(lib.te_matmul_relprop_qk_bf16(_ptr(R), _ptr(r_scale), 0 if r_scale is None else r_scale.stride(0),
+                                                 _ptr(q), q_sb, q_sh, q_sn, _ptr(k), k_sb, k_sh, k_sn, _ptr(zc),
+                                                 _ptr(cam_q), cq[0], cq[1], cq[2], _ptr(cam_k), ck[0], ck[1], ck[2],
+                                                 B, H, N, D, float(out_scale), _variant(variant), _ptr(ws), ws.numel(),
+                                                 _stream(q)), "te_matmul_relprop_qk_bf16")
+    return cam_q, cam_k
+
+
+def add_relprop_bf16(R: Tensor, X0: Tensor, X1: Tensor, variant="ours", deferred: bool = False):
+    """Add.relprop with bf16 operands (same shape, or X1 of batch 1); R and the results fp32 (add_relprop)."""
+    _bf16_rule(variant, 1.0, "Add.relprop")
+    X0, X1 = _c16(X0), _c16(X1)
+    R = _c(R)
+    B = X0.shape[0]
+    n = X0[0].numel()
+    if X1.shape == X0.shape:
+        x1_bs = n
+    elif X1.shape[0] == 1 and X1.shape[1:] == X0.shape[1:]:
+        x1_bs = 0
+    else:
+        raise _lib.TeError(f"Add.relprop (bf16): unsupported operand shapes {tuple(X0.shape)} + {tuple(X1.shape)}")
+    if R.numel() != X0.numel():
+        raise _lib.TeError("Add.relprop: relevance / input size mismatch")
+    out0 = torch.empty(X0.shape, dtype=torch.float32, device=X0.device)
+    out1 = torch.empty(X0.shape, dtype=torch.float32, device=X0.device)
+    x1_elems = n if x1_bs else n / B
+    if deferred:
+        fac = torch.empty((B, 2), dtype=torch.float32, device=X0.device)
+        with _on_device(X0) as lib, _timed("add_deferred_bf16", 0.0, B * (14.0 * n + 2.0 * x1_elems)):
+            ws = _ws(lib.te_add_relprop_deferred_workspace_bytes(B, n), X0)
+            _lib.check(lib.te_add_relprop_deferred_bf16(_ptr(R), _ptr(X0), _ptr(X1), _ptr(out0), _ptr(out1), _ptr(fac),
+                                                        B, n, x1_bs, _ptr(ws), ws.numel(), _stream(X0)),
+                       "te_add_relprop_deferred_bf16")
+        return Deferred(out0, fac[:, 0]), Deferred(out1, fac[:, 1])
+    with _on_device(X0) as lib, _timed("add_bf16", 0.0, B * (14.0 * n + 2.0 * x1_elems)):
+        ws = _ws(lib.te_add_relprop_workspace_bytes(B, n), X0)
+        _lib.check(lib.te_add_relprop_bf16(_ptr(R), _ptr(X0), _ptr(X1), _ptr(out0), _ptr(out1), B, n, x1_bs,
+                                           _variant(variant), _ptr(ws), ws.numel(), _stream(X0)), "te_add_relprop_bf16")
+    return out0, out1
