@@ -2,7 +2,7 @@
 """Measurement infrastructure (not product code): per-shape rate of the two Linear.relprop kernels on one MI355X,
 next to the register-only fp32-MFMA rate the same chip sustains (benchmarks/mfma_peak.hip).
 
-    [TE_LINEAR_TILE=128x128|128x64|64x64] python benchmarks/linear_bench.py [--batch 64] [--clock] [--lib ...]   (GPU box)
+    python benchmarks/linear_bench.py [--batch 64] [--clock] [--lib ...]   (GPU box)
 """
 import argparse
 import ctypes
@@ -33,7 +33,7 @@ def main():
             getattr(lib, n).restype = ctypes.c_int
             getattr(lib, n).argtypes = _lib.SIGNATURES[n][1]
     d = torch.device("cuda:0")
-    res = {"env_TE_LINEAR_TILE": os.environ.get("TE_LINEAR_TILE", "auto"), "lib": args.lib or "product"}
+    res = {"lib": args.lib or "product"}
 
     if not args.skip_peak:
         pk = ctypes.CDLL(os.path.join(ROOT, "benchmarks", "libmfma_peak.so"))

@@ -78,20 +78,6 @@ def main():
                                             x6_fp32equiv_tf=round(flops / t_gemm * 1e-6, 1),
                                             x6_bf16_tf=round(6 * flops / t_gemm * 1e-6, 1),
                                             torch_tf=round(flops / t_stock * 1e-6, 1), rel_diff=err)), flush=True)
-            if os.environ.get("TE_X6_G_PROF") == "1":      # study build: in-kernel wall-clock stamps of the last launch
-                al = lambda n: (n + 255) // 256 * 256      # noqa: E731
-                off = al(lib.te_linear_x6_planes_bytes(T, K)) + 512 * 256 * 128 * 4 + 8192
-                raw = ws[off: off + 512 * 64].view(torch.int64).view(512, 8).cpu()
-                act = raw[raw[:, 4] > 0].double()
-                t0 = act[:, 7].min()
-                m = act.mean(0) * 0.01
-                print("PROF " + json.dumps(dict(layer=name, direction=direction, wgs=int(act.shape[0]),
-                                                span_us=round(float(((act[:, 7] - t0) + act[:, 6]).max() * 0.01), 1),
-                                                loop_us=round(float(m[0]), 1), epi_us=round(float(m[1]), 1),
-                                                pub_us=round(float(m[2]), 1), wait_us=round(float(m[3]), 1),
-                                                steps=round(float(act[:, 4].mean()), 1), nepi=round(float(act[:, 5].mean()), 2),
-                                                ns_per_step=round(float(act[:, 0].sum() / act[:, 4].sum() * 10), 1),
-                                                wg_total_us=round(float(m[6]), 1), start_skew_us=round(float((act[:, 7] - t0).max() * 0.01), 1))), flush=True)
             tot["x6"] += t_gemm
             tot["x6_split"] += t_split
             tot["torch"] += t_stock

@@ -54,11 +54,6 @@ int te_version(void);
 const char* te_status_string(int status);
 /* 0 if device 0..n-1 contains a gfx950 agent usable by this library, TE_ERR_NO_DEVICE otherwise */
 int te_device_check(void);
-/* 0 for the shipped library.  Bit 0: built with -DTE_X6_STUDY (measurement builds: TE_X6_STAGES_3 / TE_X6_KSPLIT schedules
- * and the main-loop ablations are compiled in; the shipped library's x6 entry points answer TE_ERR_UNSUPPORTED to those
- * flags).  Bit 1: built with -DTE_STUDY (getenv switches and study variants of the attention, fp32-MFMA and GELU-plane
- * kernels compiled in). */
-int te_x6_study_build(void);
 /* Provenance of this binary: "<16 hex>-<8 hex>" = sha256 over csrc/{*.hip,*.h} + include/{*.h} (names and contents,
  * sorted) and over the compiler flags, baked in by build.py.  The Python loader recomputes the first half from the tree it
  * was imported from and refuses a library built from other sources; bench.py and smoke() print it. */
@@ -286,9 +281,7 @@ int te_rollout_f32(const float* cams, int64_t L, int64_t start_layer, int64_t B,
  * a tile, else 128 rows / two 256-thread workgroups per CU; the result does not depend on the tile geometry, bit for
  * bit), TE_X6_TILE_128 / TE_X6_TILE_256 pin it; shifted left by TE_X6_TILE_Z_SHIFT / TE_X6_TILE_C_SHIFT they pin one pass.
  * TE_X6_TILE_128x128: 128 x 128 tiles, three 256-thread workgroups per CU (launches with few weight rows).
- * TE_X6_STAGES_3: three LDS stages instead of two in the 256-row geometry (measurement; same results).  STUDY BUILDS ONLY
- * (-DTE_X6_STUDY, te_x6_study_build() & 1): the shipped library does not contain the instantiation and answers
- * TE_ERR_UNSUPPORTED -- likewise TE_X6_KSPLIT.
+ * Unknown flag bits: TE_ERR_INVALID_ARG.
  *
  * Failure is loud.  A workgroup that continues a tile another workgroup started waits for that one's accumulators for at
  * most 250 ms.  If the wait expires it ORs 1 into *status -- a caller-owned, caller-zeroed device word that is NEVER
@@ -302,11 +295,7 @@ int te_rollout_f32(const float* cams, int64_t L, int64_t start_layer, int64_t B,
 #define TE_X6_TILE_128 1
 #define TE_X6_TILE_256 2
 #define TE_X6_TILE_128x128 3
-#define TE_X6_STAGES_3 0x100
 #define TE_X6_TEST_DROP_HANDOVER 0x200
-#define TE_X6_KSPLIT 0x8000            /* study, off by default: products with K >= 1536 and <= 768 weight rows as two K segments per
-                                          output (two k-ordered chains, summed once).  It changes the bits: set it for every
-                                          launch of a process or for none.  Measured: no gain in the step */
 #define TE_X6_WHOLE_TILES 0x10000       /* ranges cut at tile boundaries only, whatever the fill of the last round: for callers that
                                           keep several streams busy (the idle CUs of a last round are used by their other kernels,
                                           and no tile is handed over between workgroups).  Same results, bit for bit */
@@ -339,7 +328,7 @@ int te_linear_relprop_x6_check(const void* ws, int64_t T, int64_t in_f, int64_t 
  *   variant ours: w_planes as above, Y (the forward output) required; x_abs_planes optional (the |X| planes).
  *   variant lrp : w_planes_lrp from te_linear_x6_prepare_weights_lrp_f32 (P3 planes of max(W,0), min(W,0) and of their
  *                 transposes); in_f % 128 == 0; Y, bias, w_planes unused (may be NULL).
- * flags: TE_X6_TILE_* | TE_X6_STAGES_3 | test hooks; status as te_linear_relprop_x6_f32. */
+ * flags: TE_X6_TILE_* | test hooks; status as te_linear_relprop_x6_f32. */
 int te_linear_relprop_x6_general_supported(int64_t T, int64_t in_f, int64_t out_f, int variant);
 size_t te_linear_x6_weight_planes_lrp_bytes(int64_t in_f, int64_t out_f);
 int te_linear_x6_prepare_weights_lrp_f32(const float* W, int64_t in_f, int64_t out_f, void* planes, size_t planes_bytes,
@@ -355,7 +344,7 @@ int te_linear_relprop_x6_general_f32(const float* R, const float* r_scale, int64
  * modules/layers_ours.py:207 = nn.Linear): out [T, M] = X [T, K] . W^T + bias [M] with W given as signed P3 planes of an
  * [M, K] matrix.  te_linear_x6_split_matrix_f32 builds such planes from a row-major [rows, K] matrix (transposed = 0) or
  * from its transpose stored as [K, rows] (transposed = 1: the planes of W^T for d_x = d_y W).  M % 128 == 0, K % 16 == 0.
- * x_planes = NULL: X is split into the workspace first.  flags: TE_X6_TILE_* | TE_X6_STAGES_3 | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID;
+ * x_planes = NULL: X is split into the workspace first.  flags: TE_X6_TILE_* | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID;
  * status: as te_linear_relprop_x6_f32. */
 int te_gemm_x6_supported(int64_t T, int64_t K, int64_t M);
 size_t te_gemm_x6_workspace_bytes(int64_t T, int64_t K, int64_t M);

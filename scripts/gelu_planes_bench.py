@@ -46,7 +46,7 @@ def main():
         ("split_dual of a", lambda: lib.te_linear_x6_split_dual_f32(y.data_ptr(), T, K, p0.data_ptr(), p1.data_ptr(), nb, s), 16),
         ("gelu_forward -> fp32 + planes", lambda: ops.gelu_forward_planes(x), 20),
     ]
-    print(f"T={T} K={K} TE_GELU_SPLIT={os.environ.get('TE_GELU_SPLIT', '(default: staged)')}")
+    print(f"T={T} K={K}")
     for name, fn, bpe in rows:
         us = t(fn)
         print(f"  {name:32s} {us:8.1f} us   {bpe * n / us / 1e6:6.2f} TB/s ({bpe} B per element)")

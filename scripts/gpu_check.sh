@@ -43,7 +43,6 @@ if [[ $PART == *B* ]]; then
   for cfg in vit_l16_384 bert_base_512; do
     ( timeout 300 python bench.py --full --config $cfg --steps 3 --warmup 1 --cpu-maps 2 > "$LINES/bench_$cfg.json" 2> "$LINES/bench_$cfg.err" )
   done
-  ( timeout 400 bash scripts/x6_pmc.sh > gpurun_out/x6_pmc.log 2>&1 )
   ( ATTN_PMC_SKIP_P2=1 timeout 200 bash scripts/attn_pmc.sh > gpurun_out/attn_pmc.log 2>&1 )
   for f in 0 1; do
     ( echo -n "serial step, TE_X6_FUSE_GELU=$f: "; TE_X6_FUSE_GELU=$f timeout 200 python bench.py --steps 10 --overlap-backward off --inflight 1 --cpu-baseline off --no-roofline 2>/dev/null \

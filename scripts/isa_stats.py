@@ -5,7 +5,7 @@ Per kernel: VGPRs / AGPRs, spills, LDS bytes, and instruction counts by class fo
 loop (the innermost backward-branch region with the most MFMAs): MFMA, other VALU, LDS, global / buffer memory, SALU,
 waitcnt, barriers -- and VALU per MFMA, the figure the PMC passes report dynamically (profiles/*_pmc_summary.csv).
 
-    python scripts/isa_stats.py transformer-explainability_amd/csrc/te_attn_rules.hip [--kernel av_rule] [--defines TE_STUDY]
+    python scripts/isa_stats.py transformer-explainability_amd/csrc/te_attn_rules.hip [--kernel qk_rule]
 """
 import argparse
 import os

@@ -6,8 +6,7 @@ time, against the 8 TB/s spec peak -- on COLD data: every repetition works on it
 rotate through more than 1 GB, so nothing is served from the 256 MB Infinity Cache (the in-step condition: a rule's
 operands were written by kernels that ran hundreds of MB of traffic earlier).
 
-    python scripts/stream_kernels_bw.py                 # shipped kernels
-    TE_HEADMEAN_VARIANT=0 python scripts/stream_kernels_bw.py --only headmean    # the grid-stride head-mean kernel
+    python scripts/stream_kernels_bw.py
 """
 import argparse
 import os

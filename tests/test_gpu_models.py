@@ -128,7 +128,7 @@ def _e2e_vs_fp64(name, ours, prefix, k_median=2.0, k_median_l2=None, k_max=1.5):
     reference's own evaluations (`_null_quantile_of_median_ratio`: 4.03 / 3.13 for the 16 headline samples) instead of a
     constant picked after looking at one realisation.  Round 5 asserted 1.5 there after measuring 0.73 / 0.60; the
     reference's own evaluations exceed 1.5 in one draw of ten (90th percentile 1.83 / 1.45), and round 6's attention
-    forward -- closer to fp64 than the kernel it replaced on every output, scripts/attn_fwd_accuracy.py -- drew 1.18 / 1.66."""
+    forward -- closer to fp64 than the kernel it replaced on every output (profiles/r06_attention_fwd6_ab.log) -- drew 1.18 / 1.66."""
     import numpy as np
     from scipy.stats import binom
     fx = np.load(os.path.join(os.path.dirname(__file__), "golden", "e2e_fp64.npz"))

@@ -238,11 +238,10 @@ def _x6_operands(T, in_f, out_f, seed):
 
 
 @pytest.mark.parametrize("T,in_f,out_f", [(1100, 768, 2304), (900, 3072, 768), (700, 256, 512), (257, 128, 256)])
-def test_linear_x6_schedules_are_bitwise_equal(T, in_f, out_f):
-    """One k-ordered chain per output whatever the schedule: the three tile geometries (per pass), two and three LDS stages
-    (round 4 study: prefetch distance 2 in the 256-row geometry), and a 16-workgroup grid that cuts nearly every tile of these
-    small shapes in two (the stream-K hand-over, which the default grid only uses at batch-64 sizes) give the same bits --
-    for the rule and for the plain product of the same kernel."""
+def test_linear_x6_schedules_bitwise_equal_retired_flags_refused(T, in_f, out_f):
+    """One k-ordered chain per output whatever the schedule: the three tile geometries (per pass), whole-tile ranges, and a
+    16-workgroup grid that cuts nearly every tile of these small shapes in two (the stream-K hand-over, which the default grid
+    only uses at batch-64 sizes) give the same bits -- for the rule and for the plain product of the same kernel."""
     from transformer_explainability_amd import ops
     Xd, Wd, bd, Rd, Y = _x6_operands(T, in_f, out_f, 300)
     was = ops.USE_LINEAR_X6
@@ -254,35 +253,21 @@ def test_linear_x6_schedules_are_bitwise_equal(T, in_f, out_f):
         wp = ops.x6_matrix_planes(Wd, False, cache)
         gbase = ops.gemm_x6(Xd, wp, bd, out_f)
         check(f"gemm_x6_small({T},{in_f},{out_f})", gbase, Y, 1e-5)
-        # the study schedules (three LDS stages, the K split) exist in -DTE_X6_STUDY builds only
+        # the retired study flags (0x100: three LDS stages, 0x8000: the K split) are unknown bits now: refused
         from transformer_explainability_amd import _lib
-        study = ops.x6_study_build()
-        if not study:
-            for fl in (ops.TE_X6_STAGES_3, ops.TE_X6_KSPLIT):
-                ops.X6_TILE, ops.X6_FLAGS = 0, fl
-                with pytest.raises(_lib.TeError):
-                    ops.linear_relprop(Rd, Xd, Wd, Y=Y, bias=bd, cache=cache)
-                with pytest.raises(_lib.TeError):
-                    ops.gemm_x6(Xd, wp, bd, out_f)
+        for fl in (0x100, 0x8000):
+            ops.X6_TILE, ops.X6_FLAGS = 0, fl
+            with pytest.raises(_lib.TeError):
+                ops.linear_relprop(Rd, Xd, Wd, Y=Y, bias=bd, cache=cache)
+            with pytest.raises(_lib.TeError):
+                ops.gemm_x6(Xd, wp, bd, out_f)
         for tile in (1, 2, 3):                   # 128 x 256, 256 x 256, 128 x 128 tiles
-            for st in ((0, ops.TE_X6_STAGES_3, ops.TE_X6_WHOLE_TILES) if study else (0, ops.TE_X6_WHOLE_TILES)):      # (+ ranges cut at tile boundaries only)
+            for st in (0, ops.TE_X6_WHOLE_TILES):                  # (+ ranges cut at tile boundaries only)
                 for grid in (0, ops.TE_X6_TEST_SMALL_GRID):
                     ops.X6_TILE, ops.X6_FLAGS = tile, st | grid
                     got = ops.linear_relprop(Rd, Xd, Wd, Y=Y, bias=bd, cache=cache)
                     assert torch.equal(got, base), (tile, st, grid)
                     assert torch.equal(ops.gemm_x6(Xd, wp, bd, out_f), gbase), (tile, st, grid)
-        # the K-split study (TE_X6_KSPLIT: two k-ordered chains per output for K >= 1536 into <= 768 weight rows; off by
-        # default, it changes the bits): within the setting every geometry and schedule agrees bit for bit as well
-        if study and in_f >= 1536 and out_f <= 768:
-            ops.X6_TILE, ops.X6_FLAGS = 0, ops.TE_X6_KSPLIT
-            kbase = ops.linear_relprop(Rd, Xd, Wd, Y=Y, bias=bd, cache=cache)
-            gk = ops.gemm_x6(Xd, wp, bd, out_f)
-            check(f"linear_x6_ksplit_vs_single_chain({T},{in_f},{out_f})", kbase, base, 1e-5)
-            for tile in (1, 2, 3):
-                for grid in (0, ops.TE_X6_TEST_SMALL_GRID):
-                    ops.X6_TILE, ops.X6_FLAGS = tile, ops.TE_X6_KSPLIT | grid
-                    assert torch.equal(ops.linear_relprop(Rd, Xd, Wd, Y=Y, bias=bd, cache=cache), kbase), (tile, grid)
-                    assert torch.equal(ops.gemm_x6(Xd, wp, bd, out_f), gk), (tile, grid)
         # per-pass pins: Z on 128-row tiles, C on 256-row tiles and the other way round
         ops.X6_TILE = 0
         for fl in ((1 << ops.TE_X6_TILE_Z_SHIFT) | (2 << ops.TE_X6_TILE_C_SHIFT),

@@ -33,7 +33,6 @@ SIGNATURES = {
     "te_version": (_I, []),
     "te_status_string": (c_char_p, [_I]),
     "te_device_check": (_I, []),
-    "te_x6_study_build": (_I, []),
     "te_build_id": (c_char_p, []),
     "te_linear_relprop_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
     "te_linear_relprop_f32": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _F, _I, _P, _SZ, _P]),

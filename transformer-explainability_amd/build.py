@@ -71,15 +71,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     os.makedirs(LIB_DIR, exist_ok=True)
     headers = [os.path.join(CSRC, "te_common.h"), os.path.join(CSRC, "te_attn_l6.h"), os.path.join(INCLUDE, "te_relprop.h"), __file__]
-    # measurement builds only (benchmarks/, scripts/): TE_BUILD_DEFINES="TE_X6_STUDY" adds -D flags; they are built NEXT TO the
-    # shipped library (lib/libte_relprop_study.so, objects in build_study/) and selected with TE_RELPROP_LIB, so that a
-    # measurement never replaces the library the tests load
-    extra = ["-D" + d for d in os.environ.get("TE_BUILD_DEFINES", "").split() if d]
-    obj_dir, lib_path = (OBJ_DIR + "_study", LIB_PATH.replace(".so", "_study.so")) if extra else (OBJ_DIR, LIB_PATH)
-    os.makedirs(obj_dir, exist_ok=True)
+    obj_dir, lib_path = OBJ_DIR, LIB_PATH
     # provenance: a content hash of every source + the flags, baked into te_api.o (te_build_id()) and
     # checked by _lib.load() against the tree.  A changed id recompiles te_api.hip even when its own mtime says "fresh".
-    bid = _buildid_module().build_id([*CXXFLAGS, *extra])
+    bid = _buildid_module().build_id(CXXFLAGS)
     stamp = os.path.join(obj_dir, "build_id.txt")
     old_bid = open(stamp).read().strip() if os.path.exists(stamp) else None
     if old_bid == bid and os.path.exists(lib_path) and not force:
@@ -92,7 +87,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         objs.append(o)
         stale_id = src == "te_api.hip" and old_bid != bid
         if force or stale_id or _newer(s, o) or any(_newer(h, o) for h in headers):
-            cmd = [hipcc, *CXXFLAGS, *extra, "-I", INCLUDE, "-I", CSRC, "-c", s, "-o", o]
+            cmd = [hipcc, *CXXFLAGS, "-I", INCLUDE, "-I", CSRC, "-c", s, "-o", o]
             if src == "te_api.hip":
                 cmd.insert(-4, f'-DTE_BUILD_ID="{bid}"')
             if verbose:

@@ -10,17 +10,6 @@ extern "C" int te_version(void) { return 600; /* 0.6.0: round 6 -- te_build_id()
 #endif
 extern "C" const char* te_build_id(void) { return TE_BUILD_ID; }
 
-extern "C" int te_x6_study_build(void) {
-  int bits = 0;
-#ifdef TE_X6_STUDY
-  bits |= 1;      // x6 study schedules (TE_X6_STAGES_3 / TE_X6_KSPLIT) and main-loop ablations compiled in
-#endif
-#ifdef TE_STUDY
-  bits |= 2;      // getenv switches and study variants of the attention / fp32-MFMA / GELU-plane kernels compiled in
-#endif
-  return bits;
-}
-
 extern "C" const char* te_status_string(int status) {
   switch (status) {
     case TE_OK: return "ok";

@@ -17,8 +17,6 @@
 // The column side (d_v, d_k: bwd6l_cols_kernel below) reads rowdot from the workspace this kernel fills.
 //
 // Every reduction has a fixed order that depends on N only: a batch equals its samples run one by one, bit for bit.
-#include <stdlib.h>
-
 #include "te_attn_l6.h"
 
 namespace te_attn_bwd6l {
@@ -369,12 +367,7 @@ int launch_rows(const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn,
                 int64_t B, int64_t H, int64_t N, float scale, int need_qk, hipStream_t stream) {
   const te_attn_l6::Strided dos{do_sb, do_sh, do_sn}, os{o_sb, o_sh, o_sn}, ks{k_sb, k_sh, k_sn}, vs{v_sb, v_sh, v_sn}, dqs{dq_sb, dq_sh, dq_sn};
   const int NBr = (int)((N + 31) >> 5), G8 = (NBr + 7) / 8, G4 = (NBr + 3) / 4;
-  bool w8 = 5 * G8 * 8 <= 6 * G4 * 4;            // (te_attn_fwd6l.hip: launch)
-#ifdef TE_STUDY
-  static const int wenv = [] { const char* e = getenv("TE_BWD6L_WAVES"); return e ? atoi(e) : 0; }();
-  if (wenv == 8) w8 = true;
-  if (wenv == 4) w8 = false;
-#endif
+  const bool w8 = 5 * G8 * 8 <= 6 * G4 * 4;      // (te_attn_fwd6l.hip: launch)
   return w8 ? launch_w<8>(d_out, dos, out, os, k, ks, v, vs, attn, d_attn, rowdot, d_q, dqs, B, H, N, scale, need_qk, stream)
             : launch_w<4>(d_out, dos, out, os, k, ks, v, vs, attn, d_attn, rowdot, d_q, dqs, B, H, N, scale, need_qk, stream);
 }
@@ -385,12 +378,7 @@ int launch_cols(const float* attn, const float* d_attn, const float* rowdot, con
                 int64_t dk_sb, int64_t dk_sh, int64_t dk_sn, int64_t B, int64_t H, int64_t N, float scale, int need_qk, hipStream_t stream) {
   const te_attn_l6::Strided dos{do_sb, do_sh, do_sn}, qs{q_sb, q_sh, q_sn}, dvs{dv_sb, dv_sh, dv_sn}, dks{dk_sb, dk_sh, dk_sn};
   const int NBr = (int)((N + 31) >> 5), G8 = (NBr + 7) / 8, G4 = (NBr + 3) / 4;
-  bool w8 = 5 * G8 * 8 <= 6 * G4 * 4;
-#ifdef TE_STUDY
-  static const int wenv = [] { const char* e = getenv("TE_BWD6L_WAVES"); return e ? atoi(e) : 0; }();
-  if (wenv == 8) w8 = true;
-  if (wenv == 4) w8 = false;
-#endif
+  const bool w8 = 5 * G8 * 8 <= 6 * G4 * 4;
   return w8 ? launch_cols_w<8>(attn, d_attn, rowdot, d_out, dos, q, qs, d_v, dvs, d_k, dks, B, H, N, scale, need_qk, stream)
             : launch_cols_w<4>(attn, d_attn, rowdot, d_out, dos, q, qs, d_v, dvs, d_k, dks, B, H, N, scale, need_qk, stream);
 }

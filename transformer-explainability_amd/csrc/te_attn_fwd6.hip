@@ -167,11 +167,6 @@ constexpr int kTileLd = 36;                                 // floats per tile r
 // LAST = the key block that may straddle N: its pieces are guarded per lane.  Every other block leaves as buffer stores whose hardware
 // range check (descriptor = the (b, h)'s N x N matrix) drops the rows at or beyond N: no branch, no exec masking, 32-bit offsets.
 typedef __amdgpu_buffer_rsrc_t Rsrc;
-#ifdef TE_FWD6_NO_BUFSTORE
-constexpr bool kNoBufStore = true;      // measurement builds: the global-store path for every block
-#else
-constexpr bool kNoBufStore = false;
-#endif
 template <bool LAST>
 __device__ __forceinline__ void block_out(float* __restrict__ tile, const f32x16& a, float* __restrict__ base, Rsrc rs, int i0, int j0, int N) {
   const int lane = threadIdx.x & 63, n = lane & 31, kh = lane >> 5;
@@ -183,7 +178,7 @@ __device__ __forceinline__ void block_out(float* __restrict__ tile, const f32x16
   for (int m = 0; m < 4; ++m) {
     const int r = r8 + 8 * m;
     const f32x4 v = *reinterpret_cast<const f32x4*>(tile + r * kTileLd + 4 * c);
-    if constexpr (LAST || kNoBufStore) {
+    if constexpr (LAST) {
       if (i0 + r < N && j0 + 4 * c < N) store_piece(base + (int64_t)(i0 + r) * N, j0 + 4 * c, N, v);
     } else {
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (unsigned)(((i0 + r) * N + j0 + 4 * c) * 4), 0, 0);

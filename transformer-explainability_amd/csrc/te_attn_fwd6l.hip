@@ -24,8 +24,6 @@
 // eight rows per buffer-store instruction (the descriptor's range check drops the rows at or beyond N).
 //
 // Every reduction has a fixed order that depends on N only: a batch equals its samples run one by one, bit for bit.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "te_attn_l6.h"
@@ -36,8 +34,7 @@ namespace {
 
 using namespace te_attn_l6;
 
-// OPT (measurement builds, TE_FWD6L_OPT): 1 no N x N stores, 2 no exponentials, 4 no second product, 8 no pass 1, 16 no recomputation
-template <int W, int OPT>
+template <int W>
 __global__ __launch_bounds__(64 * W, 2) void fwd6l_kernel(const float* __restrict__ q, Strided qs, const float* __restrict__ k, Strided ks,
                                                           const float* __restrict__ v, Strided vs, const float* __restrict__ mask,
                                                           float* __restrict__ zqk, float* __restrict__ xsc, float* __restrict__ attn,
@@ -111,7 +108,6 @@ __global__ __launch_bounds__(64 * W, 2) void fwd6l_kernel(const float* __restric
       }
   };
   auto blocks_out = [&](const f32x16 (&a)[NKB], Rsrc rs, int c, bool tail) __attribute__((always_inline)) {
-    if constexpr (OPT & 1) return;
     if (tail) {
 #pragma unroll
       for (int u = 0; u < NKB; ++u) block_out<true>(tile, a[u], rs, ro, kKC * c + 32 * u, N);
@@ -130,7 +126,7 @@ __global__ __launch_bounds__(64 * W, 2) void fwd6l_kernel(const float* __restric
     const int cn = last ? 0 : c + 1;                 // behind the last chunk: chunk 0 again, with its v rows, for pass 2
     request_k<W>(kr, k_bh, ks.sn, N, cn);
     if (last) request_v<W>(vr, v_bh, vs.sn, N, 0);
-    if (owner && !(OPT & 8)) {
+    if (owner) {
       scores<W>(acc, buf, qb);
       if (zqk) blocks_out(acc, z_rs, c, last);
       if (xsc) {
@@ -154,7 +150,7 @@ __global__ __launch_bounds__(64 * W, 2) void fwd6l_kernel(const float* __restric
       for (int u = 0; u < NKB; ++u)
 #pragma unroll
         for (int e2 = 0; e2 < 8; ++e2)
-          s2[e2 & 1] = add2(s2[e2 & 1], ((OPT & 2) ? sub2(acc[u][2 * e2], acc[u][2 * e2 + 1], mr) : exp2_le0(sub2(acc[u][2 * e2], acc[u][2 * e2 + 1], mr))));
+          s2[e2 & 1] = add2(s2[e2 & 1], exp2_le0(sub2(acc[u][2 * e2], acc[u][2 * e2 + 1], mr)));
       const f32x2 s1 = add2(s2[0], s2[1]);
       l = l * exp_le0(m - mr) + (s1[0] + s1[1]);
       m = mn;
@@ -190,28 +186,21 @@ __global__ __launch_bounds__(64 * W, 2) void fwd6l_kernel(const float* __restric
       request_v<W>(vr, v_bh, vs.sn, N, c + 1);
     }
     if (owner) {
-      if constexpr (OPT & 16) {
-#pragma unroll
-        for (int u = 0; u < NKB; ++u)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) acc[u][e] = (float)(e + c);
-      } else {
-        scores<W>(acc, buf, qb);
-      }
+      scores<W>(acc, buf, qb);
       soft_in(c);
 #pragma unroll
       for (int u = 0; u < NKB; ++u)
 #pragma unroll
         for (int e2 = 0; e2 < 8; ++e2) {
           const f32x2 xx = sub2(acc[u][2 * e2], acc[u][2 * e2 + 1], mx);
-          const f32x2 p = div2((OPT & 2) ? xx : exp2_le0(xx), sum, rcs);
+          const f32x2 p = div2(exp2_le0(xx), sum, rcs);
           acc[u][2 * e2] = p[0], acc[u][2 * e2 + 1] = p[1];
         }
       blocks_out(acc, a_rs, c, last);
       // K16 step s of the chunk = keys 16 s .. 16 s + 15 = (u = s / 2, g = 2 (s & 1), 2 (s & 1) + 1): B element t = 4 gg + c of lane (i, h)
       const unsigned char* const vfrag = buf + kOperand;
 #pragma unroll
-      for (int s = 0; s < ((OPT & 4) ? 0 : 2 * NKB); ++s) {
+      for (int s = 0; s < 2 * NKB; ++s) {
         const int u = s >> 1, g0 = 2 * (s & 1);
         const float x[8] = {acc[u][4 * g0],     acc[u][4 * g0 + 1], acc[u][4 * g0 + 2], acc[u][4 * g0 + 3],
                             acc[u][4 * g0 + 4], acc[u][4 * g0 + 5], acc[u][4 * g0 + 6], acc[u][4 * g0 + 7]};
@@ -244,15 +233,15 @@ __global__ __launch_bounds__(64 * W, 2) void fwd6l_kernel(const float* __restric
   }
 }
 
-template <int W, int OPT = 0>
+template <int W>
 int launch_w(const float* q, Strided qs, const float* k, Strided ks, const float* v, Strided vs, const float* mask, float* z_qk,
              float* x_scaled, float* attn, float* out, Strided os, int64_t B, int64_t H, int64_t N, float scale, hipStream_t stream) {
   const int NBr = (int)((N + 31) >> 5);
   const int G = (NBr + W - 1) / W, RB = (NBr + G - 1) / G;      // parts of a (b, h), row blocks (waves) of a part
   const int64_t BH = B * H, slots = ((BH + 7) / 8) * G;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fwd6l_kernel<W, OPT>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg<W>::kLds);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fwd6l_kernel<W>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg<W>::kLds);
   if (e != hipSuccess) return (int)e;
-  fwd6l_kernel<W, OPT><<<dim3((unsigned)(slots * 8)), dim3(64 * W), Cfg<W>::kLds, stream>>>(q, qs, k, ks, v, vs, mask, z_qk, x_scaled, attn, out, os,
+  fwd6l_kernel<W><<<dim3((unsigned)(slots * 8)), dim3(64 * W), Cfg<W>::kLds, stream>>>(q, qs, k, ks, v, vs, mask, z_qk, x_scaled, attn, out, os,
                                                                                       (int)H, (int)N, (int)BH, G, RB, scale);
   return TE_OK;
 }
@@ -272,36 +261,7 @@ int launch(const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float
   // 8-wave workgroups are ~10 % faster at equal wave utilisation (measured: profiles/r06_attention_fwd_long_ab.log); the 4-wave
   // cut wins where it leaves fewer waves without a row block: owners / (parts x waves) at least 1.2 x the 8-wave cut's
   const int NBr = (int)((N + 31) >> 5), G8 = (NBr + 7) / 8, G4 = (NBr + 3) / 4;
-  bool w8 = 5 * G8 * 8 <= 6 * G4 * 4;            // (NBr / (4 G4)) / (NBr / (8 G8)) < 1.2
-#ifdef TE_STUDY      // TE_FWD6L_WAVES=4 / 8 forces the cut, TE_FWD6L_OPT the measurement switches (measurement builds)
-  static const int wenv = [] { const char* e = getenv("TE_FWD6L_WAVES"); return e ? atoi(e) : 0; }();
-  if (wenv == 8) w8 = true;
-  if (wenv == 4) w8 = false;
-  static const int opt = [] { const char* e = getenv("TE_FWD6L_OPT"); return e ? atoi(e) : 0; }();
-#define TE_FWD6L_ARGS q, qs, k, ks, v, vs, mask, z_qk, x_scaled, attn, out, os, B, H, N, scale, stream
-  if (w8) {
-    switch (opt) {
-      case 1: return launch_w<8, 1>(TE_FWD6L_ARGS);
-      case 2: return launch_w<8, 2>(TE_FWD6L_ARGS);
-      case 4: return launch_w<8, 4>(TE_FWD6L_ARGS);
-      case 8: return launch_w<8, 8>(TE_FWD6L_ARGS);
-      case 16: return launch_w<8, 16>(TE_FWD6L_ARGS);
-      case 31: return launch_w<8, 31>(TE_FWD6L_ARGS);
-      default: break;
-    }
-  } else {
-    switch (opt) {
-      case 1: return launch_w<4, 1>(TE_FWD6L_ARGS);
-      case 2: return launch_w<4, 2>(TE_FWD6L_ARGS);
-      case 4: return launch_w<4, 4>(TE_FWD6L_ARGS);
-      case 8: return launch_w<4, 8>(TE_FWD6L_ARGS);
-      case 16: return launch_w<4, 16>(TE_FWD6L_ARGS);
-      case 31: return launch_w<4, 31>(TE_FWD6L_ARGS);
-      default: break;
-    }
-  }
-#undef TE_FWD6L_ARGS
-#endif
+  const bool w8 = 5 * G8 * 8 <= 6 * G4 * 4;      // (NBr / (4 G4)) / (NBr / (8 G8)) < 1.2
   return w8 ? launch_w<8>(q, qs, k, ks, v, vs, mask, z_qk, x_scaled, attn, out, os, B, H, N, scale, stream)
             : launch_w<4>(q, qs, k, ks, v, vs, mask, z_qk, x_scaled, attn, out, os, B, H, N, scale, stream);
 }

@@ -15,14 +15,10 @@
 //
 // Round 6: for 64 < N <= 640 the entry points below dispatch to te_attn_fwd6l.hip (forward) and te_attn_bwd6l.hip (backward: the
 // column side always, the row side when the caller hands over the block's forward output or needs no d_q / d_k) -- bf16 MFMAs with
-// split operands, 1.4-2.2 x these kernels, which remain for N <= 64, for the backward without `out`, and as the comparison path of
-// the A/B scripts (TE_ATTN_FWD_LONG / TE_ATTN_BWD_LONG / TE_ATTN_BWD_COLS = old in measurement builds).
+// split operands, 1.4-2.2 x these kernels, which remain for N <= 64 and for the backward without `out`.
 //
 // fp32 MFMAs (v_mfma_f32_32x32x2_f32 / 16x16x4_f32): exact k-ordered fma chains; every reduction has a fixed order that
 // depends on N only, so a batch equals its samples run one by one, bit for bit.
-#include <stdlib.h>
-#include <string.h>
-
 #include <algorithm>
 
 #include "te_common.h"
@@ -488,12 +484,7 @@ extern "C" int te_attention_forward_strided_f32(const float* q, int64_t q_sb, in
       !strides_ok(o_sb, o_sh, o_sn))
     return TE_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
-#ifdef TE_STUDY      // TE_ATTN_FWD_LONG=old selects the round-3 kernel in measurement builds for same-box A/B runs
-  static const bool old_fwd = [] { const char* e = getenv("TE_ATTN_FWD_LONG"); return e && !strcmp(e, "old"); }();
-#else
-  constexpr bool old_fwd = false;
-#endif
-  if (!old_fwd && te_attn_fwd6l::supported(B, H, N, D)) {
+  if (te_attn_fwd6l::supported(B, H, N, D)) {
     const int rc = te_attn_fwd6l::launch(q, q_sb, q_sh, q_sn, k, k_sb, k_sh, k_sn, v, v_sb, v_sh, v_sn, mask, z_qk, x_scaled, attn,
                                          out, o_sb, o_sh, o_sn, B, H, N, scale, stream);
     if (rc != TE_OK) return rc;
@@ -530,12 +521,7 @@ static int backward_strided(const float* d_out, int64_t do_sb, int64_t do_sh, in
   if (!ws || ws_bytes < te_attention_backward_strided_workspace_bytes(B, H, N)) return TE_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   float* rowdot = (float*)ws;
-#ifdef TE_STUDY      // TE_ATTN_BWD_LONG=old selects the round-3 row kernel in measurement builds for same-box A/B runs
-  static const bool old_rows = [] { const char* e = getenv("TE_ATTN_BWD_LONG"); return e && !strcmp(e, "old"); }();
-#else
-  constexpr bool old_rows = false;
-#endif
-  if (!old_rows && (out || !need_qk) && te_attn_bwd6l::supported(B, H, N, D)) {
+  if ((out || !need_qk) && te_attn_bwd6l::supported(B, H, N, D)) {
     const int rc = te_attn_bwd6l::launch_rows(d_out, do_sb, do_sh, do_sn, out, o_sb, o_sh, o_sn, k, k_sb, k_sh, k_sn, v, v_sb, v_sh, v_sn,
                                               attn, d_attn, rowdot, d_q, dq_sb, dq_sh, dq_sn, B, H, N, scale, need_qk ? 1 : 0, stream);
     if (rc != TE_OK) return rc;
@@ -545,12 +531,7 @@ static int backward_strided(const float* d_out, int64_t do_sb, int64_t do_sh, in
         d_out, Strided{do_sb, do_sh, do_sn}, k, Strided{k_sb, k_sh, k_sn}, v, Strided{v_sb, v_sh, v_sn}, attn, d_attn, rowdot,
         d_q, Strided{dq_sb, dq_sh, dq_sn}, (int)H, (int)N, (int)ntile, scale, need_qk ? 1 : 0);
   }
-#ifdef TE_STUDY      // TE_ATTN_BWD_COLS=old selects the round-3 column kernel in measurement builds
-  static const bool old_cols = [] { const char* e = getenv("TE_ATTN_BWD_COLS"); return e && !strcmp(e, "old"); }();
-#else
-  constexpr bool old_cols = false;
-#endif
-  if (!old_cols && te_attn_bwd6l::supported(B, H, N, D)) {
+  if (te_attn_bwd6l::supported(B, H, N, D)) {
     const int rc = te_attn_bwd6l::launch_cols(attn, d_attn, rowdot, d_out, do_sb, do_sh, do_sn, q, q_sb, q_sh, q_sn, d_v, dv_sb, dv_sh, dv_sn,
                                               d_k, dk_sb, dk_sh, dk_sn, B, H, N, scale, need_qk ? 1 : 0, stream);
     if (rc != TE_OK) return rc;

@@ -25,7 +25,6 @@
 #include "te_common.h"
 
 namespace te_attn_rules {   // te_attn_rules.hip: the one-pass rule kernels (default)
-bool enabled();
 bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
 int av_launch(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const float* attn, const float* v, int64_t v_sb,
               int64_t v_sh, int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn, float* cam_attn,
@@ -528,7 +527,7 @@ int av_launch(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const fl
     Z = wsZ;
     z_sb = H * N * TS, z_sh = N * TS, z_sn = TS;
   }
-  if (te_attn_rules::enabled() && te_attn_rules::supported(B, H, N, D))
+  if (te_attn_rules::supported(B, H, N, D))
     return te_attn_rules::av_launch(R, r_sb, r_sh, r_sn, attn, v, v_sb, v_sh, v_sn, Z, z_sb, z_sh, z_sn, cam_attn, cam_v,
                                     cv_sb, cv_sh, cv_sn, B, H, N, scale, stream);
   if (!z_contig) return TE_ERR_UNSUPPORTED;      // the 64 x 64-tile kernels read Z as contiguous [B*H,N,64]
@@ -553,7 +552,7 @@ int qk_launch(const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int6
     z_qk_kernel<<<dim3((unsigned)(BH * nt * nt)), blk, 0, stream>>>(q, qs, k, ks, wsZ, (int)H, (int)N, BH, nt);
     Z = wsZ;
   }
-  if (te_attn_rules::enabled() && te_attn_rules::supported(B, H, N, D))
+  if (te_attn_rules::supported(B, H, N, D))
     // (the per-group cam_q partials of N > 256 live in the S region of the workspace, which this path never writes:
     //  ngroups * 64 <= N whenever ngroups > 1)
     return te_attn_rules::qk_launch(Rnn, q, q_sb, q_sh, q_sn, k, k_sb, k_sh, k_sn, Z, cam_q, cq_sb, cq_sh, cq_sn, cam_k,

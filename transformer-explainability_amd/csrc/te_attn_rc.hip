@@ -475,21 +475,6 @@ __device__ __forceinline__ void row_dots(float* __restrict__ rdv, Rsrc r_rs, Rsr
   }
 }
 
-// measurement builds (-DTE_STUDY): phase stamps of one workgroup of the second round (scripts/attn_rc_prof.py)
-#ifdef TE_STUDY
-__device__ long long g_rc_prof[8 * 16];
-#define RC_MARK(i)                                                                  \
-  do {                                                                              \
-    if (blockIdx.x == 300 && (threadIdx.x & 63) == 0) {                             \
-      g_rc_prof[(threadIdx.x >> 6) * 16 + (i)] = clock64();                         \
-      if ((i) == 0) g_rc_prof[(threadIdx.x >> 6) * 16 + 15] = wall_clock64();       \
-      if ((i) == 7) g_rc_prof[(threadIdx.x >> 6) * 16 + 14] = wall_clock64();       \
-    }                                                                               \
-  } while (0)
-#else
-#define RC_MARK(i) do { } while (0)
-#endif
-
 template <int MODE>
 __global__ __launch_bounds__(kT) void qk_rc_kernel(const float* __restrict__ Rnn, const float* __restrict__ Z,
                                                    const float* __restrict__ q, Strided qs, const float* __restrict__ k,
@@ -515,10 +500,8 @@ __global__ __launch_bounds__(kT) void qk_rc_kernel(const float* __restrict__ Rnn
   const float f = has_f ? r_scale[(int64_t)b * r_scale_stride] : 1.0f;
   const bool owner = wave < NB;                                        // wave-uniform
 
-  RC_MARK(0);
   stage_planes<true>(Pk, k_bh, ks.sn, N, NS);                                // k^T planes: the row phase's A operand
   if (both) stage_planes<false>(Pq, q_bh, qs.sn, N, NS);                      // q^T planes: the column phase's
-  RC_MARK(1);
   float rd_own = 0.0f;
   if constexpr (MODE == BWD) {
     if (dO != nullptr) {
@@ -550,7 +533,6 @@ __global__ __launch_bounds__(kT) void qk_rc_kernel(const float* __restrict__ Rnn
     }
   }
   __syncthreads();
-  RC_MARK(2);
 
   // ---- row side: cam_q[i][d] = q[i][d] * (sum_j S[i][j] k[j][d]) * scale   (BWD: d_q = the sum) ----
   if (owner) {
@@ -560,7 +542,6 @@ __global__ __launch_bounds__(kT) void qk_rc_kernel(const float* __restrict__ Rnn
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[mb][e] = 0.0f;
     phase_rows<MODE>(acc, Pk, plane, r_rs, z_rs, N, NB, wave, f, has_f, scale, rdv);
-    RC_MARK(3);
     const int i = wave * 32 + n;
     if (i < N) {
       const float* qrow = q_bh + (int64_t)i * qs.sn + 4 * hh;
@@ -586,13 +567,11 @@ __global__ __launch_bounds__(kT) void qk_rc_kernel(const float* __restrict__ Rnn
         }
     }
   }
-  RC_MARK(4);
   if (!both) {
     __syncthreads();                                                   // every wave is done with the k^T planes
     stage_planes<false>(Pq, q_bh, qs.sn, N, NS);                       // q^T planes: the column phase's A operand
     __syncthreads();
   }
-  RC_MARK(5);
 
   // ---- column side: cam_k[j][d] = k[j][d] * (sum_i S[i][j] q[i][d]) * scale   (BWD: d_k = the sum) ----
   if (owner) {
@@ -602,7 +581,6 @@ __global__ __launch_bounds__(kT) void qk_rc_kernel(const float* __restrict__ Rnn
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[mb][e] = 0.0f;
     phase<MODE, COLS>(acc, Pq, plane, r_rs, z_rs, N, NS, wave, f, has_f, scale, rd_own, rdv);
-    RC_MARK(6);
     const int j = wave * 32 + n;
     if (j < N) {
       const float* krow = k_bh + (int64_t)j * ks.sn + 4 * hh;
@@ -628,7 +606,6 @@ __global__ __launch_bounds__(kT) void qk_rc_kernel(const float* __restrict__ Rnn
         }
     }
   }
-  RC_MARK(7);
 }
 
 inline size_t lds_bytes(int64_t N, bool both) {
@@ -672,9 +649,3 @@ int qk_launch(int mode, const float* Rnn, const float* q, int64_t q_sb, int64_t 
 }
 
 }  // namespace te_attn_rc
-
-#ifdef TE_STUDY
-extern "C" int te_attn_rc_profile(long long* host_out) {      // 8 waves x 16 stamps (measurement builds only)
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(te_attn_rc::g_rc_prof), sizeof(long long) * 8 * 16);
-}
-#endif

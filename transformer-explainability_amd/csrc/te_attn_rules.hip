@@ -1,65 +1,53 @@
 // te_attn_rules.hip -- ONE-PASS attention relprop rules for gfx950 (head dim 64): each rule reads its N x N operands
 // once and never writes S = safe_divide(R, Z) to memory (modules/layers_ours.py:48-60,122-127; ViT_LRP.py:157-173;
-// BERT.py:367-393).
+// BERT.py:367-393), and the attention producers.
 //
 //   AV rule:  S = sd(R, Z_av) [N,64];  cam_attn = attn .(S v^T);  cam_v = v .(attn^T S)
 //   QK rule:  S = sd(R_nn, Z_qk) [N,N]; cam_q = q .(S k);         cam_k = k .(S^T q)
 //
 // Z is the cached forward product of the very einsum / MatMul whose rule is evaluated (te_attn_mfma.hip header).
 //
-// One workgroup (512 threads = 8 waves, one per (b, h, key group of <= 256 keys)) keeps the key-side operand (v or k,
-// <= 256 x 64) resident in LDS and walks the query rows in tiles of 32.  Per tile the row-side product AND the
-// column-side product are formed from the same LDS image of the [32, keys] tile:
+// Which kernels run:
+//   AV rule                      te_attn_kb.hip (wave-owned key blocks), every N <= 4096
+//   QK rule                      te_attn_rc.hip for N <= 224, qk_rule_kernel below beyond
+//   attention forward            te_attn_fwd6.hip (N <= 224)
+//   backward, first half         te_attn_kb.hip: d_attn = d_out v^T (the tensor save_attn_gradients receives,
+//                                ViT_LRP.py:144-145) and d_v = attn^T d_out
+//   backward, second half        d_s = attn .(d_attn - rowsum(d_attn . attn)) * scale (softmax backward), d_q = d_s k,
+//                                d_k = d_s^T q: te_attn_rc.hip for N <= 160 or with the forward output at hand,
+//                                qk_rule_kernel<BWD> otherwise
 //
-//   AV:  S tile [32,64] (from R, Z) and the attn tile [32,keys] -> LDS
-//        G = S v^T            one 32x32 output block per wave (v_mfma_f32_32x32x2_f32), K = 64
-//        cam_attn = attn . G  straight from the accumulators
-//        cam_v  += attn^T S   (keys x 64) as 32x32 blocks, two per wave, accumulators live across all row tiles
-//   QK:  S tile [32,keys] = sd(R_nn, Z_qk) and the q tile [32,64] -> LDS
-//        cam_q  = S k         32x64 output as eight 16x16 blocks, one per wave (v_mfma_f32_16x16x4_f32), K = keys:
-//                             every wave busy without a split-K reduction
-//        cam_k += S^T q       as for cam_v
+// qk_rule_kernel: one workgroup (512 threads = 8 waves, one per (b, h, key group of <= 256 keys)) keeps k (<= 256 x 64)
+// resident in LDS and walks the query rows in tiles of 32.  Per tile the row-side product AND the column-side product
+// are formed from the same LDS image of the [32, keys] tile:
+//
+//   S tile [32,keys] = sd(R_nn, Z_qk) and the q tile [32,64] -> LDS
+//   cam_q  = S k         32x64 output as eight 16x16 blocks, one per wave (v_mfma_f32_16x16x4_f32), K = keys:
+//                        every wave busy without a split-K reduction
+//   cam_k += S^T q       (keys x 64) as 32x32 blocks, two per wave, accumulators live across all row tiles
 //
 // Every tile of the next step is requested (global -> registers) before the MFMAs of the current one start, so HBM
-// latency hides under ~4000 MFMA-pipe cycles per wave and tile.  Traffic per (b,h): AV reads attn, R, Z, v once and
-// writes cam_attn, cam_v; QK reads R_nn, Z_qk, q, k once and writes cam_q, cam_k = the rules' algorithmic bytes (the
-// 64 x 64-tile kernels of te_attn_mfma.hip wrote S to a workspace and re-read it and attn: ~8 N^2 passes per layer).
-// N > 256: the keys are cut into groups of <= 256 (one workgroup each); the column side of a group is complete, the
-// QK rule's row side (cam_q) is a per-group partial that a small finishing kernel sums in group order.
-//
-// Producers on the same machinery, N <= 224 (k AND v resident), head dim 64:
-//   attn_fwd_kernel          z_qk = q k^T (unscaled, written for the QK rule), attn = softmax(z_qk * scale) over the
-//                            LDS tile, out = attn v written as 'b n (h d)' -- ViT_LRP.py:132-152 in one pass over
-//                            the fused qkv activation (no q/k/v copies, no separate scale / softmax / transpose passes)
-//   av_rule_kernel<BWD>      attention-gradient backward, first half: d_attn = d_out v^T (the tensor
-//                            save_attn_gradients receives, ViT_LRP.py:144-145) and d_v = attn^T d_out
-//   qk_rule_kernel<BWD>      second half: d_s = attn .(d_attn - rowsum(d_attn . attn)) * scale formed in the tile
-//                            (softmax backward), d_q = d_s k, d_k = d_s^T q
+// latency hides under ~4000 MFMA-pipe cycles per wave and tile.  Traffic per (b,h): R_nn, Z_qk, q, k read once, cam_q,
+// cam_k written once = the rule's algorithmic bytes (the 64 x 64-tile kernels of te_attn_mfma.hip wrote S to a workspace
+// and re-read it: ~8 N^2 passes per layer).  N > 256: the keys are cut into groups of <= 256 (one workgroup each); the
+// column side of a group is complete, the row side (cam_q) is a per-group partial that a small finishing kernel sums in
+// group order.
 //
 // All reductions run in a fixed order that depends on N only: a batch equals its samples run one by one, bit for bit.
-// LDS images of the rule kernels: PADDED row-major tiles (row strides 68 / 256 / 260 floats, see below) -- every MFMA
-// fragment address is a per-lane base plus a compile-time offset, and both products read the same row-major tile (the
-// row side as 16-B fragments along a row, the column side as 4-byte fragments down the rows).  The forward producer,
-// which holds k AND v, has no room for padding and keeps XOR-swizzled images ([rows][64]: the 16-B chunks of a row
-// XOR-ed by (row & 15); the [32][256] tile the same within each group of 16 chunks).
-#include <stdlib.h>
-#include <string.h>
-
+// LDS images: PADDED row-major tiles (row strides 68 / 260 floats, see below) -- every MFMA fragment address is a per-lane
+// base plus a compile-time offset, and both products read the same row-major tile (the row side as 16-B fragments along a
+// row, the column side as 4-byte fragments down the rows).
 #include "te_common.h"
 
-namespace te_attn_kb {      // te_attn_kb.hip: wave-owned key blocks (round 5) -- the default AV kernels
+namespace te_attn_kb {      // te_attn_kb.hip: wave-owned key blocks (round 5) -- the AV rule and the first half of the backward
 bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
 int av_launch(int mode, const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const float* attn, const float* v,
               int64_t v_sb, int64_t v_sh, int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn,
               float* cam_attn, float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn, int64_t B, int64_t H, int64_t N,
               float scale, hipStream_t stream);
-int qk_launch(const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb,
-              int64_t k_sh, int64_t k_sn, const float* Z, float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn,
-              float* cam_k, int64_t ck_sb, int64_t ck_sh, int64_t ck_sn, int64_t B, int64_t H, int64_t N, float scale,
-              float* qpart, const float* r_scale, int64_t r_scale_stride, int* ngroups_out, hipStream_t stream);
 }  // namespace te_attn_kb
 
-namespace te_attn_rc {      // te_attn_rc.hip: row-block and key-block owners (round 6) -- the default QK rule / softmax backward, N <= 224
+namespace te_attn_rc {      // te_attn_rc.hip: row-block and key-block owners (round 6) -- the QK rule / softmax backward, N <= 224
 bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
 int qk_launch(int mode, const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb,
               int64_t k_sh, int64_t k_sn, const float* Z, float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn, float* cam_k,
@@ -68,7 +56,7 @@ int qk_launch(int mode, const float* Rnn, const float* q, int64_t q_sb, int64_t 
               int64_t o_sh = 0, int64_t o_sn = 0);
 }  // namespace te_attn_rc
 
-namespace te_attn_fwd6 {      // te_attn_fwd6.hip: row-block owners on bf16 MFMAs (round 6) -- the default attention forward, N <= 224
+namespace te_attn_fwd6 {      // te_attn_fwd6.hip: row-block owners on bf16 MFMAs (round 6) -- the attention forward, N <= 224
 bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
 int launch(const float* qkv, float* z_qk, float* attn, float* out, int64_t B, int64_t H, int64_t N, float scale, hipStream_t stream,
            void* out_planes = nullptr, void* out_abs_planes = nullptr);
@@ -81,8 +69,6 @@ namespace {
 constexpr int TI = 32;         // query rows per tile
 constexpr int kT = 512;        // threads per workgroup
 constexpr int kWaves = kT / 64;
-constexpr int NJMAX = 256;     // keys per workgroup
-constexpr int WLD = 256;       // row stride of the [TI][keys] tile
 
 struct Strided {  // [B,H,N,D] view, D contiguous
   int64_t sb, sh, sn;
@@ -93,15 +79,6 @@ typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
 #define TE_MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 #define TE_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-__device__ __forceinline__ int swz64(int row, int chunk) { return row * 64 + ((chunk ^ (row & 15)) << 2); }
-// (ld = floats per row, a multiple of 64: the keys of a group, <= 256)
-__device__ __forceinline__ int swzw(int row, int chunk, int ld = WLD) {
-  return row * ld + (((chunk & ~15) | ((chunk ^ row) & 15)) << 2);
-}
-// element (row, x) of a swizzled tile
-__device__ __forceinline__ float at64(const float* __restrict__ T, int row, int x) {
-  return T[swz64(row, x >> 2) + (x & 3)];
-}
 __device__ __forceinline__ int crow(int e, int kh) { return (e & 3) + 8 * (e >> 2) + 4 * kh; }
 
 __device__ __forceinline__ void zero16(f32x16& a) {
@@ -198,110 +175,21 @@ __device__ __forceinline__ f32x4 fast_fix(const FastMap& m, int r, f32x4 L, int 
   return out;
 }
 
-// key-side operand (v or k) of this group: rows [j0, j0 + nj) -> LDS [nj32][64], rows >= nj zero
-__device__ __forceinline__ void stage_keys(float* __restrict__ Kt, const float* __restrict__ src, int64_t sn, int nj,
-                                           int nj32) {
-  for (int idx = threadIdx.x; idx < nj32 * 16; idx += kT) {
-    const int row = idx >> 4, c = idx & 15;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row < nj) v = *reinterpret_cast<const f32x4_u*>(src + (int64_t)row * sn + (c << 2));
-    *reinterpret_cast<f32x4*>(Kt + swz64(row, c)) = v;
-  }
-}
-
-// row-side product with a 32x32 output block:  acc += A[32 x 64] B[32 x 64]^T, both K-contiguous [rows][64] images.
-// All sixteen fragments are requested before the first MFMA (one LDS round trip per product instead of one per
-// four MFMAs -- hipcc otherwise waits lgkmcnt(0) in front of every group).  `between(kg)` runs after the kg-th group
-// of four MFMAs (kg = 0..7, also when the wave has no block: active == false): the caller issues ONE global memory
-// instruction there, so that the next tile's loads stream under the MFMAs instead of queueing up in a separate phase
-// -- a CU moves ~10 B per clock from HBM, a tile needs ~6500 clocks of that, about as long as its MFMAs.
-template <class F>
-__device__ __forceinline__ void row_product32(f32x16& acc, bool active, const float* __restrict__ At, int arow,
-                                              const float* __restrict__ Bt, int brow, int kh, F&& between) {
-  f32x4 a[8], bq[8];
-  if (active) {
-#pragma unroll
-    for (int kg = 0; kg < 8; ++kg) {
-      a[kg] = *reinterpret_cast<const f32x4*>(At + swz64(arow, kg * 2 + kh));
-      bq[kg] = *reinterpret_cast<const f32x4*>(Bt + swz64(brow, kg * 2 + kh));
-    }
-  }
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int kg = 0; kg < 8; ++kg) {
-    if (active) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc = TE_MFMA32(a[kg][j], bq[kg][j], acc);
-    }
-    between(kg);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// row-side product with a 16x16 output block over K = nj32 keys:  acc += W[16 x keys] X[keys x 16], W = the
-// [TI][256] tile (K = key contiguous), XtT = the key-side operand TRANSPOSED [64][256] (K = key contiguous), both
-// read with ds_read_b128; software-pipelined two 16-key groups at a time (the next pair's fragments are requested
-// before the current pair's eight MFMAs).  nj32 is a multiple of 32.
-__device__ __forceinline__ void row_product16(f32x4& acc, const float* __restrict__ Wt, int arow,
-                                              const float* __restrict__ XtT, int dcol, int kq, int nj32, int ld) {
-  const int np = nj32 >> 5;
-  f32x4 a0 = *reinterpret_cast<const f32x4*>(Wt + swzw(arow, kq, ld)), a1 = *reinterpret_cast<const f32x4*>(Wt + swzw(arow, 4 + kq, ld));
-  f32x4 b0 = *reinterpret_cast<const f32x4*>(XtT + swzw(dcol, kq, ld)), b1 = *reinterpret_cast<const f32x4*>(XtT + swzw(dcol, 4 + kq, ld));
-  for (int kp = 0; kp < np; ++kp) {
-    const int c = (kp + 1 < np) ? (kp + 1) * 8 + kq : kq;      // (last trip: a harmless re-read)
-    const f32x4 na0 = *reinterpret_cast<const f32x4*>(Wt + swzw(arow, c, ld)), na1 = *reinterpret_cast<const f32x4*>(Wt + swzw(arow, c + 4, ld));
-    const f32x4 nb0 = *reinterpret_cast<const f32x4*>(XtT + swzw(dcol, c, ld)), nb1 = *reinterpret_cast<const f32x4*>(XtT + swzw(dcol, c + 4, ld));
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc = TE_MFMA16(a0[j], b0[j], acc);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc = TE_MFMA16(a1[j], b1[j], acc);
-    __builtin_amdgcn_sched_barrier(0);
-    a0 = na0, a1 = na1, b0 = nb0, b1 = nb1;
-  }
-}
-
-// key-side operand transposed: rows [j0, j0 + nj) of src [.,64] -> LDS [64][256] (element (j, d) at (d, j)), keys
-// >= nj zero
-__device__ __forceinline__ void stage_keys_T(float* __restrict__ KtT, const float* __restrict__ src, int64_t sn, int nj,
-                                             int nj32, int ld) {
-  for (int idx = threadIdx.x; idx < nj32 * 16; idx += kT) {
-    const int row = idx >> 4, c = idx & 15;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row < nj) v = *reinterpret_cast<const f32x4_u*>(src + (int64_t)row * sn + (c << 2));
-#pragma unroll
-    for (int e = 0; e < 4; ++e) KtT[swzw((c << 2) + e, row >> 2, ld) + (row & 3)] = v[e];
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
-// PADDED LDS images of the two rule kernels (the forward producer below keeps the swizzled ones: with k AND v resident it
-// has no room for padding).  [rows][64] tiles have a row stride of SLD = 68 floats, the [TI][keys] tile ALD = 256 (AV:
-// only read 4 bytes per lane along a row) or QLD = 260 (QK: also read as 16-B fragments down 16 rows), the transposed
-// k image [64][QLD].  Every fragment address is then a per-lane base plus a compile-time offset -- no XOR per read, no
+// PADDED LDS images of the rule kernel.  [rows][64] tiles have a row stride of SLD = 68 floats, the [TI][keys] tile
+// QLD = 260 (also read as 16-B fragments down 16 rows), the transposed k image [64][QLD].  Every fragment address is then a per-lane base plus a compile-time offset -- no XOR per read, no
 // address registers -- and the column-side products read their K = query-row operands as 4-byte fragments straight
 // from the row-major tiles, so the TRANSPOSED copies of the tile (64 scalar ds_write_b32 + address arithmetic per
 // thread and tile) are gone.  Vector-ALU instructions are not free beside MFMAs: a CU's time for these rules is the
 // SUM of its MFMA cycles and its other vector-instruction cycles.
 // ------------------------------------------------------------------------------------------------
 constexpr int SLD = 68;
-constexpr int ALD = 256;
 constexpr int QLD = 260;
 
 __device__ __forceinline__ void p_store_wide(float* __restrict__ lds, const WideMap& m, const WideTile& t, int ld) {
 #pragma unroll
   for (int r = 0; r < 4; ++r)
     if (m.row[r] >= 0) *reinterpret_cast<f32x4*>(lds + m.row[r] * ld + (m.c4[r] << 2)) = t.v[r];
-}
-// key-side operand: rows [0, nj) of src [.,64] -> LDS [nj32][SLD], rows >= nj zero
-__device__ __forceinline__ void p_stage_keys(float* __restrict__ Kt, const float* __restrict__ src, int64_t sn, int nj,
-                                             int nj32) {
-  for (int idx = threadIdx.x; idx < nj32 * 16; idx += kT) {
-    const int row = idx >> 4, c = idx & 15;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row < nj) v = *reinterpret_cast<const f32x4_u*>(src + (int64_t)row * sn + (c << 2));
-    *reinterpret_cast<f32x4*>(Kt + row * SLD + (c << 2)) = v;
-  }
 }
 // ... transposed: element (j, d) -> KtT[d][j], lanes along j (conflict-free scalar LDS stores; the 16-B global loads of
 // a wave touch 64 rows, whose other chunks the same wave fetches in its next trips)
@@ -315,32 +203,6 @@ __device__ __forceinline__ void p_stage_keys_T(float* __restrict__ KtT, const fl
 #pragma unroll
       for (int e = 0; e < 4; ++e) KtT[((c << 2) + e) * QLD + row] = v[e];
     }
-  }
-}
-
-// row-side product, 32x32 output block: acc += A[32 x 64] B[32 x 64]^T.  Ap = A + arow * SLD + 4 kh, Bp likewise: the
-// sixteen 16-B fragments sit at Ap + 8 kg / Bp + 8 kg.  All of them are requested before the first MFMA; `between(kg)`
-// runs after the kg-th group of four MFMAs (see row_product32).
-template <class F>
-__device__ __forceinline__ void p_row_product32(f32x16& acc, bool active, const float* __restrict__ Ap,
-                                                const float* __restrict__ Bp, F&& between) {
-  f32x4 a[8], bq[8];
-  if (active) {
-#pragma unroll
-    for (int kg = 0; kg < 8; ++kg) {
-      a[kg] = *reinterpret_cast<const f32x4*>(Ap + 8 * kg);
-      bq[kg] = *reinterpret_cast<const f32x4*>(Bp + 8 * kg);
-    }
-  }
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int kg = 0; kg < 8; ++kg) {
-    if (active) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc = TE_MFMA32(a[kg][j], bq[kg][j], acc);
-    }
-    between(kg);
-    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
@@ -379,12 +241,12 @@ __device__ __forceinline__ void p_col_product(f32x16 (&acc)[2], const float* __r
   }
 }
 
-// out = RAW ? acc : (x . acc) * scale for the column accumulators; x from its padded LDS image Kt [keys][SLD] (XLDS) or
-// from global memory -- all sixteen values of a block requested before the first is used
-template <bool RAW, bool XLDS>
-__device__ __forceinline__ void p_col_epilogue(const f32x16 (&acc)[2], const float* __restrict__ Kt,
-                                               const float* __restrict__ XG, int64_t xsn, float* __restrict__ out,
-                                               int64_t osn, int nj, int wave, int lr, int kh, int nblk, float scale) {
+// out = RAW ? acc : (x . acc) * scale for the column accumulators; x from global memory -- all sixteen values of a block
+// requested before the first is used
+template <bool RAW>
+__device__ __forceinline__ void p_col_epilogue(const f32x16 (&acc)[2], const float* __restrict__ XG, int64_t xsn,
+                                               float* __restrict__ out, int64_t osn, int nj, int wave, int lr, int kh, int nblk,
+                                               float scale) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     const int t = wave + s * kWaves;
@@ -395,8 +257,7 @@ __device__ __forceinline__ void p_col_epilogue(const f32x16 (&acc)[2], const flo
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int j = (t >> 1) * 32 + crow(e, kh);
-          if constexpr (XLDS) x[e] = Kt[j * SLD + d];
-          else x[e] = XG[(int64_t)min(j, nj - 1) * xsn + d];
+          x[e] = XG[(int64_t)min(j, nj - 1) * xsn + d];
         }
       }
 #pragma unroll
@@ -434,14 +295,11 @@ __device__ __forceinline__ void p_row_product16(f32x4& acc, const float* __restr
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// AV rule.  R strided [B,H,N,64]; Z contiguous [B*H,N,64]; attn, cam_attn contiguous [B*H,N,N]; v, cam_v strided.
-// grid = BH * ngroups (bh fastest: with BH a multiple of 8 a (b,h)'s groups share an XCD)
-// ------------------------------------------------------------------------------------------------
 enum { RULE = 0, BWD = 1 };
 
-// Phase timing of workgroup 0 (tuning aid, TE_ATTN_PROF=1 via te_attn_rules_profile()): prof[wave * 8 + phase]
-// accumulates shader-clock cycles between the marks of one tile; nullptr in every normal launch.
+// Phase timing of workgroup 0: prof[wave * 8 + phase] accumulates shader-clock cycles between the marks of one tile.
+// Every launch passes nullptr.  The argument stays because dropping it and its never-taken branches changes the
+// kernel's code (120 instructions, 4 VGPRs): a kernel change that needs its own same-box measurement.
 #define TE_MARK(slot)                                                          \
   do {                                                                         \
     if (prof != nullptr && blockIdx.x == 0 && (threadIdx.x & 63) == 0) {       \
@@ -450,115 +308,6 @@ enum { RULE = 0, BWD = 1 };
       tprev = now__;                                                           \
     }                                                                          \
   } while (0)
-
-template <int MODE>
-__global__ __launch_bounds__(kT) void av_rule_kernel(
-    const float* __restrict__ R, Strided rs, const float* __restrict__ Z, Strided zs, const float* __restrict__ attn,
-    const float* __restrict__ v, Strided vs, float* __restrict__ cam_attn, float* __restrict__ cam_v, Strided cs, int H,
-    int N, int BH, int JG, float scale, long long* __restrict__ prof) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  long long tprev = prof ? clock64() : 0;
-  float* Vt = smem;                    // [JG][SLD]  v of this key group (JG = keys per group: 128 / 192 / 256)
-  float* St = Vt + JG * SLD;           // [TI][SLD]  S: row-side A operand (16-B fragments along d), column-side B operand
-  float* At = St + TI * SLD;           // [TI][ALD]  the attn tile: column-side A operand, and the rule's own factor
-  const int bh = blockIdx.x % BH, g = blockIdx.x / BH;
-  const int b = bh / H, h = bh % H;
-  const int j0 = g * JG, nj = min(JG, N - j0), nj32 = (nj + 31) & ~31, njb = nj32 >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, lr = lane & 31, kh = lane >> 5;
-  const float* r_bh = R + (int64_t)b * rs.sb + (int64_t)h * rs.sh;
-  const float* z_bh = (MODE == RULE) ? Z + (int64_t)b * zs.sb + (int64_t)h * zs.sh : nullptr;
-  const float* a_bh = attn + (int64_t)bh * N * N + j0;
-  float* ca_bh = cam_attn + (int64_t)bh * N * N + j0;
-  const float* v_bh = v + (int64_t)b * vs.sb + (int64_t)h * vs.sh + (int64_t)j0 * vs.sn;
-  const int ntiles = (N + TI - 1) / TI;
-  const WideMap wm = wide_map(nj32 >> 2);
-  const FastMap fm = fast_map(nj32 >> 2, nj32, nj);
-  const int srow = threadIdx.x >> 4, sc = threadIdx.x & 15;      // this thread's float4 of the [32][64] S tile
-
-  WideTile ta;                                  // raw (fast_load) until the tile is consumed
-  f32x4 rr = {0.f, 0.f, 0.f, 0.f}, zz = {0.f, 0.f, 0.f, 0.f};
-  // part p = 0..5 of tile `it`: the four float4 slots of the attn tile, then the R and Z float4 of the S tile
-  // (branch-free: rows beyond N re-read the tile's last row and are zeroed when the tile is consumed)
-  auto fetch_part = [&](int it, int p) __attribute__((always_inline)) {
-    const int i0 = it * TI, rows_valid = min(TI, N - i0);
-    if (p < 4) {
-      if (!fm.fast) ta.v[p] = load_wide_slot(wm, p, a_bh + (int64_t)i0 * N, N, rows_valid, nj);
-      else if (p * kT < fm.nslots) ta.v[p] = fast_load(fm, p, a_bh, i0, N, rows_valid);
-    } else if (p == 4) {
-      rr = *reinterpret_cast<const f32x4_u*>(r_bh + ((unsigned)(i0 + min(srow, rows_valid - 1)) * (unsigned)rs.sn + (unsigned)(sc << 2)));
-    } else if (p == 5) {
-      if constexpr (MODE == RULE)
-        zz = *reinterpret_cast<const f32x4_u*>(z_bh + ((unsigned)(i0 + min(srow, rows_valid - 1)) * (unsigned)zs.sn + (unsigned)(sc << 2)));
-    }
-  };
-#pragma unroll
-  for (int p = 0; p < 6; ++p) fetch_part(0, p);
-  p_stage_keys(Vt, v_bh, vs.sn, nj, nj32);      // (after the requests of tile 0: one HBM round trip for both)
-  f32x16 accv[2];
-  zero16(accv[0]);
-  zero16(accv[1]);
-  for (int it = 0; it < ntiles; ++it) {
-    const int i0 = it * TI;
-    TE_MARK(0);
-    __syncthreads();                       // the previous tile's readers are done (first trip: nothing to wait for)
-    TE_MARK(1);
-    {
-      const int rows_valid = min(TI, N - i0);
-      f32x4 s = rr;                                                  // BWD: the tile of d_out itself
-      if constexpr (MODE == RULE) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[e] = te_sd(rr[e], zz[e]);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s[e] = (srow < rows_valid) ? s[e] : 0.0f;      // rows beyond N
-      *reinterpret_cast<f32x4*>(St + srow * SLD + (sc << 2)) = s;
-      if (fm.fast && !(fm.plain && rows_valid == TI)) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ta.v[r] = fast_fix(fm, r, ta.v[r], nj, rows_valid);
-      }
-      p_store_wide(At, wm, ta, ALD);
-    }
-    TE_MARK(2);
-    __syncthreads();
-    TE_MARK(3);
-    if (it + 1 < ntiles) {
-#pragma unroll
-      for (int p = 0; p < 6; ++p) fetch_part(it + 1, p);
-    }
-    TE_MARK(4);
-    // G = S v^T for key block `wave`; cam_attn = attn . G straight from the accumulators
-    if (wave < njb) {
-      f32x16 gacc;
-      zero16(gacc);
-      const int jl = wave * 32 + lr;
-      p_row_product32(gacc, true, St + lr * SLD + 4 * kh, Vt + jl * SLD + 4 * kh, [](int) {});
-      if constexpr (MODE == RULE) {        // the block's sixteen attention values in one LDS round trip
-        float av[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) av[e] = At[crow(e, kh) * ALD + jl];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) gacc[e] = (av[e] * gacc[e]) * scale;
-      }
-      float* dst = ca_bh + (int64_t)(i0 + 4 * kh) * N + jl;
-      const int nrow = N - i0 - 4 * kh;                       // rows of this half-wave's block that exist
-      if (jl < nj) {
-        if (nrow >= 28) {                                     // every row of the block exists: plain stores
-#pragma unroll
-          for (int e = 0; e < 16; ++e) dst[(int64_t)((e & 3) + 8 * (e >> 2)) * N] = gacc[e];
-        } else {
-#pragma unroll
-          for (int e = 0; e < 16; ++e)
-            if ((e & 3) + 8 * (e >> 2) < nrow) dst[(int64_t)((e & 3) + 8 * (e >> 2)) * N] = gacc[e];
-        }
-      }
-    }
-    TE_MARK(5);
-    p_col_product<ALD>(accv, At + kh * ALD + lr, St + kh * SLD + lr, wave, 2 * njb, (min(TI, N - i0) + 7) >> 3, [](int) {});
-    TE_MARK(6);
-  }
-  float* o_bh = cam_v + (int64_t)b * cs.sb + (int64_t)h * cs.sh + (int64_t)j0 * cs.sn;
-  p_col_epilogue<MODE == BWD, true>(accv, Vt, v_bh, vs.sn, o_bh, cs.sn, nj, wave, lr, kh, 2 * njb, scale);
-}
 
 // ------------------------------------------------------------------------------------------------
 // QK rule.  Rnn, Z contiguous [B*H,N,N]; q, k, cam_q, cam_k strided.  ngroups > 1: cam_q goes to `qpart`
@@ -713,7 +462,7 @@ __global__ __launch_bounds__(kT) void qk_rule_kernel(
     TE_MARK(6);
   }
   float* o_bh = cam_k + (int64_t)b * cks.sb + (int64_t)h * cks.sh + (int64_t)j0 * cks.sn;
-  p_col_epilogue<MODE == BWD, false>(acck, nullptr, k_bh, ks.sn, o_bh, cks.sn, nj, wave, lr, kh, 2 * njb, scale);
+  p_col_epilogue<MODE == BWD>(acck, k_bh, ks.sn, o_bh, cks.sn, nj, wave, lr, kh, 2 * njb, scale);
 }
 
 // cam_q[i,d] = q[i,d] * (sum over groups of qpart[g][bh][i][d], in group order) * scale
@@ -738,157 +487,20 @@ __global__ __launch_bounds__(256) void qk_finish_kernel(const float* __restrict_
   *reinterpret_cast<f32x4_u*>(cam_q + (int64_t)b * cqs.sb + (int64_t)h * cqs.sh + (int64_t)i * cqs.sn + (c << 2)) = o;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Producer: attention forward of one (b, h) on the fused qkv activation [B,N,3C] ('b n (qkv h d)', ViT_LRP.py:135):
-//   z_qk [BH,N,N] = q k^T (unscaled);  attn [BH,N,N] = softmax(z_qk * scale);  out [B,N,C] ('b n (h d)') = attn v
-// N <= 224: k and v (2 x 56 KB) stay in LDS next to the q tile and the [32][256] score tile.
-// ------------------------------------------------------------------------------------------------
+// the attention producers serve N <= 224 (te_attn_fwd6.hip: forward; te_attn_kb.hip, te_attn_rc.hip and qk_rule_kernel<BWD>:
+// backward -- the softmax backward needs every key of a row in one group)
 constexpr int NJF = 224;
-__global__ __launch_bounds__(kT) void attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ zqk,
-                                                      float* __restrict__ attn, float* __restrict__ out, int H, int N,
-                                                      float scale) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* Kt = smem;                    // [NJF][64]   k (row-side B operand of q k^T, K = d contiguous)
-  float* VtT = Kt + NJF * 64;          // [64][256]   v TRANSPOSED (row-side B operand of P v, K = key contiguous)
-  float* Qt = VtT + 64 * WLD;          // [TI][64]
-  float* Wt = Qt + TI * 64;            // [TI][256]: scaled scores, then probabilities
-  const int bh = blockIdx.x, b = bh / H, h = bh % H;
-  const int C = H * 64;
-  const int64_t sn = 3 * (int64_t)C;
-  const int nj = N, nj32 = (nj + 31) & ~31, njb = nj32 >> 5;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 31, kh = lane >> 5;
-  const float* q_bh = qkv + (int64_t)b * N * sn + h * 64;
-  const float* k_bh = q_bh + C;
-  const float* v_bh = q_bh + 2 * C;
-  float* z_bh = zqk + (int64_t)bh * N * N;
-  float* a_bh = attn + (int64_t)bh * N * N;
-  float* o_bh = out + (int64_t)b * N * C + h * 64;
-  const int ntiles = (N + TI - 1) / TI;
-  const int srow = threadIdx.x >> 4, sc = threadIdx.x & 15;
-  f32x4 qq = {0.f, 0.f, 0.f, 0.f};
-  auto fetch = [&](int it) __attribute__((always_inline)) {
-    const int i0 = it * TI;
-    qq = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (i0 + srow < N) qq = *reinterpret_cast<const f32x4_u*>(q_bh + (int64_t)(i0 + srow) * sn + (sc << 2));
-  };
-  fetch(0);
-  stage_keys(Kt, k_bh, sn, nj, nj32);
-  stage_keys_T(VtT, v_bh, sn, nj, nj32, WLD);
-  const int ib = wave >> 2, db = wave & 3, l15 = lane & 15, kq = lane >> 4;
-  for (int it = 0; it < ntiles; ++it) {
-    const int i0 = it * TI;
-    __syncthreads();                           // previous tile's readers of Qt / Wt are done
-    *reinterpret_cast<f32x4*>(Qt + swz64(srow, sc)) = qq;
-    __syncthreads();
-    if (it + 1 < ntiles) fetch(it + 1);
-    if (wave < njb) {
-      // scores of key block `wave`: z = q k^T
-      f32x16 z;
-      zero16(z);
-      row_product32(z, true, Qt, lr, Kt, wave * 32 + lr, kh, [](int) {});
-      const int jl = wave * 32 + lr;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) Wt[swzw(crow(e, kh), jl >> 2) + (jl & 3)] = z[e];      // unscaled scores
-    }
-    __syncthreads();
-    {
-      // row softmax over the nj valid columns: 16 lanes per row, float4 chunks sc + 16 m
-      f32x4 x[4];
-      float mx = -INFINITY;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int c = sc + 16 * m;
-        x[m] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        if (c * 4 < nj32) {
-          x[m] = *reinterpret_cast<const f32x4*>(Wt + swzw(srow, c));
-          // z_qk leaves as whole-row 16-B stores from here (the accumulator layout would need a dword store per element)
-          if (i0 + srow < N) {
-            float* zdst = z_bh + (int64_t)(i0 + srow) * N + c * 4;
-            if (c * 4 + 3 < nj) {
-              *reinterpret_cast<f32x4_u*>(zdst) = x[m];
-            } else {
-#pragma unroll
-              for (int e = 0; e < 4; ++e)
-                if (c * 4 + e < nj) zdst[e] = x[m][e];
-            }
-          }
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            x[m][e] = (c * 4 + e < nj) ? x[m][e] * scale : -INFINITY;      // 'dots = einsum(...) * self.scale' (ViT_LRP.py:139)
-            mx = fmaxf(mx, x[m][e]);
-          }
-        }
-      }
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-      float sum = 0.0f;
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          x[m][e] = expf(x[m][e] - mx);                    // exp(-inf) = 0 for the padded columns
-          sum = sum + x[m][e];
-        }
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) sum = sum + __shfl_xor(sum, off, 64);
-      const bool row_ok = i0 + srow < N;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int c = sc + 16 * m;
-        if (c * 4 < nj32) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) x[m][e] = x[m][e] / sum;
-          *reinterpret_cast<f32x4*>(Wt + swzw(srow, c)) = x[m];
-          if (row_ok) {
-            float* dst = a_bh + (int64_t)(i0 + srow) * N;
-            if (c * 4 + 3 < nj) {
-              *reinterpret_cast<f32x4_u*>(dst + c * 4) = x[m];
-            } else {
-#pragma unroll
-              for (int e = 0; e < 4; ++e)
-                if (c * 4 + e < nj) dst[c * 4 + e] = x[m][e];
-            }
-          }
-        }
-      }
-    }
-    __syncthreads();
-    {
-      // out block (ib, db) = P[16 x keys] v[keys x 16]
-      f32x4 o = {0.f, 0.f, 0.f, 0.f};
-      const int arow = ib * 16 + l15, dcol = db * 16 + l15;
-      row_product16(o, Wt, arow, VtT, dcol, kq, nj32, WLD);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int il = ib * 16 + kq * 4 + r;
-        if (i0 + il < N) o_bh[(int64_t)(i0 + il) * C + dcol] = o[r];
-      }
-    }
-  }
-}
 
-inline size_t lds_av(int jg) { return (size_t)(jg * SLD + TI * SLD + TI * ALD) * sizeof(float); }      // 109 KB at 256 keys
 inline size_t lds_qk(int /*jg*/, bool bwd) {                                                          // 106 (114) KB
   return (size_t)(64 * QLD + TI * SLD + TI * QLD + (bwd ? TI * 64 : 0)) * sizeof(float);
 }
-constexpr size_t kLdsFwd = (size_t)(NJF * 64 + 64 * WLD + TI * 64 + TI * WLD) * sizeof(float);   // 160 KB: all of a CU's LDS
 
 // Keys per workgroup: 256 (one 112-136 KB workgroup per CU).  Groups of 128 keys (64-72 KB: two workgroups per CU) were
 // measured SLOWER on the MI355X (ViT-B B=64: AV 202 vs 170 us, QK 319 vs 257 us; N = 577 / 512 alike): the time of a
 // row tile is dominated by per-tile costs that do not shrink with the tile, so halving the keys
-// doubles them.  TE_ATTN_JG = 128 | 192 | 256 pins the group size (tuning).
-inline void groups_for(int64_t N, int& ng, int& jg, int jmax = 0) {
-#ifdef TE_STUDY      // measurement builds only: the shipped library reads no environment
-  static const int pinned = [] {
-    const char* e = getenv("TE_ATTN_JG");
-    const int v = e ? atoi(e) : 0;
-    return (v == 128 || v == 192 || v == 256) ? v : 0;
-  }();
-#else
-  constexpr int pinned = 0;
-#endif
-  if (jmax == 0) jmax = pinned ? pinned : 256;
-  ng = (int)((N + jmax - 1) / jmax);
+// doubles them.
+inline void groups_for(int64_t N, int& ng, int& jg) {
+  ng = (int)((N + 255) / 256);
   jg = (int)(((N + ng - 1) / ng + 63) & ~(int64_t)63);      // equal groups, whole 64-key units (the LDS row stride)
 }
 
@@ -899,100 +511,11 @@ inline void allow_lds(K kern, size_t bytes) {
 
 }  // namespace
 
-// tuning aid: device buffer of 2 x 64 counters (AV kernel, QK kernel) the next launches accumulate into; NULL = off
-#ifdef TE_STUDY      // measurement builds only (scripts/attn_phase_profile.py): the shipped library has no mutable globals
-static long long* g_prof = nullptr;
-}  // namespace te_attn_rules
-extern "C" void te_attn_rules_profile(long long* device_buffer) { te_attn_rules::g_prof = device_buffer; }
-namespace te_attn_rules {
-#else
-static long long* const g_prof = nullptr;
-#endif
-
-bool enabled() {
-  // TE_ATTN_IMPL=tiles selects the 64 x 64-tile kernels of te_attn_mfma.hip (kept as the on-device cross-check)
-#ifdef TE_STUDY
-  static const bool on = [] {
-    const char* e = getenv("TE_ATTN_IMPL");
-    return !(e && !strcmp(e, "tiles"));
-  }();
-  return on;
-#else
-  return true;
-#endif
-}
-
-// which AV kernels run: 1 (default) = te_attn_kb.hip (wave-owned key blocks), 0 = av_rule_kernel above (round 2).
-// TE_ATTN_AV=old selects the round-2 kernel in measurement builds (-DTE_STUDY) for same-box A/B runs.
-static bool use_kb_av() {
-#ifdef TE_STUDY
-  static const bool on = [] {
-    const char* e = getenv("TE_ATTN_AV");
-    return !(e && !strcmp(e, "old"));
-  }();
-  return on;
-#else
-  return true;
-#endif
-}
-
-// The QK rule on wave-owned key blocks (te_attn_kb.hip: qk6_kb_kernel) is a STUDY: TE_ATTN_QK=x6 in measurement builds.
-// Round 5: correct in every parity test, but 2 of 10 replays of the ViT-B step differed from the serial step in the last bits
-// of one sample -- hipcc had moved a register with a hidden load in flight above its wait and onto the loop back-edge.
-// Fixed (30 of 30 replays bitwise since; scripts/check_hidden_loads.py guards the class), and with that 5-8 % faster than
-// qk_rule_kernel below (172-178 vs 182-192 us at N = 197): its row product is a partial sum per wave that meets in LDS, 900
-// instructions per tile and wave against the AV kernel's 570 -- not enough to replace the kernel every test has run on.
-static bool use_kb_qk() {
-#ifdef TE_STUDY
-  static const bool on = [] {
-    const char* e = getenv("TE_ATTN_QK");
-    return e && !strcmp(e, "x6");
-  }();
-  return on;
-#else
-  return false;
-#endif
-}
-
-// which QK-rule / softmax-backward kernels run at N <= 224: 1 (default) = te_attn_rc.hip (row-block and key-block owners, bf16
-// MFMAs on split operands), 0 = qk_rule_kernel above (round 2).  TE_ATTN_QK=old selects the round-2 kernel in measurement
-// builds (-DTE_STUDY) for same-box A/B runs.
-static bool use_rc_qk() {
-#ifdef TE_STUDY
-  static const bool on = [] {
-    const char* e = getenv("TE_ATTN_QK");
-    return !(e && (!strcmp(e, "old") || !strcmp(e, "x6")));
-  }();
-  return on;
-#else
-  return true;
-#endif
-}
-
 // The softmax half of the backward pass on te_attn_rc.hip: measured against qk_rule_kernel<BWD> on one box (profiles/
 // r06_attention_qk_rc_ab.log) it wins below ~160 tokens (69 vs 75 us at N = 128), ties at 224 and LOSES at 197 (the headline:
-// 272 vs 257 us for the whole backward pair -- its separate rowdot pass over the row panels), so it serves N <= 160 only;
-// TE_ATTN_QK=rc_bwd forces it in measurement builds.
-static bool use_rc_bwd(int64_t N) {
-#ifdef TE_STUDY
-  static const int forced = [] {
-    const char* e = getenv("TE_ATTN_QK");
-    return (e && !strcmp(e, "rc_bwd")) ? 1 : (e && (!strcmp(e, "old") || !strcmp(e, "x6"))) ? -1 : 0;
-  }();
-  if (forced) return forced > 0;
-#endif
-  return N <= 160;
-}
-
-// With the forward output at hand (te_attention_backward_out_f32) the rc kernel's row dots cost nothing and it serves every N <= 224;
-// TE_ATTN_QK=old keeps the round-2 kernel in measurement builds.
-static bool use_rc_bwd_out(bool have_out) {
-#ifdef TE_STUDY
-  static const bool old_only = [] { const char* e = getenv("TE_ATTN_QK"); return e && !strcmp(e, "old"); }();
-  if (old_only) return false;
-#endif
-  return have_out;
-}
+// 272 vs 257 us for the whole backward pair -- its separate rowdot pass over the row panels), so it serves N <= 160 only.
+// With the forward output at hand (te_attention_backward_out_f32) its row dots cost nothing and it serves every N <= 224.
+static bool use_rc_bwd(int64_t N) { return N <= 160; }
 
 bool supported(int64_t B, int64_t H, int64_t N, int64_t D) {
   int ng, jg;
@@ -1001,22 +524,14 @@ bool supported(int64_t B, int64_t H, int64_t N, int64_t D) {
   return D == 64 && N >= 1 && N <= 4096 && B * H * ng <= 0x7fffffff;
 }
 
+// (te_attn_kb::supported accepts every shape supported() accepts: the AV rule always runs on wave-owned key blocks)
 int av_launch(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const float* attn, const float* v, int64_t v_sb,
               int64_t v_sh, int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn, float* cam_attn,
               float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn, int64_t B, int64_t H, int64_t N, float scale,
               hipStream_t stream) {
-  int ng, jg;
-  groups_for(N, ng, jg);
-  const int BH = (int)(B * H);
   if (r_sn > 65536 || z_sn > 65536) return TE_ERR_UNSUPPORTED;      // 32-bit row offsets inside a (b, h) view
-  if (use_kb_av() && te_attn_kb::supported(B, H, N, 64))
-    return te_attn_kb::av_launch(0, R, r_sb, r_sh, r_sn, attn, v, v_sb, v_sh, v_sn, Z, z_sb, z_sh, z_sn, cam_attn, cam_v, cv_sb,
-                                 cv_sh, cv_sn, B, H, N, scale, stream);
-  allow_lds(av_rule_kernel<RULE>, lds_av(256));
-  av_rule_kernel<RULE><<<dim3((unsigned)(BH * ng)), dim3(kT), lds_av(jg), stream>>>(
-      R, Strided{r_sb, r_sh, r_sn}, Z, Strided{z_sb, z_sh, z_sn}, attn, v, Strided{v_sb, v_sh, v_sn}, cam_attn, cam_v,
-      Strided{cv_sb, cv_sh, cv_sn}, (int)H, (int)N, BH, jg, scale, g_prof);
-  return TE_OK;
+  return te_attn_kb::av_launch(0, R, r_sb, r_sh, r_sn, attn, v, v_sb, v_sh, v_sn, Z, z_sb, z_sh, z_sn, cam_attn, cam_v, cv_sb,
+                               cv_sh, cv_sn, B, H, N, scale, stream);
 }
 
 int qk_launch(const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb,
@@ -1027,27 +542,14 @@ int qk_launch(const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int6
   groups_for(N, ng, jg);
   const int BH = (int)(B * H);
   if (q_sn > 65536) return TE_ERR_UNSUPPORTED;                       // 32-bit row offsets inside a (b, h) view
-  if (use_rc_qk() && te_attn_rc::supported(B, H, N, 64))
+  if (te_attn_rc::supported(B, H, N, 64))
     return te_attn_rc::qk_launch(0, Rnn, q, q_sb, q_sh, q_sn, k, k_sb, k_sh, k_sn, Z, cam_q, cq_sb, cq_sh, cq_sn, cam_k, ck_sb, ck_sh,
                                  ck_sn, B, H, N, scale, r_scale, r_scale_stride, stream);
-  if (use_kb_qk() && te_attn_kb::supported(B, H, N, 64)) {
-    const Strided qs{q_sb, q_sh, q_sn}, cqs{cq_sb, cq_sh, cq_sn};
-    int kng = 1;
-    int rc = te_attn_kb::qk_launch(Rnn, q, q_sb, q_sh, q_sn, k, k_sb, k_sh, k_sn, Z, cam_q, cq_sb, cq_sh, cq_sn, cam_k, ck_sb,
-                                   ck_sh, ck_sn, B, H, N, scale, qpart, r_scale, r_scale_stride, &kng, stream);
-    if (rc != TE_OK) return rc;
-    if (kng > 1) {
-      const int64_t n4 = (int64_t)BH * N * 16;
-      qk_finish_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream>>>(qpart, q, qs, cam_q, cqs, (int)H, (int)N,
-                                                                                    BH, kng, scale);
-    }
-    return TE_OK;
-  }
   allow_lds(qk_rule_kernel<RULE>, lds_qk(256, false));
   const Strided qs{q_sb, q_sh, q_sn}, ks{k_sb, k_sh, k_sn}, cqs{cq_sb, cq_sh, cq_sn}, cks{ck_sb, ck_sh, ck_sn};
   qk_rule_kernel<RULE><<<dim3((unsigned)(BH * ng)), dim3(kT), lds_qk(jg, false), stream>>>(Rnn, Z, q, qs, k, ks, cam_q, cqs, cam_k,
                                                                               cks, qpart, (int)H, (int)N, BH, jg, ng,
-                                                                              scale, g_prof ? g_prof + 64 : nullptr, r_scale,
+                                                                              scale, nullptr, r_scale,
                                                                               r_scale_stride);
   if (ng > 1) {
     const int64_t n4 = (int64_t)BH * N * 16;
@@ -1072,21 +574,9 @@ extern "C" int te_attention_forward_f32(const float* qkv, float* z_qk, float* at
                                         int64_t N, int64_t D, float scale, te_stream_t stream_) {
   if (!qkv || !z_qk || !attn || !out || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
   if (!te_attention_forward_supported(N, D) || B * H > 0x7fffffff) return TE_ERR_UNSUPPORTED;
-  hipStream_t stream = (hipStream_t)stream_;
-#ifdef TE_STUDY      // TE_ATTN_FWD=old selects the round-2 kernel in measurement builds for same-box A/B runs
-  static const bool old_fwd = [] { const char* e = getenv("TE_ATTN_FWD"); return e && !strcmp(e, "old"); }();
-#else
-  constexpr bool old_fwd = false;
-#endif
-  if (!old_fwd && te_attn_fwd6::supported(B, H, N, D)) {
-    const int rc = te_attn_fwd6::launch(qkv, z_qk, attn, out, B, H, N, scale, stream);
-    if (rc != TE_OK) return rc;
-    TE_RETURN_IF_LAUNCH_FAILED();
-    return TE_OK;
-  }
-  te_attn_rules::allow_lds(te_attn_rules::attn_fwd_kernel, te_attn_rules::kLdsFwd);
-  te_attn_rules::attn_fwd_kernel<<<dim3((unsigned)(B * H)), dim3(te_attn_rules::kT), te_attn_rules::kLdsFwd, stream>>>(
-      qkv, z_qk, attn, out, (int)H, (int)N, scale);
+  // (te_attn_fwd6::supported covers every shape accepted above)
+  const int rc = te_attn_fwd6::launch(qkv, z_qk, attn, out, B, H, N, scale, (hipStream_t)stream_);
+  if (rc != TE_OK) return rc;
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
 }
@@ -1105,23 +595,16 @@ static int attention_backward_impl(const float* d_out, const float* out, const f
   const Strided heads{N * C, 64, C};            // [B,N,C] seen as [B,H,N,64]
   const Strided fused{N * 3 * C, 64, 3 * C};    // one of q / k / v inside [B,N,3C]
   int ng, jg;
-  groups_for(N, ng, jg, 256);                   // N <= 224: one group (the softmax backward needs every key of a row)
+  groups_for(N, ng, jg);                        // N <= 224: one group (the softmax backward needs every key of a row)
   // d_attn = d_out v^T ; d_v = attn^T d_out
-  if (use_kb_av() && te_attn_kb::supported(B, H, N, 64)) {
-    int rc = te_attn_kb::av_launch(1, d_out, heads.sb, heads.sh, heads.sn, attn, qkv + 2 * C, fused.sb, fused.sh, fused.sn,
-                                   nullptr, 0, 0, 0, d_attn, d_qkv + 2 * C, fused.sb, fused.sh, fused.sn, B, H, N, 1.0f, stream);
-    if (rc != TE_OK) return rc;
-  } else {
-    allow_lds(av_rule_kernel<BWD>, lds_av(256));
-    av_rule_kernel<BWD><<<dim3((unsigned)BH), dim3(kT), lds_av(jg), stream>>>(d_out, heads, nullptr, Strided{0, 0, 0}, attn,
-                                                                        qkv + 2 * C, fused, d_attn, d_qkv + 2 * C, fused,
-                                                                        (int)H, (int)N, BH, jg, 1.0f, nullptr);
-  }
-  if (need_qk && (use_rc_bwd(N) || use_rc_bwd_out(out != nullptr)) && te_attn_rc::supported(B, H, N, 64)) {
+  int rc = te_attn_kb::av_launch(1, d_out, heads.sb, heads.sh, heads.sn, attn, qkv + 2 * C, fused.sb, fused.sh, fused.sn, nullptr,
+                                 0, 0, 0, d_attn, d_qkv + 2 * C, fused.sb, fused.sh, fused.sn, B, H, N, 1.0f, stream);
+  if (rc != TE_OK) return rc;
+  if (need_qk && (use_rc_bwd(N) || out != nullptr) && te_attn_rc::supported(B, H, N, 64)) {
     // d_s = softmax backward * scale ; d_q = d_s k ; d_k = d_s^T q   (te_attn_rc.hip)
-    int rc = te_attn_rc::qk_launch(1, d_attn, qkv, fused.sb, fused.sh, fused.sn, qkv + C, fused.sb, fused.sh, fused.sn, attn, d_qkv,
-                                   fused.sb, fused.sh, fused.sn, d_qkv + C, fused.sb, fused.sh, fused.sn, B, H, N, scale, nullptr, 0,
-                                   stream, out ? d_out : nullptr, out, heads.sb, heads.sh, heads.sn);
+    rc = te_attn_rc::qk_launch(1, d_attn, qkv, fused.sb, fused.sh, fused.sn, qkv + C, fused.sb, fused.sh, fused.sn, attn, d_qkv,
+                               fused.sb, fused.sh, fused.sn, d_qkv + C, fused.sb, fused.sh, fused.sn, B, H, N, scale, nullptr, 0,
+                               stream, out ? d_out : nullptr, out, heads.sb, heads.sh, heads.sn);
     if (rc != TE_OK) return rc;
   } else if (need_qk) {
     // d_s = softmax backward * scale ; d_q = d_s k ; d_k = d_s^T q

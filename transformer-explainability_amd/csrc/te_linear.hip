@@ -43,8 +43,6 @@
 //
 // Odd shapes (in_f or out_f not a multiple of 4, or forced by TE_IMPL_SIMPLE) use plain one-thread-per-output
 // kernels; they double as the on-device cross-check for the tiled path.
-#include <stdlib.h>
-#include <string.h>
 
 #include <type_traits>
 
@@ -165,37 +163,6 @@ __device__ __forceinline__ void load_kn_tile_fast(const float* __restrict__ M, i
   for (int i = 0; i < BN / 32; ++i) reg[i] = *reinterpret_cast<const f32x4*>(p + (int64_t)i * RPI * Nn);
 }
 
-// Direct-to-LDS staging (global_load_lds_dwordx4: 64 lanes x 16 B land at a wave-uniform LDS base + lane * 16, no VGPR
-// round trip, no ds_write): the LDS images above are lane-linear in the thread index (float4 slot idx = t + 256 i sits
-// at float offset 4 idx), so the XOR swizzle of the K-contiguous tile moves to the SOURCE address -- lane (row, physical
-// chunk pc) fetches logical chunk pc ^ ((row >> 1) & 7) of its row; the eight lanes of a row still read one 128-B line.
-__device__ __forceinline__ void glds16(const float* __restrict__ src, float* __restrict__ lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-template <int ROWS>
-__device__ __forceinline__ void glds_rows_tile(float* __restrict__ lds, const float* __restrict__ M, int64_t K,
-                                               int64_t row0, int64_t k0, int wave_base) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int i = 0; i < ROWS / 32; ++i) {
-    const int idx = wave_base + lane + i * kThreads;
-    const int row = idx >> 3, lc = (idx & 7) ^ ((row >> 1) & 7);
-    glds16(M + (row0 + row) * K + k0 + (lc << 2), lds + (wave_base + i * kThreads) * 4);
-  }
-}
-template <int BN>
-__device__ __forceinline__ void glds_kn_tile(float* __restrict__ lds, const float* __restrict__ M, int64_t Nn, int64_t k0,
-                                             int64_t n0, int wave_base) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int i = 0; i < BN / 32; ++i) {
-    const int idx = wave_base + lane + i * kThreads;
-    const int kk = idx / (BN / 4), c4 = idx % (BN / 4);
-    glds16(M + (k0 + kk) * Nn + n0 + (c4 << 2), lds + (wave_base + i * kThreads) * 4);
-  }
-}
-
 // K-loop schedule shared by both kernels (one K-step = 4 k-groups of 8):
 //
 //     k-group 0 : MFMAs on fragments read during the PREVIOUS step's last group   | reads of group 1
@@ -254,7 +221,7 @@ __device__ __forceinline__ void row_factors(const RowScale& rs, int64_t gr0, int
   }
 }
 
-template <int ZM, bool SWAP, int BM, int BN, int VAR = 0>
+template <int ZM, bool SWAP, int BM, int BN>
 __global__ __launch_bounds__(kThreads, 2) void linear_k1_kernel(
     const float* __restrict__ X, const float* __restrict__ W, const float* __restrict__ R,
     const float* __restrict__ Y, const float* __restrict__ bias,
@@ -303,7 +270,7 @@ __global__ __launch_bounds__(kThreads, 2) void linear_k1_kernel(
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if constexpr (FWD) {
-        // |X| and |W| were formed when the tiles were staged (abs_regs): a plain GEMM inner loop, no VALU
+        // |X| and |W| were formed when the tiles were staged (abs_store): a plain GEMM inner loop, no VALU
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -346,24 +313,13 @@ __global__ __launch_bounds__(kThreads, 2) void linear_k1_kernel(
         load_rows_tile<BN>(W, Nn, K, tc.col0, (int64_t)kt * BK, rb);
       }
     };
-    // one-product Z-pass: the operands are |X| and |W|; clearing the sign bits once per staged element (6 VALU ops
-    // per thread and K-step, next to the LDS stores) instead of once per fragment use inside the MFMA stream
-    auto abs_regs = [&]() __attribute__((always_inline)) {
-      if constexpr (FWD) {
-#pragma unroll
-        for (int i = 0; i < BM / 32; ++i)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ra[i][e] = te_abs(ra[i][e]);
-#pragma unroll
-        for (int i = 0; i < BN / 32; ++i)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) rb[i][e] = te_abs(rb[i][e]);
-      }
-    };
-    if constexpr (FWD && (VAR == 2)) {
-      // prefetch distance 2: two register stages; the loads of K-step kt+2 are issued right after the barrier that
+    if constexpr (FWD) {
+      // one-product Z-pass: the operands are |X| and |W|; the sign bits are cleared once per staged element (6 VALU
+      // ops per thread and K-step, next to the LDS stores) instead of once per fragment use inside the MFMA stream.
+      // Prefetch distance 2: two register stages; the loads of K-step kt+2 are issued right after the barrier that
       // published step kt+1 and are consumed (abs + ds_write) at the end of step kt+1 -- two K-steps of MFMAs cover
-      // one global round trip instead of three quarters of one
+      // one global round trip instead of three quarters of one (with the batched epilogue below: -6.3 % against
+      // distance 1 and a per-element epilogue, profiles/r01_zfwd_variants.log)
       f32x4 qa[BM / 32], qb[BN / 32];
       auto load_into = [&](int kt, f32x4 (&xa)[BM / 32], f32x4 (&xb)[BN / 32]) __attribute__((always_inline)) {
         if constexpr (FAST) {
@@ -449,7 +405,6 @@ __global__ __launch_bounds__(kThreads, 2) void linear_k1_kernel(
       return;
     }
     load_next(0);
-    abs_regs();
     store_rows_tile<BM>(smem, ra);
     store_rows_tile<BN>(smem + A_SZ, rb);
     __syncthreads();
@@ -469,7 +424,6 @@ __global__ __launch_bounds__(kThreads, 2) void linear_k1_kernel(
       mma_group(f0);
       __builtin_amdgcn_sched_barrier(0);
       if (more) {
-        abs_regs();
         store_rows_tile<BM>(smem + (cur ^ 1) * STAGE, ra);
         store_rows_tile<BN>(smem + (cur ^ 1) * STAGE + A_SZ, rb);
         __syncthreads();
@@ -484,7 +438,7 @@ __global__ __launch_bounds__(kThreads, 2) void linear_k1_kernel(
   else k_loop(std::false_type{});
 
   // Epilogue.  C/D layout of the 32x32 MFMA: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5).
-  if constexpr (FWD && VAR >= 1) {
+  if constexpr (FWD) {
     if (interior) {
       // all 32 loads of a 32x32 block in flight before the first use (the generic loop below waits per element:
       // its rare exact_z call sits between consecutive loads)
@@ -557,7 +511,7 @@ __global__ __launch_bounds__(kThreads, 2) void linear_k1_kernel(
 //             products P = S W+, N = S W-, epilogue out = x (P + N) - l_b P - h_b N with x read from / out written
 //             to the NCHW image through the patch geometry (no im2col copy); l_b, h_b = sample b's pixel min / max
 // ------------------------------------------------------------------------------------------------
-template <int MODE, bool SWAP, bool ACCUM, int BM, int BN, bool GLDS = false>
+template <int MODE, bool SWAP, bool ACCUM, int BM, int BN>
 __global__ __launch_bounds__(kThreads, 2) void linear_k2_kernel(
     const float* __restrict__ S, const float* __restrict__ W, const float* __restrict__ X,
     float* __restrict__ out, int64_t T, int64_t K, int64_t Nn, int nbn, int ntiles, float scale, TeZbGeom zb) {
@@ -628,41 +582,6 @@ __global__ __launch_bounds__(kThreads, 2) void linear_k2_kernel(
 
   auto k_loop = [&](auto fast_tag) __attribute__((always_inline)) {
     constexpr bool FAST = decltype(fast_tag)::value;
-    if constexpr (FAST && GLDS) {
-      // interior tiles, direct-to-LDS staging: the next K-step's tiles are requested at the top of the step (its
-      // stage was released by the barrier that ended the previous step) and are waited for by the step's one barrier
-      const int wave_base = __builtin_amdgcn_readfirstlane(threadIdx.x & ~63);
-      auto stage = [&](int st, int kt) __attribute__((always_inline)) {
-        glds_rows_tile<BM>(smem + st * STAGE, S, K, tc.row0, (int64_t)kt * BK, wave_base);
-        glds_kn_tile<BN>(smem + st * STAGE + A_SZ, W, Nn, (int64_t)kt * BK, tc.col0, wave_base);
-      };
-      stage(0, 0);
-      __syncthreads();
-      Frag f0, f1;
-      read_frag(f0, 0, 0);
-      int cur = 0;
-      for (int kt = 0; kt < nk; ++kt) {
-        const bool more = kt + 1 < nk;
-        if (more) stage(cur ^ 1, kt + 1);
-        read_frag(f1, cur, 1);
-        mma_group(f0);
-        __builtin_amdgcn_sched_barrier(0);
-        read_frag(f0, cur, 2);
-        mma_group(f1);
-        __builtin_amdgcn_sched_barrier(0);
-        read_frag(f1, cur, 3);
-        mma_group(f0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (more) {
-          __syncthreads();
-          read_frag(f0, cur ^ 1, 0);
-        }
-        mma_group(f1);
-        __builtin_amdgcn_sched_barrier(0);
-        cur ^= 1;
-      }
-      return;
-    }
     f32x4 ra[BM / 32], rb[BN / 32];
     auto load_next = [&](int kt) __attribute__((always_inline)) {
       if constexpr (FAST) {
@@ -828,19 +747,8 @@ enum Tile { TILE_128x128 = 0, TILE_128x64 = 1, TILE_64x64 = 2 };
 // Tile choice per launch.  A launch whose tile count is just above a multiple of the CU count wastes most of its
 // last round: 12,608 x 768 outputs are 594 tiles of 128x128 = 2.32 per CU (the third round a third full) but 1188
 // of 128x64 = 4.64 per CU.  Estimated chip efficiency of a tile = (tiles / CUs) / ceil(tiles / CUs) x a per-tile
-// factor; the best estimate wins.  TE_LINEAR_TILE = 128x128 | 128x64 | 64x64 pins the choice (tuning).
+// factor; the best estimate wins.
 inline Tile pick_tile(int64_t T, int64_t n_out, bool one_product = false) {
-#ifdef TE_STUDY      // measurement builds only (TE_BUILD_DEFINES=TE_STUDY): the shipped library reads no environment
-  static const int pinned = [] {
-    const char* e = getenv("TE_LINEAR_TILE");
-    if (!e) return -1;
-    if (!strcmp(e, "128x128")) return (int)TILE_128x128;
-    if (!strcmp(e, "128x64")) return (int)TILE_128x64;
-    if (!strcmp(e, "64x64")) return (int)TILE_64x64;
-    return -1;
-  }();
-  if (pinned >= 0) return (Tile)pinned;
-#endif
   auto eff = [&](int bm, int bn, double factor) {
     const int64_t tiles = te_ceil_div(T, bm) * te_ceil_div(n_out, bn);
     return factor * ((double)tiles / kCUs) / (double)te_ceil_div(tiles, kCUs);
@@ -854,37 +762,16 @@ inline Tile pick_tile(int64_t T, int64_t n_out, bool one_product = false) {
   return (e1 > e0) ? TILE_128x64 : TILE_128x128;
 }
 
-template <int ZM, bool SWAP, int BM, int BN, int VAR = 0>
-inline void launch_k1v(const float* X, const float* W, const float* R, const float* Y, const float* bias, float* S1,
-                       float* S2, int64_t T, int64_t in_f, int64_t out_f, hipStream_t stream, RowScale rs) {
-  const int nbn = (int)te_ceil_div(out_f, BN);
-  const int ntiles = (int)te_ceil_div(T, BM) * nbn;
-  constexpr size_t lds = k1_lds<BM, BN>();
-  allow_lds(linear_k1_kernel<ZM, SWAP, BM, BN, VAR>, lds);
-  linear_k1_kernel<ZM, SWAP, BM, BN, VAR><<<dim3((unsigned)ntiles), dim3(kThreads), lds, stream>>>(
-      X, W, R, Y, bias, S1, S2, T, in_f, out_f, nbn, ntiles, rs);
-}
 template <int ZM, bool SWAP, int BM, int BN>
 inline void launch_k1(const float* X, const float* W, const float* R, const float* Y, const float* bias, float* S1,
                       float* S2, int64_t T, int64_t in_f, int64_t out_f, hipStream_t stream,
                       RowScale rs = RowScale{nullptr, 0, 1}) {
-  if constexpr (ZM == ZM_FWD) {
-    // TE_ZFWD_VARIANT (tuning study, profiles/r01_zfwd_variants.log): 0 = per-element epilogue, distance-1 prefetch;
-    // 1 = batched epilogue loads (-3.5 %); 2 = 1 + prefetch distance 2 (-6.3 %, default)
-#ifdef TE_STUDY      // variants 0 / 1 (one of which spills) exist in measurement builds only
-    static const int var = [] {
-      const char* e = getenv("TE_ZFWD_VARIANT");
-      return e ? atoi(e) : 2;
-    }();
-    switch (var) {
-      case 0: return launch_k1v<ZM, SWAP, BM, BN, 0>(X, W, R, Y, bias, S1, S2, T, in_f, out_f, stream, rs);
-      case 1: return launch_k1v<ZM, SWAP, BM, BN, 1>(X, W, R, Y, bias, S1, S2, T, in_f, out_f, stream, rs);
-      default: break;
-    }
-#endif
-    return launch_k1v<ZM, SWAP, BM, BN, 2>(X, W, R, Y, bias, S1, S2, T, in_f, out_f, stream, rs);
-  }
-  launch_k1v<ZM, SWAP, BM, BN, 0>(X, W, R, Y, bias, S1, S2, T, in_f, out_f, stream, rs);
+  const int nbn = (int)te_ceil_div(out_f, BN);
+  const int ntiles = (int)te_ceil_div(T, BM) * nbn;
+  constexpr size_t lds = k1_lds<BM, BN>();
+  allow_lds(linear_k1_kernel<ZM, SWAP, BM, BN>, lds);
+  linear_k1_kernel<ZM, SWAP, BM, BN><<<dim3((unsigned)ntiles), dim3(kThreads), lds, stream>>>(
+      X, W, R, Y, bias, S1, S2, T, in_f, out_f, nbn, ntiles, rs);
 }
 template <int MODE, bool SWAP, bool ACCUM, int BM, int BN>
 inline void launch_k2(const float* S, const float* W, const float* X, float* out, int64_t T, int64_t in_f,
@@ -892,20 +779,6 @@ inline void launch_k2(const float* S, const float* W, const float* X, float* out
   const int nbn = (int)te_ceil_div(in_f, BN);
   const int ntiles = (int)te_ceil_div(T, BM) * nbn;
   constexpr size_t lds = k2_lds<BM, BN>();
-  if constexpr (MODE == 0 && !SWAP && !ACCUM) {
-#ifdef TE_STUDY      // TE_CPASS_GLDS=1: direct-to-LDS staging of the interior tiles (tuning study; see glds16) -- measurement builds
-    static const bool glds = [] {
-      const char* e = getenv("TE_CPASS_GLDS");
-      return e && atoi(e) != 0;
-    }();
-    if (glds) {
-      allow_lds(linear_k2_kernel<MODE, SWAP, ACCUM, BM, BN, true>, lds);
-      linear_k2_kernel<MODE, SWAP, ACCUM, BM, BN, true><<<dim3((unsigned)ntiles), dim3(kThreads), lds, stream>>>(
-          S, W, X, out, T, out_f, in_f, nbn, ntiles, scale, zb);
-      return;
-    }
-#endif
-  }
   allow_lds(linear_k2_kernel<MODE, SWAP, ACCUM, BM, BN>, lds);
   linear_k2_kernel<MODE, SWAP, ACCUM, BM, BN><<<dim3((unsigned)ntiles), dim3(kThreads), lds, stream>>>(
       S, W, X, out, T, out_f, in_f, nbn, ntiles, scale, zb);

@@ -45,12 +45,9 @@
 //                   the same loop: MODE_ZI, MODE_Z1, MODE_CI, MODE_X (te_linear_relprop_x6_general_f32)
 //   loud hand-over  a wait for another workgroup's accumulators is bounded (250 ms), sets a sticky status word, poisons the
 //                   tile with NaN and makes every later wait give up at once: never a plausible wrong result, never a hang
-//   main loop       raw s_barrier + counted s_waitcnt (a __syncthreads() drains direct-to-LDS loads); NST = 3 (prefetch
-//                   distance 2) and KSPLIT = 2 (two K segments per output) are measured studies, off by default
+//   main loop       raw s_barrier + counted s_waitcnt (a __syncthreads() drains direct-to-LDS loads), two LDS stages
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "te_common.h"
@@ -212,69 +209,11 @@ __global__ __launch_bounds__(256) void split_kernel(const float* __restrict__ sr
 //                 forward product plus the planes of |a| for fc2's rule (te_linear_x6_split_dual_f32's outputs, bit for bit)
 // ------------------------------------------------------------------------------------------------
 enum { SRC_GELU_BWD = 0, SRC_GELU_FWD = 1 };
-template <int SRC>
-__global__ __launch_bounds__(256) void gelu_split_kernel(const float* __restrict__ g, const float* __restrict__ x,
-                                                         float* __restrict__ y, unsigned char* __restrict__ dst,
-                                                         unsigned char* __restrict__ dst_abs, int64_t R, int64_t K) {
-  const int r = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int64_t rb = blockIdx.x;
-  const int64_t ks = (int64_t)blockIdx.y * 8 + sl;
-  const int64_t nks = K >> 4;
-  if (ks >= nks) return;
-  const int64_t row = rb * 32 + r;
-  float v[16];
-  if (row < R) {
-    const int64_t at = row * K + ks * 16;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const f32x4 xv = *reinterpret_cast<const f32x4*>(x + at + 4 * c);
-      if constexpr (SRC == SRC_GELU_BWD) {
-        const f32x4 gv = *reinterpret_cast<const f32x4*>(g + at + 4 * c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[4 * c + e] = te_gelu_grad(gv[e], xv[e]);
-      } else {
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = v[4 * c + e] = te_gelu(xv[e]);
-        *reinterpret_cast<f32x4*>(y + at + 4 * c) = o;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) v[e] = 0.0f;
-  }
-  unsigned p[8][3];                    // [pair of consecutive k][plane]
-#pragma unroll
-  for (int e = 0; e < 8; ++e) split3_pk(v[2 * e], v[2 * e + 1], p[e]);
-  auto store = [&](unsigned char* d) __attribute__((always_inline)) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh) {
-        u32x4 w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = p[4 * kh + e][q];
-        *reinterpret_cast<u32x4*>(d + q * kFrag + kh * 512) = w;
-      }
-  };
-  store(dst + ((rb * nks + ks) * 3) * kFrag + r * 16);
-  if constexpr (SRC == SRC_GELU_FWD) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {      // planes of |a| from the planes of a: as split_kernel's dst_abs
-      const unsigned m = p[e][0] & 0x80008000u;
-      p[e][0] &= 0x7fff7fffu;
-      p[e][1] ^= m & (((p[e][1] & 0x7fff7fffu) + 0x7fff7fffu) & 0x80008000u);
-      p[e][2] ^= m & (((p[e][2] & 0x7fff7fffu) + 0x7fff7fffu) & 0x80008000u);
-    }
-    store(dst_abs + ((rb * nks + ks) * 3) * kFrag + r * 16);
-  }
-}
-
-// The same producers with the elementwise work in a COALESCED mapping: a block's 32 rows x 128 k tile is read as 1024
-// float4 (a wave covers 512 contiguous bytes of two rows per instruction, four values per thread and step -- the shape of the
-// stand-alone gelu kernels), the results cross to split_kernel's (row, K16 step) mapping through LDS, and only the split and
-// the plane stores run there.  gelu_split_kernel above does the erf / exp arithmetic on 16 values per thread behind
-// row-strided loads; measured against it in round 5.
+// The elementwise work runs in a COALESCED mapping: a block's 32 rows x 128 k tile is read as 1024 float4 (a wave covers 512
+// contiguous bytes of two rows per instruction, four values per thread and step -- the shape of the stand-alone gelu kernels),
+// the results cross to split_kernel's (row, K16 step) mapping through LDS, and only the split and the plane stores run there
+// (measured in round 5 against a kernel doing the erf / exp arithmetic on 16 values per thread behind row-strided loads:
+// DESIGN.md section 6).
 constexpr int kGsPitch = 132;               // floats per tile row in LDS: 128 + 4 (16-B reads of 32 rows hit every bank once)
 template <int SRC>
 __global__ __launch_bounds__(256) void gelu_split_lds_kernel(const float* __restrict__ g, const float* __restrict__ x,
@@ -343,17 +282,6 @@ __global__ __launch_bounds__(256) void gelu_split_lds_kernel(const float* __rest
   }
 }
 
-// (measurement builds: TE_GELU_SPLIT=direct runs gelu_split_kernel instead; the shipped build does not instantiate it)
-#ifdef TE_STUDY
-static bool gelu_split_direct() {
-  static const bool on = [] {
-    const char* e = getenv("TE_GELU_SPLIT");
-    return e && !strcmp(e, "direct");
-  }();
-  return on;
-}
-#endif
-
 __global__ __launch_bounds__(256) void zero_words_kernel(u32x4* __restrict__ p) {
   p[(size_t)blockIdx.x * 256 + threadIdx.x] = u32x4{0u, 0u, 0u, 0u};
 }
@@ -386,15 +314,15 @@ struct X6Params {
   int64_t a_group_stride;      // bytes between consecutive 32-row groups of A  = nks * (3 or 6) KiB
   int64_t b_rb_stride;         // bytes between consecutive 32-row blocks of B  = nks * 3 KiB
   int nks;                     // K / 16
-  int ksplit;                  // 1, or 2: every output = chain(k < K/2) + chain(k >= K/2), two work items per tile (kseg_rule)
-  float* seg_part;             // ksplit == 2: [tile][threads][accumulators] of the first segment ...
-  unsigned* seg_flags;         // ... and [tile] "it is there" flags, zero before the launch
-
+  // pad0_ / pad1_: bytes no kernel reads, which keep every field at its offset in the kernel arguments.  Without them hipcc
+  // merges the scalar loads of nks and ntm / ntn, allocates SGPRs differently and changes the spills of the 128 x 256 Z- and
+  // C-pass kernels: a kernel change that would need its own same-box measurement.
+  unsigned char pad0_[20];
   int ntm, ntn;                // tiles along the weight side / the activation side (set by launch_x6 from rows_w, T)
   int rows_w;                  // weight-side rows of the product: out_f (Z-pass, plain product), 2 in_f (C-pass: +/- pairs)
   int t_fast;                  // tile order inside the launch: 0 = weight side fastest, 1 = activation side fastest
   int whole_tiles;             // 1: ranges are cut at tile boundaries only (all workgroups of a round in k lock-step)
-  int whole_tiles_forced;      // study builds: whole_tiles was set by the caller (TE_X6_SNAP)
+  int pad1_;
   int ncb;                     // 32-row blocks of the activation side = ceil(T / 32)
   int64_t T;
   int in_f, out_f;
@@ -420,21 +348,15 @@ struct X6Params {
   float scale;                 // MODE_C / MODE_CI / MODE_X: factor on the result (alpha, -beta)
   int accum;                   // MODE_X: 1 = add to what out holds (MODE_CI always does)
   int x_sign;                  // MODE_X: +1 = X+ masks the product, -1 = X-
-  int opt;                     // schedule options (kX6Opt*): results do not depend on them
 };
 // (round 6, measured and removed: requesting the NEXT tile's first stage before the epilogue, non-temporal epilogue accesses, and
 // warm-up requests of the tile's R / Y lines during the last loop steps -- all neutral or negative, profiles/r06_x6_epilogue_study.log)
-constexpr int kX6OptStaged = 8;            // Z modes, 128-row wave tiles: R / Y of the epilogue through the LDS, one cache line per load instruction
-constexpr int kX6OptSkipEpilogue = 4;      // measurement builds: no epilogue (what it costs in place; garbage results)
-constexpr int kX6OptDefault = kX6OptStaged;
 
-// keeps a vector value alive without using it (study paths).  Device pass only: a "v" constraint in the HOST pass of a kernel
-// template silently drops the host stub of the instantiation (the ablation kernels 1-4 / 6 stopped linking that way).
+// a no-op four loaded vectors pass through.  Device pass only: a "v" constraint in the HOST pass of a kernel template silently
+// drops the host stub of the instantiation.
 #if defined(__HIP_DEVICE_COMPILE__)
-#define X6_KEEP(v) asm volatile("" ::"v"(v))
-#define X6_PASS4(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))      // a no-op four loaded vectors pass through
+#define X6_PASS4(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
 #else
-#define X6_KEEP(v) (void)(v)
 #define X6_PASS4(a, b, c, d) (void)0
 #endif
 
@@ -452,11 +374,9 @@ __device__ __forceinline__ void swap_halves(unsigned& lo_keep, unsigned& hi_keep
 }
 
 // ------------------------------------------------------------------------------------------------
-// STUDY (only instantiated under -DTE_X6_STUDY, benchmarks/x6_bench.py --study): timing-only ablations of the main loop --
-// 1: no global loads after the first stage; 2: + no barrier; 3: + no LDS reads (MFMAs on resident fragments);
-// 4: the shipped loop without the epilogue.  Their results are garbage by construction.
-// NST = LDS stages: 2 (stage ks + 1 lands while ks is multiplied) or 3 (prefetch distance 2: a fill that misses the
-// XCD's L2 -- workgroups at different k offsets of shared panels, i.e. every stream-K launch -- has two steps to land).
+// Two LDS stages: stage ks + 1 lands while ks is multiplied (a third stage, prefetch distance 2, ran the C-pass 7 % slower:
+// DESIGN.md 3.1b item 1, profiles/r04_x6_variants.log).
+constexpr int kStages = 2;
 // Tile geometry WM (weight rows x activation rows of a workgroup tile; waves as NWM x NWN, each MI x 2 blocks of 32 x 32):
 //   2: 256 x 256, 2 x 4 waves of 128 x 64 (one 512-thread workgroup per CU)
 //   1: 128 x 256, 1 x 4 waves of 128 x 64 (two 256-thread workgroups per CU)
@@ -477,20 +397,17 @@ struct X6Geo {
 
 // LDS of a workgroup: the stages, or -- Z modes of the 128-row wave tiles -- the epilogue's staging area if that is larger (16 KiB per
 // wave: two buffers of one 32 x 32 block of R and of Y), then one 512-B bias slot per wave and the hand-over word
-template <int WM, int MODE, int NST>
+template <int WM, int MODE>
 struct X6Lds {
   using GEO = X6Geo<WM>;
   static constexpr bool STAGED = (MODE == MODE_Z || MODE == MODE_ZI || MODE == MODE_Z1) && GEO::MI == 4;
-  static constexpr int STAGES = NST * (GEO::NPA + GEO::NPB) * kFrag;
+  static constexpr int STAGES = kStages * (GEO::NPA + GEO::NPB) * kFrag;
   static constexpr int MAIN = (STAGED && GEO::NW * 16384 > STAGES) ? GEO::NW * 16384 : STAGES;
   static constexpr int TOTAL = MAIN + GEO::NW * 512 + 16;
 };
 
-// KSPLIT = 2: a separate instantiation, so that launches without the K split carry none of its code or registers (with the
-// split as a run-time branch the Z-pass epilogue spilled 277 VGPRs and every un-split launch ran 6-16 % slower, measured).
-template <int WM, int MODE, int STUDY = 0, int NST = 2, int KSPLIT = 1>
+template <int WM, int MODE>
 __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(const X6Params p) {
-  static_assert(NST == 2 || NST == 3, "two or three LDS stages");
   using GEO = X6Geo<WM>;
   constexpr int NW = GEO::NW, NWM = GEO::NWM, NWN = GEO::NWN, MI = GEO::MI;
   constexpr bool IS_Z = (MODE == MODE_Z || MODE == MODE_ZI || MODE == MODE_Z1);
@@ -501,14 +418,9 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
   static_assert(NPA / 3 == NW, "each wave stages one weight-side block");
   constexpr int PBW = NPB / 3 / NW;                  // activation-side 32-row blocks each wave stages (2 or 1)
   constexpr int STAGE = NP * kFrag;
-  constexpr int LPS = 3 + 3 * PBW;                   // direct-to-LDS loads one stage_in issues per lane
   constexpr int GROUPS = NPA / G;                    // A groups per tile: 4 WM (Z) or 2 WM (C)
-  constexpr bool FULL = (STUDY == 0 || STUDY >= 4);  // study builds: 5 = shipped + time stamps, 6 = no epilogue + stamps
-  constexpr bool EPI = (STUDY == 0 || STUDY == 5), PROF = (STUDY == 5 || STUDY == 6);
   // Z modes on 128-row wave tiles stage the R / Y blocks of the epilogue through the (then idle) LDS: 16 KiB per wave (X6Staged)
-  constexpr int LDS_MAIN = X6Lds<WM, MODE, NST>::MAIN;
-  long long prof_loop = 0, prof_epi = 0, prof_pub = 0, prof_wait = 0, prof_t0 = 0, prof_t1 = 0, prof_steps = 0, prof_nepi = 0;
-  const long long prof_start = PROF ? wall_clock64() : 0;
+  constexpr int LDS_MAIN = X6Lds<WM, MODE>::MAIN;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   const int lane = threadIdx.x & 63;
@@ -519,13 +431,11 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
   // ---- this workgroup's range of the (tile, K-step) space: whole tiles per XCD, equal ranges inside one ----
   const int bid = blockIdx.x, spx = gridDim.x >> 3;
   const int xcd = bid & 7, slot = bid >> 3;
-  // A launch with ksplit = 2 runs two work items ("virtual tiles") per tile, K segment 0 and K segment 1, each a k-ordered
-  // chain of nks steps; an XCD walks all its segment-0 items, then its segment-1 items.
-  const int nks = p.nks / KSPLIT;                    // steps of one work item
+  const int nks = p.nks;
   const int tiles = p.ntm * p.ntn;
   const int tx0 = (int)((int64_t)tiles * xcd / 8), tx1 = (int)((int64_t)tiles * (xcd + 1) / 8);
   const int ntx = tx1 - tx0;
-  const int64_t iters = (int64_t)ntx * KSPLIT * nks;
+  const int64_t iters = (int64_t)ntx * nks;
   auto cut = [&](int s) -> int64_t {
     int64_t b = iters * s / spx;
     const int r = (int)(b % nks);
@@ -555,9 +465,7 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
     } else {
       tile = full0 + seq - (head ? 1 : 0), k0 = 0, k1 = nks;
     }
-    const int seg = (KSPLIT == 2 && tile >= ntx) ? 1 : 0;      // K segment of this work item
-    tile = tile - seg * ntx + tx0;
-    const int kseg0 = seg * nks;                       // its first K16 step
+    tile += tx0;
     int tn, tm;
     if (p.t_fast) {
       tm = tile / p.ntn, tn = tile - tm * p.ntn;
@@ -569,14 +477,14 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
     //      activation-side blocks -- each 3 KiB contiguous in memory and in the stage; wave-uniform pointers ----
     const unsigned char* srcA;
     if constexpr (!IS_C)
-      srcA = p.A + (int64_t)(tm * GROUPS + wave) * p.a_group_stride + (int64_t)(kseg0 + k0) * kRB;
+      srcA = p.A + (int64_t)(tm * GROUPS + wave) * p.a_group_stride + (int64_t)k0 * kRB;
     else
-      srcA = p.A + (int64_t)(tm * GROUPS + (wave >> 1)) * p.a_group_stride + (int64_t)(kseg0 + k0) * (2 * kRB) + (wave & 1) * kRB;
+      srcA = p.A + (int64_t)(tm * GROUPS + (wave >> 1)) * p.a_group_stride + (int64_t)k0 * (2 * kRB) + (wave & 1) * kRB;
     const unsigned char* srcB[PBW];
 #pragma unroll
     for (int u = 0; u < PBW; ++u) {
       const int cb = min(tn * (GEO::TT / 32) + wave * PBW + u, p.ncb - 1);
-      srcB[u] = p.B + (int64_t)cb * p.b_rb_stride + (int64_t)(kseg0 + k0) * kRB;
+      srcB[u] = p.B + (int64_t)cb * p.b_rb_stride + (int64_t)k0 * kRB;
     }
     unsigned char* const ldsA = smem + wave * kRB;
     unsigned char* const ldsB = smem + NPA * kFrag + wave * (PBW * kRB);
@@ -594,9 +502,6 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
         for (int q = 0; q < 3; ++q) glds16(srcB[u] + q * kFrag + lane16, ldsB + stg * STAGE + (u * 3 + q) * kFrag);
     };
 
-    if constexpr (PROF) {
-      if (threadIdx.x == 0) prof_t0 = wall_clock64();
-    }
     // Bounded, loud wait for a flag another workgroup raises (release) once its accumulators are in memory; uniform
     // result.  On expiry: the caller's sticky status word and this pass's error word are set, `false` comes back.
     auto wait_for = [&](unsigned* flag) -> bool {
@@ -655,42 +560,17 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
           for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.0f;
     }
 
-    if constexpr (PROF) {
-      if (threadIdx.x == 0) {
-        const long long t = wall_clock64();
-        prof_wait += t - prof_t0;
-        prof_t0 = t;
-        prof_steps += k1 - k0;
-      }
-    }
-    // ---- main loop: stage ks + 1 (and, NST = 3, ks + 2) lands while stage ks is multiplied ----
+    // ---- main loop: stage ks + 1 lands while stage ks is multiplied ----
     stage_in(0, 0);
-    if constexpr (NST == 3) stage_in(1, (k0 + 1 < k1) ? 1 : 0);
     int st = 0;
     bf16x8 a[MI][3], b[2][3];
-    if constexpr (STUDY == 3) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) b[ni][q] = *reinterpret_cast<const bf16x8*>(smem + NPA * kFrag + wn * (2 * kRB) + lane16 + ni * kRB + q * kFrag);
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) a[mi][q] = *reinterpret_cast<const bf16x8*>(smem + wm * (MI * kRB) + lane16 + mi * kRB + q * kFrag);
-    }
     for (int ks = k0; ks < k1; ++ks) {
-      // This step's stage has landed (own loads: counted vmcnt -- loads retire in issue order, so with three stages the
-      // LPS loads of the youngest fill stay in flight across the barrier; every wave's: the barrier), and the stage of
-      // step ks - 1 is free again (every wave finished its fragment reads before it arrived here: lgkmcnt(0) at the last
-      // MFMA round).  A RAW s_barrier: __syncthreads() carries a workgroup fence, for which hipcc drains vmcnt(0) -- a
-      // direct-to-LDS load is a pending LDS write -- i.e. it would cut the prefetch distance back to one step.
-      if constexpr (FULL) {
-        if constexpr (NST == 3) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(LPS) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      }
-      if constexpr (FULL || STUDY == 1) __builtin_amdgcn_s_barrier();
+      // This step's stage has landed (own loads: vmcnt; every wave's: the barrier), and the stage of step ks - 1 is free
+      // again (every wave finished its fragment reads before it arrived here: lgkmcnt(0) at the last MFMA round).  A RAW
+      // s_barrier: __syncthreads() carries a workgroup fence, for which hipcc drains vmcnt(0) -- a direct-to-LDS load is a
+      // pending LDS write -- i.e. it would cut the prefetch distance back to one step.
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
       const unsigned char* sA = smem + st * STAGE + wm * (MI * kRB) + lane16;
       const unsigned char* sB = smem + st * STAGE + NPA * kFrag + wn * (2 * kRB) + lane16;
       // The order below is pinned with sched_barrier: left to itself hipcc's scheduler flips between an order that
@@ -711,12 +591,12 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
       const unsigned aA = (unsigned)(uintptr_t)sA, aB = (unsigned)(uintptr_t)sB;
 #define X6_SB __builtin_amdgcn_sched_barrier(0)
 #define X6_RDB(ni, r) \
-  if constexpr (STUDY != 3) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(b[ni][PB[r]]) : "v"(aB), "i"((ni) * kRB + PB[r] * kFrag))
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(b[ni][PB[r]]) : "v"(aB), "i"((ni) * kRB + PB[r] * kFrag))
 #define X6_RDA(mi, r) \
-  if constexpr (STUDY != 3) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(a[mi][PA[r]]) : "v"(aA), "i"((mi) * kRB + PA[r] * kFrag))
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(a[mi][PA[r]]) : "v"(aA), "i"((mi) * kRB + PA[r] * kFrag))
 #define X6_WAIT(n)                                                           \
   X6_SB;                                                                     \
-  if constexpr (STUDY != 3) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); \
+  asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); \
   X6_SB
 #define X6_MM(mi, ni, q) acc[mi][ni] = TE_MFMA_BF16(a[mi][PA[q]], b[ni][PB[q]], acc[mi][ni])
 #define X6_RD_HEAD(r) X6_SB; X6_RDB(0, r); X6_RDA(0, r); X6_RDA(1, r); X6_SB
@@ -727,7 +607,7 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
 #define X6_RD4(r) X6_SB; X6_RDB(0, r); X6_RDA(0, r); X6_RDA(1, r); X6_RDB(1, r); X6_SB
         X6_RD4(0);
         X6_RD4(1);                                                   // 8 issued
-        if constexpr (FULL) stage_in((st + NST - 1) % NST, (ks + NST - 1 < k1) ? 1 : 0);
+        stage_in((st + 1) % kStages, (ks + 1 < k1) ? 1 : 0);
         X6_WAIT(6); X6_MM(0, 0, 0);
         X6_WAIT(5); X6_MM(1, 0, 0);
         X6_WAIT(4); X6_MM(1, 1, 0); X6_MM(0, 1, 0);
@@ -749,7 +629,7 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
       X6_RD_HEAD(0);
       X6_RD_TAIL(0);                                                 // 6 issued
       // the next step's stage is requested before the first MFMA (a direct-to-LDS load between MFMAs costs issue slots)
-      if constexpr (FULL) stage_in((st + NST - 1) % NST, (ks + NST - 1 < k1) ? 1 : 0);
+      stage_in((st + 1) % kStages, (ks + 1 < k1) ? 1 : 0);
       X6_WAIT(4); X6_MM(0, 0, 0);
       X6_WAIT(3); X6_MM(1, 0, 0);
       X6_WAIT(2); X6_MM(1, 1, 0); X6_MM(0, 1, 0);
@@ -784,15 +664,9 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
 #undef X6_MM
 #undef X6_RD_HEAD
 #undef X6_RD_TAIL
-      st = (st + 1 == NST) ? 0 : st + 1;
+      st = (st + 1 == kStages) ? 0 : st + 1;
     }
 
-    if constexpr (PROF) {
-      if (threadIdx.x == 0) {
-        prof_t1 = wall_clock64();
-        prof_loop += prof_t1 - prof_t0;
-      }
-    }
     // ---- accumulators to memory + flag (guide: plain stores -> vmcnt(0) -> barrier -> release -> flag) ----
     auto publish = [&](float* dst, unsigned* flag) __attribute__((always_inline)) {
       f32x4* op = reinterpret_cast<f32x4*>(dst) + (size_t)wave * (GEO::ACC / 4) * 64 + lane;
@@ -816,64 +690,10 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (!p.drop_handover) __hip_atomic_store(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if constexpr (PROF) prof_pub += wall_clock64() - prof_t1;
       }
     };
     if (k1 < nks) {            // a cut work item: the workgroup 8 above continues this chain
       publish(my_part, p.flags + bid);
-      continue;
-    }
-    if constexpr (KSPLIT == 2) {
-      // Two K segments per tile, each its own k-ordered chain, summed once: out = chain(segment 0) + chain(segment 1),
-      // whatever the schedule.  Segment 0 leaves its accumulators in seg_part[tile]; segment 1 -- a later work item of the
-      // same XCD, i.e. a HIGHER workgroup slot running at the same time -- waits for them here, at its END.
-      float* const sp = p.seg_part + (size_t)tile * GEO::THREADS * GEO::ACC;
-      unsigned* const sflag = p.seg_flags + tile;
-      if (seg == 0) {
-        publish(sp, sflag);
-        __syncthreads();
-        continue;
-      }
-      const bool got = wait_for(sflag);
-      const f32x4* ip = reinterpret_cast<const f32x4*>(sp) + (size_t)wave * (GEO::ACC / 4) * 64 + lane;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const f32x4 v = ip[c * 64];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[mi][ni][4 * c + e] = got ? v[e] + acc[mi][ni][4 * c + e] : __builtin_nanf("");
-          }
-          ip += 4 * 64;
-          asm volatile("" : "+v"(ip));
-          __builtin_amdgcn_sched_barrier(0);      // one block (16 registers) of segment 0 in flight at a time: the
-        }                                         // accumulators are live here, a batch of all 32 loads would spill
-    }
-
-#ifdef TE_X6_STUDY
-    if (p.opt & kX6OptSkipEpilogue) {
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) X6_KEEP(acc[mi][ni]);
-      __syncthreads();
-      continue;
-    }
-#endif
-    if constexpr (!EPI) {
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) X6_KEEP(acc[mi][ni]);
-      __syncthreads();
-      if constexpr (PROF) {
-        if (threadIdx.x == 0) {
-          prof_epi += wall_clock64() - prof_t1;
-          prof_nepi += 1;
-        }
-      }
       continue;
     }
     // ---- epilogue.  32x32 block (mi, ni): lane (tc = lane & 31, h = lane >> 5) holds activation row t and, for
@@ -904,199 +724,160 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
         if (p.bias) bv = *reinterpret_cast<const f32x4*>(p.bias + (tm * (NWM * MI) + wm * MI) * 32 + lane * 4);
         *reinterpret_cast<f32x4*>(bias_lds + lane * 4) = bv;
       }
-      bool staged_done = false;
-      if constexpr (X6Lds<WM, MODE, NST>::STAGED) {
-#ifdef TE_X6_STUDY      // (measurement builds keep the round-3 epilogue of these geometries behind TE_X6_OPT for same-box A/B runs)
-        const bool staged = (p.opt & kX6OptStaged) != 0;
-#else
-        constexpr bool staged = true;
-#endif
-        if (staged) {
-          staged_done = true;
-          // Round 6 (profiles/r06_x6_epilogue_study.log (5)): a lane of the accumulator layout owns the 16-byte pieces g = 0..3 of ONE
-          // 128-byte line of its row, so the four load instructions of a block touched the same 32 lines back to back and the in-order L1
-          // stalled on the pending fills.  Here every line is requested by ONE instruction: a direct-to-LDS load covers 8 rows x 128 B
-          // (8 lanes per line), chunk order XOR-permuted by the row so that the read-back in the accumulator layout -- lane (tc, h),
-          // piece g = chunk 2g + h of row tc -- is bank-conflict free: [row][128 B] images, row r holds chunk c at slot c ^ ((r >> 1) & 7).
-          constexpr int NL = (MODE == MODE_Z1) ? 4 : 8;                 // direct-to-LDS loads per block
-          __builtin_amdgcn_s_barrier();                                 // every wave has read its last fragments: the stages are free
-          unsigned char* const stg = smem + wave * 16384;               // two buffers of (R block, Y block)
-          unsigned rda[4];
+      if constexpr (X6Lds<WM, MODE>::STAGED) {
+        // Round 6 (profiles/r06_x6_epilogue_study.log (5)): a lane of the accumulator layout owns the 16-byte pieces g = 0..3 of ONE
+        // 128-byte line of its row, so the four load instructions of a block touched the same 32 lines back to back and the in-order L1
+        // stalled on the pending fills.  Here every line is requested by ONE instruction: a direct-to-LDS load covers 8 rows x 128 B
+        // (8 lanes per line), chunk order XOR-permuted by the row so that the read-back in the accumulator layout -- lane (tc, h),
+        // piece g = chunk 2g + h of row tc -- is bank-conflict free: [row][128 B] images, row r holds chunk c at slot c ^ ((r >> 1) & 7).
+        constexpr int NL = (MODE == MODE_Z1) ? 4 : 8;                 // direct-to-LDS loads per block
+        __builtin_amdgcn_s_barrier();                                 // every wave has read its last fragments: the stages are free
+        unsigned char* const stg = smem + wave * 16384;               // two buffers of (R block, Y block)
+        unsigned rda[4];
 #pragma unroll
-          for (int g = 0; g < 4; ++g)
-            rda[g] = (unsigned)(uintptr_t)stg + tc * 128 + (((2 * g + h) ^ ((tc >> 1) & 7)) << 4);
-          const unsigned bia = (unsigned)(uintptr_t)bias_lds + h * 16;
-          const int r8 = lane >> 3;
-          auto request = [&](int bi, int buf) __attribute__((always_inline)) {
-            const int ni = bi / MI, mi = bi % MI;
-            const int cb = tn * (GEO::TT / 32) + wn * 2 + ni;
-            const int j0 = (tm * (NWM * MI) + wm * MI + mi) * 32;
+        for (int g = 0; g < 4; ++g)
+          rda[g] = (unsigned)(uintptr_t)stg + tc * 128 + (((2 * g + h) ^ ((tc >> 1) & 7)) << 4);
+        const unsigned bia = (unsigned)(uintptr_t)bias_lds + h * 16;
+        const int r8 = lane >> 3;
+        auto request = [&](int bi, int buf) __attribute__((always_inline)) {
+          const int ni = bi / MI, mi = bi % MI;
+          const int cb = tn * (GEO::TT / 32) + wn * 2 + ni;
+          const int j0 = (tm * (NWM * MI) + wm * MI + mi) * 32;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const int row = 8 * i + r8;
-              const int64_t t = min((int64_t)cb * 32 + row, p.T - 1);
-              const int64_t off = t * p.out_f + j0 + (((lane & 7) ^ ((row >> 1) & 7)) << 2);
-              glds16(reinterpret_cast<const unsigned char*>(p.R + off), stg + buf * 8192 + i * 1024);
-              if constexpr (MODE != MODE_Z1)
-                glds16(reinterpret_cast<const unsigned char*>(p.Y + off), stg + buf * 8192 + 4096 + i * 1024);
-            }
+          for (int i = 0; i < 4; ++i) {
+            const int row = 8 * i + r8;
+            const int64_t t = min((int64_t)cb * 32 + row, p.T - 1);
+            const int64_t off = t * p.out_f + j0 + (((lane & 7) ^ ((row >> 1) & 7)) << 2);
+            glds16(reinterpret_cast<const unsigned char*>(p.R + off), stg + buf * 8192 + i * 1024);
+            if constexpr (MODE != MODE_Z1)
+              glds16(reinterpret_cast<const unsigned char*>(p.Y + off), stg + buf * 8192 + 4096 + i * 1024);
+          }
+        };
+        // Two blocks in flight: block bi + 2 is requested into block bi's buffer as soon as block bi sits in registers.  The wait for
+        // block bi is hand-counted: younger in the queue are the loads of block bi + 1 and the S stores of blocks bi - 2 and bi - 1
+        // (six each, if the wave's row blocks exist: `all_blk`; else only the loads are counted, which waits longer, never shorter).
+        const bool all_blk = blk[0] && blk[1];
+        request(0, 0);
+        request(1, 1);
+#pragma unroll
+        for (int bi = 0; bi < 2 * MI; ++bi) {
+          const int ni = bi / MI, mi = bi % MI, buf = bi & 1;
+          const int cb = tn * (GEO::TT / 32) + wn * 2 + ni;
+          const int j0 = (tm * (NWM * MI) + wm * MI + mi) * 32;
+          constexpr int kStore = 6;
+          const int yl = (bi + 1 < 2 * MI) ? NL : 0, ys = (bi >= 2 ? kStore : 0) + (bi >= 1 ? kStore : 0);
+          if (all_blk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(yl + ys) : "memory");
+          else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(yl) : "memory");
+          f32x4 r4[4], y4[4], b4[4];
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r4[g]) : "v"(rda[g]), "i"(buf * 8192));
+            if constexpr (MODE != MODE_Z1)
+              asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(y4[g]) : "v"(rda[g]), "i"(buf * 8192 + 4096));
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(b4[g]) : "v"(bia), "i"((mi * 32 + 8 * g) * 4));
+          }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          if (bi + 2 < 2 * MI) request(bi + 2, buf);
+          X6_PASS4(r4[0], r4[1], r4[2], r4[3]);
+          if constexpr (MODE != MODE_Z1) X6_PASS4(y4[0], y4[1], y4[2], y4[3]);
+          X6_PASS4(b4[0], b4[1], b4[2], b4[3]);
+          // Element pairs on packed fp32 instructions (z, the division: sd2 -- an IEEE quotient without its range scaling, correctly
+          // rounded inside the normal range).  Which elements cancel is kept as wave-level lane masks (the compare's own result,
+          // OR-ed on the scalar unit); the per-lane bit mask the fallback wants is rebuilt only if one is set.
+          unsigned w[4][3][2];
+          unsigned long long any_cancel = 0;
+          auto z_of = [&](int g, int c0, f32x2& z2, f32x2& a2) __attribute__((always_inline)) {
+            a2 = f32x2{acc[mi][ni][4 * g + c0], acc[mi][ni][4 * g + c0 + 1]};
+            if constexpr (MODE == MODE_Z)            // Z  = X+ W+^T + X- W-^T = ((Y - b) + |X||W|^T) / 2  (>= 0)
+              z2 = f32x2{0.5f, 0.5f} * ((f32x2{y4[g][c0], y4[g][c0 + 1]} - f32x2{b4[g][c0], b4[g][c0 + 1]}) + a2);
+            else if constexpr (MODE == MODE_ZI)      // Z' = X+ W-^T + X- W+^T = ((Y - b) - |X||W|^T) / 2  (<= 0)
+              z2 = f32x2{0.5f, 0.5f} * ((f32x2{y4[g][c0], y4[g][c0 + 1]} - f32x2{b4[g][c0], b4[g][c0 + 1]}) - a2);
+            else                                     // one-sided product: the accumulator is Z
+              z2 = a2;
           };
-          // Two blocks in flight: block bi + 2 is requested into block bi's buffer as soon as block bi sits in registers.  The wait for
-          // block bi is hand-counted: younger in the queue are the loads of block bi + 1 and the S stores of blocks bi - 2 and bi - 1
-          // (six each, if the wave's row blocks exist: `all_blk`; else only the loads are counted, which waits longer, never shorter).
-          const bool all_blk = blk[0] && blk[1];
-#ifdef TE_X6_STUDY      // TE_X6_OPT bit 6: shader-clock stamps of the epilogue's phases, waves 0 and 4 (one SIMD) of workgroup 163
-          long long* const stamp_out = reinterpret_cast<long long*>(p.flags + 2048) + 4608 + (wave >> 2) * 64;
-          const bool stamping = (p.opt & 64) && bid == 163 && (wave & 3) == 0 && lane == 0;
-          int stamp_i = 0;
-#define X6_STAMP()                                                                              \
-  if (p.opt & 64) {                                                                             \
-    long long t_;                                                                               \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                  \
-    if (stamping) stamp_out[stamp_i] = t_;                                                      \
-    ++stamp_i;                                                                                  \
-  }
-#else
-#define X6_STAMP()
-#endif
-          X6_STAMP();
-          request(0, 0);
-          request(1, 1);
+          auto cancels = [&](float z, float a_abs) __attribute__((always_inline)) -> bool {
+            if constexpr (MODE == MODE_Z) return !(z > kCancelTol * a_abs);
+            else if constexpr (MODE == MODE_ZI) return !(-z > kCancelTol * a_abs);
+            else return false;
+          };
 #pragma unroll
-          for (int bi = 0; bi < 2 * MI; ++bi) {
-            const int ni = bi / MI, mi = bi % MI, buf = bi & 1;
-            const int cb = tn * (GEO::TT / 32) + wn * 2 + ni;
-            const int j0 = (tm * (NWM * MI) + wm * MI + mi) * 32;
-            constexpr int kStore = 6;
-            const int yl = (bi + 1 < 2 * MI) ? NL : 0, ys = (bi >= 2 ? kStore : 0) + (bi >= 1 ? kStore : 0);
-            X6_STAMP();
-            if (all_blk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(yl + ys) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(yl) : "memory");
-            X6_STAMP();
-            f32x4 r4[4], y4[4], b4[4];
+          for (int g = 0; g < 4; ++g) {
+            float sv4[4];
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r4[g]) : "v"(rda[g]), "i"(buf * 8192));
-              if constexpr (MODE != MODE_Z1)
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(y4[g]) : "v"(rda[g]), "i"(buf * 8192 + 4096));
-              asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(b4[g]) : "v"(bia), "i"((mi * 32 + 8 * g) * 4));
+            for (int c0 = 0; c0 < 4; c0 += 2) {
+              f32x2 z2, a2;
+              z_of(g, c0, z2, a2);
+              f32x2 rr = {r4[g][c0], r4[g][c0 + 1]};
+              if (p.rs) rr = rr * f32x2{f[ni], f[ni]};
+              const f32x2 sv = sd2(rr, z2);
+#pragma unroll
+              for (int e = 0; e < 2; ++e) {
+                const bool cancel = cancels(z2[e], a2[e]);
+                if constexpr (MODE != MODE_Z1) any_cancel |= __builtin_amdgcn_ballot_w64(cancel);
+                sv4[c0 + e] = (live[ni] && !cancel) ? sv[e] : 0.0f;
+              }
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (bi + 2 < 2 * MI) request(bi + 2, buf);
-            X6_STAMP();
-            X6_PASS4(r4[0], r4[1], r4[2], r4[3]);
-            if constexpr (MODE != MODE_Z1) X6_PASS4(y4[0], y4[1], y4[2], y4[3]);
-            X6_PASS4(b4[0], b4[1], b4[2], b4[3]);
-            // Element pairs on packed fp32 instructions (z, the division: sd2 -- an IEEE quotient without its range scaling, correctly
-            // rounded inside the normal range).  Which elements cancel is kept as wave-level lane masks (the compare's own result,
-            // OR-ed on the scalar unit); the per-lane bit mask the fallback wants is rebuilt only if one is set.
-            unsigned w[4][3][2];
-            unsigned long long any_cancel = 0;
-            auto z_of = [&](int g, int c0, f32x2& z2, f32x2& a2) __attribute__((always_inline)) {
-              a2 = f32x2{acc[mi][ni][4 * g + c0], acc[mi][ni][4 * g + c0 + 1]};
-              if constexpr (MODE == MODE_Z)            // Z  = X+ W+^T + X- W-^T = ((Y - b) + |X||W|^T) / 2  (>= 0)
-                z2 = f32x2{0.5f, 0.5f} * ((f32x2{y4[g][c0], y4[g][c0 + 1]} - f32x2{b4[g][c0], b4[g][c0 + 1]}) + a2);
-              else if constexpr (MODE == MODE_ZI)      // Z' = X+ W-^T + X- W+^T = ((Y - b) - |X||W|^T) / 2  (<= 0)
-                z2 = f32x2{0.5f, 0.5f} * ((f32x2{y4[g][c0], y4[g][c0 + 1]} - f32x2{b4[g][c0], b4[g][c0 + 1]}) - a2);
-              else                                     // one-sided product: the accumulator is Z
-                z2 = a2;
-            };
-            auto cancels = [&](float z, float a_abs) __attribute__((always_inline)) -> bool {
-              if constexpr (MODE == MODE_Z) return !(z > kCancelTol * a_abs);
-              else if constexpr (MODE == MODE_ZI) return !(-z > kCancelTol * a_abs);
-              else return false;
-            };
+            unsigned lo[3], hi[3];
+            split3_pk(sv4[0], sv4[1], lo);
+            split3_pk(sv4[2], sv4[3], hi);
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              float sv4[4];
+            for (int q = 0; q < 3; ++q) {
+              w[g][q][0] = lo[q];
+              w[g][q][1] = hi[q];
+            }
+          }
+          unsigned bad = 0;                          // elements whose Z needs the cancellation fallback
+          if (any_cancel != 0) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
 #pragma unroll
               for (int c0 = 0; c0 < 4; c0 += 2) {
                 f32x2 z2, a2;
                 z_of(g, c0, z2, a2);
-                f32x2 rr = {r4[g][c0], r4[g][c0 + 1]};
-                if (p.rs) rr = rr * f32x2{f[ni], f[ni]};
-                const f32x2 sv = sd2(rr, z2);
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                  const bool cancel = cancels(z2[e], a2[e]);
-                  if constexpr (MODE != MODE_Z1) any_cancel |= __builtin_amdgcn_ballot_w64(cancel);
-                  sv4[c0 + e] = (live[ni] && !cancel) ? sv[e] : 0.0f;
-                }
+                bad |= (cancels(z2[0], a2[0]) ? 1u : 0u) << (4 * g + c0);
+                bad |= (cancels(z2[1], a2[1]) ? 1u : 0u) << (4 * g + c0 + 1);
               }
-              unsigned lo[3], hi[3];
-              split3_pk(sv4[0], sv4[1], lo);
-              split3_pk(sv4[2], sv4[3], hi);
-#pragma unroll
-              for (int q = 0; q < 3; ++q) {
-                w[g][q][0] = lo[q];
-                w[g][q][1] = hi[q];
-              }
-            }
-            unsigned bad = 0;                          // elements whose Z needs the cancellation fallback
-            if (any_cancel != 0) {
-#pragma unroll
-              for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int c0 = 0; c0 < 4; c0 += 2) {
-                  f32x2 z2, a2;
-                  z_of(g, c0, z2, a2);
-                  bad |= (cancels(z2[0], a2[0]) ? 1u : 0u) << (4 * g + c0);
-                  bad |= (cancels(z2[1], a2[1]) ? 1u : 0u) << (4 * g + c0 + 1);
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < 2; ++g)
-#pragma unroll
-              for (int q = 0; q < 3; ++q)
-#pragma unroll
-                for (int d = 0; d < 2; ++d) swap_halves(w[g][q][d], w[g + 2][q][d]);
-#ifdef TE_X6_STUDY
-            if (p.opt & 64) {
-#pragma unroll
-              for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int q = 0; q < 3; ++q) asm volatile("" : "+v"(w[g][q][0]), "+v"(w[g][q][1]));      // (the arithmetic ends before the stamp)
-            }
-#endif
-            X6_STAMP();
-            if (blk[ni]) {
-              unsigned char* Srow = p.S + (int64_t)cb * nksS * kRB + tc * 16;
-              unsigned char* sp = Srow + (int64_t)((j0 >> 4) + h) * kRB;
-#pragma unroll
-              for (int q = 0; q < 3; ++q)
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                  u32x4 v = {w[c][q][0], w[c][q][1], w[c + 2][q][0], w[c + 2][q][1]};
-                  *reinterpret_cast<u32x4*>(sp + q * kFrag + c * 512) = v;
-                }
-              if (!live[ni]) bad = 0;
-              if (__builtin_amdgcn_ballot_w64(bad != 0) != 0) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const float* Rrow = p.R + tl[ni] * p.out_f;
-#pragma clang loop unroll(disable)
-                for (int e = 0; e < 16; ++e) {
-                  if ((bad >> e) & 1u) {
-                    const int jj = j0 + 8 * (e >> 2) + 4 * h + (e & 3);
-                    const float z = (MODE == MODE_ZI) ? exact_zi(p.X + tl[ni] * p.in_f, p.W + (int64_t)jj * p.in_f, p.in_f)
-                                                      : exact_z(p.X + tl[ni] * p.in_f, p.W + (int64_t)jj * p.in_f, p.in_f);
-                    float rr = Rrow[jj];
-                    if (p.rs) rr = rr * f[ni];
-                    unsigned pl[3];
-                    split3(te_sd(rr, z), pl);
-                    unsigned short* d = reinterpret_cast<unsigned short*>(Srow + (int64_t)(jj >> 4) * kRB + ((jj >> 3) & 1) * 512) + (jj & 7);
-                    d[0] = (unsigned short)pl[0];
-                    d[kFrag / 2] = (unsigned short)pl[1];
-                    d[kFrag] = (unsigned short)pl[2];
-                  }
-                }
-              }
-            }
-            X6_STAMP();
           }
-#undef X6_STAMP
+#pragma unroll
+          for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+#pragma unroll
+              for (int d = 0; d < 2; ++d) swap_halves(w[g][q][d], w[g + 2][q][d]);
+          if (blk[ni]) {
+            unsigned char* Srow = p.S + (int64_t)cb * nksS * kRB + tc * 16;
+            unsigned char* sp = Srow + (int64_t)((j0 >> 4) + h) * kRB;
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+#pragma unroll
+              for (int c = 0; c < 2; ++c) {
+                u32x4 v = {w[c][q][0], w[c][q][1], w[c + 2][q][0], w[c + 2][q][1]};
+                *reinterpret_cast<u32x4*>(sp + q * kFrag + c * 512) = v;
+              }
+            if (!live[ni]) bad = 0;
+            if (__builtin_amdgcn_ballot_w64(bad != 0) != 0) {
+              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+              const float* Rrow = p.R + tl[ni] * p.out_f;
+#pragma clang loop unroll(disable)
+              for (int e = 0; e < 16; ++e) {
+                if ((bad >> e) & 1u) {
+                  const int jj = j0 + 8 * (e >> 2) + 4 * h + (e & 3);
+                  const float z = (MODE == MODE_ZI) ? exact_zi(p.X + tl[ni] * p.in_f, p.W + (int64_t)jj * p.in_f, p.in_f)
+                                                    : exact_z(p.X + tl[ni] * p.in_f, p.W + (int64_t)jj * p.in_f, p.in_f);
+                  float rr = Rrow[jj];
+                  if (p.rs) rr = rr * f[ni];
+                  unsigned pl[3];
+                  split3(te_sd(rr, z), pl);
+                  unsigned short* d = reinterpret_cast<unsigned short*>(Srow + (int64_t)(jj >> 4) * kRB + ((jj >> 3) & 1) * 512) + (jj & 7);
+                  d[0] = (unsigned short)pl[0];
+                  d[kFrag / 2] = (unsigned short)pl[1];
+                  d[kFrag] = (unsigned short)pl[2];
+                }
+              }
+            }
+          }
         }
-      }
-      if (!staged_done) {
+      } else {
       // (128 x 128 geometry: three waves per SIMD cover the load latency, and 168 VGPRs do not hold a second buffer)
       constexpr int NBUF = (MI == 4) ? 2 : 1;
       f32x4 r4[NBUF][4], y4[NBUF][4];
@@ -1104,13 +885,6 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
         const int ni = bi / MI, mi = bi % MI;
         const int j0 = (tm * (NWM * MI) + wm * MI + mi) * 32;
         const float* Rrow = p.R + tl[ni] * p.out_f + j0 + 4 * h;
-#ifdef TE_X6_STUDY      // TE_X6_OPT bit 4: the epilogue without its R / Y loads (garbage results: what the loads cost)
-        if (p.opt & 16) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) r4[buf][g] = f32x4{1.0f, 2.0f, 3.0f, 4.0f}, y4[buf][g] = f32x4{1.0f, 2.0f, 3.0f, 4.0f};
-          return;
-        }
-#endif
 #pragma unroll
         for (int g = 0; g < 4; ++g) r4[buf][g] = *reinterpret_cast<const f32x4*>(Rrow + 8 * g);
         if constexpr (MODE != MODE_Z1) {
@@ -1174,15 +948,6 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
           for (int q = 0; q < 3; ++q)
 #pragma unroll
             for (int d = 0; d < 2; ++d) swap_halves(w[g][q][d], w[g + 2][q][d]);
-#ifdef TE_X6_STUDY      // TE_X6_OPT bit 5: the epilogue without its S stores (garbage results: what the stores cost)
-        if (p.opt & 32) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) asm volatile("" ::"v"(w[g][q][0]), "v"(w[g][q][1]));
-          continue;
-        }
-#endif
         if (blk[ni]) {
           unsigned char* Srow = p.S + (int64_t)cb * nksS * kRB + tc * 16;
           unsigned char* sp = Srow + (int64_t)((j0 >> 4) + h) * kRB;
@@ -1220,7 +985,7 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
           }
         }
       }
-      }      // (!staged_done)
+      }
     } else if constexpr (MODE == MODE_G) {
       // plain product: out[t][m] = acc + bias[m] (fp32 row-major [T, M]); the wave's 128 bias values through its LDS slot
       float* const bias_lds = reinterpret_cast<float*>(smem + LDS_MAIN) + wave * 128;
@@ -1314,64 +1079,17 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
         }
     }
     __syncthreads();       // every wave is done with the stages before the next fragment's first loads land in them
-    if constexpr (PROF) {
-      if (threadIdx.x == 0) {
-        prof_epi += wall_clock64() - prof_t1;
-        prof_nepi += 1;
-      }
-    }
-  }
-  if constexpr (PROF) {
-    if (threadIdx.x == 0) {
-      long long* o = reinterpret_cast<long long*>(p.flags + 2048) + (size_t)bid * 8;
-      o[0] = prof_loop, o[1] = prof_epi, o[2] = prof_pub, o[3] = prof_wait, o[4] = prof_steps, o[5] = prof_nepi;
-      o[6] = wall_clock64() - prof_start;
-      o[7] = prof_start;
-    }
   }
 }
 
 inline size_t planes_bytes(int64_t rows, int64_t K) {
   return (size_t)te_ceil_div(rows, 32) * 32 * (size_t)K * 6;
 }
-// Fixed K split -- a STUDY, off by default (the flag TE_X6_KSPLIT turns it on; it changes which chains an output is summed
-// from, i.e. the bits: a caller sets it for every launch of a process or for none).  Products with a long K and few weight rows --
-// out_f = 768 against K = 2304 / 3072: fc2's forward, the input gradients of qkv and fc1, fc2's Z-pass -- are 150 tiles
-// of 256 x 256 for 256 CUs, and a tile is a SEQUENTIAL chain of K / 16 steps however it is scheduled.  Two chains per output
-// (the same two for every tile geometry, batch size and schedule: a property of the layer's shape only, so results stay
-// bitwise batch- and geometry-invariant) halve that floor and double the work items.  Measured:
-// isolated launches gain 10-17 % over 128 x 256 tiles, but only 5 % over the 128 x 128 geometry that shipped with it, and
-// IN THE STEP nothing (ViT-B/16: 893 vs 896 maps/s, same box, A B A B) or less than nothing (BERT-512: 286 vs 292
-// sequences/s: at T = 16 384 the un-split 128 x 128 launch is exactly one tile per workgroup slot) -- the CUs a narrow
-// launch leaves idle are used by the other stream of the step anyway.  Not shipped.
-inline int kseg_shape(int64_t K, int64_t rows_w) { return (K >= 1536 && rows_w <= 768 && (K / 16) % 2 == 0) ? 2 : 1; }
-#ifdef TE_X6_STUDY
-inline int kseg_rule(int64_t K, int64_t rows_w, int flags) { return (flags & TE_X6_KSPLIT) ? kseg_shape(K, rows_w) : 1; }
-#else
-inline int kseg_rule(int64_t, int64_t, int) { return 1; }
-#endif
-// study-only schedules (TE_X6_STAGES_3, TE_X6_KSPLIT) are not compiled into the shipped library: a caller that asks for one
-// gets TE_ERR_UNSUPPORTED instead of a heavily spilling kernel
-inline bool study_flags_refused(int flags) {
-#ifdef TE_X6_STUDY
-  (void)flags;
-  return false;
-#else
-  return (flags & (TE_X6_STAGES_3 | TE_X6_KSPLIT)) != 0;
-#endif
-}
-inline size_t seg_part_bytes(int64_t T, int64_t K, int64_t rows_w) {       // accumulators of segment 0, any geometry
-  return kseg_shape(K, rows_w) == 2 ? te_align_up((size_t)te_ceil_div(T, 256) * 256 * (size_t)rows_w * 4, 256) : 0;
-}
-inline size_t seg_flag_words(int64_t T, int64_t K, int64_t rows_w) {       // one per tile of the smallest geometry, x 1024
-  return kseg_shape(K, rows_w) == 2 ? te_align_up((size_t)te_ceil_div(T, 128) * (size_t)(rows_w / 128), 1024) : 0;
-}
-inline size_t seg_region_bytes(int64_t T, int64_t K, int64_t rows_w) {
-  return seg_part_bytes(T, K, rows_w) + seg_flag_words(T, K, rows_w) * 4;
-}
+// (A fixed K split -- two k-ordered chains per output for long-K, few-row products -- was measured and not shipped:
+// 5 % over the 128 x 128 geometry in isolated launches, nothing in the step)
 constexpr size_t kPartialBytes = (size_t)512 * 256 * 128 * 4;       // grid x threads x accumulators: 64 MiB covers every geometry
 constexpr double kWholeTileSlack = 1.15;                          // whole tiles if ceil(r) <= 1.15 r (launch_x6)
-constexpr size_t kFlagBytes = 65536;                                 // 512 flags + the error word (+ study time stamps), per pass
+constexpr size_t kFlagBytes = 65536;                                 // 512 flags + the error word, per pass
 
 inline int pick_wm(int64_t in_f, int64_t out_f) {
   if (out_f % 256 == 0 && in_f % 128 == 0) return 2;
@@ -1392,28 +1110,21 @@ inline long long spin_ticks_for_current_device() {
   return cached[dev];
 }
 
-template <int WM, int MODE, int STUDY = 0, int NST = 2, int KSPLIT = 1>
+template <int WM, int MODE>
 int launch_x6(const X6Params& p, hipStream_t stream) {
   using GEO = X6Geo<WM>;
-  constexpr int lds = X6Lds<WM, MODE, NST>::TOTAL;
+  constexpr int lds = X6Lds<WM, MODE>::TOTAL;
   static_assert(lds * (WM == 0 ? 3 : WM == 1 ? 2 : 1) <= 160 * 1024, "LDS of the workgroups of one CU");
   static_assert((size_t)8 * GEO::MAX_SPX * GEO::THREADS * GEO::ACC * 4 <= kPartialBytes && 8 * GEO::MAX_SPX < kErrWord, "workspace");
-  auto kern = x6_kernel<WM, MODE, STUDY, NST, KSPLIT>;
+  auto kern = x6_kernel<WM, MODE>;
   // an attribute of the code object ON THE CURRENT DEVICE: set per launch (idempotent, no data-path state)
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return (int)e;
   X6Params q = p;
-  q.ksplit = KSPLIT;
   q.ntm = p.rows_w / GEO::TM;
   q.ntn = (int)te_ceil_div(p.T, GEO::TT);
-  const int64_t tiles = (int64_t)q.ntm * q.ntn * q.ksplit;      // work items
-  int max_spx = p.small_grid ? 2 : GEO::MAX_SPX;
-#ifdef TE_X6_STUDY      // TE_X6_CUS_PER_XCD=<n <= 32>: leave 32 - n CUs of every XCD to the kernels of other streams (overlapped-step study)
-  if (const char* e_cu = getenv("TE_X6_CUS_PER_XCD")) {
-    const int n = atoi(e_cu);
-    if (n >= 1 && n <= 32 && !p.small_grid) max_spx = GEO::MAX_SPX * n / 32;
-  }
-#endif
+  const int64_t tiles = (int64_t)q.ntm * q.ntn;
+  const int max_spx = p.small_grid ? 2 : GEO::MAX_SPX;
   const int spx = (int)std::min<int64_t>(max_spx, std::max<int64_t>(1, te_ceil_div(tiles, 8)));
   // Stream-K or whole tiles?  With equal (tile, k) ranges the workgroups of an XCD sit at different k offsets of their
   // tiles and nothing one of them fetches is still in the 4 MB L2 when its neighbour needs it; cut at tile boundaries
@@ -1423,39 +1134,18 @@ int launch_x6(const X6Params& p, hipStream_t stream) {
   const double r = (double)tiles / (8.0 * spx);
   // TE_X6_WHOLE_TILES (the caller runs concurrent streams): whole tiles always -- the last round's idle CUs are not lost, the
   // other streams' kernels use them, while stream-K keeps ALL CUs for the whole launch at the slower skewed step
-  if (!q.whole_tiles_forced)
-    q.whole_tiles = ((p.prefer_whole || std::ceil(r) <= kWholeTileSlack * r) && !p.small_grid) ? 1 : 0;
+  q.whole_tiles = ((p.prefer_whole || std::ceil(r) <= kWholeTileSlack * r) && !p.small_grid) ? 1 : 0;
   if (!q.status) q.status = q.flags + kErrWord;
   q.spin_ticks = spin_ticks_for_current_device();
-  q.opt = kX6OptDefault;
-#ifdef TE_X6_STUDY      // measurement builds: TE_X6_OPT=<bits> overrides the schedule options, read per launch (benchmarks/x6_variants.py
-  if (const char* e_opt = getenv("TE_X6_OPT")) q.opt = atoi(e_opt);      // interleaves the variants in one process)
-#endif
   kern<<<dim3(8 * spx), dim3(GEO::THREADS), lds, stream>>>(q);
   return TE_OK;
 }
 
-// Two LDS stages everywhere; TE_X6_STAGES_3 (measurement) runs the 256 x 256 geometry with three (prefetch distance 2 behind
-// a raw barrier, 148 KiB).  Measured on the MI355X, ViT-B/16 batch 64 (profiles/r04_x6_variants.log): Z-pass and plain
-// products +-0.5 %, C-pass 7 % SLOWER -- a fill that misses the L2 is not what the loop waits for; the third stage's
-// traffic in flight costs more than its latency cover buys.
 template <int MODE>
-int launch_x6_mode(int wm, bool three_stages, const X6Params& p, hipStream_t stream) {
-#ifdef TE_X6_STUDY      // NST = 3 and KSPLIT = 2 are measured studies: compiled into study builds only
-  if constexpr (MODE != MODE_C && MODE != MODE_CI) {
-    if (p.seg_part && p.seg_flags && kseg_shape((int64_t)p.nks * 16, p.rows_w) == 2) {
-      if (wm == 2) return launch_x6<2, MODE, 0, 2, 2>(p, stream);
-      if (wm == 1) return launch_x6<1, MODE, 0, 2, 2>(p, stream);
-      return launch_x6<0, MODE, 0, 2, 2>(p, stream);
-    }
-  }
-  if (wm == 2 && three_stages) return launch_x6<2, MODE, 0, 3>(p, stream);
-#else
-  if (three_stages || p.seg_part || p.seg_flags) return TE_ERR_UNSUPPORTED;      // (the entry points reject the flags first)
-#endif
-  if (wm == 2) return launch_x6<2, MODE, 0, 2>(p, stream);
-  if (wm == 1) return launch_x6<1, MODE, 0, 2>(p, stream);
-  return launch_x6<0, MODE, 0, 2>(p, stream);
+int launch_x6_mode(int wm, const X6Params& p, hipStream_t stream) {
+  if (wm == 2) return launch_x6<2, MODE>(p, stream);
+  if (wm == 1) return launch_x6<1, MODE>(p, stream);
+  return launch_x6<0, MODE>(p, stream);
 }
 
 // Tile geometry of a launch (2 / 1 / 0 = 256 x 256 / 128 x 256 / 128 x 128; the result does not depend on it, bit for bit).
@@ -1465,18 +1155,16 @@ int launch_x6_mode(int wm, bool three_stages, const X6Params& p, hipStream_t str
 // 32): out_f = 768 at T = 12 608 / 16 384 (300 / 384 tiles of 128 x 256) runs 8-15 % faster on 128 x 128 tiles (Z-pass
 // 143 -> 121 us and 431 -> 368 us, products 119 -> 106, 401 -> 360, 313 -> 280, 408 -> 368 us); out_f = 1024 at T = 18 464
 // (584 tiles) is 10 % faster on 128 x 256.
-inline int choose_geo(int wm_max, int64_t T, int64_t rows_w, int pin, int min_tiles_256 = 256, bool small_ok = false,
-                      int ksplit = 1) {
+inline int choose_geo(int wm_max, int64_t T, int64_t rows_w, int pin, int min_tiles_256 = 256, bool small_ok = false) {
   if (pin == TE_X6_TILE_128) return 1;
   if (pin == TE_X6_TILE_256) return wm_max;
   if (pin == TE_X6_TILE_128x128) return 0;
   const int64_t t256 = te_ceil_div(T, 256);
   // 256-row tiles (one 512-thread workgroup per CU, every operand byte staged once for eight waves) where that gives
   // every CU a tile ...
-  if (wm_max == 2 && t256 * (rows_w / 256) * ksplit >= min_tiles_256) return 2;       // (work items: tiles x K segments)
+  if (wm_max == 2 && t256 * (rows_w / 256) >= min_tiles_256) return 2;
   // ... 128 x 256 (two workgroups per CU) while there are at least ~1.75 tiles per CU, else 128 x 128 (three per CU)
-  static const bool no_small = [] { const char* e = getenv("TE_X6_SMALL_TILES"); return e && atoi(e) == 0; }();      // (A/B knob)
-  if (small_ok && !no_small && t256 * (rows_w / 128) * ksplit < 448) return 0;
+  if (small_ok && t256 * (rows_w / 128) < 448) return 0;
   return 1;
 }
 
@@ -1562,21 +1250,13 @@ extern "C" int te_linear_x6_split_dual_f32(const float* A, int64_t rows, int64_t
   return TE_OK;
 }
 
-// GELU producers that write operand planes (gelu_split_kernel above); planes / planes_abs: te_linear_x6_planes_bytes(rows, K)
+// GELU producers that write operand planes (gelu_split_lds_kernel above); planes / planes_abs: te_linear_x6_planes_bytes(rows, K)
 extern "C" int te_gelu_backward_x6_planes_f32(const float* dy, const float* x, int64_t rows, int64_t K, void* planes,
                                               size_t planes_bytes_, te_stream_t stream_) {
   if (!dy || !x || !planes || rows < 1) return TE_ERR_INVALID_ARG;
   if (K < 16 || K % 16 || !te_aligned16(dy) || !te_aligned16(x) || rows > ((int64_t)1 << 26)) return TE_ERR_UNSUPPORTED;
   if (planes_bytes_ < planes_bytes(rows, K) || !te_aligned16(planes)) return TE_ERR_WORKSPACE;
   const dim3 grid((unsigned)te_ceil_div(rows, 32), (unsigned)te_ceil_div(K / 16, 8));
-#ifdef TE_STUDY
-  if (gelu_split_direct()) {
-    gelu_split_kernel<SRC_GELU_BWD><<<grid, dim3(256), 0, (hipStream_t)stream_>>>(dy, x, nullptr, (unsigned char*)planes,
-                                                                                 nullptr, rows, K);
-    TE_RETURN_IF_LAUNCH_FAILED();
-    return TE_OK;
-  }
-#endif
   gelu_split_lds_kernel<SRC_GELU_BWD><<<grid, dim3(256), 0, (hipStream_t)stream_>>>(dy, x, nullptr, (unsigned char*)planes,
                                                                                    nullptr, rows, K);
   TE_RETURN_IF_LAUNCH_FAILED();
@@ -1589,14 +1269,6 @@ extern "C" int te_gelu_forward_x6_planes_f32(const float* x, float* y, int64_t r
   if (K < 16 || K % 16 || !te_aligned16(x) || !te_aligned16(y) || rows > ((int64_t)1 << 26)) return TE_ERR_UNSUPPORTED;
   if (planes_bytes_ < planes_bytes(rows, K) || !te_aligned16(planes) || !te_aligned16(planes_abs)) return TE_ERR_WORKSPACE;
   const dim3 grid((unsigned)te_ceil_div(rows, 32), (unsigned)te_ceil_div(K / 16, 8));
-#ifdef TE_STUDY
-  if (gelu_split_direct()) {
-    gelu_split_kernel<SRC_GELU_FWD><<<grid, dim3(256), 0, (hipStream_t)stream_>>>(nullptr, x, y, (unsigned char*)planes,
-                                                                                 (unsigned char*)planes_abs, rows, K);
-    TE_RETURN_IF_LAUNCH_FAILED();
-    return TE_OK;
-  }
-#endif
   gelu_split_lds_kernel<SRC_GELU_FWD><<<grid, dim3(256), 0, (hipStream_t)stream_>>>(nullptr, x, y, (unsigned char*)planes,
                                                                                    (unsigned char*)planes_abs, rows, K);
   TE_RETURN_IF_LAUNCH_FAILED();
@@ -1605,15 +1277,14 @@ extern "C" int te_gelu_forward_x6_planes_f32(const float* x, float* y, int64_t r
 
 extern "C" size_t te_gemm_x6_workspace_bytes(int64_t T, int64_t K, int64_t M) {
   if (!te_gemm_x6_supported(T, K, M)) return 0;
-  return te_align_up(planes_bytes(T, K), 256) + kPartialBytes + kFlagBytes + seg_region_bytes(T, K, M);
+  return te_align_up(planes_bytes(T, K), 256) + kPartialBytes + kFlagBytes;
 }
 
 extern "C" int te_gemm_x6_f32(const float* X, const void* x_planes, const void* w_planes, const float* bias, float* out,
                               int64_t T, int64_t K, int64_t M, int flags, unsigned* status, void* ws, size_t ws_bytes,
                               te_stream_t stream_) {
   if ((!X && !x_planes) || !w_planes || !out) return TE_ERR_INVALID_ARG;
-  if ((flags & ~(3 | TE_X6_STAGES_3 | TE_X6_KSPLIT | TE_X6_WHOLE_TILES | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID)) != 0) return TE_ERR_INVALID_ARG;
-  if (study_flags_refused(flags)) return TE_ERR_UNSUPPORTED;
+  if ((flags & ~(3 | TE_X6_WHOLE_TILES | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID)) != 0) return TE_ERR_INVALID_ARG;
   if (!te_gemm_x6_supported(T, K, M)) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_gemm_x6_workspace_bytes(T, K, M) || !te_aligned16(ws)) return TE_ERR_WORKSPACE;
   if ((X && !te_aligned16(X)) || !te_aligned16(out) || !te_aligned16(w_planes) || (bias && !te_aligned16(bias)) ||
@@ -1628,28 +1299,17 @@ extern "C" int te_gemm_x6_f32(const float* X, const void* x_planes, const void* 
   unsigned* flag_words = (unsigned*)q;
   q += kFlagBytes;
   zero_words_kernel<<<dim3(kFlagBytes / 16 / 256), dim3(256), 0, stream>>>(reinterpret_cast<u32x4*>(flag_words));
-  float* seg_part = nullptr;
-  unsigned* seg_flags = nullptr;
-  if (kseg_rule(K, M, flags) == 2) {
-    seg_part = (float*)q;
-    seg_flags = (unsigned*)(q + seg_part_bytes(T, K, M));
-    zero_words_kernel<<<dim3((unsigned)(seg_flag_words(T, K, M) / 1024)), dim3(256), 0, stream>>>(reinterpret_cast<u32x4*>(seg_flags));
-  }
   if (!x_planes) {
     int rc = te_linear_x6_split_matrix_f32(X, T, K, 0, Xs, planes_bytes(T, K), stream_);
     if (rc != TE_OK) return rc;
     x_planes = Xs;
   }
-  int wm = choose_geo((M % 256 == 0) ? 2 : 1, T, M, flags & 3, 192, true, kseg_rule(K, M, flags));
+  const int wm = choose_geo((M % 256 == 0) ? 2 : 1, T, M, flags & 3, 192, true);
   X6Params p{};
   p.status = status;
   p.drop_handover = (flags & TE_X6_TEST_DROP_HANDOVER) ? 1 : 0;
   p.small_grid = (flags & TE_X6_TEST_SMALL_GRID) ? 1 : 0;
   p.prefer_whole = (flags & TE_X6_WHOLE_TILES) ? 1 : 0;
-#ifdef TE_X6_STUDY
-  if (const char* e = getenv("TE_X6_ORDER")) p.t_fast = atoi(e);
-  if (const char* e = getenv("TE_X6_SNAP")) p.whole_tiles = atoi(e), p.whole_tiles_forced = 1;
-#endif
   p.T = T;
   p.in_f = (int)K;
   p.out_f = (int)M;
@@ -1657,8 +1317,6 @@ extern "C" int te_gemm_x6_f32(const float* X, const void* x_planes, const void* 
   p.rows_w = (int)M;
   p.partial = partial;
   p.flags = flag_words;
-  p.seg_part = seg_part;
-  p.seg_flags = seg_flags;
   p.bias = bias;
   p.out = out;
   p.A = (const unsigned char*)w_planes;
@@ -1666,15 +1324,7 @@ extern "C" int te_gemm_x6_f32(const float* X, const void* x_planes, const void* 
   p.nks = (int)(K / 16);
   p.a_group_stride = (int64_t)p.nks * kRB;
   p.b_rb_stride = (int64_t)p.nks * kRB;
-  int rc;
-#ifdef TE_X6_STUDY
-  // study builds (benchmarks/x6_gemm_bench.py): TE_X6_G_WM pins the tile geometry, TE_X6_G_PROF=1 runs the time-stamped kernel
-  if (const char* e = getenv("TE_X6_G_WM")) wm = (atoi(e) == 2 && M % 256 == 0) ? 2 : 1;
-  const char* pe = getenv("TE_X6_G_PROF");
-  if (pe && atoi(pe) == 1) rc = (wm == 2) ? launch_x6<2, MODE_G, 5>(p, stream) : launch_x6<1, MODE_G, 5>(p, stream);
-  else
-#endif
-  rc = launch_x6_mode<MODE_G>(wm, (flags & TE_X6_STAGES_3) != 0, p, stream);
+  const int rc = launch_x6_mode<MODE_G>(wm, p, stream);
   if (rc != TE_OK) return rc;
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
@@ -1683,8 +1333,7 @@ extern "C" int te_gemm_x6_f32(const float* X, const void* x_planes, const void* 
 // workspace: |X| planes, S planes, the accumulators of cut tiles, flags (Z-pass, C-pass)
 extern "C" size_t te_linear_relprop_x6_workspace_bytes(int64_t T, int64_t in_f, int64_t out_f) {
   if (!te_linear_relprop_x6_supported(T, in_f, out_f)) return 0;
-  return te_align_up(planes_bytes(T, in_f), 256) + te_align_up(planes_bytes(T, out_f), 256) + kPartialBytes + 2 * kFlagBytes +
-         seg_region_bytes(T, in_f, out_f);
+  return te_align_up(planes_bytes(T, in_f), 256) + te_align_up(planes_bytes(T, out_f), 256) + kPartialBytes + 2 * kFlagBytes;
 }
 
 extern "C" int te_linear_relprop_x6_f32(const float* R, const float* r_scale, int64_t r_scale_stride,
@@ -1710,7 +1359,6 @@ extern "C" int te_linear_relprop_x6_f32(const float* R, const float* r_scale, in
   q += kPartialBytes;
   unsigned* flag_words = (unsigned*)q;
   q += 2 * kFlagBytes;
-  unsigned char* const seg_region = q;          // shared by the two passes (they run one after the other)
   const unsigned char* wz = (const unsigned char*)w_planes;
   const unsigned char* wc = wz + te_align_up(planes_bytes(out_f, in_f), 256);
 
@@ -1731,21 +1379,11 @@ extern "C" int te_linear_relprop_x6_f32(const float* R, const float* r_scale, in
   const int wm_max = pick_wm(in_f, out_f);
   const int pin_z = ((flags >> TE_X6_TILE_Z_SHIFT) & 3) ? ((flags >> TE_X6_TILE_Z_SHIFT) & 3) : (flags & 3);      // per-pass pins win
   const int pin_c = ((flags >> TE_X6_TILE_C_SHIFT) & 3) ? ((flags >> TE_X6_TILE_C_SHIFT) & 3) : (flags & 3);
-  const int wm_z = choose_geo(wm_max, T, out_f, pin_z, 256, true, kseg_rule(in_f, out_f, flags));
+  const int wm_z = choose_geo(wm_max, T, out_f, pin_z, 256, true);
   const int wm_c = choose_geo(wm_max, T, 2 * in_f, pin_c);
-#ifdef TE_X6_STUDY
-  const int study = (flags >> 5) & 7;      // study builds: run ablation `study` of the main loop instead
-  flags &= ~0xe0;
-#endif
-  if ((flags & ~(0x1f | TE_X6_STAGES_3 | TE_X6_KSPLIT | TE_X6_WHOLE_TILES | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID | 0x3c00)) != 0) return TE_ERR_INVALID_ARG;
-  if (study_flags_refused(flags)) return TE_ERR_UNSUPPORTED;
-  const bool three_stages = (flags & TE_X6_STAGES_3) != 0;
+  if ((flags & ~(0x1f | TE_X6_WHOLE_TILES | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID | 0x3c00)) != 0) return TE_ERR_INVALID_ARG;
   int wm = 0;
   X6Params p{};
-#ifdef TE_X6_STUDY
-  if (const char* e = getenv("TE_X6_ORDER")) p.t_fast = atoi(e);
-  if (const char* e = getenv("TE_X6_SNAP")) p.whole_tiles = atoi(e), p.whole_tiles_forced = 1;
-#endif
   p.T = T;
   p.in_f = (int)in_f;
   p.out_f = (int)out_f;
@@ -1776,24 +1414,7 @@ extern "C" int te_linear_relprop_x6_f32(const float* R, const float* r_scale, in
     wm = wm_z;
     p.rows_w = (int)out_f;
     p.flags = flag_words;
-    p.seg_part = nullptr, p.seg_flags = nullptr;
-    if (kseg_rule(in_f, out_f, flags) == 2) {
-      p.seg_part = (float*)seg_region;
-      p.seg_flags = (unsigned*)(seg_region + seg_part_bytes(T, in_f, out_f));
-      zero_words_kernel<<<dim3((unsigned)(seg_flag_words(T, in_f, out_f) / 1024)), dim3(256), 0, stream>>>(
-          reinterpret_cast<u32x4*>(p.seg_flags));
-    }
-#ifdef TE_X6_STUDY
-    if (wm == 2 && study == 1) rc = launch_x6<2, MODE_Z, 1>(p, stream);
-    else if (wm == 2 && study == 2) rc = launch_x6<2, MODE_Z, 2>(p, stream);
-    else if (wm == 2 && study == 3) rc = launch_x6<2, MODE_Z, 3>(p, stream);
-    else if (wm == 2 && study == 4) rc = launch_x6<2, MODE_Z, 4>(p, stream);
-    else if (wm == 2 && study == 5) rc = launch_x6<2, MODE_Z, 5>(p, stream);
-    else if (wm == 2 && study == 6) rc = launch_x6<2, MODE_Z, 6>(p, stream);
-    else if (wm == 1 && study == 5) rc = launch_x6<1, MODE_Z, 5>(p, stream);
-    else
-#endif
-    rc = launch_x6_mode<MODE_Z>(wm, three_stages, p, stream);
+    rc = launch_x6_mode<MODE_Z>(wm, p, stream);
     if (rc != TE_OK) return rc;
   }
   if (phases & TE_X6_PHASE_C) {   // C-pass: D[(i, +-)][t] = sum_j W+-[j][i] S[t][j]
@@ -1805,18 +1426,7 @@ extern "C" int te_linear_relprop_x6_f32(const float* R, const float* r_scale, in
     wm = wm_c;
     p.rows_w = (int)(2 * in_f);
     p.flags = flag_words + kFlagBytes / 4;
-    p.seg_part = nullptr, p.seg_flags = nullptr;       // (the C-pass has 2 in_f weight rows: never a launch the split helps)
-#ifdef TE_X6_STUDY
-    if (wm == 2 && study == 1) rc = launch_x6<2, MODE_C, 1>(p, stream);
-    else if (wm == 2 && study == 2) rc = launch_x6<2, MODE_C, 2>(p, stream);
-    else if (wm == 2 && study == 3) rc = launch_x6<2, MODE_C, 3>(p, stream);
-    else if (wm == 2 && study == 4) rc = launch_x6<2, MODE_C, 4>(p, stream);
-    else if (wm == 2 && study == 5) rc = launch_x6<2, MODE_C, 5>(p, stream);
-    else if (wm == 2 && study == 6) rc = launch_x6<2, MODE_C, 6>(p, stream);
-    else if (wm == 1 && study == 5) rc = launch_x6<1, MODE_C, 5>(p, stream);
-    else
-#endif
-    rc = launch_x6_mode<MODE_C>(wm, three_stages, p, stream);
+    rc = launch_x6_mode<MODE_C>(wm, p, stream);
     if (rc != TE_OK) return rc;
   }
   TE_RETURN_IF_LAUNCH_FAILED();
@@ -1831,8 +1441,8 @@ extern "C" int te_linear_relprop_x6_f32(const float* R, const float* r_scale, in
 //         -> MODE_CI: out += -beta (X+ . (S' W-) + X- . (S' W+))                                   18 (+18) bf16 product units
 //   lrp : four one-sided launches per half: MODE_Z1 on (W+, X+) -> S1, on (W-, X-) -> S2; MODE_X on (W+^T, S1) masked by X+,
 //         on (W-^T, S2) masked by X- (accumulating); the inhibitor half crosses the weight signs.   24 (+24) units
-// Every product is an x6 product (six bf16 partial products, fp32 accumulation), every output one k-ordered chain (two where
-// kseg_rule splits K): bitwise batch-invariant like the default rule.
+// Every product is an x6 product (six bf16 partial products, fp32 accumulation), every output one k-ordered chain: bitwise
+// batch-invariant like the default rule.
 extern "C" int te_linear_relprop_x6_general_supported(int64_t T, int64_t in_f, int64_t out_f, int variant) {
   if (!te_linear_relprop_x6_supported(T, in_f, out_f)) return 0;
   if (variant == TE_VARIANT_LRP) return (in_f % 128 == 0) ? 1 : 0;       // the masked products have in_f weight-side rows
@@ -1868,7 +1478,7 @@ extern "C" size_t te_linear_relprop_x6_general_workspace_bytes(int64_t T, int64_
   if (!te_linear_relprop_x6_general_supported(T, in_f, out_f, variant)) return 0;
   // two plane sets of the input side (|X|, or X+ and X-), two of the output side (S / S', or S1 and S2)
   return 2 * te_align_up(planes_bytes(T, in_f), 256) + 2 * te_align_up(planes_bytes(T, out_f), 256) + kPartialBytes +
-         kGeneralPasses * kFlagBytes + std::max(seg_region_bytes(T, in_f, out_f), seg_region_bytes(T, out_f, in_f));
+         kGeneralPasses * kFlagBytes;
 }
 
 extern "C" int te_linear_relprop_x6_general_f32(const float* R, const float* r_scale, int64_t r_scale_stride,
@@ -1888,8 +1498,7 @@ extern "C" int te_linear_relprop_x6_general_f32(const float* R, const float* r_s
       (bias && !te_aligned16(bias)) || (x_abs_planes && !te_aligned16(x_abs_planes)))
     return TE_ERR_UNSUPPORTED;
   if (r_scale && (rows_per_sample <= 0 || rows_per_sample > 0x7fffffff || T % rows_per_sample)) return TE_ERR_INVALID_ARG;
-  if ((flags & ~(3 | TE_X6_STAGES_3 | TE_X6_KSPLIT | TE_X6_WHOLE_TILES | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID)) != 0) return TE_ERR_INVALID_ARG;
-  if (study_flags_refused(flags)) return TE_ERR_UNSUPPORTED;
+  if ((flags & ~(3 | TE_X6_WHOLE_TILES | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID)) != 0) return TE_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   const float beta = alpha - 1.0f;
   unsigned char* q = (unsigned char*)ws;
@@ -1905,7 +1514,6 @@ extern "C" int te_linear_relprop_x6_general_f32(const float* R, const float* r_s
   q += kPartialBytes;
   unsigned* flag_words = (unsigned*)q;
   q += kGeneralPasses * kFlagBytes;
-  unsigned char* const seg_region = q;
   zero_words_kernel<<<dim3(kGeneralPasses * kFlagBytes / 16 / 256), dim3(256), 0, stream>>>(reinterpret_cast<u32x4*>(flag_words));
 
   X6Params base{};
@@ -1928,19 +1536,9 @@ extern "C" int te_linear_relprop_x6_general_f32(const float* R, const float* r_s
   base.drop_handover = (flags & TE_X6_TEST_DROP_HANDOVER) ? 1 : 0;
   base.small_grid = (flags & TE_X6_TEST_SMALL_GRID) ? 1 : 0;
   base.prefer_whole = (flags & TE_X6_WHOLE_TILES) ? 1 : 0;
-  const bool three_stages = (flags & TE_X6_STAGES_3) != 0;
   const int pin = flags & 3;
   int pass = 0;
   // one launch: a Z-like pass (K = in_f, weight-side rows = out_f) or an output-side pass (K = out_f)
-  auto seg_setup = [&](X6Params& p, int64_t K, int64_t rows_w) {
-    p.seg_part = nullptr, p.seg_flags = nullptr;
-    if (kseg_rule(K, rows_w, flags) == 2) {
-      p.seg_part = (float*)seg_region;
-      p.seg_flags = (unsigned*)(seg_region + seg_part_bytes(T, K, rows_w));
-      zero_words_kernel<<<dim3((unsigned)(seg_flag_words(T, K, rows_w) / 1024)), dim3(256), 0, stream>>>(
-          reinterpret_cast<u32x4*>(p.seg_flags));
-    }
-  };
   auto z_like = [&](auto mode_tag, const unsigned char* A, const unsigned char* B, unsigned char* S) -> int {
     constexpr int MODE = decltype(mode_tag)::value;
     X6Params p = base;
@@ -1951,9 +1549,8 @@ extern "C" int te_linear_relprop_x6_general_f32(const float* R, const float* r_s
     p.b_rb_stride = (int64_t)p.nks * kRB;
     p.rows_w = (int)out_f;
     p.flags = flag_words + (size_t)(pass++) * (kFlagBytes / 4);
-    seg_setup(p, in_f, out_f);
-    const int wm = choose_geo(pick_wm(in_f, out_f), T, out_f, pin, 256, true, kseg_rule(in_f, out_f, flags));
-    return launch_x6_mode<MODE>(wm, three_stages, p, stream);
+    const int wm = choose_geo(pick_wm(in_f, out_f), T, out_f, pin, 256, true);
+    return launch_x6_mode<MODE>(wm, p, stream);
   };
   int rc;
   if (!lrp) {
@@ -1975,7 +1572,7 @@ extern "C" int te_linear_relprop_x6_general_f32(const float* R, const float* r_s
       p.rows_w = (int)(2 * in_f);
       p.scale = scale;
       p.flags = flag_words + (size_t)(pass++) * (kFlagBytes / 4);
-      return launch_x6_mode<MODE>(choose_geo(pick_wm(in_f, out_f), T, 2 * in_f, pin), three_stages, p, stream);
+      return launch_x6_mode<MODE>(choose_geo(pick_wm(in_f, out_f), T, 2 * in_f, pin), p, stream);
     };
     rc = z_like(std::integral_constant<int, MODE_Z>{}, wz, (const unsigned char*)x_abs_planes, Sa);
     if (rc != TE_OK) return rc;
@@ -2005,9 +1602,8 @@ extern "C" int te_linear_relprop_x6_general_f32(const float* R, const float* r_s
       p.rows_w = (int)in_f;
       p.scale = scale, p.accum = accum, p.x_sign = sign;
       p.flags = flag_words + (size_t)(pass++ % kGeneralPasses) * (kFlagBytes / 4);
-      seg_setup(p, out_f, in_f);
-      const int wm = choose_geo((in_f % 256 == 0) ? 2 : 1, T, in_f, pin, 192, true, kseg_rule(out_f, in_f, flags));
-      return launch_x6_mode<MODE_X>(wm, three_stages, p, stream);
+      const int wm = choose_geo((in_f % 256 == 0) ? 2 : 1, T, in_f, pin, 192, true);
+      return launch_x6_mode<MODE_X>(wm, p, stream);
     };
     for (int half = 0; half < (beta != 0.0f ? 2 : 1); ++half) {
       // half 0: f(pw, nw, px, nx) (activator); half 1: f(nw, pw, px, nx) (inhibitor) -- the weight signs cross
