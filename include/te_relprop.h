@@ -501,7 +501,7 @@ int te_perturb_f32(const float* vis, const float* data, float* out, int64_t B, i
                    const int64_t* ks, int64_t n_steps, const float* mean, const float* std_, void* ws,
                    size_t ws_bytes, te_stream_t stream);
 
-/* ---- bf16 operands (a bf16 model: model.to(torch.bfloat16)) -----------------------------------------------
+/* ---- bf16 operands (a bf16 ViT / DeiT or BERT model: model.to(torch.bfloat16)) ----------------------------
  * The rules of variant "ours", alpha = 1, evaluated in fp32 on the model's own bf16 tensors (te_bf16_t, read exactly:
  * bf16 -> fp32 is exact).  Relevance operands and outputs, safe_divide, per-sample sums and factors are fp32 as in the
  * _f32 entry points; the arguments mean what they mean there.  csrc/te_bf16.hip (GEMM-shaped rules, bf16 MFMAs) and
@@ -549,6 +549,15 @@ int te_add_relprop_bf16(const float* R, const te_bf16_t* X0, const te_bf16_t* X1
 int te_add_relprop_deferred_bf16(const float* R, const te_bf16_t* X0, const te_bf16_t* X1, float* a, float* b,
                                  float* fac, int64_t B, int64_t n, int64_t x1_batch_stride, void* ws, size_t ws_bytes,
                                  te_stream_t stream);
+/* The broadcast-mask Add of BERT self-attention (te_add_bcast_relprop_f32 / _deferred_f32) with bf16 X0 [B,H,N,N] and
+ * mask [B,N]: same arguments, workspace (te_add_bcast_relprop_workspace_bytes), N <= 2048 and validation; variant ours
+ * only.  Same arithmetic and summation order: the _f32 call's bits on exact fp32 copies of X0 and the mask. */
+int te_add_bcast_relprop_bf16(const float* R, const te_bf16_t* X0, const te_bf16_t* mask, float* out0, float* out1,
+                              int64_t B, int64_t H, int64_t N, int variant, void* ws, size_t ws_bytes,
+                              te_stream_t stream);
+int te_add_bcast_relprop_deferred_bf16(const float* R, const te_bf16_t* X0, const te_bf16_t* mask, float* a,
+                                       float* out1, float* fac, int64_t B, int64_t H, int64_t N, void* ws,
+                                       size_t ws_bytes, te_stream_t stream);
 int te_clone_relprop_bf16(const float* R0, const float* R1, const float* R2, const te_bf16_t* X, float* out, int64_t n,
                           te_stream_t stream);
 int te_clone_relprop_scaled_bf16(const float* R0, const float* s0, int64_t s0_stride, const float* R1, const float* s1,

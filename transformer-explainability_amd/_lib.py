@@ -134,6 +134,8 @@ SIGNATURES = {
                                        _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _F, _I, _P, _SZ, _P]),
     "te_add_relprop_bf16": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _P, _SZ, _P]),
     "te_add_relprop_deferred_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
+    "te_add_bcast_relprop_bf16": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _P, _SZ, _P]),
+    "te_add_bcast_relprop_deferred_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
     "te_clone_relprop_bf16": (_I, [_P, _P, _P, _P, _P, _I64, _P]),
     "te_clone_relprop_scaled_bf16": (_I, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _P]),
     "te_index_select_relprop_bf16": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _P]),

@@ -374,8 +374,9 @@ def make_bert_module(L):
             device = input_ids.device if input_ids is not None else inputs_embeds.device
             if attention_mask is None:
                 attention_mask = torch.ones(shape, device=device)
-            # transformers 3.5.1 get_extended_attention_mask: (1 - mask)[:, None, None, :] * -10000
-            ext = (1.0 - attention_mask[:, None, None, :].to(torch.float32)) * -10000.0
+            # transformers 3.5.1 get_extended_attention_mask: the mask cast to the parameters' dtype, then
+            # (1 - mask)[:, None, None, :] * -10000 in that dtype (bf16: 0 / -9984)
+            ext = (1.0 - attention_mask[:, None, None, :].to(next(self.parameters()).dtype)) * -10000.0
             emb = self.embeddings(input_ids=input_ids, position_ids=position_ids, token_type_ids=token_type_ids,
                                   inputs_embeds=inputs_embeds)
             seq = self.encoder(emb, attention_mask=ext, head_mask=head_mask)[0]

@@ -387,8 +387,12 @@ __global__ __launch_bounds__(kTC) void attn_bwd_cols_kernel(const float* __restr
   const int j0 = jt * TI;
   if (j0 >= N) return;
   const int lane = threadIdx.x & 63, lr = lane & 31, kh = lane >> 5;
-  const float* a_bh = attn + (int64_t)bh * N * N + j0 + lr;
-  const float* g_bh = dattn + (int64_t)bh * N * N + j0 + lr;
+  const bool key_ok = j0 + lr < N;
+  // lanes past the last key read column N - 1 (their products are zeroed below): the last (b, h) of attn / dattn ends at
+  // column N - 1 of row N - 1, so column j0 + lr would read past the end of the buffer
+  const int jc = key_ok ? j0 + lr : N - 1;
+  const float* a_bh = attn + (int64_t)bh * N * N + jc;
+  const float* g_bh = dattn + (int64_t)bh * N * N + jc;
   const float* rd = rowdot + (int64_t)bh * N;
   const float* do_bh = dout + b * dos.sb + h * dos.sh + lr;
   const float* q_bh = q + b * qs.sb + h * qs.sh + lr;
@@ -400,7 +404,6 @@ __global__ __launch_bounds__(kTC) void attn_bwd_cols_kernel(const float* __restr
       av[d][e] = 0.0f;
       ak[d][e] = 0.0f;
     }
-  const bool key_ok = j0 + lr < N;
   const int npair = (N + 1) >> 1;
   // U steps of operands are requested before the first of their MFMAs: the loop is bound by the latency of its loads
   // otherwise (measured: 29 % of the MFMA rate with two steps in flight)

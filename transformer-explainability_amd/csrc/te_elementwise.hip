@@ -234,28 +234,31 @@ __global__ __launch_bounds__(kThreads) void add_apply_kernel(
 // ------------------------------------------------------------------------------------------------
 // Broadcast-mask Add of BERT self-attention (BERT.py:342,386-388).  Rows are the H*N (h,i) pairs of a
 // sample, columns j index the key token / mask entry.  Each thread owns columns j = tid + 256*c.
+// TX: the operand type of X0 and the mask (fp32, or bf16 read through ldx); R, the fp64 column / sample sums, the
+// factors and the outputs are fp32 / fp64 for both, in the same order, so a bf16 call gives the fp32 call's bits on
+// exact fp32 copies of its operands.
 // ------------------------------------------------------------------------------------------------
 constexpr int kMaxColsPerThread = 8;  // N <= 2048
 
 // STORE: also write the unscaled a = X0 . S (deferred form: the per-sample factor goes to the consumer, the QK rule)
-template <bool STORE>
+template <bool STORE, typename TX>
 __global__ __launch_bounds__(kThreads) void addb_sums_kernel(
-    const float* __restrict__ R, const float* __restrict__ X0, const float* __restrict__ mask,
+    const float* __restrict__ R, const TX* __restrict__ X0, const TX* __restrict__ mask,
     double* __restrict__ partial, float* __restrict__ a_out, int64_t rows, int64_t N, int64_t rows_per_block) {
   __shared__ double smem[3 * (kThreads / 64)];
   const int64_t b = blockIdx.y;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r1 = min(rows, r0 + rows_per_block);
   const float* r = R + b * rows * N;
-  const float* x0 = X0 + b * rows * N;
-  const float* m = mask + b * N;
+  const TX* x0 = X0 + b * rows * N;
+  const TX* m = mask + b * N;
   double csum[kMaxColsPerThread];
   float mv[kMaxColsPerThread];
 #pragma unroll
   for (int c = 0; c < kMaxColsPerThread; ++c) {
     csum[c] = 0.0;
     const int64_t j = threadIdx.x + (int64_t)c * kThreads;
-    mv[c] = (j < N) ? m[j] : 0.0f;
+    mv[c] = (j < N) ? ldx(m + j) : 0.0f;
   }
   double sa = 0.0, sr = 0.0, dummy = 0.0;
   float* ao = STORE ? a_out + b * rows * N : nullptr;
@@ -270,7 +273,7 @@ __global__ __launch_bounds__(kThreads) void addb_sums_kernel(
         for (int u = 0; u < RU; ++u) {
           const bool ok = row + u < r1;
           rv[u] = ok ? r[(row + u) * N + j] : 0.0f;
-          av[u] = ok ? x0[(row + u) * N + j] : 0.0f;
+          av[u] = ok ? ldx(x0 + ((row + u) * N + j)) : 0.0f;
         }
 #pragma unroll
         for (int u = 0; u < RU; ++u)
@@ -301,8 +304,9 @@ __global__ __launch_bounds__(kThreads) void addb_sums_kernel(
 // One block per sample: fold the partials, form b_j = mask_j * C1_j, the three sums and the factors.
 // fac[b] = {fa, fb}; bvec[b][j] = b_j (unscaled).
 // out1 (optional): the mask's relevance b_j * fb, written here in the deferred form (addb_apply_kernel writes it else)
+template <typename TX>
 __global__ __launch_bounds__(kThreads) void addb_finalize_kernel(
-    const double* __restrict__ partial, const float* __restrict__ mask, float* __restrict__ fac,
+    const double* __restrict__ partial, const TX* __restrict__ mask, float* __restrict__ fac,
     float* __restrict__ bvec, int64_t N, int nblk, int ours, float* __restrict__ out1) {
   __shared__ double smem[3 * (kThreads / 64)];
   __shared__ float fb_s;
@@ -312,7 +316,7 @@ __global__ __launch_bounds__(kThreads) void addb_finalize_kernel(
   for (int64_t j = threadIdx.x; j < N; j += kThreads) {
     double c1 = 0.0;
     for (int p = 0; p < nblk; ++p) c1 += base[(int64_t)p * (N + 2) + 2 + j];
-    const float bj = mask[b * N + j] * (float)c1;
+    const float bj = ldx(mask + (b * N + j)) * (float)c1;
     bvec[b * N + j] = bj;
     sb += (double)bj;
   }
@@ -335,8 +339,9 @@ __global__ __launch_bounds__(kThreads) void addb_finalize_kernel(
   }
 }
 
+template <typename TX>
 __global__ __launch_bounds__(kThreads) void addb_apply_kernel(
-    const float* __restrict__ R, const float* __restrict__ X0, const float* __restrict__ mask,
+    const float* __restrict__ R, const TX* __restrict__ X0, const TX* __restrict__ mask,
     const float* __restrict__ fac, const float* __restrict__ bvec, float* __restrict__ out0,
     float* __restrict__ out1, int64_t rows, int64_t N, int64_t rows_per_block) {
   const int64_t b = blockIdx.y;
@@ -344,8 +349,8 @@ __global__ __launch_bounds__(kThreads) void addb_apply_kernel(
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r1 = min(rows, r0 + rows_per_block);
   const float* r = R + b * rows * N;
-  const float* x0 = X0 + b * rows * N;
-  const float* m = mask + b * N;
+  const TX* x0 = X0 + b * rows * N;
+  const TX* m = mask + b * N;
   float* o0 = out0 + b * rows * N;
   if (out1 != nullptr && blockIdx.x == 0) {
     for (int64_t j = threadIdx.x; j < N; j += kThreads) out1[b * N + j] = bvec[b * N + j] * fb;
@@ -354,14 +359,14 @@ __global__ __launch_bounds__(kThreads) void addb_apply_kernel(
 #pragma unroll
   for (int c = 0; c < kMaxColsPerThread; ++c) {
     const int64_t j = threadIdx.x + (int64_t)c * kThreads;
-    mv[c] = (j < N) ? m[j] : 0.0f;
+    mv[c] = (j < N) ? ldx(m + j) : 0.0f;
   }
   for (int64_t row = r0; row < r1; ++row) {
 #pragma unroll
     for (int c = 0; c < kMaxColsPerThread; ++c) {
       const int64_t j = threadIdx.x + (int64_t)c * kThreads;
       if (j < N) {
-        const float rv = r[row * N + j], av = x0[row * N + j];
+        const float rv = r[row * N + j], av = ldx(x0 + (row * N + j));
         const float s = te_sd(rv, av + mv[c]);
         o0[row * N + j] = (av * s) * fa;
       }
@@ -686,12 +691,15 @@ extern "C" size_t te_add_bcast_relprop_workspace_bytes(int64_t B, int64_t H, int
   return part + fac + bvec;
 }
 
-extern "C" int te_add_bcast_relprop_f32(const float* R, const float* X0, const float* mask,
-                                        float* out0, float* out1, int64_t B, int64_t H, int64_t N,
-                                        int variant, void* ws, size_t ws_bytes, te_stream_t stream_) {
+namespace {
+// TX = float: te_add_bcast_relprop_f32; TX = te_bf16_t: the bf16 form, variant ours only (as every bf16 rule)
+template <typename TX>
+int add_bcast_relprop(const float* R, const TX* X0, const TX* mask, float* out0, float* out1, int64_t B, int64_t H,
+                      int64_t N, int variant, void* ws, size_t ws_bytes, te_stream_t stream_) {
   if (!R || !X0 || !mask || !out0 || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
   const int var = variant & 0xff;
   if (var != TE_VARIANT_OURS && var != TE_VARIANT_LRP) return TE_ERR_INVALID_ARG;
+  if (sizeof(TX) != sizeof(float) && var != TE_VARIANT_OURS) return TE_ERR_UNSUPPORTED;
   if (N > (int64_t)kMaxColsPerThread * kThreads) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_add_bcast_relprop_workspace_bytes(B, H, N)) return TE_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
@@ -705,20 +713,17 @@ extern "C" int te_add_bcast_relprop_f32(const float* R, const float* X0, const f
   p += te_align_up((size_t)B * 2 * sizeof(float), 256);
   float* bvec = (float*)p;
   dim3 grid(nblk, (unsigned)B), block(kThreads);
-  addb_sums_kernel<false><<<grid, block, 0, stream>>>(R, X0, mask, partial, nullptr, rows, N, rpb);
-  addb_finalize_kernel<<<dim3((unsigned)B), block, 0, stream>>>(partial, mask, fac, bvec, N, nblk,
-                                                               var == TE_VARIANT_OURS ? 1 : 0, nullptr);
-  addb_apply_kernel<<<grid, block, 0, stream>>>(R, X0, mask, fac, bvec, out0, out1, rows, N, rpb);
+  addb_sums_kernel<false, TX><<<grid, block, 0, stream>>>(R, X0, mask, partial, nullptr, rows, N, rpb);
+  addb_finalize_kernel<TX><<<dim3((unsigned)B), block, 0, stream>>>(partial, mask, fac, bvec, N, nblk,
+                                                                   var == TE_VARIANT_OURS ? 1 : 0, nullptr);
+  addb_apply_kernel<TX><<<grid, block, 0, stream>>>(R, X0, mask, fac, bvec, out0, out1, rows, N, rpb);
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
 }
 
-// Deferred form (variant ours): ONE pass over R and X0 writes the unscaled a = X0 . S; fac [B,2] = {fa, fb} goes to the
-// consumer (te_matmul_relprop_qk_fwd_scaled_f32 multiplies the relevance operand by fa in its S tile); out1 [B,N]
-// (optional) = the mask's relevance, already scaled.  a * fa is bitwise te_add_bcast_relprop_f32's out0.
-extern "C" int te_add_bcast_relprop_deferred_f32(const float* R, const float* X0, const float* mask, float* a,
-                                                 float* out1, float* fac, int64_t B, int64_t H, int64_t N, void* ws,
-                                                 size_t ws_bytes, te_stream_t stream_) {
+template <typename TX>
+int add_bcast_relprop_deferred(const float* R, const TX* X0, const TX* mask, float* a, float* out1, float* fac,
+                               int64_t B, int64_t H, int64_t N, void* ws, size_t ws_bytes, te_stream_t stream_) {
   if (!R || !X0 || !mask || !a || !fac || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
   if (N > (int64_t)kMaxColsPerThread * kThreads || B > 65535) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_add_bcast_relprop_workspace_bytes(B, H, N)) return TE_ERR_WORKSPACE;
@@ -732,10 +737,38 @@ extern "C" int te_add_bcast_relprop_deferred_f32(const float* R, const float* X0
   p += te_align_up((size_t)B * 2 * sizeof(float), 256);        // (the two-pass form's factor slot: unused here)
   float* bvec = (float*)p;
   dim3 grid(nblk, (unsigned)B), block(kThreads);
-  addb_sums_kernel<true><<<grid, block, 0, stream>>>(R, X0, mask, partial, a, rows, N, rpb);
-  addb_finalize_kernel<<<dim3((unsigned)B), block, 0, stream>>>(partial, mask, fac, bvec, N, nblk, 1, out1);
+  addb_sums_kernel<true, TX><<<grid, block, 0, stream>>>(R, X0, mask, partial, a, rows, N, rpb);
+  addb_finalize_kernel<TX><<<dim3((unsigned)B), block, 0, stream>>>(partial, mask, fac, bvec, N, nblk, 1, out1);
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
+}
+}  // namespace
+
+extern "C" int te_add_bcast_relprop_f32(const float* R, const float* X0, const float* mask,
+                                        float* out0, float* out1, int64_t B, int64_t H, int64_t N,
+                                        int variant, void* ws, size_t ws_bytes, te_stream_t stream_) {
+  return add_bcast_relprop(R, X0, mask, out0, out1, B, H, N, variant, ws, ws_bytes, stream_);
+}
+
+extern "C" int te_add_bcast_relprop_bf16(const float* R, const te_bf16_t* X0, const te_bf16_t* mask, float* out0,
+                                         float* out1, int64_t B, int64_t H, int64_t N, int variant, void* ws,
+                                         size_t ws_bytes, te_stream_t stream_) {
+  return add_bcast_relprop(R, X0, mask, out0, out1, B, H, N, variant, ws, ws_bytes, stream_);
+}
+
+// Deferred form (variant ours): ONE pass over R and X0 writes the unscaled a = X0 . S; fac [B,2] = {fa, fb} goes to the
+// consumer (te_matmul_relprop_qk_fwd_scaled_f32 multiplies the relevance operand by fa in its S tile); out1 [B,N]
+// (optional) = the mask's relevance, already scaled.  a * fa is bitwise te_add_bcast_relprop_f32's out0.
+extern "C" int te_add_bcast_relprop_deferred_f32(const float* R, const float* X0, const float* mask, float* a,
+                                                 float* out1, float* fac, int64_t B, int64_t H, int64_t N, void* ws,
+                                                 size_t ws_bytes, te_stream_t stream_) {
+  return add_bcast_relprop_deferred(R, X0, mask, a, out1, fac, B, H, N, ws, ws_bytes, stream_);
+}
+
+extern "C" int te_add_bcast_relprop_deferred_bf16(const float* R, const te_bf16_t* X0, const te_bf16_t* mask, float* a,
+                                                  float* out1, float* fac, int64_t B, int64_t H, int64_t N, void* ws,
+                                                  size_t ws_bytes, te_stream_t stream_) {
+  return add_bcast_relprop_deferred(R, X0, mask, a, out1, fac, B, H, N, ws, ws_bytes, stream_);
 }
 
 // ---- Clone ------------------------------------------------------------------------------------------

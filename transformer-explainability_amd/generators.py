@@ -404,8 +404,9 @@ class Generator:
         min-max normalised over the whole [N, N] map, CLS row with the CLS slot zeroed."""
         layers = self._explain(input_ids, attention_mask, index, lowest_layer=len(self.model.bert.encoder.layer) - 1)
         sa = layers[-1].attention.self
-        cam = sa.get_attn().detach()
-        grad = sa.get_attn_gradients().mean(dim=[2, 3], keepdim=True)
+        # (a bf16 model: evaluated in fp32 on its attention and gradient, like the relprop maps; a no-op for fp32)
+        cam = sa.get_attn().detach().float()
+        grad = sa.get_attn_gradients().float().mean(dim=[2, 3], keepdim=True)
         cam = (cam * grad).mean(dim=1).clamp(min=0)
         lo = cam.amin(dim=(1, 2), keepdim=True)
         hi = cam.amax(dim=(1, 2), keepdim=True)

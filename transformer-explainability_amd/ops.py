@@ -59,9 +59,9 @@ def _variant(v) -> int:
 
 
 # The dtypes the kernels take: fp32 everywhere; bf16 OPERANDS (activations, weights, attention gradients of a bf16 model)
-# on the rules of a ViT / DeiT explanation (variant ours, alpha = 1), with fp32 relevance (the *_bf16 paths below).
-DTYPES_MSG = ("relprop kernels take float32 tensors, or bfloat16 operands with float32 relevance on the ViT rules of "
-              "variant 'ours' with alpha = 1")
+# on the rules of a ViT / DeiT or BERT explanation (variant ours, alpha = 1), with fp32 relevance (the *_bf16 paths below).
+DTYPES_MSG = ("relprop kernels take float32 tensors, or bfloat16 operands with float32 relevance on the ViT / DeiT and "
+              "BERT rules of variant 'ours' with alpha = 1")
 
 
 def _prep(t: Tensor) -> Tensor:
@@ -924,6 +924,11 @@ def gelu_backward(dy: Tensor, x: Tensor) -> Tensor:
 USE_DEFERRED_ADD = True
 
 
+def _is_bcast_mask(X0: Tensor, X1: Tensor) -> bool:
+    """X1 is the BERT broadcast mask [B,1,1,N] (or [1,1,1,N]) against the scores X0 [B,H,N,N] (BERT.py:342,386-388)."""
+    return X1.dim() == 4 and X0.dim() == 4 and X1.shape[1] == 1 and X1.shape[2] == 1 and X0.shape[1] * X0.shape[2] != 1
+
+
 def add_relprop(R: Tensor, X0: Tensor, X1: Tensor, variant="ours", deferred: bool = False):
     """Add.relprop with per-sample sums.  dim 0 is the batch.  X1 has X0's shape, or batch 1 (shared by
     all samples), or is the BERT broadcast mask [B,1,1,N] against X0 [B,H,N,N].
@@ -934,7 +939,7 @@ def add_relprop(R: Tensor, X0: Tensor, X1: Tensor, variant="ours", deferred: boo
     B = X0.shape[0]
     R, X0 = _c(R), _c(X0)
     n = X0[0].numel()
-    if X1.dim() == 4 and X0.dim() == 4 and X1.shape[1] == 1 and X1.shape[2] == 1 and X0.shape[1] * X0.shape[2] != 1:
+    if _is_bcast_mask(X0, X1):
         H, N = X0.shape[1], X0.shape[3]
         mask = _c(X1).reshape(X1.shape[0], N)
         if mask.shape[0] == 1 and B > 1:
@@ -1294,12 +1299,38 @@ def matmul_relprop_qk_bf16(R, q: Tensor, k: Tensor, out_scale: float = 1.0, cam_
 
 
 def add_relprop_bf16(R: Tensor, X0: Tensor, X1: Tensor, variant="ours", deferred: bool = False):
-    """Add.relprop with bf16 operands (same shape, or X1 of batch 1); R and the results fp32 (add_relprop)."""
+    """Add.relprop with bf16 operands (same shape, X1 of batch 1, or the BERT broadcast mask [B,1,1,N] / [1,1,1,N]
+    against X0 [B,H,N,N]); R and the results fp32, returned as add_relprop returns them."""
     _bf16_rule(variant, 1.0, "Add.relprop")
     X0, X1 = _c16(X0), _c16(X1)
     R = _c(R)
     B = X0.shape[0]
     n = X0[0].numel()
+    if _is_bcast_mask(X0, X1):
+        H, N = X0.shape[1], X0.shape[3]
+        if X0.shape[2] != N or X1.shape[3] != N or X1.shape[0] not in (1, B) or R.numel() != X0.numel():
+            raise _lib.TeError(f"Add.relprop (bf16): mask {tuple(X1.shape)} against scores {tuple(X0.shape)} with "
+                               f"relevance {tuple(R.shape)}: expected [B|1,1,1,N], [B,H,N,N], [B,H,N,N]")
+        mask = X1.reshape(X1.shape[0], N)
+        if mask.shape[0] == 1 and B > 1:
+            mask = mask.expand(B, N).contiguous()
+        out0 = torch.empty(X0.shape, dtype=torch.float32, device=X0.device)
+        out1 = torch.empty((B, 1, 1, N), dtype=torch.float32, device=X0.device)
+        nb = B * (10.0 * H * N * N + 6.0 * N)
+        if deferred:
+            fac = torch.empty((B, 2), dtype=torch.float32, device=X0.device)
+            with _on_device(X0) as lib, _timed("add_bcast_mask_deferred_bf16", 0.0, nb):
+                ws = _ws(lib.te_add_bcast_relprop_workspace_bytes(B, H, N), X0)
+                _lib.check(lib.te_add_bcast_relprop_deferred_bf16(_ptr(R), _ptr(X0), _ptr(mask), _ptr(out0), _ptr(out1),
+                                                                  _ptr(fac), B, H, N, _ptr(ws), ws.numel(), _stream(X0)),
+                           "te_add_bcast_relprop_deferred_bf16")
+            return Deferred(out0, fac[:, 0]), out1
+        with _on_device(X0) as lib, _timed("add_bcast_mask_bf16", 0.0, nb):
+            ws = _ws(lib.te_add_bcast_relprop_workspace_bytes(B, H, N), X0)
+            _lib.check(lib.te_add_bcast_relprop_bf16(_ptr(R), _ptr(X0), _ptr(mask), _ptr(out0), _ptr(out1), B, H, N,
+                                                     _variant(variant), _ptr(ws), ws.numel(), _stream(X0)),
+                       "te_add_bcast_relprop_bf16")
+        return out0, out1
     if X1.shape == X0.shape:
         x1_bs = n
     elif X1.shape[0] == 1 and X1.shape[1:] == X0.shape[1:]:
