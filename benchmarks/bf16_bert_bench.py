@@ -4,7 +4,8 @@ inputs of test_config3_bert_base_512_batch32) in one process on the same inputs.
     python benchmarks/bf16_bert_bench.py [--batch 32] [--steps 10] [--warmup 3] [--rules]
 
 Prints one JSON line: sequences/s of Generator(model).generate_LRP(ids, mask, start_layer=0) for the model in bf16 (the bf16
-relprop kernels; forward and backward on stock PyTorch), eager and replayed as a GraphedCall, and in fp32 with the package
+relprop kernels; forward and backward on stock PyTorch, and again with the fused bf16 producers of csrc/te_attn_bf16.hip,
+ops.USE_FUSED_PRODUCERS), eager and replayed as a GraphedCall, and in fp32 with the package
 defaults (eager) and with the fused fp32 producers bench.py --config bert_base_512 uses (eager and GraphedCall); device-event
 timing after warm-up.  --rules adds, for the bf16 step, every relprop C-ABI call bracketed by HIP events
 (ops.KERNEL_TIMER) with its ALGORITHMIC flops and bytes.  For a kernel table run the script under
@@ -65,6 +66,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rules", action="store_true")
+    ap.add_argument("--only", choices=["all", "bf16", "bf16_fused"], default="all")      # one line alone: a kernel trace of one mode
     a = ap.parse_args()
 
     import transformer_explainability_amd as te
@@ -77,7 +79,22 @@ def main():
 
     m16 = _model(torch.bfloat16)
     gen16 = Generator(m16)
-    t16 = _eager_and_graphed(gen16, ids, mask, a, res, "bf16")
+    t16 = float("inf")
+    if a.only in ("all", "bf16"):
+        t16 = _eager_and_graphed(gen16, ids, mask, a, res, "bf16")
+    if a.only in ("all", "bf16_fused"):
+        was = ops.USE_FUSED_PRODUCERS
+        ops.USE_FUSED_PRODUCERS = True
+        try:
+            t16 = min(t16, _eager_and_graphed(gen16, ids, mask, a, res, "bf16_fused_producers"))
+            assert all(l.attention.self._fused_anchor is not None for l in m16.bert.encoder.layer), \
+                "the bf16 layers did not take the fused route"
+        finally:
+            ops.USE_FUSED_PRODUCERS = was
+    if a.only != "all":
+        res["build_id"] = te._lib.build_id()
+        print(json.dumps(res), flush=True)
+        return
     if a.rules:
         timer = _RuleTimer()
         ops.KERNEL_TIMER = timer

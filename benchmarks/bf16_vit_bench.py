@@ -3,7 +3,9 @@
     python benchmarks/bf16_vit_bench.py [--batch 64] [--steps 10] [--warmup 3] [--rules]
 
 Prints one JSON line: maps/s of LRP(model).generate_LRP(x) for the model in bf16 (the bf16 relprop kernels) and in fp32
-(twice: the package defaults, and with the fused fp32 producers bench.py uses), device-event timing after warm-up.
+(twice: the package defaults, and with the fused fp32 producers bench.py uses), and for the bf16 model with the fused bf16
+producers (ops.USE_FUSED_PRODUCERS, csrc/te_attn_bf16.hip); device-event timing after warm-up.  --only bf16 / bf16_fused
+runs that one line alone (a kernel trace of one mode).
 --rules adds, for the bf16 step, every relprop C-ABI call bracketed by HIP events (ops.KERNEL_TIMER) with its ALGORITHMIC
 flops and bytes: time, achieved GB/s and the HBM fraction (8 TB/s) per rule.  For a kernel table run the script under
 ``rocprofv3 --kernel-trace --stats -- python benchmarks/bf16_vit_bench.py --steps 2 --warmup 1``.
@@ -85,6 +87,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rules", action="store_true")
+    ap.add_argument("--only", choices=["all", "bf16", "bf16_fused"], default="all")
     a = ap.parse_args()
 
     import transformer_explainability_amd as te
@@ -98,9 +101,26 @@ def main():
     m16 = _model(torch.bfloat16)
     x16 = x32.to(torch.bfloat16)
     lrp16 = LRP(m16)
-    t16 = _time(lambda: lrp16.generate_LRP(x16, start_layer=1), a.steps, a.warmup)
-    res["bf16_maps_per_s"] = round(a.batch / t16, 1)
-    res["bf16_step_ms"] = round(t16 * 1e3, 2)
+    t16 = None
+    if a.only in ("all", "bf16"):
+        t16 = _time(lambda: lrp16.generate_LRP(x16, start_layer=1), a.steps, a.warmup)
+        res["bf16_maps_per_s"] = round(a.batch / t16, 1)
+        res["bf16_step_ms"] = round(t16 * 1e3, 2)
+    if a.only in ("all", "bf16_fused"):
+        was = ops.USE_FUSED_PRODUCERS
+        ops.USE_FUSED_PRODUCERS = True
+        try:
+            t16f = _time(lambda: lrp16.generate_LRP(x16, start_layer=1), a.steps, a.warmup)
+            assert all(b.attn._fused_anchor is not None for b in m16.blocks), "the bf16 blocks did not take the fused route"
+        finally:
+            ops.USE_FUSED_PRODUCERS = was
+        res["bf16_fused_producers_maps_per_s"] = round(a.batch / t16f, 1)
+        res["bf16_fused_producers_step_ms"] = round(t16f * 1e3, 2)
+    if a.only != "all":
+        res["build_id"] = te._lib.build_id()
+        print(json.dumps(res), flush=True)
+        return
+    t16 = min(t16, t16f)
     if a.rules:
         timer = _RuleTimer()
         ops.KERNEL_TIMER = timer

@@ -567,6 +567,37 @@ int te_index_select_relprop_bf16(const float* R, const te_bf16_t* X, float* out,
                                  int64_t index, te_stream_t stream);
 int te_gradcam_headmean_bf16(const te_bf16_t* grad, const float* cam, float* out, int64_t B, int64_t H, int64_t N,
                              te_stream_t stream);
+/* The attention producers (te_attention_forward_strided_f32 / te_attention_backward_strided_f32) of a bf16 model: the same
+ * argument order with te_bf16_t operands and outputs, head dim 64, 1 <= N <= 640 (te_attention_bf16_supported;
+ * TE_ERR_UNSUPPORTED otherwise, and for views whose base is not 16-byte aligned or whose strides are not multiples of 8
+ * elements).  csrc/te_attn_bf16.hip.  Every output is rounded to bf16 exactly once, from an fp32 value, where the stock bf16
+ * path rounds, so that a rule's Z is the product of the very operands the cache holds:
+ *   forward : z_qk (optional) = bf16(q k^T) ; x_scaled (optional) = bf16(z_qk * scale) from the rounded z_qk, WITHOUT the mask
+ *             (BERT's Add.X[0]) ; attn = bf16(softmax(s)), evaluated in fp32, s = bf16(x_scaled + mask[b, key]) (mask [B,N]
+ *             bf16 additive, NULL = none: s = x_scaled) ; out = bf16(attn v) from the rounded attn, fp32 accumulation
+ *   backward: d_attn = bf16(d_out v^T) ; d_v = bf16(attn^T d_out) ; need_qk: d_s = bf16(attn (d_attn - rowsum(attn d_attn)))
+ *             from the rounded d_attn (the sums are taken over the N x N tensors, not from d_out . out),
+ *             d_q = bf16(scale d_s k), d_k = bf16(scale d_s^T q).  need_qk == 0: d_q / d_k are not written, q / k / the
+ *             workspace may be NULL.  Workspace (need_qk): te_attention_backward_strided_bf16_workspace_bytes, B*H*N floats.
+ * A launch that the runtime refuses is reported as TE_ERR_UNSUPPORTED, not as a hipError_t. */
+int te_attention_bf16_supported(int64_t N, int64_t D);
+size_t te_attention_backward_strided_bf16_workspace_bytes(int64_t B, int64_t H, int64_t N);
+int te_attention_forward_strided_bf16(const te_bf16_t* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                                      const te_bf16_t* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                                      const te_bf16_t* v, int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                                      const te_bf16_t* mask, te_bf16_t* z_qk, te_bf16_t* x_scaled, te_bf16_t* attn,
+                                      te_bf16_t* out, int64_t o_sb, int64_t o_sh, int64_t o_sn,
+                                      int64_t B, int64_t H, int64_t N, int64_t D, float scale, te_stream_t stream);
+int te_attention_backward_strided_bf16(const te_bf16_t* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn,
+                                       const te_bf16_t* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                                       const te_bf16_t* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                                       const te_bf16_t* v, int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                                       const te_bf16_t* attn, te_bf16_t* d_attn,
+                                       te_bf16_t* d_q, int64_t dq_sb, int64_t dq_sh, int64_t dq_sn,
+                                       te_bf16_t* d_k, int64_t dk_sb, int64_t dk_sh, int64_t dk_sn,
+                                       te_bf16_t* d_v, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
+                                       int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk,
+                                       void* ws, size_t ws_bytes, te_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -140,6 +140,14 @@ SIGNATURES = {
     "te_clone_relprop_scaled_bf16": (_I, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _P]),
     "te_index_select_relprop_bf16": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _P]),
     "te_gradcam_headmean_bf16": (_I, [_P, _P, _P, _I64, _I64, _I64, _P]),
+    # bf16 attention producers (csrc/te_attn_bf16.hip): the argument lists of the _strided_f32 entry points
+    "te_attention_bf16_supported": (_I, [_I64, _I64]),
+    "te_attention_backward_strided_bf16_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "te_attention_forward_strided_bf16": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P,
+                                               _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _F, _P]),
+    "te_attention_backward_strided_bf16": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64,
+                                                _I64, _I64, _P, _P, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64,
+                                                _I64, _I64, _I64, _I64, _I64, _I64, _F, _I, _P, _SZ, _P]),
 }
 
 

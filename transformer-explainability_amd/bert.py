@@ -148,9 +148,13 @@ def make_bert_module(L):
             h1, h2, h3 = self.clone(hidden_states, 3)
             self._fused_anchor = None
             B, N, _ = hidden_states.shape
-            if (ops.USE_FUSED_PRODUCERS and hidden_states.is_cuda and hidden_states.dtype == torch.float32
-                    and not self.training and ops.attention_forward_supported(N, self.attention_head_size)
-                    and (attention_mask is None or tuple(attention_mask.shape) == (B, 1, 1, N))):
+            dt = hidden_states.dtype
+            if (ops.USE_FUSED_PRODUCERS and hidden_states.is_cuda and not self.training
+                    and ((dt == torch.float32 and ops.attention_forward_supported(N, self.attention_head_size))
+                         or (dt == torch.bfloat16 and ops.attention_forward_bf16_supported(N, self.attention_head_size)))
+                    and (attention_mask is None
+                         or (tuple(attention_mask.shape) == (B, 1, 1, N)
+                             and (dt == torch.float32 or attention_mask.dtype == dt)))):
                 return self._forward_fused(h1, h2, h3, attention_mask)
             q = self.transpose_for_scores(self.query(h1))
             k = self.transpose_for_scores(self.key(h2))

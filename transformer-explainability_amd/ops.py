@@ -668,6 +668,11 @@ def attention_forward_supported(N: int, D: int) -> bool:
     return bool(lib.te_attention_forward_supported(int(N), int(D)) or lib.te_attention_strided_supported(int(N), int(D)))
 
 
+def attention_forward_bf16_supported(N: int, D: int) -> bool:
+    """The bf16 producer kernels of csrc/te_attn_bf16.hip take the shape (head dim 64, 1 <= N <= 640)."""
+    return bool(_lib.load().te_attention_bf16_supported(int(N), int(D)))
+
+
 def _heads(t: Tensor, H: int):
     """[B,N,H*64] activation (any batch / token strides, contiguous features) -> (pointer tensor, sb, sh, sn) of its
     [B,H,N,64] view."""
@@ -683,6 +688,8 @@ def attention_forward_qkv(q: Tensor, k: Tensor, v: Tensor, num_heads: int, scale
     mask [B,N] additive or None -> (out [B,N,C], attn [B,H,N,N], z_qk [B,H,N,N] unscaled or None, x = z_qk * scale
     [B,H,N,N] or None: the scaled scores BEFORE the mask is added, i.e. the first operand of BERT's Add module).
     csrc/te_attn_long.hip."""
+    if _is_bf16(q) or _is_bf16(k) or _is_bf16(v):
+        return attention_forward_qkv_bf16(q, k, v, num_heads, scale, mask, want_z, want_x)
     B, N, C = q.shape
     H, D = num_heads, C // num_heads
     dev = q.device
@@ -701,6 +708,54 @@ def attention_forward_qkv(q: Tensor, k: Tensor, v: Tensor, num_heads: int, scale
     return out, attn, zqk, xsc
 
 
+def attention_forward_qkv_bf16(q: Tensor, k: Tensor, v: Tensor, num_heads: int, scale: float,
+                               mask: Optional[Tensor] = None, want_z: bool = True, want_x: bool = False):
+    """attention_forward_qkv on bf16 views (a bf16 model): every result is bf16, rounded once from fp32 where the stock bf16
+    path rounds -- z_qk = bf16(q k^T), x = bf16(z_qk * scale), attn = bf16(softmax(bf16(x + mask))), out = bf16(attn v) with
+    the rounded attn.  csrc/te_attn_bf16.hip; head dim 64, N <= 640 (attention_forward_bf16_supported)."""
+    q, k, v = _prep_bf16(q), _prep_bf16(k), _prep_bf16(v)
+    B, N, C = q.shape
+    H, D = num_heads, C // num_heads
+    dev = q.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.bfloat16, device=dev)      # noqa: E731
+    out, attn = new(B, N, C), new(B, H, N, N)
+    zqk = new(B, H, N, N) if want_z else None
+    xsc = new(B, H, N, N) if want_x else None
+    mk = None if mask is None else _c16(mask.reshape(B, N))
+    (q, qb, qh, qn), (k, kb, kh, kn), (v, vb, vh, vn) = _heads(q, H), _heads(k, H), _heads(v, H)
+    with _on_device(q) as lib, _timed("attention_forward", 4.0 * B * H * N * N * D,
+                                      2.0 * B * ((2 + bool(want_x)) * H * N * N + 4 * N * C)):
+        _lib.check(lib.te_attention_forward_strided_bf16(_ptr(q), qb, qh, qn, _ptr(k), kb, kh, kn, _ptr(v), vb, vh, vn,
+                                                         _ptr(mk), _ptr(zqk), _ptr(xsc), _ptr(attn), _ptr(out), N * C, 64, C,
+                                                         B, H, N, D, float(scale), _stream(q)),
+                   "te_attention_forward_strided_bf16")
+    return out, attn, zqk, xsc
+
+
+def attention_backward_qkv_bf16(d_out: Tensor, q: Optional[Tensor], k: Optional[Tensor], v: Tensor, attn: Tensor,
+                                num_heads: int, scale: float, d_q: Optional[Tensor], d_k: Optional[Tensor], d_v: Tensor,
+                                need_qk: bool = True) -> Tensor:
+    """attention_backward_qkv on bf16 tensors: d_attn = bf16(d_out v^T), d_v = bf16(attn^T d_out), and with need_qk
+    d_q = bf16(scale d_s k), d_k = bf16(scale d_s^T q), d_s = bf16(attn (d_attn - rowsum(attn d_attn))).  The row sums are
+    taken over the N x N tensors: the forward output is not an operand.  csrc/te_attn_bf16.hip."""
+    B, N, C = d_out.shape
+    H, D = num_heads, C // num_heads
+    d_out, attn = _c16(d_out), _c16(attn)
+    d_attn = torch.empty_like(attn)
+    hd = lambda t: (None, 0, 0, 0) if t is None else _heads(_prep_bf16(t), H)      # noqa: E731
+    (q, qb, qh, qn), (k, kb, kh, kn), (v, vb, vh, vn) = hd(q), hd(k), hd(v)
+    (dq, dqb, dqh, dqn), (dk, dkb, dkh, dkn), (dv, dvb, dvh, dvn) = hd(d_q), hd(d_k), hd(d_v)
+    with _on_device(d_out) as lib, _timed("attention_backward", (8.0 if need_qk else 4.0) * B * H * N * N * D,
+                                          2.0 * B * ((5 if need_qk else 2) * H * N * N + 8 * N * C)):
+        ws = _ws(lib.te_attention_backward_strided_bf16_workspace_bytes(B, H, N), d_out)
+        _lib.check(lib.te_attention_backward_strided_bf16(_ptr(d_out), N * C, 64, C, _ptr(q), qb, qh, qn, _ptr(k), kb, kh, kn,
+                                                          _ptr(v), vb, vh, vn, _ptr(attn), _ptr(d_attn), _ptr(dq), dqb, dqh,
+                                                          dqn, _ptr(dk), dkb, dkh, dkn, _ptr(dv), dvb, dvh, dvn, B, H, N, D,
+                                                          float(scale), int(bool(need_qk)), _ptr(ws), ws.numel(),
+                                                          _stream(d_out)), "te_attention_backward_strided_bf16")
+    return d_attn
+
+
 def attention_backward_qkv(d_out: Tensor, q: Tensor, k: Tensor, v: Tensor, attn: Tensor, num_heads: int, scale: float,
                            d_q: Optional[Tensor], d_k: Optional[Tensor], d_v: Tensor, need_qk: bool = True,
                            out: Optional[Tensor] = None) -> Tensor:
@@ -708,6 +763,8 @@ def attention_backward_qkv(d_out: Tensor, q: Tensor, k: Tensor, v: Tensor, attn:
     None with need_qk=False).  Returns d_attn [B,H,N,N].  out: the forward output [B,N,C] attention_forward_qkv returned for
     these inputs, if the caller still holds it -- the softmax backward's row sums are then d_out . out and the row side runs
     on csrc/te_attn_bwd6l.hip (te_attention_backward_strided_out_f32)."""
+    if any(_is_bf16(t) for t in (d_out, q, k, v, attn)):
+        return attention_backward_qkv_bf16(d_out, q, k, v, attn, num_heads, scale, d_q, d_k, d_v, need_qk=need_qk)
     B, N, C = d_out.shape
     H, D = num_heads, C // num_heads
     d_out, attn = _c(d_out), _c(attn)
@@ -746,7 +803,15 @@ def attention_forward(qkv: Tensor, num_heads: int, scale: float, planes: bool = 
     """qkv [B,N,3C] ('b n (qkv h d)') -> (out [B,N,C] = softmax(q k^T * scale) v as 'b n (h d)', attn [B,H,N,N],
     z_qk [B,H,N,N] = the unscaled q k^T).  ViT_LRP.py:132-152 without the q/k/v, scale, softmax and transpose passes.
     planes=True (attention_forward_planes_supported): additionally the signed planes of out [B N, C] and the planes of |out| --
-    what gemm_x6's split pass over out would build -- as a fourth and fifth result."""
+    what gemm_x6's split pass over out would build -- as a fourth and fifth result.
+    A bf16 qkv (a bf16 model) runs on csrc/te_attn_bf16.hip and returns bf16 tensors; planes=True is fp32-only."""
+    if _is_bf16(qkv):
+        if planes:
+            raise _lib.TeError("attention_forward(planes=True): operand planes are emitted from float32 activations only")
+        qkv = _c16(qkv)
+        C = qkv.shape[-1] // 3
+        out, attn, zqk, _ = attention_forward_qkv_bf16(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], num_heads, scale)
+        return out, attn, zqk
     qkv = _c(qkv)
     B, N, C3 = qkv.shape
     C = C3 // 3
@@ -778,7 +843,15 @@ def attention_backward(d_out: Tensor, qkv: Tensor, attn: Tensor, num_heads: int,
     """Gradient of attention_forward: d_out [B,N,C] -> (d_attn [B,H,N,N], d_qkv [B,N,3C]).  need_qk=False: nothing below
     consumes d_qkv (the lowest block whose attention gradient is wanted): only d_attn is meaningful, d_qkv is scratch.
     out: the forward output attention_forward returned for these inputs, if the caller still holds it -- the softmax half then
-    takes its row sums from d_out . out (te_attention_backward_out_f32)."""
+    takes its row sums from d_out . out (te_attention_backward_out_f32).  bf16 tensors: csrc/te_attn_bf16.hip (`out` unused)."""
+    if _is_bf16(d_out) or _is_bf16(qkv) or _is_bf16(attn):
+        qkv = _c16(qkv)
+        C = qkv.shape[-1] // 3
+        d_qkv = torch.empty_like(qkv)
+        th = lambda t, i: t[..., i * C:(i + 1) * C]      # noqa: E731
+        d_attn = attention_backward_qkv_bf16(d_out, th(qkv, 0), th(qkv, 1), th(qkv, 2), attn, num_heads, scale,
+                                             th(d_qkv, 0), th(d_qkv, 1), th(d_qkv, 2), need_qk=need_qk)
+        return d_attn, d_qkv
     d_out, qkv, attn = _c(d_out), _c(qkv), _c(attn)
     B, N, C3 = qkv.shape
     C = C3 // 3

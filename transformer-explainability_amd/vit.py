@@ -200,8 +200,9 @@ def make_vit_module(L):
             B, N, C = x.shape
             H = self.num_heads
             self._fused_anchor = None
-            if (ops.USE_FUSED_PRODUCERS and x.is_cuda and x.dtype == torch.float32 and not self.training
-                    and ops.attention_forward_supported(N, C // H)):
+            if ops.USE_FUSED_PRODUCERS and x.is_cuda and not self.training and (
+                    (x.dtype == torch.float32 and ops.attention_forward_supported(N, C // H))
+                    or (x.dtype == torch.bfloat16 and ops.attention_forward_bf16_supported(N, C // H))):
                 return self._forward_fused(x)
             q, k, v = split_qkv(self.qkv(x), H)                                 # 'b n (qkv h d) -> qkv b h n d'
             self.save_v(v)
