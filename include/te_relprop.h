@@ -567,6 +567,22 @@ int te_index_select_relprop_bf16(const float* R, const te_bf16_t* X, float* out,
                                  int64_t index, te_stream_t stream);
 int te_gradcam_headmean_bf16(const te_bf16_t* grad, const float* cam, float* out, int64_t B, int64_t H, int64_t N,
                              te_stream_t stream);
+/* Head mean of a bf16 model's attention probabilities, the input of the attention rollouts and of the last-layer
+ * baselines (ViT_explanation_generator.py:74-83, ViT_LRP.py:391-397, ExplanationGenerator.py:108-127):
+ *   out[b,i,j] = (sum_h f(attn[b,h,i,j])) / H,   f = identity, or max(., 0) with TE_HEADMEAN_CLAMP,
+ * heads added in index order in fp32, one division at the end (torch's mean on the exact fp32 upcast).  attn: element
+ * (b,h,i,j) at attn + b*a_sb + h*a_sh + i*N + j (any element offsets: no alignment requirement); out: contiguous fp32
+ * [B,N,N] -- e.g. one layer's slice of the [L,B,N,N] stack te_rollout_f32 reads -- or, with TE_HEADMEAN_ROW0, [B,N] =
+ * query row 0 alone (the same values bit for bit).  Fixed order, no atomics: a batch equals its samples.
+ * B <= 65535 (TE_ERR_UNSUPPORTED otherwise); unknown flag bits: TE_ERR_INVALID_ARG. */
+enum { TE_HEADMEAN_CLAMP = 1, TE_HEADMEAN_ROW0 = 2 };
+int te_attn_headmean_bf16(const te_bf16_t* attn, int64_t a_sb, int64_t a_sh, float* out, int64_t B, int64_t H, int64_t N,
+                          int flags, te_stream_t stream);
+/* te_perturb_f32 with a bf16 result (the input of a bf16 classifier): vis and data stay fp32, every value is evaluated
+ * in fp32 exactly as te_perturb_f32 does and rounded once to bf16, to nearest even.  Same workspace, same limits. */
+int te_perturb_bf16(const float* vis, const float* data, te_bf16_t* out, int64_t B, int64_t C, int64_t HW,
+                    const int64_t* ks, int64_t n_steps, const float* mean, const float* std_, void* ws,
+                    size_t ws_bytes, te_stream_t stream);
 /* The attention producers (te_attention_forward_strided_f32 / te_attention_backward_strided_f32) of a bf16 model: the same
  * argument order with te_bf16_t operands and outputs, head dim 64, 1 <= N <= 640 (te_attention_bf16_supported;
  * TE_ERR_UNSUPPORTED otherwise, and for views whose base is not 16-byte aligned or whose strides are not multiples of 8

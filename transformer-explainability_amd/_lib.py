@@ -25,6 +25,8 @@ TE_IMPL_SIMPLE = 0x100
 TE_ROLLOUT_NORMALISE = 1
 TE_ROLLOUT_CLS_FIXUP = 2
 TE_ROLLOUT_ROW0 = 4
+TE_HEADMEAN_CLAMP = 1
+TE_HEADMEAN_ROW0 = 2
 
 _P, _I64, _F, _I, _SZ = c_void_p, c_int64, c_float, c_int, c_size_t
 
@@ -140,6 +142,8 @@ SIGNATURES = {
     "te_clone_relprop_scaled_bf16": (_I, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _P]),
     "te_index_select_relprop_bf16": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _P]),
     "te_gradcam_headmean_bf16": (_I, [_P, _P, _P, _I64, _I64, _I64, _P]),
+    "te_attn_headmean_bf16": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I, _P]),
+    "te_perturb_bf16": (_I, [_P, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _SZ, _P]),
     # bf16 attention producers (csrc/te_attn_bf16.hip): the argument lists of the _strided_f32 entry points
     "te_attention_bf16_supported": (_I, [_I64, _I64]),
     "te_attention_backward_strided_bf16_workspace_bytes": (_SZ, [_I64, _I64, _I64]),

@@ -559,6 +559,54 @@ __global__ __launch_bounds__(kThreads) void headmean_flat_kernel(
   }
 }
 
+// Head mean of a bf16 model's attention probabilities (te_attn_headmean_bf16): out[b,e] = (sum_h f(attn[b,h,e])) / H over
+// e in [0, n), f = identity or max(., 0), heads added in index order in fp32 (torch's mean; the bf16 -> fp32 widening is
+// exact).  n = N*N, or N for the class-token row alone.  A thread owns 8 consecutive elements: one 16-B load per head --
+// up to HB heads' loads in flight, as in headmean_flat_kernel -- and two 16-B stores.  Head bases are arbitrary element
+// offsets (N*N is odd at N = 197), hence the 2-byte-aligned vector type: gfx950 global loads take any alignment.
+typedef uint32_t u32x4_u2 __attribute__((ext_vector_type(4), aligned(2)));
+
+template <int HB, bool CLAMP>
+__global__ __launch_bounds__(kThreads) void attn_headmean_kernel(
+    const te_bf16_t* __restrict__ attn, int64_t a_sb, int64_t a_sh, float* __restrict__ out, int H, int64_t n) {
+  const int64_t b = blockIdx.y;
+  const float fH = (float)H;
+  const te_bf16_t* a = attn + b * a_sb;
+  float* o = out + b * n;
+  const int64_t e = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 8;
+  if (e >= n) return;
+  if (e + 7 < n) {
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int h0 = 0; h0 < H; h0 += HB) {
+      u32x4_u2 v[HB];
+#pragma unroll
+      for (int u = 0; u < HB; ++u)
+        if (h0 + u < H) v[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_u2*>(a + (h0 + u) * a_sh + e));
+#pragma unroll
+      for (int u = 0; u < HB; ++u)
+        if (h0 + u < H) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const float lo = __uint_as_float(v[u][k] << 16), hi = __uint_as_float(v[u][k] & 0xffff0000u);
+            acc[2 * k] = acc[2 * k] + (CLAMP ? fmaxf(lo, 0.0f) : lo);
+            acc[2 * k + 1] = acc[2 * k + 1] + (CLAMP ? fmaxf(hi, 0.0f) : hi);
+          }
+        }
+    }
+    st<f32x4_u>(o + e, f32x4_u{acc[0] / fH, acc[1] / fH, acc[2] / fH, acc[3] / fH});
+    st<f32x4_u>(o + e + 4, f32x4_u{acc[4] / fH, acc[5] / fH, acc[6] / fH, acc[7] / fH});
+  } else {
+    for (int64_t ee = e; ee < n; ++ee) {
+      float acc = 0.0f;
+      for (int h = 0; h < H; ++h) {
+        const float x = ldx(a + h * a_sh + ee);
+        acc = acc + (CLAMP ? fmaxf(x, 0.0f) : x);
+      }
+      o[ee] = acc / fH;
+    }
+  }
+}
+
 inline int pick_blocks_per_sample(int64_t B, int64_t n) {
   // >= ~2048 blocks in flight for the chip (256 CUs x 8), each block >= 4096 elements, <= 64 chunks.
   int64_t bps = te_ceil_div(2048, B);
@@ -914,4 +962,26 @@ extern "C" int te_gradcam_headmean_f32(const float* grad, const float* cam, floa
 extern "C" int te_gradcam_headmean_bf16(const te_bf16_t* grad, const float* cam, float* out, int64_t B, int64_t H,
                                         int64_t N, te_stream_t stream_) {
   return gradcam_headmean(grad, cam, out, B, H, N, stream_);
+}
+
+// ---- head mean of bf16 attention probabilities --------------------------------------------------------
+extern "C" int te_attn_headmean_bf16(const te_bf16_t* attn, int64_t a_sb, int64_t a_sh, float* out, int64_t B, int64_t H,
+                                     int64_t N, int flags, te_stream_t stream_) {
+  if (!attn || !out || B <= 0 || H <= 0 || N <= 0 || a_sb < 0 || a_sh < 0) return TE_ERR_INVALID_ARG;
+  if (flags & ~(TE_HEADMEAN_CLAMP | TE_HEADMEAN_ROW0)) return TE_ERR_INVALID_ARG;
+  if (B > 65535 || H > 0x7fffffff) return TE_ERR_UNSUPPORTED;
+  hipStream_t stream = (hipStream_t)stream_;
+  const int64_t n = (flags & TE_HEADMEAN_ROW0) ? N : N * N;
+  const dim3 grid((unsigned)te_ceil_div(n, (int64_t)kThreads * 8), (unsigned)B), blk(kThreads);
+  const bool clamp = (flags & TE_HEADMEAN_CLAMP) != 0;
+  // every head in flight for H <= 12 (ViT-B, BERT-base) and H <= 16 (ViT-L); more heads take several trips of 16
+  if (H <= 12) {
+    if (clamp) attn_headmean_kernel<12, true><<<grid, blk, 0, stream>>>(attn, a_sb, a_sh, out, (int)H, n);
+    else attn_headmean_kernel<12, false><<<grid, blk, 0, stream>>>(attn, a_sb, a_sh, out, (int)H, n);
+  } else {
+    if (clamp) attn_headmean_kernel<16, true><<<grid, blk, 0, stream>>>(attn, a_sb, a_sh, out, (int)H, n);
+    else attn_headmean_kernel<16, false><<<grid, blk, 0, stream>>>(attn, a_sb, a_sh, out, (int)H, n);
+  }
+  TE_RETURN_IF_LAUNCH_FAILED();
+  return TE_OK;
 }

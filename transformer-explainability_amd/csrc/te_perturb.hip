@@ -170,6 +170,78 @@ __global__ __launch_bounds__(256) void perturb_apply_kernel(const float* __restr
   }
 }
 
+// bf16-output form (te_perturb_bf16): the same fp32 expression, rounded ONCE to bf16 (nearest even, v_cvt_pk_bf16_f32).  The
+// kernel is store-bound, so a thread owns 8 consecutive pixels (two 16-B loads of vis and of every channel, one 16-B store
+// per channel and step) and walks the steps itself: the image and the relevance row are read once, not once per step, and
+// the S stores of a wave go to S streams of 1 KiB each.  blockIdx.z selects a group of `spg` steps (the host takes one
+// group when the batch alone fills the chip, one step per group otherwise).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ uint32_t te_pack_bf16(float a, float b) {       // a in the low half
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void perturb_apply_bf16_kernel(const float* __restrict__ vis,
+                                                                 const float* __restrict__ data,
+                                                                 const uint32_t* __restrict__ sel,
+                                                                 te_bf16_t* __restrict__ out, int64_t B, int64_t C,
+                                                                 int64_t HW, int S, int spg, Norm nm) {
+  const int64_t b = blockIdx.y;
+  const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * VEC;
+  if (i0 >= HW) return;
+  const int s0 = (int)blockIdx.z * spg, s1 = min(S, s0 + spg);
+  uint32_t key[VEC];
+  if constexpr (VEC == 8) {
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(vis + b * HW + i0);
+    const f32x4 v1 = *reinterpret_cast<const f32x4*>(vis + b * HW + i0 + 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      key[j] = te_key(v0[j]);
+      key[4 + j] = te_key(v1[j]);
+    }
+  } else {
+    key[0] = te_key(vis[b * HW + i0]);
+  }
+  for (int64_t c = 0; c < C; ++c) {
+    const float* src = data + (b * C + c) * HW + i0;
+    const float mean = nm.mean[c], sd = nm.std[c];
+    float x[VEC], y0[VEC];                 // y0: the value of a removed pixel
+    if constexpr (VEC == 8) {
+      const f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        x[j] = x0[j];
+        x[4 + j] = x1[j];
+      }
+    } else {
+      x[0] = src[0];
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      y0[j] = (0.0f - mean) / sd;
+      x[j] = (x[j] - mean) / sd;
+    }
+    for (int s = s0; s < s1; ++s) {
+      const uint32_t thr = sel[(b * S + s) * 2], cut = sel[(b * S + s) * 2 + 1];
+      te_bf16_t* dst = out + (((int64_t)s * B + b) * C + c) * HW + i0;
+      float y[VEC];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j)
+        y[j] = (key[j] > thr || (key[j] == thr && (uint32_t)(i0 + j) < cut)) ? y0[j] : x[j];
+      if constexpr (VEC == 8) {
+        const u32x4 p = {te_pack_bf16(y[0], y[1]), te_pack_bf16(y[2], y[3]), te_pack_bf16(y[4], y[5]),
+                         te_pack_bf16(y[6], y[7])};
+        __builtin_nontemporal_store(p, reinterpret_cast<u32x4*>(dst));
+      } else {
+        dst[0] = (te_bf16_t)(te_pack_bf16(y[0], 0.0f) & 0xffffu);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" size_t te_perturb_workspace_bytes(int64_t B, int64_t n_steps) {
@@ -177,24 +249,35 @@ extern "C" size_t te_perturb_workspace_bytes(int64_t B, int64_t n_steps) {
   return te_align_up((size_t)B * (size_t)n_steps * 2 * sizeof(uint32_t), 256);
 }
 
-extern "C" int te_perturb_f32(const float* vis, const float* data, float* out, int64_t B, int64_t C, int64_t HW,
-                              const int64_t* ks, int64_t n_steps, const float* mean, const float* std_, void* ws,
-                              size_t ws_bytes, te_stream_t stream_) {
+namespace {
+// argument checks + the selection kernel, shared by the fp32 and the bf16-output entry points
+int perturb_select(const float* vis, const float* data, const void* out, int64_t B, int64_t C, int64_t HW,
+                   const int64_t* ks, int64_t n_steps, const float* mean, const float* std_, void* ws, size_t ws_bytes,
+                   hipStream_t stream, Norm* nm) {
   if (!vis || !data || !out || !ks || B <= 0 || C <= 0 || HW <= 0 || n_steps <= 0) return TE_ERR_INVALID_ARG;
   if (n_steps > kMaxSteps || C > TE_PERTURB_MAX_CHANNELS || HW > (int64_t)0x7fffffff) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_perturb_workspace_bytes(B, n_steps)) return TE_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
   Steps st;
   st.n = (int)n_steps;
   for (int s = 0; s < kMaxSteps; ++s) st.k[s] = 0;
   for (int s = 0; s < st.n; ++s) st.k[s] = ks[s] < 0 ? 0 : (ks[s] > HW ? HW : ks[s]);
-  Norm nm;
   for (int c = 0; c < TE_PERTURB_MAX_CHANNELS; ++c) {
-    nm.mean[c] = (mean && c < C) ? mean[c] : 0.0f;
-    nm.std[c] = (std_ && c < C) ? std_[c] : 1.0f;
+    nm->mean[c] = (mean && c < C) ? mean[c] : 0.0f;
+    nm->std[c] = (std_ && c < C) ? std_[c] : 1.0f;
   }
-  uint32_t* sel = (uint32_t*)ws;
-  perturb_select_kernel<<<dim3((unsigned)B), dim3(kSelThreads), 0, stream>>>(vis, sel, HW, st);
+  perturb_select_kernel<<<dim3((unsigned)B), dim3(kSelThreads), 0, stream>>>(vis, (uint32_t*)ws, HW, st);
+  return TE_OK;
+}
+}  // namespace
+
+extern "C" int te_perturb_f32(const float* vis, const float* data, float* out, int64_t B, int64_t C, int64_t HW,
+                              const int64_t* ks, int64_t n_steps, const float* mean, const float* std_, void* ws,
+                              size_t ws_bytes, te_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  Norm nm;
+  const int rc = perturb_select(vis, data, out, B, C, HW, ks, n_steps, mean, std_, ws, ws_bytes, stream, &nm);
+  if (rc != TE_OK) return rc;
+  const uint32_t* sel = (const uint32_t*)ws;
   const bool vec = (HW % 4 == 0) && te_aligned16(vis) && te_aligned16(data) && te_aligned16(out);
   if (vec)
     perturb_apply_kernel<4><<<dim3((unsigned)te_ceil_div(HW / 4, 256), (unsigned)B, (unsigned)n_steps), dim3(256), 0,
@@ -202,6 +285,29 @@ extern "C" int te_perturb_f32(const float* vis, const float* data, float* out, i
   else
     perturb_apply_kernel<1><<<dim3((unsigned)te_ceil_div(HW, 256), (unsigned)B, (unsigned)n_steps), dim3(256), 0,
                               stream>>>(vis, data, sel, out, B, C, HW, (int)n_steps, nm);
+  TE_RETURN_IF_LAUNCH_FAILED();
+  return TE_OK;
+}
+
+extern "C" int te_perturb_bf16(const float* vis, const float* data, te_bf16_t* out, int64_t B, int64_t C, int64_t HW,
+                               const int64_t* ks, int64_t n_steps, const float* mean, const float* std_, void* ws,
+                               size_t ws_bytes, te_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  Norm nm;
+  const int rc = perturb_select(vis, data, out, B, C, HW, ks, n_steps, mean, std_, ws, ws_bytes, stream, &nm);
+  if (rc != TE_OK) return rc;
+  const uint32_t* sel = (const uint32_t*)ws;
+  // 16-B accesses need HW % 8 == 0 (a bf16 row of the output then starts on a 16-B boundary); anything else, and
+  // unaligned bases, take the element-wise form
+  const bool vec = (HW % 8 == 0) && te_aligned16(vis) && te_aligned16(data) && te_aligned16(out);
+  const int64_t bx = te_ceil_div(vec ? HW / 8 : HW, 256);
+  // all steps inside one thread once B * bx blocks fill the chip (256 CUs x 4 resident blocks); else one step per block
+  const int spg = (bx * B >= 1024) ? (int)n_steps : 1;
+  const dim3 grid((unsigned)bx, (unsigned)B, (unsigned)te_ceil_div(n_steps, spg));
+  if (vec)
+    perturb_apply_bf16_kernel<8><<<grid, dim3(256), 0, stream>>>(vis, data, sel, out, B, C, HW, (int)n_steps, spg, nm);
+  else
+    perturb_apply_bf16_kernel<1><<<grid, dim3(256), 0, stream>>>(vis, data, sel, out, B, C, HW, (int)n_steps, spg, nm);
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
 }

@@ -31,6 +31,19 @@ def _one_hot(output: torch.Tensor, index) -> torch.Tensor:
     return one_hot
 
 
+def _headmean_stack(attns):
+    """Per-layer head means of the attention probabilities as the fp32 [L,B,N,N] stack ops.rollout reads.  A bf16 model:
+    te_attn_headmean_bf16 writes every layer's fp32 mean straight into its slice (heads summed in fp32 on the exact
+    upcast; the probabilities are read once, as bf16).  fp32: the reference's own expression."""
+    if ops._is_bf16(attns[0]):
+        B, _, N, _ = attns[0].shape
+        stack = torch.empty((len(attns), B, N, N), dtype=torch.float32, device=attns[0].device)
+        for i, a in enumerate(attns):
+            ops.attn_headmean(a, out=stack[i])
+        return stack
+    return torch.stack([a.mean(dim=1) for a in attns], 0)
+
+
 def _attention_gradients(loss, attn_modules):
     """Attention gradients of the listed modules (lowest block first), nothing else: no weight gradients, nothing below
     the lowest listed block."""
@@ -154,8 +167,9 @@ class Baselines:
         last.save_attn_gradients(grad)
         B, H, N, _ = grad.shape
         side = int(round((N - 1) ** 0.5))
-        cam = last.get_attention_map().detach()[:, :, 0, 1:].reshape(B, H, side, side)
-        g = grad[:, :, 0, 1:].reshape(B, H, side, side).mean(dim=[2, 3], keepdim=True)
+        # (a bf16 model: evaluated in fp32 on its attention and gradient, like the relprop maps; a no-op for fp32)
+        cam = last.get_attention_map().detach()[:, :, 0, 1:].float().reshape(B, H, side, side)
+        g = grad[:, :, 0, 1:].float().reshape(B, H, side, side).mean(dim=[2, 3], keepdim=True)
         cam = (cam * g).mean(1).clamp(min=0)
         lo = cam.amin(dim=(1, 2), keepdim=True)
         hi = cam.amax(dim=(1, 2), keepdim=True)
@@ -165,8 +179,8 @@ class Baselines:
     def generate_rollout(self, input, start_layer=0):
         """attention rollout (:74-83): head-averaged attention, identity added, rows normalised, chained."""
         self.model(input)
-        mats = [blk.attn.get_attention_map().detach().mean(dim=1) for blk in self.model.blocks]
-        joint = ops.rollout(torch.stack(mats, 0), start_layer=start_layer, normalise=True)
+        stack = _headmean_stack([blk.attn.get_attention_map().detach() for blk in self.model.blocks])
+        joint = ops.rollout(stack, start_layer=start_layer, normalise=True)
         return joint[:, 0, 1:]
 
 
@@ -187,8 +201,9 @@ def generate_visualization(attribution_generator, original_image, class_index=No
     [3,H,W] -> bilinear x16 -> min-max -> JET overlay, uint8 [H,W,3].  The reference closes over a global
     ``attribution_generator``; here it is the first argument.  Up-sampling + normalisation run on the device
     (te_heatmap_f32)."""
-    dev = next(attribution_generator.model.parameters()).device
-    maps = attribution_generator.generate_LRP(original_image.unsqueeze(0).to(dev), method=method, index=class_index,
+    par = next(attribution_generator.model.parameters())
+    image = original_image.unsqueeze(0).to(device=par.device, dtype=par.dtype)      # (a bf16 model takes a bf16 image)
+    maps = attribution_generator.generate_LRP(image, method=method, index=class_index,
                                               start_layer=start_layer).detach()
     patch = attribution_generator.model.patch_embed.patch_size[0]
     heat = ops.heatmap(maps, scale=patch, normalise=True)[0, 0].cpu().numpy()
@@ -385,7 +400,11 @@ class Generator:
         """ExplanationGenerator.py:108-114: head-mean of the last layer's attention probabilities, CLS row."""
         with torch.no_grad():
             self.model(input_ids=input_ids, attention_mask=attention_mask)
-            cam = self.model.bert.encoder.layer[-1].attention.self.get_attn().mean(dim=1)[:, 0].clone()
+            attn = self.model.bert.encoder.layer[-1].attention.self.get_attn()
+            if ops._is_bf16(attn):           # fp32 map of a bf16 model: the class-token row's head mean, summed in fp32
+                cam = ops.attn_headmean(attn, row0=True)
+            else:
+                cam = attn.mean(dim=1)[:, 0].clone()
         cam[:, 0] = 0
         return cam
 
@@ -393,8 +412,8 @@ class Generator:
         """ExplanationGenerator.py:116-127: row-normalised rollout of the head-averaged attention probabilities."""
         with torch.no_grad():
             self.model(input_ids=input_ids, attention_mask=attention_mask)
-            mats = [lay.attention.self.get_attn().mean(dim=1) for lay in self.model.bert.encoder.layer]
-            joint = ops.rollout(torch.stack(mats, 0), start_layer=start_layer, normalise=True)
+            stack = _headmean_stack([lay.attention.self.get_attn() for lay in self.model.bert.encoder.layer])
+            joint = ops.rollout(stack, start_layer=start_layer, normalise=True)
         out = joint[:, 0].clone()
         out[:, 0] = 0
         return out

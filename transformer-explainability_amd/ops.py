@@ -13,8 +13,8 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import (TE_IMPL_SIMPLE, TE_ROLLOUT_CLS_FIXUP, TE_ROLLOUT_NORMALISE, TE_ROLLOUT_ROW0, TE_VARIANT_LRP,
-                   TE_VARIANT_OURS)
+from ._lib import (TE_HEADMEAN_CLAMP, TE_HEADMEAN_ROW0, TE_IMPL_SIMPLE, TE_ROLLOUT_CLS_FIXUP, TE_ROLLOUT_NORMALISE,
+                   TE_ROLLOUT_ROW0, TE_VARIANT_LRP, TE_VARIANT_OURS)
 
 Tensor = torch.Tensor
 _VARIANTS = {"ours": TE_VARIANT_OURS, "lrp": TE_VARIANT_LRP}
@@ -1120,6 +1120,30 @@ def gradcam_headmean(grad: Tensor, cam: Tensor, out: Optional[Tensor] = None) ->
     return out
 
 
+def attn_headmean(attn: Tensor, out: Optional[Tensor] = None, clamp: bool = False, row0: bool = False) -> Tensor:
+    """bf16 attention probabilities [B,H,N,N] (batch / head strides, last two dims contiguous) -> fp32 [B,N,N] =
+    mean_h attn (clamp: mean_h max(attn, 0)), heads summed in order in fp32; row0=True -> [B,N], query row 0 alone.
+    ``out``: a contiguous fp32 destination, e.g. one layer's slice of the rollout stack.  fp32 attention has no kernel
+    here: the generators keep their torch expressions for it."""
+    attn = _prep_bf16(attn)
+    if attn.dim() != 4 or attn.shape[2] != attn.shape[3]:
+        raise _lib.TeError(f"attn_headmean: expected [B,H,N,N] attention probabilities, got {tuple(attn.shape)}")
+    B, H, N, _ = attn.shape
+    if attn.stride(3) != 1 or attn.stride(2) != N:
+        attn = attn.contiguous()
+    shape = (B, N) if row0 else (B, N, N)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=attn.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != attn.device:
+        raise _lib.TeError(f"attn_headmean: out must be a contiguous float32 {shape} on {attn.device}")
+    flags = (TE_HEADMEAN_CLAMP if clamp else 0) | (TE_HEADMEAN_ROW0 if row0 else 0)
+    n = N if row0 else N * N
+    with _on_device(attn) as lib, _timed("attn_headmean", 0.0, 2.0 * B * H * n + 4.0 * B * n):
+        _lib.check(lib.te_attn_headmean_bf16(_ptr(attn), attn.stride(0), attn.stride(1), _ptr(out), B, H, N, flags,
+                                             _stream(attn)), "te_attn_headmean_bf16")
+    return out
+
+
 # ---------------------------------------------------------------------------------------- a11
 # The generators consume row 0 of the rollout only: chain it as a row vector (te_rollout_f32 with TE_ROLLOUT_ROW0).
 # Tests flip this to run the full (N x N)(N x N) product chain and slice row 0 afterwards.
@@ -1201,11 +1225,14 @@ def heatmap(maps: Tensor, scale: int = 16, normalise: bool = True, with_mask: bo
 
 # ---------------------------------------------------------------------------------------- 8f.4 perturbation inputs
 def perturb(vis: Tensor, data: Tensor, ks: Sequence[int], mean: Optional[Sequence[float]] = None,
-            std: Optional[Sequence[float]] = None) -> Tensor:
+            std: Optional[Sequence[float]] = None, out_dtype: torch.dtype = torch.float32) -> Tensor:
     """pertubation_eval_from_hdf5.py:88-101 for all steps at once: vis [B, H*W] (or [B,1,H,W]) relevance, data
     [B,C,H,W] -> [len(ks), B, C, H, W]: the ks[s] most relevant pixels of every sample zeroed in every channel, then
-    (x - mean[c]) / std[c]."""
+    (x - mean[c]) / std[c].  out_dtype=torch.bfloat16 (the input of a bf16 classifier): the same fp32 values rounded once
+    to bf16, to nearest even -- ``perturb(...).to(torch.bfloat16)`` bit for bit, without the fp32 tensor."""
     import ctypes
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.TeError(f"perturb: out_dtype must be float32 or bfloat16, got {out_dtype}")
     data = _c(data)
     B, C, H, W = data.shape
     HW = H * W
@@ -1213,14 +1240,15 @@ def perturb(vis: Tensor, data: Tensor, ks: Sequence[int], mean: Optional[Sequenc
     if vis.shape[1] != HW:
         raise _lib.TeError(f"perturb: vis {tuple(vis.shape)} does not cover the {H}x{W} pixels of data")
     S = len(ks)
-    out = torch.empty((S, B, C, H, W), dtype=torch.float32, device=data.device)
+    out = torch.empty((S, B, C, H, W), dtype=out_dtype, device=data.device)
     k_arr = (ctypes.c_int64 * S)(*[int(k) for k in ks])
     m_arr = None if mean is None else (ctypes.c_float * C)(*[float(v) for v in mean])
     s_arr = None if std is None else (ctypes.c_float * C)(*[float(v) for v in std])
+    name = "te_perturb_f32" if out_dtype == torch.float32 else "te_perturb_bf16"
     with _on_device(data) as lib:
         ws = _ws(lib.te_perturb_workspace_bytes(B, S), data)
-        _lib.check(lib.te_perturb_f32(_ptr(vis), _ptr(data), _ptr(out), B, C, HW, k_arr, S, m_arr, s_arr, _ptr(ws),
-                                      ws.numel(), _stream(data)), "te_perturb_f32")
+        _lib.check(getattr(lib, name)(_ptr(vis), _ptr(data), _ptr(out), B, C, HW, k_arr, S, m_arr, s_arr, _ptr(ws),
+                                      ws.numel(), _stream(data)), name)
     return out
 
 

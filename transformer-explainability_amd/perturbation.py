@@ -4,7 +4,7 @@ baselines/ViT/pertubation_eval_from_hdf5.py:25-144 without its dataset / hdf5 / 
 Per batch the reference runs, for each of 9 perturbation steps, torch.topk over 50,176 relevance values per image, an
 index repeat, a clone, a scatter and a normalisation, then one model forward and five small reductions with a
 device-to-host copy each.  Here the 9 masked + normalised copies (and the normalised original, as step k = 0) come out
-of ONE te_perturb_f32 call, the forwards run as one batch of 10 B images (chunked by ``max_forward_batch``), and the
+of ONE te_perturb_f32 call (te_perturb_bf16 for a bf16 classifier), the forwards run as one batch of 10 B images (chunked by ``max_forward_batch``), and the
 metrics stay on the device until ``arrays()`` / ``save()``.
 
 Result arrays have the reference's names and shapes (``save`` writes the same six .npy files, :120-125).
@@ -35,6 +35,13 @@ class PerturbationEvaluator:
         else:
             raise Exception("scale not valid")                                       # :39
         self.model = model.eval()
+        # the classifier's dtype, taken once: a bf16 model gets its 10 B inputs in bf16 straight from te_perturb_bf16
+        # (the fp32 values rounded once), logits go back to fp32 before any metric.  fp32 models: the calls below are
+        # today's.  Other dtypes have no kernel.
+        par = next(self.model.parameters(), None)
+        self.input_dtype = torch.bfloat16 if par is not None and par.dtype == torch.bfloat16 else torch.float32
+        if par is not None and par.is_floating_point() and par.dtype not in (torch.float32, torch.bfloat16):
+            raise ops._lib.TeError(f"PerturbationEvaluator: {ops.DTYPES_MSG}; the classifier is {par.dtype}")
         self.neg, self.wrong = bool(neg), bool(wrong)
         self.mean, self.std = tuple(mean), tuple(std)
         self.ks = [int(self.base_size * s) for s in self.steps]                      # :91
@@ -64,7 +71,10 @@ class PerturbationEvaluator:
         vis = vis.reshape(B, -1).float()
         if self.neg:
             vis = -vis                                                               # :85-86
-        x = ops.perturb(vis, data.float(), [0] + self.ks, self.mean, self.std)       # [10,B,C,H,W]; step 0 = original
+        if self.input_dtype == torch.bfloat16:
+            x = ops.perturb(vis, data.float(), [0] + self.ks, self.mean, self.std, out_dtype=torch.bfloat16)
+        else:
+            x = ops.perturb(vis, data.float(), [0] + self.ks, self.mean, self.std)   # [10,B,C,H,W]; step 0 = original
         S = len(self.ks)
         logits = self._forward(x.reshape((S + 1) * B, *data.shape[1:])).reshape(S + 1, B, -1).float()
         pred = logits[0]                                                             # :56-66

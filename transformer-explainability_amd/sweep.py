@@ -166,11 +166,29 @@ class SaliencySweep:
         self.method, self.vis_class, self.is_ablation = method, vis_class, bool(is_ablation)
         self.lrp, self.orig_lrp, self.baselines, self.device = lrp, orig_lrp, baselines, device
 
+    def _generator(self):
+        """The generator object the method runs on (generate_visualizations.py:67-93)."""
+        if self.method in ("full_lrp", "lrp_last_layer"):
+            return self.orig_lrp
+        return self.baselines if self.method in ("rollout", "attn_gradcam") else self.lrp
+
+    def _to_model_dtype(self, data):
+        """The normalised batch in the dtype of the model the method runs on: a bf16 model takes bf16 images (the maps
+        stay fp32: bf16 operands, fp32 relevance).  full_lrp / lrp_last_layer run on the lrp rule library, which has no
+        bf16 rules: refused here, before the forward pass and before anything reaches the store."""
+        par = next(self._generator().model.parameters(), None)
+        if par is None or not par.is_floating_point() or par.dtype == data.dtype:
+            return data
+        if par.dtype == torch.bfloat16 and self._generator() is self.orig_lrp:
+            ops._bf16_rule("lrp", 1.0, f"the sweep method {self.method!r} (the lrp rule library)")
+        return data.to(par.dtype)
+
     def explain(self, data, target=None, return_maps=False):
         """One batch of normalised images -> min-max normalised maps [B,1,H,W] at image resolution (:60-98);
         return_maps: also the patch-level maps [B, g*g] they were up-sampled from."""
         index = target if self.vis_class == "target" else None                   # :62-64
         m = self.method
+        data = self._to_model_dtype(data)
         if m == "rollout":
             res = self.baselines.generate_rollout(data, start_layer=1)
         elif m == "lrp":

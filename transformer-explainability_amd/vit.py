@@ -481,7 +481,10 @@ def make_vit_module(L):
                 return c.clamp(min=0).mean(dim=1)[:, 0, 1:]
 
             if method == "last_layer_attn":
-                return self.blocks[-1].attn.get_attn().clamp(min=0).mean(dim=1)[:, 0, 1:]
+                attn = self.blocks[-1].attn.get_attn()
+                if ops._is_bf16(attn):       # fp32 map of a bf16 model: clamp, then the head mean summed in fp32
+                    return ops.attn_headmean(attn.detach(), clamp=True, row0=True)[:, 1:]
+                return attn.clamp(min=0).mean(dim=1)[:, 0, 1:]
             return None   # unknown method: the reference falls through silently
 
     def vit_base_patch16_224(pretrained=False, **kwargs):
