@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""Compare the gfx950 device code of two source trees, one translation unit at a time.
+
+    python scripts/isa_diff.py OLD_TREE NEW_TREE [FILE.hip ...]
+
+A refactor of csrc/ (helpers moved between files, headers split or merged) must not change a single instruction.  For every
+entry of build.SOURCES (or only the files named) both trees' file is compiled with build.CXXFLAGS plus
+`--cuda-device-only -S`, and the two listings are compared after a normalisation that removes what names alone change:
+
+  * `__hip_cuid_<hex>` (a hash of the input path and content) becomes `__hip_cuid_X`;
+  * every distinct mangled symbol `_Z...` becomes `SYM<k>`, numbered in order of first appearance: moving a parameter type
+    such as `Strided` out of an anonymous namespace renames the kernel and changes nothing else.
+
+One line per file: lines, sha256 of the old and of the new normalised listing, `same` / `DIFFERENT`.  Exit status 1 on any
+difference (the normalised listings of a differing file are kept in --keep DIR for `diff`).  Flags and the file list are the
+flags and the list of NEW_TREE's build.py.
+"""
+import argparse
+import hashlib
+import importlib.util
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+PKG = "transformer-explainability_amd"
+MAX_JOBS = 16
+
+
+def load_build(tree):
+    spec = importlib.util.spec_from_file_location("_te_build", os.path.join(tree, PKG, "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def normalise(text):
+    text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", text)
+    names = {}
+    return re.sub(r"_Z[A-Za-z0-9_]+", lambda m: names.setdefault(m.group(0), "SYM%d" % len(names)), text)
+
+
+def listing(build, tree, src, out):
+    csrc = os.path.join(tree, PKG, "csrc")
+    cmd = [build._hipcc(), *build.CXXFLAGS, "--cuda-device-only", "-S", "-I", os.path.join(tree, "include"), "-I", csrc,
+           os.path.join(csrc, src), "-o", out]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed on %s of %s:\n%s" % (src, tree, r.stdout))
+    with open(out) as f:
+        return normalise(f.read())
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("old_tree")
+    ap.add_argument("new_tree")
+    ap.add_argument("files", nargs="*", help="entries of build.SOURCES (default: all)")
+    ap.add_argument("--keep", metavar="DIR", help="write the normalised listings of differing files here")
+    ap.add_argument("-j", type=int, default=min(MAX_JOBS, os.cpu_count() or 1))
+    a = ap.parse_args()
+    old_tree, new_tree = os.path.abspath(a.old_tree), os.path.abspath(a.new_tree)
+    build = load_build(new_tree)
+    sources = a.files or build.SOURCES
+    unknown = [s for s in sources if s not in build.SOURCES]
+    if unknown:
+        sys.exit("not in build.SOURCES: " + " ".join(unknown))
+    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max(1, min(a.j, MAX_JOBS))) as pool:
+        jobs = {(side, s): pool.submit(listing, build, tree, s, os.path.join(tmp, "%s_%s.s" % (side, s)))
+                for s in sources for side, tree in (("old", old_tree), ("new", new_tree))}
+        different = 0
+        print("%-22s %8s  %-16s %-16s" % ("file", "lines", "sha256 old", "sha256 new"))
+        for s in sources:
+            old, new = jobs["old", s].result(), jobs["new", s].result()
+            h_old, h_new = (hashlib.sha256(t.encode()).hexdigest()[:16] for t in (old, new))
+            same = old == new
+            different += not same
+            print("%-22s %8d  %-16s %-16s %s" % (s, new.count("\n"), h_old, h_new, "same" if same else "DIFFERENT"), flush=True)
+            if not same and a.keep:
+                os.makedirs(a.keep, exist_ok=True)
+                for side, t in (("old", old), ("new", new)):
+                    with open(os.path.join(a.keep, "%s.%s.s" % (s, side)), "w") as f:
+                        f.write(t)
+    print("%d of %d translation units differ" % (different, len(sources)))
+    return 1 if different else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

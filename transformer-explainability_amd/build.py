@@ -70,11 +70,13 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     os.makedirs(OBJ_DIR, exist_ok=True)
     os.makedirs(LIB_DIR, exist_ok=True)
-    headers = [os.path.join(CSRC, "te_common.h"), os.path.join(CSRC, "te_attn_l6.h"), os.path.join(INCLUDE, "te_relprop.h"), __file__]
+    buildid = _buildid_module()
+    # every csrc/*.h and include/*.h makes every object stale: the list the build id hashes, so a new header cannot be forgotten
+    headers = [f for f in buildid.source_files() if f.endswith(".h")] + [__file__]
     obj_dir, lib_path = OBJ_DIR, LIB_PATH
     # provenance: a content hash of every source + the flags, baked into te_api.o (te_build_id()) and
     # checked by _lib.load() against the tree.  A changed id recompiles te_api.hip even when its own mtime says "fresh".
-    bid = _buildid_module().build_id(CXXFLAGS)
+    bid = buildid.build_id(CXXFLAGS)
     stamp = os.path.join(obj_dir, "build_id.txt")
     old_bid = open(stamp).read().strip() if os.path.exists(stamp) else None
     if old_bid == bid and os.path.exists(lib_path) and not force:

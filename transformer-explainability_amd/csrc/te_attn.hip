@@ -12,31 +12,11 @@
 // This file holds the SIMPLE kernels (one thread per output element, k-ordered fmaf chains); the
 // LDS-tiled MFMA versions live in te_attn_mfma.hip and are selected by the API below unless
 // TE_IMPL_SIMPLE is set or the head dim is not 64.
-#include "te_common.h"
-
-namespace te_attn_mfma {
-// implemented in te_attn_mfma.hip; return false if the shape is not supported by the tiled kernels
-bool av_supported(int64_t N, int64_t D);
-int av_launch(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const float* attn,
-              const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh,
-              int64_t z_sn, float* cam_attn, float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn, int64_t B,
-              int64_t H, int64_t N, int64_t D, float scale, float* ws, hipStream_t stream);
-bool qk_supported(int64_t N, int64_t D);
-int qk_launch(const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
-              const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn, const float* Z, float* cam_q, int64_t cq_sb,
-              int64_t cq_sh, int64_t cq_sn, float* cam_k, int64_t ck_sb, int64_t ck_sh, int64_t ck_sn,
-              int64_t B, int64_t H, int64_t N, int64_t D, float scale, float* ws, const float* r_scale,
-              int64_t r_scale_stride, hipStream_t stream);
-}  // namespace te_attn_mfma
+#include "te_internal.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-
-struct Strided {  // [B,H,N,D] view, D contiguous
-  int64_t sb, sh, sn;
-  __device__ __forceinline__ int64_t at(int64_t b, int64_t h, int64_t n) const { return b * sb + h * sh + n * sn; }
-};
 
 // S[b,h,i,d] = sd(R[b,h,i,d], sum_j attn[b,h,i,j] v[b,h,j,d])             (contiguous workspace)
 __global__ __launch_bounds__(kThreads) void av_s_simple(
@@ -134,6 +114,7 @@ __global__ __launch_bounds__(kThreads) void qk_cam_k_simple(
   cam_k[cs.at(b, h, j) + d] = (k[ks.at(b, h, j) + d] * u) * scale;
 }
 
+// (local on purpose: the simple kernels take any non-negative strides; te_attn_long.hip's strides_ok asks for 16-byte rows)
 inline bool strides_ok(int64_t sb, int64_t sh, int64_t sn) { return sb >= 0 && sh >= 0 && sn > 0; }
 
 }  // namespace

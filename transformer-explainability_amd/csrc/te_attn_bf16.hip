@@ -25,15 +25,11 @@
 //        row sums that kernel left in the workspace, and d_v^T = d_out^T X, d_k^T = q^T d_s with d_out^T / q^T staged 64 query
 //        rows at a time.
 // Every sum has an order that depends on N and the position only: a batch equals its samples bit for bit.
-#include "te_common.h"
+#include "te_x6.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+// (te_common.h: the vector types, Strided, crow; te_x6.h: TE_MFMA_BF16 -- one plane per operand here, no split)
 typedef uint32_t u32x2_u __attribute__((ext_vector_type(2), aligned(2)));      // four bf16 of a row of an N x N tensor (N odd: 2-byte aligned)
 
 constexpr int kT = 256;          // threads: four waves
@@ -43,14 +39,9 @@ constexpr int CH = 4;            // key blocks per pass of the wave-private tile
 constexpr int TP = CH * TI + 4;  // tile row pitch in bf16 (264 B: 8-byte aligned rows, lanes 2 banks apart)
 constexpr int QC = 64;           // query rows staged per step of the column kernel
 
-#define TE_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-struct Strided {  // [B,H,N,64] view, last dim contiguous
-  int64_t sb, sh, sn;
-};
-
 __device__ __forceinline__ float bf2f(uint32_t b) { return __uint_as_float(b << 16); }
-// two fp32 -> two bf16, round to nearest even (v_cvt_pk_bf16_f32); a in the low half
+// two fp32 -> two bf16, round to nearest even (v_cvt_pk_bf16_f32); a in the low half.  (pack2, exp_neg and tpos are local: the
+// rounding points of a bf16 model have no twin among the fp32 kernels)
 __device__ __forceinline__ uint32_t pack2(float a, float b) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
 }
@@ -62,8 +53,6 @@ __device__ __forceinline__ float rbf(float x) { return lo(pack2(x, 0.0f)); }    
 // softmax is two exponentials per element of the N x N tensor and bounded the kernel (VALU) before
 __device__ __forceinline__ float exp_neg(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 
-// accumulator register e of lane half kh <-> row of the 32x32 block
-__device__ __forceinline__ int crow(int e, int kh) { return (e & 3) + 8 * (e >> 2) + 4 * kh; }
 // Position of row kk of a 32-block in a transposed LDS operand: MFMA step s (rows 16 s ..) of lane half kh takes the rows
 // 16 s + 4 kh + {0..3, 8..11} -- registers 8 s .. 8 s + 7 of the block that is the other operand -- from 8 contiguous elements.
 __device__ __forceinline__ int tpos(int kk) { return (kk & 16) | (((kk >> 2) & 1) << 3) | (((kk >> 3) & 1) << 2) | (kk & 3); }

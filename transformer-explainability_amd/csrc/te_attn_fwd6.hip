@@ -16,7 +16,7 @@
 //   * out, transposed:     O[d][i] = sum_j v[j][d] p[i][j]  -- A = v^T (planes in LDS, written over k's after one barrier from loads
 //     requested before the first product, K order = the accumulator layout's: request_vt / write_vt), B = the probabilities straight from the accumulator registers, split into planes per
 //     K16 step; a lane (i, h) ends up with out[i][32 mb + 8 g + 4 h + (0..3)]: 16-byte pieces of the 'b n (h d)' row;
-//   * both products on v_mfma_f32_32x32x16_bf16 with three-way split operands (te_linear_x6.hip: an fp32 value is the exact sum of
+//   * both products on v_mfma_f32_32x32x16_bf16 with three-way split operands (te_x6.h: an fp32 value is the exact sum of
 //     three bf16 values; the six partial products above 2^-24, smallest first, fp32 accumulation): fp32-class accuracy
 //     (tests/test_gpu_producers.py: against stock PyTorch and against fp64);
 //   * two barriers per WORKGROUP (k planes staged / k planes free for v^T), none per tile: the seven row-block waves drift apart and
@@ -25,7 +25,9 @@
 // Every reduction has a fixed order that depends on N only: a batch equals its samples run one by one, bit for bit.
 #include <type_traits>
 
-#include "te_common.h"
+#include "te_buffer.h"
+#include "te_internal.h"
+#include "te_x6.h"
 
 namespace te_attn_fwd6 {
 
@@ -35,34 +37,8 @@ constexpr int kT = 512;                 // 8 waves; wave w owns query-row block 
 constexpr int kMaxN = 224;
 constexpr int kMaxB = kMaxN / 32;       // row / key blocks
 constexpr int kMaxS = kMaxN / 16;       // K16 steps over the keys (second product)
-constexpr int kFrag = 1024;             // one plane fragment: [kh 2][r 32][8 bf16]
 
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-#define TE_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-// x0, x1 -> three packed bf16 pairs (x0 low half): x = p[0] + p[1] + p[2] exactly (te_linear_x6.hip: split3_pk)
-__device__ __forceinline__ void split3_pk(float x0, float x1, unsigned (&p)[3]) {
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
-    p[q] = u;
-    x0 = x0 - __uint_as_float(u << 16);
-    x1 = x1 - __uint_as_float(u & 0xffff0000u);
-  }
-}
-// eight fp32 values (K order t = 0..7) -> the three plane operands of one lane
-__device__ __forceinline__ void planes_of8(const float (&x)[8], bf16x8 (&b)[3]) {
-  unsigned pk[4][3];
-#pragma unroll
-  for (int t2 = 0; t2 < 4; ++t2) split3_pk(x[2 * t2], x[2 * t2 + 1], pk[t2]);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) b[q] = __builtin_bit_cast(bf16x8, u32x4{pk[0][q], pk[1][q], pk[2][q], pk[3][q]});
-}
+// (te_x6.h: split3_pk, planes_of8, div2, swap_halves and the order of the six partial products, PA / PB)
 
 // k [rows < N][64] as A planes with M = key, K = d:  Pk[plane 3][step 4][jb NB][kh 2][r 32][8]: element = plane q of
 // k[32 jb + r][16 step + 8 kh + t].  One item = 8 consecutive d of one key: 8 threads cover the 256 bytes of a key's row.
@@ -131,16 +107,9 @@ __device__ __forceinline__ void write_vt(unsigned char* __restrict__ Pv, f32x4 (
   }
 }
 
-// e / s, correctly rounded wherever no intermediate leaves the normal range (the hardware's own expansion of an IEEE division
-// without its range scaling; s = a row's sum of exponentials, in [1, N])
-__device__ __forceinline__ f32x2 div2(f32x2 e, float s, float rcs) {
-  f32x2 q = e * f32x2{rcs, rcs};
-  const f32x2 r = __builtin_elementwise_fma(f32x2{-s, -s}, q, e);
-  return __builtin_elementwise_fma(r, f32x2{rcs, rcs}, q);
-}
-
 // exp(x) for x <= 0 (a score minus its row's maximum): 2^t on v_exp_f32 with t = x log2(e) carried as a rounded product plus its
-// exact residual (fma) plus the low part of log2(e): e^x = 2^t_hi (1 + ln2 t_lo) to ~1 ulp; results below the normal range are 0
+// exact residual (fma) plus the low part of log2(e): e^x = 2^t_hi (1 + ln2 t_lo) to ~1 ulp; results below the normal range are 0.
+// Local on purpose: scalar, and zero below -87 -- te_attn_l6.h's exp_le0 is the packed form that clamps at -150 (other bits).
 __device__ __forceinline__ float exp_le0(float x) {
   constexpr float kL2eHi = 1.44269502162933349609375f, kL2eLo = 1.925963033500011e-08f, kLn2 = 0.693147182464599609375f;
   const float t = x * kL2eHi;
@@ -166,7 +135,6 @@ __device__ __forceinline__ void store_piece(float* __restrict__ row, int j0, int
 constexpr int kTileLd = 36;                                 // floats per tile row
 // LAST = the key block that may straddle N: its pieces are guarded per lane.  Every other block leaves as buffer stores whose hardware
 // range check (descriptor = the (b, h)'s N x N matrix) drops the rows at or beyond N: no branch, no exec masking, 32-bit offsets.
-typedef __amdgpu_buffer_rsrc_t Rsrc;
 template <bool LAST>
 __device__ __forceinline__ void block_out(float* __restrict__ tile, const f32x16& a, float* __restrict__ base, Rsrc rs, int i0, int j0, int N) {
   const int lane = threadIdx.x & 63, n = lane & 31, kh = lane >> 5;
@@ -184,24 +152,6 @@ __device__ __forceinline__ void block_out(float* __restrict__ tile, const f32x16
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (unsigned)(((i0 + r) * N + j0 + 4 * c) * 4), 0, 0);
     }
   }
-}
-
-template <int I, int END, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < END) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, END>(f);
-  }
-}
-
-constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};      // planes (1,1) (0,2) (2,0) (0,1) (1,0) (0,0): smallest first
-
-// (v_permlane32_swap: lanes 32-63 of the first operand <-> lanes 0-31 of the second; te_linear_x6.hip)
-__device__ __forceinline__ void swap_halves(unsigned& lo_keep, unsigned& hi_keep) {
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  const u32x2 r = __builtin_amdgcn_permlane32_swap(lo_keep, hi_keep, false, false);
-  lo_keep = r[0];
-  hi_keep = r[1];
 }
 
 // PLANES: `out` also leaves as the operand planes of the projection that consumes it -- the signed planes of out [B N, C] and the

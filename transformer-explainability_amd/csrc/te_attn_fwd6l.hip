@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "te_attn_l6.h"
+#include "te_internal.h"
 
 namespace te_attn_fwd6l {
 

@@ -28,7 +28,9 @@
 // Reductions run in an order that depends on N only: a batch equals its samples run one by one, bit for bit.
 #include <type_traits>
 
-#include "te_common.h"
+#include "te_buffer.h"
+#include "te_internal.h"
+#include "te_x6.h"
 
 namespace te_attn_kb {
 
@@ -39,63 +41,9 @@ constexpr int kT = 512;        // threads per workgroup
 constexpr int kWaves = kT / 64;
 constexpr int XLD = 36;        // row stride (floats) of a wave's [32][32] staging block
 
-struct Strided {  // [B,H,N,64] view, 64 contiguous
-  int64_t sb, sh, sn;
-};
-
-// row (inside a 32-row block) of accumulator element e of lane half kh (v_mfma_f32_32x32x2_f32: D[i][j], j = lane & 31)
-__device__ __forceinline__ int crow(int e, int kh) { return (e & 3) + 8 * (e >> 2) + 4 * kh; }
-
-__device__ __forceinline__ void zero16(f32x16& a) {
-#pragma unroll
-  for (int e = 0; e < 16; ++e) a[e] = 0.0f;
-}
-
 enum { RULE = 0, BWD = 1 };
 
-// Buffer addressing (buffer_load / buffer_store ... s[rsrc], s_off offen): a 128-bit descriptor built from wave-uniform
-// values, a 32-bit per-lane byte offset and a scalar byte offset; accesses past `bytes` return 0 / are dropped.
-typedef __amdgpu_buffer_rsrc_t Rsrc;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ Rsrc make_rsrc(const float* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-}
-// bytes of a strided [N, 64] view (row stride sn floats) from its first element
-__device__ __forceinline__ unsigned view_bytes(int N, int64_t sn) { return ((unsigned)(N - 1) * (unsigned)sn + 64u) * 4u; }
-__device__ __forceinline__ float ld32(Rsrc r, unsigned voff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
-}
-__device__ __forceinline__ f32x4 ld128(Rsrc r, unsigned voff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-__device__ __forceinline__ void st32(float x, Rsrc r, unsigned voff) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, x), r, voff, 0, 0);
-}
-// A store the compiler's s_waitcnt insertion does not see.  With loads AND stores in flight hipcc assumes they may retire
-// out of order and drains vmcnt to zero before every use of a loaded value; hidden, the loads alone are counted exactly.
-// Safe: vmcnt counts these stores too, so a wait hipcc computes for its loads can only wait longer than it thinks, never
-// shorter (loads retire in order among themselves); the store data is read at issue (no expcnt for VMEM stores on gfx9+).
-// Loads hipcc's s_waitcnt insertion does not see either: across a loop back-edge it loses the age order of in-flight loads
-// and waits vmcnt(0) at the first use of ANY of them -- a full drain of the prefetch pipeline once per tile.  The tile loop
-// therefore issues all its global loads and stores as inline asm and waits with hand-counted s_waitcnt vmcnt(n), n = the
-// number of YOUNGER LOADS in flight (stores are never counted: loads retire in order among themselves, and a store that
-// retires late only makes the wait longer).  After the wait, TE_PIN makes the value's first use follow it in program order.
-__device__ __forceinline__ f32x4 ld128_hidden(Rsrc r, unsigned voff) {
-  f32x4 v;
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=&v"(v) : "v"(voff), "s"(r));
-  return v;
-}
-#define TE_VM_WAIT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define TE_PIN(v) asm volatile("" : "+v"(v))
-__device__ __forceinline__ void st128_hidden(f32x4 x, Rsrc r, unsigned voff) {
-  // (s_nop: a store of more than 64 bits reads the upper half of its data one cycle late -- the VALU instruction that follows
-  //  must not write those registers.  hipcc pads this hazard for its own stores, not for inline asm: without the wait state
-  //  cam_q came back with the upper 8 bytes of some lanes' 16-byte pieces replaced by whatever was written next, sporadically)
-  asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" : : "v"(x), "v"(voff), "s"(r));
-}
-__device__ __forceinline__ void st32_hidden(float x, Rsrc r, unsigned voff) {
-  asm volatile("buffer_store_dword %0, %1, %2, 0 offen" : : "v"(x), "v"(voff), "s"(r));
-}
+// (te_buffer.h: the descriptor, the plain and the hidden loads / stores of the tile loop and why they are hidden)
 
 // ------------------------------------------------------------------------------------------------
 // AV rule (MODE RULE):  S = sd(R, Z) [N,64];  cam_attn = attn . (S v^T) * scale;  cam_v = v . (attn^T S) * scale
@@ -103,7 +51,7 @@ __device__ __forceinline__ void st32_hidden(float x, Rsrc r, unsigned voff) {
 // R, Z strided [B,H,N,64]; attn, cam_attn contiguous [B*H,N,N]; v, cam_v strided.
 // grid = BH * ngroups (bh fastest); workgroup g of a (b, h) owns key blocks [g KBG, (g + 1) KBG), wave w block g KBG + w.
 //
-// The products run on bf16 MFMAs at fp32 accuracy ("x6", as te_linear_x6.hip): every fp32 operand is the exact sum of three
+// The products run on bf16 MFMAs at fp32 accuracy ("x6", te_x6.h): every fp32 operand is the exact sum of three
 // bf16 planes, the six partial products above 2^-24 are kept (a1 b1 + a0 b2 + a2 b0 + a0 b1 + a1 b0 + a0 b0, smallest first),
 // fp32 accumulation.  Why: v_mfma_f32_32x32x2_f32 runs at the fp32 VECTOR rate and its time ADDS to the vector-ALU time of
 // the SIMD's waves (per-wave phase profile of the round-5 fp32-MFMA version of this kernel,
@@ -118,39 +66,7 @@ __device__ __forceinline__ void st32_hidden(float x, Rsrc r, unsigned voff) {
 //                 [d][row position] from LDS, the row positions permuted to that order (pos = row with bits 2 and 3 swapped)
 // The S producer (all 512 threads, one float4 each) writes both plane images of its tile.
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-#define TE_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-// x = p[0] + p[1] + p[2] exactly (te_linear_x6.hip: split3_pk); p[q] = the packed pair (x0 low half, x1 high half) of plane q
-__device__ __forceinline__ void split3_pk(float x0, float x1, unsigned (&p)[3]) {
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
-    p[q] = u;
-    x0 = x0 - __builtin_bit_cast(float, u << 16);
-    x1 = x1 - __builtin_bit_cast(float, u & 0xffff0000u);
-  }
-}
-// eight consecutive K values -> one MFMA operand fragment per plane
-__device__ __forceinline__ void split3_x8(const float (&x)[8], bf16x8 (&pl)[3]) {
-  unsigned w[4][3];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) split3_pk(x[2 * i], x[2 * i + 1], w[i]);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) pl[q] = __builtin_bit_cast(bf16x8, u32x4{w[0][q], w[1][q], w[2][q], w[3][q]});
-}
-// acc += a b with the six partial products, smallest first
-__device__ __forceinline__ void mfma_x6(f32x16& acc, const bf16x8 (&a)[3], const bf16x8 (&b)[3]) {
-  acc = TE_MFMA_BF16(a[1], b[1], acc);
-  acc = TE_MFMA_BF16(a[0], b[2], acc);
-  acc = TE_MFMA_BF16(a[2], b[0], acc);
-  acc = TE_MFMA_BF16(a[0], b[1], acc);
-  acc = TE_MFMA_BF16(a[1], b[0], acc);
-  acc = TE_MFMA_BF16(a[0], b[0], acc);
-}
+// (te_x6.h: split3_pk, planes_of8, mfma_x6)
 
 constexpr int kRLD = 144;                  // bytes per row of a row-major S plane [32 rows][64 d] (128 + 16: conflict-free b128)
 constexpr int kTLD = 80;                   // bytes per row of a transposed S plane [64 d][32 row positions] (64 + 16)
@@ -211,8 +127,8 @@ __global__ __launch_bounds__(kT) void av6_kb_kernel(
   const unsigned r_off = ((unsigned)srow * (unsigned)rs.sn + 4u * sc) * 4u, z_off = ((unsigned)srow * (unsigned)zs.sn + 4u * sc) * 4u;
   const unsigned r_tile = (unsigned)TI * (unsigned)rs.sn * 4u, z_tile = (unsigned)TI * (unsigned)zs.sn * 4u;
   auto fetch_rz = [&](int it) __attribute__((always_inline)) {          // (any it: tiles beyond the last read zeros)
-    rr = ld128_hidden(r_rs, r_off + (unsigned)it * r_tile);
-    if constexpr (MODE == RULE) zz = ld128_hidden(z_rs, z_off + (unsigned)it * z_tile);
+    ld128_hidden(rr, r_rs, r_off + (unsigned)it * r_tile);
+    if constexpr (MODE == RULE) ld128_hidden(zz, z_rs, z_off + (unsigned)it * z_tile);
   };
   constexpr int kRz = (MODE == RULE) ? 2 : 1;
   auto pin_rz = [&]() __attribute__((always_inline)) {
@@ -280,7 +196,7 @@ __global__ __launch_bounds__(kT) void av6_kb_kernel(
     for (int s4 = 0; s4 < 4; ++s4) {
       const f32x4 lo = ld128(v_rs, off + 64u * s4), hi = ld128(v_rs, off + 64u * s4 + 16u);
       const float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      split3_x8(x, vpl[s4]);
+      planes_of8(x, vpl[s4]);
     }
   }
   float* const Xb = Xw[wave];
@@ -292,7 +208,7 @@ __global__ __launch_bounds__(kT) void av6_kb_kernel(
   auto fetch_attn = [&](int it, f32x4 (&dst)[4]) __attribute__((always_inline)) {
     const unsigned base = (unsigned)(it * TI) * row_bytes;
 #pragma unroll
-    for (int p = 0; p < 4; ++p) dst[p] = ld128_hidden(a_rs, lane_x4 + (base + (unsigned)(8 * p) * row_bytes));
+    for (int p = 0; p < 4; ++p) ld128_hidden(dst[p], a_rs, lane_x4 + (base + (unsigned)(8 * p) * row_bytes));
   };
   auto to_acc = [&](const f32x4 (&src)[4], float (&dst)[16]) __attribute__((always_inline)) {
 #pragma unroll
@@ -370,7 +286,7 @@ __global__ __launch_bounds__(kT) void av6_kb_kernel(
       for (int s2 = 0; s2 < 2; ++s2) {
         const float x[8] = {ac[8 * s2], ac[8 * s2 + 1], ac[8 * s2 + 2], ac[8 * s2 + 3],
                             ac[8 * s2 + 4], ac[8 * s2 + 5], ac[8 * s2 + 6], ac[8 * s2 + 7]};
-        split3_x8(x, apl[s2]);
+        planes_of8(x, apl[s2]);
       }
 #pragma unroll
       for (int db = 0; db < 2; ++db) {

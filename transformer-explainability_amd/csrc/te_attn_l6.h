@@ -1,14 +1,14 @@
 // te_attn_l6.h -- what the long-sequence attention producers (te_attn_fwd6l.hip, te_attn_bwd6l.hip; round 6) share: the chunk
-// geometry, the three-way bf16 split, the staging of a 64-wide operand's chunk as MFMA A-operand planes in LDS (key-major for a
+// geometry, the staging of a 64-wide operand's chunk as MFMA A-operand planes in LDS (key-major for a
 // product that contracts the head dimension, head-dimension-major for one that contracts the keys), the product of a chunk with
 // the wave's own 32 rows, and the way a 32 x 32 block of an [N, N] tensor travels between the accumulator layout and memory.
 #pragma once
-#include "te_common.h"
+#include "te_buffer.h"
+#include "te_x6.h"
 
 namespace te_attn_l6 {
 
 constexpr int kMaxN = 640;
-constexpr int kFrag = 1024;             // one plane fragment: [kh 2][r 32][8 bf16]
 constexpr int kTileLd = 36;             // floats per row of the wave-private [32][36] tile (conflict-free 16-byte writes)
 // W waves per workgroup; wave w owns row block part * RB + w.  A chunk = 8 W keys, so that staging it is one item per thread:
 //   W = 8: 64-key chunks (2 key blocks, 4 K16 steps of the second product), 135 KB of LDS, one workgroup per CU
@@ -28,36 +28,7 @@ struct Cfg {
   static constexpr int kLds = kTileOff + W * 32 * kTileLd * 4;
 };
 
-struct Strided {  // [B,H,N,64] view, 64 contiguous
-  int64_t sb, sh, sn;
-};
-
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t Rsrc;
-
-#define TE_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-// x0, x1 -> three packed bf16 pairs (x0 low half): x = p[0] + p[1] + p[2] exactly (te_linear_x6.hip: split3_pk)
-__device__ __forceinline__ void split3_pk(float x0, float x1, unsigned (&p)[3]) {
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
-    p[q] = u;
-    x0 = x0 - __uint_as_float(u << 16);
-    x1 = x1 - __uint_as_float(u & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ void planes_of8(const float (&x)[8], bf16x8 (&b)[3]) {
-  unsigned pk[4][3];
-#pragma unroll
-  for (int t2 = 0; t2 < 4; ++t2) split3_pk(x[2 * t2], x[2 * t2 + 1], pk[t2]);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) b[q] = __builtin_bit_cast(bf16x8, u32x4{pk[0][q], pk[1][q], pk[2][q], pk[3][q]});
-}
+// (te_x6.h: the three-way split -- split3_pk, planes_of8 --, div2 and the order of the six partial products, PA / PB; te_buffer.h: Rsrc)
 
 // ---- chunk c of k [N][64] as A planes with M = key, K = d:  Pk[plane 3][step 4][jb kNKB][kh 2][r 32][8], element = plane q of
 // k[kKC c + 32 jb + r][16 step + 8 kh + t].  One item per thread: 8 consecutive d of one key (8 threads cover a key's 256 bytes).
@@ -116,12 +87,6 @@ __device__ __forceinline__ void write_v(unsigned char* __restrict__ Pv, const VR
   for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8*>(dst + q * Cfg<W>::kPlane) = b[q];
 }
 
-// e / s, correctly rounded wherever no intermediate leaves the normal range (te_attn_fwd6.hip: div2)
-__device__ __forceinline__ f32x2 div2(f32x2 e, float s, float rcs) {
-  f32x2 q = e * f32x2{rcs, rcs};
-  const f32x2 r = __builtin_elementwise_fma(f32x2{-s, -s}, q, e);
-  return __builtin_elementwise_fma(r, f32x2{rcs, rcs}, q);
-}
 // exp(x) for two x <= 0 (a score minus its row's maximum; -inf for the keys beyond N) on packed fp32 instructions: 2^t on
 // v_exp_f32 with t = x log2(e) carried as a rounded product plus its exact residual (fma) plus the low part of log2(e):
 // e^x = 2^t_hi (1 + ln2 t_lo) to ~1 ulp.  x is clamped at -150 first (2^-216 = 0 on v_exp_f32; -inf - (-inf) never forms).
@@ -133,6 +98,7 @@ __device__ __forceinline__ f32x2 exp2_le0(f32x2 x) {
   const f32x2 r = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
   return __builtin_elementwise_fma(r * f32x2{kLn2, kLn2}, lo, r);
 }
+// (local on purpose: te_attn_fwd6.hip has a scalar exp_le0 of its own that is zero below -87 -- other bits for x < -87)
 __device__ __forceinline__ float exp_le0(float x) { return exp2_le0(f32x2{x, x})[0]; }
 __device__ __forceinline__ f32x2 add2(f32x2 a, f32x2 b) { return f32x2{a[0] + b[0], a[1] + b[1]}; }
 __device__ __forceinline__ f32x2 sub2(float a, float b, float m) { return f32x2{a - m, b - m}; }
@@ -182,8 +148,6 @@ __device__ __forceinline__ void block_out(float* __restrict__ tile, const f32x16
     }
   }
 }
-
-constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};      // planes (1,1) (0,2) (2,0) (0,1) (1,0) (0,0): smallest first
 
 // scores of one chunk, transposed: acc[u][4 g + c] = sum_d k[kKC c + 32 u + 8 g + 4 h + c][d] q[i][d] for lane (i, h); the key
 // blocks' chains interleaved.  Called by both passes: the same instruction sequence on the same operands, the same bits.

@@ -21,25 +21,7 @@
 // depends on N only, so a batch equals its samples run one by one, bit for bit.
 #include <algorithm>
 
-#include "te_common.h"
-
-namespace te_attn_fwd6l {      // te_attn_fwd6l.hip: row-block owners on bf16 MFMAs, two walks over the keys (round 6) -- the default forward, 64 < N <= 640
-bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
-int launch(const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
-           const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sn, const float* mask, float* z_qk, float* x_scaled, float* attn,
-           float* out, int64_t o_sb, int64_t o_sh, int64_t o_sn, int64_t B, int64_t H, int64_t N, float scale, hipStream_t stream);
-}  // namespace te_attn_fwd6l
-
-namespace te_attn_bwd6l {      // te_attn_bwd6l.hip: the row side of the backward pass in the same structure (round 6), 64 < N <= 640
-bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
-int launch_rows(const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn, const float* out, int64_t o_sb, int64_t o_sh,
-                int64_t o_sn, const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn, const float* v, int64_t v_sb, int64_t v_sh,
-                int64_t v_sn, const float* attn, float* d_attn, float* rowdot, float* d_q, int64_t dq_sb, int64_t dq_sh, int64_t dq_sn,
-                int64_t B, int64_t H, int64_t N, float scale, int need_qk, hipStream_t stream);
-int launch_cols(const float* attn, const float* d_attn, const float* rowdot, const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn,
-                const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, float* d_v, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn, float* d_k,
-                int64_t dk_sb, int64_t dk_sh, int64_t dk_sn, int64_t B, int64_t H, int64_t N, float scale, int need_qk, hipStream_t stream);
-}  // namespace te_attn_bwd6l
+#include "te_internal.h"
 
 namespace {
 
@@ -52,17 +34,7 @@ constexpr int VLD = 80;         // row stride of the [192][64] key-side operand 
 constexpr int KG = 256;         // keys staged per pass of the score products
 constexpr int KV = 192;         // keys staged per pass of the row products (P v, d_s k)
 
-struct Strided {  // [B,H,N,64] view, last dim contiguous
-  int64_t sb, sh, sn;
-};
-
-#define TE_MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-#define TE_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int crow(int e, int kh) { return (e & 3) + 8 * (e >> 2) + 4 * kh; }
+// (te_common.h: Strided, f32x4_u, f32x2, crow, TE_MFMA32 / TE_MFMA16)
 __device__ __forceinline__ int ldw_of(int N) { return ((N + 31) & ~31) + 4; }
 
 // A group of <= 256 rows x 64 floats of a strided operand travels global -> registers (fetch_rows: 8 float4 per thread, the
@@ -464,6 +436,7 @@ inline void allow_lds(K kern, size_t bytes) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+// (local on purpose: these kernels move 16-byte pieces of [.., 64] rows; te_attn.hip's strides_ok accepts any non-negative strides)
 inline bool strides_ok(int64_t sb, int64_t sh, int64_t sn) { return sb >= 0 && sh >= 0 && sn >= 64 && (sn % 4) == 0 && (sh % 4) == 0 && (sb % 4) == 0; }
 
 }  // namespace

@@ -22,19 +22,7 @@
 // flight in registers while the current chunk's MFMAs and epilogue run.  Strided [B,H,N,D] operands are read in
 // place (fused qkv layout).  Blocks of one (b,h) are blockIdx = tile * BH + bh apart: with BH a multiple of 8 they
 // land on one XCD and share that L2's copy of k / v / S.
-#include "te_common.h"
-
-namespace te_attn_rules {   // te_attn_rules.hip: the one-pass rule kernels (default)
-bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
-int av_launch(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const float* attn, const float* v, int64_t v_sb,
-              int64_t v_sh, int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn, float* cam_attn,
-              float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn, int64_t B, int64_t H, int64_t N, float scale,
-              hipStream_t stream);
-int qk_launch(const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb,
-              int64_t k_sh, int64_t k_sn, const float* Z, float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn,
-              float* cam_k, int64_t ck_sb, int64_t ck_sh, int64_t ck_sn, int64_t B, int64_t H, int64_t N, float scale,
-              float* qpart, const float* r_scale, int64_t r_scale_stride, hipStream_t stream);
-}  // namespace te_attn_rules
+#include "te_internal.h"
 
 namespace te_attn_mfma {
 
@@ -43,45 +31,8 @@ namespace {
 constexpr int TS = 64;        // tile side
 constexpr int kThreads = 256;
 
-struct Strided {  // [B,H,N,D] view, D contiguous
-  int64_t sb, sh, sn;
-};
-
-// 16-byte access that only promises 4-byte alignment (legal for gfx950 global loads / stores)
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
-
-#define TE_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
 __device__ __forceinline__ int swz(int row, int chunk) { return row * TS + ((chunk ^ (row & 15)) << 2); }
-// row of accumulator element e inside the wave's 32 x 32 block (C/D layout of the 32x32 MFMA)
-__device__ __forceinline__ int crow(int e, int kh) { return (e & 3) + 8 * (e >> 2) + 4 * kh; }
-
-__device__ __forceinline__ void zero(f32x16& a) {
-#pragma unroll
-  for (int e = 0; e < 16; ++e) a[e] = 0.0f;
-}
-
-// guarded 4-wide access at a dword-aligned address: elements [c, c+4) of a row with `cols_valid` valid columns
-__device__ __forceinline__ f32x4 load4(const float* __restrict__ p, int c, int cols_valid) {
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (c + 3 < cols_valid) {
-    v = *reinterpret_cast<const f32x4_u*>(p + c);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (c + e < cols_valid) v[e] = p[c + e];
-  }
-  return v;
-}
-__device__ __forceinline__ void store4(float* __restrict__ p, int c, int cols_valid, f32x4 v) {
-  if (c + 3 < cols_valid) {
-    *reinterpret_cast<f32x4_u*>(p + c) = v;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (c + e < cols_valid) p[c + e] = v[e];
-  }
-}
+// (te_common.h: Strided, f32x4_u, crow, zero16, load4 / store4, TE_MFMA32)
 
 // One 64 x 64 tile in flight: thread t holds elements (row = idx >> 4, cols 4 * (idx & 15) ..+3), idx = t + 256 i.
 struct TileRegs {
@@ -137,7 +88,7 @@ __device__ __forceinline__ void mma64(f32x16& acc, const float* __restrict__ At,
       const int k = kg * 8 + kh * 4 + j;
       const float av = A_KM ? frag_km(At, k, wm * 32 + lr) : a[j];
       const float bv = B_KM ? frag_km(Bt, k, wn * 32 + lr) : b[j];
-      acc = TE_MFMA(av, bv, acc);
+      acc = TE_MFMA32(av, bv, acc);
     }
   }
 }
@@ -208,7 +159,7 @@ __global__ __launch_bounds__(kThreads) void av_row_kernel(
     if (c + 1 < nch) load_tile(tv, v_bh + (int64_t)(c + 1) * TS * vs.sn, vs.sn, min(TS, N - (c + 1) * TS), TS);
     if (row_active && (wn * 32) < kc) {
       f32x16 g;
-      zero(g);
+      zero16(g);
       mma64<false, false>(g, St, Vt, wm, wn, lr, kh);
       const int gj = c * TS + wn * 32 + lr;
       if (rows_valid == TS && kc == TS) {
@@ -252,7 +203,7 @@ __global__ __launch_bounds__(kThreads) void col_kernel(
   const float* y_bh = Y + (int64_t)b * ys.sb + (int64_t)h * ys.sh;
   const int nch = (N + TS - 1) / TS;
   f32x16 acc;
-  zero(acc);
+  zero16(acc);
   TileRegs tm, ty;
   load_tile(tm, m_bh, N, min(TS, N), cols_valid);      // [k = i][m = j]
   load_tile(ty, y_bh, ys.sn, min(TS, N), TS);          // [k = i][n = d]
@@ -348,7 +299,7 @@ __global__ __launch_bounds__(kThreads) void qk_row_kernel(
   };
 
   f32x16 accq;
-  zero(accq);
+  zero16(accq);
   TileRegs tk, ts;
   load_tile(tk, k_bh, ks.sn, min(TS, N), TS);
   s_chunk(ts, 0);
@@ -396,7 +347,7 @@ __global__ __launch_bounds__(kThreads) void z_av_kernel(const float* __restrict_
   const float* v_bh = v + (int64_t)b * vs.sb + (int64_t)h * vs.sh;
   const int nch = (N + TS - 1) / TS;
   f32x16 acc;
-  zero(acc);
+  zero16(acc);
   TileRegs ta, tv;
   load_tile(ta, a_bh, N, rows_valid, min(TS, N));
   load_tile(tv, v_bh, vs.sn, min(TS, N), TS);
@@ -440,7 +391,7 @@ __global__ __launch_bounds__(kThreads) void z_qk_kernel(const float* __restrict_
   __syncthreads();
   if ((wm * 32) < rows_valid && (wn * 32) < cols_valid) {
     f32x16 acc;
-    zero(acc);
+    zero16(acc);
     mma64<false, false>(acc, Qt, Kt, wm, wn, lr, kh);
     const int gj = col0 + wn * 32 + lr;
     if (gj < N) {
@@ -470,7 +421,7 @@ __global__ __launch_bounds__(kThreads) void rollout_bmm_mfma_kernel(const float*
   const float* a_b = A + ((int64_t)b * N + row0) * N;
   const float* b_b = Bm + (int64_t)b * N * N + col0;
   f32x16 acc;
-  zero(acc);
+  zero16(acc);
   TileRegs ta, tb;
   load_tile(ta, a_b, N, rows_valid, min(TS, N));
   load_tile(tb, b_b, N, min(TS, N), cols_valid);

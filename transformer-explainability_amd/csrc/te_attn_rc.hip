@@ -16,13 +16,13 @@
 //     twice (15 + 15 vector instructions per element against the 40-60 of a trip through LDS and two barriers per tile).
 //   * every output is then ONE k-ordered chain inside one wave (K = all keys / all query rows, sixteen at a time): no partial
 //     sums, no LDS reduction, no arrival counters, no barrier inside a phase; a batch equals its samples bit for bit.
-//   * the products run on bf16 MFMAs with split operands (te_linear_x6.hip: an fp32 value is the exact sum of three bf16
+//   * the products run on bf16 MFMAs with split operands (te_x6.h: an fp32 value is the exact sum of three bf16
 //     values; six partial products, smallest first, fp32 accumulation): the evaluated TRANSPOSED, D[d][i], so that a lane owns
 //     ONE query row (key) and runs of four consecutive d -- q / cam_q (k / cam_k) move as 16-byte pieces.
 //   * the only shared operand is the 64-wide one: k^T (row phase) and then q^T (column phase) as bf16 planes in MFMA-fragment
 //     order in LDS (84 KB at N <= 224), staged once per phase -- one barrier per phase, not per tile.
 //   * the global loads of a phase run three K16 steps ahead in a ring of register sets; they are inline asm hipcc's waitcnt
-//     insertion does not see (te_attn_kb.hip explains why), waited for with hand-counted vmcnt; a set is re-requested only
+//     insertion does not see (te_buffer.h explains why), waited for with hand-counted vmcnt; a set is re-requested only
 //     after its values were consumed, and scripts/check_hidden_loads.py walks the compiled loops (tests/test_isa_hazards.py).
 //
 // N <= 224 (one workgroup per (b, h), the ViT-B/16 224^2 and DeiT shapes); longer sequences stay on te_attn_rules.hip.
@@ -31,7 +31,9 @@
 
 #include <type_traits>
 
-#include "te_common.h"
+#include "te_buffer.h"
+#include "te_internal.h"
+#include "te_x6.h"
 
 namespace te_attn_rc {
 
@@ -40,47 +42,11 @@ namespace {
 constexpr int kT = 512;                 // threads per workgroup: 8 waves, wave w owns row block w and key block w
 constexpr int kMaxN = 224;              // 7 blocks of 32
 constexpr int kMaxSteps = kMaxN / 16;   // K16 steps of a phase
-constexpr int kFrag = 1024;             // one plane fragment: [kh 2][r 32][8 bf16]
-
-struct Strided {  // [B,H,N,64] view, 64 contiguous
-  int64_t sb, sh, sn;
-};
-
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t Rsrc;
 
 enum { RULE = 0, BWD = 1 };
 enum { ROWS = 0, COLS = 1 };
 
-#define TE_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-#define TE_VM_WAIT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define TE_PIN(v) asm volatile("" : "+v"(v))
-
-__device__ __forceinline__ Rsrc make_rsrc(const float* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-}
-// loads hipcc's s_waitcnt insertion does not see (te_attn_kb.hip): offsets past the descriptor's size return 0 per dword
-__device__ __forceinline__ void ld128_hidden(f32x4& v, Rsrc r, unsigned voff) {
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=&v"(v) : "v"(voff), "s"(r));
-}
-__device__ __forceinline__ void ld32_hidden(float& v, Rsrc r, unsigned voff) {
-  asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=&v"(v) : "v"(voff), "s"(r));
-}
-
-// x0, x1 -> three packed bf16 pairs (x0 low half): x = p[0] + p[1] + p[2] exactly (te_linear_x6.hip: split3_pk)
-__device__ __forceinline__ void split3_pk(float x0, float x1, unsigned (&p)[3]) {
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
-    p[q] = u;
-    x0 = x0 - __uint_as_float(u << 16);
-    x1 = x1 - __uint_as_float(u & 0xffff0000u);
-  }
-}
+// (te_buffer.h: the hidden loads and their waits; te_x6.h: split3_pk, sd2 and the order of the six partial products, PA / PB)
 
 // The 64-wide operand M [rows < N][64] (k or q of this (b, h)) as bf16 planes in MFMA A-fragment order in LDS:
 //   Pl[plane 3][step NS][mb 2][kh 2][r 32][8]:  element = plane q of M[16 step + 8 kh + t][32 mb + r], t = 0..7
@@ -119,40 +85,6 @@ __device__ __forceinline__ void stage_planes(unsigned char* __restrict__ Pl, con
         *reinterpret_cast<u32x4*>(dst + (size_t)q * NS * 2 * kFrag) = u32x4{pl[0][q], pl[1][q], pl[2][q], pl[3][q]};
     }
   }
-}
-
-template <int I, int END, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < END) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, END>(f);
-  }
-}
-template <int N_>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
-}
-
-// safe_divide (modules/layers_ours.py:10-13) of two element pairs on packed fp32 instructions: den = b + 1e-9 (one rounding),
-// an exact-zero den replaced by 1e-9, a / den, zero where b == 0.  The quotient is formed as in the hardware's own expansion of
-// an IEEE division without its range scaling (v_rcp_f32, one Newton step on the reciprocal, q = a rc, the exact residual
-// r = a - den q by fma, q + r rc): correctly rounded wherever no intermediate leaves the normal range -- |den| >= 1e-16 by
-// construction, relevance values and attention scores are far inside it -- at 8 instead of 17 vector instructions per element.
-// The kernel is bound by vector-instruction issue (phase stamps: profiles/r06_attention_qk_rc_*.log), S is evaluated twice per
-// element, and the six-product sums that consume it are re-associated against the reference anyway.
-__device__ __forceinline__ f32x2 sd2(f32x2 a, f32x2 b) {
-  f32x2 den = b + f32x2{1e-9f, 1e-9f};
-  den[0] = (den[0] == 0.0f) ? 1e-9f : den[0];
-  den[1] = (den[1] == 0.0f) ? 1e-9f : den[1];
-  f32x2 rc = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-  const f32x2 e = __builtin_elementwise_fma(-den, rc, f32x2{1.0f, 1.0f});
-  rc = __builtin_elementwise_fma(e, rc, rc);
-  f32x2 q = a * rc;
-  const f32x2 r = __builtin_elementwise_fma(-den, q, a);
-  q = __builtin_elementwise_fma(r, rc, q);
-  q[0] = (b[0] != 0.0f) ? q[0] : 0.0f;
-  q[1] = (b[1] != 0.0f) ? q[1] : 0.0f;
-  return q;
 }
 
 // One phase of one wave.  SIDE = ROWS: the wave's 32 query rows against every key (A = k^T planes; a lane's S values are 8
@@ -271,8 +203,7 @@ __device__ __forceinline__ void phase(f32x16 (&acc)[2], const unsigned char* __r
         pin((s + 1) % RING);
         make_planes(s + 1, (s + 1) % RING, bn);                       // (of no use when s + 1 == NS: never multiplied)
       }
-      // six partial products per block, smallest first (te_linear_x6.hip): planes (1,1) (0,2) (2,0) (0,1) (1,0) (0,0)
-      constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};
+      // six partial products per block, smallest first (te_x6.h: PA / PB)
 #pragma unroll
       for (int p6 = 0; p6 < 6; ++p6)
 #pragma unroll
@@ -397,7 +328,6 @@ __device__ __forceinline__ void phase_rows(f32x16 (&acc)[2], const unsigned char
         Ba[q] = __builtin_bit_cast(bf16x8, wa);
         Bb[q] = __builtin_bit_cast(bf16x8, wb);
       }
-      constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         bf16x8 a[2][3];

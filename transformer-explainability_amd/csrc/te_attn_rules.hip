@@ -37,30 +37,7 @@
 // LDS images: PADDED row-major tiles (row strides 68 / 260 floats, see below) -- every MFMA fragment address is a per-lane
 // base plus a compile-time offset, and both products read the same row-major tile (the row side as 16-B fragments along a
 // row, the column side as 4-byte fragments down the rows).
-#include "te_common.h"
-
-namespace te_attn_kb {      // te_attn_kb.hip: wave-owned key blocks (round 5) -- the AV rule and the first half of the backward
-bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
-int av_launch(int mode, const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const float* attn, const float* v,
-              int64_t v_sb, int64_t v_sh, int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn,
-              float* cam_attn, float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn, int64_t B, int64_t H, int64_t N,
-              float scale, hipStream_t stream);
-}  // namespace te_attn_kb
-
-namespace te_attn_rc {      // te_attn_rc.hip: row-block and key-block owners (round 6) -- the QK rule / softmax backward, N <= 224
-bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
-int qk_launch(int mode, const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb,
-              int64_t k_sh, int64_t k_sn, const float* Z, float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn, float* cam_k,
-              int64_t ck_sb, int64_t ck_sh, int64_t ck_sn, int64_t B, int64_t H, int64_t N, float scale, const float* r_scale,
-              int64_t r_scale_stride, hipStream_t stream, const float* d_out = nullptr, const float* out = nullptr, int64_t o_sb = 0,
-              int64_t o_sh = 0, int64_t o_sn = 0);
-}  // namespace te_attn_rc
-
-namespace te_attn_fwd6 {      // te_attn_fwd6.hip: row-block owners on bf16 MFMAs (round 6) -- the attention forward, N <= 224
-bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
-int launch(const float* qkv, float* z_qk, float* attn, float* out, int64_t B, int64_t H, int64_t N, float scale, hipStream_t stream,
-           void* out_planes = nullptr, void* out_abs_planes = nullptr);
-}  // namespace te_attn_fwd6
+#include "te_internal.h"
 
 namespace te_attn_rules {
 
@@ -70,34 +47,7 @@ constexpr int TI = 32;         // query rows per tile
 constexpr int kT = 512;        // threads per workgroup
 constexpr int kWaves = kT / 64;
 
-struct Strided {  // [B,H,N,D] view, D contiguous
-  int64_t sb, sh, sn;
-};
-
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
-
-#define TE_MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-#define TE_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
-__device__ __forceinline__ int crow(int e, int kh) { return (e & 3) + 8 * (e >> 2) + 4 * kh; }
-
-__device__ __forceinline__ void zero16(f32x16& a) {
-#pragma unroll
-  for (int e = 0; e < 16; ++e) a[e] = 0.0f;
-}
-
-// guarded 4-wide access at a dword-aligned address: elements [c, c+4) of a row with `cols_valid` valid columns
-__device__ __forceinline__ f32x4 load4(const float* __restrict__ p, int c, int cols_valid) {
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (c + 3 < cols_valid) {
-    v = *reinterpret_cast<const f32x4_u*>(p + c);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (c + e < cols_valid) v[e] = p[c + e];
-  }
-  return v;
-}
+// (te_common.h: Strided, f32x4_u, crow, zero16, load4, TE_MFMA32 / TE_MFMA16)
 
 // The [TI][nj] tile of an [N,N] operand in flight: thread t holds float4 slots idx = t + 512 r (r < 4) of the
 // [TI][NJ32 / 4] float4 grid; (row, c4) per slot are loop-invariant.
@@ -564,8 +514,6 @@ int qk_launch(const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int6
 // ================================================================================================
 // C ABI of the producers
 // ================================================================================================
-using te_attn_rules::Strided;
-
 extern "C" int te_attention_forward_supported(int64_t N, int64_t D) {
   return (D == 64 && N >= 1 && N <= te_attn_rules::NJF) ? 1 : 0;
 }

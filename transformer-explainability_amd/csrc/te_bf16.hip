@@ -2,8 +2,8 @@
 //
 // Semantics (include/te_relprop.h, "bf16 operands"): the reference's rule evaluated in fp32 on the model's own bf16
 // tensors.  A bf16 operand is read exactly (bf16 -> fp32 is exact) and enters an MFMA as ONE bf16 plane; the only fp32
-// operand of a product is S = safe_divide(R, Z), which enters as the exact sum of three bf16 planes (split3, the split of
-// te_linear_x6.hip).  Every bf16 x bf16 product is exact in the fp32 accumulator of v_mfma_f32_16x16x32_bf16, so each
+// operand of a product is S = safe_divide(R, Z), which enters as the exact sum of three bf16 planes (split3_u16, the split
+// of te_x6.h).  Every bf16 x bf16 product is exact in the fp32 accumulator of v_mfma_f32_16x16x32_bf16, so each
 // product of a rule is an fp32-accumulated sum of exact terms.
 //
 //   Linear   Z-pass   Z = [X+ | X-] . [W+ | W-]^T        (X+ / X- split from the bf16 X in registers; all terms >= 0)
@@ -26,10 +26,7 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kThreads = 256;
 constexpr int kBK = 32;
@@ -39,8 +36,10 @@ constexpr int kAttTile = 64;
 
 __device__ __forceinline__ float bf(uint16_t b) { return __uint_as_float((unsigned)b << 16); }
 
-// x = p[0] + p[1] + p[2] exactly (round to nearest even, subtract, repeat): the split of te_linear_x6.hip
-__device__ __forceinline__ void split3(float x, uint16_t (&p)[3]) {
+// x = p[0] + p[1] + p[2] exactly: the split of te_x6.h, one value at a time, planes as stored (16 bits).  Local on purpose: the
+// same bits as te_x6.h's split3, but that one is a view of split3_pk and carries a second (zero) lane through the three
+// rounds, which changes the instructions of the two kernels below (scripts/isa_diff.py); kept so that they stay as measured.
+__device__ __forceinline__ void split3_u16(float x, uint16_t (&p)[3]) {
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
     const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x, 0.0f}, bf16x2));
@@ -141,7 +140,8 @@ __device__ __forceinline__ bf16x8 frag(const uint16_t (*lds)[kLd], int row, int 
   return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u16x8*>(&lds[row][8 * (lane >> 4)]));
 }
 
-#define TE_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
+// (local: the 16x16x32 bf16 MFMA of this GEMM loop; te_common.h's TE_MFMA16 is the fp32 16x16x4 one)
+#define TE_MFMA16_BF16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
 template <int BM, int BN, int AK, int NB, int EPI>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) void gemm_kernel(GemmArgs g) {
@@ -205,8 +205,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
         const bf16x8 xn = __builtin_bit_cast(bf16x8, (u16x8)(x & neg));
 #pragma unroll
         for (int ni = 0; ni < FN; ++ni) {
-          acc[0][mi][ni] = TE_MFMA16(xp, b[0][ni], acc[0][mi][ni]);
-          acc[0][mi][ni] = TE_MFMA16(xn, b[NB - 1][ni], acc[0][mi][ni]);
+          acc[0][mi][ni] = TE_MFMA16_BF16(xp, b[0][ni], acc[0][mi][ni]);
+          acc[0][mi][ni] = TE_MFMA16_BF16(xn, b[NB - 1][ni], acc[0][mi][ni]);
         }
       } else {
         bf16x8 a[NPA];
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
 #pragma unroll
             for (int q = NPA - 1; q >= 0; --q) {
               f32x4& c = acc[PER_PLANE ? q : j][mi][ni];
-              c = TE_MFMA16(a[q], b[j][ni], c);
+              c = TE_MFMA16_BF16(a[q], b[j][ni], c);
             }
       }
     }
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
           float r = g.R[m * g.r_ld + n];
           if (g.rs) r = r * g.rs[(m / g.rps) * g.rs_stride];
           uint16_t p[3];
-          split3(te_sd(r, v), p);
+          split3_u16(te_sd(r, v), p);
           const int64_t o = m * g.N + n, ps = g.M * g.N;
 #pragma unroll
           for (int q = 0; q < 3; ++q) g.planes[q * ps + o] = p[q];
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(64) void s_planes_kernel(const float* __restrict__ 
     if constexpr (sizeof(TZ) == 2) zv = bf(zr[c]);
     else zv = zr[c];
     uint16_t p[3];
-    split3(te_sd(rv, zv), p);
+    split3_u16(te_sd(rv, zv), p);
 #pragma unroll
     for (int q = 0; q < 3; ++q) out[q * total + c] = p[q];
   }

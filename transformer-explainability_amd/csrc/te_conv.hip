@@ -16,7 +16,7 @@
 //           geometry -- no im2col / col2im copies.
 // Rounding: Za differs from the reference's three convolutions by the order of fp32 additions only (all terms of
 // sum_k (x - l) w+ + (x - h) w- are >= 0, so Za is well conditioned).
-#include "te_common.h"
+#include "te_internal.h"
 
 namespace {
 

@@ -12,9 +12,7 @@ namespace {
 
 constexpr int kThreads = 256;
 
-// 16-byte vector access that only promises 4-byte alignment (gfx950 global loads/stores of
-// dwordx4 are legal at dword alignment); used where per-(b,h) bases are odd multiples of 4 B.
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
+// (te_common.h: f32x4_u, the 16-byte access that only promises 4-byte alignment -- used where per-(b,h) bases are odd multiples of 4 B)
 
 template <typename V>
 __device__ __forceinline__ V ld(const float* p) { return *reinterpret_cast<const V*>(p); }

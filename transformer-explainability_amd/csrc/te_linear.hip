@@ -46,7 +46,7 @@
 
 #include <type_traits>
 
-#include "te_common.h"
+#include "te_internal.h"
 
 namespace {
 
@@ -133,8 +133,6 @@ __device__ __forceinline__ float te_neg(float x) {
 }
 
 __device__ __forceinline__ float te_abs(float x) { return __int_as_float(__float_as_int(x) & 0x7fffffff); }
-
-#define TE_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 struct TileCoord {
   int64_t row0, col0;
@@ -274,7 +272,7 @@ __global__ __launch_bounds__(kThreads, 2) void linear_k1_kernel(
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < NI; ++ni) acc[0][mi][ni] = TE_MFMA(f.a[mi][j], f.b[ni][j], acc[0][mi][ni]);
+          for (int ni = 0; ni < NI; ++ni) acc[0][mi][ni] = TE_MFMA32(f.a[mi][j], f.b[ni][j], acc[0][mi][ni]);
       } else {
         float ap[MI], an[MI], bp[NI], bn[NI];
 #pragma unroll
@@ -291,12 +289,12 @@ __global__ __launch_bounds__(kThreads, 2) void linear_k1_kernel(
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < NI; ++ni) acc[0][mi][ni] = TE_MFMA(ap[mi], bp[ni], acc[0][mi][ni]);
+          for (int ni = 0; ni < NI; ++ni) acc[0][mi][ni] = TE_MFMA32(ap[mi], bp[ni], acc[0][mi][ni]);
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
           for (int ni = 0; ni < NI; ++ni)
-            acc[NACC - 1][mi][ni] = TE_MFMA(an[mi], bn[ni], acc[NACC - 1][mi][ni]);
+            acc[NACC - 1][mi][ni] = TE_MFMA32(an[mi], bn[ni], acc[NACC - 1][mi][ni]);
       }
     }
   };
@@ -568,14 +566,14 @@ __global__ __launch_bounds__(kThreads, 2) void linear_k2_kernel(
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < NI; ++ni) acc[0][mi][ni] = TE_MFMA(f.a[mi][j], bp[ni], acc[0][mi][ni]);
+          for (int ni = 0; ni < NI; ++ni) acc[0][mi][ni] = TE_MFMA32(f.a[mi][j], bp[ni], acc[0][mi][ni]);
       }
       if constexpr (BOTH || MODE == 2) {
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
           for (int ni = 0; ni < NI; ++ni)
-            acc[NACC - 1][mi][ni] = TE_MFMA(f.a[mi][j], bn[ni], acc[NACC - 1][mi][ni]);
+            acc[NACC - 1][mi][ni] = TE_MFMA32(f.a[mi][j], bn[ni], acc[NACC - 1][mi][ni]);
       }
     }
   };

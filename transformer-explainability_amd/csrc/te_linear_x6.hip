@@ -50,15 +50,11 @@
 #include <cmath>
 #include <type_traits>
 
-#include "te_common.h"
+#include "te_x6.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kFrag = 1024;                   // one plane fragment: 32 rows x 16 k bf16 as [kh][r][8]
+// (te_x6.h: TE_MFMA_BF16, kFrag = one plane fragment, the split -- split3_pk, split3 --, sd2, swap_halves, PA / PB)
 constexpr int kRB = 3 * kFrag;                // one 32-row block, one K16 step
 constexpr int kMinFrag = 4;                   // a cut closer than this many K-steps to a tile boundary snaps onto it
 constexpr float kCancelTol = 0.0078125f;      // as te_linear.hip
@@ -73,47 +69,7 @@ constexpr int kErrWord = 1023;                 // flags[0 .. 767] = hand-over fl
 // sign of X, out (+)= scale (X+- . acc).
 enum { MODE_Z = 0, MODE_C = 1, MODE_G = 2, MODE_ZI = 3, MODE_Z1 = 4, MODE_CI = 5, MODE_X = 6 };
 
-#define TE_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float bf16_f32(unsigned b) { return __uint_as_float(b << 16); }
-// x = p[0] + p[1] + p[2] exactly: round to nearest even (v_cvt_pk_bf16_f32), subtract (the residual of a round-to-nearest
-// bf16 is representable in fp32), repeat.  Pairs: p[q] = the packed bf16 pair (x0 low half, x1 high half) of plane q.
-__device__ __forceinline__ void split3_pk(float x0, float x1, unsigned (&p)[3]) {
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
-    p[q] = u;
-    x0 = x0 - __uint_as_float(u << 16);
-    x1 = x1 - __uint_as_float(u & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ void split3(float x, unsigned (&p)[3]) {
-  unsigned pk[3];
-  split3_pk(x, 0.0f, pk);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) p[q] = pk[q] & 0xffffu;
-}
-
-// safe_divide (te_common.h: te_sd) of two element pairs on packed fp32 instructions, as in te_attn_rc.hip: den = b + 1e-9 (one
-// rounding), an exact-zero den replaced by 1e-9, a / den, zero where b == 0.  The quotient is the hardware's own expansion of an IEEE
-// division without its range scaling (v_rcp_f32, one Newton step on the reciprocal, q = a rc, the exact residual r = a - den q by
-// fma, q + r rc): correctly rounded wherever no intermediate leaves the normal range -- |den| >= 1e-16 by construction.
-__device__ __forceinline__ f32x2 sd2(f32x2 a, f32x2 b) {
-  f32x2 den = b + f32x2{1e-9f, 1e-9f};
-  den[0] = (den[0] == 0.0f) ? 1e-9f : den[0];
-  den[1] = (den[1] == 0.0f) ? 1e-9f : den[1];
-  f32x2 rc = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-  const f32x2 e = __builtin_elementwise_fma(-den, rc, f32x2{1.0f, 1.0f});
-  rc = __builtin_elementwise_fma(e, rc, rc);
-  f32x2 q = a * rc;
-  const f32x2 r = __builtin_elementwise_fma(-den, q, a);
-  q = __builtin_elementwise_fma(r, rc, q);
-  q[0] = (b[0] != 0.0f) ? q[0] : 0.0f;
-  q[1] = (b[1] != 0.0f) ? q[1] : 0.0f;
-  return q;
-}
 
 enum { OP_ABS = 0, OP_POS = 1, OP_NEG = 2, OP_ID = 3 };
 template <int OP>
@@ -365,14 +321,6 @@ __device__ __forceinline__ void glds16(const unsigned char* src, unsigned char* 
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-__device__ __forceinline__ void swap_halves(unsigned& lo_keep, unsigned& hi_keep) {
-  // after the call: lanes 0-31 hold {own lo_keep, partner's lo_keep}; lanes 32-63 hold {partner's hi_keep, own hi_keep}
-  // (v_permlane32_swap: lanes 32-63 of the first operand <-> lanes 0-31 of the second)
-  const u32x2 r = __builtin_amdgcn_permlane32_swap(lo_keep, hi_keep, false, false);
-  lo_keep = r[0];
-  hi_keep = r[1];
-}
-
 // ------------------------------------------------------------------------------------------------
 // Two LDS stages: stage ks + 1 lands while ks is multiplied (a third stage, prefetch distance 2, ran the C-pass 7 % slower:
 // DESIGN.md 3.1b item 1, profiles/r04_x6_variants.log).
@@ -583,7 +531,6 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
       // 3-5 reuse what is resident), three to six at a time between the MFMAs, and each MFMA waits for exactly its own
       // operands.  After the barrier all eight waves read at once and the LDS delivers one 1 KiB fragment per 8 clocks:
       // waiting for a whole round (6 fragments x 8 waves) before the first MFMA idled the pipe for ~13 % of the step.
-      constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};
       // The reads are inline asm with hand-counted waits (guide 5.7): hipcc waits lgkmcnt(0) before the first MFMA once a
       // direct-to-LDS load is in flight.  lgkmcnt counts LDS returns in order: with I reads issued, fragment n (0-based)
       // is present once at most I - 1 - n are outstanding.  (Waits the compiler adds for its own LDS operations can only

@@ -20,7 +20,6 @@
 
 namespace {
 
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
 constexpr int kThreads = 256;
 constexpr int kRowsPerBlock = kThreads / 64;
 constexpr int kMaxChunks = 8;      // float4 per lane: C <= 64 * 4 * 8 = 2048

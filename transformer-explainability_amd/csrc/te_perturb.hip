@@ -175,10 +175,6 @@ __global__ __launch_bounds__(256) void perturb_apply_kernel(const float* __restr
 // per channel and step) and walks the steps itself: the image and the relevance row are read once, not once per step, and
 // the S stores of a wave go to S streams of 1 KiB each.  blockIdx.z selects a group of `spg` steps (the host takes one
 // group when the batch alone fills the chip, one step per group otherwise).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ uint32_t te_pack_bf16(float a, float b) {       // a in the low half
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
 }

@@ -19,11 +19,7 @@
 // and accumulates r[k] * row into per-lane registers; the four waves are folded through LDS in a fixed order and
 // the slab's partial vector goes to the workspace, which the NEXT step folds (again in slab order) into its r.
 // Slab size and fold order depend on N only, so a batch equals its samples run one by one, bit for bit.
-#include "te_common.h"
-
-namespace te_attn_mfma {
-int rollout_bmm_launch(const float* A, const float* Bm, float* C, int64_t B, int64_t N, hipStream_t stream);
-}
+#include "te_internal.h"
 
 namespace {
 
