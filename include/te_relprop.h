@@ -472,6 +472,32 @@ int te_gelu_backward_f32(const float* dy, const float* x, float* dx, int64_t n, 
 int te_heatmap_f32(const float* maps, float* heat, float* fg_mask, int64_t B, int64_t g, int64_t scale,
                    int normalise, te_stream_t stream);
 
+/* ---- segmentation test of a relevance map ---------------------------------------------
+ * replaces, per image, the metrics of baselines/ViT/imagenet_seg_eval.py:219-232,263-273 = utils/metrices.py:26-38
+ * (F1), :81-99 (average precision), :135-178 (pixel accuracy, intersection / union), in ONE launch with no host
+ * synchronisation (a HIP graph captures it).  heat fp32 [B,H,W], fg_mask fp32 [B,H,W] of 0.0 / 1.0 (te_heatmap_f32's
+ * outputs as they are), labels int64 [B,H,W], all contiguous.
+ *   counts [B,6] = correct, labeled, inter0, inter1, union0, union1: a pixel is valid iff label >= 0; correct =
+ *                  #(valid and mask == label); inter_c = #(valid and mask == c and label == c); union_c = #(valid and
+ *                  mask == c) + #(label == c) - inter_c.  Labels >= 2 are valid and belong to neither class.
+ *   f1 [B,H]     = the F1 of every image ROW (the script hands a 2-D mask to get_f1_scores, whose batch loop then runs
+ *                  over the rows): 2 tp / (2 tp + fp + fn) with prediction mask == 1 and target label == 1 (a label of -1
+ *                  is not-target); 0 for a row with 2 tp + fp + fn = 0.
+ *   ap [B]       = sklearn.average_precision_score over the 2*H*W class scores: class 1 scores h, class 0 scores the
+ *                  fp32 value 1 - h, truth is clamp(label, 0) == c; thresholds are the DISTINCT scores in descending
+ *                  order, AP = sum_i (R_i - R_{i-1}) P_i with P_i = tp_i / n_i, R_i = tp_i / npos in fp64; 0 when no pixel is
+ *                  valid or npos = 0.
+ * NaN rule: a NaN heat value counts as 0 and its mask value as 0 (the clean-up of :227-230 / foreground_split).
+ * Ignore rule: pixels with label < 0 drop out of counts and of both classes of AP; F1 sees them as not-target.
+ * The integers are exact; the fp64 sum of AP is taken in an order fixed by the image alone, without floating-point
+ * atomics: every output of image b is the same 64-bit pattern alone or in any batch, wherever the workspace lies.
+ * Refused on the host before any HIP call: null pointers / non-positive sizes TE_ERR_INVALID_ARG; H*W > 2^20 or
+ * B > 65535 TE_ERR_UNSUPPORTED; a workspace smaller than te_seg_metrics_workspace_bytes TE_ERR_WORKSPACE (the query
+ * gives 0 for sizes the entry point refuses).  ws: 8-byte aligned. */
+size_t te_seg_metrics_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int te_seg_metrics_f32(const float* heat, const float* fg_mask, const int64_t* labels, int64_t* counts, double* ap,
+                       double* f1, int64_t B, int64_t H, int64_t W, void* ws, size_t ws_bytes, te_stream_t stream);
+
 /* ---- Conv2d.relprop, z^B rule of the patch embedding (method="full") ------------------
  * replaces modules/layers_ours.py:242-256 (= modules/layers_lrp.py:223-237), the `X.shape[1] == 3` branch, for a
  * convolution with stride == kernel == p and no padding (baselines/ViT/ViT_LRP.py:215-242, PatchEmbed):

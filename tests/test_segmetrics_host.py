@@ -1,0 +1,127 @@
+"""Host-side checks of the device segmentation test (no GPU needed): te_seg_metrics_workspace_bytes / te_seg_metrics_f32 are
+declared, exported and bound, their limits answer before any device call, ops.seg_metrics refuses what has no kernel with a
+TeError, the evaluator's torch path still reproduces the reference on CPU tensors, and te_key is defined once, in a header."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "transformer-explainability_amd", "csrc")
+NEW_SYMBOLS = ["te_seg_metrics_workspace_bytes", "te_seg_metrics_f32"]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__
+    __graft_entry__.build()
+    from transformer_explainability_amd import _lib
+    return _lib.load()
+
+
+def _header_args(name):
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "te_relprop.h")).read(), flags=re.S)
+    m = re.search(r"\b" + name + r"\s*\(([^)]*)\)", header)
+    assert m, name
+    return len([a for a in m.group(1).split(",") if a.strip()])
+
+
+def test_entry_points_declared_exported_bound(lib):
+    from transformer_explainability_amd import _lib
+    for name in NEW_SYMBOLS:
+        assert name in _lib.SIGNATURES, name
+        assert hasattr(lib, name), name
+        assert len(_lib.SIGNATURES[name][1]) == _header_args(name), name
+    assert _header_args("te_seg_metrics_f32") == 12 and _header_args("te_seg_metrics_workspace_bytes") == 3
+
+
+def test_header_comment_states_the_semantics():
+    header = open(os.path.join(ROOT, "include", "te_relprop.h")).read()
+    block = header[header.index("segmentation test of a relevance map"):header.index("int te_seg_metrics_f32")]
+    for cite in ("imagenet_seg_eval.py:219-232,263-273", "26-38", "81-99", "135-178", "NaN rule", "Ignore rule"):
+        assert cite in block, cite
+
+
+def test_workspace_query(lib):
+    q = lib.te_seg_metrics_workspace_bytes
+    for bad in ((0, 224, 224), (-1, 224, 224), (4, 0, 224), (4, 224, 0), (4, -3, 224), (4, 224, -3)):
+        assert q(*bad) == 0, bad
+    sizes = [q(B, 224, 224) for B in (1, 2, 8, 64, 65535)]
+    assert sizes[0] > 0 and all(a < b for a, b in zip(sizes, sizes[1:]))
+    assert q(3, 30, 34) > 0 and q(1, 1, 1) > 0 and q(1, 1024, 1024) > 0
+
+
+def test_entry_point_validates_on_the_host(lib):
+    """Every refusal below comes before any HIP call (the pointers are never dereferenced; this host has no device)."""
+    f = lib.te_seg_metrics_f32
+    p = ctypes.c_void_p(256)
+    B, H, W = 2, 8, 8
+    ws = lib.te_seg_metrics_workspace_bytes(B, H, W)
+    assert ws > 0
+    ok = [p, p, p, p, p, p, B, H, W, p, ws, None]
+    for i in range(6):                                   # a null tensor pointer
+        args = list(ok)
+        args[i] = None
+        assert f(*args) == -1, i
+    for i in (6, 7, 8):                                  # non-positive sizes
+        for v in (0, -1):
+            args = list(ok)
+            args[i] = v
+            assert f(*args) == -1, (i, v)
+    big = 1 << 40
+    assert f(p, p, p, p, p, p, 1, (1 << 20) + 1, 1, p, big, None) == -3           # H*W = 2^20 + 1
+    assert f(p, p, p, p, p, p, 1, 1, (1 << 20) + 1, p, big, None) == -3
+    assert f(p, p, p, p, p, p, 1, 1025, 1024, p, big, None) == -3
+    assert f(p, p, p, p, p, p, 1, 1 << 40, 1 << 40, p, big, None) == -3           # no overflow of H*W
+    assert f(p, p, p, p, p, p, 65536, H, W, p, big, None) == -3                   # B = 65536
+    assert f(p, p, p, p, p, p, B, H, W, p, ws - 1, None) == -2                    # short workspace
+    assert f(p, p, p, p, p, p, B, H, W, p, 0, None) == -2
+    assert f(p, p, p, p, p, p, B, H, W, None, ws, None) == -2
+
+
+def test_ops_seg_metrics_refuses_cpu_and_fp64():
+    from transformer_explainability_amd import ops, TeError
+    heat, mask, labels = torch.rand(2, 8, 8), torch.zeros(2, 8, 8), torch.zeros(2, 8, 8, dtype=torch.long)
+    with pytest.raises(TeError, match="CPU"):
+        ops.seg_metrics(heat, mask, labels)
+    with pytest.raises(TeError, match="float32"):
+        ops.seg_metrics(heat.double(), mask, labels)
+    with pytest.raises(TeError, match="float32"):
+        ops.seg_metrics(heat, mask.double(), labels)
+    with pytest.raises(TeError, match="integer labels"):
+        ops.seg_metrics(heat, mask, labels.float())
+
+
+def test_evaluator_cpu_path_still_reproduces_the_reference():
+    """CPU tensors keep the torch functions: the reference's own results for test_segmentation.inputs()."""
+    from test_segmentation import inputs
+    from transformer_explainability_amd import segmentation as sg
+    g = load_golden("seg_metrics.npz")
+    heat, mask, labels = inputs()
+    ev = sg.SegmentationEvaluator(explain=None)
+    correct, labeled, inter, union, ap, f1 = ev.update_from_heat(heat, mask, labels)
+    assert torch.equal(correct, g["correct"].long()) and torch.equal(labeled, g["labeled"].long())
+    assert torch.equal(inter, g["inter"].long()) and torch.equal(union, g["union"].long())
+    assert float((ap - g["ap"]).abs().max()) < 1e-12 and float((f1 - g["f1"]).abs().max()) < 1e-12
+    assert ap.dtype == torch.float64 and f1.shape == (3, 32) and inter.shape == (3, 2)
+    s = ev.summary()
+    assert abs(s["mAP"] - float(g["ap"].mean())) < 1e-12 and abs(s["mF1"] - float(g["f1"].mean())) < 1e-12
+    assert ev.total_correct == int(g["correct"].sum()) and np.array_equal(ev.total_union, g["union"].sum(0).numpy())
+
+
+def test_te_key_has_one_definition_in_a_header():
+    found = []
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith((".hip", ".h")):
+            text = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, name)).read())
+            n = len(re.findall(r"__forceinline__\s+[\w:]+\s+te_key\s*\(", text))
+            if n:
+                found.append((name, n))
+    assert found == [("te_common.h", 1)], found
+    for user in ("te_perturb.hip", "te_segmetrics.hip"):
+        assert re.search(r"\bte_key\s*\(", open(os.path.join(CSRC, user)).read()), user

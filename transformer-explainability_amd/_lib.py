@@ -113,6 +113,8 @@ SIGNATURES = {
     "te_index_select_relprop_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _P]),
     "te_gradcam_headmean_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _P]),
     "te_heatmap_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, _P]),
+    "te_seg_metrics_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "te_seg_metrics_f32": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
     "te_conv2d_zb_relprop_workspace_bytes": (_SZ, [_I64] * 6),
     "te_conv2d_zb_relprop_f32": (_I, [_P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P, _SZ,
                                       _P]),

@@ -102,6 +102,14 @@ __device__ __forceinline__ float te_sd(float a, float b) {
   return q * ((b != 0.0f) ? 1.0f : 0.0f);
 }
 
+// order-preserving key of the radix select (te_perturb.hip) and the radix sort (te_segmetrics.hip):
+// a > b (as floats, -0 == +0, NaN largest as in torch.topk) <=> key(a) > key(b)
+__device__ __forceinline__ uint32_t te_key(float v) {
+  uint32_t u = __float_as_uint(v);
+  if (u == 0x80000000u) u = 0;                       // -0 -> +0
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 __device__ __forceinline__ double te_wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, TE_WAVE);

@@ -28,13 +28,6 @@ struct Norm {
   float mean[TE_PERTURB_MAX_CHANNELS], std[TE_PERTURB_MAX_CHANNELS];
 };
 
-// order-preserving key: a > b (as floats, -0 == +0, NaN largest as in torch.topk) <=> key(a) > key(b)
-__device__ __forceinline__ uint32_t te_key(float v) {
-  uint32_t u = __float_as_uint(v);
-  if (u == 0x80000000u) u = 0;                       // -0 -> +0
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // sel[b][s] = {threshold key, cut}: pixel i of sample b is removed at step s iff
 //   key_i > thr  ||  (key_i == thr && i < cut)
 __global__ __launch_bounds__(kSelThreads) void perturb_select_kernel(const float* __restrict__ vis,

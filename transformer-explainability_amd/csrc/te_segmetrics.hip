@@ -1,0 +1,282 @@
+// te_segmetrics.hip -- the segmentation test of a relevance map on the device (gfx950), SURVEY.md section 8(f) row 2:
+// pixel accuracy, intersection / union, average precision and the per-row F1 of baselines/ViT/imagenet_seg_eval.py:219-232,
+// 263-273 with utils/metrices.py:26-38, 81-99, 135-178, per image, from the heat map, the foreground mask and the labels.
+//
+// One workgroup of 16 waves per image (a batch is B independent images, so every output of an image is the same bits in
+// any batch), one launch, no host involvement:
+//   1. build : a wave per image row reads heat / mask / labels once: the six counts, the row's F1, and the 2*H*W sort
+//              elements (te_key(score) << 1 | truth) -- class 0 scores the fp32 value 1 - h, class 1 scores h.  A pixel with
+//              label < 0 gets key 0, which no cleaned score has: it sorts behind every real score and is never scanned.
+//   2. sort  : LSD radix sort of the elements, 4 passes of 8 bits over the key, ping-pong in the workspace (L2).  Every wave
+//              owns a contiguous segment of the source; a (digit, wave) table in LDS, scanned digit-major, gives each wave
+//              its destination per digit, and inside a 64-element step the lanes of one digit are ranked by ballots -- so
+//              every pass is stable.  The table of the next pass is counted while this pass scatters (integer LDS atomics:
+//              the counts do not depend on the order of arrival).
+//   3. scan  : over the sorted scores in descending order, the runs of equal keys: (tp_i, n_i) at the end of every run,
+//              compacted into the idle half of the workspace -- integers only.
+//   4. sum   : AP = sum_i (R_i - R_{i-1}) P_i in fp64, P_i = tp_i / n_i, R_i = tp_i / npos: thread t adds the runs t, t + 1024,
+//              ... in that order, then a fixed tree -- an order that depends on the image alone.
+#include "te_common.h"
+
+namespace {
+
+constexpr int kThreads = 1024;
+constexpr int kWaves = kThreads / TE_WAVE;
+constexpr int kDigits = 256;
+constexpr int64_t kMaxPixels = (int64_t)1 << 20;
+constexpr int64_t kMaxBatch = 65535;
+
+// the lanes of the wave that hold the same 8-bit digit as this lane, among the `live` ones
+__device__ __forceinline__ uint64_t match_digit(uint32_t digit, bool live) {
+  uint64_t m = __ballot(live);
+#pragma unroll
+  for (int bit = 0; bit < 8; ++bit) {
+    const bool one = (digit >> bit) & 1u;
+    const uint64_t b = __ballot(live && one);
+    m &= one ? b : ~b;
+  }
+  return m;
+}
+
+// exclusive prefix of v over the block's threads; wtot: kWaves words of LDS
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wtot) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t incl = v;
+#pragma unroll
+  for (int off = 1; off < TE_WAVE; off <<= 1) {
+    const uint32_t n = __shfl_up(incl, off, TE_WAVE);
+    if (lane >= off) incl += n;
+  }
+  if (lane == TE_WAVE - 1) wtot[wave] = incl;
+  __syncthreads();
+  uint32_t before = 0;
+  for (int w = 0; w < wave; ++w) before += wtot[w];
+  __syncthreads();
+  return before + incl - v;
+}
+
+__global__ __launch_bounds__(kThreads) void seg_metrics_kernel(const float* __restrict__ heat,
+                                                               const float* __restrict__ mask,
+                                                               const int64_t* __restrict__ labels,
+                                                               int64_t* __restrict__ counts, double* __restrict__ ap,
+                                                               double* __restrict__ f1, int H, int W, uint64_t* ws) {
+  __shared__ uint32_t cnt[2][kDigits * kWaves];      // [digit][wave]: elements of a digit in a wave's source segment
+  __shared__ uint32_t wtot[kWaves], wend[kWaves];
+  __shared__ uint32_t tally[8];
+  __shared__ double red[kWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b = blockIdx.x;
+  const uint32_t N = (uint32_t)H * (uint32_t)W, T2 = 2 * N;
+  const uint32_t S = (T2 + kThreads - 1) / kThreads * TE_WAVE;      // elements per wave segment, a multiple of 64
+  const uint64_t below = (1ull << lane) - 1;
+  uint64_t* src = ws + (size_t)b * 2 * T2;
+  uint64_t* dst = src + T2;
+  const float* hb = heat + b * N;
+  const float* mb = mask + b * N;
+  const int64_t* lb = labels + b * N;
+
+  for (int i = tid; i < 2 * kDigits * kWaves; i += kThreads) (&cnt[0][0])[i] = 0;
+  if (tid < 8) tally[tid] = 0;
+  __syncthreads();
+
+  // ---- 1. build
+  uint32_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // correct, labeled, inter 0/1, predicted 0/1, labelled 0/1
+  for (int r = wave; r < H; r += kWaves) {
+    uint32_t tp = 0, fp = 0, fn = 0;
+    for (int c0 = 0; c0 < W; c0 += TE_WAVE) {
+      const int c = c0 + lane;
+      const bool live = c < W;
+      const uint32_t p = (uint32_t)r * (uint32_t)W + (uint32_t)c;
+      float h = 0.0f, mf = 0.0f;
+      int64_t lab = -1;
+      if (live) {
+        h = hb[p];
+        mf = mb[p];
+        lab = lb[p];
+      }
+      if (h != h) {                                // foreground_split's clean-up: NaN heat -> 0, its mask -> 0
+        h = 0.0f;
+        mf = 0.0f;
+      }
+      const int64_t mi = (int64_t)mf;
+      const bool valid = live && lab >= 0;
+      const int64_t pred = valid ? mi + 1 : 0, tgt = lab + 1;
+      const int64_t inter = (pred == tgt) ? pred : 0;
+      acc[0] += (valid && mi == lab) ? 1u : 0u;
+      acc[1] += valid ? 1u : 0u;
+      acc[2] += (inter == 1) ? 1u : 0u;
+      acc[3] += (inter == 2) ? 1u : 0u;
+      acc[4] += (pred == 1) ? 1u : 0u;
+      acc[5] += (pred == 2) ? 1u : 0u;
+      acc[6] += (tgt == 1) ? 1u : 0u;
+      acc[7] += (tgt == 2) ? 1u : 0u;
+      const bool P = live && mi == 1, T = live && lab == 1;
+      tp += (uint32_t)__popcll(__ballot(P && T));
+      fp += (uint32_t)__popcll(__ballot(P && !T));
+      fn += (uint32_t)__popcll(__ballot(live && !P && T));
+      if (live) {
+        const uint64_t e0 = valid ? (((uint64_t)te_key(1.0f - h) << 1) | (lab == 0 ? 1u : 0u)) : 0ull;
+        const uint64_t e1 = valid ? (((uint64_t)te_key(h) << 1) | (lab == 1 ? 1u : 0u)) : 0ull;
+        src[p] = e0;
+        src[N + p] = e1;
+        atomicAdd(&cnt[0][((uint32_t)(e0 >> 1) & 0xffu) * kWaves + p / S], 1u);
+        atomicAdd(&cnt[0][((uint32_t)(e1 >> 1) & 0xffu) * kWaves + (N + p) / S], 1u);
+      }
+    }
+    if (lane == 0) {
+      const uint32_t den = 2 * tp + fp + fn;
+      f1[b * H + r] = den > 0 ? (double)(2 * tp) / (double)den : 0.0;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    uint32_t v = acc[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, TE_WAVE);
+    if (lane == 0) atomicAdd(&tally[k], v);
+  }
+  __syncthreads();
+  if (tid < 6) {
+    const uint32_t v = tid < 4 ? tally[tid] : tally[tid] + tally[tid + 2] - tally[tid - 2];   // union = pred + lab - inter
+    counts[b * 6 + tid] = (int64_t)v;
+  }
+  const uint32_t M = 2 * tally[1];                 // scores that take part in AP
+
+  // ---- 2. sort (ascending; the ignored pixels' key 0 comes first)
+  for (int pass = 0; pass < 4; ++pass) {
+    volatile uint32_t* cur = cnt[pass & 1];
+    uint32_t* nxt = cnt[(pass + 1) & 1];
+    const int shift = 1 + 8 * pass;
+    {                                              // (digit, wave) counts -> start of each wave's elements of each digit
+      uint32_t v[4], sum = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        v[k] = cur[4 * tid + k];
+        sum += v[k];
+      }
+      uint32_t off = block_exclusive_scan(sum, wtot);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        cur[4 * tid + k] = off;
+        off += v[k];
+      }
+      for (int k = 0; k < 4; ++k) nxt[4 * tid + k] = 0;
+    }
+    __syncthreads();
+    const uint32_t seg0 = (uint32_t)wave * S, seg1 = min(seg0 + S, T2);
+    uint32_t idx = seg0 + lane;
+    uint64_t e_next = idx < seg1 ? src[idx] : 0ull;
+    for (uint32_t base = seg0; base < seg1; base += TE_WAVE) {
+      const uint64_t e = e_next;
+      const bool live = idx < seg1;
+      idx += TE_WAVE;
+      e_next = idx < seg1 ? src[idx] : 0ull;
+      const uint32_t digit = (uint32_t)(e >> shift) & 0xffu;
+      const uint64_t m = match_digit(digit, live);
+      const uint32_t rank = (uint32_t)__popcll(m & below), same = (uint32_t)__popcll(m);
+      if (live) {
+        const uint32_t at = cur[digit * kWaves + wave];
+        const uint32_t pos = at + rank;
+        dst[pos] = e;
+        if (rank == same - 1) cur[digit * kWaves + wave] = at + same;      // after every lane of the digit has read it
+        if (pass < 3) atomicAdd(&nxt[((uint32_t)(e >> (shift + 8)) & 0xffu) * kWaves + pos / S], 1u);
+      }
+    }
+    __syncthreads();
+    uint64_t* t = src;
+    src = dst;
+    dst = t;
+  }
+
+  // ---- 3. runs of equal scores, descending: element j is src[T2 - 1 - j], j < M
+  const uint32_t seg0 = (uint32_t)wave * S, seg1 = min(seg0 + S, M);
+  {
+    uint32_t nt = 0, ne = 0;
+    for (uint32_t base = seg0; base < seg1; base += TE_WAVE) {
+      const uint32_t j = base + lane;
+      const bool live = j < seg1;
+      bool t = false, end = false;
+      if (live) {
+        const uint64_t e = src[T2 - 1 - j];
+        t = e & 1u;
+        end = (j + 1 == M) || ((src[T2 - 2 - j] >> 1) != (e >> 1));
+      }
+      nt += (uint32_t)__popcll(__ballot(t));
+      ne += (uint32_t)__popcll(__ballot(end));
+    }
+    if (lane == 0) {
+      wtot[wave] = nt;
+      wend[wave] = ne;
+    }
+  }
+  __syncthreads();
+  uint32_t tp_before = 0, runs_before = 0, npos = 0, nruns = 0;
+  for (int w = 0; w < kWaves; ++w) {
+    if (w < wave) {
+      tp_before += wtot[w];
+      runs_before += wend[w];
+    }
+    npos += wtot[w];
+    nruns += wend[w];
+  }
+  for (uint32_t base = seg0; base < seg1; base += TE_WAVE) {
+    const uint32_t j = base + lane;
+    const bool live = j < seg1;
+    bool t = false, end = false;
+    if (live) {
+      const uint64_t e = src[T2 - 1 - j];
+      t = e & 1u;
+      end = (j + 1 == M) || ((src[T2 - 2 - j] >> 1) != (e >> 1));
+    }
+    const uint64_t tb = __ballot(t), eb = __ballot(end);
+    if (end) {
+      const uint32_t tp = tp_before + (uint32_t)__popcll(tb & (below | (1ull << lane)));
+      dst[runs_before + (uint32_t)__popcll(eb & below)] = (uint64_t)tp | ((uint64_t)(j + 1) << 32);
+    }
+    tp_before += (uint32_t)__popcll(tb);
+    runs_before += (uint32_t)__popcll(eb);
+  }
+  __syncthreads();
+
+  // ---- 4. AP (utils/metrices.py:81-99 = sklearn.average_precision_score): 0 when nothing is labelled or nothing is positive
+  double sum = 0.0;
+  if (npos > 0) {
+    const double dpos = (double)npos;
+    for (uint32_t k = tid; k < nruns; k += kThreads) {
+      const uint64_t rk = dst[k];
+      const uint32_t tp = (uint32_t)rk, n = (uint32_t)(rk >> 32);
+      const uint32_t tp_prev = k ? (uint32_t)dst[k - 1] : 0u;
+      const double precision = (double)tp / (double)n, recall = (double)tp / dpos, prev = (double)tp_prev / dpos;
+      sum += (recall - prev) * precision;
+    }
+  }
+  sum = te_wave_sum(sum);
+  if (lane == 0) red[wave] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    double tot = 0.0;
+    for (int w = 0; w < kWaves; ++w) tot += red[w];
+    ap[b] = tot;
+  }
+}
+
+}  // namespace
+
+extern "C" size_t te_seg_metrics_workspace_bytes(int64_t B, int64_t H, int64_t W) {
+  if (B <= 0 || H <= 0 || W <= 0 || B > kMaxBatch || H > kMaxPixels || W > kMaxPixels || H * W > kMaxPixels) return 0;
+  // two buffers of 2*H*W 8-byte sort elements per image
+  return te_align_up((size_t)B * 2 * 2 * (size_t)(H * W) * sizeof(uint64_t), 256);
+}
+
+extern "C" int te_seg_metrics_f32(const float* heat, const float* fg_mask, const int64_t* labels, int64_t* counts,
+                                  double* ap, double* f1, int64_t B, int64_t H, int64_t W, void* ws, size_t ws_bytes,
+                                  te_stream_t stream) {
+  if (!heat || !fg_mask || !labels || !counts || !ap || !f1 || B <= 0 || H <= 0 || W <= 0) return TE_ERR_INVALID_ARG;
+  if (B > kMaxBatch || H > kMaxPixels || W > kMaxPixels || H * W > kMaxPixels) return TE_ERR_UNSUPPORTED;
+  if (!ws || ws_bytes < te_seg_metrics_workspace_bytes(B, H, W)) return TE_ERR_WORKSPACE;
+  if (((uintptr_t)ws) & 7u) return TE_ERR_INVALID_ARG;
+  seg_metrics_kernel<<<dim3((unsigned)B), dim3(kThreads), 0, (hipStream_t)stream>>>(heat, fg_mask, labels, counts, ap, f1,
+                                                                                   (int)H, (int)W, (uint64_t*)ws);
+  TE_RETURN_IF_LAUNCH_FAILED();
+  return TE_OK;
+}

@@ -1223,6 +1223,41 @@ def heatmap(maps: Tensor, scale: int = 16, normalise: bool = True, with_mask: bo
     return (heat, mask) if with_mask else heat
 
 
+def seg_metrics_packed(heat: Tensor, mask: Tensor, labels: Tensor):
+    """``seg_metrics`` and the flat int64 buffer its results are views of -- counts [B*6], then the bits of ap [B], then
+    the bits of f1 [B*H]: one device-to-host copy of it brings all three over."""
+    if heat.dtype != torch.float32 or mask.dtype != torch.float32:
+        raise _lib.TeError(f"seg_metrics takes a float32 heat map and a float32 0/1 mask, got {heat.dtype} / {mask.dtype}")
+    if labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+        raise _lib.TeError(f"seg_metrics takes integer labels, got {labels.dtype}")
+    if not (heat.is_cuda and mask.is_cuda and labels.is_cuda):
+        raise _lib.TeError("seg_metrics needs tensors on the MI355X (got a CPU tensor); there is no CPU fallback")
+    if heat.dim() != 3 or mask.shape != heat.shape or labels.shape != heat.shape:
+        raise _lib.TeError(f"seg_metrics: heat, mask and labels must be [B,H,W] alike, got {tuple(heat.shape)}, "
+                           f"{tuple(mask.shape)}, {tuple(labels.shape)}")
+    heat, mask = _c(heat), _c(mask)
+    labels = labels.to(torch.int64).contiguous()
+    B, H, W = heat.shape
+    flat = torch.empty((B * (7 + H),), dtype=torch.int64, device=heat.device)
+    counts = flat[:6 * B].view(B, 6)
+    ap = flat[6 * B:7 * B].view(torch.float64)
+    f1 = flat[7 * B:].view(torch.float64).view(B, H)
+    with _on_device(heat) as lib:
+        ws = _ws(lib.te_seg_metrics_workspace_bytes(B, H, W), heat)
+        _lib.check(lib.te_seg_metrics_f32(_ptr(heat), _ptr(mask), _ptr(labels), _ptr(counts), _ptr(ap), _ptr(f1), B, H, W,
+                                          _ptr(ws), ws.numel(), _stream(heat)), "te_seg_metrics_f32")
+    return counts, ap, f1, flat
+
+
+def seg_metrics(heat: Tensor, mask: Tensor, labels: Tensor):
+    """The segmentation test of imagenet_seg_eval.py:219-232,263-273 per image, one launch, no synchronisation: heat
+    [B,H,W] fp32, mask [B,H,W] fp32 0/1 (ops.heatmap's outputs as they are: NaN heat counts as 0 with mask 0), labels
+    [B,H,W] of an integer dtype (< 0 = ignore) -> (counts int64 [B,6] = correct, labeled, inter0, inter1, union0, union1;
+    ap float64 [B]; f1 float64 [B,H] = the F1 of every image row), as segmentation.pixel_accuracy / intersection_union /
+    average_precision / row_f1 define them."""
+    return seg_metrics_packed(heat, mask, labels)[:3]
+
+
 # ---------------------------------------------------------------------------------------- 8f.4 perturbation inputs
 def perturb(vis: Tensor, data: Tensor, ks: Sequence[int], mean: Optional[Sequence[float]] = None,
             std: Optional[Sequence[float]] = None, out_dtype: torch.dtype = torch.float32) -> Tensor:

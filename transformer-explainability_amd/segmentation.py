@@ -3,8 +3,10 @@ of baselines/ViT/imagenet_seg_eval.py:170-311 with the metrics of utils/metrices
 intersection / union :154-178, average precision :81-99, F1 :26-38), without the dataset / saver / image dumps.
 
 The map -> (heat, foreground mask) step (:214-222: bilinear x16, min-max, mean threshold) is the te_heatmap_f32 kernel;
-the metrics are a handful of reductions and one sort over 2*H*W scores per image, evaluated on the device for the
-whole batch (the reference does them one image at a time in numpy / scikit-learn after a device-to-host copy each).
+the metrics are a handful of reductions and one sort over 2*H*W scores per image (the reference does them one image at a
+time in numpy / scikit-learn after a device-to-host copy each).  On the MI355X they are the te_seg_metrics_f32 kernel
+(ops.seg_metrics: one launch per batch, a workgroup per image, and ONE device-to-host copy for the running totals); the
+torch functions below are the CPU path and the restatement the kernel is tested against.
 
 Semantics kept from the reference, including its quirks:
   * a batch is B independent images (the script runs with batch_size = 1, :31);
@@ -100,10 +102,26 @@ class SegmentationEvaluator:
 
     def update(self, image, labels):
         maps = self.explain(image).detach()
-        heat, mask = foreground_split(maps.reshape(maps.shape[0], -1), self.scale)
+        maps = maps.reshape(maps.shape[0], -1)
+        if maps.is_cuda:                         # the NaN clean-up of foreground_split is inside te_seg_metrics_f32
+            heat, mask = ops.heatmap(maps, scale=self.scale, normalise=True, with_mask=True)
+            return self.update_from_heat(heat[:, 0], mask[:, 0], labels)
+        heat, mask = foreground_split(maps, self.scale)
         return self.update_from_heat(heat, mask, labels)
 
     def update_from_heat(self, heat, mask, labels):
+        if heat.is_cuda:
+            counts, ap, f1, flat = ops.seg_metrics_packed(heat.float(), mask.float(), labels)
+            B = counts.shape[0]
+            host = flat.cpu().numpy()            # the one device-to-host copy of this update
+            c = host[:6 * B].reshape(B, 6).sum(0)
+            self.total_correct += int(c[0])
+            self.total_label += int(c[1])
+            self.total_inter += c[2:4]
+            self.total_union += c[4:6]
+            self.total_ap += [float(v) for v in host[6 * B:7 * B].view(np.float64)]
+            self.total_f1 += [r for r in host[7 * B:].view(np.float64).reshape(B, -1)]
+            return counts[:, 0], counts[:, 1], counts[:, 2:4], counts[:, 4:6], ap, f1
         correct, labeled = pixel_accuracy(mask, labels)
         inter, union = intersection_union(mask, labels)
         ap, f1 = average_precision(heat, labels), row_f1(mask, labels)
