@@ -498,6 +498,64 @@ size_t te_seg_metrics_workspace_bytes(int64_t B, int64_t H, int64_t W);
 int te_seg_metrics_f32(const float* heat, const float* fg_mask, const int64_t* labels, int64_t* counts, double* ap,
                        double* f1, int64_t B, int64_t H, int64_t W, void* ws, size_t ws_bytes, te_stream_t stream);
 
+/* ---- rationale test of a BERT relevance vector (ERASER Movie Reviews) ---------------------
+ * replaces, per document, the rationale production of BERT_rationale_benchmark/models/pipeline/bert_pipeline.py:547-582
+ * (clamp(min=0) :552, scores_per_word_from_scores_per_token :96-138, sixteen topk calls :567-569) and the per-document
+ * part of BERT_rationale_benchmark/metrics.py:168-215 (hard rationales) and :217-253 (soft scores), in ONE launch with
+ * no host synchronisation (a HIP graph captures it).  scores fp32 [B,N] relevance per wordpiece; word_ids int32 [B,N]:
+ * the word a wordpiece belongs to, -1 for [CLS] / [SEP] / [UNK] / [PAD] and for everything beyond the scored words (ids
+ * >= Wmax are ignored as well); truth uint8 [B,Wmax]: the human rationale, nonzero = rationale word; ks: HOST array of
+ * n_ks <= TE_RATIONALE_MAX_KS positive rationale sizes.  flags: TE_RATIONALE_CLAMP clamps the scores at 0 first (:552).
+ *   word_scores [B,Wmax] fp32 = the maximum over the word's wordpieces (:109-124); a word without a wordpiece, and every
+ *                  entry at or past n_words, is 0.
+ *   n_words [B]  int32 = highest word id + 1.
+ *   order [B,Wmax] int32 = the word indices by descending score, ties in ASCENDING WORD INDEX (torch.topk leaves ties
+ *                  unspecified, and after the clamp every non-positive word ties at 0: the rule of te_perturb_f32); -1 at
+ *                  and past n_words.
+ *   counts [B,n_ks,2] int32 = (tp_k, pred_k): pred_k = min(k, n_words) (the reference's topk raises for k > n_words; this
+ *                  library clips), tp_k = the rationale words among the first pred_k of order.
+ *   soft [B,4]   fp64 = average precision, AUPRC, ROC-AUC, npos of the word scores against truth over the n_words words
+ *                  (sklearn.average_precision_score, auc(precision_recall_curve), roc_auc_score): with (tp_i, n_i) at
+ *                  the end of the i-th run of equal scores in descending order, P_i = tp_i / n_i, R_i = tp_i / npos,
+ *                  F_i = (n_i - tp_i) / nneg, P_0 = 1, R_0 = F_0 = 0:  AP = sum (R_i - R_{i-1}) P_i,
+ *                  AUPRC = sum (R_i - R_{i-1}) (P_i + P_{i-1}) / 2,  ROC-AUC = sum (F_i - F_{i-1}) (R_i + R_{i-1}) / 2.
+ *                  A document of one class (npos = 0 or npos = n_words) gets 0 for all three; npos tells the caller to
+ *                  discard it, as _score_aggregator(..., True) does.
+ * NaN rule: a NaN score counts as 0 (sklearn raises on NaN; the explanation path never produces one).
+ * Integers and the word maximum are exact; the fp64 sums run in an order fixed by the document alone, without
+ * floating-point atomics: every output of document b is the same bit pattern alone or in any batch.
+ * Refused on the host before any HIP call: null pointers, non-positive sizes, n_ks outside 1..16, a non-positive k or
+ * unknown flag bits TE_ERR_INVALID_ARG; N or Wmax > 2048 or B > 65535 TE_ERR_UNSUPPORTED; a workspace smaller than
+ * te_rationale_metrics_workspace_bytes TE_ERR_WORKSPACE (the query gives 0 for sizes the entry point refuses).
+ * ws: 8-byte aligned. */
+#define TE_RATIONALE_MAX_KS 16
+#define TE_RATIONALE_CLAMP 1
+size_t te_rationale_metrics_workspace_bytes(int64_t B, int64_t N, int64_t Wmax);
+int te_rationale_metrics_f32(const float* scores, const int32_t* word_ids, const uint8_t* truth, float* word_scores,
+                             int32_t* n_words, int32_t* order, int32_t* counts, double* soft, int64_t B, int64_t N,
+                             int64_t Wmax, const int64_t* ks, int64_t n_ks, int flags, void* ws, size_t ws_bytes,
+                             te_stream_t stream);
+
+/* ---- erased inputs of ERASER's faithfulness numbers ----------------------------------------------------
+ * builds, in ONE launch, every erased copy of a batch that comprehensiveness and sufficiency (metrics.py:255-282,
+ * 301-313) need.  THE REFERENCE TREE HAS NO PRODUCER FOR THESE, only the consumer: what follows is this project's
+ * definition.  input_ids / attention_mask int64 [B,N]; word_ids int32 [B,N], order int32 [B,Wmax] and n_words int32 [B]
+ * as te_rationale_metrics_f32 takes / gives them; fractions: HOST array of n_t <= TE_TOKEN_ERASE_MAX_FRACTIONS values
+ * in (0, 1] (metrics.py:610 defaults to 0.01, 0.05, 0.1, 0.2, 0.5).  For fraction t the rationale of document b is the
+ * first m = min(n_words, max(1, ceil(t * n_words))) entries of order (the product and ceil in IEEE fp64, i.e. the value
+ * the host computes; 0 for a document without words) -> n_rationale int32 [n_t,B].
+ *   ids_out / mask_out int64 [2,n_t,B,N]: copy [0][t] (comprehensiveness) drops every wordpiece of a rationale word,
+ *   copy [1][t] (sufficiency) keeps only those.  Tokens with word id -1 and mask 1 ([CLS], [SEP], [UNK]) are kept in
+ *   both; tokens with mask 0 are dropped.  The kept tokens are compacted to the left in their original order with
+ *   mask 1; the rest is pad_id with mask 0.
+ * Refused on the host before any HIP call: null pointers, non-positive sizes, n_t outside 1..8, a fraction outside
+ * (0, 1] TE_ERR_INVALID_ARG; N or Wmax > 2048 or B > 65535 TE_ERR_UNSUPPORTED. */
+#define TE_TOKEN_ERASE_MAX_FRACTIONS 8
+int te_token_erase(const int64_t* input_ids, const int64_t* attention_mask, const int32_t* word_ids,
+                   const int32_t* order, const int32_t* n_words, int64_t* ids_out, int64_t* mask_out,
+                   int32_t* n_rationale, int64_t B, int64_t N, int64_t Wmax, const double* fractions, int64_t n_t,
+                   int64_t pad_id, te_stream_t stream);
+
 /* ---- Conv2d.relprop, z^B rule of the patch embedding (method="full") ------------------
  * replaces modules/layers_ours.py:242-256 (= modules/layers_lrp.py:223-237), the `X.shape[1] == 3` branch, for a
  * convolution with stride == kernel == p and no padding (baselines/ViT/ViT_LRP.py:215-242, PatchEmbed):

@@ -27,6 +27,9 @@ TE_ROLLOUT_CLS_FIXUP = 2
 TE_ROLLOUT_ROW0 = 4
 TE_HEADMEAN_CLAMP = 1
 TE_HEADMEAN_ROW0 = 2
+TE_RATIONALE_CLAMP = 1
+TE_RATIONALE_MAX_KS = 16
+TE_TOKEN_ERASE_MAX_FRACTIONS = 8
 
 _P, _I64, _F, _I, _SZ = c_void_p, c_int64, c_float, c_int, c_size_t
 
@@ -115,6 +118,9 @@ SIGNATURES = {
     "te_heatmap_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, _P]),
     "te_seg_metrics_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "te_seg_metrics_f32": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
+    "te_rationale_metrics_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "te_rationale_metrics_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _I64, _I, _P, _SZ, _P]),
+    "te_token_erase": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _I64, _I64, _P]),
     "te_conv2d_zb_relprop_workspace_bytes": (_SZ, [_I64] * 6),
     "te_conv2d_zb_relprop_f32": (_I, [_P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P, _SZ,
                                       _P]),

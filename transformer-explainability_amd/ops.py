@@ -13,8 +13,8 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import (TE_HEADMEAN_CLAMP, TE_HEADMEAN_ROW0, TE_IMPL_SIMPLE, TE_ROLLOUT_CLS_FIXUP, TE_ROLLOUT_NORMALISE,
-                   TE_ROLLOUT_ROW0, TE_VARIANT_LRP, TE_VARIANT_OURS)
+from ._lib import (TE_HEADMEAN_CLAMP, TE_HEADMEAN_ROW0, TE_IMPL_SIMPLE, TE_RATIONALE_CLAMP, TE_ROLLOUT_CLS_FIXUP,
+                   TE_ROLLOUT_NORMALISE, TE_ROLLOUT_ROW0, TE_VARIANT_LRP, TE_VARIANT_OURS)
 
 Tensor = torch.Tensor
 _VARIANTS = {"ours": TE_VARIANT_OURS, "lrp": TE_VARIANT_LRP}
@@ -1256,6 +1256,97 @@ def seg_metrics(heat: Tensor, mask: Tensor, labels: Tensor):
     ap float64 [B]; f1 float64 [B,H] = the F1 of every image row), as segmentation.pixel_accuracy / intersection_union /
     average_precision / row_f1 define them."""
     return seg_metrics_packed(heat, mask, labels)[:3]
+
+
+# ---------------------------------------------------------------------------------------- 8f rationale test (BERT)
+def _is_integer(t: Tensor) -> bool:
+    return not (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool)
+
+
+class _on_device_of_ids(_on_device):
+    """``_on_device`` for a call whose tensors are all integers (te_token_erase): no dtype rule to apply."""
+
+    def __init__(self, t: Tensor):
+        global _checked_device
+        if not _checked_device:
+            _lib.require_device()
+            _checked_device = True
+        self.ctx = torch.cuda.device(t.device)
+
+
+def rationale_metrics(scores: Tensor, word_ids: Tensor, truth: Tensor, ks: Sequence[int], clamp: bool = True):
+    """The rationale test of bert_pipeline.py:547-582 + metrics.py:168-253 per document, one launch, no synchronisation:
+    scores [B,N] fp32 relevance per wordpiece, word_ids [B,N] of an integer dtype (the word of a wordpiece, -1 = none),
+    truth [B,Wmax] bool / uint8 (the human rationale per word), ks: at most 16 positive rationale sizes ->
+    (word_scores fp32 [B,Wmax], n_words int32 [B], order int32 [B,Wmax], counts int32 [B,len(ks),2] = (tp_k, pred_k),
+    soft fp64 [B,4] = AP, AUPRC, ROC-AUC, npos), as rationale.word_scores / topk_counts / soft_scores define them:
+    ties in ascending word index, pred_k = min(k, n_words), NaN scores count as 0."""
+    import ctypes
+    if scores.dtype != torch.float32:
+        raise _lib.TeError(f"rationale_metrics takes float32 scores, got {scores.dtype}")
+    if not _is_integer(word_ids):
+        raise _lib.TeError(f"rationale_metrics takes integer word ids, got {word_ids.dtype}")
+    if truth.dtype not in (torch.bool, torch.uint8):
+        raise _lib.TeError(f"rationale_metrics takes a bool or uint8 truth mask, got {truth.dtype}")
+    if not (scores.is_cuda and word_ids.is_cuda and truth.is_cuda):
+        raise _lib.TeError("rationale_metrics needs tensors on the MI355X (got a CPU tensor); there is no CPU fallback")
+    if scores.dim() != 2 or word_ids.shape != scores.shape or truth.dim() != 2 or truth.shape[0] != scores.shape[0]:
+        raise _lib.TeError(f"rationale_metrics: scores and word_ids must be [B,N] alike and truth [B,Wmax], got "
+                           f"{tuple(scores.shape)}, {tuple(word_ids.shape)}, {tuple(truth.shape)}")
+    ks = [int(k) for k in ks]
+    scores = _c(scores)
+    word_ids = word_ids.to(torch.int32).contiguous()
+    truth = truth.contiguous().view(torch.uint8)
+    (B, N), Wmax, K = scores.shape, truth.shape[1], len(ks)
+    dev = scores.device
+    word_scores = torch.empty((B, Wmax), dtype=torch.float32, device=dev)
+    n_words = torch.empty((B,), dtype=torch.int32, device=dev)
+    order = torch.empty((B, Wmax), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, K, 2), dtype=torch.int32, device=dev)
+    soft = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    k_arr = (ctypes.c_int64 * max(K, 1))(*ks)
+    with _on_device(scores) as lib:
+        ws = _ws(lib.te_rationale_metrics_workspace_bytes(B, N, Wmax), scores)
+        _lib.check(lib.te_rationale_metrics_f32(_ptr(scores), _ptr(word_ids), _ptr(truth), _ptr(word_scores),
+                                                _ptr(n_words), _ptr(order), _ptr(counts), _ptr(soft), B, N, Wmax, k_arr,
+                                                K, TE_RATIONALE_CLAMP if clamp else 0, _ptr(ws), ws.numel(),
+                                                _stream(scores)), "te_rationale_metrics_f32")
+    return word_scores, n_words, order, counts, soft
+
+
+def token_erase(input_ids: Tensor, attention_mask: Tensor, word_ids: Tensor, order: Tensor, n_words: Tensor,
+                fractions: Sequence[float], pad_id: int = 0):
+    """Every erased copy ERASER's faithfulness numbers need, in one launch: input_ids / attention_mask [B,N] of an integer
+    dtype, word_ids [B,N], order [B,Wmax] and n_words [B] as ``rationale_metrics`` takes / gives them, fractions: at most 8
+    values in (0, 1] -> (ids_out int64 [2,T,B,N], mask_out int64 [2,T,B,N], n_rationale int32 [T,B]).  For fraction t the
+    first min(n_words, max(1, ceil(t n_words))) words of ``order`` form the rationale; copy [0] (comprehensiveness) drops
+    their wordpieces, copy [1] (sufficiency) keeps only those; tokens with word id -1 and mask 1 stay in both; the kept
+    tokens move to the left in their order, the rest is ``pad_id`` with mask 0 (rationale.token_erase_torch)."""
+    import ctypes
+    tensors = (input_ids, attention_mask, word_ids, order, n_words)
+    for name, t in zip(("input_ids", "attention_mask", "word_ids", "order", "n_words"), tensors):
+        if not (_is_integer(t) or (name == "attention_mask" and t.dtype == torch.bool)):
+            raise _lib.TeError(f"token_erase takes integer tensors, got {t.dtype} for {name}")
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.TeError("token_erase needs tensors on the MI355X (got a CPU tensor); there is no CPU fallback")
+    if (input_ids.dim() != 2 or attention_mask.shape != input_ids.shape or word_ids.shape != input_ids.shape
+            or order.dim() != 2 or order.shape[0] != input_ids.shape[0] or tuple(n_words.shape) != (input_ids.shape[0],)):
+        raise _lib.TeError(f"token_erase: input_ids, attention_mask and word_ids must be [B,N] alike, order [B,Wmax] and "
+                           f"n_words [B], got {[tuple(t.shape) for t in tensors]}")
+    fr = [float(t) for t in fractions]
+    input_ids = input_ids.to(torch.int64).contiguous()
+    attention_mask = attention_mask.to(torch.int64).contiguous()
+    word_ids, order, n_words = (t.to(torch.int32).contiguous() for t in (word_ids, order, n_words))
+    (B, N), Wmax, T = input_ids.shape, order.shape[1], len(fr)
+    ids_out = torch.empty((2, T, B, N), dtype=torch.int64, device=input_ids.device)
+    mask_out = torch.empty_like(ids_out)
+    n_rationale = torch.empty((T, B), dtype=torch.int32, device=input_ids.device)
+    f_arr = (ctypes.c_double * max(T, 1))(*fr)
+    with _on_device_of_ids(input_ids) as lib:
+        _lib.check(lib.te_token_erase(_ptr(input_ids), _ptr(attention_mask), _ptr(word_ids), _ptr(order), _ptr(n_words),
+                                      _ptr(ids_out), _ptr(mask_out), _ptr(n_rationale), B, N, Wmax, f_arr, T, int(pad_id),
+                                      _stream(input_ids)), "te_token_erase")
+    return ids_out, mask_out, n_rationale
 
 
 # ---------------------------------------------------------------------------------------- 8f.4 perturbation inputs
