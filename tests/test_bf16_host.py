@@ -69,3 +69,53 @@ def test_one_hot_seed_is_fp32_for_bf16_logits():
     assert oh.dtype == torch.float32
     assert torch.equal(oh, torch.tensor([[0.0, 1.0, 0.0], [1.0, 0.0, 0.0]]))
     assert _one_hot(logits.float(), None).dtype == torch.float32
+
+
+# ------------------------------------------------------------------------------------------------ fair inputs
+def _fp32_oracle_share(fn32, fn64, tol):
+    """max |fp32 oracle - fp64 oracle| / max |fp64 oracle| per output, which must stay within tol / 4."""
+    import bf16_rule_inputs as I
+    out32, out64 = fn32(), fn64()
+    if torch.is_tensor(out32):
+        out32, out64 = (out32,), (out64,)
+    worst = max(I.rel_to_max(a, b) for a, b in zip(out32, out64))
+    assert worst <= tol / 4, (worst, tol)
+    return worst
+
+
+def test_rule_test_inputs_leave_the_tolerance_to_the_kernels():
+    """The inputs of test_gpu_bf16_rules.py (zeros, -0.0, exact cancellation, seeds, shapes) must not eat the tolerance
+    those tests grant the kernels against the fp64 oracle: the plain fp32 oracle on the same inputs stays within a quarter
+    of it, for every Add, Clone and head-mean input the device tests build.  (The second-trip head-mean case is compared
+    with the fp32 oracle itself on the device, so it has no share to check.)"""
+    import bf16_rule_inputs as I
+    from oracle import relprop_oracle as O
+    worst = {"add": 0.0, "clone": 0.0, "headmean": 0.0}
+    add_cases = sorted({(shape, shared) for shape, _ in I.ADD_CASES for shared in (False, True)})
+    for shape, shared in add_cases + [(I.ADD_MODEL_SHAPE, False)]:
+        R, X0, X1 = I.add_inputs(shape, shared)
+        assert X0.dtype == X1.dtype == torch.bfloat16 and R.dtype == torch.float32
+        z = X0.float() + X1.float()
+        frac = float(((z == 0) & (X0.float() != 0)).float().mean())
+        assert 0.01 < frac < 0.12 or z.numel() < 100, (shape, shared, frac)      # cancellation is really there
+        w = _fp32_oracle_share(lambda: O.add_relprop(R, X0.float(), X1.float()),
+                               lambda: O.add_relprop(R.double(), X0.double(), X1.double()), I.ADD_TOL)
+        worst["add"] = max(worst["add"], w)
+    for shape, _ in I.CLONE_CASES:
+        for num in (2, 3):
+            Rs, X = I.clone_inputs(shape, num)
+            fac = I.clone_factors(shape[0])
+            variants = [Rs]
+            for pos in I.clone_deferred_positions(num):          # the materialised operands of the scaled form
+                variants.append([r * fac[:, I.clone_factor_column(j, pos)].view(-1, 1, 1) if j in pos else r
+                                 for j, r in enumerate(Rs)])
+            for rs in variants:
+                w = _fp32_oracle_share(lambda: O.clone_relprop(rs, X.float()),
+                                       lambda: O.clone_relprop([r.double() for r in rs], X.double()), I.CLONE_TOL)
+                worst["clone"] = max(worst["clone"], w)
+    for B, H, N, _ in I.HEADMEAN_CASES:
+        g, c = I.headmean_inputs(B, H, N)
+        w = _fp32_oracle_share(lambda: O.gradcam_headmean(g.float(), c),
+                               lambda: O.gradcam_headmean(g.double(), c.double()), I.HEADMEAN_TOL)
+        worst["headmean"] = max(worst["headmean"], w)
+    print("fp32 oracle vs fp64 oracle, relative to the tensor maximum:", worst)
