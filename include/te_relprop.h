@@ -698,6 +698,25 @@ int te_attention_backward_strided_bf16(const te_bf16_t* d_out, int64_t do_sb, in
                                        te_bf16_t* d_v, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
                                        int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk,
                                        void* ws, size_t ws_bytes, te_stream_t stream);
+/* Conv2d.relprop, z^B rule, of a bf16 patch embedding (method="full" on a bf16 ViT; csrc/te_conv_bf16.hip): the rule of
+ * te_conv2d_zb_relprop_f32 evaluated in fp32 on the bf16 X [B,C,H,W] and W [E,C,p,p], fp32 R (token-major [B,P,E],
+ * samples r_bs >= P*E floats apart, any 4-byte alignment: cam[:, 1:] is consumed in place) and fp32 out [B,C,H,W].
+ *   Za = conv(X,W) - l_b sum_k W+[e,k] - h_b sum_k W-[e,k] + 1e-9 ; S = R / Za ; out = X convT(S,W) - l_b convT(S,W+) - h_b convT(S,W-)
+ * conv(X,W) is RECOMPUTED from the bf16 operands on bf16 MFMAs with fp32 accumulation (every product exact): the layer's
+ * cached bf16 output and its bias are not arguments.  S enters the second product as three bf16 planes (its exact split).
+ * w_planes = te_conv2d_zb_bf16_prepare_weights of W: W+^T, W-^T [K = C p p][E] and the two channel sums (fp64-accumulated),
+ * te_conv2d_zb_bf16_weight_planes_bytes bytes, built once per weight version.  X, W, w_planes and ws 16-byte aligned
+ * (TE_ERR_INVALID_ARG / TE_ERR_WORKSPACE otherwise).  Shapes: te_conv2d_zb_relprop_bf16_supported -- C == 3, E and K = 3 p p
+ * multiples of 128 (p a multiple of 16) -- with H % p == W % p == 0; TE_ERR_UNSUPPORTED otherwise (callers then run
+ * te_conv2d_zb_relprop_f32 on exact fp32 copies with Y = their fp32 convolution).  Fixed k-order: a batch equals its samples. */
+int te_conv2d_zb_relprop_bf16_supported(int64_t C, int64_t E, int64_t p);
+size_t te_conv2d_zb_relprop_bf16_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int64_t E, int64_t p);
+size_t te_conv2d_zb_bf16_weight_planes_bytes(int64_t C, int64_t E, int64_t p);
+int te_conv2d_zb_bf16_prepare_weights(const te_bf16_t* W, int64_t C, int64_t E, int64_t p, void* planes,
+                                      size_t planes_bytes, te_stream_t stream);
+int te_conv2d_zb_relprop_bf16(const float* R, int64_t r_bs, const te_bf16_t* X, const te_bf16_t* W, const void* w_planes,
+                              float* out, int64_t B, int64_t C, int64_t H, int64_t W_, int64_t E, int64_t p, void* ws,
+                              size_t ws_bytes, te_stream_t stream);
 
 #ifdef __cplusplus
 }

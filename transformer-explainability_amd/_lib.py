@@ -17,7 +17,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TE_RELPROP_LIB") or os.path.join(_PKG, "lib", "libte_relprop.so")
 
 TE_OK = 0
-MIN_LIB_VERSION = 600      # te_version(): 0.6.0, the round-6 ABI (te_build_id)
+MIN_LIB_VERSION = 601      # te_version(): 0.6.1, te_conv2d_zb_relprop_bf16 (0.6.0: te_build_id)
 TE_ERR_UNSUPPORTED = -3
 TE_VARIANT_OURS = 0
 TE_VARIANT_LRP = 1
@@ -152,6 +152,12 @@ SIGNATURES = {
     "te_gradcam_headmean_bf16": (_I, [_P, _P, _P, _I64, _I64, _I64, _P]),
     "te_attn_headmean_bf16": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I, _P]),
     "te_perturb_bf16": (_I, [_P, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _SZ, _P]),
+    # the z^B rule of a bf16 patch embedding (csrc/te_conv_bf16.hip)
+    "te_conv2d_zb_relprop_bf16_supported": (_I, [_I64, _I64, _I64]),
+    "te_conv2d_zb_relprop_bf16_workspace_bytes": (_SZ, [_I64] * 6),
+    "te_conv2d_zb_bf16_weight_planes_bytes": (_SZ, [_I64, _I64, _I64]),
+    "te_conv2d_zb_bf16_prepare_weights": (_I, [_P, _I64, _I64, _I64, _P, _SZ, _P]),
+    "te_conv2d_zb_relprop_bf16": (_I, [_P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P]),
     # bf16 attention producers (csrc/te_attn_bf16.hip): the argument lists of the _strided_f32 entry points
     "te_attention_bf16_supported": (_I, [_I64, _I64]),
     "te_attention_backward_strided_bf16_workspace_bytes": (_SZ, [_I64, _I64, _I64]),

@@ -22,19 +22,12 @@
 // grid and of the number of rows: a batch equals its samples bit for bit.
 #include <cstring>
 
-#include "te_common.h"
+#include "te_bf16_tile.h"
 
 namespace {
 
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kThreads = 256;
-constexpr int kBK = 32;
-constexpr int kLd = kBK + 8;          // LDS row pitch in bf16 elements (80 B: 16-byte aligned rows)
 constexpr int kLinTile = 128;         // Linear tiles (and the multiple in_f / out_f must have)
 constexpr int kAttTile = 64;
-
-__device__ __forceinline__ float bf(uint16_t b) { return __uint_as_float((unsigned)b << 16); }
 
 // x = p[0] + p[1] + p[2] exactly: the split of te_x6.h, one value at a time, planes as stored (16 bits).  Local on purpose: the
 // same bits as te_x6.h's split3, but that one is a view of split3_pk and carries a second (zero) lane through the three
@@ -135,13 +128,6 @@ __device__ __forceinline__ void store(const Stage<BR>& st, int64_t sr, int64_t s
     }
   }
 }
-
-__device__ __forceinline__ bf16x8 frag(const uint16_t (*lds)[kLd], int row, int lane) {
-  return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u16x8*>(&lds[row][8 * (lane >> 4)]));
-}
-
-// (local: the 16x16x32 bf16 MFMA of this GEMM loop; te_common.h's TE_MFMA16 is the fp32 16x16x4 one)
-#define TE_MFMA16_BF16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
 template <int BM, int BN, int AK, int NB, int EPI>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) void gemm_kernel(GemmArgs g) {

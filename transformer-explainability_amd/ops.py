@@ -1176,16 +1176,22 @@ def rollout(cams: Tensor, start_layer: int = 0, normalise: bool = False, cls_fix
 
 
 # ---------------------------------------------------------------------------------------- 8f.3 Conv2d z^B
-def conv2d_zb_relprop(R: Tensor, X: Tensor, W: Tensor, Y: Tensor, bias: Optional[Tensor] = None) -> Tensor:
+def conv2d_zb_relprop(R: Tensor, X: Tensor, W: Tensor, Y: Optional[Tensor], bias: Optional[Tensor] = None,
+                      cache: Optional[dict] = None) -> Tensor:
     """Conv2d.relprop, z^B rule (layers_ours.py:242-256), for a stride == kernel, padding 0 convolution (the ViT patch
     embedding).  R [B,E,Hp,Wp] with any strides (the token-major view PatchEmbed.relprop builds is consumed in
-    place), X [B,C,H,W], W [E,C,p,p], Y = the layer's forward output [B,E,Hp,Wp] -> relevance [B,C,H,W]."""
+    place), X [B,C,H,W], W [E,C,p,p], Y = the layer's forward output [B,E,Hp,Wp] -> relevance [B,C,H,W].
+    bf16 X / W (a bf16 model): conv2d_zb_relprop_bf16, which reads neither Y nor the bias; `cache` keeps its weight planes."""
+    if _is_bf16(X) or _is_bf16(W):
+        return conv2d_zb_relprop_bf16(R, X, W, cache=cache)
     B, C, H, Wd = X.shape
     E, p = W.shape[0], W.shape[2]
     if W.shape[1] != C or W.shape[3] != p or H % p or Wd % p:
         raise _lib.TeError(f"conv2d_zb_relprop: not a patch convolution: X {tuple(X.shape)}, W {tuple(W.shape)}")
     Hp, Wp = H // p, Wd // p
     P = Hp * Wp
+    if Y is None:
+        raise _lib.TeError("conv2d_zb_relprop: float32 X / W need Y, the layer's forward output (only bfloat16 operands do without)")
     if tuple(R.shape) != (B, E, Hp, Wp) or tuple(Y.shape) != (B, E, Hp, Wp):
         raise _lib.TeError(f"conv2d_zb_relprop: R {tuple(R.shape)} / Y {tuple(Y.shape)} do not match [B,E,H/p,W/p]")
     Rt = R.permute(0, 2, 3, 1)                       # [B,Hp,Wp,E]
@@ -1394,6 +1400,12 @@ def attention_bf16_route(N: int, D: int) -> str:
     return "bf16" if _lib.load().te_matmul_relprop_bf16_supported(int(N), int(D)) else "fp32-upcast"
 
 
+def conv_bf16_route(C: int, E: int, p: int) -> str:
+    """'bf16' (te_conv2d_zb_relprop_bf16: 3 channels, E and 3 p p multiples of 128) or 'fp32-upcast'
+    (te_conv2d_zb_relprop_f32 on fp32 copies of X and W, with their fp32 convolution as Y)."""
+    return "bf16" if _lib.load().te_conv2d_zb_relprop_bf16_supported(int(C), int(E), int(p)) else "fp32-upcast"
+
+
 def bf16_weight_planes(W: Tensor, cache: Optional[dict] = None) -> Tensor:
     """W+, W- and their transposes for te_linear_relprop_bf16, built once per weight version (cached like
     x6_weight_planes: keyed on the weight's identity, dropped by x6_invalidate / load_state_dict / .to())."""
@@ -1582,3 +1594,65 @@ def add_relprop_bf16(R: Tensor, X0: Tensor, X1: Tensor, variant="ours", deferred
         _lib.check(lib.te_add_relprop_bf16(_ptr(R), _ptr(X0), _ptr(X1), _ptr(out0), _ptr(out1), B, n, x1_bs,
                                            _variant(variant), _ptr(ws), ws.numel(), _stream(X0)), "te_add_relprop_bf16")
     return out0, out1
+
+
+def conv_bf16_weight_planes(W: Tensor, cache: Optional[dict] = None) -> Tuple[Tensor, Tensor]:
+    """(the contiguous 16-byte aligned W [E,C,p,p], its planes: W+^T, W-^T and the two channel sums) for
+    te_conv2d_zb_relprop_bf16, built once per weight version (cached like bf16_weight_planes: keyed on the weight's identity,
+    dropped by x6_invalidate / load_state_dict / .to())."""
+    E, C, p, _ = W.shape
+    key = _weight_key(W)
+    if cache is not None:
+        hit = cache.get("conv_bf16_planes")
+        if hit is not None and hit[0] == key:
+            return hit[1], hit[2]
+    Wc = _c16(W.detach())
+    if Wc.data_ptr() % 16:
+        Wc = Wc.clone()
+    with _on_device(Wc) as lib:
+        planes = _ws(lib.te_conv2d_zb_bf16_weight_planes_bytes(C, E, p), Wc)
+        _lib.check(lib.te_conv2d_zb_bf16_prepare_weights(_ptr(Wc), C, E, p, _ptr(planes), planes.numel(), _stream(Wc)),
+                   "te_conv2d_zb_bf16_prepare_weights")
+    if cache is not None:
+        cache["conv_bf16_planes"] = (key, Wc, planes)
+    return Wc, planes
+
+
+def conv2d_zb_relprop_bf16(R: Tensor, X: Tensor, W: Tensor, cache: Optional[dict] = None) -> Tensor:
+    """The z^B rule of a bf16 patch embedding: R [B,E,Hp,Wp] fp32 (any strides; the token-major view of cam[:, 1:] is read
+    in place), X [B,C,H,W] and W [E,C,p,p] bf16 -> fp32 [B,C,H,W].  conv(X, W) is recomputed from the bf16 operands -- on
+    bf16 MFMAs (csrc/te_conv_bf16.hip), or, for a geometry that kernel does not tile (conv_bf16_route), as the fp32
+    convolution of exact fp32 copies handed to the fp32 kernel; the layer's bf16 output is never the denominator."""
+    for t in (X, W):                                     # mixed dtypes, bf16 relevance, then CPU tensors, are refused
+        if not _is_bf16(t):
+            raise _lib.TeError(f"{DTYPES_MSG}; this bf16 rule got a {t.dtype} operand")
+    _prep(R), _prep_bf16(X), _prep_bf16(W)
+    B, C, H, Wd = X.shape
+    E, p = W.shape[0], W.shape[2]
+    if W.shape[1] != C or W.shape[3] != p or H % p or Wd % p:
+        raise _lib.TeError(f"conv2d_zb_relprop: not a patch convolution: X {tuple(X.shape)}, W {tuple(W.shape)}")
+    Hp, Wp = H // p, Wd // p
+    P = Hp * Wp
+    if tuple(R.shape) != (B, E, Hp, Wp):
+        raise _lib.TeError(f"conv2d_zb_relprop: R {tuple(R.shape)} does not match [B,E,H/p,W/p]")
+    if conv_bf16_route(C, E, p) != "bf16":
+        Xf, Wf = X.float(), W.detach().float()
+        return conv2d_zb_relprop(R, Xf, Wf, torch.nn.functional.conv2d(Xf, Wf, stride=p))
+    Rt = R.permute(0, 2, 3, 1)                       # [B,Hp,Wp,E]
+    st = Rt.stride()
+    if not (st[3] == 1 and st[2] == E and st[1] == Wp * E and st[0] >= P * E):
+        Rt = Rt.contiguous()
+        st = Rt.stride()
+    X = _c16(X)
+    if X.data_ptr() % 16:
+        X = X.clone()
+    Wc, planes = conv_bf16_weight_planes(W, cache)
+    out = torch.empty(X.shape, dtype=torch.float32, device=X.device)
+    T, K = B * P, C * p * p
+    # flops = the bf16 MFMA work executed (one product in the Z-pass, six in the C-pass); bytes = algorithmic traffic
+    with _on_device(X) as lib, _timed("conv2d_zb_bf16", 14.0 * T * K * E,
+                                      4.0 * T * K + 6.0 * K * E + 4.0 * T * E + 12.0 * T * E + 4.0 * T * K):
+        ws = _ws(lib.te_conv2d_zb_relprop_bf16_workspace_bytes(B, C, H, Wd, E, p), X)
+        _lib.check(lib.te_conv2d_zb_relprop_bf16(_ptr(Rt), st[0], _ptr(X), _ptr(Wc), _ptr(planes), _ptr(out), B, C, H, Wd,
+                                                 E, p, _ptr(ws), ws.numel(), _stream(X)), "te_conv2d_zb_relprop_bf16")
+    return out

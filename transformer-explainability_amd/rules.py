@@ -142,8 +142,8 @@ def x6_cache(module) -> dict:
     return c
 
 
-class Linear(nn.Linear, RelProp):
-    """layers_ours.py:207-230 / layers_lrp.py:188-211 -> te_linear_relprop_f32."""
+class _ScratchCache:
+    """Mixin of the layers that keep derived weight planes (Linear, Conv2d)."""
 
     # The derived operand planes (x6_cache) are device scratch, not state: they are rebuilt on demand, so they are kept out of
     # pickling / deepcopy / torch.save(model), and dropped whenever the parameters are replaced wholesale.
@@ -159,6 +159,10 @@ class Linear(nn.Linear, RelProp):
     def _apply(self, fn, *args, **kwargs):
         ops.x6_invalidate(self)
         return super()._apply(fn, *args, **kwargs)
+
+
+class Linear(_ScratchCache, nn.Linear, RelProp):
+    """layers_ours.py:207-230 / layers_lrp.py:188-211 -> te_linear_relprop_f32."""
 
     def forward(self, x):
         from . import producers                      # 8f.1: forward and / or input gradient on te_gemm_x6_f32
@@ -338,10 +342,11 @@ class BatchNorm2d(nn.BatchNorm2d, _OffPath):
     pass
 
 
-class Conv2d(nn.Conv2d, RelProp):
+class Conv2d(_ScratchCache, nn.Conv2d, RelProp):
     """layers_ours.py:232-279.  Accelerated: the z^B rule of an image-input (3-channel) convolution whose stride
     equals its kernel with no padding -- the ViT patch embedding, reached by method="full" (ViT_LRP.py:337-343) ->
-    te_conv2d_zb_relprop_f32.  Other geometries are off the transformer path."""
+    te_conv2d_zb_relprop_f32, or te_conv2d_zb_relprop_bf16 on a bf16 layer (its weight planes live in x6_cache).  Other
+    geometries are off the transformer path."""
 
     def relprop(self, R, alpha):
         k = self.kernel_size
@@ -350,4 +355,7 @@ class Conv2d(nn.Conv2d, RelProp):
         if not patch:
             raise NotImplementedError("Conv2d.relprop: only the z^B rule of a patch-embedding convolution "
                                       "(3 input channels, stride == kernel, no padding) is accelerated")
+        if self.X.dtype == torch.bfloat16 or self.weight.dtype == torch.bfloat16:
+            # a bf16 layer: conv(X, W) is recomputed from the bf16 operands; its rounded output self.Y is not read
+            return ops.conv2d_zb_relprop_bf16(R, self.X, self.weight.detach(), cache=x6_cache(self))
         return ops.conv2d_zb_relprop(R, self.X, self.weight, self.Y, self.bias)
