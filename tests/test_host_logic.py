@@ -428,3 +428,145 @@ def test_gelu_consumer_hint_is_not_state():
     layer = model.bert.encoder.layer[0]
     assert layer.intermediate.intermediate_act_fn.__dict__["_te_feeds"][0] is layer.output.dense
     assert not any("act_fn" in k for k in model.state_dict())
+
+
+# (fused producers, X6_GEMM, USE_LINEAR_X6, X6_KEEP_ABS, layer in train mode) x (T, in_f, out_f): does the layer take operand
+# planes from its producer?  Filled by evaluating the three expressions this function replaced -- vit.Attention._forward_fused,
+# producers.gelu and the split-dual condition of ops.gemm_x6 -- on the commit before it existed (they agreed on all 240
+# points): True on the three below, False on the other 237.
+_PLANE_SHAPES = [(260, 128, 128), (260, 512, 128), (197, 768, 768), (12608, 768, 1000), (12608, 768, 768)]
+_TAKES_PLANES = {(True, "all", True, True, False, 260, 128, 128), (True, "all", True, True, False, 260, 512, 128),
+                 (True, "all", True, True, False, 12608, 768, 768)}
+
+
+def test_plane_emission_decision_is_one_function():
+    """producers.takes_producer_planes is the one answer producer and consumer share.  It equals the table above on the whole
+    sweep, and so do the three expressions it replaced, transcribed here without the tensor checks their call sites had
+    already made (fp32 device tensor of >= 2 dims: attention_forward_planes_supported / gelu_usable / linear_plan)."""
+    import itertools
+    from transformer_explainability_amd import _lib, ops, producers, rules
+    lib = _lib.load()
+    was = (ops.USE_FUSED_PRODUCERS, ops.X6_GEMM, ops.USE_LINEAR_X6, ops.X6_KEEP_ABS)
+    layers = {s: rules.Linear(s[1], s[2]) for s in _PLANE_SHAPES}
+
+    def plan_fwd(lin, T):          # producers.linear_plan(x, lin)[0] for an fp32 device x of T rows
+        out_f, in_f = lin.weight.shape
+        return ops.USE_FUSED_PRODUCERS and ops.X6_GEMM != "off" and not lin.training and ops.gemm_x6_wanted(T, in_f, out_f)
+
+    def old_attention(lin, T, C):
+        out_f, in_f = lin.weight.shape
+        return bool(in_f == C and ops.USE_FUSED_PRODUCERS and ops.X6_GEMM != "off" and not lin.training
+                    and ops.gemm_x6_wanted(T, in_f, out_f) and ops.USE_LINEAR_X6 and ops.X6_KEEP_ABS
+                    and ops.linear_relprop_x6_supported(T, in_f, out_f))
+
+    def old_gelu(lin, T, K):
+        out_f, in_f = lin.weight.shape
+        return bool(lin.weight.shape[1] == K and plan_fwd(lin, T) and ops.USE_LINEAR_X6 and ops.X6_KEEP_ABS
+                    and ops.linear_relprop_x6_supported(T, in_f, out_f))
+
+    def old_gemm_x6(lin, T, K):    # reached through Linear.forward -> producers.linear with fwd_x6 = plan[0], keep_abs = the dict
+        out_f, in_f = lin.weight.shape
+        return bool(plan_fwd(lin, T) and ops.USE_LINEAR_X6 and ops.X6_KEEP_ABS and lib.te_linear_relprop_x6_supported(T, K, out_f))
+
+    try:
+        n = 0
+        for fused, gemm, lx6, keep, train in itertools.product((False, True), ("all", "auto", "off"), (False, True),
+                                                               (False, True), (False, True)):
+            ops.USE_FUSED_PRODUCERS, ops.X6_GEMM, ops.USE_LINEAR_X6, ops.X6_KEEP_ABS = fused, gemm, lx6, keep
+            for (T, in_f, out_f), lin in layers.items():
+                lin.train(train)
+                want = (fused, gemm, lx6, keep, train, T, in_f, out_f) in _TAKES_PLANES
+                got = producers.takes_producer_planes(lin, T, in_f)
+                assert got is want, (fused, gemm, lx6, keep, train, T, in_f, out_f, got)
+                assert old_attention(lin, T, in_f) == old_gelu(lin, T, in_f) == old_gemm_x6(lin, T, in_f) == want
+                assert not producers.takes_producer_planes(lin, T, in_f + 16)      # a tensor of another width is not its input
+                n += 1
+        assert n == 240
+    finally:
+        ops.USE_FUSED_PRODUCERS, ops.X6_GEMM, ops.USE_LINEAR_X6, ops.X6_KEEP_ABS = was
+
+
+def test_plane_mailboxes_post_take_drop():
+    """The three hand-over mailboxes of a layer's scratch dict (ops.post_* / take_* / drop_x_planes): taking pops the entry
+    whatever the outcome and returns the planes only to the tensor they were posted for."""
+    from transformer_explainability_amd import ops
+    xs, xa, pl = torch.zeros(3), torch.ones(3), torch.full((3,), 2.0)
+    x = torch.randn(2, 5, 8)
+    T, K = 10, 8
+    # forward planes: key match and the held tensor's address
+    c = {}
+    ops.post_x_planes(c, x, xs, xa)
+    assert c["x_planes_from_producer"][0] == ops._x_abs_key(x, T, K) and c["x_planes_from_producer"][3] is x
+    got = ops.take_x_planes(c, x, T, K)
+    assert got[0] is xs and got[1] is xa and not c
+    ops.post_x_planes(c, x, xs, xa)
+    x.add_(0)                                                    # the version counter moved
+    assert ops.take_x_planes(c, x, T, K) is None and not c
+    ops.post_x_planes(c, x, xs, xa)
+    assert ops.take_x_planes(c, x.clone(), T, K) is None and not c       # another tensor of the same shape
+    ops.post_x_planes(c, x, xs, xa)
+    ops.post_x_abs_planes(c, x, T, K, xa)
+    ops.drop_x_planes(c)
+    assert list(c) == ["x_abs_planes"]
+    ops.post_x_planes(c, x, xs, xa)
+    ops.drop_x_planes(c, with_abs=True)
+    assert not c
+    # |X| planes: key match
+    ops.post_x_abs_planes(c, x, T, K, xa)
+    assert c["x_abs_planes"] == (ops._x_abs_key(x, T, K), xa)
+    assert ops.take_x_abs_planes(c, x, T, K) is xa and not c
+    ops.post_x_abs_planes(c, x, T, K, xa)
+    x.add_(0)
+    assert ops.take_x_abs_planes(c, x, T, K) is None and not c
+    ops.post_x_abs_planes(c, x, T, K, xa)
+    assert ops.take_x_abs_planes(c, x.clone(), T, K) is None and not c
+    # gradient planes: the placeholder's address, shape and all-zero strides
+    h = torch.randn(2, 5, 8)
+    dy = ops.post_dy_planes(c, pl, h)
+    base, shape, planes = c["dy_planes_from_consumer"]
+    assert shape == (2, 5, 8) and planes is pl and base.shape == (1,) and dy.data_ptr() == base.data_ptr()
+    assert dy.shape == h.shape and dy.dtype == h.dtype and not any(dy.stride()) and torch.isnan(dy).all()
+    assert ops.take_dy_planes(c, dy) is pl and not c
+    dy = ops.post_dy_planes(c, pl, h)
+    assert ops.take_dy_planes(c, torch.full_like(h, float("nan"))) is None and not c     # right shape, real strides, other address
+    dy = ops.post_dy_planes(c, pl, h)
+    assert ops.take_dy_planes(c, torch.zeros(1).expand(2, 5, 8)) is None and not c       # zero strides at another address
+    dy = ops.post_dy_planes(c, pl, torch.randn(1, 1, 8))
+    assert ops.take_dy_planes(c, dy.expand(2, 5, 8)) is None and not c                   # the address, another shape
+    dy = ops.post_dy_planes(c, pl, torch.randn(1, 1))
+    assert ops.take_dy_planes(c, dy.as_strided((1, 1), (1, 1))) is None and not c        # address and shape, a non-zero stride
+    assert ops.take_dy_planes(c, dy) is None                                             # nothing posted
+
+
+def test_cached_planes_helper():
+    """ops._cached_planes: one build per weight version as the caller holds the weight (ops._weight_key), stored as
+    (key, *payload) -- the layout x6_invalidate, the tests and the five public plane functions rely on."""
+    from transformer_explainability_amd import ops
+    W = torch.randn(6, 6)
+    built = []
+
+    def build(Wd):
+        assert Wd.data_ptr() == W.data_ptr() and not Wd.requires_grad
+        built.append(Wd)
+        return (torch.full((2,), float(len(built))),)
+
+    c = {}
+    (p1,) = ops._cached_planes(W, c, "x6_planes", build)
+    (p2,) = ops._cached_planes(W, c, "x6_planes", build)
+    assert p1 is p2 and len(built) == 1
+    assert c["x6_planes"] == (ops._weight_key(W), p1) and len(c["x6_planes"]) == 2
+    W.add_(0)
+    (p3,) = ops._cached_planes(W, c, "x6_planes", build)
+    assert len(built) == 2 and p3 is not p1 and c["x6_planes"] == (ops._weight_key(W), p3)
+    (p4,) = ops._cached_planes(W.t(), c, "x6_planes", build)           # a transposed view of the same storage: other strides
+    assert len(built) == 3 and c["x6_planes"][0] == ops._weight_key(W.t())
+    (p5,) = ops._cached_planes(W, c, "x6_gemm_planes", build)          # entries do not share builds
+    assert len(built) == 4 and set(c) == {"x6_planes", "x6_gemm_planes"}
+    for _ in range(2):
+        ops._cached_planes(W, None, "x6_planes", build)                # no dict: built every time
+    assert len(built) == 6
+    Wc, pl = ops._cached_planes(W, c, "conv_bf16_planes", lambda Wd: (Wd, p1))     # a two-part payload keeps its order
+    assert c["conv_bf16_planes"] == (ops._weight_key(W), Wc, pl) and pl is p1 and Wc.data_ptr() == W.data_ptr()
+    Wp = torch.nn.Parameter(torch.randn(4, 4))
+    (q,) = ops._cached_planes(Wp, c, "bf16_planes", lambda Wd: (Wd,))   # a parameter reaches the build step detached
+    assert not q.requires_grad and q.data_ptr() == Wp.data_ptr()

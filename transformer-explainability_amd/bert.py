@@ -308,18 +308,15 @@ def make_bert_module(L):
             alpha = kwargs.get("alpha", 1)
             var = self.clone.variant
             cls = lambda t: t[:, :1]                                             # noqa: E731
-            def lin(r, m):       # the staleness guard of the cached forward output applies here as in Linear.relprop
-                y = R_ours._cached_y(m)
-                return ops.linear_relprop(r, cls(m.X), m.weight.detach(), alpha=alpha, variant=var,
-                                          Y=None if y is None else cls(y), bias=m.bias, cache=R_ours.x6_cache(m))
             dfr = ops.USE_DEFERRED_ADD
             c1, c2 = ops.add_relprop(cam_cls, cls(self.output.add.X[0]), cls(self.output.add.X[1]), variant=var,
                                      deferred=dfr)
-            c1 = lin(lin(c1, self.output.dense), self.intermediate.dense)
+            c1 = R_ours.linear_rule(self.output.dense, c1, alpha, cls, var)
+            c1 = R_ours.linear_rule(self.intermediate.dense, c1, alpha, cls, var)
             cam = ops.clone_relprop((c1, c2), cls(self.clone.X))
             att = self.attention
             a1, a2 = ops.add_relprop(cam, cls(att.output.add.X[0]), cls(att.output.add.X[1]), variant=var, deferred=dfr)
-            a1 = lin(a1, att.output.dense)
+            a1 = R_ours.linear_rule(att.output.dense, a1, alpha, cls, var)
             B, N, C = att.clone.X.shape
             dense = torch.zeros((2, B, N, C), dtype=a1.dtype, device=a1.device)
             dense[0, :, 0] = a1[:, 0]

@@ -280,24 +280,32 @@ def x6_invalidate(obj) -> int:
     return n
 
 
-def x6_weight_planes(W: Tensor, cache: Optional[dict] = None) -> Tensor:
-    """bf16 operand planes of a Linear weight for te_linear_relprop_x6_f32, built once per weight version.  `cache` is a
-    dict owned by the layer (rules.Linear keeps one); the entry is keyed on the weight's identity (_weight_key), so an
-    optimiser step or an in-place edit of the weight rebuilds the planes."""
-    out_f, in_f = W.shape
+def _cached_planes(W: Tensor, cache: Optional[dict], name: str, build) -> tuple:
+    """The payload of cache[name] = (_weight_key(W), *payload), built by ``build(W.detach())`` once per weight version (an
+    optimiser step or an in-place edit of the weight changes the key); cache = None builds every time.  `cache` is the
+    layer's scratch dict (rules.x6_cache; DESIGN.md "The layer's scratch dict")."""
     key = _weight_key(W)
-    if cache is not None:
-        hit = cache.get("x6_planes")
-        if hit is not None and hit[0] == key:
-            return hit[1]
-    Wc = _c(W.detach())
+    hit = None if cache is None else cache.get(name)
+    if hit is None or hit[0] != key:
+        hit = (key, *build(W.detach()))
+        if cache is not None:
+            cache[name] = hit
+    return hit[1:]
+
+
+def _prepare_planes(Wc: Tensor, bytes_fn: str, prepare_fn: str, dims: tuple, *extra) -> Tensor:
+    """planes = prepare_fn(Wc, *dims, *extra) in a buffer of bytes_fn(*dims) bytes (the weight-side prepare calls of the C ABI)."""
     with _on_device(Wc) as lib:
-        planes = _ws(lib.te_linear_x6_weight_planes_bytes(in_f, out_f), Wc)
-        _lib.check(lib.te_linear_x6_prepare_weights_f32(_ptr(Wc), in_f, out_f, _ptr(planes), planes.numel(), _stream(Wc)),
-                   "te_linear_x6_prepare_weights_f32")
-    if cache is not None:
-        cache["x6_planes"] = (key, planes)
+        planes = _ws(getattr(lib, bytes_fn)(*dims), Wc)
+        _lib.check(getattr(lib, prepare_fn)(_ptr(Wc), *dims, *extra, _ptr(planes), planes.numel(), _stream(Wc)), prepare_fn)
     return planes
+
+
+def x6_weight_planes(W: Tensor, cache: Optional[dict] = None) -> Tensor:
+    """bf16 operand planes of a Linear weight for te_linear_relprop_x6_f32 (cached: _cached_planes)."""
+    out_f, in_f = W.shape
+    return _cached_planes(W, cache, "x6_planes", lambda Wd: (_prepare_planes(
+        _c(Wd), "te_linear_x6_weight_planes_bytes", "te_linear_x6_prepare_weights_f32", (in_f, out_f)),))[0]
 
 
 # The forward output and the input gradient of a Linear layer on the x6 kernels (SURVEY.md 8f.1; te_gemm_x6_f32) under
@@ -322,42 +330,19 @@ def gemm_x6_wanted(T: int, K: int, M: int) -> bool:
 
 def x6_weight_planes_lrp(W: Tensor, cache: Optional[dict] = None) -> Tensor:
     """P3 planes of max(W,0), min(W,0) and of their transposes: the weight side of te_linear_relprop_x6_general_f32 for
-    variant lrp (one-sided products); built once per weight version like x6_weight_planes."""
+    variant lrp (one-sided products); cached like x6_weight_planes."""
     out_f, in_f = W.shape
-    key = _weight_key(W)
-    if cache is not None:
-        hit = cache.get("x6_planes_lrp")
-        if hit is not None and hit[0] == key:
-            return hit[1]
-    Wc = _c(W.detach())
-    with _on_device(Wc) as lib:
-        planes = _ws(lib.te_linear_x6_weight_planes_lrp_bytes(in_f, out_f), Wc)
-        _lib.check(lib.te_linear_x6_prepare_weights_lrp_f32(_ptr(Wc), in_f, out_f, _ptr(planes), planes.numel(),
-                                                            _stream(Wc)), "te_linear_x6_prepare_weights_lrp_f32")
-    if cache is not None:
-        cache["x6_planes_lrp"] = (key, planes)
-    return planes
+    return _cached_planes(W, cache, "x6_planes_lrp", lambda Wd: (_prepare_planes(
+        _c(Wd), "te_linear_x6_weight_planes_lrp_bytes", "te_linear_x6_prepare_weights_lrp_f32", (in_f, out_f)),))[0]
 
 
 def x6_matrix_planes(W: Tensor, transposed: bool, cache: Optional[dict] = None) -> Tensor:
     """Signed bf16 operand planes of W [out, in] (transposed=False: rows = out, the forward product's weight side) or of
-    W^T (transposed=True: rows = in, the input gradient's), built once per weight version (cache as x6_weight_planes)."""
+    W^T (transposed=True: rows = in, the input gradient's); cached like x6_weight_planes."""
     out_f, in_f = W.shape
-    name = "x6_gemm_planes_T" if transposed else "x6_gemm_planes"
-    key = _weight_key(W)
-    if cache is not None:
-        hit = cache.get(name)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-    Wc = _c(W.detach())
-    rows, K = (in_f, out_f) if transposed else (out_f, in_f)
-    with _on_device(Wc) as lib:
-        planes = _ws(lib.te_linear_x6_planes_bytes(rows, K), Wc)
-        _lib.check(lib.te_linear_x6_split_matrix_f32(_ptr(Wc), rows, K, int(transposed), _ptr(planes), planes.numel(),
-                                                     _stream(Wc)), "te_linear_x6_split_matrix_f32")
-    if cache is not None:
-        cache[name] = (key, planes)
-    return planes
+    dims = (in_f, out_f) if transposed else (out_f, in_f)
+    return _cached_planes(W, cache, "x6_gemm_planes_T" if transposed else "x6_gemm_planes", lambda Wd: (_prepare_planes(
+        _c(Wd), "te_linear_x6_planes_bytes", "te_linear_x6_split_matrix_f32", dims, int(transposed)),))[0]
 
 
 def linear_relprop_x6_supported(T: int, in_f: int, out_f: int) -> bool:
@@ -375,13 +360,72 @@ def _x_abs_key(X: Tensor, T: int, K: int):
     return (X.data_ptr(), X._version, T, K, str(X.device))
 
 
+# The three plane hand-overs between layers, each a mailbox in the consuming layer's scratch dict: one function posts, one
+# takes (pops the entry, validates it, returns the planes or None).  Who calls them, and how long an entry may live:
+# DESIGN.md "The layer's scratch dict".
+def post_x_planes(cache: dict, X: Tensor, xs: Tensor, xa: Tensor):
+    """A producer of X leaves the signed planes of X [T, K] and the planes of |X| for the Linear that consumes X.  The entry
+    HOLDS X: while it exists, X's address cannot be recycled for a tensor that would meet the key by accident."""
+    K = X.shape[-1]
+    cache["x_planes_from_producer"] = (_x_abs_key(X, X.numel() // K, K), xs, xa, X)
+
+
+def take_x_planes(cache: dict, X: Tensor, T: int, K: int):
+    """(xs, xa) if a producer posted the planes of exactly this X, else None."""
+    hit = cache.pop("x_planes_from_producer", None)
+    if hit is not None and hit[0] == _x_abs_key(X, T, K) and hit[3].data_ptr() == X.data_ptr():
+        return hit[1], hit[2]
+    return None
+
+
+def drop_x_planes(cache: dict, with_abs: bool = False):
+    """Nothing of an earlier call may wait for this call's input (with_abs: nor for its rule)."""
+    cache.pop("x_planes_from_producer", None)
+    if with_abs:
+        cache.pop("x_abs_planes", None)
+
+
+def post_x_abs_planes(cache: dict, X: Tensor, T: int, K: int, xa: Tensor):
+    """The layer's forward product leaves the planes of |X| for its own relprop rule."""
+    cache["x_abs_planes"] = (_x_abs_key(X, T, K), xa)
+
+
+def take_x_abs_planes(cache: dict, X: Tensor, T: int, K: int) -> Optional[Tensor]:
+    """The planes of |X| if the forward product of exactly this X left them, else None.  Consumed once: 6 B per input
+    element (0.4 GB per ViT-B block at batch 64) must not outlive the rule."""
+    hit = cache.pop("x_abs_planes", None)
+    return hit[1] if hit is not None and hit[0] == _x_abs_key(X, T, K) else None
+
+
+def post_dy_planes(cache: dict, planes: Tensor, like: Tensor) -> Tensor:
+    """A consumer's backward leaves the planes of its input gradient for the backward of the Linear that produced `like`;
+    returns what autograd carries instead of the fp32 gradient: a zero-stride NaN placeholder of like's shape (whoever
+    reads it reads NaN, not stale memory)."""
+    base = torch.full((1,), float("nan"), dtype=like.dtype, device=like.device)
+    cache["dy_planes_from_consumer"] = (base, tuple(like.shape), planes)
+    return base.expand(like.shape)
+
+
+def take_dy_planes(cache: dict, dy: Tensor) -> Optional[Tensor]:
+    """The posted planes if dy is the placeholder of that post (its address, shape, all-zero strides), else None."""
+    hit = cache.pop("dy_planes_from_consumer", None)
+    if hit is not None and dy.data_ptr() == hit[0].data_ptr() and tuple(dy.shape) == hit[1] and not any(dy.stride()):
+        return hit[2]
+    return None
+
+
+def rule_takes_abs_planes(T: int, in_f: int, out_f: int) -> bool:
+    """Will Linear.relprop of a [T, in_f] input run on te_linear_relprop_x6_f32 and read the planes of |X| its forward
+    product leaves behind?  (The rule-side half of producers.takes_producer_planes.)"""
+    return bool(USE_LINEAR_X6 and X6_KEEP_ABS and linear_relprop_x6_supported(T, in_f, out_f))
+
+
 def gemm_x6(X: Tensor, w_planes: Tensor, bias: Optional[Tensor], M: int, timer_name: str = "gemm_x6",
             keep_abs: Optional[dict] = None, x_planes: Optional[Tensor] = None) -> Tensor:
     """out [..., M] = X [..., K] . W^T + bias with W as signed planes of an [M, K] matrix (x6_matrix_planes).
-    keep_abs: the layer's cache dict -- the split pass then also writes the planes of |X| (bit for bit those of a split of |X|) (te_linear_x6_split_dual_f32) and
-    leaves them there for the layer's relprop rule (linear_relprop: the rule's own split pass over X disappears); a producer
-    of X that emitted both plane sets itself left them under "x_planes_from_producer" (gelu_forward_planes) and the split
-    pass disappears as well.
+    keep_abs: the layer's scratch dict -- the signed planes of X are taken from X's producer if it posted them there, else
+    split here, together with the planes of |X| where the layer's rule will read them (te_linear_x6_split_dual_f32: bit for
+    bit those of a split of |X|); the planes of |X| are posted for that rule (DESIGN.md "The layer's scratch dict").
     x_planes: the signed planes of X from its producer (gelu_backward_planes) -- X is then used for its shape only and never
     read (it may be the zero-stride placeholder the producer returned instead of an fp32 tensor)."""
     K = X.shape[-1]
@@ -396,23 +440,20 @@ def gemm_x6(X: Tensor, w_planes: Tensor, bias: Optional[Tensor], M: int, timer_n
         x_bytes = (6.0 if x_planes is not None else 10.0) * T * K      # planes read / fp32 read + planes written
         xs = x_planes
         if xs is None and keep_abs is not None:
-            hit = keep_abs.pop("x_planes_from_producer", None)
-            # the entry HOLDS the tensor the planes were split from (hit[3]): while the entry exists that address cannot be
-            # recycled for a new tensor that would meet the key by accident
-            if hit is not None and hit[0] == _x_abs_key(X, T, K) and hit[3].data_ptr() == X.data_ptr():
-                xs, x_bytes = hit[1], 6.0 * T * K
-                keep_abs["x_abs_planes"] = (hit[0], hit[2])
+            got = take_x_planes(keep_abs, X, T, K)
+            if got is not None:
+                xs, x_bytes = got[0], 6.0 * T * K
+                post_x_abs_planes(keep_abs, X, T, K, got[1])
         if xs is not None and xs.numel() * xs.element_size() < lib.te_linear_x6_planes_bytes(T, K):
             raise _lib.TeError(f"gemm_x6: the operand planes handed in hold {xs.numel() * xs.element_size()} bytes, "
                                f"[{T}, {K}] needs {lib.te_linear_x6_planes_bytes(T, K)}")
         with _timed(timer_name, 12.0 * T * K * M, x_bytes + 6.0 * K * M + 4.0 * T * M):
-            if (xs is None and keep_abs is not None and USE_LINEAR_X6 and X6_KEEP_ABS
-                    and lib.te_linear_relprop_x6_supported(T, K, M)):
+            if xs is None and keep_abs is not None and rule_takes_abs_planes(T, K, M):
                 nb = lib.te_linear_x6_planes_bytes(T, K)
                 xs, xa = _ws(nb, Xc), _ws(nb, Xc)
                 _lib.check(lib.te_linear_x6_split_dual_f32(_ptr(Xc), T, K, _ptr(xs), _ptr(xa), nb, _stream(Xc)),
                            "te_linear_x6_split_dual_f32")
-                keep_abs["x_abs_planes"] = (_x_abs_key(X, T, K), xa)
+                post_x_abs_planes(keep_abs, X, T, K, xa)
             _lib.check(lib.te_gemm_x6_f32(_ptr(Xc) if Xc is not None else None, _ptr(xs), _ptr(w_planes), _ptr(bc), _ptr(out),
                                           T, K, M, (X6_TILE | X6_FLAGS) & ~0x3c00, _ptr(x6_status(X.device)), _ptr(ws),
                                           ws.numel(), _stream(like)), "te_gemm_x6_f32")
@@ -460,16 +501,9 @@ def linear_relprop(R: Tensor, X: Tensor, W: Tensor, alpha: float = 1.0, variant=
             bg = None if bias is None else _c(bias.detach())
             general = Yg.shape[0] == T and Yg.data_ptr() % 16 == 0 and (bg is None or bg.data_ptr() % 16 == 0)
     if general:
-        rs_ptr, rs_stride, rps = None, 0, 1
-        if r_scale is not None:
-            rs_ptr, rs_stride, rps = r_scale.data_ptr(), r_scale.stride(0), T // r_scale.shape[0]
         wp = x6_weight_planes(W, cache) if var_code == TE_VARIANT_OURS else None
         wpl = x6_weight_planes_lrp(W, cache) if var_code == TE_VARIANT_LRP else None
-        xa = None
-        if cache is not None and var_code == TE_VARIANT_OURS:
-            hit = cache.pop("x_abs_planes", None)
-            if hit is not None and hit[0] == _x_abs_key(X, T, in_f):
-                xa = hit[1]
+        xa = take_x_abs_planes(cache, X, T, in_f) if cache is not None and var_code == TE_VARIANT_OURS else None
         gemm = 2.0 * T * in_f * out_f
         halves = 2 if alpha != 1 else 1
         units = (18.0 if var_code == TE_VARIANT_OURS else 24.0) * halves
@@ -492,12 +526,8 @@ def linear_relprop(R: Tensor, X: Tensor, W: Tensor, alpha: float = 1.0, variant=
     if (fwd and USE_LINEAR_X6 and Yc.data_ptr() % 16 == 0 and (bc is None or bc.data_ptr() % 16 == 0)
             and _lib.load().te_linear_relprop_x6_supported(T, in_f, out_f)):
         planes = x6_weight_planes(W, cache)           # (keyed on W as the caller holds it, not on a contiguous copy)
-        xa = None       # the planes of |X| the layer's own forward product left behind (gemm_x6 keep_abs), if X is that tensor
-        if cache is not None:
-            # consumed once: 6 B per input element (0.4 GB per ViT-B block at batch 64) must not outlive the rule
-            hit = cache.pop("x_abs_planes", None)
-            if hit is not None and hit[0] == _x_abs_key(X, T, in_f):
-                xa = hit[1]
+        # the planes of |X| the layer's own forward product left behind (gemm_x6 keep_abs), if X is that tensor
+        xa = take_x_abs_planes(cache, X, T, in_f) if cache is not None else None
         with _on_device(Xc) as lib:
             ws = _ws(lib.te_linear_relprop_x6_workspace_bytes(T, in_f, out_f), Xc)
             status = x6_status(Xc.device)
@@ -1407,22 +1437,10 @@ def conv_bf16_route(C: int, E: int, p: int) -> str:
 
 
 def bf16_weight_planes(W: Tensor, cache: Optional[dict] = None) -> Tensor:
-    """W+, W- and their transposes for te_linear_relprop_bf16, built once per weight version (cached like
-    x6_weight_planes: keyed on the weight's identity, dropped by x6_invalidate / load_state_dict / .to())."""
+    """W+, W- and their transposes for te_linear_relprop_bf16; cached like x6_weight_planes."""
     out_f, in_f = W.shape
-    key = _weight_key(W)
-    if cache is not None:
-        hit = cache.get("bf16_planes")
-        if hit is not None and hit[0] == key:
-            return hit[1]
-    Wc = _c16(W.detach())
-    with _on_device(Wc) as lib:
-        planes = _ws(lib.te_linear_bf16_weight_planes_bytes(in_f, out_f), Wc)
-        _lib.check(lib.te_linear_bf16_prepare_weights(_ptr(Wc), in_f, out_f, _ptr(planes), planes.numel(), _stream(Wc)),
-                   "te_linear_bf16_prepare_weights")
-    if cache is not None:
-        cache["bf16_planes"] = (key, planes)
-    return planes
+    return _cached_planes(W, cache, "bf16_planes", lambda Wd: (_prepare_planes(
+        _c16(Wd), "te_linear_bf16_weight_planes_bytes", "te_linear_bf16_prepare_weights", (in_f, out_f)),))[0]
 
 
 def _rows(X: Tensor, K: int) -> Tuple[Tensor, int]:
@@ -1598,24 +1616,15 @@ def add_relprop_bf16(R: Tensor, X0: Tensor, X1: Tensor, variant="ours", deferred
 
 def conv_bf16_weight_planes(W: Tensor, cache: Optional[dict] = None) -> Tuple[Tensor, Tensor]:
     """(the contiguous 16-byte aligned W [E,C,p,p], its planes: W+^T, W-^T and the two channel sums) for
-    te_conv2d_zb_relprop_bf16, built once per weight version (cached like bf16_weight_planes: keyed on the weight's identity,
-    dropped by x6_invalidate / load_state_dict / .to())."""
+    te_conv2d_zb_relprop_bf16; cached like x6_weight_planes."""
     E, C, p, _ = W.shape
-    key = _weight_key(W)
-    if cache is not None:
-        hit = cache.get("conv_bf16_planes")
-        if hit is not None and hit[0] == key:
-            return hit[1], hit[2]
-    Wc = _c16(W.detach())
-    if Wc.data_ptr() % 16:
-        Wc = Wc.clone()
-    with _on_device(Wc) as lib:
-        planes = _ws(lib.te_conv2d_zb_bf16_weight_planes_bytes(C, E, p), Wc)
-        _lib.check(lib.te_conv2d_zb_bf16_prepare_weights(_ptr(Wc), C, E, p, _ptr(planes), planes.numel(), _stream(Wc)),
-                   "te_conv2d_zb_bf16_prepare_weights")
-    if cache is not None:
-        cache["conv_bf16_planes"] = (key, Wc, planes)
-    return Wc, planes
+
+    def build(Wd):
+        Wc = _c16(Wd)
+        if Wc.data_ptr() % 16:
+            Wc = Wc.clone()
+        return Wc, _prepare_planes(Wc, "te_conv2d_zb_bf16_weight_planes_bytes", "te_conv2d_zb_bf16_prepare_weights", (C, E, p))
+    return _cached_planes(W, cache, "conv_bf16_planes", build)
 
 
 def conv2d_zb_relprop_bf16(R: Tensor, X: Tensor, W: Tensor, cache: Optional[dict] = None) -> Tensor:

@@ -60,19 +60,11 @@ class _ResidualLayerNorm(torch.autograd.Function):
 
 
 class _Gelu(torch.autograd.Function):
-    """nn.GELU.  Round 5: between two Linear layers that run on the x6 kernels it emits their operand
-    planes itself (csrc/te_linear_x6.hip: gelu_split_kernel) --
-      forward   feeds = the cache dict of the Linear that consumes the output (rules.GELU.feeds): the output is written as
-                fp32 and as the two plane sets that layer's forward product and rule would otherwise split from it; they wait
-                in that dict under "x_planes_from_producer", keyed on the output tensor (ops.gemm_x6 checks the key);
-      backward  source = the cache dict of the Linear whose output this node received, if that layer forms its input gradient
-                on gemm_x6 (producers.linear marks its output): the gradient leaves this node as planes in that dict
-                ("dy_planes_from_consumer") and as a zero-stride NaN placeholder in autograd's hands -- _Linear.backward
-                recognises the placeholder by its address and never reads it; anything else that consumed it would read
-                NaN, not stale memory.  ONLY inside ``ops.gelu_backward_plane_handoff()`` (round 6): the
-                generators of this package, which drive the backward pass themselves towards attention tensors only, opt
-                in for their own forward pass; under a plain ``model(x)`` the node returns the real fp32 gradient, so
-                ``autograd.grad(out, h)``, ``h.retain_grad()``, tensor hooks and second consumers see standard autograd."""
+    """nn.GELU.  Between two Linear layers that run on the x6 kernels it emits their operand planes itself
+    (csrc/te_linear_x6.hip: gelu_split_kernel): forward into `feeds`, the scratch dict of the Linear that consumes the
+    output; backward into `source`, the scratch dict of the Linear whose output this node received -- autograd then
+    carries a NaN placeholder, which is why `source` is only set inside ``ops.gelu_backward_plane_handoff()``
+    (DESIGN.md "The layer's scratch dict")."""
 
     @staticmethod
     def forward(ctx, x, feeds, source):
@@ -80,8 +72,7 @@ class _Gelu(torch.autograd.Function):
         ctx.source = source
         if feeds is not None:
             y, xs, xa = ops.gelu_forward_planes(x)
-            K = y.shape[-1]
-            feeds["x_planes_from_producer"] = (ops._x_abs_key(y, y.numel() // K, K), xs, xa, y)
+            ops.post_x_planes(feeds, y, xs, xa)
             return y
         return ops.gelu_forward(x)
 
@@ -89,10 +80,7 @@ class _Gelu(torch.autograd.Function):
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         if ctx.source is not None:
-            planes = ops.gelu_backward_planes(dy, x)
-            base = torch.full((1,), float("nan"), dtype=x.dtype, device=x.device)
-            ctx.source["dy_planes_from_consumer"] = (base, tuple(x.shape), planes)
-            return base.expand(x.shape), None, None
+            return ops.post_dy_planes(ctx.source, ops.gelu_backward_planes(dy, x), x), None, None
         return ops.gelu_backward(dy, x), None, None
 
 
@@ -116,14 +104,9 @@ class _Linear(torch.autograd.Function):
         w = ctx.weight
         if ctx.bwd_x6:
             # the GELU node that consumed this layer's output may have left the gradient as operand planes (_Gelu.backward);
-            # dy is then its zero-stride placeholder, recognised by address and shape, and is never read
-            hit = ctx.cache.pop("dy_planes_from_consumer", None)
-            planes = None
-            if (hit is not None and dy.data_ptr() == hit[0].data_ptr() and tuple(dy.shape) == hit[1]
-                    and not any(dy.stride())):
-                planes = hit[2]
+            # dy is then its placeholder and is never read
             dx = ops.gemm_x6(dy, ops.x6_matrix_planes(w, True, ctx.cache), None, w.shape[1], "linear_backward_x6",
-                             x_planes=planes)
+                             x_planes=ops.take_dy_planes(ctx.cache, dy))
         else:
             dx = torch.matmul(dy, w)
         return dx, None, None, None, None, None
@@ -137,6 +120,15 @@ def linear_plan(x: torch.Tensor, lin):
     out_f, in_f = lin.weight.shape
     T = x.numel() // in_f
     return ops.gemm_x6_wanted(T, in_f, out_f), ops.gemm_x6_wanted(T, out_f, in_f)
+
+
+def takes_producer_planes(lin, T: int, K: int) -> bool:
+    """Will `lin` (a rules.Linear) take the operand planes of a [T, K] fp32 device tensor from the tensor's producer: forward
+    product on gemm_x6 (linear_plan) AND rule on the x6 kernel that reads the planes of |X|?  The ONE answer the emitting
+    producers (gelu, vit.Attention) and the consumer (ops.gemm_x6) share -- DESIGN.md "The layer's scratch dict"."""
+    out_f, in_f = lin.weight.shape
+    return bool(K == in_f and ops.USE_FUSED_PRODUCERS and ops.X6_GEMM != "off" and not lin.training
+                and ops.gemm_x6_wanted(T, in_f, out_f) and ops.rule_takes_abs_planes(T, in_f, out_f))
 
 
 # The parameters enter the producer nodes DETACHED: these nodes produce the input gradient only, and autograd is told so
@@ -165,13 +157,11 @@ def gelu(x, consumer=None, consumer_cache=None):
     """consumer: the Linear layer the output goes to, if the caller knows it (rules.GELU.feeds), and its cache dict."""
     feeds = source = None
     if ops.gelu_planes_supported(x):
-        if consumer is not None and consumer.weight.shape[1] == x.shape[-1] and linear_plan(x, consumer)[0]:
-            out_f, in_f = consumer.weight.shape
-            if (ops.USE_LINEAR_X6 and ops.X6_KEEP_ABS
-                    and ops.linear_relprop_x6_supported(x.numel() // in_f, in_f, out_f)):
-                feeds = consumer_cache
+        K = x.shape[-1]
+        if consumer is not None and takes_producer_planes(consumer, x.numel() // K, K):
+            feeds = consumer_cache
         if ops.gelu_backward_handoff_active():     # opt-in of the caller that owns the backward pass (ops.py, ADVICE r5)
             source = getattr(x, "_te_bwd_x6_cache", None)
     if feeds is None and consumer_cache is not None:
-        consumer_cache.pop("x_planes_from_producer", None)      # nothing of an earlier call may wait there for this one's output
+        ops.drop_x_planes(consumer_cache)
     return _Gelu.apply(x, feeds, source)

@@ -167,21 +167,28 @@ class Linear(_ScratchCache, nn.Linear, RelProp):
     def forward(self, x):
         from . import producers                      # 8f.1: forward and / or input gradient on te_gemm_x6_f32
         plan = producers.linear_plan(x, self)
-        if not plan[0]:
-            x6_cache(self).pop("x_abs_planes", None)      # no x6 forward product of THIS input: nothing for the rule to reuse
-            x6_cache(self).pop("x_planes_from_producer", None)
+        if not plan[0]:      # no x6 forward product of THIS input: nothing may wait for it, nothing for the rule to reuse
+            ops.drop_x_planes(x6_cache(self), with_abs=True)
         if plan[0] or plan[1]:
             return producers.linear(x, self, x6_cache(self), plan)
         return super().forward(x)
 
     def relprop(self, R, alpha):
-        # self.Y (the forward output, cached by forward_hook like the reference does) lets the kernel derive
-        # Z = X+ W+^T + X- W-^T from one product instead of two
-        Y = _cached_y(self)
-        if Y is not None and Y.shape[:-1] != self.X.shape[:-1]:
-            Y = None
-        return ops.linear_relprop(R, self.X, self.weight.detach(), alpha=alpha, variant=self.variant, Y=Y,
-                                  bias=self.bias, cache=x6_cache(self))
+        return linear_rule(self, R, alpha)
+
+
+def linear_rule(m, R, alpha, rows=None, variant=None):
+    """The one route from a Linear layer `m` to ops.linear_relprop.  m.Y (the forward output, cached by forward_hook like
+    the reference does) lets the kernel derive Z = X+ W+^T + X- W-^T from one product instead of two -- while it is what
+    the forward pass wrote (_cached_y) and has X's rows.  rows: a selector applied to X and Y (``t[:, :1]``: the cls slice
+    of Block.relprop_cls_only / BertLayer.relprop_cls_only, which also pass the variant their other rules run under)."""
+    X, Y = m.X, _cached_y(m)
+    if Y is not None and Y.shape[:-1] != X.shape[:-1]:
+        Y = None
+    if rows is not None:
+        X, Y = rows(X), None if Y is None else rows(Y)
+    return ops.linear_relprop(R, X, m.weight.detach(), alpha=alpha, variant=variant or m.variant, Y=Y, bias=m.bias,
+                              cache=x6_cache(m))
 
 
 class Add(RelProp):

@@ -78,12 +78,11 @@ class _FusedAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, num_heads, scale, module, feeds=None):
-        # feeds (round 6): the cache dict of the projection layer, if that layer will run its forward product and its rule on
-        # the x6 kernels -- the producer then writes the operand planes of `out` itself and the layer's split pass disappears
-        # (the GELU pattern: producers._Gelu; the consumer checks that the planes belong to the tensor it receives)
+        # feeds: the scratch dict of the projection layer if that layer takes the operand planes of `out` from this node
+        # (producers.takes_producer_planes; DESIGN.md "The layer's scratch dict")
         if feeds is not None:
             out, attn, zqk, xs, xa = ops.attention_forward(qkv, num_heads, scale, planes=True)
-            feeds["x_planes_from_producer"] = (ops._x_abs_key(out, out.numel() // out.shape[-1], out.shape[-1]), xs, xa, out)
+            ops.post_x_planes(feeds, out, xs, xa)
         else:
             out, attn, zqk = ops.attention_forward(qkv, num_heads, scale)
         ctx.save_for_backward(qkv, attn, out)      # (out: the projection's input, alive anyway; the backward's row sums come from it)
@@ -221,14 +220,9 @@ def make_vit_module(L):
             H, D = self.num_heads, C // self.num_heads
             qkv = self.qkv(x)
             feeds = None
-            if isinstance(self.proj, L.Linear) and ops.attention_forward_planes_supported(qkv, H):
-                from .rules import x6_cache
-                out_f, in_f = self.proj.weight.shape
-                # (the layer's own plan for an input of out's shape: producers.linear_plan / producers.gelu)
-                if (in_f == C and ops.USE_FUSED_PRODUCERS and ops.X6_GEMM != "off" and not self.proj.training
-                        and ops.gemm_x6_wanted(B * N, in_f, out_f) and ops.USE_LINEAR_X6 and ops.X6_KEEP_ABS
-                        and ops.linear_relprop_x6_supported(B * N, in_f, out_f)):
-                    feeds = x6_cache(self.proj)
+            if (isinstance(self.proj, L.Linear) and ops.attention_forward_planes_supported(qkv, H)
+                    and producers.takes_producer_planes(self.proj, B * N, C)):
+                feeds = R_ours.x6_cache(self.proj)
             out, attn, zqk = _FusedAttention.apply(qkv, H, self.scale, self, feeds)
             self._fused_anchor = qkv if qkv.requires_grad else None
             q, k, v = qkv.detach().view(B, N, 3, H, D).permute(2, 0, 3, 1, 4)
@@ -317,14 +311,11 @@ def make_vit_module(L):
             cls = lambda t: t[:, :1]                                             # noqa: E731
             dfr = ops.USE_DEFERRED_ADD
             c1, c2 = ops.add_relprop(cam_cls, cls(self.add2.X[0]), cls(self.add2.X[1]), variant=var, deferred=dfr)
-            def lin(r, m):       # the staleness guard of the cached forward output applies here as in Linear.relprop
-                y = R_ours._cached_y(m)
-                return ops.linear_relprop(r, cls(m.X), m.weight.detach(), alpha=alpha, variant=var,
-                                          Y=None if y is None else cls(y), bias=m.bias, cache=R_ours.x6_cache(m))
-            c2 = lin(lin(c2, self.mlp.fc2), self.mlp.fc1)
+            c2 = R_ours.linear_rule(self.mlp.fc2, c2, alpha, cls, var)
+            c2 = R_ours.linear_rule(self.mlp.fc1, c2, alpha, cls, var)
             cam = ops.clone_relprop((c1, c2), cls(self.clone2.X))
             c1, c2 = ops.add_relprop(cam, cls(self.add1.X[0]), cls(self.add1.X[1]), variant=var, deferred=dfr)
-            c2 = lin(c2, self.attn.proj)
+            c2 = R_ours.linear_rule(self.attn.proj, c2, alpha, cls, var)
             if isinstance(c1, ops.Deferred):
                 c1 = c1.materialise()
             B, N, C = self.clone1.X.shape
