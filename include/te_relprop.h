@@ -718,6 +718,59 @@ int te_conv2d_zb_relprop_bf16(const float* R, int64_t r_bs, const te_bf16_t* X, 
                               float* out, int64_t B, int64_t C, int64_t H, int64_t W_, int64_t E, int64_t p, void* ws,
                               size_t ws_bytes, te_stream_t stream);
 
+/* ---- fp64 operands (an fp64 ViT / DeiT or BERT model: model.double()) ------------------------------------------------
+ * The rules of variant "ours", alpha = 1, evaluated in DOUBLE on the model's own fp64 tensors: operands, relevance,
+ * safe_divide, per-sample sums, factors and outputs are all fp64; nothing is routed through an fp32 or bf16 kernel.
+ * csrc/te_f64.hip: the GEMM-shaped rules on v_mfma_f64_16x16x4_f64 (one loop, any M, N, K >= 1, every operand a strided
+ * view read in place: no shape predicate and no other route), the streaming rules as plain fp64 kernels.  No pointer needs
+ * more than the 8-byte alignment of a double.  Every output's summation order is fixed by its own indices: a batch equals
+ * its samples bit for bit, and a call repeated gives the same bits.
+ *
+ * Linear.relprop: R [T,out_f] (row stride r_ld), X [T,in_f] (row stride x_ld: the cls rows of a [B,N,C] activation are read
+ * in place), W [out_f,in_f] (row stride w_ld) -> out [T,in_f] contiguous.
+ *   Z = X+ W+^T + X- W-^T (both operands sign-split in registers: no weight planes, nothing cached; the layer's forward
+ *   output is not an argument) ; S = sd(R, Z) as fp64 [T,out_f] in ws ; out = X+ . (S W+) + X- . (S W-) */
+size_t te_linear_relprop_f64_workspace_bytes(int64_t T, int64_t in_f, int64_t out_f);
+int te_linear_relprop_f64(const double* R, int64_t r_ld, const double* X, int64_t x_ld, const double* W, int64_t w_ld,
+                          double* out, int64_t T, int64_t in_f, int64_t out_f, void* ws, size_t ws_bytes,
+                          te_stream_t stream);
+/* The two attention rules: the arguments of te_matmul_relprop_av_fwdz_f32 / te_matmul_relprop_qk_fwd_scaled_f32 without a
+ * variant and a relevance factor.  Z (the product whose rule is evaluated: attn v [B,H,N,D] strided, the UNSCALED q k^T
+ * [B,H,N,N] contiguous) is always an operand.  attn, R (QK) and cam_attn contiguous; R (AV), q, k, v and the cam_q / cam_k /
+ * cam_v outputs strided with a contiguous last dim.  S = sd(R, Z) in ws;
+ *   cam_attn = attn . (S v^T), cam_v = v . (attn^T S), cam_q = q . (S k), cam_k = k . (S^T q), each times out_scale. */
+size_t te_matmul_relprop_av_f64_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t D);
+size_t te_matmul_relprop_qk_f64_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t D);
+int te_matmul_relprop_av_f64(const double* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const double* attn,
+                             const double* v, int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                             const double* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn,
+                             double* cam_attn, double* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn,
+                             int64_t B, int64_t H, int64_t N, int64_t D, double out_scale,
+                             void* ws, size_t ws_bytes, te_stream_t stream);
+int te_matmul_relprop_qk_f64(const double* R, const double* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                             const double* k, int64_t k_sb, int64_t k_sh, int64_t k_sn, const double* Z,
+                             double* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn,
+                             double* cam_k, int64_t ck_sb, int64_t ck_sh, int64_t ck_sn,
+                             int64_t B, int64_t H, int64_t N, int64_t D, double out_scale,
+                             void* ws, size_t ws_bytes, te_stream_t stream);
+/* Add.relprop, variant ours (te_add_relprop_f32's arguments): the three per-sample sums in fp64, 2048 consecutive elements
+ * per workgroup in a fixed tree, the workgroups' sums added in index order.  te_add_bcast_relprop_f64: the BERT mask form,
+ * X0 [B,H,N,N], mask [B,N] mask_batch_stride elements apart (0: one mask for every sample), out1 [B,N]. */
+size_t te_add_relprop_f64_workspace_bytes(int64_t B, int64_t n);
+int te_add_relprop_f64(const double* R, const double* X0, const double* X1, double* out0, double* out1, int64_t B,
+                       int64_t n, int64_t x1_batch_stride, void* ws, size_t ws_bytes, te_stream_t stream);
+size_t te_add_bcast_relprop_f64_workspace_bytes(int64_t B, int64_t H, int64_t N);
+int te_add_bcast_relprop_f64(const double* R, const double* X0, const double* mask, int64_t mask_batch_stride,
+                             double* out0, double* out1, int64_t B, int64_t H, int64_t N, void* ws, size_t ws_bytes,
+                             te_stream_t stream);
+/* Clone (R2 may be NULL), IndexSelect (dim 1, one index) and the gradient x relevance head mean, as their _f32 entries. */
+int te_clone_relprop_f64(const double* R0, const double* R1, const double* R2, const double* X, double* out, int64_t n,
+                         te_stream_t stream);
+int te_index_select_relprop_f64(const double* R, const double* X, double* out, int64_t B, int64_t N, int64_t C,
+                                int64_t index, te_stream_t stream);
+int te_gradcam_headmean_f64(const double* grad, const double* cam, double* out, int64_t B, int64_t H, int64_t N,
+                            te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

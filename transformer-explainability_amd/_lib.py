@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 
 import torch  # noqa: F401  (must precede dlopen of libte_relprop: loads torch's libamdhip64 first)
 
@@ -17,7 +17,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TE_RELPROP_LIB") or os.path.join(_PKG, "lib", "libte_relprop.so")
 
 TE_OK = 0
-MIN_LIB_VERSION = 601      # te_version(): 0.6.1, te_conv2d_zb_relprop_bf16 (0.6.0: te_build_id)
+MIN_LIB_VERSION = 700      # te_version(): 0.7.0, the fp64 rules (0.6.1: te_conv2d_zb_relprop_bf16, 0.6.0: te_build_id)
 TE_ERR_UNSUPPORTED = -3
 TE_VARIANT_OURS = 0
 TE_VARIANT_LRP = 1
@@ -31,7 +31,7 @@ TE_RATIONALE_CLAMP = 1
 TE_RATIONALE_MAX_KS = 16
 TE_TOKEN_ERASE_MAX_FRACTIONS = 8
 
-_P, _I64, _F, _I, _SZ = c_void_p, c_int64, c_float, c_int, c_size_t
+_P, _I64, _F, _I, _SZ, _D = c_void_p, c_int64, c_float, c_int, c_size_t, c_double
 
 # name -> (restype, argtypes); mirrors include/te_relprop.h one to one
 SIGNATURES = {
@@ -152,6 +152,22 @@ SIGNATURES = {
     "te_gradcam_headmean_bf16": (_I, [_P, _P, _P, _I64, _I64, _I64, _P]),
     "te_attn_headmean_bf16": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I, _P]),
     "te_perturb_bf16": (_I, [_P, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _SZ, _P]),
+    # fp64 operands (csrc/te_f64.hip)
+    "te_linear_relprop_f64_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "te_linear_relprop_f64": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, _SZ, _P]),
+    "te_matmul_relprop_av_f64_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "te_matmul_relprop_qk_f64_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "te_matmul_relprop_av_f64": (_I, [_P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P,
+                                      _I64, _I64, _I64, _I64, _I64, _I64, _I64, _D, _P, _SZ, _P]),
+    "te_matmul_relprop_qk_f64": (_I, [_P, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _P,
+                                      _I64, _I64, _I64, _I64, _I64, _I64, _I64, _D, _P, _SZ, _P]),
+    "te_add_relprop_f64_workspace_bytes": (_SZ, [_I64, _I64]),
+    "te_add_relprop_f64": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
+    "te_add_bcast_relprop_f64_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "te_add_bcast_relprop_f64": (_I, [_P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
+    "te_clone_relprop_f64": (_I, [_P, _P, _P, _P, _P, _I64, _P]),
+    "te_index_select_relprop_f64": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _P]),
+    "te_gradcam_headmean_f64": (_I, [_P, _P, _P, _I64, _I64, _I64, _P]),
     # the z^B rule of a bf16 patch embedding (csrc/te_conv_bf16.hip)
     "te_conv2d_zb_relprop_bf16_supported": (_I, [_I64, _I64, _I64]),
     "te_conv2d_zb_relprop_bf16_workspace_bytes": (_SZ, [_I64] * 6),

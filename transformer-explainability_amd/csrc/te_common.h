@@ -31,6 +31,10 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // fp32 MFMAs: exact k-ordered fma chains at the fp32 vector rate (the bf16 ones live in te_x6.h)
 #define TE_MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 #define TE_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+// the fp64 MFMA (te_f64.hip): A / B one double per lane, [row = lane & 15][k = lane >> 4]; C / D col = lane & 15,
+// row = (lane >> 4) + 4 reg -- not the row map of TE_MFMA16
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+#define TE_MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
 // A [B,H,N,D] view with D contiguous: element (b, h, n, d) at base + b sb + h sh + n sn + d, so that q / k / v inside the fused
 // qkv activation and the 'b n (h d)' layouts are read and written in place.
@@ -100,6 +104,13 @@ __device__ __forceinline__ float te_sd(float a, float b) {
   den = (den == 0.0f) ? 1e-9f : den;
   float q = a / den;
   return q * ((b != 0.0f) ? 1.0f : 0.0f);
+}
+// ... and in double (te_f64.hip), as the reference's expression evaluates on double tensors: the same four steps in fp64
+__device__ __forceinline__ double te_sd(double a, double b) {
+  double den = b + 1e-9;
+  den = (den == 0.0) ? 1e-9 : den;
+  double q = a / den;
+  return q * ((b != 0.0) ? 1.0 : 0.0);
 }
 
 // order-preserving key of the radix select (te_perturb.hip) and the radix sort (te_segmetrics.hip):

@@ -105,6 +105,11 @@ class LRP:
         ops.x6_raise_if_failed(next(self.model.parameters()).device)
 
     def _generate(self, input, index, method, is_ablation, start_layer):
+        if method == "full" and ops._is_f64(input):
+            # (refused before the forward pass: the z^B patch rule has no fp64 kernel, and no part of an fp64 map is
+            # computed in a narrower format)
+            raise ops._lib.TeError(f"{ops.DTYPES_MSG}; method='full' (the z^B patch rule) is not implemented for a "
+                                   "torch.float64 model: run it on a float32 or bfloat16 model")
         with ops.gelu_backward_plane_handoff():      # this call drives the backward pass itself (attention tensors only)
             output = self.model(input)
         kwargs = {"alpha": 1}

@@ -1,7 +1,8 @@
 """Tensor-level wrappers over the C ABI: shape/stride plumbing, output + workspace allocation.
 
-Every function takes fp32 tensors that live on one MI355X, enqueues HIP kernels on torch's current
-stream for that device and returns torch tensors (no synchronisation).  Shapes follow the reference's
+Every function takes fp32 tensors that live on one MI355X (or, on the rules of an explanation, bf16 operands with fp32
+relevance, or fp64 tensors throughout: DTYPES_MSG), enqueues HIP kernels on torch's current stream for that device and
+returns torch tensors (no synchronisation).  Shapes follow the reference's
 relprop rules; see include/te_relprop.h for the exact semantics and reference citations.
 """
 from __future__ import annotations
@@ -59,9 +60,10 @@ def _variant(v) -> int:
 
 
 # The dtypes the kernels take: fp32 everywhere; bf16 OPERANDS (activations, weights, attention gradients of a bf16 model)
-# on the rules of a ViT / DeiT or BERT explanation (variant ours, alpha = 1), with fp32 relevance (the *_bf16 paths below).
-DTYPES_MSG = ("relprop kernels take float32 tensors, or bfloat16 operands with float32 relevance on the ViT / DeiT and "
-              "BERT rules of variant 'ours' with alpha = 1")
+# on the rules of a ViT / DeiT or BERT explanation (variant ours, alpha = 1), with fp32 relevance (the *_bf16 paths below);
+# float64 everywhere -- operands AND relevance -- on the same rules (the *_f64 paths at the end of this file).
+DTYPES_MSG = ("relprop kernels take float32 tensors, or bfloat16 operands with float32 relevance, or float64 operands with "
+              "float64 relevance, the latter two on the ViT / DeiT and BERT rules of variant 'ours' with alpha = 1")
 
 
 def _prep(t: Tensor) -> Tensor:
@@ -82,6 +84,33 @@ def _prep_bf16(t: Tensor) -> Tensor:
     if not t.is_cuda:
         raise _lib.TeError("relprop kernels need tensors on the MI355X (got a CPU tensor); there is no CPU fallback")
     return t
+
+
+def _is_f64(t) -> bool:
+    if isinstance(t, Deferred):
+        t = t.t
+    return torch.is_tensor(t) and t.dtype == torch.float64
+
+
+def _any_f64(*ts) -> bool:
+    return any(_is_f64(t) for t in ts)
+
+
+def _f64_rule(variant, alpha, what, **tensors):
+    """The fp64 paths: variant ours with alpha = 1, EVERY tensor float64 (operands and relevance alike: nothing of an fp64
+    explanation is computed in a narrower format), on the MI355X.  Raises before any HIP call."""
+    var = (_VARIANTS[variant] if isinstance(variant, str) else int(variant)) & 0xff
+    if var != TE_VARIANT_OURS or alpha != 1:
+        raise _lib.TeError(f"{what} with torch.float64 operands: only variant 'ours' with alpha = 1 is implemented "
+                           f"(got variant {variant!r}, alpha {alpha}); run the model in float32 for other rules")
+    bad = {n: t.dtype for n, t in tensors.items() if t is not None and t.dtype != torch.float64}
+    if bad:
+        raise _lib.TeError(f"{DTYPES_MSG}; {what} got torch.float64 mixed with "
+                           + ", ".join(f"{n}: {d}" for n, d in bad.items())
+                           + " -- an fp64 rule takes fp64 operands and fp64 relevance only")
+    for t in tensors.values():
+        if t is not None and not t.is_cuda:
+            raise _lib.TeError("relprop kernels need tensors on the MI355X (got a CPU tensor); there is no CPU fallback")
 
 
 def _c16(t: Tensor) -> Tensor:
@@ -119,7 +148,8 @@ class _on_device:
 
     def __init__(self, t: Tensor):
         global _checked_device
-        _prep_bf16(t) if _is_bf16(t) else _prep(t)
+        if not _is_f64(t):           # (an fp64 rule has validated its tensors itself: _f64_rule)
+            _prep_bf16(t) if _is_bf16(t) else _prep(t)
         if not _checked_device:
             _lib.require_device()
             _checked_device = True
@@ -467,6 +497,8 @@ def linear_relprop(R: Tensor, X: Tensor, W: Tensor, alpha: float = 1.0, variant=
     (variant ours, alpha = 1) the Z-pass needs one product instead of two.  cache: a dict owned by the layer, where the
     bf16 operand planes of W are kept between calls (x6_weight_planes).
     bf16 X / W (a bf16 model): linear_relprop_bf16."""
+    if _any_f64(R, X, W):
+        return linear_relprop_f64(R, X, W, alpha=alpha, variant=variant)
     if _is_bf16(X) or _is_bf16(W):
         return linear_relprop_bf16(R, X, W, alpha=alpha, variant=variant, cache=cache)
     out_f, in_f = W.shape
@@ -617,6 +649,8 @@ def matmul_relprop_av(R: Tensor, attn: Tensor, v: Tensor, out_scale: float = 1.0
     Returns (cam_attn [B,H,N,N], cam_v [B,H,N,D]); cam_v is written into `cam_v_out` if given (a
     [B,H,N,D] view, e.g. a slice of the 'b n (qkv h d)' relevance buffer).  z (optional) = attn @ v as the
     forward pass computed it (self.Y of the product module).  bf16 attn / v: matmul_relprop_av_bf16."""
+    if _any_f64(R, attn, v):
+        return matmul_relprop_av_f64(R, attn, v, out_scale, cam_v_out, variant, z)
     if _is_bf16(attn) or _is_bf16(v):
         return matmul_relprop_av_bf16(R, attn, v, out_scale, cam_v_out, variant, z)
     B, H, N, D = v.shape
@@ -656,6 +690,8 @@ def matmul_relprop_qk(R: Tensor, q: Tensor, k: Tensor, out_scale: float = 1.0,
                       variant="ours", z: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """QK rule.  R [B,H,N,N]; q, k [B,H,N,D] -> (cam_q, cam_k) [B,H,N,D].  z (optional) = the UNSCALED q @ k^T as
     the forward pass computed it (self.Y of the product module).  bf16 q / k: matmul_relprop_qk_bf16."""
+    if _any_f64(R, q, k):
+        return matmul_relprop_qk_f64(R, q, k, out_scale, cam_q_out, cam_k_out, variant, z)
     if _is_bf16(q) or _is_bf16(k):
         return matmul_relprop_qk_bf16(R, q, k, out_scale, cam_q_out, cam_k_out, variant, z)
     B, H, N, D = q.shape
@@ -1037,6 +1073,8 @@ def add_relprop(R: Tensor, X0: Tensor, X1: Tensor, variant="ours", deferred: boo
     all samples), or is the BERT broadcast mask [B,1,1,N] against X0 [B,H,N,N].
     deferred=True (variant ours, same-shape operands): one streaming pass; returns two ``Deferred`` (unscaled tensor +
     per-sample factor) for clone_relprop / linear_relprop to consume.  bf16 X0 / X1: add_relprop_bf16."""
+    if _any_f64(R, X0, X1):
+        return add_relprop_f64(R, X0, X1, variant, deferred)
     if _is_bf16(X0) or _is_bf16(X1):
         return add_relprop_bf16(R, X0, X1, variant, deferred)
     B = X0.shape[0]
@@ -1094,6 +1132,8 @@ def clone_relprop(Rs: Sequence, X: Tensor) -> Tensor:
     bf16 X: te_clone_relprop(_scaled)_bf16, fp32 relevance and output."""
     if len(Rs) not in (2, 3):
         raise _lib.TeError(f"Clone.relprop supports 2 or 3 aliases, got {len(Rs)}")
+    if _any_f64(X, *Rs):
+        return clone_relprop_f64(Rs, X)
     bf = _is_bf16(X)
     X = _c16(X) if bf else _c(X)
     sfx = "bf16" if bf else "f32"
@@ -1122,7 +1162,9 @@ def clone_relprop(Rs: Sequence, X: Tensor) -> Tensor:
 
 # ---------------------------------------------------------------------------------------- a7
 def index_select_relprop(R: Tensor, X: Tensor, index: int) -> Tensor:
-    """IndexSelect.relprop for dim=1: R [B,1,C] or [B,C], X [B,N,C] -> [B,N,C] (fp32; X may be bf16)."""
+    """IndexSelect.relprop for dim=1: R [B,1,C] or [B,C], X [B,N,C] -> [B,N,C] (fp32; X may be bf16; fp64 R and X -> fp64)."""
+    if _any_f64(R, X):
+        return index_select_relprop_f64(R, X, index)
     bf = _is_bf16(X)
     X = _c16(X) if bf else _c(X)
     B, N, C = X.shape
@@ -1137,7 +1179,10 @@ def index_select_relprop(R: Tensor, X: Tensor, index: int) -> Tensor:
 
 # ---------------------------------------------------------------------------------------- a10
 def gradcam_headmean(grad: Tensor, cam: Tensor, out: Optional[Tensor] = None) -> Tensor:
-    """grad, cam [B,H,N,N] -> [B,N,N] = mean_h max(grad*cam, 0), per sample (grad may be bf16; cam and out fp32)."""
+    """grad, cam [B,H,N,N] -> [B,N,N] = mean_h max(grad*cam, 0), per sample (grad may be bf16; cam and out fp32; fp64 grad
+    and cam -> fp64)."""
+    if _any_f64(grad, cam, out):
+        return gradcam_headmean_f64(grad, cam, out)
     bf = _is_bf16(grad)
     grad, cam = (_c16(grad) if bf else _c(grad)), _c(cam)
     B, H, N, _ = cam.shape
@@ -1183,7 +1228,9 @@ USE_ROW0_CHAIN = True
 def rollout(cams: Tensor, start_layer: int = 0, normalise: bool = False, cls_fixup: bool = False,
             row0_only: bool = False) -> Tensor:
     """cams [L,B,N,N] -> joint [B,N,N] (compute_rollout_attention); row0_only=True -> joint[:, 0] as [B,N] (the only row
-    the generators read: ViT_LRP.py:369, ExplanationGenerator.py:58-59)."""
+    the generators read: ViT_LRP.py:369, ExplanationGenerator.py:58-59).  fp64 cams: rollout_f64."""
+    if _is_f64(cams):
+        return rollout_f64(cams, start_layer, normalise, cls_fixup, row0_only)
     cams = _c(cams)
     L, B, N, _ = cams.shape
     flags = (TE_ROLLOUT_NORMALISE if normalise else 0) | (TE_ROLLOUT_CLS_FIXUP if cls_fixup else 0) | \
@@ -1212,6 +1259,9 @@ def conv2d_zb_relprop(R: Tensor, X: Tensor, W: Tensor, Y: Optional[Tensor], bias
     embedding).  R [B,E,Hp,Wp] with any strides (the token-major view PatchEmbed.relprop builds is consumed in
     place), X [B,C,H,W], W [E,C,p,p], Y = the layer's forward output [B,E,Hp,Wp] -> relevance [B,C,H,W].
     bf16 X / W (a bf16 model): conv2d_zb_relprop_bf16, which reads neither Y nor the bias; `cache` keeps its weight planes."""
+    if _any_f64(R, X, W):
+        raise _lib.TeError(f"{DTYPES_MSG}; Conv2d.relprop (the z^B patch rule of method='full') has no torch.float64 "
+                           "kernel: run method='full' on a float32 or bfloat16 model")
     if _is_bf16(X) or _is_bf16(W):
         return conv2d_zb_relprop_bf16(R, X, W, cache=cache)
     B, C, H, Wd = X.shape
@@ -1665,3 +1715,206 @@ def conv2d_zb_relprop_bf16(R: Tensor, X: Tensor, W: Tensor, cache: Optional[dict
         _lib.check(lib.te_conv2d_zb_relprop_bf16(_ptr(Rt), st[0], _ptr(X), _ptr(Wc), _ptr(planes), _ptr(out), B, C, H, Wd,
                                                  E, p, _ptr(ws), ws.numel(), _stream(X)), "te_conv2d_zb_relprop_bf16")
     return out
+
+
+# ---------------------------------------------------------------------------------------- fp64 models
+# An fp64 model (model.double()) is explained in double throughout: the rules below (variant ours, alpha = 1) take fp64
+# operands AND fp64 relevance, and return fp64 (csrc/te_f64.hip; include/te_relprop.h, "fp64 operands").  One GEMM loop on
+# the fp64 MFMA serves every shape, so there is no route to choose and nothing to fall back to; Linear recomputes Z from X
+# and W (the cached forward output is an fp32 economy), the attention rules take Z from the cached product or form it with
+# torch.matmul in fp64.  A ``Deferred`` relevance is materialised first; deferred=True returns plain tensors.
+def _plain(R):
+    return R.materialise() if isinstance(R, Deferred) else R
+
+
+def _rows64(X: Tensor, K: int) -> Tuple[Tensor, int]:
+    """[..., K] fp64 tensor -> ([T, K] view, row stride), copying only if its rows are not uniformly strided."""
+    X2 = X.reshape(-1, K)
+    if X2.stride(1) != 1 or (X2.shape[0] > 1 and X2.stride(0) < K):
+        X2 = X2.contiguous()
+    return X2, (X2.stride(0) if X2.shape[0] > 1 else K)
+
+
+def _bhnd64(t: Tensor) -> Tuple[Tensor, int, int, int]:
+    if t.stride(-1) != 1 or min(t.stride()[:3]) < 0:
+        t = t.contiguous()
+    sb, sh, sn, _ = t.stride()
+    return t, sb, sh, sn
+
+
+def linear_relprop_f64(R, X: Tensor, W: Tensor, alpha: float = 1.0, variant="ours") -> Tensor:
+    """Linear.relprop in double: R [..., out], X [..., in] (a strided view is read in place), W [out, in] -> fp64 [..., in]."""
+    R = _plain(R)
+    _f64_rule(variant, alpha, "Linear.relprop", R=R, X=X, W=W)
+    out_f, in_f = W.shape
+    lead = X.shape[:-1]
+    R2, r_ld = _rows64(R, out_f)
+    X2, x_ld = _rows64(X, in_f)
+    W2, w_ld = _rows64(W, in_f)
+    T = X2.shape[0]
+    if R2.shape[0] != T:
+        raise _lib.TeError(f"Linear.relprop: R has {R2.shape[0]} rows, X has {T}")
+    out = torch.empty((T, in_f), dtype=torch.float64, device=X.device)
+    gemm = 2.0 * T * in_f * out_f
+    with _on_device(X2) as lib, _timed("linear_f64", 4.0 * gemm, 8.0 * (2 * T * in_f + 2 * in_f * out_f + 3 * T * out_f + T * in_f)):
+        ws = _ws(lib.te_linear_relprop_f64_workspace_bytes(T, in_f, out_f), X2)
+        _lib.check(lib.te_linear_relprop_f64(_ptr(R2), r_ld, _ptr(X2), x_ld, _ptr(W2), w_ld, _ptr(out), T, in_f, out_f,
+                                             _ptr(ws), ws.numel(), _stream(X2)), "te_linear_relprop_f64")
+    return out.reshape(*lead, in_f)
+
+
+def _out64(t: Optional[Tensor], shape, device, what: str) -> Tensor:
+    if t is None:
+        return torch.empty(shape, dtype=torch.float64, device=device)
+    if t.dtype != torch.float64 or t.stride(-1) != 1 or tuple(t.shape) != tuple(shape):
+        raise _lib.TeError(f"{what} must be torch.float64 {tuple(shape)} with a contiguous last dim (got {t.dtype} "
+                           f"{tuple(t.shape)})")
+    return t
+
+
+def matmul_relprop_av_f64(R: Tensor, attn: Tensor, v: Tensor, out_scale: float = 1.0, cam_v_out: Optional[Tensor] = None,
+                          variant="ours", z: Optional[Tensor] = None):
+    """AV rule in double (matmul_relprop_av): every tensor fp64; z = attn @ v as cached, else formed here in fp64."""
+    R = _plain(R)
+    z = None if z is None or tuple(z.shape) != tuple(v.shape) else z.detach()
+    _f64_rule(variant, 1.0, "the attention AV rule", R=R, attn=attn, v=v, z=z)
+    B, H, N, D = v.shape
+    if z is None:
+        z = torch.matmul(attn, v)
+    zc, z_sb, z_sh, z_sn = _bhnd64(z)
+    R, r_sb, r_sh, r_sn = _bhnd64(R)
+    v, v_sb, v_sh, v_sn = _bhnd64(v)
+    attn = attn.contiguous()
+    cam_attn = torch.empty((B, H, N, N), dtype=torch.float64, device=attn.device)
+    cam_v = _out64(cam_v_out, (B, H, N, D), attn.device, "cam_v_out")
+    cv_sb, cv_sh, cv_sn, _ = cam_v.stride()
+    with _on_device(attn) as lib, _timed("attention_av_rule_f64", 4.0 * B * H * N * N * D, 8.0 * B * H * (2 * N * N + 6 * N * D)):
+        ws = _ws(lib.te_matmul_relprop_av_f64_workspace_bytes(B, H, N, D), attn)
+        _lib.check(lib.te_matmul_relprop_av_f64(_ptr(R), r_sb, r_sh, r_sn, _ptr(attn), _ptr(v), v_sb, v_sh, v_sn, _ptr(zc),
+                                                z_sb, z_sh, z_sn, _ptr(cam_attn), _ptr(cam_v), cv_sb, cv_sh, cv_sn, B, H, N,
+                                                D, float(out_scale), _ptr(ws), ws.numel(), _stream(attn)),
+                   "te_matmul_relprop_av_f64")
+    return cam_attn, cam_v
+
+
+def matmul_relprop_qk_f64(R, q: Tensor, k: Tensor, out_scale: float = 1.0, cam_q_out: Optional[Tensor] = None,
+                          cam_k_out: Optional[Tensor] = None, variant="ours", z: Optional[Tensor] = None):
+    """QK rule in double (matmul_relprop_qk): every tensor fp64; z = the unscaled q @ k^T as cached, else formed here."""
+    R = _plain(R)
+    B, H, N, D = q.shape
+    z = None if z is None or tuple(z.shape) != (B, H, N, N) else z.detach()
+    _f64_rule(variant, 1.0, "the attention QK rule", R=R, q=q, k=k, z=z)
+    if z is None:
+        z = torch.matmul(q, k.transpose(-1, -2))
+    z, R = z.contiguous(), R.contiguous()
+    q, q_sb, q_sh, q_sn = _bhnd64(q)
+    k, k_sb, k_sh, k_sn = _bhnd64(k)
+    cam_q = _out64(cam_q_out, (B, H, N, D), q.device, "cam_q_out")
+    cam_k = _out64(cam_k_out, (B, H, N, D), q.device, "cam_k_out")
+    cq, ck = cam_q.stride(), cam_k.stride()
+    with _on_device(q) as lib, _timed("attention_qk_rule_f64", 4.0 * B * H * N * N * D, 8.0 * B * H * (4 * N * N + 6 * N * D)):
+        ws = _ws(lib.te_matmul_relprop_qk_f64_workspace_bytes(B, H, N, D), q)
+        _lib.check(lib.te_matmul_relprop_qk_f64(_ptr(R), _ptr(q), q_sb, q_sh, q_sn, _ptr(k), k_sb, k_sh, k_sn, _ptr(z),
+                                                _ptr(cam_q), cq[0], cq[1], cq[2], _ptr(cam_k), ck[0], ck[1], ck[2], B, H, N,
+                                                D, float(out_scale), _ptr(ws), ws.numel(), _stream(q)),
+                   "te_matmul_relprop_qk_f64")
+    return cam_q, cam_k
+
+
+def add_relprop_f64(R, X0: Tensor, X1: Tensor, variant="ours", deferred: bool = False):
+    """Add.relprop (ours) in double: X1 of X0's shape, of batch 1, or the BERT mask [B|1,1,1,N] against X0 [B,H,N,N].
+    Plain fp64 tensors whatever `deferred` says (there is no deferred fp64 kernel)."""
+    R = _plain(R)
+    _f64_rule(variant, 1.0, "Add.relprop", R=R, X0=X0, X1=X1)
+    B = X0.shape[0]
+    R, X0, X1 = R.contiguous(), X0.contiguous(), X1.contiguous()
+    n = X0[0].numel()
+    if R.numel() != X0.numel():
+        raise _lib.TeError("Add.relprop: relevance / input size mismatch")
+    out0 = torch.empty_like(X0)
+    if _is_bcast_mask(X0, X1):
+        H, N = X0.shape[1], X0.shape[3]
+        if X0.shape[2] != N or X1.shape[3] != N or X1.shape[0] not in (1, B):
+            raise _lib.TeError(f"Add.relprop (fp64): mask {tuple(X1.shape)} against scores {tuple(X0.shape)}: expected "
+                               "[B|1,1,1,N] and [B,H,N,N]")
+        out1 = torch.empty((B, 1, 1, N), dtype=torch.float64, device=X0.device)
+        with _on_device(X0) as lib, _timed("add_bcast_mask_f64", 0.0, 8.0 * B * (5 * H * N * N + 3 * N)):
+            ws = _ws(lib.te_add_bcast_relprop_f64_workspace_bytes(B, H, N), X0)
+            _lib.check(lib.te_add_bcast_relprop_f64(_ptr(R), _ptr(X0), _ptr(X1), N if X1.shape[0] == B and B > 1 else 0,
+                                                    _ptr(out0), _ptr(out1), B, H, N, _ptr(ws), ws.numel(), _stream(X0)),
+                       "te_add_bcast_relprop_f64")
+        return out0, out1
+    if X1.shape == X0.shape:
+        x1_bs = n
+    elif X1.shape[0] == 1 and X1.shape[1:] == X0.shape[1:]:
+        x1_bs = 0
+    else:
+        raise _lib.TeError(f"Add.relprop (fp64): unsupported operand shapes {tuple(X0.shape)} + {tuple(X1.shape)}")
+    out1 = torch.empty_like(X0)
+    with _on_device(X0) as lib, _timed("add_f64", 0.0, 8.0 * B * (7 * n + (n if x1_bs else n / B))):
+        ws = _ws(lib.te_add_relprop_f64_workspace_bytes(B, n), X0)
+        _lib.check(lib.te_add_relprop_f64(_ptr(R), _ptr(X0), _ptr(X1), _ptr(out0), _ptr(out1), B, n, x1_bs, _ptr(ws),
+                                          ws.numel(), _stream(X0)), "te_add_relprop_f64")
+    return out0, out1
+
+
+def clone_relprop_f64(Rs: Sequence, X: Tensor) -> Tensor:
+    """Clone.relprop in double: 2 or 3 fp64 relevance aliases (``Deferred`` ones are materialised) of the fp64 X."""
+    Rs = [_plain(r) for r in Rs]
+    _f64_rule("ours", 1.0, "Clone.relprop", X=X, **{f"R{i}": r for i, r in enumerate(Rs)})
+    X = X.contiguous()
+    Rs = [r.contiguous() for r in Rs]
+    for r in Rs:
+        if r.numel() != X.numel():
+            raise _lib.TeError("Clone.relprop: relevance / input size mismatch")
+    out = torch.empty_like(X)
+    with _on_device(X) as lib, _timed("clone_f64", 0.0, 8.0 * X.numel() * (len(Rs) + 2)):
+        _lib.check(lib.te_clone_relprop_f64(_ptr(Rs[0]), _ptr(Rs[1]), _ptr(Rs[2]) if len(Rs) == 3 else None, _ptr(X),
+                                            _ptr(out), X.numel(), _stream(X)), "te_clone_relprop_f64")
+    return out
+
+
+def index_select_relprop_f64(R: Tensor, X: Tensor, index: int) -> Tensor:
+    """IndexSelect.relprop (dim 1, one index) in double."""
+    _f64_rule("ours", 1.0, "IndexSelect.relprop", R=R, X=X)
+    X = X.contiguous()
+    B, N, C = X.shape
+    R = R.contiguous().reshape(B, C)
+    out = torch.empty_like(X)
+    with _on_device(X) as lib, _timed("index_select_f64", 0.0, 8.0 * (2 * X.numel() + B * C)):
+        _lib.check(lib.te_index_select_relprop_f64(_ptr(R), _ptr(X), _ptr(out), B, N, C, int(index), _stream(X)),
+                   "te_index_select_relprop_f64")
+    return out
+
+
+def gradcam_headmean_f64(grad: Tensor, cam: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """mean_h max(grad * cam, 0) in double: heads added in index order, one division."""
+    _f64_rule("ours", 1.0, "the gradient x relevance head mean", grad=grad, cam=cam, out=out)
+    grad, cam = grad.contiguous(), cam.contiguous()
+    B, H, N, _ = cam.shape
+    if out is None:
+        out = torch.empty((B, N, N), dtype=torch.float64, device=cam.device)
+    elif not out.is_contiguous() or tuple(out.shape) != (B, N, N):
+        raise _lib.TeError(f"gradcam_headmean: out must be a contiguous float64 {(B, N, N)}")
+    with _on_device(cam) as lib, _timed("headmean_f64", 0.0, 8.0 * (2 * B * H * N * N + B * N * N)):
+        _lib.check(lib.te_gradcam_headmean_f64(_ptr(grad), _ptr(cam), _ptr(out), B, H, N, _stream(cam)),
+                   "te_gradcam_headmean_f64")
+    return out
+
+
+def rollout_f64(cams: Tensor, start_layer: int = 0, normalise: bool = False, cls_fixup: bool = False,
+                row0_only: bool = False) -> Tensor:
+    """The rollout tail of an fp64 explanation: the reference's own torch expressions (ViT_LRP.py:38-49,
+    ExplanationGenerator.py:7-18,58) on the fp64 [L,B,N,N] stack -- 58 us per step in fp32, not the hot path."""
+    L, B, N, _ = cams.shape
+    eye = torch.eye(N, dtype=cams.dtype, device=cams.device).expand(B, N, N)
+    mats = [cams[i] + eye for i in range(L)]
+    if normalise:
+        mats = [m / m.sum(dim=-1, keepdim=True) for m in mats]
+    joint = mats[start_layer]
+    for i in range(start_layer + 1, L):
+        joint = mats[i].bmm(joint)
+    if cls_fixup:
+        joint = joint.clone()
+        joint[:, 0, 0] = joint[:, 0].min(dim=-1).values
+    return joint[:, 0] if row0_only else joint

@@ -416,6 +416,9 @@ def make_vit_module(L):
             """ViT_LRP.py:324-398.  cam: one-hot [B, num_classes]; returns per-sample maps."""
             if method is None:
                 method = self.default_method
+            if method == "full" and ops._is_f64(cam):       # before any rule runs: Conv2d's z^B rule has no fp64 kernel
+                raise ops._lib.TeError(f"{ops.DTYPES_MSG}; method='full' (the z^B patch rule) is not implemented for "
+                                       "torch.float64 relevance: run it on a float32 or bfloat16 model")
             prune = self.prune_below_start_layer and method in ("transformer_attribution", "grad")
             stop_at = self.blocks[start_layer].attn if prune else None
             if stop_at is not None:
