@@ -12,7 +12,9 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import methods as M
 from . import ops
+from .vit import relprop_tail
 
 
 def _one_hot(output: torch.Tensor, index) -> torch.Tensor:
@@ -69,6 +71,41 @@ def _attention_gradients(loss, attn_modules):
         m.save_attn_gradients(g)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# The tails of the two attention baselines as functions of the model with its populated caches (Baselines calls them; so
+# does LRP.generate_all, which serves them from the forward / backward pass it runs anyway).
+def cam_attn_tail(model):
+    """ViT_explanation_generator.py:57-72 on the last block's attention and attention gradient."""
+    last = model.blocks[-1].attn
+    grad = last.get_attn_gradients()
+    B, H, N, _ = grad.shape
+    side = int(round((N - 1) ** 0.5))
+    # (a bf16 model: evaluated in fp32 on its attention and gradient, like the relprop maps; a no-op for fp32)
+    cam = last.get_attention_map().detach()[:, :, 0, 1:].float().reshape(B, H, side, side)
+    g = grad[:, :, 0, 1:].float().reshape(B, H, side, side).mean(dim=[2, 3], keepdim=True)
+    cam = (cam * g).mean(1).clamp(min=0)
+    lo = cam.amin(dim=(1, 2), keepdim=True)
+    hi = cam.amax(dim=(1, 2), keepdim=True)
+    cam = (cam - lo) / (hi - lo)
+    return cam[0] if B == 1 else cam
+
+
+def attn_rollout_tail(model, start_layer=0):
+    """ViT_explanation_generator.py:76-83 on the attention probabilities of every block."""
+    stack = _headmean_stack([blk.attn.get_attention_map().detach() for blk in model.blocks])
+    joint = ops.rollout(stack, start_layer=start_layer, normalise=True)
+    return joint[:, 0, 1:]
+
+
+def _refuse_before_forward(input, wanted):
+    """The dtype refusals of the single-method calls, raised before the forward pass."""
+    if "full" in wanted and ops._is_f64(input):
+        # (refused before the forward pass: the z^B patch rule has no fp64 kernel, and no part of an fp64 map is
+        # computed in a narrower format)
+        raise ops._lib.TeError(f"{ops.DTYPES_MSG}; method='full' (the z^B patch rule) is not implemented for a "
+                               "torch.float64 model: run it on a float32 or bfloat16 model")
+
+
 class LRP:
     """baselines/ViT/ViT_explanation_generator.py:20-41.  Batched: B inputs -> B maps (B = 1 is the reference's call).
 
@@ -104,12 +141,68 @@ class LRP:
         NaN).  Synchronises the device: call it where the maps are read back anyway, never inside a step."""
         ops.x6_raise_if_failed(next(self.model.parameters()).device)
 
+    def generate_all(self, input, methods, index=None, is_ablation=False, start_layer=0):
+        """(extension) The maps of several methods of the SAME batch from one pass: ``methods`` is any subset of the
+        ``method=`` names of generate_LRP plus the two baselines as "attn_rollout" / "attn_gradcam" (served from this
+        model: ``Baselines(self.model)``); returns {name: map}, each entry the shape, dtype and bits of the single call
+        (``generate_LRP(input, index, method=name, is_ablation, start_layer)``, ``Baselines.generate_rollout(input,
+        start_layer)``, ``Baselines.generate_cam_attn(input, index)``).
+
+        One forward pass, then only what the union of the methods needs (methods.LRP_NEEDS): no backward pass and no
+        relprop for {"last_layer_attn", "attn_rollout"}, the last block's attention gradient alone for "attn_gradcam",
+        one relprop chain for all relprop methods, which "full" continues below the blocks.  ``prune`` is honoured only
+        when every requested method reads the blocks >= start_layer alone (methods.prunable); ``overlap_backward``, the
+        x6 status poll / post and the GELU-backward plane hand-off behave as in generate_LRP.  An unknown name raises
+        ValueError, the dtype refusals of the single calls raise their TeError, both before the forward pass."""
+        wanted = M.check(methods, M.LRP_NEEDS)
+        _refuse_before_forward(input, wanted)
+        if input.dtype == torch.float16:
+            raise ops._lib.TeError(f"{ops.DTYPES_MSG}; got {input.dtype} here")
+        if input.is_cuda:
+            ops.x6_poll(input.device)
+        out = self._generate_all(input, wanted, index, is_ablation, start_layer)
+        if input.is_cuda:
+            ops.x6_post(input.device)
+        return out
+
+    def _generate_all(self, input, wanted, index, is_ablation, start_layer):
+        need = M.needs(wanted, M.LRP_NEEDS, is_ablation, M.LRP_ABLATION_NEEDS)
+        model = self.model
+        with ops.gelu_backward_plane_handoff():      # this call drives the backward pass itself (attention tensors only)
+            output = model(input)
+        ours = tuple(m for m in wanted if m not in M.BASELINE_METHODS)       # the tails of model.relprop
+        maps = {}
+        if not need.forward_only:
+            kwargs = {"alpha": 1}
+            one_hot = _one_hot(output, index)
+            loss = torch.sum(one_hot * output)
+            # as in _generate: the flag is set for THIS call only
+            user_flag = model.prune_below_start_layer
+            pruned = bool((self.prune or user_flag) and need.relprop and M.prunable(wanted, M.LRP_NEEDS))
+            model.prune_below_start_layer = pruned
+            blocks = list(model.blocks)
+            grad_blocks = blocks[start_layer if pruned else 0:] if need.all_grads else blocks[-1:] if need.last_grad else []
+            try:
+                if need.relprop and self.overlap_backward and input.is_cuda:
+                    maps = self._relprop_beside_backward(loss, one_hot, ours, is_ablation, start_layer, kwargs, grad_blocks)
+                else:
+                    if grad_blocks:
+                        _attention_gradients(loss, [blk.attn for blk in grad_blocks])
+                    if need.relprop:
+                        maps = model.relprop(one_hot, method=ours, is_ablation=is_ablation, start_layer=start_layer,
+                                             **kwargs)
+            finally:
+                model.prune_below_start_layer = user_flag
+        if not need.relprop:                         # ("last_layer_attn": the forward pass has produced all it reads)
+            maps = {m: relprop_tail(model, m, None, is_ablation, start_layer) for m in ours}
+        if "attn_rollout" in wanted:
+            maps["attn_rollout"] = attn_rollout_tail(model, start_layer)
+        if "attn_gradcam" in wanted:
+            maps["attn_gradcam"] = cam_attn_tail(model)
+        return {m: maps[m] for m in wanted}
+
     def _generate(self, input, index, method, is_ablation, start_layer):
-        if method == "full" and ops._is_f64(input):
-            # (refused before the forward pass: the z^B patch rule has no fp64 kernel, and no part of an fp64 map is
-            # computed in a narrower format)
-            raise ops._lib.TeError(f"{ops.DTYPES_MSG}; method='full' (the z^B patch rule) is not implemented for a "
-                                   "torch.float64 model: run it on a float32 or bfloat16 model")
+        _refuse_before_forward(input, (method,))
         with ops.gelu_backward_plane_handoff():      # this call drives the backward pass itself (attention tensors only)
             output = self.model(input)
         kwargs = {"alpha": 1}
@@ -138,7 +231,8 @@ class LRP:
         side = self._relprop_stream
         side.wait_stream(main)                      # forward caches + one-hot are complete
         # backward on the main stream (autograd runs each node on its forward op's stream)
-        _attention_gradients(loss, [blk.attn for blk in grad_blocks])
+        if grad_blocks:
+            _attention_gradients(loss, [blk.attn for blk in grad_blocks])
         grads_ready = main.record_event()
         self.model._before_tail = lambda: torch.cuda.current_stream(dev).wait_event(grads_ready)
         try:
@@ -148,8 +242,10 @@ class LRP:
         finally:
             self.model._before_tail = None
         main.wait_stream(side)
-        if out is not None and not torch.cuda.is_current_stream_capturing():
-            out.record_stream(main)
+        if not torch.cuda.is_current_stream_capturing():
+            for t in (out.values() if isinstance(out, dict) else (out,)):     # (generate_all: a dict of maps)
+                if t is not None:
+                    t.record_stream(main)
         return out
 
 
@@ -167,26 +263,14 @@ class Baselines:
         with ops.gelu_backward_plane_handoff():      # this call drives the backward pass itself (attention tensors only)
             output = self.model(input, register_hook=True)
         one_hot = _one_hot(output, index)
-        last = self.model.blocks[-1].attn
-        (grad,) = torch.autograd.grad(torch.sum(one_hot * output), [last.get_attention_map()])
-        last.save_attn_gradients(grad)
-        B, H, N, _ = grad.shape
-        side = int(round((N - 1) ** 0.5))
-        # (a bf16 model: evaluated in fp32 on its attention and gradient, like the relprop maps; a no-op for fp32)
-        cam = last.get_attention_map().detach()[:, :, 0, 1:].float().reshape(B, H, side, side)
-        g = grad[:, :, 0, 1:].float().reshape(B, H, side, side).mean(dim=[2, 3], keepdim=True)
-        cam = (cam * g).mean(1).clamp(min=0)
-        lo = cam.amin(dim=(1, 2), keepdim=True)
-        hi = cam.amax(dim=(1, 2), keepdim=True)
-        cam = (cam - lo) / (hi - lo)
-        return cam[0] if B == 1 else cam
+        # (the last block's gradient only; through the driver, so that a block on the producer kernels is served too)
+        _attention_gradients(torch.sum(one_hot * output), [self.model.blocks[-1].attn])
+        return cam_attn_tail(self.model)
 
     def generate_rollout(self, input, start_layer=0):
         """attention rollout (:74-83): head-averaged attention, identity added, rows normalised, chained."""
         self.model(input)
-        stack = _headmean_stack([blk.attn.get_attention_map().detach() for blk in self.model.blocks])
-        joint = ops.rollout(stack, start_layer=start_layer, normalise=True)
-        return joint[:, 0, 1:]
+        return attn_rollout_tail(self.model, start_layer)
 
 
 def _jet_bgr(mask01: np.ndarray) -> np.ndarray:
@@ -325,30 +409,46 @@ class Generator:
 
     def _explain(self, input_ids, attention_mask, index, lowest_layer=0):
         """forward, attention-gradient backward, relprop.  With prune=True only the layers >= lowest_layer are served."""
+        return self._pass(input_ids, attention_mask, index, lowest_layer)[0]
+
+    def _pass(self, input_ids, attention_mask, index, lowest_layer=0, grads="all", relprop=True, prune=None):
+        """One pass: forward; the attention gradients of ``grads`` ("all": the layers served, "last": the last layer
+        alone, None: no backward pass); the relprop chain if ``relprop``.  prune (default: self.prune): only the layers
+        >= lowest_layer are served.  -> (the encoder layers, what model.relprop returned or None)."""
         from .rules import StopRelprop
+        prune = self.prune if prune is None else bool(prune)
+        layers = self.model.bert.encoder.layer
+        if grads is None and not relprop:            # forward only: as generate_attn_last_layer / generate_rollout
+            with torch.no_grad():
+                self.model(input_ids=input_ids, attention_mask=attention_mask)
+            return layers, None
         with ops.gelu_backward_plane_handoff():      # this call drives the backward pass itself (attention tensors only)
             output = self.model(input_ids=input_ids, attention_mask=attention_mask)[0]
         one_hot = _one_hot(output, index)
         loss = torch.sum(one_hot * output)
-        layers = self.model.bert.encoder.layer
-        first = lowest_layer if self.prune else 0
+        first = lowest_layer if prune else 0
         side = main = None
-        if self.overlap_backward and one_hot.is_cuda:
+        if relprop and self.overlap_backward and one_hot.is_cuda:
             main = torch.cuda.current_stream(one_hot.device)
             if self._relprop_stream is None:
                 self._relprop_stream = torch.cuda.Stream(device=one_hot.device)
             side = self._relprop_stream
             side.wait_stream(main)                  # forward caches + one-hot are complete
-        _attention_gradients(loss, [lay.attention.self for lay in list(layers)[first:]])      # main stream
-        stop_at = layers[first].attention.self if self.prune else None
+        grad_layers = list(layers)[first:] if grads == "all" else list(layers)[-1:] if grads == "last" else []
+        if grad_layers:
+            _attention_gradients(loss, [lay.attention.self for lay in grad_layers])      # main stream
+        if not relprop:
+            return layers, None
+        stop_at = layers[first].attention.self if prune else None
         if stop_at is not None:
             stop_at._stop_after_attn_cam = True
+        cam = None
         try:
             if side is not None:
                 with torch.cuda.stream(side):
-                    self.model.relprop(one_hot, alpha=1)
+                    cam = self.model.relprop(one_hot, alpha=1)
             else:
-                self.model.relprop(one_hot, alpha=1)
+                cam = self.model.relprop(one_hot, alpha=1)
         except StopRelprop:
             pass
         finally:
@@ -356,7 +456,38 @@ class Generator:
                 stop_at._stop_after_attn_cam = False
             if side is not None:
                 main.wait_stream(side)              # the tail (head-mean, rollout) reads both streams' results
-        return layers
+        if cam is not None and side is not None and not torch.cuda.is_current_stream_capturing():
+            cam.record_stream(main)
+        return layers, cam
+
+    def generate_all(self, input_ids, attention_mask, methods, index=None, start_layer=11, rollout_start_layer=0):
+        """(extension) The vectors of several methods of the SAME batch from one pass: ``methods`` is any subset of
+        "LRP", "LRP_last_layer", "full_lrp", "attn_last_layer", "rollout", "attn_gradcam" (the generate_* methods);
+        returns {name: vector}, each entry the shape, dtype and bits of the single call (generate_LRP with
+        ``start_layer``, generate_rollout with ``rollout_start_layer``).  One forward pass and at most one backward
+        pass and one relprop chain, only as far as the union of the methods needs (methods.GENERATOR_NEEDS); "full_lrp"
+        keeps what model.relprop returns.  ``prune`` is honoured only when every requested method reads the layers it
+        serves alone (methods.prunable).  An unknown name raises ValueError before the forward pass."""
+        wanted = M.check(methods, M.GENERATOR_NEEDS)
+        need = M.needs(wanted, M.GENERATOR_NEEDS)
+        if input_ids.is_cuda:
+            ops.x6_poll(input_ids.device)        # a lost x6 hand-over of an earlier call: raised once, no synchronisation
+        n_layers = len(self.model.bert.encoder.layer)
+        pruned = bool(self.prune and M.prunable(wanted, M.GENERATOR_NEEDS))
+        lowest = start_layer if "LRP" in wanted else n_layers - 1
+        _, cam = self._pass(input_ids, attention_mask, index, lowest_layer=lowest,
+                            grads="all" if need.all_grads else "last" if need.last_grad else None,
+                            relprop=need.relprop, prune=pruned)
+        tails = {"LRP": lambda: lrp_tail(self.model, start_layer, pruned),
+                 "LRP_last_layer": lambda: lrp_last_layer_tail(self.model),
+                 "full_lrp": lambda: full_lrp_tail(cam),
+                 "attn_last_layer": lambda: attn_last_layer_tail(self.model),
+                 "rollout": lambda: rollout_tail(self.model, rollout_start_layer),
+                 "attn_gradcam": lambda: attn_gradcam_tail(self.model)}
+        out = {m: tails[m]() for m in wanted}
+        if input_ids.is_cuda:
+            ops.x6_post(input_ids.device)
+        return out
 
     def generate_LRP(self, input_ids, attention_mask, index=None, start_layer=11):
         if input_ids.is_cuda:
@@ -369,23 +500,12 @@ class Generator:
 
     def attribution_tail(self, start_layer=11):
         """ExplanationGenerator.py:47-59 on the attn_cam / attention gradients cached by relprop + backward."""
-        layers = self.model.bert.encoder.layer
-        first = layers[-1].attention.self.get_attn_cam()
-        B, _, N, _ = first.shape
-        stack = torch.empty((len(layers), B, N, N), dtype=first.dtype, device=first.device)
-        for i, lay in enumerate(layers):
-            sa = lay.attention.self
-            if i >= start_layer or not self.prune:            # (the rollout reads layers >= start_layer only)
-                ops.gradcam_headmean(sa.get_attn_gradients(), sa.get_attn_cam(), out=stack[i])
-        # ExplanationGenerator.py:7-18 (row-normalised rollout) + :58 (CLS fix-up) -> row 0
-        return ops.rollout(stack, start_layer=start_layer, normalise=True, cls_fixup=True, row0_only=True)
+        return lrp_tail(self.model, start_layer, self.prune)
 
     def generate_LRP_last_layer(self, input_ids, attention_mask, index=None):
         """ExplanationGenerator.py:62-84: head-mean of the last layer's attn_cam, CLS row, CLS slot zeroed."""
-        layers = self._explain(input_ids, attention_mask, index, lowest_layer=len(self.model.bert.encoder.layer) - 1)
-        cam = layers[-1].attention.self.get_attn_cam().clamp(min=0).mean(dim=1)[:, 0].clone()
-        cam[:, 0] = 0
-        return cam
+        self._explain(input_ids, attention_mask, index, lowest_layer=len(self.model.bert.encoder.layer) - 1)
+        return lrp_last_layer_tail(self.model)
 
     def generate_full_lrp(self, input_ids, attention_mask, index=None):
         """ExplanationGenerator.py:86-106: relevance propagated to the encoder input, summed over the hidden
@@ -397,43 +517,86 @@ class Generator:
         # relprop reads the attention gradients nowhere, but the reference runs the backward first (:100-101) and the
         # accessors are part of the boundary: keep them populated
         _attention_gradients(torch.sum(one_hot * output), [lay.attention.self for lay in layers])
-        cam = self.model.relprop(one_hot, alpha=1).sum(dim=2)
-        cam[:, 0] = 0
-        return cam
+        return full_lrp_tail(self.model.relprop(one_hot, alpha=1))
 
     def generate_attn_last_layer(self, input_ids, attention_mask, index=None):
         """ExplanationGenerator.py:108-114: head-mean of the last layer's attention probabilities, CLS row."""
         with torch.no_grad():
             self.model(input_ids=input_ids, attention_mask=attention_mask)
-            attn = self.model.bert.encoder.layer[-1].attention.self.get_attn()
-            if ops._is_bf16(attn):           # fp32 map of a bf16 model: the class-token row's head mean, summed in fp32
-                cam = ops.attn_headmean(attn, row0=True)
-            else:
-                cam = attn.mean(dim=1)[:, 0].clone()
-        cam[:, 0] = 0
-        return cam
+        return attn_last_layer_tail(self.model)
 
     def generate_rollout(self, input_ids, attention_mask, start_layer=0, index=None):
         """ExplanationGenerator.py:116-127: row-normalised rollout of the head-averaged attention probabilities."""
         with torch.no_grad():
             self.model(input_ids=input_ids, attention_mask=attention_mask)
-            stack = _headmean_stack([lay.attention.self.get_attn() for lay in self.model.bert.encoder.layer])
-            joint = ops.rollout(stack, start_layer=start_layer, normalise=True)
-        out = joint[:, 0].clone()
-        out[:, 0] = 0
-        return out
+        return rollout_tail(self.model, start_layer)
 
     def generate_attn_gradcam(self, input_ids, attention_mask, index=None):
         """ExplanationGenerator.py:129-155: last layer's attention x its per-head mean gradient, head-mean, clamped,
         min-max normalised over the whole [N, N] map, CLS row with the CLS slot zeroed."""
-        layers = self._explain(input_ids, attention_mask, index, lowest_layer=len(self.model.bert.encoder.layer) - 1)
-        sa = layers[-1].attention.self
-        # (a bf16 model: evaluated in fp32 on its attention and gradient, like the relprop maps; a no-op for fp32)
-        cam = sa.get_attn().detach().float()
-        grad = sa.get_attn_gradients().float().mean(dim=[2, 3], keepdim=True)
-        cam = (cam * grad).mean(dim=1).clamp(min=0)
-        lo = cam.amin(dim=(1, 2), keepdim=True)
-        hi = cam.amax(dim=(1, 2), keepdim=True)
-        cam = ((cam - lo) / (hi - lo))[:, 0].clone()
-        cam[:, 0] = 0
-        return cam
+        self._explain(input_ids, attention_mask, index, lowest_layer=len(self.model.bert.encoder.layer) - 1)
+        return attn_gradcam_tail(self.model)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The tails of the Generator methods as functions of the BERT model with its populated caches (the generate_* methods
+# call them; Generator.generate_all serves several from one pass).
+def lrp_tail(model, start_layer=11, pruned=False):
+    """ExplanationGenerator.py:47-59 on the attn_cam / attention gradients cached by relprop + backward.  pruned: the
+    pass served the layers >= start_layer only."""
+    layers = model.bert.encoder.layer
+    first = layers[-1].attention.self.get_attn_cam()
+    B, _, N, _ = first.shape
+    stack = torch.empty((len(layers), B, N, N), dtype=first.dtype, device=first.device)
+    for i, lay in enumerate(layers):
+        sa = lay.attention.self
+        if i >= start_layer or not pruned:            # (the rollout reads layers >= start_layer only)
+            ops.gradcam_headmean(sa.get_attn_gradients(), sa.get_attn_cam(), out=stack[i])
+    # ExplanationGenerator.py:7-18 (row-normalised rollout) + :58 (CLS fix-up) -> row 0
+    return ops.rollout(stack, start_layer=start_layer, normalise=True, cls_fixup=True, row0_only=True)
+
+
+def lrp_last_layer_tail(model):
+    cam = model.bert.encoder.layer[-1].attention.self.get_attn_cam().clamp(min=0).mean(dim=1)[:, 0].clone()
+    cam[:, 0] = 0
+    return cam
+
+
+def full_lrp_tail(cam):
+    """``cam``: what model.relprop returned (the relevance of the encoder input)."""
+    cam = cam.sum(dim=2)
+    cam[:, 0] = 0
+    return cam
+
+
+def attn_last_layer_tail(model):
+    with torch.no_grad():
+        attn = model.bert.encoder.layer[-1].attention.self.get_attn()
+        if ops._is_bf16(attn):           # fp32 map of a bf16 model: the class-token row's head mean, summed in fp32
+            cam = ops.attn_headmean(attn, row0=True)
+        else:
+            cam = attn.mean(dim=1)[:, 0].clone()
+    cam[:, 0] = 0
+    return cam
+
+
+def rollout_tail(model, start_layer=0):
+    with torch.no_grad():
+        stack = _headmean_stack([lay.attention.self.get_attn() for lay in model.bert.encoder.layer])
+        joint = ops.rollout(stack, start_layer=start_layer, normalise=True)
+    out = joint[:, 0].clone()
+    out[:, 0] = 0
+    return out
+
+
+def attn_gradcam_tail(model):
+    sa = model.bert.encoder.layer[-1].attention.self
+    # (a bf16 model: evaluated in fp32 on its attention and gradient, like the relprop maps; a no-op for fp32)
+    cam = sa.get_attn().detach().float()
+    grad = sa.get_attn_gradients().float().mean(dim=[2, 3], keepdim=True)
+    cam = (cam * grad).mean(dim=1).clamp(min=0)
+    lo = cam.amin(dim=(1, 2), keepdim=True)
+    hi = cam.amax(dim=(1, 2), keepdim=True)
+    cam = ((cam - lo) / (hi - lo))[:, 0].clone()
+    cam[:, 0] = 0
+    return cam

@@ -283,6 +283,18 @@ class RationaleEvaluator:
         scores = self.explain(input_ids, attention_mask, index).detach()
         return self.update_from_scores(scores, word_ids, truth, truth_total, input_ids, attention_mask)
 
+    @staticmethod
+    def update_all(evaluators, generator, input_ids, attention_mask, word_ids, truth, truth_total=None, index=None,
+                   start_layer=11, rollout_start_layer=0):
+        """One batch for SEVERAL methods: ``evaluators`` = {Generator.generate_all name: RationaleEvaluator}; ONE
+        ``generator.generate_all`` serves every method's relevance (one forward pass, at most one backward pass and one
+        relprop chain), then each evaluator's ``update_from_scores`` runs as in ``update``.  The faithfulness forwards
+        stay per method: the erased inputs differ.  -> {name: what update returns}."""
+        scores = generator.generate_all(input_ids, attention_mask, tuple(evaluators), index=index,
+                                        start_layer=start_layer, rollout_start_layer=rollout_start_layer)
+        return {name: ev.update_from_scores(scores[name].detach(), word_ids, truth, truth_total, input_ids, attention_mask)
+                for name, ev in evaluators.items()}
+
     @torch.no_grad()
     def update_from_scores(self, scores, word_ids, truth, truth_total=None, input_ids=None, attention_mask=None):
         scores = scores.float()

@@ -226,6 +226,122 @@ class SaliencySweep:
         return store
 
 
+# SaliencySweepAll: sweep method -> (the generator object it runs on, its generate_all name).  lrp / transformer_attribution
+# are the SAME call (generate_visualizations.py:70-75 reach the same branch of relprop): computed once, stored twice.
+_ALL_ON_LRP = {"lrp": "transformer_attribution", "transformer_attribution": "transformer_attribution",
+               "attn_last_layer": "last_layer_attn"}
+_ALL_ON_BASELINES = {"rollout": "attn_rollout", "attn_gradcam": "attn_gradcam"}
+_ALL_ON_ORIG = {"full_lrp": "full", "lrp_last_layer": "last_layer"}
+
+
+class SaliencySweepAll:
+    """``SaliencySweep`` for SEVERAL methods over the same batches: one pass per model object instead of one per method
+    (LRP.generate_all), every method's maps bit for bit what ``SaliencySweep(method)`` stores.
+
+    Methods are grouped by the MODEL OBJECT they run on:
+      * lrp, transformer_attribution, attn_last_layer run on ``lrp.model`` -- and so do rollout and attn_gradcam when
+        ``baselines.model is lrp.model`` (the two baselines are then tails of the same forward / backward pass);
+      * full_lrp and lrp_last_layer share one pass on ``orig_lrp.model``;
+      * a ``baselines`` built on ANOTHER model object (the reference builds it on the hook-only ViT_new model,
+        generate_visualizations.py:172-183) keeps its own passes, one per baseline method: different weights or a
+        different module tree give different maps, so nothing may be shared.  That is correct, not a missed saving.
+    Only the generator objects the requested methods need must be given; a missing one raises ValueError here."""
+
+    def __init__(self, methods, lrp=None, orig_lrp=None, baselines=None, vis_class="top", is_ablation=False, device=None):
+        methods = tuple(dict.fromkeys(methods))
+        bad = [m for m in methods if m not in METHODS]
+        if bad or not methods:
+            raise ValueError(f"methods must be a non-empty subset of {METHODS}, got {bad or methods}")
+        self.methods, self.vis_class, self.is_ablation = methods, vis_class, bool(is_ablation)
+        self.lrp, self.orig_lrp, self.baselines, self.device = lrp, orig_lrp, baselines, device
+        self.groups = self._group()
+
+    def _group(self):
+        """[(kind, generator, {sweep method: generate_all name})], kind in "lrp" / "orig_lrp" / "baselines" (the last:
+        one Baselines call per method)."""
+        shared = self.baselines is not None and self.lrp is not None and self.baselines.model is self.lrp.model
+        on_lrp, on_orig, on_base = {}, {}, {}
+        for m in self.methods:
+            if m in _ALL_ON_LRP:
+                on_lrp[m] = _ALL_ON_LRP[m]
+            elif m in _ALL_ON_ORIG:
+                on_orig[m] = _ALL_ON_ORIG[m]
+            elif shared:
+                on_lrp[m] = _ALL_ON_BASELINES[m]
+            else:
+                on_base[m] = _ALL_ON_BASELINES[m]
+        groups = []
+        for kind, gen, names in (("lrp", self.lrp, on_lrp), ("orig_lrp", self.orig_lrp, on_orig),
+                                 ("baselines", self.baselines, on_base)):
+            if names and gen is None:
+                raise ValueError(f"the methods {tuple(names)} run on ``{kind}``, which was not given")
+            if names:
+                groups.append((kind, gen, names))
+        return groups
+
+    @staticmethod
+    def _to_model_dtype(data, gen, kind, names):
+        """As SaliencySweep._to_model_dtype: the batch in the dtype of the model of this group."""
+        par = next(gen.model.parameters(), None)
+        if par is None or not par.is_floating_point() or par.dtype == data.dtype:
+            return data
+        if par.dtype == torch.bfloat16 and kind == "orig_lrp":
+            ops._bf16_rule("lrp", 1.0, f"the sweep methods {tuple(names)} (the lrp rule library)")
+        return data.to(par.dtype)
+
+    def explain(self, data, target=None):
+        """One batch of normalised images -> {method: min-max normalised maps [B,1,H,W] at image resolution}."""
+        index = target if self.vis_class == "target" else None
+        B, H = data.shape[0], data.shape[-1]
+        out = {}
+        for kind, gen, names in self.groups:
+            x = self._to_model_dtype(data, gen, kind, names)
+            if kind == "lrp":
+                res = gen.generate_all(x, tuple(dict.fromkeys(names.values())), index=index, start_layer=1)
+            elif kind == "orig_lrp":
+                res = gen.generate_all(x, tuple(dict.fromkeys(names.values())), index=index,
+                                       is_ablation=self.is_ablation)
+            else:
+                res = {}
+                if "rollout" in names:
+                    res["attn_rollout"] = gen.generate_rollout(x, start_layer=1)
+                if "attn_gradcam" in names:
+                    res["attn_gradcam"] = gen.generate_cam_attn(x, index=index)
+            heats = {}
+            for m, name in names.items():
+                if name not in heats:                # (lrp / transformer_attribution: one map, one heat map, two stores)
+                    heats[name] = _heat(res[name], B, H)
+                out[m] = heats[name]
+        return {m: out[m] for m in self.methods}
+
+    def run(self, loader_batches, stores, rank=0, world=1):
+        """loader_batches as SaliencySweep.run; stores: {method: ResultsStore}, one per requested method."""
+        missing = [m for m in self.methods if m not in stores]
+        if missing:
+            raise ValueError(f"no store for the methods {missing}")
+        for data, target in loader_batches:
+            dev = self.device if self.device is not None else data.device
+            vis = self.explain(normalize(data.to(dev)), target.to(dev))
+            cuda = [v for v in vis.values() if torch.is_tensor(v) and v.is_cuda]
+            if cuda:
+                # as SaliencySweep.run: the x6 status is checked BEFORE any append, so a failed batch is written to and
+                # counted in no store
+                ops.x6_raise_if_failed(cuda[0].device)
+            for m in self.methods:
+                stores[m].append(data, target, vis[m])
+        return stores
+
+
+def _heat(res, B, H):
+    """generate_visualizations.py:95-97 on the patch-level (or, full_lrp, pixel-level) maps of one batch."""
+    res = res.detach().reshape(B, -1)
+    g = int(round(res.shape[1] ** 0.5))
+    if g == H:                                   # full_lrp is already at pixel resolution (:95): min-max only
+        lo, hi = res.amin(dim=1, keepdim=True), res.amax(dim=1, keepdim=True)
+        return ((res - lo) / (hi - lo)).reshape(B, 1, H, H)
+    return ops.heatmap(res, scale=H // g, normalise=True)   # :96-97: bilinear x16 + min-max, one launch
+
+
 def shard_batches(dataset, batch_size, rank=0, world=1):
     """The rank's contiguous block of ``dataset`` (items (image, target)) in batches, plus its [lo, hi)."""
     lo, hi = parallel.shard_range(len(dataset), rank, world)

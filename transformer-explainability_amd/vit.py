@@ -18,7 +18,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import ops, producers
+from . import methods, ops, producers
 from . import rules as R_ours
 
 __all__ = ["VisionTransformer", "vit_base_patch16_224", "vit_large_patch16_224", "deit_base_patch16_224",
@@ -28,6 +28,65 @@ __all__ = ["VisionTransformer", "vit_base_patch16_224", "vit_large_patch16_224",
 def compute_rollout_attention(all_layer_matrices, start_layer=0):
     """ViT_LRP.py:38-49 (identity added, NO row normalisation).  list of L [B,N,N] -> [B,N,N]."""
     return ops.rollout(torch.stack(list(all_layer_matrices), 0), start_layer=start_layer, normalise=False)
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# The per-method tails of VisionTransformer.relprop (ViT_LRP.py:337-398) as functions of the model with its populated
+# caches: ``model.relprop`` calls them, and one relprop chain can serve several of them (methods.py says what each reads).
+def tail_full(model, cam, **kwargs):
+    """ViT_LRP.py:337-343: position-embedding Add, drop the class token, z^B rule of the patch embedding, sum over the
+    colour channels -> [B, H, W].  ``cam``: the relevance the chain returned below block 0."""
+    cam, _ = model.add.relprop(cam, **kwargs)
+    cam = model.patch_embed.relprop(cam[:, 1:], **kwargs)
+    return cam.sum(dim=1)
+
+
+def tail_rollout(model, start_layer=0):
+    mats = [blk.attn.get_attn_cam().clamp(min=0).mean(dim=1) for blk in model.blocks]
+    return compute_rollout_attention(mats, start_layer=start_layer)[:, 0, 1:]
+
+
+def tail_attribution(model, start_layer=0, pruned=False):
+    """ViT_LRP.py:357-369: per block mean_h max(grad * attn_cam, 0), then rollout, row 0.  pruned: the chain and the
+    backward pass stopped at block start_layer, the blocks below hold nothing current."""
+    first = model.blocks[-1].attn.get_attn_cam()
+    Bn, _, N, _ = first.shape
+    stack = torch.empty((len(model.blocks), Bn, N, N), dtype=first.dtype, device=first.device)
+    for i, blk in enumerate(model.blocks):
+        if i >= start_layer or not pruned:       # (the rollout reads layers >= start_layer only)
+            ops.gradcam_headmean(blk.attn.get_attn_gradients(), blk.attn.get_attn_cam(), out=stack[i])
+    return ops.rollout(stack, start_layer=start_layer, normalise=False, row0_only=True)[:, 1:]
+
+
+def tail_layer(model, method, is_ablation=False):
+    blk = model.blocks[-1] if method == "last_layer" else model.blocks[1]
+    c = blk.attn.get_attn_cam()
+    if is_ablation:
+        c = blk.attn.get_attn_gradients() * c
+    return c.clamp(min=0).mean(dim=1)[:, 0, 1:]
+
+
+def tail_last_layer_attn(model):
+    attn = model.blocks[-1].attn.get_attn()
+    if ops._is_bf16(attn):       # fp32 map of a bf16 model: clamp, then the head mean summed in fp32
+        return ops.attn_headmean(attn.detach(), clamp=True, row0=True)[:, 1:]
+    return attn.clamp(min=0).mean(dim=1)[:, 0, 1:]
+
+
+def relprop_tail(model, method, cam=None, is_ablation=False, start_layer=0, pruned=False, **kwargs):
+    """The map of ``method`` from the caches a forward pass, the backward pass and the relprop chain left on ``model``
+    (``cam``: what the chain returned; only "full" reads it)."""
+    if method == "full":
+        return tail_full(model, cam, **kwargs)
+    if method == "rollout":
+        return tail_rollout(model, start_layer)
+    if method in ("transformer_attribution", "grad"):
+        return tail_attribution(model, start_layer, pruned)
+    if method in ("last_layer", "second_layer"):
+        return tail_layer(model, method, is_ablation)
+    if method == "last_layer_attn":
+        return tail_last_layer_attn(model)
+    return None   # unknown method: the reference falls through silently
 
 
 def _trunc_normal_(t, std=.02):
@@ -413,13 +472,20 @@ def make_vit_module(L):
 
         # ------------------------------------------------------------------------------------------
         def relprop(self, cam=None, method=None, is_ablation=False, start_layer=0, **kwargs):
-            """ViT_LRP.py:324-398.  cam: one-hot [B, num_classes]; returns per-sample maps."""
+            """ViT_LRP.py:324-398.  cam: one-hot [B, num_classes]; returns per-sample maps.
+            (extension) ``method`` may be a tuple / list of names: ONE chain then serves every tail and the result is a
+            dict name -> map, each entry what the single-method call returns (LRP.generate_all)."""
             if method is None:
                 method = self.default_method
-            if method == "full" and ops._is_f64(cam):       # before any rule runs: Conv2d's z^B rule has no fp64 kernel
+            several = not isinstance(method, str)
+            wanted = tuple(method) if several else (method,)
+            if "full" in wanted and ops._is_f64(cam):       # before any rule runs: Conv2d's z^B rule has no fp64 kernel
                 raise ops._lib.TeError(f"{ops.DTYPES_MSG}; method='full' (the z^B patch rule) is not implemented for "
                                        "torch.float64 relevance: run it on a float32 or bfloat16 model")
-            prune = self.prune_below_start_layer and method in ("transformer_attribution", "grad")
+            if several:     # the prune rule of methods.py: every requested tail reads the blocks >= start_layer alone
+                prune = self.prune_below_start_layer and methods.prunable(wanted, methods.LRP_NEEDS)
+            else:
+                prune = self.prune_below_start_layer and method in ("transformer_attribution", "grad")
             stop_at = self.blocks[start_layer].attn if prune else None
             if stop_at is not None:
                 stop_at._stop_after_attn_cam = True
@@ -446,40 +512,8 @@ def make_vit_module(L):
             if hook is not None:
                 hook()
 
-            if method == "full":
-                # ViT_LRP.py:337-343: position-embedding Add, drop the class token, z^B rule of the patch
-                # embedding, sum over the colour channels -> [B, H, W]
-                cam, _ = self.add.relprop(cam, **kwargs)
-                cam = self.patch_embed.relprop(cam[:, 1:], **kwargs)
-                return cam.sum(dim=1)
-
-            if method == "rollout":
-                mats = [blk.attn.get_attn_cam().clamp(min=0).mean(dim=1) for blk in self.blocks]
-                return compute_rollout_attention(mats, start_layer=start_layer)[:, 0, 1:]
-
-            if method in ("transformer_attribution", "grad"):
-                # ViT_LRP.py:357-369: per block mean_h max(grad * attn_cam, 0), then rollout, row 0
-                first = self.blocks[-1].attn.get_attn_cam()
-                Bn, _, N, _ = first.shape
-                stack = torch.empty((len(self.blocks), Bn, N, N), dtype=first.dtype, device=first.device)
-                for i, blk in enumerate(self.blocks):
-                    if i >= start_layer or not prune:       # (the rollout reads layers >= start_layer only)
-                        ops.gradcam_headmean(blk.attn.get_attn_gradients(), blk.attn.get_attn_cam(), out=stack[i])
-                return ops.rollout(stack, start_layer=start_layer, normalise=False, row0_only=True)[:, 1:]
-
-            if method in ("last_layer", "second_layer"):
-                blk = self.blocks[-1] if method == "last_layer" else self.blocks[1]
-                c = blk.attn.get_attn_cam()
-                if is_ablation:
-                    c = blk.attn.get_attn_gradients() * c
-                return c.clamp(min=0).mean(dim=1)[:, 0, 1:]
-
-            if method == "last_layer_attn":
-                attn = self.blocks[-1].attn.get_attn()
-                if ops._is_bf16(attn):       # fp32 map of a bf16 model: clamp, then the head mean summed in fp32
-                    return ops.attn_headmean(attn.detach(), clamp=True, row0=True)[:, 1:]
-                return attn.clamp(min=0).mean(dim=1)[:, 0, 1:]
-            return None   # unknown method: the reference falls through silently
+            maps = {m: relprop_tail(self, m, cam, is_ablation, start_layer, prune, **kwargs) for m in wanted}
+            return maps if several else maps[method]
 
     def vit_base_patch16_224(pretrained=False, **kwargs):
         model = VisionTransformer(patch_size=16, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4, qkv_bias=True,
