@@ -67,6 +67,70 @@ def test_argument_validation_without_device(lib):
     assert lib.te_rollout_f32(None, 1, 0, 1, 4, 0, None, None, 0, None) == -1
 
 
+def test_attention_entry_points_reject_on_the_host(lib):
+    """What every fp32 attention entry point answers before it touches a device: the status of each refusal.  P is a fake non-null,
+    16-byte-aligned address that the host never dereferences; every call below returns before the first HIP call."""
+    P, B, H, N, D = 4096, 2, 2, 100, 64
+    C = H * D
+    view = lambda name: {name + "_sb": N * C, name + "_sh": 64, name + "_sn": C}      # noqa: E731
+    dims = dict(B=B, H=H, N=N, D=D)
+
+    def status(fn, base, **changed):
+        assert set(changed) <= set(base), changed
+        return getattr(lib, fn)(*{**base, **changed}.values())
+
+    fwd_s = dict(q=P, **view("q"), k=P, **view("k"), v=P, **view("v"), mask=None, z_qk=P, x_scaled=None, attn=P, out=P, **view("o"),
+                 **dims, scale=0.125, stream=None)
+    f = "te_attention_forward_strided_f32"
+    assert [status(f, fwd_s, q=None), status(f, fwd_s, N=0)] == [-1, -1]
+    assert [status(f, fwd_s, N=641), status(f, fwd_s, D=80), status(f, fwd_s, q_sn=66)] == [-3, -3, -3]
+
+    ws_bytes = lib.te_attention_backward_strided_workspace_bytes(B, H, N)
+    bwd_s = dict(d_out=P, **view("do"), q=P, **view("q"), k=P, **view("k"), v=P, **view("v"), attn=P, d_attn=P, d_q=P, **view("dq"),
+                 d_k=P, **view("dk"), d_v=P, **view("dv"), **dims, scale=0.125, need_qk=1, ws=P, ws_bytes=ws_bytes, stream=None)
+    f = "te_attention_backward_strided_f32"
+    assert [status(f, bwd_s, d_out=None), status(f, bwd_s, d_q=None)] == [-1, -1]
+    assert [status(f, bwd_s, N=641), status(f, bwd_s, D=80), status(f, bwd_s, dv_sn=66)] == [-3, -3, -3]
+    assert [status(f, bwd_s, ws=None), status(f, bwd_s, ws_bytes=16), status(f, bwd_s, d_q=None, need_qk=0, ws=None)] == [-2, -2, -2]
+    bwd_so = dict(d_out=P, **view("do"), out=P, **view("o"), **{k: v for k, v in bwd_s.items() if k not in ("d_out", "do_sb", "do_sh", "do_sn")})
+    assert status("te_attention_backward_strided_out_f32", bwd_so, out=None) == -1
+
+    fwd = dict(qkv=P, z_qk=P, attn=P, out=P, **dims, scale=0.125, stream=None)
+    f = "te_attention_forward_f32"
+    assert status(f, fwd, qkv=None) == -1
+    assert [status(f, fwd, N=225), status(f, fwd, D=80)] == [-3, -3]
+    planes_bytes = lib.te_linear_x6_planes_bytes(B * N, H * D)
+    assert planes_bytes > 16
+    fwd_p = dict(qkv=P, z_qk=P, attn=P, out=P, out_planes=P, out_abs_planes=None, planes_bytes=planes_bytes, **dims, scale=0.125, stream=None)
+    f = "te_attention_forward_planes_f32"
+    assert status(f, fwd_p, out_planes=None) == -1
+    assert status(f, fwd_p, N=225) == -3
+    assert [status(f, fwd_p, planes_bytes=16), status(f, fwd_p, out_planes=P + 4)] == [-2, -2]
+    bwd = dict(d_out=P, qkv=P, attn=P, d_attn=P, d_qkv=P, **dims, scale=0.125, need_qk=1, stream=None)
+    f = "te_attention_backward_f32"
+    assert status(f, bwd, d_out=None) == -1
+    assert status(f, bwd, N=225) == -3
+    bwd_o = dict(d_out=P, out=P, **{k: v for k, v in bwd.items() if k != "d_out"})
+    assert status("te_attention_backward_out_f32", bwd_o, out=None) == -1
+
+    ws_bytes = lib.te_matmul_relprop_av_workspace_bytes(B, H, N, D)
+    av = dict(R=P, **view("r"), attn=P, v=P, **view("v"), Z=P, z_sb=H * N * D, z_sh=N * D, z_sn=D, cam_attn=P, cam_v=P, **view("cv"),
+              **dims, scale=1.0, variant=0, ws=P, ws_bytes=ws_bytes, stream=None)
+    f = "te_matmul_relprop_av_fwdz_f32"
+    assert [status(f, av, R=None), status(f, av, r_sb=-1), status(f, av, r_sn=0), status(f, av, D=0)] == [-1, -1, -1, -1]
+    assert [status(f, av, ws=None), status(f, av, ws_bytes=ws_bytes - 256)] == [-2, -2]
+    ws_bytes = lib.te_matmul_relprop_qk_workspace_bytes(B, H, N, D)
+    qk = dict(R=P, r_scale=None, r_scale_stride=0, q=P, **view("q"), k=P, **view("k"), Z=P, cam_q=P, **view("cq"), cam_k=P, **view("ck"),
+              **dims, scale=1.0, variant=0, ws=P, ws_bytes=ws_bytes, stream=None)
+    f = "te_matmul_relprop_qk_fwd_scaled_f32"
+    assert [status(f, qk, R=None), status(f, qk, q_sb=-1)] == [-1, -1]
+    assert [status(f, qk, ws=None), status(f, qk, ws_bytes=ws_bytes - 256)] == [-2, -2]
+
+    assert [lib.te_attention_forward_supported(n, 64) for n in (0, 1, 224, 225)] == [0, 1, 1, 0]
+    assert [lib.te_attention_strided_supported(n, 64) for n in (0, 1, 640, 641)] == [0, 1, 1, 0]
+    assert lib.te_attention_forward_supported(100, 80) == 0 and lib.te_attention_strided_supported(100, 80) == 0
+
+
 def test_product_path_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

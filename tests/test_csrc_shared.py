@@ -80,7 +80,7 @@ PRIMITIVES = [
 ]
 
 # the launchers another translation unit calls live in these namespaces (and one free function)
-LAUNCHER_NAMESPACES = ["te_attn_mfma", "te_attn_rules", "te_attn_kb", "te_attn_rc", "te_attn_fwd6", "te_attn_fwd6l", "te_attn_bwd6l"]
+LAUNCHER_NAMESPACES = ["te_attn_mfma", "te_attn_rules", "te_attn_kb", "te_attn_rc", "te_attn_fwd6", "te_attn_fwd6l", "te_attn_bwd6l", "te_attn_long"]
 
 
 def definitions(sources, pattern):

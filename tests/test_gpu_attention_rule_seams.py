@@ -2,7 +2,7 @@
 dispatch -- the sequence lengths at which a kernel family changes, a key block or key group is partial, or the number
 of key groups changes -- from N = 2 to beyond 4096, against the fp64 oracle.
 
-Which code a length reaches (head dim 64):
+Which code a length reaches (head dim 64; csrc/te_attn.hip holds the whole dispatch, one chain per entry point):
   N <= 224        QK rule on te_attn_rc.hip (`both` = 1 up to 208, the re-staged two-phase form for 209-224)
   225 .. 4096     QK rule on qk_rule_kernel<RULE>: ng = ceil(N / 256) key groups of jg = roundup64(ceil(N / ng)) keys;
                   the last group's nj & 3 selects the tail assembly, nj < 4 the guarded loads, ng > 1 the finishing kernel

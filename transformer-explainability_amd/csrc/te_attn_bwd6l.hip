@@ -362,26 +362,18 @@ bool supported(int64_t B, int64_t H, int64_t N, int64_t D) {
 }
 
 // out may be null with need_qk = 0 only (nothing but d_attn is formed then)
-int launch_rows(const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn, const float* out, int64_t o_sb, int64_t o_sh,
-                int64_t o_sn, const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn, const float* v, int64_t v_sb, int64_t v_sh,
-                int64_t v_sn, const float* attn, float* d_attn, float* rowdot, float* d_q, int64_t dq_sb, int64_t dq_sh, int64_t dq_sn,
-                int64_t B, int64_t H, int64_t N, float scale, int need_qk, hipStream_t stream) {
-  const Strided dos{do_sb, do_sh, do_sn}, os{o_sb, o_sh, o_sn}, ks{k_sb, k_sh, k_sn}, vs{v_sb, v_sh, v_sn}, dqs{dq_sb, dq_sh, dq_sn};
-  const int NBr = (int)((N + 31) >> 5), G8 = (NBr + 7) / 8, G4 = (NBr + 3) / 4;
-  const bool w8 = 5 * G8 * 8 <= 6 * G4 * 4;      // (te_attn_fwd6l.hip: launch)
-  return w8 ? launch_w<8>(d_out, dos, out, os, k, ks, v, vs, attn, d_attn, rowdot, d_q, dqs, B, H, N, scale, need_qk, stream)
-            : launch_w<4>(d_out, dos, out, os, k, ks, v, vs, attn, d_attn, rowdot, d_q, dqs, B, H, N, scale, need_qk, stream);
+int launch_rows(const float* d_out, Strided dos, const float* out, Strided os, const float* k, Strided ks, const float* v, Strided vs,
+                const float* attn, float* d_attn, float* rowdot, float* d_q, Strided dqs, int64_t B, int64_t H, int64_t N, float scale,
+                int need_qk, hipStream_t stream) {
+  return eight_waves(N) ? launch_w<8>(d_out, dos, out, os, k, ks, v, vs, attn, d_attn, rowdot, d_q, dqs, B, H, N, scale, need_qk, stream)
+                        : launch_w<4>(d_out, dos, out, os, k, ks, v, vs, attn, d_attn, rowdot, d_q, dqs, B, H, N, scale, need_qk, stream);
 }
 
-
-int launch_cols(const float* attn, const float* d_attn, const float* rowdot, const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn,
-                const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, float* d_v, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn, float* d_k,
-                int64_t dk_sb, int64_t dk_sh, int64_t dk_sn, int64_t B, int64_t H, int64_t N, float scale, int need_qk, hipStream_t stream) {
-  const Strided dos{do_sb, do_sh, do_sn}, qs{q_sb, q_sh, q_sn}, dvs{dv_sb, dv_sh, dv_sn}, dks{dk_sb, dk_sh, dk_sn};
-  const int NBr = (int)((N + 31) >> 5), G8 = (NBr + 7) / 8, G4 = (NBr + 3) / 4;
-  const bool w8 = 5 * G8 * 8 <= 6 * G4 * 4;
-  return w8 ? launch_cols_w<8>(attn, d_attn, rowdot, d_out, dos, q, qs, d_v, dvs, d_k, dks, B, H, N, scale, need_qk, stream)
-            : launch_cols_w<4>(attn, d_attn, rowdot, d_out, dos, q, qs, d_v, dvs, d_k, dks, B, H, N, scale, need_qk, stream);
+int launch_cols(const float* attn, const float* d_attn, const float* rowdot, const float* d_out, Strided dos, const float* q, Strided qs,
+                float* d_v, Strided dvs, float* d_k, Strided dks, int64_t B, int64_t H, int64_t N, float scale, int need_qk,
+                hipStream_t stream) {
+  return eight_waves(N) ? launch_cols_w<8>(attn, d_attn, rowdot, d_out, dos, q, qs, d_v, dvs, d_k, dks, B, H, N, scale, need_qk, stream)
+                        : launch_cols_w<4>(attn, d_attn, rowdot, d_out, dos, q, qs, d_v, dvs, d_k, dks, B, H, N, scale, need_qk, stream);
 }
 
 }  // namespace te_attn_bwd6l

@@ -255,16 +255,10 @@ bool supported(int64_t B, int64_t H, int64_t N, int64_t D) {
   return D == 64 && N > 64 && N <= kMaxN && B >= 1 && H >= 1 && B * H <= (1 << 24);
 }
 
-int launch(const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
-           const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sn, const float* mask, float* z_qk, float* x_scaled, float* attn,
-           float* out, int64_t o_sb, int64_t o_sh, int64_t o_sn, int64_t B, int64_t H, int64_t N, float scale, hipStream_t stream) {
-  const Strided qs{q_sb, q_sh, q_sn}, ks{k_sb, k_sh, k_sn}, vs{v_sb, v_sh, v_sn}, os{o_sb, o_sh, o_sn};
-  // 8-wave workgroups are ~10 % faster at equal wave utilisation (measured: profiles/r06_attention_fwd_long_ab.log); the 4-wave
-  // cut wins where it leaves fewer waves without a row block: owners / (parts x waves) at least 1.2 x the 8-wave cut's
-  const int NBr = (int)((N + 31) >> 5), G8 = (NBr + 7) / 8, G4 = (NBr + 3) / 4;
-  const bool w8 = 5 * G8 * 8 <= 6 * G4 * 4;      // (NBr / (4 G4)) / (NBr / (8 G8)) < 1.2
-  return w8 ? launch_w<8>(q, qs, k, ks, v, vs, mask, z_qk, x_scaled, attn, out, os, B, H, N, scale, stream)
-            : launch_w<4>(q, qs, k, ks, v, vs, mask, z_qk, x_scaled, attn, out, os, B, H, N, scale, stream);
+int launch(const float* q, Strided qs, const float* k, Strided ks, const float* v, Strided vs, const float* mask, float* z_qk,
+           float* x_scaled, float* attn, float* out, Strided os, int64_t B, int64_t H, int64_t N, float scale, hipStream_t stream) {
+  return eight_waves(N) ? launch_w<8>(q, qs, k, ks, v, vs, mask, z_qk, x_scaled, attn, out, os, B, H, N, scale, stream)
+                        : launch_w<4>(q, qs, k, ks, v, vs, mask, z_qk, x_scaled, attn, out, os, B, H, N, scale, stream);
 }
 
 }  // namespace te_attn_fwd6l

@@ -351,19 +351,16 @@ bool supported(int64_t B, int64_t H, int64_t N, int64_t D) {
 }
 
 // mode 0: the AV rule; mode 1: d_attn / d_v of the attention backward (R = d_out, Z ignored, scale ignored)
-int av_launch(int mode, const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const float* attn, const float* v,
-              int64_t v_sb, int64_t v_sh, int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn,
-              float* cam_attn, float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn, int64_t B, int64_t H, int64_t N,
-              float scale, hipStream_t stream) {
+int av_launch(int mode, const float* R, Strided rs, const float* attn, const float* v, Strided vs, const float* Z, Strided zs,
+              float* cam_attn, float* cam_v, Strided cs, int64_t B, int64_t H, int64_t N, float scale, hipStream_t stream) {
   int ng, kbg;
   groups_for(N, ng, kbg);
   const int BH = (int)(B * H);
   // 32-bit row offsets inside a (b, h) view, and the hardware range check that drops the rows >= N of a partial key block needs
   // a row stride of at least the 64 floats a row holds: every strided view of the launch
   auto stride_ok = [](int64_t sn) { return sn >= 64 && sn <= 65536; };
-  if (!stride_ok(r_sn) || !stride_ok(v_sn) || !stride_ok(cv_sn) || (mode == 0 && !stride_ok(z_sn))) return TE_ERR_UNSUPPORTED;
+  if (!stride_ok(rs.sn) || !stride_ok(vs.sn) || !stride_ok(cs.sn) || (mode == 0 && !stride_ok(zs.sn))) return TE_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)(BH * ng)), blk(kT);
-  const Strided rs{r_sb, r_sh, r_sn}, zs{z_sb, z_sh, z_sn}, vs{v_sb, v_sh, v_sn}, cs{cv_sb, cv_sh, cv_sn};
   if (mode == 0)
     av6_kb_kernel<RULE><<<grid, blk, 0, stream>>>(R, rs, Z, zs, attn, v, vs, cam_attn, cam_v, cs, (int)H, (int)N, BH, kbg, scale);
   else

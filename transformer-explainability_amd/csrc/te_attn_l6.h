@@ -28,6 +28,14 @@ struct Cfg {
   static constexpr int kLds = kTileOff + W * 32 * kTileLd * 4;
 };
 
+// Which W a launcher takes for a length: 8-wave workgroups are ~10 % faster at equal wave utilisation (measured: profiles/
+// r06_attention_fwd_long_ab.log); the 4-wave cut wins where it leaves fewer waves without a row block: owners / (parts x waves) at
+// least 1.2 x the 8-wave cut's
+inline bool eight_waves(int64_t N) {
+  const int NBr = (int)((N + 31) >> 5), G8 = (NBr + 7) / 8, G4 = (NBr + 3) / 4;
+  return 5 * G8 * 8 <= 6 * G4 * 4;      // (NBr / (4 G4)) / (NBr / (8 G8)) < 1.2
+}
+
 // (te_x6.h: the three-way split -- split3_pk, planes_of8 --, div2 and the order of the six partial products, PA / PB; te_buffer.h: Rsrc)
 
 // ---- chunk c of k [N][64] as A planes with M = key, K = d:  Pk[plane 3][step 4][jb kNKB][kh 2][r 32][8], element = plane q of

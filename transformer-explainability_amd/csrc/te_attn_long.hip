@@ -1,5 +1,5 @@
-// te_attn_long.hip -- attention producers for the sequence lengths the one-workgroup-per-head kernels of
-// te_attn_rules.hip cannot hold (they keep k AND v of a head in LDS: N <= 224): ViT-L/16 at 384^2 (N = 577,
+// te_attn_long.hip -- attention producers for the sequence lengths the one-workgroup-per-head kernels behind the
+// fused-qkv entry points cannot hold (they keep k AND v of a head in LDS: N <= 224): ViT-L/16 at 384^2 (N = 577,
 // baselines/ViT/ViT_LRP.py:132-152,419-425) and BERT (N = 512; separate q / k / v activations, scores / sqrt(D), additive
 // mask, BERT_explainability/modules/BERT/BERT.py:307-365).  Head dim 64, N <= 640, any [B,H,N,64] strides.
 //
@@ -13,9 +13,9 @@
 //             cols  one wave per (b, h, 32 keys): d_v = attn^T d_out, d_k = d_s^T q over all N query rows, operands
 //                straight from global memory (the key block of a row is one 128-B line), accumulators in registers
 //
-// Round 6: for 64 < N <= 640 the entry points below dispatch to te_attn_fwd6l.hip (forward) and te_attn_bwd6l.hip (backward: the
-// column side always, the row side when the caller hands over the block's forward output or needs no d_q / d_k) -- bf16 MFMAs with
-// split operands, 1.4-2.2 x these kernels, which remain for N <= 64 and for the backward without `out`.
+// The host side of this file only launches.  Since round 6 te_attn_fwd6l.hip / te_attn_bwd6l.hip (bf16 MFMAs with split operands, 1.4-2.2 x these
+// kernels) take 64 < N <= 640; these kernels remain for N <= 64 and for the row side of a backward without the forward output.
+// The choice is the dispatch of te_attn.hip.
 //
 // fp32 MFMAs (v_mfma_f32_32x32x2_f32 / 16x16x4_f32): exact k-ordered fma chains; every reduction has a fixed order that
 // depends on N only, so a batch equals its samples run one by one, bit for bit.
@@ -436,116 +436,44 @@ inline void allow_lds(K kern, size_t bytes) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-// (local on purpose: these kernels move 16-byte pieces of [.., 64] rows; te_attn.hip's strides_ok accepts any non-negative strides)
-inline bool strides_ok(int64_t sb, int64_t sh, int64_t sn) { return sb >= 0 && sh >= 0 && sn >= 64 && (sn % 4) == 0 && (sh % 4) == 0 && (sb % 4) == 0; }
-
 }  // namespace
 
-extern "C" int te_attention_strided_supported(int64_t N, int64_t D) { return (D == 64 && N >= 1 && N <= NMAX) ? 1 : 0; }
+namespace te_attn_long {
 
-extern "C" size_t te_attention_backward_strided_workspace_bytes(int64_t B, int64_t H, int64_t N) {
-  return te_align_up((size_t)(B * H * N) * sizeof(float), 256);
+bool supported(int64_t B, int64_t H, int64_t N, int64_t D) {
+  return D == 64 && N >= 1 && N <= NMAX && B * H * te_ceil_div(N, TI) <= 0x7fffffff;
 }
 
-extern "C" int te_attention_forward_strided_f32(const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k,
-                                                int64_t k_sb, int64_t k_sh, int64_t k_sn, const float* v, int64_t v_sb,
-                                                int64_t v_sh, int64_t v_sn, const float* mask, float* z_qk,
-                                                float* x_scaled, float* attn, float* out, int64_t o_sb, int64_t o_sh,
-                                                int64_t o_sn, int64_t B, int64_t H, int64_t N, int64_t D, float scale,
-                                                te_stream_t stream_) {
-  if (!q || !k || !v || !attn || !out || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
+// (not te_attn.hip's check of a rule's views, which accepts any non-negative strides: these kernels, and the round-6 ones that take
+// the same calls, move 16-byte pieces of [.., 64] rows)
+bool strides_ok(Strided s) { return s.sb >= 0 && s.sh >= 0 && s.sn >= 64 && (s.sn % 4) == 0 && (s.sh % 4) == 0 && (s.sb % 4) == 0; }
+
+int fwd_launch(const float* q, Strided qs, const float* k, Strided ks, const float* v, Strided vs, const float* mask, float* z_qk,
+               float* x_scaled, float* attn, float* out, Strided os, int64_t B, int64_t H, int64_t N, float scale, hipStream_t stream) {
   const int64_t ntile = te_ceil_div(N, TI);
-  if (!te_attention_strided_supported(N, D) || B * H * ntile > 0x7fffffff) return TE_ERR_UNSUPPORTED;
-  if (!strides_ok(q_sb, q_sh, q_sn) || !strides_ok(k_sb, k_sh, k_sn) || !strides_ok(v_sb, v_sh, v_sn) ||
-      !strides_ok(o_sb, o_sh, o_sn))
-    return TE_ERR_UNSUPPORTED;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (te_attn_fwd6l::supported(B, H, N, D)) {
-    const int rc = te_attn_fwd6l::launch(q, q_sb, q_sh, q_sn, k, k_sb, k_sh, k_sn, v, v_sb, v_sh, v_sn, mask, z_qk, x_scaled, attn,
-                                         out, o_sb, o_sh, o_sn, B, H, N, scale, stream);
-    if (rc != TE_OK) return rc;
-    TE_RETURN_IF_LAUNCH_FAILED();
-    return TE_OK;
-  }
   allow_lds(attn_fwd_rows_kernel, lds_rows(NMAX));
-  attn_fwd_rows_kernel<<<dim3((unsigned)(B * H * ntile)), dim3(kT), lds_rows(N), stream>>>(
-      q, Strided{q_sb, q_sh, q_sn}, k, Strided{k_sb, k_sh, k_sn}, v, Strided{v_sb, v_sh, v_sn}, mask, z_qk, x_scaled, attn,
-      out, Strided{o_sb, o_sh, o_sn}, (int)H, (int)N, (int)ntile, scale);
-  TE_RETURN_IF_LAUNCH_FAILED();
+  attn_fwd_rows_kernel<<<dim3((unsigned)(B * H * ntile)), dim3(kT), lds_rows(N), stream>>>(q, qs, k, ks, v, vs, mask, z_qk, x_scaled, attn, out, os,
+                                                                                          (int)H, (int)N, (int)ntile, scale);
   return TE_OK;
 }
 
-// out (optional): the forward output attention_forward returned for these inputs ([B,H,N,64] view).  With it -- or with
-// need_qk = 0, where no row sum is needed -- the row side runs on te_attn_bwd6l.hip (row sums from d_out . out); without it
-// on attn_bwd_rows_kernel (row sums from d_attn . attn).
-static int backward_strided(const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn, const float* out, int64_t o_sb,
-                            int64_t o_sh, int64_t o_sn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k,
-                            int64_t k_sb, int64_t k_sh, int64_t k_sn, const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sn,
-                            const float* attn, float* d_attn, float* d_q, int64_t dq_sb, int64_t dq_sh, int64_t dq_sn, float* d_k,
-                            int64_t dk_sb, int64_t dk_sh, int64_t dk_sn, float* d_v, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
-                            int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk, void* ws, size_t ws_bytes,
-                            te_stream_t stream_) {
-  if (!d_out || !k || !v || !attn || !d_attn || !d_v || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
-  if (need_qk && (!q || !d_q || !d_k)) return TE_ERR_INVALID_ARG;
+// row sums from d_attn . attn, left in rowdot [B*H,N] for the column side
+int bwd_rows_launch(const float* d_out, Strided dos, const float* k, Strided ks, const float* v, Strided vs, const float* attn, float* d_attn,
+                    float* rowdot, float* d_q, Strided dqs, int64_t B, int64_t H, int64_t N, float scale, int need_qk, hipStream_t stream) {
   const int64_t ntile = te_ceil_div(N, TI);
-  if (!te_attention_strided_supported(N, D) || B * H * ntile > 0x7fffffff) return TE_ERR_UNSUPPORTED;
-  if (!strides_ok(do_sb, do_sh, do_sn) || !strides_ok(k_sb, k_sh, k_sn) || !strides_ok(v_sb, v_sh, v_sn) ||
-      !strides_ok(dv_sb, dv_sh, dv_sn) || (out && !strides_ok(o_sb, o_sh, o_sn)))
-    return TE_ERR_UNSUPPORTED;
-  if (need_qk && (!strides_ok(q_sb, q_sh, q_sn) || !strides_ok(dq_sb, dq_sh, dq_sn) || !strides_ok(dk_sb, dk_sh, dk_sn)))
-    return TE_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < te_attention_backward_strided_workspace_bytes(B, H, N)) return TE_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  float* rowdot = (float*)ws;
-  if ((out || !need_qk) && te_attn_bwd6l::supported(B, H, N, D)) {
-    const int rc = te_attn_bwd6l::launch_rows(d_out, do_sb, do_sh, do_sn, out, o_sb, o_sh, o_sn, k, k_sb, k_sh, k_sn, v, v_sb, v_sh, v_sn,
-                                              attn, d_attn, rowdot, d_q, dq_sb, dq_sh, dq_sn, B, H, N, scale, need_qk ? 1 : 0, stream);
-    if (rc != TE_OK) return rc;
-  } else {
-    allow_lds(attn_bwd_rows_kernel, lds_rows(NMAX));
-    attn_bwd_rows_kernel<<<dim3((unsigned)(B * H * ntile)), dim3(kT), lds_rows(N), stream>>>(
-        d_out, Strided{do_sb, do_sh, do_sn}, k, Strided{k_sb, k_sh, k_sn}, v, Strided{v_sb, v_sh, v_sn}, attn, d_attn, rowdot,
-        d_q, Strided{dq_sb, dq_sh, dq_sn}, (int)H, (int)N, (int)ntile, scale, need_qk ? 1 : 0);
-  }
-  if (te_attn_bwd6l::supported(B, H, N, D)) {
-    const int rc = te_attn_bwd6l::launch_cols(attn, d_attn, rowdot, d_out, do_sb, do_sh, do_sn, q, q_sb, q_sh, q_sn, d_v, dv_sb, dv_sh, dv_sn,
-                                              d_k, dk_sb, dk_sh, dk_sn, B, H, N, scale, need_qk ? 1 : 0, stream);
-    if (rc != TE_OK) return rc;
-    TE_RETURN_IF_LAUNCH_FAILED();
-    return TE_OK;
-  }
-  const int64_t nwg = te_ceil_div(ntile, 4);       // four key blocks (waves) per workgroup
-  attn_bwd_cols_kernel<<<dim3((unsigned)(B * H * nwg)), dim3(kTC), 0, stream>>>(
-      attn, d_attn, rowdot, d_out, Strided{do_sb, do_sh, do_sn}, q, Strided{q_sb, q_sh, q_sn}, d_v,
-      Strided{dv_sb, dv_sh, dv_sn}, d_k, Strided{dk_sb, dk_sh, dk_sn}, (int)H, (int)N, (int)nwg, scale, need_qk ? 1 : 0);
-  TE_RETURN_IF_LAUNCH_FAILED();
+  allow_lds(attn_bwd_rows_kernel, lds_rows(NMAX));
+  attn_bwd_rows_kernel<<<dim3((unsigned)(B * H * ntile)), dim3(kT), lds_rows(N), stream>>>(d_out, dos, k, ks, v, vs, attn, d_attn, rowdot, d_q, dqs,
+                                                                                          (int)H, (int)N, (int)ntile, scale, need_qk);
   return TE_OK;
 }
 
-extern "C" int te_attention_backward_strided_f32(const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn,
-                                                 const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k,
-                                                 int64_t k_sb, int64_t k_sh, int64_t k_sn, const float* v, int64_t v_sb,
-                                                 int64_t v_sh, int64_t v_sn, const float* attn, float* d_attn, float* d_q,
-                                                 int64_t dq_sb, int64_t dq_sh, int64_t dq_sn, float* d_k, int64_t dk_sb,
-                                                 int64_t dk_sh, int64_t dk_sn, float* d_v, int64_t dv_sb, int64_t dv_sh,
-                                                 int64_t dv_sn, int64_t B, int64_t H, int64_t N, int64_t D, float scale,
-                                                 int need_qk, void* ws, size_t ws_bytes, te_stream_t stream_) {
-  return backward_strided(d_out, do_sb, do_sh, do_sn, nullptr, 0, 0, 0, q, q_sb, q_sh, q_sn, k, k_sb, k_sh, k_sn, v, v_sb, v_sh, v_sn,
-                          attn, d_attn, d_q, dq_sb, dq_sh, dq_sn, d_k, dk_sb, dk_sh, dk_sn, d_v, dv_sb, dv_sh, dv_sn, B, H, N, D, scale,
-                          need_qk, ws, ws_bytes, stream_);
+int bwd_cols_launch(const float* attn, const float* d_attn, const float* rowdot, const float* d_out, Strided dos, const float* q, Strided qs,
+                    float* d_v, Strided dvs, float* d_k, Strided dks, int64_t B, int64_t H, int64_t N, float scale, int need_qk,
+                    hipStream_t stream) {
+  const int64_t nwg = te_ceil_div(te_ceil_div(N, TI), 4);       // four key blocks (waves) per workgroup
+  attn_bwd_cols_kernel<<<dim3((unsigned)(B * H * nwg)), dim3(kTC), 0, stream>>>(attn, d_attn, rowdot, d_out, dos, q, qs, d_v, dvs, d_k, dks, (int)H,
+                                                                               (int)N, (int)nwg, scale, need_qk);
+  return TE_OK;
 }
 
-extern "C" int te_attention_backward_strided_out_f32(const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn,
-                                                     const float* out, int64_t o_sb, int64_t o_sh, int64_t o_sn, const float* q,
-                                                     int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb,
-                                                     int64_t k_sh, int64_t k_sn, const float* v, int64_t v_sb, int64_t v_sh,
-                                                     int64_t v_sn, const float* attn, float* d_attn, float* d_q, int64_t dq_sb,
-                                                     int64_t dq_sh, int64_t dq_sn, float* d_k, int64_t dk_sb, int64_t dk_sh,
-                                                     int64_t dk_sn, float* d_v, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
-                                                     int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk, void* ws,
-                                                     size_t ws_bytes, te_stream_t stream_) {
-  if (!out) return TE_ERR_INVALID_ARG;
-  return backward_strided(d_out, do_sb, do_sh, do_sn, out, o_sb, o_sh, o_sn, q, q_sb, q_sh, q_sn, k, k_sb, k_sh, k_sn, v, v_sb, v_sh,
-                          v_sn, attn, d_attn, d_q, dq_sb, dq_sh, dq_sn, d_k, dk_sb, dk_sh, dk_sn, d_v, dv_sb, dv_sh, dv_sn, B, H, N, D,
-                          scale, need_qk, ws, ws_bytes, stream_);
-}
+}  // namespace te_attn_long

@@ -9,6 +9,9 @@
 // bits), so the rule kernels take it as an input: each rule is then two products, not three, and S agrees with the
 // forward pass to the last bit of Z.  Callers without a cached Z get it from z_av_kernel / z_qk_kernel first.
 //
+// The host side of this file only launches: te_attn.hip's dispatch decides which calls reach these kernels (the rules beyond N = 4096; Z for every
+// caller without one, whichever kernel then evaluates the rule).
+//
 // Kernels (256 threads = 4 waves as 2 x 2, one 64 x 64 output tile per block per product, v_mfma_f32_32x32x2_f32):
 //   av_row  (b,h, 64 query rows):  S = sd(R, Z) -> LDS + workspace; per 64-key chunk G = S v^T -> cam_attn = attn . G
 //   qk_row  (b,h, 64 query rows):  per 64-key chunk S = sd(R_nn, Z) -> LDS + workspace; cam_q += S_chunk k_chunk
@@ -456,61 +459,44 @@ int rollout_bmm_launch(const float* A, const float* Bm, float* C, int64_t B, int
   return TE_OK;
 }
 
-bool av_supported(int64_t N, int64_t D) { return D == TS && N >= 1 && N <= (1 << 20); }
-bool qk_supported(int64_t N, int64_t D) { return D == TS && N >= 1 && N <= (1 << 20); }
+bool supported(int64_t N, int64_t D) { return D == TS && N >= 1 && N <= (1 << 20); }
 
-// workspace (floats): S [B*H,N,64] followed by Z [B*H,N,64] (used only when the caller passes Z == NULL)
-int av_launch(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const float* attn, const float* v,
-              int64_t v_sb, int64_t v_sh, int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn,
-              float* cam_attn, float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn, int64_t B, int64_t H,
-              int64_t N, int64_t D, float scale, float* ws, hipStream_t stream) {
-  if (D != TS) return TE_ERR_UNSUPPORTED;
-  const bool z_contig = !Z || (z_sn == TS && z_sh == N * TS && z_sb == H * N * TS);
+// Z [B*H,N,64] = attn v and Z [B*H,N,N] = q k^T, contiguous
+int z_av_launch(const float* attn, const float* v, Strided vs, float* Z, int64_t B, int64_t H, int64_t N, hipStream_t stream) {
   const int BH = (int)(B * H);
   const int nt = (int)((N + TS - 1) / TS);
-  const Strided rs{r_sb, r_sh, r_sn}, vs{v_sb, v_sh, v_sn}, cs{cv_sb, cv_sh, cv_sn};
-  const Strided ss{H * N * (int64_t)TS, N * (int64_t)TS, (int64_t)TS};   // workspace S [B,H,N,64]
-  float* wsS = ws;
-  const dim3 grid((unsigned)(BH * nt)), blk(kThreads);
-  if (!Z) {
-    float* wsZ = ws + (size_t)BH * N * TS;
-    z_av_kernel<<<grid, blk, 0, stream>>>(attn, v, vs, wsZ, (int)H, (int)N, BH);
-    Z = wsZ;
-    z_sb = H * N * TS, z_sh = N * TS, z_sn = TS;
-  }
-  if (te_attn_rules::supported(B, H, N, D))
-    return te_attn_rules::av_launch(R, r_sb, r_sh, r_sn, attn, v, v_sb, v_sh, v_sn, Z, z_sb, z_sh, z_sn, cam_attn, cam_v,
-                                    cv_sb, cv_sh, cv_sn, B, H, N, scale, stream);
-  if (!z_contig) return TE_ERR_UNSUPPORTED;      // the 64 x 64-tile kernels read Z as contiguous [B*H,N,64]
-  av_row_kernel<<<grid, blk, 0, stream>>>(R, rs, Z, attn, v, vs, cam_attn, wsS, (int)H, (int)N, BH, scale);
-  col_kernel<<<grid, blk, 0, stream>>>(attn, wsS, ss, v, vs, cam_v, cs, (int)H, (int)N, BH, scale);
+  z_av_kernel<<<dim3((unsigned)(BH * nt)), dim3(kThreads), 0, stream>>>(attn, v, vs, Z, (int)H, (int)N, BH);
   return TE_OK;
 }
 
-// workspace (floats): S [B*H,N,N] followed by Z [B*H,N,N] (used only when the caller passes Z == NULL)
-int qk_launch(const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k,
-              int64_t k_sb, int64_t k_sh, int64_t k_sn, const float* Z, float* cam_q, int64_t cq_sb, int64_t cq_sh,
-              int64_t cq_sn, float* cam_k, int64_t ck_sb, int64_t ck_sh, int64_t ck_sn, int64_t B, int64_t H, int64_t N,
-              int64_t D, float scale, float* ws, const float* r_scale, int64_t r_scale_stride, hipStream_t stream) {
-  if (D != TS) return TE_ERR_UNSUPPORTED;
+// S: [B*H,N,64] floats of workspace
+int av_launch(const float* R, Strided rs, const float* attn, const float* v, Strided vs, const float* Z, Strided zs, float* cam_attn,
+              float* cam_v, Strided cs, int64_t B, int64_t H, int64_t N, float scale, float* S, hipStream_t stream) {
+  const Strided ss{H * N * (int64_t)TS, N * (int64_t)TS, (int64_t)TS};   // workspace S [B,H,N,64]
+  if (zs.sn != ss.sn || zs.sh != ss.sh || zs.sb != ss.sb) return TE_ERR_UNSUPPORTED;      // the 64 x 64-tile kernels read Z as contiguous [B*H,N,64]
   const int BH = (int)(B * H);
   const int nt = (int)((N + TS - 1) / TS);
-  const Strided qs{q_sb, q_sh, q_sn}, ks{k_sb, k_sh, k_sn}, cqs{cq_sb, cq_sh, cq_sn}, cks{ck_sb, ck_sh, ck_sn};
-  float* wsS = ws;
   const dim3 grid((unsigned)(BH * nt)), blk(kThreads);
-  if (!Z) {
-    float* wsZ = ws + (size_t)BH * N * N;
-    z_qk_kernel<<<dim3((unsigned)(BH * nt * nt)), blk, 0, stream>>>(q, qs, k, ks, wsZ, (int)H, (int)N, BH, nt);
-    Z = wsZ;
-  }
-  if (te_attn_rules::supported(B, H, N, D))
-    // (the per-group cam_q partials of N > 256 live in the S region of the workspace, which this path never writes:
-    //  ngroups * 64 <= N whenever ngroups > 1)
-    return te_attn_rules::qk_launch(Rnn, q, q_sb, q_sh, q_sn, k, k_sb, k_sh, k_sn, Z, cam_q, cq_sb, cq_sh, cq_sn, cam_k,
-                                    ck_sb, ck_sh, ck_sn, B, H, N, scale, wsS, r_scale, r_scale_stride, stream);
-  if (r_scale) return TE_ERR_UNSUPPORTED;        // only the one-pass kernel takes the deferred factor
-  qk_row_kernel<<<grid, blk, 0, stream>>>(Rnn, Z, q, qs, k, ks, cam_q, cqs, wsS, (int)H, (int)N, BH, scale);
-  col_kernel<<<grid, blk, 0, stream>>>(wsS, q, qs, k, ks, cam_k, cks, (int)H, (int)N, BH, scale);
+  av_row_kernel<<<grid, blk, 0, stream>>>(R, rs, Z, attn, v, vs, cam_attn, S, (int)H, (int)N, BH, scale);
+  col_kernel<<<grid, blk, 0, stream>>>(attn, S, ss, v, vs, cam_v, cs, (int)H, (int)N, BH, scale);
+  return TE_OK;
+}
+
+int z_qk_launch(const float* q, Strided qs, const float* k, Strided ks, float* Z, int64_t B, int64_t H, int64_t N, hipStream_t stream) {
+  const int BH = (int)(B * H);
+  const int nt = (int)((N + TS - 1) / TS);
+  z_qk_kernel<<<dim3((unsigned)(BH * nt * nt)), dim3(kThreads), 0, stream>>>(q, qs, k, ks, Z, (int)H, (int)N, BH, nt);
+  return TE_OK;
+}
+
+// S: [B*H,N,N] floats of workspace; Z contiguous [B*H,N,N]
+int qk_launch(const float* Rnn, const float* q, Strided qs, const float* k, Strided ks, const float* Z, float* cam_q, Strided cqs,
+              float* cam_k, Strided cks, int64_t B, int64_t H, int64_t N, float scale, float* S, hipStream_t stream) {
+  const int BH = (int)(B * H);
+  const int nt = (int)((N + TS - 1) / TS);
+  const dim3 grid((unsigned)(BH * nt)), blk(kThreads);
+  qk_row_kernel<<<grid, blk, 0, stream>>>(Rnn, Z, q, qs, k, ks, cam_q, cqs, S, (int)H, (int)N, BH, scale);
+  col_kernel<<<grid, blk, 0, stream>>>(S, q, qs, k, ks, cam_k, cks, (int)H, (int)N, BH, scale);
   return TE_OK;
 }
 

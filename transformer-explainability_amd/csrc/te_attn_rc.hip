@@ -552,15 +552,12 @@ bool supported(int64_t B, int64_t H, int64_t N, int64_t D) {
 
 // mode 0: the QK rule (Rnn = relevance of the scores, Z = the cached unscaled q k^T); mode 1: softmax backward (Rnn = d_attn,
 // Z = attn; cam_q / cam_k receive d_q / d_k).  Views [B,H,N,64] with element strides; Rnn, Z contiguous [B*H,N,N].
-// d_out / out (mode 1, optional): the attention block's output gradient and forward output as [B,H,N,64] views with the strides
-// o_s*: the row dots of the softmax backward then come from them instead of a pass over d_attn and attn.
-int qk_launch(int mode, const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb,
-              int64_t k_sh, int64_t k_sn, const float* Z, float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn, float* cam_k,
-              int64_t ck_sb, int64_t ck_sh, int64_t ck_sn, int64_t B, int64_t H, int64_t N, float scale, const float* r_scale,
-              int64_t r_scale_stride, hipStream_t stream, const float* d_out, const float* out, int64_t o_sb, int64_t o_sh,
-              int64_t o_sn) {
+// d_out / out (mode 1, optional): the attention block's output gradient and forward output, both [B,H,N,64] views with the
+// strides os: the row dots of the softmax backward then come from them instead of a pass over d_attn and attn.
+int qk_launch(int mode, const float* Rnn, const float* q, Strided qs, const float* k, Strided ks, const float* Z, float* cam_q,
+              Strided cqs, float* cam_k, Strided cks, int64_t B, int64_t H, int64_t N, float scale, const float* r_scale,
+              int64_t r_scale_stride, hipStream_t stream, const float* d_out, const float* out, Strided os) {
   if (!supported(B, H, N, 64)) return TE_ERR_UNSUPPORTED;
-  const Strided qs{q_sb, q_sh, q_sn}, ks{k_sb, k_sh, k_sn}, cqs{cq_sb, cq_sh, cq_sn}, cks{ck_sb, ck_sh, ck_sn};
   const int both = lds_bytes(N, true) <= kLdsMax ? 1 : 0;
   const size_t lds = lds_bytes(N, both != 0);
   const dim3 grid((unsigned)(B * H));
@@ -572,8 +569,7 @@ int qk_launch(int mode, const float* Rnn, const float* q, int64_t q_sb, int64_t 
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(qk_rc_kernel<BWD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
     const bool from_out = d_out != nullptr && out != nullptr;
     qk_rc_kernel<BWD><<<grid, dim3(kT), lds, stream>>>(Rnn, Z, q, qs, k, ks, cam_q, cqs, cam_k, cks, (int)H, (int)N, scale, nullptr, 0,
-                                                      both, from_out ? d_out : nullptr, from_out ? out : nullptr,
-                                                      Strided{o_sb, o_sh, o_sn});
+                                                      both, from_out ? d_out : nullptr, from_out ? out : nullptr, os);
   }
   return TE_OK;
 }

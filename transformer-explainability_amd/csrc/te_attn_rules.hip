@@ -1,21 +1,13 @@
-// te_attn_rules.hip -- ONE-PASS attention relprop rules for gfx950 (head dim 64): each rule reads its N x N operands
-// once and never writes S = safe_divide(R, Z) to memory (modules/layers_ours.py:48-60,122-127; ViT_LRP.py:157-173;
-// BERT.py:367-393), and the attention producers.
+// te_attn_rules.hip -- the ONE-PASS QK rule for gfx950 (head dim 64): it reads its N x N operands once and never writes
+// S = safe_divide(R, Z) to memory (modules/layers_ours.py:48-60,122-127; ViT_LRP.py:157-173; BERT.py:367-393).  The same kernel
+// evaluates the softmax half of the attention backward.
 //
-//   AV rule:  S = sd(R, Z_av) [N,64];  cam_attn = attn .(S v^T);  cam_v = v .(attn^T S)
-//   QK rule:  S = sd(R_nn, Z_qk) [N,N]; cam_q = q .(S k);         cam_k = k .(S^T q)
+//   QK rule (RULE):  S = sd(R_nn, Z_qk) [N,N];  cam_q = q .(S k);  cam_k = k .(S^T q)
+//   backward (BWD):  d_s = attn .(d_attn - rowsum(d_attn . attn)) * scale;  d_q = d_s k;  d_k = d_s^T q
 //
-// Z is the cached forward product of the very einsum / MatMul whose rule is evaluated (te_attn_mfma.hip header).
-//
-// Which kernels run:
-//   AV rule                      te_attn_kb.hip (wave-owned key blocks), every N <= 4096
-//   QK rule                      te_attn_rc.hip for N <= 224, qk_rule_kernel below beyond
-//   attention forward            te_attn_fwd6.hip (N <= 224)
-//   backward, first half         te_attn_kb.hip: d_attn = d_out v^T (the tensor save_attn_gradients receives,
-//                                ViT_LRP.py:144-145) and d_v = attn^T d_out
-//   backward, second half        d_s = attn .(d_attn - rowsum(d_attn . attn)) * scale (softmax backward), d_q = d_s k,
-//                                d_k = d_s^T q: te_attn_rc.hip for N <= 160 or with the forward output at hand,
-//                                qk_rule_kernel<BWD> otherwise
+// Z is the cached forward product of the very einsum / MatMul whose rule is evaluated (te_attn_mfma.hip header).  The host side of
+// this file only launches: which calls reach it (the rule for 224 < N <= 4096, the backward for 160 < N <= 224 without the forward output) is
+// the dispatch of te_attn.hip.  The AV rule's one-pass kernel lives in te_attn_kb.hip.
 //
 // qk_rule_kernel: one workgroup (512 threads = 8 waves, one per (b, h, key group of <= 256 keys)) keeps k (<= 256 x 64)
 // resident in LDS and walks the query rows in tiles of 32.  Per tile the row-side product AND the column-side product
@@ -437,10 +429,6 @@ __global__ __launch_bounds__(256) void qk_finish_kernel(const float* __restrict_
   *reinterpret_cast<f32x4_u*>(cam_q + (int64_t)b * cqs.sb + (int64_t)h * cqs.sh + (int64_t)i * cqs.sn + (c << 2)) = o;
 }
 
-// the attention producers serve N <= 224 (te_attn_fwd6.hip: forward; te_attn_kb.hip, te_attn_rc.hip and qk_rule_kernel<BWD>:
-// backward -- the softmax backward needs every key of a row in one group)
-constexpr int NJF = 224;
-
 inline size_t lds_qk(int /*jg*/, bool bwd) {                                                          // 106 (114) KB
   return (size_t)(64 * QLD + TI * SLD + TI * QLD + (bwd ? TI * 64 : 0)) * sizeof(float);
 }
@@ -461,138 +449,38 @@ inline void allow_lds(K kern, size_t bytes) {
 
 }  // namespace
 
-// The softmax half of the backward pass on te_attn_rc.hip: measured against qk_rule_kernel<BWD> on one box (profiles/
-// r06_attention_qk_rc_ab.log) it wins below ~160 tokens (69 vs 75 us at N = 128), ties at 224 and LOSES at 197 (the headline:
-// 272 vs 257 us for the whole backward pair -- its separate rowdot pass over the row panels), so it serves N <= 160 only.
-// With the forward output at hand (te_attention_backward_out_f32) its row dots cost nothing and it serves every N <= 224.
-static bool use_rc_bwd(int64_t N) { return N <= 160; }
-
 bool supported(int64_t B, int64_t H, int64_t N, int64_t D) {
   int ng, jg;
   groups_for(N, ng, jg);
-  // (32-bit offsets inside a (b, h) view: N <= 4096 and, checked by the launchers, a row stride <= 2^16 floats)
+  // (32-bit offsets inside a (b, h) view: N <= 4096 and, asked of the rule's q by the dispatch, a row stride <= 2^16 floats)
   return D == 64 && N >= 1 && N <= 4096 && B * H * ng <= 0x7fffffff;
 }
 
-// (te_attn_kb::supported accepts every shape supported() accepts: the AV rule always runs on wave-owned key blocks)
-int av_launch(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const float* attn, const float* v, int64_t v_sb,
-              int64_t v_sh, int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn, float* cam_attn,
-              float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn, int64_t B, int64_t H, int64_t N, float scale,
-              hipStream_t stream) {
-  if (r_sn > 65536 || z_sn > 65536) return TE_ERR_UNSUPPORTED;      // 32-bit row offsets inside a (b, h) view
-  return te_attn_kb::av_launch(0, R, r_sb, r_sh, r_sn, attn, v, v_sb, v_sh, v_sn, Z, z_sb, z_sh, z_sn, cam_attn, cam_v, cv_sb,
-                               cv_sh, cv_sn, B, H, N, scale, stream);
-}
-
-int qk_launch(const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb,
-              int64_t k_sh, int64_t k_sn, const float* Z, float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn,
-              float* cam_k, int64_t ck_sb, int64_t ck_sh, int64_t ck_sn, int64_t B, int64_t H, int64_t N, float scale,
-              float* qpart, const float* r_scale, int64_t r_scale_stride, hipStream_t stream) {
+// mode RULE: the QK rule (Rnn = relevance of the scores, Z = the cached unscaled q k^T; qpart: [ng][B*H][N][64] floats when
+// ng > 1).  mode BWD: softmax backward (Rnn = d_attn, Z = attn; cam_q / cam_k receive d_q / d_k) -- one key group only.
+int qk_launch(int mode, const float* Rnn, const float* q, Strided qs, const float* k, Strided ks, const float* Z, float* cam_q,
+              Strided cqs, float* cam_k, Strided cks, int64_t B, int64_t H, int64_t N, float scale, float* qpart, const float* r_scale,
+              int64_t r_scale_stride, hipStream_t stream) {
   int ng, jg;
   groups_for(N, ng, jg);
   const int BH = (int)(B * H);
-  if (q_sn > 65536) return TE_ERR_UNSUPPORTED;                       // 32-bit row offsets inside a (b, h) view
-  if (te_attn_rc::supported(B, H, N, 64))
-    return te_attn_rc::qk_launch(0, Rnn, q, q_sb, q_sh, q_sn, k, k_sb, k_sh, k_sn, Z, cam_q, cq_sb, cq_sh, cq_sn, cam_k, ck_sb, ck_sh,
-                                 ck_sn, B, H, N, scale, r_scale, r_scale_stride, stream);
-  allow_lds(qk_rule_kernel<RULE>, lds_qk(256, false));
-  const Strided qs{q_sb, q_sh, q_sn}, ks{k_sb, k_sh, k_sn}, cqs{cq_sb, cq_sh, cq_sn}, cks{ck_sb, ck_sh, ck_sn};
-  qk_rule_kernel<RULE><<<dim3((unsigned)(BH * ng)), dim3(kT), lds_qk(jg, false), stream>>>(Rnn, Z, q, qs, k, ks, cam_q, cqs, cam_k,
-                                                                              cks, qpart, (int)H, (int)N, BH, jg, ng,
-                                                                              scale, nullptr, r_scale,
-                                                                              r_scale_stride);
-  if (ng > 1) {
-    const int64_t n4 = (int64_t)BH * N * 16;
-    qk_finish_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream>>>(qpart, q, qs, cam_q, cqs, (int)H,
-                                                                                  (int)N, BH, ng, scale);
+  const dim3 grid((unsigned)(BH * ng)), blk(kT);
+  if (mode == RULE) {
+    allow_lds(qk_rule_kernel<RULE>, lds_qk(256, false));
+    qk_rule_kernel<RULE><<<grid, blk, lds_qk(jg, false), stream>>>(Rnn, Z, q, qs, k, ks, cam_q, cqs, cam_k, cks, qpart, (int)H, (int)N, BH,
+                                                                  jg, ng, scale, nullptr, r_scale, r_scale_stride);
+    if (ng > 1) {
+      const int64_t n4 = (int64_t)BH * N * 16;
+      qk_finish_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream>>>(qpart, q, qs, cam_q, cqs, (int)H, (int)N, BH, ng,
+                                                                                    scale);
+    }
+    return TE_OK;
   }
+  if (ng != 1) return TE_ERR_UNSUPPORTED;      // the softmax backward needs every key of a row in one group
+  allow_lds(qk_rule_kernel<BWD>, lds_qk(256, true));
+  qk_rule_kernel<BWD><<<grid, blk, lds_qk(jg, true), stream>>>(Rnn, Z, q, qs, k, ks, cam_q, cqs, cam_k, cks, nullptr, (int)H, (int)N, BH, jg,
+                                                              1, scale, nullptr, nullptr, 0);
   return TE_OK;
 }
 
 }  // namespace te_attn_rules
-
-// ================================================================================================
-// C ABI of the producers
-// ================================================================================================
-extern "C" int te_attention_forward_supported(int64_t N, int64_t D) {
-  return (D == 64 && N >= 1 && N <= te_attn_rules::NJF) ? 1 : 0;
-}
-
-extern "C" int te_attention_forward_f32(const float* qkv, float* z_qk, float* attn, float* out, int64_t B, int64_t H,
-                                        int64_t N, int64_t D, float scale, te_stream_t stream_) {
-  if (!qkv || !z_qk || !attn || !out || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
-  if (!te_attention_forward_supported(N, D) || B * H > 0x7fffffff) return TE_ERR_UNSUPPORTED;
-  // (te_attn_fwd6::supported covers every shape accepted above)
-  const int rc = te_attn_fwd6::launch(qkv, z_qk, attn, out, B, H, N, scale, (hipStream_t)stream_);
-  if (rc != TE_OK) return rc;
-  TE_RETURN_IF_LAUNCH_FAILED();
-  return TE_OK;
-}
-
-// `out` (optional): the block's forward output [B,N,C].  With it the softmax half runs on te_attn_rc.hip for every N <= 224 -- its row
-// dots sum_j attn d_attn = sum_d d_out out need no pass over the N x N tensors then (te_attention_backward_out_f32).
-static int attention_backward_impl(const float* d_out, const float* out, const float* qkv, const float* attn, float* d_attn,
-                                   float* d_qkv, int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk,
-                                   te_stream_t stream_) {
-  if (!d_out || !qkv || !attn || !d_attn || !d_qkv || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
-  if (!te_attention_forward_supported(N, D) || B * H > 0x7fffffff) return TE_ERR_UNSUPPORTED;
-  using namespace te_attn_rules;
-  hipStream_t stream = (hipStream_t)stream_;
-  const int64_t C = H * 64;
-  const int BH = (int)(B * H);
-  const Strided heads{N * C, 64, C};            // [B,N,C] seen as [B,H,N,64]
-  const Strided fused{N * 3 * C, 64, 3 * C};    // one of q / k / v inside [B,N,3C]
-  int ng, jg;
-  groups_for(N, ng, jg);                        // N <= 224: one group (the softmax backward needs every key of a row)
-  // d_attn = d_out v^T ; d_v = attn^T d_out
-  int rc = te_attn_kb::av_launch(1, d_out, heads.sb, heads.sh, heads.sn, attn, qkv + 2 * C, fused.sb, fused.sh, fused.sn, nullptr,
-                                 0, 0, 0, d_attn, d_qkv + 2 * C, fused.sb, fused.sh, fused.sn, B, H, N, 1.0f, stream);
-  if (rc != TE_OK) return rc;
-  if (need_qk && (use_rc_bwd(N) || out != nullptr) && te_attn_rc::supported(B, H, N, 64)) {
-    // d_s = softmax backward * scale ; d_q = d_s k ; d_k = d_s^T q   (te_attn_rc.hip)
-    rc = te_attn_rc::qk_launch(1, d_attn, qkv, fused.sb, fused.sh, fused.sn, qkv + C, fused.sb, fused.sh, fused.sn, attn, d_qkv,
-                               fused.sb, fused.sh, fused.sn, d_qkv + C, fused.sb, fused.sh, fused.sn, B, H, N, scale, nullptr, 0,
-                               stream, out ? d_out : nullptr, out, heads.sb, heads.sh, heads.sn);
-    if (rc != TE_OK) return rc;
-  } else if (need_qk) {
-    // d_s = softmax backward * scale ; d_q = d_s k ; d_k = d_s^T q
-    allow_lds(qk_rule_kernel<BWD>, lds_qk(256, true));
-    qk_rule_kernel<BWD><<<dim3((unsigned)BH), dim3(kT), lds_qk(jg, true), stream>>>(d_attn, attn, qkv, fused, qkv + C, fused,
-                                                                           d_qkv, fused, d_qkv + C, fused, nullptr,
-                                                                           (int)H, (int)N, BH, jg, 1, scale, nullptr, nullptr,
-                                                                           0);
-  }
-  TE_RETURN_IF_LAUNCH_FAILED();
-  return TE_OK;
-}
-
-// The forward producer that also writes the operand planes of `out` for the projection layer's x6 kernels (round 6):
-// out_planes = the signed planes of out [B N, H D] (te_linear_x6_planes_bytes(B N, H D) bytes each), out_abs_planes (optional) = the
-// planes of |out| -- bit for bit what te_linear_x6_split_dual_f32 writes from the fp32 tensor.  N <= 224 only (te_attn_fwd6.hip).
-extern "C" int te_attention_forward_planes_f32(const float* qkv, float* z_qk, float* attn, float* out, void* out_planes,
-                                               void* out_abs_planes, size_t planes_bytes, int64_t B, int64_t H, int64_t N,
-                                               int64_t D, float scale, te_stream_t stream_) {
-  if (!qkv || !z_qk || !attn || !out || !out_planes || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
-  if (!te_attention_forward_supported(N, D) || !te_attn_fwd6::supported(B, H, N, D)) return TE_ERR_UNSUPPORTED;
-  const size_t need = te_linear_x6_planes_bytes(B * N, H * D);
-  if (need == 0) return TE_ERR_UNSUPPORTED;
-  if (planes_bytes < need || !te_aligned16(out_planes) || (out_abs_planes && !te_aligned16(out_abs_planes))) return TE_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  const int rc = te_attn_fwd6::launch(qkv, z_qk, attn, out, B, H, N, scale, stream, out_planes, out_abs_planes);
-  if (rc != TE_OK) return rc;
-  TE_RETURN_IF_LAUNCH_FAILED();
-  return TE_OK;
-}
-
-extern "C" int te_attention_backward_f32(const float* d_out, const float* qkv, const float* attn, float* d_attn,
-                                         float* d_qkv, int64_t B, int64_t H, int64_t N, int64_t D, float scale,
-                                         int need_qk, te_stream_t stream_) {
-  return attention_backward_impl(d_out, nullptr, qkv, attn, d_attn, d_qkv, B, H, N, D, scale, need_qk, stream_);
-}
-
-extern "C" int te_attention_backward_out_f32(const float* d_out, const float* out, const float* qkv, const float* attn,
-                                             float* d_attn, float* d_qkv, int64_t B, int64_t H, int64_t N, int64_t D,
-                                             float scale, int need_qk, te_stream_t stream_) {
-  if (!out) return TE_ERR_INVALID_ARG;
-  return attention_backward_impl(d_out, out, qkv, attn, d_attn, d_qkv, B, H, N, D, scale, need_qk, stream_);
-}

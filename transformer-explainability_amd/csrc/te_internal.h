@@ -10,49 +10,39 @@
 bool te_internal_zb_cpass_tiled(const float* S, const float* W, const float* X, float* out, int64_t T, int64_t in_f,
                                 int64_t out_f, const TeZbGeom& zb, hipStream_t stream);
 
-namespace te_attn_mfma {    // te_attn_mfma.hip: LDS-tiled fp32-MFMA rule kernels (round 1), any N with head dim 64; they hand over to te_attn_rules
-// (callers: te_attn.hip, te_rollout.hip)  the *_supported return false if the shape is not covered by the tiled kernels
-bool av_supported(int64_t N, int64_t D);
-int av_launch(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const float* attn,
-              const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh,
-              int64_t z_sn, float* cam_attn, float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn, int64_t B,
-              int64_t H, int64_t N, int64_t D, float scale, float* ws, hipStream_t stream);
-bool qk_supported(int64_t N, int64_t D);
-int qk_launch(const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
-              const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn, const float* Z, float* cam_q, int64_t cq_sb,
-              int64_t cq_sh, int64_t cq_sn, float* cam_k, int64_t ck_sb, int64_t ck_sh, int64_t ck_sn,
-              int64_t B, int64_t H, int64_t N, int64_t D, float scale, float* ws, const float* r_scale,
-              int64_t r_scale_stride, hipStream_t stream);
+// The fp32 attention launchers below have ONE caller, the dispatch in te_attn.hip (te_rollout.hip for the rollout product): no
+// launcher calls a launcher of another file.  A [B,H,N,64] view crosses a file boundary as (pointer, Strided).
+enum { TE_ATTN_RULE = 0, TE_ATTN_BWD = 1 };      // `mode` of the launchers that serve a relprop rule and the attention backward
+
+namespace te_attn_mfma {    // te_attn_mfma.hip: LDS-tiled fp32-MFMA rule kernels (round 1), any N <= 2^20 with head dim 64; Z for callers without one
+bool supported(int64_t N, int64_t D);
+int z_av_launch(const float* attn, const float* v, Strided vs, float* Z, int64_t B, int64_t H, int64_t N, hipStream_t stream);
+int z_qk_launch(const float* q, Strided qs, const float* k, Strided ks, float* Z, int64_t B, int64_t H, int64_t N, hipStream_t stream);
+int av_launch(const float* R, Strided rs, const float* attn, const float* v, Strided vs, const float* Z, Strided zs, float* cam_attn,
+              float* cam_v, Strided cs, int64_t B, int64_t H, int64_t N, float scale, float* S, hipStream_t stream);
+int qk_launch(const float* Rnn, const float* q, Strided qs, const float* k, Strided ks, const float* Z, float* cam_q, Strided cqs,
+              float* cam_k, Strided cks, int64_t B, int64_t H, int64_t N, float scale, float* S, hipStream_t stream);
 int rollout_bmm_launch(const float* A, const float* Bm, float* C, int64_t B, int64_t N, hipStream_t stream);
 }  // namespace te_attn_mfma
 
-namespace te_attn_rules {   // te_attn_rules.hip: the one-pass rule kernels (default)
+namespace te_attn_rules {   // te_attn_rules.hip: the one-pass kernel (round 2) -- the QK rule for 224 < N <= 4096, the softmax backward for 160 < N <= 224
 bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
-int av_launch(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const float* attn, const float* v, int64_t v_sb,
-              int64_t v_sh, int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn, float* cam_attn,
-              float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn, int64_t B, int64_t H, int64_t N, float scale,
-              hipStream_t stream);
-int qk_launch(const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb,
-              int64_t k_sh, int64_t k_sn, const float* Z, float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn,
-              float* cam_k, int64_t ck_sb, int64_t ck_sh, int64_t ck_sn, int64_t B, int64_t H, int64_t N, float scale,
-              float* qpart, const float* r_scale, int64_t r_scale_stride, hipStream_t stream);
+int qk_launch(int mode, const float* Rnn, const float* q, Strided qs, const float* k, Strided ks, const float* Z, float* cam_q,
+              Strided cqs, float* cam_k, Strided cks, int64_t B, int64_t H, int64_t N, float scale, float* qpart, const float* r_scale,
+              int64_t r_scale_stride, hipStream_t stream);
 }  // namespace te_attn_rules
 
-namespace te_attn_kb {      // te_attn_kb.hip: wave-owned key blocks (round 5) -- the AV rule and the first half of the backward
+namespace te_attn_kb {      // te_attn_kb.hip: wave-owned key blocks (round 5) -- the AV rule (N <= 4096) and the first half of the backward
 bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
-int av_launch(int mode, const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, const float* attn, const float* v,
-              int64_t v_sb, int64_t v_sh, int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn,
-              float* cam_attn, float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn, int64_t B, int64_t H, int64_t N,
-              float scale, hipStream_t stream);
+int av_launch(int mode, const float* R, Strided rs, const float* attn, const float* v, Strided vs, const float* Z, Strided zs,
+              float* cam_attn, float* cam_v, Strided cs, int64_t B, int64_t H, int64_t N, float scale, hipStream_t stream);
 }  // namespace te_attn_kb
 
 namespace te_attn_rc {      // te_attn_rc.hip: row-block and key-block owners (round 6) -- the QK rule / softmax backward, N <= 224
 bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
-int qk_launch(int mode, const float* Rnn, const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb,
-              int64_t k_sh, int64_t k_sn, const float* Z, float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn, float* cam_k,
-              int64_t ck_sb, int64_t ck_sh, int64_t ck_sn, int64_t B, int64_t H, int64_t N, float scale, const float* r_scale,
-              int64_t r_scale_stride, hipStream_t stream, const float* d_out = nullptr, const float* out = nullptr, int64_t o_sb = 0,
-              int64_t o_sh = 0, int64_t o_sn = 0);
+int qk_launch(int mode, const float* Rnn, const float* q, Strided qs, const float* k, Strided ks, const float* Z, float* cam_q,
+              Strided cqs, float* cam_k, Strided cks, int64_t B, int64_t H, int64_t N, float scale, const float* r_scale,
+              int64_t r_scale_stride, hipStream_t stream, const float* d_out = nullptr, const float* out = nullptr, Strided os = Strided());
 }  // namespace te_attn_rc
 
 namespace te_attn_fwd6 {      // te_attn_fwd6.hip: row-block owners on bf16 MFMAs (round 6) -- the attention forward, N <= 224
@@ -63,18 +53,28 @@ int launch(const float* qkv, float* z_qk, float* attn, float* out, int64_t B, in
 
 namespace te_attn_fwd6l {      // te_attn_fwd6l.hip: row-block owners on bf16 MFMAs, two walks over the keys (round 6) -- the default forward, 64 < N <= 640
 bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
-int launch(const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
-           const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sn, const float* mask, float* z_qk, float* x_scaled, float* attn,
-           float* out, int64_t o_sb, int64_t o_sh, int64_t o_sn, int64_t B, int64_t H, int64_t N, float scale, hipStream_t stream);
+int launch(const float* q, Strided qs, const float* k, Strided ks, const float* v, Strided vs, const float* mask, float* z_qk,
+           float* x_scaled, float* attn, float* out, Strided os, int64_t B, int64_t H, int64_t N, float scale, hipStream_t stream);
 }  // namespace te_attn_fwd6l
 
-namespace te_attn_bwd6l {      // te_attn_bwd6l.hip: the row side of the backward pass in the same structure (round 6), 64 < N <= 640
+namespace te_attn_bwd6l {      // te_attn_bwd6l.hip: both sides of the backward pass in the same structure (round 6), 64 < N <= 640
 bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
-int launch_rows(const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn, const float* out, int64_t o_sb, int64_t o_sh,
-                int64_t o_sn, const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn, const float* v, int64_t v_sb, int64_t v_sh,
-                int64_t v_sn, const float* attn, float* d_attn, float* rowdot, float* d_q, int64_t dq_sb, int64_t dq_sh, int64_t dq_sn,
-                int64_t B, int64_t H, int64_t N, float scale, int need_qk, hipStream_t stream);
-int launch_cols(const float* attn, const float* d_attn, const float* rowdot, const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn,
-                const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, float* d_v, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn, float* d_k,
-                int64_t dk_sb, int64_t dk_sh, int64_t dk_sn, int64_t B, int64_t H, int64_t N, float scale, int need_qk, hipStream_t stream);
+int launch_rows(const float* d_out, Strided dos, const float* out, Strided os, const float* k, Strided ks, const float* v, Strided vs,
+                const float* attn, float* d_attn, float* rowdot, float* d_q, Strided dqs, int64_t B, int64_t H, int64_t N, float scale,
+                int need_qk, hipStream_t stream);
+int launch_cols(const float* attn, const float* d_attn, const float* rowdot, const float* d_out, Strided dos, const float* q, Strided qs,
+                float* d_v, Strided dvs, float* d_k, Strided dks, int64_t B, int64_t H, int64_t N, float scale, int need_qk,
+                hipStream_t stream);
 }  // namespace te_attn_bwd6l
+
+namespace te_attn_long {      // te_attn_long.hip: row-tile producers on fp32 MFMAs (round 3), N <= 640 -- what the round-6 files do not take
+bool supported(int64_t B, int64_t H, int64_t N, int64_t D);
+bool strides_ok(Strided s);      // 16-byte pieces of rows of at least 64 floats: asked of every view of a strided producer call
+int fwd_launch(const float* q, Strided qs, const float* k, Strided ks, const float* v, Strided vs, const float* mask, float* z_qk,
+               float* x_scaled, float* attn, float* out, Strided os, int64_t B, int64_t H, int64_t N, float scale, hipStream_t stream);
+int bwd_rows_launch(const float* d_out, Strided dos, const float* k, Strided ks, const float* v, Strided vs, const float* attn, float* d_attn,
+                    float* rowdot, float* d_q, Strided dqs, int64_t B, int64_t H, int64_t N, float scale, int need_qk, hipStream_t stream);
+int bwd_cols_launch(const float* attn, const float* d_attn, const float* rowdot, const float* d_out, Strided dos, const float* q, Strided qs,
+                    float* d_v, Strided dvs, float* d_k, Strided dks, int64_t B, int64_t H, int64_t N, float scale, int need_qk,
+                    hipStream_t stream);
+}  // namespace te_attn_long
