@@ -771,6 +771,34 @@ int te_index_select_relprop_f64(const double* R, const double* X, double* out, i
 int te_gradcam_headmean_f64(const double* grad, const double* cam, double* out, int64_t B, int64_t H, int64_t N,
                             te_stream_t stream);
 
+/* ---- head_mask (csrc/te_headmask.hip) ---------------------------------------------------------------------------------
+ * Mul.relprop of BertSelfAttention for the operands [attention_probs, head_mask] (BERT.py:375-377; Mul is RelPropSimple,
+ * BERT_explainability/modules/layers_ours.py:49-61,77-79); the mask operand's relevance is discarded, as the reference does.
+ *   R, out [B,H,rows,cols] contiguous, in the relevance type; P [B,H,rows,cols] contiguous, in the operand type; the mask value
+ *   of plane (b, h) is m[b * m_sb + h] in the operand type, m_sb = 0: one mask for the whole batch (else m_sb >= H).
+ *     Z = P m ; S = sd(R, Z) ; out = P (S m)              every operation rounded on its own, in this order
+ *   _f32: all fp32.  _bf16: P and m bf16, read exactly, Z = float(P) float(m) (exact in fp32), R and out fp32.  _f64: all fp64.
+ *   out == R is allowed (each element is read before it is written).  A plane whose m is exactly 0 is written as zeros; its R and
+ *   P are not read.  One streaming pass without sums or atomics: 16-byte accesses from the first 16-byte boundary of `out`
+ *   inside each plane, single elements in front of it and at the tail; pointers need their element's alignment only.  The grid
+ *   is flat (B*H may exceed 65535); a batch equals its samples by construction.
+ *   TE_ERR_INVALID_ARG: a null pointer, a size <= 0, 0 < m_sb < H. */
+int te_mul_head_relprop_f32(const float* R, const float* P, const float* m, int64_t m_sb, float* out, int64_t B, int64_t H,
+                            int64_t rows, int64_t cols, te_stream_t stream);
+int te_mul_head_relprop_bf16(const float* R, const te_bf16_t* P, const te_bf16_t* m, int64_t m_sb, float* out, int64_t B,
+                             int64_t H, int64_t rows, int64_t cols, te_stream_t stream);
+int te_mul_head_relprop_f64(const double* R, const double* P, const double* m, int64_t m_sb, double* out, int64_t B, int64_t H,
+                            int64_t rows, int64_t cols, te_stream_t stream);
+/* Per-head relevance (Voita et al. 2019): out[b][h] = sum over n, d of R[b][h][n][d], R a strided [B,H,N,D] view with a
+ * contiguous last dimension (the 'b n (h d)' relevance entering an attention layer is read in place), out [B,H] fp64.
+ * One workgroup per (b, h); every addend enters an fp64 accumulator, and the order of the additions is fixed by the indices
+ * alone (spans of 4 per thread in index order, a shuffle tree, the waves in order; no atomics): a call repeated gives the same
+ * bits and a batch equals its samples.  TE_ERR_INVALID_ARG: a null pointer, a size <= 0, a negative stride, r_sn < D. */
+int te_head_relevance_f32(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, double* out, int64_t B, int64_t H,
+                          int64_t N, int64_t D, te_stream_t stream);
+int te_head_relevance_f64(const double* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, double* out, int64_t B, int64_t H,
+                          int64_t N, int64_t D, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

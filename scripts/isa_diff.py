@@ -11,8 +11,8 @@ entry of build.SOURCES (or only the files named) both trees' file is compiled wi
   * every distinct mangled symbol `_Z...` becomes `SYM<k>`, numbered in order of first appearance: moving a parameter type
     such as `Strided` out of an anonymous namespace renames the kernel and changes nothing else.
 
-One line per file: lines, sha256 of the old and of the new normalised listing, `same` / `DIFFERENT`.  Exit status 1 on any
-difference (the normalised listings of a differing file are kept in --keep DIR for `diff`).  Flags and the file list are the
+One line per file: lines, sha256 of the old and of the new normalised listing, `same` / `DIFFERENT` (`new`: a file OLD_TREE
+does not have).  Exit status 1 on any difference (the normalised listings of a differing file are kept in --keep DIR for `diff`).  Flags and the file list are the
 flags and the list of NEW_TREE's build.py.
 """
 import argparse
@@ -67,12 +67,18 @@ def main():
     unknown = [s for s in sources if s not in build.SOURCES]
     if unknown:
         sys.exit("not in build.SOURCES: " + " ".join(unknown))
+    # a translation unit that only NEW_TREE has (a new kernel file) is reported as `new`: there is nothing to compare it with
+    added = [s for s in sources if not os.path.exists(os.path.join(old_tree, PKG, "csrc", s))]
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max(1, min(a.j, MAX_JOBS))) as pool:
         jobs = {(side, s): pool.submit(listing, build, tree, s, os.path.join(tmp, "%s_%s.s" % (side, s)))
-                for s in sources for side, tree in (("old", old_tree), ("new", new_tree))}
+                for s in sources for side, tree in (("old", old_tree), ("new", new_tree)) if not (side == "old" and s in added)}
         different = 0
         print("%-22s %8s  %-16s %-16s" % ("file", "lines", "sha256 old", "sha256 new"))
         for s in sources:
+            if s in added:
+                new = jobs["new", s].result()
+                print("%-22s %8d  %-16s %-16s new" % (s, new.count("\n"), "-", hashlib.sha256(new.encode()).hexdigest()[:16]), flush=True)
+                continue
             old, new = jobs["old", s].result(), jobs["new", s].result()
             h_old, h_new = (hashlib.sha256(t.encode()).hexdigest()[:16] for t in (old, new))
             same = old == new
@@ -83,7 +89,8 @@ def main():
                 for side, t in (("old", old), ("new", new)):
                     with open(os.path.join(a.keep, "%s.%s.s" % (s, side)), "w") as f:
                         f.write(t)
-    print("%d of %d translation units differ" % (different, len(sources)))
+    print("%d of %d translation units differ%s" % (different, len(sources) - len(added),
+                                                   ", %d new" % len(added) if added else ""))
     return 1 if different else 0
 
 

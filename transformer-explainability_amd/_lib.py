@@ -168,6 +168,12 @@ SIGNATURES = {
     "te_clone_relprop_f64": (_I, [_P, _P, _P, _P, _P, _I64, _P]),
     "te_index_select_relprop_f64": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _P]),
     "te_gradcam_headmean_f64": (_I, [_P, _P, _P, _I64, _I64, _I64, _P]),
+    # head_mask: the Mul rule and the per-head relevance (csrc/te_headmask.hip)
+    "te_mul_head_relprop_f32": (_I, [_P, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+    "te_mul_head_relprop_bf16": (_I, [_P, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+    "te_mul_head_relprop_f64": (_I, [_P, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+    "te_head_relevance_f32": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+    "te_head_relevance_f64": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P]),
     # the z^B rule of a bf16 patch embedding (csrc/te_conv_bf16.hip)
     "te_conv2d_zb_relprop_bf16_supported": (_I, [_I64, _I64, _I64]),
     "te_conv2d_zb_relprop_bf16_workspace_bytes": (_SZ, [_I64] * 6),

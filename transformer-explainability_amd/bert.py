@@ -127,6 +127,10 @@ def make_bert_module(L):
             self.clone = L.Clone()
             self.head_mask = self.attention_mask = None
             self.attn_cam = self.attn = self.attn_gradients = None
+            # (extension, off by default) relprop stores ops.head_relevance of the relevance it receives: fp64 [B,H], the
+            # relevance arriving at each head's slice of the context layer (Generator.generate_head_relevance)
+            self.save_head_relevance = False
+            self.head_relevance = None
 
         def get_attn(self): return self.attn
         def save_attn(self, attn): self.attn = attn
@@ -142,14 +146,15 @@ def make_bert_module(L):
             return x.permute(0, 2, 1, 3).flatten(2)
 
         def forward(self, hidden_states, attention_mask=None, head_mask=None, **unused):
-            if head_mask is not None:
-                raise NotImplementedError("head_mask is off the accelerated path")
+            # head_mask ([B or 1, H, 1, 1], one value per head: BertModel.get_head_mask) is rewritten on every call, as in the
+            # reference (BERT.py:316): relprop runs the Mul rule only if THIS forward pass was masked.  A masked layer always
+            # takes the stock branch below, whatever ops.USE_FUSED_PRODUCERS says: the producer kernels know no mask.
             self.head_mask, self.attention_mask = head_mask, attention_mask
             h1, h2, h3 = self.clone(hidden_states, 3)
             self._fused_anchor = None
             B, N, _ = hidden_states.shape
             dt = hidden_states.dtype
-            if (ops.USE_FUSED_PRODUCERS and hidden_states.is_cuda and not self.training
+            if (head_mask is None and ops.USE_FUSED_PRODUCERS and hidden_states.is_cuda and not self.training
                     and ((dt == torch.float32 and ops.attention_forward_supported(N, self.attention_head_size))
                          or (dt == torch.bfloat16 and ops.attention_forward_bf16_supported(N, self.attention_head_size)))
                     and (attention_mask is None
@@ -166,7 +171,13 @@ def make_bert_module(L):
             self.save_attn(probs)
             if probs.requires_grad:
                 probs.register_hook(self.save_attn_gradients)
-            ctx = self.matmul2([self.dropout(probs), v])
+            probs = self.dropout(probs)
+            if head_mask is not None:
+                # BERT.py:355-356 through the Mul module, so that its hook caches [probs, head_mask] for the rule (the reference
+                # multiplies in place of calling self.mul, and its relprop then finds no operands); the accessor and the
+                # gradient hook above stay on the unmasked probabilities: d/d probs = head_mask . d/d (probs . head_mask)
+                probs = self.mul([probs, head_mask])
+            ctx = self.matmul2([probs, v])
             ctx = ctx.permute(0, 2, 1, 3).contiguous()
             return (ctx.view(*ctx.shape[:-2], self.all_head_size),)
 
@@ -196,13 +207,17 @@ def make_bert_module(L):
             B, N, C = cam.shape
             H, D = self.num_attention_heads, self.attention_head_size
             var = self.matmul2.variant
-            probs, v = self.matmul2.X
+            probs, v = self.matmul2.X             # (probs . head_mask of a masked layer: the AV rule's own operand)
             q, kt = self.matmul1.X
             rq = torch.empty((B, N, C), dtype=cam.dtype, device=cam.device)
             rk, rv = torch.empty_like(rq), torch.empty_like(rq)
             as_heads = lambda t: t.view(B, N, H, D).permute(0, 2, 1, 3)          # noqa: E731  (views)
+            if self.save_head_relevance:
+                self.head_relevance = ops.head_relevance(as_heads(cam))
             cam1, _ = ops.matmul_relprop_av(as_heads(cam), probs, v, out_scale=0.5, cam_v_out=as_heads(rv), variant=var,
                                             z=R_ours._cached_y(self.matmul2))
+            if self.head_mask is not None:
+                cam1, _ = self.mul.relprop(cam1, **kwargs)                          # BERT.py:375-377
             self.save_attn_cam(cam1)
             if getattr(self, "_stop_after_attn_cam", False):   # Generator(prune=True): nothing below is read
                 raise L.StopRelprop()
@@ -369,19 +384,30 @@ def make_bert_module(L):
         def get_input_embeddings(self):
             return self.embeddings.word_embeddings
 
+        def get_head_mask(self, head_mask, num_hidden_layers, is_attention_chunked=False, batch_size=None):
+            """Hugging Face's ModuleUtilsMixin.get_head_mask (BERT.py:612-616) for per-head masks: [H], [L,H] or, per sample,
+            [L,B,H] -> [L, 1 or B, H, 1, 1] in the model's dtype on its device; None -> [None] * L; any other shape is a
+            ValueError (rules.expand_head_mask)."""
+            par = next(self.parameters())
+            return R_ours.expand_head_mask(head_mask, num_hidden_layers, self.config.num_attention_heads, par.dtype,
+                                           batch_size, par.device)
+
         def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None,
                     head_mask=None, inputs_embeds=None, **unused):
             shape = input_ids.size() if input_ids is not None else inputs_embeds.size()[:-1]
             device = input_ids.device if input_ids is not None else inputs_embeds.device
+            head_mask = self.get_head_mask(head_mask, self.config.num_hidden_layers, batch_size=shape[0])
             if attention_mask is None:
                 attention_mask = torch.ones(shape, device=device)
             # transformers 3.5.1 get_extended_attention_mask: the mask cast to the parameters' dtype, then
             # (1 - mask)[:, None, None, :] * -10000 in that dtype (bf16: 0 / -9984)
             ext = (1.0 - attention_mask[:, None, None, :].to(next(self.parameters()).dtype)) * -10000.0
-            emb = self.embeddings(input_ids=input_ids, position_ids=position_ids, token_type_ids=token_type_ids,
-                                  inputs_embeds=inputs_embeds)
-            seq = self.encoder(emb, attention_mask=ext, head_mask=head_mask)[0]
-            return (seq, self.pooler(seq))
+            # a masked pass is a stock-forward pass, for every layer: the same bits whatever ops.USE_FUSED_PRODUCERS says
+            with (ops.stock_forward() if torch.is_tensor(head_mask) else ops._NULL):
+                emb = self.embeddings(input_ids=input_ids, position_ids=position_ids, token_type_ids=token_type_ids,
+                                      inputs_embeds=inputs_embeds)
+                seq = self.encoder(emb, attention_mask=ext, head_mask=head_mask)[0]
+                return (seq, self.pooler(seq))
 
         exploit_cls_sparsity = True   # exact; set False to evaluate the last layer densely
 

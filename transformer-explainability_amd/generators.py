@@ -97,6 +97,25 @@ def attn_rollout_tail(model, start_layer=0):
     return joint[:, 0, 1:]
 
 
+def _masked(head_mask) -> dict:
+    """The keyword a model call takes for a head mask -- nothing at all without one, so that models whose forward knows no
+    ``head_mask`` keep working."""
+    return {} if head_mask is None else {"head_mask": head_mask}
+
+
+def _head_relevance_chain(attn_modules, chain):
+    """Run ``chain()`` (one relprop chain) with every listed attention module storing ops.head_relevance of the relevance it
+    receives -> fp64 [B, L, H], layer 0 first."""
+    for m in attn_modules:
+        m.save_head_relevance, m.head_relevance = True, None
+    try:
+        chain()
+    finally:
+        for m in attn_modules:
+            m.save_head_relevance = False
+    return torch.stack([m.head_relevance for m in attn_modules], 1)
+
+
 def _refuse_before_forward(input, wanted):
     """The dtype refusals of the single-method calls, raised before the forward pass."""
     if "full" in wanted and ops._is_f64(input):
@@ -126,12 +145,14 @@ class LRP:
         # the relprop rules and the attention-gradient backward below them (model.prune_below_start_layer)
         self.prune = bool(prune)
 
-    def generate_LRP(self, input, index=None, method="transformer_attribution", is_ablation=False, start_layer=0):
+    def generate_LRP(self, input, index=None, method="transformer_attribution", is_ablation=False, start_layer=0,
+                     head_mask=None):
+        # head_mask (extension): one value per head, [H], [L,H] or [L,B,H] (VisionTransformer.get_head_mask)
         # a lost x6 hand-over of an EARLIER call is raised here, once, without synchronising (ops.x6_poll); NaN in a map
         # means exactly that -- check() asks about the calls made so far (and synchronises)
         if input.is_cuda:
             ops.x6_poll(input.device)
-        out = self._generate(input, index, method, is_ablation, start_layer)
+        out = self._generate(input, index, method, is_ablation, start_layer, head_mask)
         if input.is_cuda:
             ops.x6_post(input.device)
         return out
@@ -141,7 +162,7 @@ class LRP:
         NaN).  Synchronises the device: call it where the maps are read back anyway, never inside a step."""
         ops.x6_raise_if_failed(next(self.model.parameters()).device)
 
-    def generate_all(self, input, methods, index=None, is_ablation=False, start_layer=0):
+    def generate_all(self, input, methods, index=None, is_ablation=False, start_layer=0, head_mask=None):
         """(extension) The maps of several methods of the SAME batch from one pass: ``methods`` is any subset of the
         ``method=`` names of generate_LRP plus the two baselines as "attn_rollout" / "attn_gradcam" (served from this
         model: ``Baselines(self.model)``); returns {name: map}, each entry the shape, dtype and bits of the single call
@@ -152,7 +173,7 @@ class LRP:
         relprop for {"last_layer_attn", "attn_rollout"}, the last block's attention gradient alone for "attn_gradcam",
         one relprop chain for all relprop methods, which "full" continues below the blocks.  ``prune`` is honoured only
         when every requested method reads the blocks >= start_layer alone (methods.prunable); ``overlap_backward``, the
-        x6 status poll / post and the GELU-backward plane hand-off behave as in generate_LRP.  An unknown name raises
+        x6 status poll / post, the GELU-backward plane hand-off and ``head_mask`` behave as in generate_LRP.  An unknown name raises
         ValueError, the dtype refusals of the single calls raise their TeError, both before the forward pass."""
         wanted = M.check(methods, M.LRP_NEEDS)
         _refuse_before_forward(input, wanted)
@@ -160,16 +181,16 @@ class LRP:
             raise ops._lib.TeError(f"{ops.DTYPES_MSG}; got {input.dtype} here")
         if input.is_cuda:
             ops.x6_poll(input.device)
-        out = self._generate_all(input, wanted, index, is_ablation, start_layer)
+        out = self._generate_all(input, wanted, index, is_ablation, start_layer, head_mask)
         if input.is_cuda:
             ops.x6_post(input.device)
         return out
 
-    def _generate_all(self, input, wanted, index, is_ablation, start_layer):
+    def _generate_all(self, input, wanted, index, is_ablation, start_layer, head_mask=None):
         need = M.needs(wanted, M.LRP_NEEDS, is_ablation, M.LRP_ABLATION_NEEDS)
         model = self.model
         with ops.gelu_backward_plane_handoff():      # this call drives the backward pass itself (attention tensors only)
-            output = model(input)
+            output = model(input, **_masked(head_mask))
         ours = tuple(m for m in wanted if m not in M.BASELINE_METHODS)       # the tails of model.relprop
         maps = {}
         if not need.forward_only:
@@ -201,10 +222,27 @@ class LRP:
             maps["attn_gradcam"] = cam_attn_tail(model)
         return {m: maps[m] for m in wanted}
 
-    def _generate(self, input, index, method, is_ablation, start_layer):
+    def generate_head_relevance(self, input, index=None, head_mask=None):
+        """(extension) Per-head relevance in the sense of Voita et al. 2019: fp64 [B, L, H], entry (b, l, h) the sum of the
+        relevance that arrives at head h's slice of block l's context layer (the argument of Attention.relprop_after_proj).
+        One forward pass and one relprop chain; no backward pass, no map.  ``head_mask`` as in generate_LRP: the scores of
+        the masked model."""
+        model = self.model
+        with torch.no_grad():
+            output = model(input, **_masked(head_mask))
+        one_hot = _one_hot(output, index)
+        user_flag = model.prune_below_start_layer      # the whole chain runs, whatever the model's prune flag says
+        model.prune_below_start_layer = False
+        try:
+            return _head_relevance_chain([blk.attn for blk in model.blocks],
+                                         lambda: model.relprop(one_hot, method=(), alpha=1))
+        finally:
+            model.prune_below_start_layer = user_flag
+
+    def _generate(self, input, index, method, is_ablation, start_layer, head_mask=None):
         _refuse_before_forward(input, (method,))
         with ops.gelu_backward_plane_handoff():      # this call drives the backward pass itself (attention tensors only)
-            output = self.model(input)
+            output = self.model(input, **_masked(head_mask))
         kwargs = {"alpha": 1}
         one_hot = _one_hot(output, index)
         loss = torch.sum(one_hot * output)
@@ -407,11 +445,12 @@ class Generator:
         """As LRP.check(): raise if an x6 Linear kernel lost a hand-over since the last check (synchronises)."""
         ops.x6_raise_if_failed(next(self.model.parameters()).device)
 
-    def _explain(self, input_ids, attention_mask, index, lowest_layer=0):
+    def _explain(self, input_ids, attention_mask, index, lowest_layer=0, head_mask=None):
         """forward, attention-gradient backward, relprop.  With prune=True only the layers >= lowest_layer are served."""
-        return self._pass(input_ids, attention_mask, index, lowest_layer)[0]
+        return self._pass(input_ids, attention_mask, index, lowest_layer, head_mask=head_mask)[0]
 
-    def _pass(self, input_ids, attention_mask, index, lowest_layer=0, grads="all", relprop=True, prune=None):
+    def _pass(self, input_ids, attention_mask, index, lowest_layer=0, grads="all", relprop=True, prune=None,
+              head_mask=None):
         """One pass: forward; the attention gradients of ``grads`` ("all": the layers served, "last": the last layer
         alone, None: no backward pass); the relprop chain if ``relprop``.  prune (default: self.prune): only the layers
         >= lowest_layer are served.  -> (the encoder layers, what model.relprop returned or None)."""
@@ -420,10 +459,10 @@ class Generator:
         layers = self.model.bert.encoder.layer
         if grads is None and not relprop:            # forward only: as generate_attn_last_layer / generate_rollout
             with torch.no_grad():
-                self.model(input_ids=input_ids, attention_mask=attention_mask)
+                self.model(input_ids=input_ids, attention_mask=attention_mask, **_masked(head_mask))
             return layers, None
         with ops.gelu_backward_plane_handoff():      # this call drives the backward pass itself (attention tensors only)
-            output = self.model(input_ids=input_ids, attention_mask=attention_mask)[0]
+            output = self.model(input_ids=input_ids, attention_mask=attention_mask, **_masked(head_mask))[0]
         one_hot = _one_hot(output, index)
         loss = torch.sum(one_hot * output)
         first = lowest_layer if prune else 0
@@ -460,14 +499,16 @@ class Generator:
             cam.record_stream(main)
         return layers, cam
 
-    def generate_all(self, input_ids, attention_mask, methods, index=None, start_layer=11, rollout_start_layer=0):
+    def generate_all(self, input_ids, attention_mask, methods, index=None, start_layer=11, rollout_start_layer=0,
+                     head_mask=None):
         """(extension) The vectors of several methods of the SAME batch from one pass: ``methods`` is any subset of
         "LRP", "LRP_last_layer", "full_lrp", "attn_last_layer", "rollout", "attn_gradcam" (the generate_* methods);
         returns {name: vector}, each entry the shape, dtype and bits of the single call (generate_LRP with
         ``start_layer``, generate_rollout with ``rollout_start_layer``).  One forward pass and at most one backward
         pass and one relprop chain, only as far as the union of the methods needs (methods.GENERATOR_NEEDS); "full_lrp"
         keeps what model.relprop returns.  ``prune`` is honoured only when every requested method reads the layers it
-        serves alone (methods.prunable).  An unknown name raises ValueError before the forward pass."""
+        serves alone (methods.prunable).  An unknown name raises ValueError before the forward pass.  ``head_mask``: as in
+        the single calls."""
         wanted = M.check(methods, M.GENERATOR_NEEDS)
         need = M.needs(wanted, M.GENERATOR_NEEDS)
         if input_ids.is_cuda:
@@ -477,7 +518,7 @@ class Generator:
         lowest = start_layer if "LRP" in wanted else n_layers - 1
         _, cam = self._pass(input_ids, attention_mask, index, lowest_layer=lowest,
                             grads="all" if need.all_grads else "last" if need.last_grad else None,
-                            relprop=need.relprop, prune=pruned)
+                            relprop=need.relprop, prune=pruned, head_mask=head_mask)
         tails = {"LRP": lambda: lrp_tail(self.model, start_layer, pruned),
                  "LRP_last_layer": lambda: lrp_last_layer_tail(self.model),
                  "full_lrp": lambda: full_lrp_tail(cam),
@@ -489,10 +530,11 @@ class Generator:
             ops.x6_post(input_ids.device)
         return out
 
-    def generate_LRP(self, input_ids, attention_mask, index=None, start_layer=11):
+    def generate_LRP(self, input_ids, attention_mask, index=None, start_layer=11, head_mask=None):
+        # head_mask (the model's own argument, BERT.py:556-625): one value per head, [H], [L,H] or, per sample, [L,B,H]
         if input_ids.is_cuda:
             ops.x6_poll(input_ids.device)        # a lost x6 hand-over of an earlier call: raised once, no synchronisation
-        self._explain(input_ids, attention_mask, index, lowest_layer=start_layer)
+        self._explain(input_ids, attention_mask, index, lowest_layer=start_layer, head_mask=head_mask)
         out = self.attribution_tail(start_layer)
         if input_ids.is_cuda:
             ops.x6_post(input_ids.device)
@@ -502,16 +544,17 @@ class Generator:
         """ExplanationGenerator.py:47-59 on the attn_cam / attention gradients cached by relprop + backward."""
         return lrp_tail(self.model, start_layer, self.prune)
 
-    def generate_LRP_last_layer(self, input_ids, attention_mask, index=None):
+    def generate_LRP_last_layer(self, input_ids, attention_mask, index=None, head_mask=None):
         """ExplanationGenerator.py:62-84: head-mean of the last layer's attn_cam, CLS row, CLS slot zeroed."""
-        self._explain(input_ids, attention_mask, index, lowest_layer=len(self.model.bert.encoder.layer) - 1)
+        self._explain(input_ids, attention_mask, index, lowest_layer=len(self.model.bert.encoder.layer) - 1,
+                      head_mask=head_mask)
         return lrp_last_layer_tail(self.model)
 
-    def generate_full_lrp(self, input_ids, attention_mask, index=None):
+    def generate_full_lrp(self, input_ids, attention_mask, index=None, head_mask=None):
         """ExplanationGenerator.py:86-106: relevance propagated to the encoder input, summed over the hidden
         dimension, CLS slot zeroed."""
         with ops.gelu_backward_plane_handoff():      # this call drives the backward pass itself (attention tensors only)
-            output = self.model(input_ids=input_ids, attention_mask=attention_mask)[0]
+            output = self.model(input_ids=input_ids, attention_mask=attention_mask, **_masked(head_mask))[0]
         one_hot = _one_hot(output, index)
         layers = self.model.bert.encoder.layer
         # relprop reads the attention gradients nowhere, but the reference runs the backward first (:100-101) and the
@@ -519,23 +562,35 @@ class Generator:
         _attention_gradients(torch.sum(one_hot * output), [lay.attention.self for lay in layers])
         return full_lrp_tail(self.model.relprop(one_hot, alpha=1))
 
-    def generate_attn_last_layer(self, input_ids, attention_mask, index=None):
+    def generate_attn_last_layer(self, input_ids, attention_mask, index=None, head_mask=None):
         """ExplanationGenerator.py:108-114: head-mean of the last layer's attention probabilities, CLS row."""
         with torch.no_grad():
-            self.model(input_ids=input_ids, attention_mask=attention_mask)
+            self.model(input_ids=input_ids, attention_mask=attention_mask, **_masked(head_mask))
         return attn_last_layer_tail(self.model)
 
-    def generate_rollout(self, input_ids, attention_mask, start_layer=0, index=None):
+    def generate_rollout(self, input_ids, attention_mask, start_layer=0, index=None, head_mask=None):
         """ExplanationGenerator.py:116-127: row-normalised rollout of the head-averaged attention probabilities."""
         with torch.no_grad():
-            self.model(input_ids=input_ids, attention_mask=attention_mask)
+            self.model(input_ids=input_ids, attention_mask=attention_mask, **_masked(head_mask))
         return rollout_tail(self.model, start_layer)
 
-    def generate_attn_gradcam(self, input_ids, attention_mask, index=None):
+    def generate_attn_gradcam(self, input_ids, attention_mask, index=None, head_mask=None):
         """ExplanationGenerator.py:129-155: last layer's attention x its per-head mean gradient, head-mean, clamped,
         min-max normalised over the whole [N, N] map, CLS row with the CLS slot zeroed."""
-        self._explain(input_ids, attention_mask, index, lowest_layer=len(self.model.bert.encoder.layer) - 1)
+        self._explain(input_ids, attention_mask, index, lowest_layer=len(self.model.bert.encoder.layer) - 1,
+                      head_mask=head_mask)
         return attn_gradcam_tail(self.model)
+
+    def generate_head_relevance(self, input_ids, attention_mask, index=None, head_mask=None):
+        """(extension) Per-head relevance in the sense of Voita et al. 2019: fp64 [B, L, H], entry (b, l, h) the sum of the
+        relevance that arrives at head h's slice of layer l's context layer (``cam`` at the top of
+        BertSelfAttention.relprop).  One forward pass and one relprop chain; no backward pass.  ``head_mask``: the scores of
+        the masked model."""
+        with torch.no_grad():
+            output = self.model(input_ids=input_ids, attention_mask=attention_mask, **_masked(head_mask))[0]
+        one_hot = _one_hot(output, index)
+        return _head_relevance_chain([lay.attention.self for lay in self.model.bert.encoder.layer],
+                                     lambda: self.model.relprop(one_hot, alpha=1))
 
 
 # ----------------------------------------------------------------------------------------------------------------------

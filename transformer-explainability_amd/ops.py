@@ -727,6 +727,21 @@ def matmul_relprop_qk(R: Tensor, q: Tensor, k: Tensor, out_scale: float = 1.0,
 USE_FUSED_PRODUCERS = False
 
 
+class stock_forward:
+    """``with ops.stock_forward(): model(...)``: this forward pass runs on stock PyTorch whatever USE_FUSED_PRODUCERS says
+    (the flag is read while the graph is built; the backward pass follows the nodes that were recorded).  A head-masked pass
+    of BertModel / VisionTransformer runs inside it: the attention producers know no mask, and with every other producer off
+    as well a masked pass gives the same bits under either setting of the flag."""
+
+    def __enter__(self):
+        global USE_FUSED_PRODUCERS
+        self.was, USE_FUSED_PRODUCERS = USE_FUSED_PRODUCERS, False
+
+    def __exit__(self, *exc):
+        global USE_FUSED_PRODUCERS
+        USE_FUSED_PRODUCERS = self.was
+
+
 def attention_forward_supported(N: int, D: int) -> bool:
     """One of the producer kernel families takes the shape: the one-workgroup-per-head kernels (N <= 224) or the
     row-tile kernels of csrc/te_attn_long.hip (N <= 640)."""
@@ -1918,3 +1933,65 @@ def rollout_f64(cams: Tensor, start_layer: int = 0, normalise: bool = False, cls
         joint = joint.clone()
         joint[:, 0, 0] = joint[:, 0].min(dim=-1).values
     return joint[:, 0] if row0_only else joint
+
+
+# ---------------------------------------------------------------------------------------- head_mask
+def _head_mask_rows(m: Tensor, B: int, H: int) -> Tuple[Tensor, int]:
+    """The mask operand of Mul.relprop, anything that broadcasts as [B or 1, H, 1, 1] -> (contiguous [B or 1, H], the
+    batch stride the kernel takes: 0 = one mask for the whole batch)."""
+    if m.numel() == H and (m.dim() < 2 or m.shape[-3:] == (H, 1, 1) or m.shape[-1] == H):
+        return m.reshape(1, H).contiguous(), 0
+    if m.numel() == B * H and m.shape[0] == B and (tuple(m.shape[1:]) in ((H,), (H, 1, 1))):
+        return m.reshape(B, H).contiguous(), H
+    raise _lib.TeError(f"Mul.relprop: a head mask must broadcast as [B or 1, H, 1, 1] = [{B} or 1, {H}, 1, 1], got "
+                       f"{tuple(m.shape)}")
+
+
+def mul_head_relprop(R: Tensor, P: Tensor, m: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """Mul.relprop for [attention_probs, head_mask] (BERT.py:375-377): R, P [B,H,rows,cols], m one value per head
+    ([H], [1|B,H] or [1|B,H,1,1]) -> P . (sd(R, P . m) . m), the relevance of P; the mask's relevance is discarded.
+    Dispatch on the operand dtype as the other rules: fp32 throughout, bf16 P and m with fp32 relevance, fp64 throughout.
+    ``out``: a contiguous destination of R's shape and dtype; ``out is R`` is allowed.  Never synchronises."""
+    if R.dim() != 4 or tuple(P.shape) != tuple(R.shape):
+        raise _lib.TeError(f"Mul.relprop: relevance {tuple(R.shape)} and operand {tuple(P.shape)} must both be [B,H,rows,cols]")
+    B, H, rows, cols = R.shape
+    if _any_f64(R, P, m, out):
+        _f64_rule("ours", 1.0, "Mul.relprop", R=R, P=P, m=m, out=out)
+        R, P, sfx = R.contiguous(), P.contiguous(), "f64"
+    else:
+        bf = _is_bf16(P) or _is_bf16(m)
+        want = (torch.float32, torch.bfloat16, torch.bfloat16) if bf else (torch.float32,) * 3
+        if (R.dtype, P.dtype, m.dtype) != want:      # (the dtypes before the device: a mixed call is refused as such)
+            raise _lib.TeError(f"{DTYPES_MSG}; Mul.relprop got relevance {R.dtype}, operand {P.dtype}, mask {m.dtype}")
+        R, P, m, sfx = _c(R), (_c16(P) if bf else _c(P)), (_prep_bf16(m) if bf else _prep(m)), ("bf16" if bf else "f32")
+    m2, m_sb = _head_mask_rows(m, B, H)
+    if out is None:
+        out = torch.empty_like(R)
+    elif out.dtype != R.dtype or tuple(out.shape) != tuple(R.shape) or not out.is_contiguous() or out.device != R.device:
+        raise _lib.TeError(f"Mul.relprop: out must be a contiguous {R.dtype} {tuple(R.shape)} on {R.device}")
+    nb = float(R.numel()) * (2 * R.element_size() + P.element_size())
+    with _on_device(P) as lib, _timed("mul_head_" + sfx, 0.0, nb):
+        _lib.check(getattr(lib, "te_mul_head_relprop_" + sfx)(_ptr(R), _ptr(P), _ptr(m2), m_sb, _ptr(out), B, H, rows, cols,
+                                                              _stream(P)), "te_mul_head_relprop_" + sfx)
+    return out
+
+
+def head_relevance(R_heads: Tensor) -> Tensor:
+    """R_heads [B,H,N,D], any strided view with a contiguous last dim (fp32 or fp64 relevance) -> fp64 [B,H], the sum over
+    (n, d) per head in a fixed order (te_head_relevance_*): the relevance that arrives at each head's slice of the context
+    layer."""
+    if R_heads.dim() != 4:
+        raise _lib.TeError(f"head_relevance: expected a [B,H,N,D] view of the relevance, got {tuple(R_heads.shape)}")
+    if _is_f64(R_heads):
+        _f64_rule("ours", 1.0, "head_relevance", R=R_heads)
+        sfx = "f64"
+    else:
+        _prep(R_heads)
+        sfx = "f32"
+    R, sb, sh, sn = _bhnd64(R_heads)
+    B, H, N, D = R.shape
+    out = torch.empty((B, H), dtype=torch.float64, device=R.device)
+    with _on_device(R) as lib, _timed("head_relevance", 0.0, float(R.numel()) * R.element_size()):
+        _lib.check(getattr(lib, "te_head_relevance_" + sfx)(_ptr(R), sb, sh, sn, _ptr(out), B, H, N, D, _stream(R)),
+                   "te_head_relevance_" + sfx)
+    return out

@@ -10,8 +10,9 @@ here ``relprop`` calls one fused closed-form kernel through the C ABI (include/t
 Batch semantics: the reference is batch-1 only; a batch of B samples is B independent batch-1
 problems (Add's "whole tensor" sums are per sample).  With B = 1 the results match the reference.
 
-Off the accelerated hot path ("API surface"): BatchNorm2d / pools / Cat / AddEye /
-Mul keep their forward so models build and run, but their relprop raises NotImplementedError here.
+Off the accelerated hot path ("API surface"): BatchNorm2d / pools / Cat / AddEye keep their
+forward so models build and run, but their relprop raises NotImplementedError here; so does Mul for every product other
+than the head mask of an attention layer (csrc/te_headmask.hip).
 Conv2d.relprop (method="full": the patch embedding's z^B rule, layers_ours.py:256-286) is implemented
 (csrc/te_conv.hip).
 """
@@ -318,8 +319,51 @@ class _OffPath(RelProp):
 
 
 class Mul(_OffPath):
+    """BERT_explainability/modules/layers_ours.py:77-79 (RelPropSimple).  Accelerated: the head mask of BertSelfAttention,
+    operands [tensor [B,H,rows,cols], mask broadcastable to [B or 1, H, 1, 1]] (BERT.py:356,375-377) ->
+    te_mul_head_relprop_*; returns [relevance of the tensor, None]: the reference discards the mask's relevance, and it
+    is not computed here.  Any other product is off the transformer path."""
+
     def forward(self, inputs):
         return torch.mul(*inputs)
+
+    @staticmethod
+    def is_head_mask(x0, x1) -> bool:
+        if not (torch.is_tensor(x0) and torch.is_tensor(x1)) or x0.dim() != 4 or x1.dim() != 4:
+            return False
+        B, H = x0.shape[:2]
+        return x1.shape[0] in (1, B) and tuple(x1.shape[1:]) == (H, 1, 1)
+
+    def relprop(self, R, alpha):
+        X = getattr(self, "X", None)
+        if not isinstance(X, (list, tuple)) or len(X) != 2 or not self.is_head_mask(*X):
+            return super().relprop(R, alpha)
+        return ops.mul_head_relprop(R, X[0], X[1]), None
+
+
+def expand_head_mask(head_mask, num_layers: int, num_heads: int, dtype=None, batch_size=None, device=None):
+    """``get_head_mask`` of Hugging Face's ModuleUtilsMixin (called at BERT.py:612-616), for the masks the kernels take: one
+    value per head.  [H] (every layer alike), [L,H], or -- an extension -- per sample [L,B,H]; any finite values.  Returns
+    ``[None] * L`` for None, else a [L, 1 or B, H, 1, 1] tensor in ``dtype`` on ``device`` (Hugging Face casts the mask to the
+    model's dtype as well), so that ``mask[i]`` broadcasts against layer i's [B,H,N,N] probabilities.  Any other shape -- the [..,N,N]
+    expansion of Hugging Face included -- is a ValueError, raised here, before the forward pass."""
+    if head_mask is None:
+        return [None] * num_layers
+    m = torch.as_tensor(head_mask)
+    L, H = num_layers, num_heads
+    if m.dim() == 1 and m.shape[0] == H:
+        m = m.view(1, 1, H).expand(L, 1, H)
+    elif m.dim() == 2 and tuple(m.shape) == (L, H):
+        m = m.view(L, 1, H)
+    elif m.dim() == 3 and m.shape[0] == L and m.shape[2] == H and (batch_size is None or m.shape[1] in (1, batch_size)):
+        pass
+    else:
+        per_sample = f"[{L},B,{H}]" if batch_size is None else f"[{L},{batch_size},{H}]"
+        raise ValueError(f"head_mask must have one value per head: shape [{H}], [{L},{H}] or {per_sample} "
+                         f"(layers, samples, heads); got {tuple(m.shape)}")
+    if dtype is None:
+        dtype = m.dtype if m.is_floating_point() else torch.float32
+    return m.to(device=device, dtype=dtype)[..., None, None]
 
 
 class AddEye(_OffPath):

@@ -237,7 +237,13 @@ def make_vit_module(L):
             self.proj = L.Linear(dim, dim)
             self.proj_drop = L.Dropout(proj_drop)
             self.softmax = L.Softmax(dim=-1)
+            self.mul = L.Mul()                              # (extension: the head mask, as BertSelfAttention.mul)
             self.attn_cam = self.attn = self.v = self.v_cam = self.attn_gradients = None
+            self.head_mask = None
+            # (extension, off by default) relprop_after_proj stores ops.head_relevance of the relevance it receives: fp64
+            # [B,H] (LRP.generate_head_relevance)
+            self.save_head_relevance = False
+            self.head_relevance = None
 
         # accessors of ViT_LRP.py:102-130
         def get_attn(self): return self.attn
@@ -254,11 +260,15 @@ def make_vit_module(L):
         def save_attn_gradients(self, g): self.attn_gradients = g
         def get_attn_gradients(self): return self.attn_gradients
 
-        def forward(self, x):
+        def forward(self, x, head_mask=None):
+            """head_mask (extension; the reference ViT has none): [B or 1, H, 1, 1], one value per head, with the semantics of
+            BertSelfAttention (BERT.py:345-358): the probabilities are multiplied by it after the accessor and the gradient hook
+            took the unmasked ones.  Rewritten on every call; a masked block always takes the stock branch."""
             B, N, C = x.shape
             H = self.num_heads
             self._fused_anchor = None
-            if ops.USE_FUSED_PRODUCERS and x.is_cuda and not self.training and (
+            self.head_mask = head_mask
+            if head_mask is None and ops.USE_FUSED_PRODUCERS and x.is_cuda and not self.training and (
                     (x.dtype == torch.float32 and ops.attention_forward_supported(N, C // H))
                     or (x.dtype == torch.bfloat16 and ops.attention_forward_bf16_supported(N, C // H))):
                 return self._forward_fused(x)
@@ -268,6 +278,8 @@ def make_vit_module(L):
             self.save_attn(attn)
             if attn.requires_grad:
                 attn.register_hook(self.save_attn_gradients)
+            if head_mask is not None:
+                attn = self.mul([attn, head_mask])
             out = self.matmul2([attn, v]).permute(0, 2, 1, 3).reshape(B, N, C)  # 'b h n d -> b n (h d)'
             return self.proj_drop(self.proj(out))
 
@@ -303,6 +315,8 @@ def make_vit_module(L):
             H = self.num_heads
             D = C // H
             r_heads = cam.view(B, N, H, D).permute(0, 2, 1, 3)                  # strided view, no copy
+            if self.save_head_relevance:
+                self.head_relevance = ops.head_relevance(r_heads)
             attn, v = self.matmul2.X
             q, k = self.matmul1.X
             cam_qkv = torch.empty((B, N, 3 * C), dtype=cam.dtype, device=cam.device)
@@ -311,6 +325,8 @@ def make_vit_module(L):
             cam1, cam_v = ops.matmul_relprop_av(r_heads, attn, v, out_scale=0.5, cam_v_out=slots[2], variant=var,
                                                 z=R_ours._cached_y(self.matmul2))
             self.save_v_cam(cam_v)
+            if self.head_mask is not None:
+                cam1, _ = self.mul.relprop(cam1, **kwargs)                      # the Mul rule of BERT.py:375-377
             self.save_attn_cam(cam1)
             if getattr(self, "_stop_after_attn_cam", False):
                 raise L.StopRelprop()
@@ -330,9 +346,9 @@ def make_vit_module(L):
             self.clone1 = L.Clone()
             self.clone2 = L.Clone()
 
-        def forward(self, x):
+        def forward(self, x, head_mask=None):
             x1, n = self._clone_norm(self.clone1, self.norm1, x)
-            x = self.add1([x1, self.attn(n)])
+            x = self.add1([x1, self.attn(n) if head_mask is None else self.attn(n, head_mask)])
             x1, n = self._clone_norm(self.clone2, self.norm2, x)
             return self.add2([x1, self.mlp(n)])
 
@@ -456,19 +472,29 @@ def make_vit_module(L):
         def no_weight_decay(self):
             return {'pos_embed', 'cls_token'}
 
-        def forward(self, x, register_hook=False):
+        def get_head_mask(self, head_mask, batch_size=None):
+            """[H], [L,H] or, per sample, [L,B,H] -> [L, 1 or B, H, 1, 1] in the model's dtype on its device; None ->
+            [None] * L; any other shape is a ValueError (rules.expand_head_mask, as BertModel.get_head_mask)."""
+            return R_ours.expand_head_mask(head_mask, len(self.blocks), self.blocks[0].attn.num_heads, self.pos_embed.dtype,
+                                           batch_size, self.pos_embed.device)
+
+        def forward(self, x, register_hook=False, head_mask=None):
             # register_hook (ViT_new.py:195): the attention-gradient hook is always registered when a graph is built
+            # head_mask (extension): one value per head, see get_head_mask; refused here, before anything runs, if misshapen
             B = x.shape[0]
-            x = self.patch_embed(x)
-            x = torch.cat((self.cls_token.expand(B, -1, -1), x), dim=1)
-            x = self.add([x, self.pos_embed])
-            if x.requires_grad:
-                x.register_hook(self.save_inp_grad)
-            for blk in self.blocks:
-                x = blk(x)
-            x = self.norm(x)
-            x = self.pool(x, dim=1, indices=self._cls_index).squeeze(1)   # (a device tensor made once: graph-capturable)
-            return self.head(x)
+            head_mask = self.get_head_mask(head_mask, B)
+            # a masked pass is a stock-forward pass, for every layer: the same bits whatever ops.USE_FUSED_PRODUCERS says
+            with (ops.stock_forward() if torch.is_tensor(head_mask) else ops._NULL):
+                x = self.patch_embed(x)
+                x = torch.cat((self.cls_token.expand(B, -1, -1), x), dim=1)
+                x = self.add([x, self.pos_embed])
+                if x.requires_grad:
+                    x.register_hook(self.save_inp_grad)
+                for blk, hm in zip(self.blocks, head_mask):
+                    x = blk(x) if hm is None else blk(x, hm)
+                x = self.norm(x)
+                x = self.pool(x, dim=1, indices=self._cls_index).squeeze(1)   # (a device tensor made once: graph-capturable)
+                return self.head(x)
 
         # ------------------------------------------------------------------------------------------
         def relprop(self, cam=None, method=None, is_ablation=False, start_layer=0, **kwargs):
