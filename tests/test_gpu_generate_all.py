@@ -264,6 +264,25 @@ def test_state_left_on_the_model_and_no_spill_over(kind):
     assert torch.equal(LRP(model).generate_LRP(x, index=index, start_layer=1), plain)
 
 
+# ------------------------------------------------------------------------------------------------ captured single call
+@pytest.mark.parametrize("overlap", [False, True])
+def test_graphed_lrp_replays_with_the_class_indices_in_force(overlap):
+    """GraphedLRP with class indices: they are the graph's second static input.  A replay with other indices, and one without
+    any (the last ones stay in force), are bitwise the eager generate_LRP with those indices."""
+    from transformer_explainability_amd.generators import LRP, GraphedLRP
+    model, x, _ = vit_model("w128-f32")
+    lrp = LRP(model, overlap_backward=overlap)
+    captured, other = [1, 15, 6], [6, 1, 15]
+    want = {tuple(i): lrp.generate_LRP(x, index=i, method="transformer_attribution", start_layer=1).clone()
+            for i in (captured, other)}
+    assert not torch.equal(want[tuple(captured)], want[tuple(other)])         # (the indices do decide the maps)
+    glrp = GraphedLRP(lrp, x, index=captured, method="transformer_attribution", start_layer=1)
+    assert same(glrp(x, index=other), want[tuple(other)])
+    assert same(glrp(x), want[tuple(other)])
+    assert same(glrp(x, index=captured), want[tuple(captured)])
+    lrp.check()
+
+
 # ------------------------------------------------------------------------------------------------ sweep
 def test_sweep_all_stores_equal_the_single_sweeps(tmp_path):
     from test_sweep import ToyImages, _generators

@@ -9,11 +9,14 @@ Same method names and arguments; differences (results identical at batch 1):
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 import torch
 
 from . import methods as M
 from . import ops
+from .rules import StopRelprop, stop_after_attn_cam
 from .vit import relprop_tail
 
 
@@ -125,42 +128,114 @@ def _refuse_before_forward(input, wanted):
                                "torch.float64 model: run it on a float32 or bfloat16 model")
 
 
-class LRP:
+@contextlib.contextmanager
+def _x6_bracket(t):
+    """Around a public call on the batch ``t``: a lost x6 hand-over of an EARLIER call is raised before it, once, without
+    synchronising (ops.x6_poll; NaN in a map means exactly that -- check() asks about the calls made so far, and
+    synchronises); the status word is posted to the host after it (ops.x6_post), not after a call that raised."""
+    if t.is_cuda:
+        ops.x6_poll(t.device)
+    yield
+    if t.is_cuda:
+        ops.x6_post(t.device)
+
+
+@contextlib.contextmanager
+def _prune_flag(model, value):
+    """The model's prune_below_start_layer flag is ``value`` for THIS call only: a user's own setting of it (and direct
+    model.relprop calls afterwards) are unaffected."""
+    user_flag = model.prune_below_start_layer
+    model.prune_below_start_layer = value
+    try:
+        yield
+    finally:
+        model.prune_below_start_layer = user_flag
+
+
+class _PassDriver:
+    """What LRP and Generator share: the options, check() and the one implementation of "attention gradients, then -- or,
+    with overlap_backward, beside them -- the relprop chain"."""
+
+    def __init__(self, model, overlap_backward, prune):
+        self.model = model
+        self.model.eval()
+        # (extension) the relprop chain reads only forward caches; the attention gradients are needed by the tail
+        # alone.  With overlap_backward the backward pass (main stream) and the relprop rules (side stream) run
+        # concurrently and join before the head-mean / rollout tail: the memory-bound backward kernels and the tails
+        # of the MFMA-bound Linear.relprop launches fill each other's idle CUs.  Same kernels, same results, bit for bit.
+        self.overlap_backward = bool(overlap_backward)
+        self._relprop_stream = None
+        # (extension, off by default) serve only the blocks / layers a method reads: see LRP and Generator
+        self.prune = bool(prune)
+
+    def check(self):
+        """Raise TeError if any x6 Linear kernel since the last check lost a stream-K hand-over (the affected maps carry
+        NaN).  Synchronises the device: call it where the maps are read back anyway, never inside a step."""
+        ops.x6_raise_if_failed(next(self.model.parameters()).device)
+
+    def _gradients_and_chain(self, loss, attn_modules, chain, tail_owner=None):
+        """The attention gradients of ``attn_modules`` (none: no backward pass), then what ``chain()`` returns (None: no
+        chain).  tail_owner: a model whose relprop runs the tail itself (ViT) and calls ``_before_tail`` in front of it."""
+        if chain is None or not (self.overlap_backward and loss.is_cuda):
+            if attn_modules:
+                _attention_gradients(loss, attn_modules)
+            return None if chain is None else chain()
+        dev = loss.device
+        main = torch.cuda.current_stream(dev)
+        if self._relprop_stream is None:
+            self._relprop_stream = torch.cuda.Stream(device=dev)
+        side = self._relprop_stream
+        side.wait_stream(main)                      # forward caches + one-hot are complete
+        # backward on the main stream (autograd runs each node on its forward op's stream)
+        if attn_modules:
+            _attention_gradients(loss, attn_modules)
+        if tail_owner is not None:
+            # (only then: every other caller runs its tail after the join below, and an event nobody waits on is one more
+            # node in a captured graph)
+            grads_ready = main.record_event()
+            tail_owner._before_tail = lambda: torch.cuda.current_stream(dev).wait_event(grads_ready)
+        try:
+            with torch.cuda.stream(side):
+                out = chain()
+        finally:
+            if tail_owner is not None:
+                tail_owner._before_tail = None
+            main.wait_stream(side)                  # whatever follows (head-mean, rollout) reads both streams' results
+        if not torch.cuda.is_current_stream_capturing():
+            for t in (out.values() if isinstance(out, dict) else (out,)):
+                if t is not None:
+                    t.record_stream(main)
+        return out
+
+
+class LRP(_PassDriver):
     """baselines/ViT/ViT_explanation_generator.py:20-41.  Batched: B inputs -> B maps (B = 1 is the reference's call).
 
     (The round-1 ``streams`` extension -- micro-batches on separate HIP streams -- is gone: it stopped making progress at
     batch 64 for reasons never diagnosed, and since round 3 the Linear rules run on persistent whole-chip kernels that
     two streams could only serialise.)"""
 
+    # what every single-method call runs, as the reference does: every attention gradient and the whole chain
+    _SINGLE_CALL_NEED = M.Needs(all_grads=True, relprop=True)
+
     def __init__(self, model, overlap_backward=False, prune=False):
-        self.model = model
-        self.model.eval()
-        # (extension) the relprop chain reads only forward caches; the attention gradients are needed by the tail
-        # alone.  With overlap_backward the backward pass (main stream) and the relprop rules (side stream) run
-        # concurrently and join before the head-mean / rollout tail: the memory-bound backward kernels and the tails
-        # of the MFMA-bound Linear.relprop launches fill each other's idle CUs.  Same kernels, same results.
-        self.overlap_backward = bool(overlap_backward)
-        self._relprop_stream = None
-        # (extension, off by default) only the blocks >= start_layer contribute to a transformer_attribution map: skip
-        # the relprop rules and the attention-gradient backward below them (model.prune_below_start_layer)
-        self.prune = bool(prune)
+        # prune: only the blocks >= start_layer contribute to a transformer_attribution map: skip the relprop rules and
+        # the attention-gradient backward below them (model.prune_below_start_layer)
+        super().__init__(model, overlap_backward, prune)
 
     def generate_LRP(self, input, index=None, method="transformer_attribution", is_ablation=False, start_layer=0,
                      head_mask=None):
         # head_mask (extension): one value per head, [H], [L,H] or [L,B,H] (VisionTransformer.get_head_mask)
-        # a lost x6 hand-over of an EARLIER call is raised here, once, without synchronising (ops.x6_poll); NaN in a map
-        # means exactly that -- check() asks about the calls made so far (and synchronises)
-        if input.is_cuda:
-            ops.x6_poll(input.device)
-        out = self._generate(input, index, method, is_ablation, start_layer, head_mask)
-        if input.is_cuda:
-            ops.x6_post(input.device)
-        return out
+        with _x6_bracket(input):
+            return self._single(input, index, method, is_ablation, start_layer, head_mask)
 
-    def check(self):
-        """Raise TeError if any x6 Linear kernel since the last check lost a stream-K hand-over (the affected maps carry
-        NaN).  Synchronises the device: call it where the maps are read back anyway, never inside a step."""
-        ops.x6_raise_if_failed(next(self.model.parameters()).device)
+    def _single(self, input, index, method="transformer_attribution", is_ablation=False, start_layer=0, head_mask=None):
+        """generate_LRP without the x6 bracket (what GraphedLRP captures).  Not planned from the needs table: a single call
+        does the reference's work whatever its tail reads, and honours ``prune`` for methods.SINGLE_CALL_PRUNED alone."""
+        _refuse_before_forward(input, (method,))
+        pruned = bool((self.prune or self.model.prune_below_start_layer) and method in M.SINGLE_CALL_PRUNED)
+        name = self.model.default_method if method is None else method
+        return self._pass(input, (name,), index, is_ablation, start_layer, head_mask, self._SINGLE_CALL_NEED, pruned)[name]
 
     def generate_all(self, input, methods, index=None, is_ablation=False, start_layer=0, head_mask=None):
         """(extension) The maps of several methods of the SAME batch from one pass: ``methods`` is any subset of the
@@ -179,48 +254,42 @@ class LRP:
         _refuse_before_forward(input, wanted)
         if input.dtype == torch.float16:
             raise ops._lib.TeError(f"{ops.DTYPES_MSG}; got {input.dtype} here")
-        if input.is_cuda:
-            ops.x6_poll(input.device)
-        out = self._generate_all(input, wanted, index, is_ablation, start_layer, head_mask)
-        if input.is_cuda:
-            ops.x6_post(input.device)
-        return out
-
-    def _generate_all(self, input, wanted, index, is_ablation, start_layer, head_mask=None):
         need = M.needs(wanted, M.LRP_NEEDS, is_ablation, M.LRP_ABLATION_NEEDS)
+        pruned = bool((self.prune or self.model.prune_below_start_layer) and need.relprop
+                      and M.prunable(wanted, M.LRP_NEEDS))
+        ours = tuple(m for m in wanted if m not in M.BASELINE_METHODS)       # the tails of model.relprop
+        with _x6_bracket(input):
+            maps = self._pass(input, ours, index, is_ablation, start_layer, head_mask, need, pruned)
+            # the two baselines are tails of the same forward / backward pass (here only: to a single call they are unknown
+            # names like any other)
+            if "attn_rollout" in wanted:
+                maps["attn_rollout"] = attn_rollout_tail(self.model, start_layer)
+            if "attn_gradcam" in wanted:
+                maps["attn_gradcam"] = cam_attn_tail(self.model)
+            return {m: maps[m] for m in wanted}
+
+    def _pass(self, input, wanted, index, is_ablation, start_layer, head_mask, need, pruned):
+        """One pass for the ``method=`` names ``wanted`` of model.relprop -> {name: map, None for a name it does not know}:
+        forward; the attention gradients and the relprop chain ``need`` (a methods.Needs) asks for, from block start_layer up
+        if ``pruned``; every tail."""
         model = self.model
         with ops.gelu_backward_plane_handoff():      # this call drives the backward pass itself (attention tensors only)
             output = model(input, **_masked(head_mask))
-        ours = tuple(m for m in wanted if m not in M.BASELINE_METHODS)       # the tails of model.relprop
         maps = {}
         if not need.forward_only:
-            kwargs = {"alpha": 1}
             one_hot = _one_hot(output, index)
             loss = torch.sum(one_hot * output)
-            # as in _generate: the flag is set for THIS call only
-            user_flag = model.prune_below_start_layer
-            pruned = bool((self.prune or user_flag) and need.relprop and M.prunable(wanted, M.LRP_NEEDS))
-            model.prune_below_start_layer = pruned
             blocks = list(model.blocks)
             grad_blocks = blocks[start_layer if pruned else 0:] if need.all_grads else blocks[-1:] if need.last_grad else []
-            try:
-                if need.relprop and self.overlap_backward and input.is_cuda:
-                    maps = self._relprop_beside_backward(loss, one_hot, ours, is_ablation, start_layer, kwargs, grad_blocks)
-                else:
-                    if grad_blocks:
-                        _attention_gradients(loss, [blk.attn for blk in grad_blocks])
-                    if need.relprop:
-                        maps = model.relprop(one_hot, method=ours, is_ablation=is_ablation, start_layer=start_layer,
-                                             **kwargs)
-            finally:
-                model.prune_below_start_layer = user_flag
+
+            def chain():            # (always a tuple of names: the model's rule for several methods, under the flag set here)
+                return model.relprop(one_hot, method=wanted, is_ablation=is_ablation, start_layer=start_layer, alpha=1)
+            with _prune_flag(model, pruned):
+                maps = self._gradients_and_chain(loss, [blk.attn for blk in grad_blocks],
+                                                 chain if need.relprop else None, tail_owner=model) or {}
         if not need.relprop:                         # ("last_layer_attn": the forward pass has produced all it reads)
-            maps = {m: relprop_tail(model, m, None, is_ablation, start_layer) for m in ours}
-        if "attn_rollout" in wanted:
-            maps["attn_rollout"] = attn_rollout_tail(model, start_layer)
-        if "attn_gradcam" in wanted:
-            maps["attn_gradcam"] = cam_attn_tail(model)
-        return {m: maps[m] for m in wanted}
+            maps = {m: relprop_tail(model, m, None, is_ablation, start_layer) for m in wanted}
+        return maps
 
     def generate_head_relevance(self, input, index=None, head_mask=None):
         """(extension) Per-head relevance in the sense of Voita et al. 2019: fp64 [B, L, H], entry (b, l, h) the sum of the
@@ -231,60 +300,9 @@ class LRP:
         with torch.no_grad():
             output = model(input, **_masked(head_mask))
         one_hot = _one_hot(output, index)
-        user_flag = model.prune_below_start_layer      # the whole chain runs, whatever the model's prune flag says
-        model.prune_below_start_layer = False
-        try:
+        with _prune_flag(model, False):              # the whole chain runs, whatever the model's prune flag says
             return _head_relevance_chain([blk.attn for blk in model.blocks],
                                          lambda: model.relprop(one_hot, method=(), alpha=1))
-        finally:
-            model.prune_below_start_layer = user_flag
-
-    def _generate(self, input, index, method, is_ablation, start_layer, head_mask=None):
-        _refuse_before_forward(input, (method,))
-        with ops.gelu_backward_plane_handoff():      # this call drives the backward pass itself (attention tensors only)
-            output = self.model(input, **_masked(head_mask))
-        kwargs = {"alpha": 1}
-        one_hot = _one_hot(output, index)
-        loss = torch.sum(one_hot * output)
-        prune = self.prune and method in ("transformer_attribution", "grad")
-        # the flag is set for THIS call only: a user's own setting of model.prune_below_start_layer (and direct
-        # model.relprop calls afterwards) are unaffected
-        user_flag = self.model.prune_below_start_layer
-        self.model.prune_below_start_layer = prune or (user_flag and method in ("transformer_attribution", "grad"))
-        grad_blocks = list(self.model.blocks)[start_layer if self.model.prune_below_start_layer else 0:]
-        try:
-            if self.overlap_backward and input.is_cuda:
-                return self._relprop_beside_backward(loss, one_hot, method, is_ablation, start_layer, kwargs, grad_blocks)
-            _attention_gradients(loss, [blk.attn for blk in grad_blocks])
-            return self.model.relprop(one_hot, method=method, is_ablation=is_ablation, start_layer=start_layer,
-                                      **kwargs)
-        finally:
-            self.model.prune_below_start_layer = user_flag
-
-    def _relprop_beside_backward(self, loss, one_hot, method, is_ablation, start_layer, kwargs, grad_blocks):
-        dev = one_hot.device
-        main = torch.cuda.current_stream(dev)
-        if self._relprop_stream is None:
-            self._relprop_stream = torch.cuda.Stream(device=dev)
-        side = self._relprop_stream
-        side.wait_stream(main)                      # forward caches + one-hot are complete
-        # backward on the main stream (autograd runs each node on its forward op's stream)
-        if grad_blocks:
-            _attention_gradients(loss, [blk.attn for blk in grad_blocks])
-        grads_ready = main.record_event()
-        self.model._before_tail = lambda: torch.cuda.current_stream(dev).wait_event(grads_ready)
-        try:
-            with torch.cuda.stream(side):
-                out = self.model.relprop(one_hot, method=method, is_ablation=is_ablation, start_layer=start_layer,
-                                         **kwargs)
-        finally:
-            self.model._before_tail = None
-        main.wait_stream(side)
-        if not torch.cuda.is_current_stream_capturing():
-            for t in (out.values() if isinstance(out, dict) else (out,)):     # (generate_all: a dict of maps)
-                if t is not None:
-                    t.record_stream(main)
-        return out
 
 
 class Baselines:
@@ -393,68 +411,44 @@ class GraphedLRP:
                  start_layer=0, warmup=2):
         if not example_input.is_cuda:
             raise RuntimeError("GraphedLRP needs inputs on the MI355X")
-        if index is not None and not torch.is_tensor(index):
-            index = torch.as_tensor(np.asarray(index), device=example_input.device)
         self.lrp = lrp
-        self.static_in = example_input.clone()
-        self.static_index = None if index is None else index.clone()
-        args = (self.static_in, self.static_index, method, is_ablation, start_layer)
-        side = torch.cuda.Stream(device=example_input.device)
-        side.wait_stream(torch.cuda.current_stream(example_input.device))
-        with torch.cuda.stream(side):          # warm-up off the capture: library handles, MIOpen find, allocator
-            for _ in range(max(1, warmup)):
-                lrp._generate(*args)
-        torch.cuda.current_stream(example_input.device).wait_stream(side)
-        torch.cuda.synchronize(example_input.device)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.static_out = lrp._generate(*args)
+        statics = (example_input,)
+        if index is not None:       # the class indices are the graph's second static input
+            statics += (torch.as_tensor(index if torch.is_tensor(index) else np.asarray(index), device=example_input.device),)
+        # (lrp._single: the pass without the x6 status poll / post, which belong to calls the host makes, not to a replay)
+        self._call = GraphedCall(lambda x, idx=None: lrp._single(x, idx, method, is_ablation, start_layer), statics, warmup)
 
     def __call__(self, input, index=None):
-        if input.shape != self.static_in.shape:
-            raise RuntimeError(f"GraphedLRP was captured for {tuple(self.static_in.shape)}, got {tuple(input.shape)}")
-        self.static_in.copy_(input)
-        if self.static_index is not None and index is not None:
-            self.static_index.copy_(torch.as_tensor(index, device=self.static_index.device).reshape(self.static_index.shape))
-        self.graph.replay()
-        return self.static_out
+        static_in, *static_index = self._call.static_in
+        if input.shape != static_in.shape:
+            raise RuntimeError(f"GraphedLRP was captured for {tuple(static_in.shape)}, got {tuple(input.shape)}")
+        if not static_index:
+            return self._call(input)
+        if index is None:           # the class indices of the last call stay in force (copying a tensor onto itself is free:
+            # torch returns at once, no kernel is launched)
+            return self._call(input, static_index[0])
+        return self._call(input, torch.as_tensor(index, device=input.device).reshape(static_index[0].shape))
 
 
-class Generator:
+class Generator(_PassDriver):
     """BERT_explainability/modules/BERT/ExplanationGenerator.py:20-59 (generate_LRP)."""
 
     def __init__(self, model, prune=False, overlap_backward=False):
-        self.model = model
-        self.model.eval()
-        # (extension, as LRP.overlap_backward) the relprop rules read forward caches only: run them on a side stream beside
-        # the attention-gradient backward pass; both streams join before anything reads attn_cam / the gradients.  Same
-        # kernels, same results, bit for bit.
-        self.overlap_backward = bool(overlap_backward)
-        self._relprop_stream = None
-        # (extension, off by default) generate_LRP reads attn_cam / attention gradients of the layers >= start_layer
-        # only (ExplanationGenerator.py:47-57) -- with the reference's default start_layer = 11 that is the LAST layer
-        # alone, yet relevance and gradients are propagated through all twelve.  prune=True stops the relprop right
-        # after layer start_layer's attn_cam is stored and asks autograd for the gradients of those layers only: the
-        # same vector bit for bit; get_attn_cam() of the layers below is then not refreshed.
-        self.prune = bool(prune)
+        # prune: generate_LRP reads attn_cam / attention gradients of the layers >= start_layer only
+        # (ExplanationGenerator.py:47-57) -- with the reference's default start_layer = 11 that is the LAST layer alone,
+        # yet relevance and gradients are propagated through all twelve.  prune=True stops the relprop right after layer
+        # start_layer's attn_cam is stored and asks autograd for the gradients of those layers only: the same vector bit
+        # for bit; get_attn_cam() of the layers below is then not refreshed.
+        super().__init__(model, overlap_backward, prune)
 
     def forward(self, input_ids, attention_mask):
         return self.model(input_ids, attention_mask)
-
-    def check(self):
-        """As LRP.check(): raise if an x6 Linear kernel lost a hand-over since the last check (synchronises)."""
-        ops.x6_raise_if_failed(next(self.model.parameters()).device)
-
-    def _explain(self, input_ids, attention_mask, index, lowest_layer=0, head_mask=None):
-        """forward, attention-gradient backward, relprop.  With prune=True only the layers >= lowest_layer are served."""
-        return self._pass(input_ids, attention_mask, index, lowest_layer, head_mask=head_mask)[0]
 
     def _pass(self, input_ids, attention_mask, index, lowest_layer=0, grads="all", relprop=True, prune=None,
               head_mask=None):
         """One pass: forward; the attention gradients of ``grads`` ("all": the layers served, "last": the last layer
         alone, None: no backward pass); the relprop chain if ``relprop``.  prune (default: self.prune): only the layers
         >= lowest_layer are served.  -> (the encoder layers, what model.relprop returned or None)."""
-        from .rules import StopRelprop
         prune = self.prune if prune is None else bool(prune)
         layers = self.model.bert.encoder.layer
         if grads is None and not relprop:            # forward only: as generate_attn_last_layer / generate_rollout
@@ -466,38 +460,16 @@ class Generator:
         one_hot = _one_hot(output, index)
         loss = torch.sum(one_hot * output)
         first = lowest_layer if prune else 0
-        side = main = None
-        if relprop and self.overlap_backward and one_hot.is_cuda:
-            main = torch.cuda.current_stream(one_hot.device)
-            if self._relprop_stream is None:
-                self._relprop_stream = torch.cuda.Stream(device=one_hot.device)
-            side = self._relprop_stream
-            side.wait_stream(main)                  # forward caches + one-hot are complete
         grad_layers = list(layers)[first:] if grads == "all" else list(layers)[-1:] if grads == "last" else []
-        if grad_layers:
-            _attention_gradients(loss, [lay.attention.self for lay in grad_layers])      # main stream
-        if not relprop:
-            return layers, None
-        stop_at = layers[first].attention.self if prune else None
-        if stop_at is not None:
-            stop_at._stop_after_attn_cam = True
-        cam = None
-        try:
-            if side is not None:
-                with torch.cuda.stream(side):
-                    cam = self.model.relprop(one_hot, alpha=1)
-            else:
-                cam = self.model.relprop(one_hot, alpha=1)
-        except StopRelprop:
-            pass
-        finally:
-            if stop_at is not None:
-                stop_at._stop_after_attn_cam = False
-            if side is not None:
-                main.wait_stream(side)              # the tail (head-mean, rollout) reads both streams' results
-        if cam is not None and side is not None and not torch.cuda.is_current_stream_capturing():
-            cam.record_stream(main)
-        return layers, cam
+
+        def chain():                # pruned: layer ``first`` ends the chain once its attn_cam is stored; nothing is returned
+            with stop_after_attn_cam(layers[first].attention.self if prune else None):
+                try:
+                    return self.model.relprop(one_hot, alpha=1)
+                except StopRelprop:
+                    return None
+        return layers, self._gradients_and_chain(loss, [lay.attention.self for lay in grad_layers],
+                                                 chain if relprop else None)
 
     def generate_all(self, input_ids, attention_mask, methods, index=None, start_layer=11, rollout_start_layer=0,
                      head_mask=None):
@@ -511,34 +483,28 @@ class Generator:
         the single calls."""
         wanted = M.check(methods, M.GENERATOR_NEEDS)
         need = M.needs(wanted, M.GENERATOR_NEEDS)
-        if input_ids.is_cuda:
-            ops.x6_poll(input_ids.device)        # a lost x6 hand-over of an earlier call: raised once, no synchronisation
-        n_layers = len(self.model.bert.encoder.layer)
         pruned = bool(self.prune and M.prunable(wanted, M.GENERATOR_NEEDS))
-        lowest = start_layer if "LRP" in wanted else n_layers - 1
-        _, cam = self._pass(input_ids, attention_mask, index, lowest_layer=lowest,
-                            grads="all" if need.all_grads else "last" if need.last_grad else None,
-                            relprop=need.relprop, prune=pruned, head_mask=head_mask)
-        tails = {"LRP": lambda: lrp_tail(self.model, start_layer, pruned),
-                 "LRP_last_layer": lambda: lrp_last_layer_tail(self.model),
-                 "full_lrp": lambda: full_lrp_tail(cam),
-                 "attn_last_layer": lambda: attn_last_layer_tail(self.model),
-                 "rollout": lambda: rollout_tail(self.model, rollout_start_layer),
-                 "attn_gradcam": lambda: attn_gradcam_tail(self.model)}
-        out = {m: tails[m]() for m in wanted}
-        if input_ids.is_cuda:
-            ops.x6_post(input_ids.device)
-        return out
+        lowest = start_layer if "LRP" in wanted else self._last_layer()
+        with _x6_bracket(input_ids):
+            _, cam = self._pass(input_ids, attention_mask, index, lowest_layer=lowest,
+                                grads="all" if need.all_grads else "last" if need.last_grad else None,
+                                relprop=need.relprop, prune=pruned, head_mask=head_mask)
+            tails = {"LRP": lambda: lrp_tail(self.model, start_layer, pruned),
+                     "LRP_last_layer": lambda: lrp_last_layer_tail(self.model),
+                     "full_lrp": lambda: full_lrp_tail(cam),
+                     "attn_last_layer": lambda: attn_last_layer_tail(self.model),
+                     "rollout": lambda: rollout_tail(self.model, rollout_start_layer),
+                     "attn_gradcam": lambda: attn_gradcam_tail(self.model)}
+            return {m: tails[m]() for m in wanted}
+
+    def _last_layer(self):
+        return len(self.model.bert.encoder.layer) - 1
 
     def generate_LRP(self, input_ids, attention_mask, index=None, start_layer=11, head_mask=None):
         # head_mask (the model's own argument, BERT.py:556-625): one value per head, [H], [L,H] or, per sample, [L,B,H]
-        if input_ids.is_cuda:
-            ops.x6_poll(input_ids.device)        # a lost x6 hand-over of an earlier call: raised once, no synchronisation
-        self._explain(input_ids, attention_mask, index, lowest_layer=start_layer, head_mask=head_mask)
-        out = self.attribution_tail(start_layer)
-        if input_ids.is_cuda:
-            ops.x6_post(input_ids.device)
-        return out
+        with _x6_bracket(input_ids):
+            self._pass(input_ids, attention_mask, index, lowest_layer=start_layer, head_mask=head_mask)
+            return self.attribution_tail(start_layer)
 
     def attribution_tail(self, start_layer=11):
         """ExplanationGenerator.py:47-59 on the attn_cam / attention gradients cached by relprop + backward."""
@@ -546,39 +512,30 @@ class Generator:
 
     def generate_LRP_last_layer(self, input_ids, attention_mask, index=None, head_mask=None):
         """ExplanationGenerator.py:62-84: head-mean of the last layer's attn_cam, CLS row, CLS slot zeroed."""
-        self._explain(input_ids, attention_mask, index, lowest_layer=len(self.model.bert.encoder.layer) - 1,
-                      head_mask=head_mask)
+        self._pass(input_ids, attention_mask, index, lowest_layer=self._last_layer(), head_mask=head_mask)
         return lrp_last_layer_tail(self.model)
 
     def generate_full_lrp(self, input_ids, attention_mask, index=None, head_mask=None):
         """ExplanationGenerator.py:86-106: relevance propagated to the encoder input, summed over the hidden
-        dimension, CLS slot zeroed."""
-        with ops.gelu_backward_plane_handoff():      # this call drives the backward pass itself (attention tensors only)
-            output = self.model(input_ids=input_ids, attention_mask=attention_mask, **_masked(head_mask))[0]
-        one_hot = _one_hot(output, index)
-        layers = self.model.bert.encoder.layer
+        dimension, CLS slot zeroed.  Never pruned: it reads the relevance below the lowest layer."""
         # relprop reads the attention gradients nowhere, but the reference runs the backward first (:100-101) and the
         # accessors are part of the boundary: keep them populated
-        _attention_gradients(torch.sum(one_hot * output), [lay.attention.self for lay in layers])
-        return full_lrp_tail(self.model.relprop(one_hot, alpha=1))
+        return full_lrp_tail(self._pass(input_ids, attention_mask, index, prune=False, head_mask=head_mask)[1])
 
     def generate_attn_last_layer(self, input_ids, attention_mask, index=None, head_mask=None):
         """ExplanationGenerator.py:108-114: head-mean of the last layer's attention probabilities, CLS row."""
-        with torch.no_grad():
-            self.model(input_ids=input_ids, attention_mask=attention_mask, **_masked(head_mask))
+        self._pass(input_ids, attention_mask, index, grads=None, relprop=False, head_mask=head_mask)
         return attn_last_layer_tail(self.model)
 
     def generate_rollout(self, input_ids, attention_mask, start_layer=0, index=None, head_mask=None):
         """ExplanationGenerator.py:116-127: row-normalised rollout of the head-averaged attention probabilities."""
-        with torch.no_grad():
-            self.model(input_ids=input_ids, attention_mask=attention_mask, **_masked(head_mask))
+        self._pass(input_ids, attention_mask, index, grads=None, relprop=False, head_mask=head_mask)
         return rollout_tail(self.model, start_layer)
 
     def generate_attn_gradcam(self, input_ids, attention_mask, index=None, head_mask=None):
         """ExplanationGenerator.py:129-155: last layer's attention x its per-head mean gradient, head-mean, clamped,
         min-max normalised over the whole [N, N] map, CLS row with the CLS slot zeroed."""
-        self._explain(input_ids, attention_mask, index, lowest_layer=len(self.model.bert.encoder.layer) - 1,
-                      head_mask=head_mask)
+        self._pass(input_ids, attention_mask, index, lowest_layer=self._last_layer(), head_mask=head_mask)
         return attn_gradcam_tail(self.model)
 
     def generate_head_relevance(self, input_ids, attention_mask, index=None, head_mask=None):

@@ -62,6 +62,9 @@ LRP_ABLATION_NEEDS = {
     "second_layer": Needs(all_grads=True),
 }
 BASELINE_METHODS = ("attn_rollout", "attn_gradcam")                # served by the Baselines tails, not by model.relprop
+# A SINGLE-method call (LRP.generate_LRP(method=...), model.relprop(method=<str>)) honours ``prune`` for these two alone: it
+# keeps the reference's work for every other method, "last_layer" included, which ``prunable`` would let a pass stop for
+SINGLE_CALL_PRUNED = ("transformer_attribution", "grad")
 
 # Generator.generate_all: the generate_* methods of BERT's ExplanationGenerator.py
 GENERATOR_NEEDS = {

@@ -18,6 +18,8 @@ Conv2d.relprop (method="full": the patch embedding's z^B rule, layers_ours.py:25
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -54,6 +56,19 @@ def forward_hook(self, input, output):
 class StopRelprop(Exception):
     """Raised by an attention module whose ``_stop_after_attn_cam`` flag is set, right after it stored its attn_cam:
     the model-level relprop loop catches it (extension: ``prune_below_start_layer``, see vit.VisionTransformer)."""
+
+
+@contextlib.contextmanager
+def stop_after_attn_cam(attn_module):
+    """While open, ``attn_module`` raises StopRelprop once its attn_cam is stored (None: no module does).  The flag is reset
+    however the chain ends; catching StopRelprop stays with the caller, who knows what a stopped chain returns."""
+    if attn_module is not None:
+        attn_module._stop_after_attn_cam = True
+    try:
+        yield
+    finally:
+        if attn_module is not None:
+            attn_module._stop_after_attn_cam = False
 
 
 def _cached_y(module):

@@ -172,23 +172,13 @@ class SaliencySweep:
             return self.orig_lrp
         return self.baselines if self.method in ("rollout", "attn_gradcam") else self.lrp
 
-    def _to_model_dtype(self, data):
-        """The normalised batch in the dtype of the model the method runs on: a bf16 model takes bf16 images (the maps
-        stay fp32: bf16 operands, fp32 relevance).  full_lrp / lrp_last_layer run on the lrp rule library, which has no
-        bf16 rules: refused here, before the forward pass and before anything reaches the store."""
-        par = next(self._generator().model.parameters(), None)
-        if par is None or not par.is_floating_point() or par.dtype == data.dtype:
-            return data
-        if par.dtype == torch.bfloat16 and self._generator() is self.orig_lrp:
-            ops._bf16_rule("lrp", 1.0, f"the sweep method {self.method!r} (the lrp rule library)")
-        return data.to(par.dtype)
-
     def explain(self, data, target=None, return_maps=False):
         """One batch of normalised images -> min-max normalised maps [B,1,H,W] at image resolution (:60-98);
         return_maps: also the patch-level maps [B, g*g] they were up-sampled from."""
         index = target if self.vis_class == "target" else None                   # :62-64
         m = self.method
-        data = self._to_model_dtype(data)
+        gen = self._generator()
+        data = _to_model_dtype(data, gen, gen is self.orig_lrp, f"the sweep method {self.method!r}")
         if m == "rollout":
             res = self.baselines.generate_rollout(data, start_layer=1)
         elif m == "lrp":
@@ -204,13 +194,8 @@ class SaliencySweep:
         else:
             res = self.baselines.generate_cam_attn(data, index=index)
         B, H = data.shape[0], data.shape[-1]
-        res = res.detach().reshape(B, -1)
-        g = int(round(res.shape[1] ** 0.5))
-        if g == H:                                   # full_lrp is already at pixel resolution (:95): min-max only
-            lo, hi = res.amin(dim=1, keepdim=True), res.amax(dim=1, keepdim=True)
-            heat = ((res - lo) / (hi - lo)).reshape(B, 1, H, H)
-        else:
-            heat = ops.heatmap(res, scale=H // g, normalise=True)   # :96-97: bilinear x16 + min-max, one launch
+        res = res.detach().reshape(B, -1)            # (the patch-level maps in the shape return_maps hands out; views, as in _heat)
+        heat = _heat(res, B, H)
         return (heat, res) if return_maps else heat
 
     def run(self, loader_batches, store, rank=0, world=1):
@@ -218,10 +203,7 @@ class SaliencySweep:
         for data, target in loader_batches:
             dev = self.device if self.device is not None else data.device
             vis = self.explain(normalize(data.to(dev)), target.to(dev))
-            if torch.is_tensor(vis) and vis.is_cuda:
-                # never store maps of a step whose x6 hand-over failed: check BEFORE the append (it synchronises, which
-                # the store's host copy would do anyway), so a failed batch is neither written nor counted
-                ops.x6_raise_if_failed(vis.device)
+            _x6_check_before_append([vis])
             store.append(data, target, vis)
         return store
 
@@ -279,23 +261,13 @@ class SaliencySweepAll:
                 groups.append((kind, gen, names))
         return groups
 
-    @staticmethod
-    def _to_model_dtype(data, gen, kind, names):
-        """As SaliencySweep._to_model_dtype: the batch in the dtype of the model of this group."""
-        par = next(gen.model.parameters(), None)
-        if par is None or not par.is_floating_point() or par.dtype == data.dtype:
-            return data
-        if par.dtype == torch.bfloat16 and kind == "orig_lrp":
-            ops._bf16_rule("lrp", 1.0, f"the sweep methods {tuple(names)} (the lrp rule library)")
-        return data.to(par.dtype)
-
     def explain(self, data, target=None):
         """One batch of normalised images -> {method: min-max normalised maps [B,1,H,W] at image resolution}."""
         index = target if self.vis_class == "target" else None
         B, H = data.shape[0], data.shape[-1]
         out = {}
         for kind, gen, names in self.groups:
-            x = self._to_model_dtype(data, gen, kind, names)
+            x = _to_model_dtype(data, gen, kind == "orig_lrp", f"the sweep methods {tuple(names)}")
             if kind == "lrp":
                 res = gen.generate_all(x, tuple(dict.fromkeys(names.values())), index=index, start_layer=1)
             elif kind == "orig_lrp":
@@ -322,14 +294,30 @@ class SaliencySweepAll:
         for data, target in loader_batches:
             dev = self.device if self.device is not None else data.device
             vis = self.explain(normalize(data.to(dev)), target.to(dev))
-            cuda = [v for v in vis.values() if torch.is_tensor(v) and v.is_cuda]
-            if cuda:
-                # as SaliencySweep.run: the x6 status is checked BEFORE any append, so a failed batch is written to and
-                # counted in no store
-                ops.x6_raise_if_failed(cuda[0].device)
+            _x6_check_before_append(vis.values())
             for m in self.methods:
                 stores[m].append(data, target, vis[m])
         return stores
+
+
+def _to_model_dtype(data, gen, on_lrp_library, what):
+    """The normalised batch in the dtype of the model ``gen`` runs on: a bf16 model takes bf16 images (the maps stay fp32:
+    bf16 operands, fp32 relevance).  on_lrp_library: ``gen`` is the orig_lrp object (full_lrp / lrp_last_layer), whose
+    rule library has no bf16 rules: refused here, before the forward pass and before anything reaches a store."""
+    par = next(gen.model.parameters(), None)
+    if par is None or not par.is_floating_point() or par.dtype == data.dtype:
+        return data
+    if par.dtype == torch.bfloat16 and on_lrp_library:
+        ops._bf16_rule("lrp", 1.0, f"{what} (the lrp rule library)")
+    return data.to(par.dtype)
+
+
+def _x6_check_before_append(maps):
+    """Never store maps of a step whose x6 hand-over failed: the status is checked BEFORE any append (it synchronises, which
+    the store's host copy would do anyway), so a failed batch is written to and counted in no store."""
+    cuda = [v for v in maps if torch.is_tensor(v) and v.is_cuda]
+    if cuda:
+        ops.x6_raise_if_failed(cuda[0].device)
 
 
 def _heat(res, B, H):

@@ -511,28 +511,23 @@ def make_vit_module(L):
             if several:     # the prune rule of methods.py: every requested tail reads the blocks >= start_layer alone
                 prune = self.prune_below_start_layer and methods.prunable(wanted, methods.LRP_NEEDS)
             else:
-                prune = self.prune_below_start_layer and method in ("transformer_attribution", "grad")
-            stop_at = self.blocks[start_layer].attn if prune else None
-            if stop_at is not None:
-                stop_at._stop_after_attn_cam = True
+                prune = self.prune_below_start_layer and method in methods.SINGLE_CALL_PRUNED
             try:
-                cam = self.head.relprop(cam, **kwargs)
-                if self.exploit_cls_sparsity and isinstance(self.head, nn.Linear):
-                    # pool.relprop puts relevance on the class token only: keep it as a [B,1,C] row through the last
-                    # block's dense rules instead of a [B,N,C] tensor that is zero everywhere else
-                    cam = ops.index_select_relprop(cam.unsqueeze(1), self.pool.X[:, :1], 0)
-                    cam = self.blocks[-1].relprop_cls_only(cam, **kwargs)
-                    rest = list(self.blocks)[:-1]
-                else:
-                    cam = self.pool.relprop(cam.unsqueeze(1), **kwargs)
-                    rest = list(self.blocks)
-                for blk in reversed(rest):
-                    cam = blk.relprop(cam, **kwargs)
+                with L.stop_after_attn_cam(self.blocks[start_layer].attn if prune else None):
+                    cam = self.head.relprop(cam, **kwargs)
+                    if self.exploit_cls_sparsity and isinstance(self.head, nn.Linear):
+                        # pool.relprop puts relevance on the class token only: keep it as a [B,1,C] row through the last
+                        # block's dense rules instead of a [B,N,C] tensor that is zero everywhere else
+                        cam = ops.index_select_relprop(cam.unsqueeze(1), self.pool.X[:, :1], 0)
+                        cam = self.blocks[-1].relprop_cls_only(cam, **kwargs)
+                        rest = list(self.blocks)[:-1]
+                    else:
+                        cam = self.pool.relprop(cam.unsqueeze(1), **kwargs)
+                        rest = list(self.blocks)
+                    for blk in reversed(rest):
+                        cam = blk.relprop(cam, **kwargs)
             except L.StopRelprop:
                 cam = None
-            finally:
-                if stop_at is not None:
-                    stop_at._stop_after_attn_cam = False
 
             hook = getattr(self, "_before_tail", None)    # LRP(overlap_backward=True): join with the backward pass here
             if hook is not None:
