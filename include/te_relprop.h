@@ -799,6 +799,33 @@ int te_head_relevance_f32(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_
 int te_head_relevance_f64(const double* R, int64_t r_sb, int64_t r_sh, int64_t r_sn, double* out, int64_t B, int64_t H,
                           int64_t N, int64_t D, te_stream_t stream);
 
+/* ---- class targets (csrc/te_classes.hip) ------------------------------------------------------------------------------
+ * The classes a batch is explained for, on the device: per sample K classes, their logits, and the K one-hot relevance rows
+ * that seed the relprop chains (LRP.generate_classes / Generator.generate_classes).  One kernel, one workgroup per sample; no
+ * allocation, no synchronisation, no memset node (graph-capturable), nothing read back by the host.
+ *   logits      [B] rows of C values, row b at logits + b * ld (ld >= C, in elements); any element alignment (bf16 rows may
+ *               start at an odd element).  _f32 / _bf16 / _f64: the logits' type; the relevance type of scores and seeds is
+ *               float, float, double.
+ *   classes_in  NULL: the K largest logits of each row, in descending order, equal values in ascending class index, -0 == +0,
+ *               NaN largest (the order of te_key; an 8-bit radix select, then a rank sort of the K candidates in LDS).
+ *               1 <= K <= min(C, TE_CLASS_TARGETS_MAX_TOPK).
+ *               else [B,K] int64 on the device: these classes, in this order, duplicates allowed.  A class outside [0, C) is
+ *               never used as an address: its classes_out is -1, its score NaN, its seed row all zero.
+ *   classes_out [B,K] int64; scores [B,K]: the logit of that class, upcast exactly (no arithmetic).
+ *   seeds       [K,B,C] (class k's seed is one contiguous [B,C]) or NULL (not written): 1 at the class, 0 elsewhere, every
+ *               element written once with 16-byte vector stores between the row's first 16-byte boundary and its last whole vector.
+ *   The buffers must not overlap.  Limits: C <= TE_CLASS_TARGETS_MAX_CLASSES (2^20), K <= 2^20, top-K K <=
+ *   TE_CLASS_TARGETS_MAX_TOPK (1024): TE_ERR_UNSUPPORTED beyond.  TE_ERR_INVALID_ARG: a null logits / classes_out / scores, a
+ *   size <= 0, ld < C, top-K K > C. */
+#define TE_CLASS_TARGETS_MAX_CLASSES (1 << 20)
+#define TE_CLASS_TARGETS_MAX_TOPK 1024
+int te_class_targets_f32(const float* logits, int64_t ld, int64_t B, int64_t C, int64_t K, const int64_t* classes_in,
+                         int64_t* classes_out, float* scores, float* seeds, te_stream_t stream);
+int te_class_targets_bf16(const te_bf16_t* logits, int64_t ld, int64_t B, int64_t C, int64_t K, const int64_t* classes_in,
+                          int64_t* classes_out, float* scores, float* seeds, te_stream_t stream);
+int te_class_targets_f64(const double* logits, int64_t ld, int64_t B, int64_t C, int64_t K, const int64_t* classes_in,
+                         int64_t* classes_out, double* scores, double* seeds, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

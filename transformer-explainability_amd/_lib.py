@@ -174,6 +174,10 @@ SIGNATURES = {
     "te_mul_head_relprop_f64": (_I, [_P, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
     "te_head_relevance_f32": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P]),
     "te_head_relevance_f64": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+    # class selection and one-hot seeds (csrc/te_classes.hip)
+    "te_class_targets_f32": (_I, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
+    "te_class_targets_bf16": (_I, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
+    "te_class_targets_f64": (_I, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
     # the z^B rule of a bf16 patch embedding (csrc/te_conv_bf16.hip)
     "te_conv2d_zb_relprop_bf16_supported": (_I, [_I64, _I64, _I64]),
     "te_conv2d_zb_relprop_bf16_workspace_bytes": (_SZ, [_I64] * 6),

@@ -10,6 +10,7 @@ Same method names and arguments; differences (results identical at batch 1):
 from __future__ import annotations
 
 import contextlib
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -49,9 +50,9 @@ def _headmean_stack(attns):
     return torch.stack([a.mean(dim=1) for a in attns], 0)
 
 
-def _attention_gradients(loss, attn_modules):
+def _attention_gradients(loss, attn_modules, retain_graph=False):
     """Attention gradients of the listed modules (lowest block first), nothing else: no weight gradients, nothing below
-    the lowest listed block."""
+    the lowest listed block.  retain_graph: another backward pass over the same forward pass follows (_class_pass)."""
     anchors = [getattr(m, "_fused_anchor", None) for m in attn_modules]
     if anchors and all(a is not None for a in anchors):
         # producer kernels (vit._FusedAttention): the gradient w.r.t. the probabilities is formed inside the block's
@@ -60,7 +61,7 @@ def _attention_gradients(loss, attn_modules):
         lowest = attn_modules[0]
         lowest._fused_stop_backward = True
         try:
-            torch.autograd.grad(loss, [anchors[0]], retain_graph=False, allow_unused=True)
+            torch.autograd.grad(loss, [anchors[0]], retain_graph=retain_graph, allow_unused=True)
         finally:
             lowest._fused_stop_backward = False
         return
@@ -69,7 +70,7 @@ def _attention_gradients(loss, attn_modules):
                                "stock PyTorch (a frozen qkv layer, or a block in train mode?); the gradient driver "
                                "handles one kind per pass -- set ops.USE_FUSED_PRODUCERS = False for this model")
     attns = [m.get_attn() for m in attn_modules]
-    grads = torch.autograd.grad(loss, attns, retain_graph=False, allow_unused=False)
+    grads = torch.autograd.grad(loss, attns, retain_graph=retain_graph, allow_unused=False)
     for m, g in zip(attn_modules, grads):
         m.save_attn_gradients(g)
 
@@ -152,6 +153,91 @@ def _prune_flag(model, value):
         model.prune_below_start_layer = user_flag
 
 
+class ClassMaps(NamedTuple):
+    """What generate_classes returns.  classes: int64 [B,K] on the device, None when ``seeds`` was given; scores [B,K]: the
+    logits of those classes (for ``seeds``: sum(seed * logits)), fp32 for fp32 and bf16 models, fp64 for fp64 models;
+    maps: {method: [B,K,...]} in the caller's order of methods, ``maps[m][:, k]`` the single call's map for ``classes[:, k]``
+    (always with the batch dimension, also at B = 1)."""
+    classes: Optional[torch.Tensor]
+    scores: torch.Tensor
+    maps: dict
+
+
+def _num_classes(model):
+    """The width of the model's logits where the model says it (ViT: num_classes; BERT: num_labels), else None: the class
+    requests are then checked after the forward pass instead of before it."""
+    for name in ("num_classes", "num_labels"):
+        n = getattr(model, name, None)
+        if isinstance(n, int) and n > 0:
+            return n
+    return None
+
+
+class TopAnd:
+    """A ``classes=`` argument of generate_classes: per sample its TOP class (the device argmax: te_class_targets, top-1)
+    next to the given ``classes`` [B] or [B,K'] -- e.g. the predicted class and the label of the perturbation protocol.  The
+    two are merged on the device after the forward pass; nothing is read back.  top_first: the top class is column 0."""
+
+    def __init__(self, classes, top_first=True):
+        self.classes, self.top_first = classes, bool(top_first)
+
+
+class _ClassRequest:
+    """Exactly one of classes / topk / seeds of a generate_classes call, validated as far as the host can see (``check`` runs
+    before the forward pass when the model states its number of classes, and again on the logits)."""
+
+    def __init__(self, classes, topk, seeds):
+        if sum(a is not None for a in (classes, topk, seeds)) != 1:
+            raise ValueError("generate_classes: give exactly one of classes / topk / seeds")
+        self.classes, self.topk, self.seeds = classes, topk, seeds
+
+    def check(self, B, C, rel_dtype, device):
+        if self.topk is not None:
+            k = self.topk
+            if isinstance(k, bool) or int(k) != k or k < 1 or (C is not None and k > C):
+                raise ValueError(f"topk must be an integer in [1, {C if C is not None else 'num_classes'}], got {self.topk!r}")
+        elif isinstance(self.classes, TopAnd):
+            given = self.classes.classes
+            given = given.reshape(B, -1) if torch.is_tensor(given) else np.asarray(given).reshape(B, -1)
+            if C is not None:
+                self.classes = TopAnd(ops.host_classes(given, B, C, device), self.classes.top_first)
+        elif self.classes is not None:
+            if C is not None:
+                self.classes = ops.host_classes(self.classes, B, C, device)
+        else:
+            t = self.seeds
+            if not torch.is_tensor(t):
+                raise ValueError("seeds must be a tensor of shape [B,C] or [B,K,C]")
+            if t.dtype != rel_dtype:
+                raise ops._lib.TeError(f"{ops.DTYPES_MSG}; the seeds of this model are {rel_dtype} (its relevance dtype), "
+                                       f"got {t.dtype}")
+            if t.dim() not in (2, 3) or t.shape[0] != B or t.numel() == 0 or (C is not None and t.shape[-1] != C):
+                raise ValueError(f"seeds must have shape [B,C] or [B,K,C] = [{B},{'K,' if t.dim() == 3 else ''}"
+                                 f"{C if C is not None else 'num_classes'}], got {tuple(t.shape)}")
+
+    def targets(self, output):
+        """On the logits [B,C] -> (classes [B,K] or None, scores [B,K], seeds [K,B,C]): ops.class_targets for classes / topk
+        (nothing is read back), the caller's own seeds otherwise."""
+        B, C = output.shape
+        logits = output.detach()
+        rel = ops.relevance_dtype(logits.dtype)
+        self.check(B, C, rel, logits.device)
+        if isinstance(self.classes, TopAnd):
+            top = ops.class_targets(logits, topk=1, with_seeds=False)[0]
+            cols = [top, self.classes.classes] if self.classes.top_first else [self.classes.classes, top]
+            return ops.class_targets(logits, classes=torch.cat(cols, 1))
+        if self.seeds is None:
+            return ops.class_targets(logits, classes=self.classes, topk=self.topk)
+        seeds = self.seeds.to(logits.device).reshape(B, -1, C).permute(1, 0, 2).contiguous()
+        scores = (seeds * logits.to(rel)).sum(dim=-1).t().contiguous()
+        return None, scores, seeds
+
+
+def _stack_classes(per_class, names):
+    """[{name: map of class k}] -> {name: [B,K,...]}."""
+    return {m: torch.stack([d[m] for d in per_class], 1) for m in names}
+
+
 class _PassDriver:
     """What LRP and Generator share: the options, check() and the one implementation of "attention gradients, then -- or,
     with overlap_backward, beside them -- the relprop chain"."""
@@ -173,12 +259,34 @@ class _PassDriver:
         NaN).  Synchronises the device: call it where the maps are read back anyway, never inside a step."""
         ops.x6_raise_if_failed(next(self.model.parameters()).device)
 
-    def _gradients_and_chain(self, loss, attn_modules, chain, tail_owner=None):
+    def _class_pass(self, output, seeds, attn_modules, chain_of, tails, tail_owner=None):
+        """The backward passes and relprop chains of SEVERAL classes over ONE forward pass, one class after another in the
+        order of ``seeds`` [K,B,C]: per class the attention gradients of ``attn_modules`` on sum(seed * output) (none: no
+        backward pass), then ``chain_of(seed)()`` (chain_of(seed) None: no chain), then ``tails(what the chain returned)``
+        -> [{name: map}] * K.  Every backward pass but the last retains the graph; the planes of |X| the forward products
+        left for their rules stay in the layers' scratch dicts until the last class's rules have read them and are gone
+        when this returns or raises (ops.x_abs_planes_kept).  Afterwards the model's accessors hold the LAST class's
+        gradients and attn_cam."""
+        K = seeds.shape[0]
+        caches = [m.__dict__["_te_cache"] for m in self.model.modules() if m.__dict__.get("_te_cache") is not None]
+        per_class = []
+        with ops.x_abs_planes_kept(caches) as kept:
+            for k in range(K):
+                kept.last = k == K - 1
+                seed = seeds[k]
+                loss = torch.sum(seed * output)
+                out = self._gradients_and_chain(loss, attn_modules, chain_of(seed), tail_owner=tail_owner,
+                                                retain_graph=not kept.last)
+                per_class.append(tails(out))
+        return per_class
+
+    def _gradients_and_chain(self, loss, attn_modules, chain, tail_owner=None, retain_graph=False):
         """The attention gradients of ``attn_modules`` (none: no backward pass), then what ``chain()`` returns (None: no
-        chain).  tail_owner: a model whose relprop runs the tail itself (ViT) and calls ``_before_tail`` in front of it."""
+        chain).  tail_owner: a model whose relprop runs the tail itself (ViT) and calls ``_before_tail`` in front of it.
+        retain_graph: the forward pass is differentiated again afterwards (_class_pass)."""
         if chain is None or not (self.overlap_backward and loss.is_cuda):
             if attn_modules:
-                _attention_gradients(loss, attn_modules)
+                _attention_gradients(loss, attn_modules, retain_graph)
             return None if chain is None else chain()
         dev = loss.device
         main = torch.cuda.current_stream(dev)
@@ -188,7 +296,7 @@ class _PassDriver:
         side.wait_stream(main)                      # forward caches + one-hot are complete
         # backward on the main stream (autograd runs each node on its forward op's stream)
         if attn_modules:
-            _attention_gradients(loss, attn_modules)
+            _attention_gradients(loss, attn_modules, retain_graph)
         if tail_owner is not None:
             # (only then: every other caller runs its tail after the join below, and an event nobody waits on is one more
             # node in a captured graph)
@@ -267,6 +375,69 @@ class LRP(_PassDriver):
             if "attn_gradcam" in wanted:
                 maps["attn_gradcam"] = cam_attn_tail(self.model)
             return {m: maps[m] for m in wanted}
+
+    def generate_classes(self, input, classes=None, topk=None, seeds=None, methods=("transformer_attribution",),
+                         is_ablation=False, start_layer=0, head_mask=None) -> ClassMaps:
+        """(extension) The maps of several CLASSES (and several methods) of the same batch from ONE forward pass.  Exactly one
+        of: ``classes`` [B,K] (or [K] for every sample alike; tensor, array or list; duplicates allowed), ``topk`` = K (the K
+        largest logits per sample, chosen on the device: no device-to-host copy), ``seeds`` [B,C] or [B,K,C] in the model's
+        relevance dtype (the relevance put on the logits instead of a one-hot, e.g. onehot(c) - onehot(c') for a contrastive
+        map; the backward pass differentiates sum(seed * logits)).  ``classes`` may also be a ``TopAnd(given)``: the per-sample
+        top class next to given ones, merged on the device.  ``methods``: as in generate_all, with its refusals.
+        Returns ClassMaps(classes, scores, maps): ``maps[m][:, k]`` has the bits of the single call on a fresh forward pass
+        with ``index=classes[:, k]`` (generate_LRP, Baselines.generate_rollout / generate_cam_attn).
+
+        One forward pass; then per class, in order, the attention gradients and the relprop chain the union of the methods
+        needs (methods.LRP_NEEDS) and every tail; methods that read the forward pass alone are computed once and returned K
+        times, and a request of such methods only runs no backward pass and no chain.  ``prune``, ``overlap_backward``,
+        ``head_mask``, ``is_ablation`` and ``start_layer`` act per class as they do per call; the x6 status poll / post happens
+        once.  Afterwards the model's accessors (get_attn_cam(), get_attn_gradients()) hold the LAST class's state.  A class
+        outside [0, num_classes) in a list, an array or a CPU tensor is a ValueError before the forward pass; in a device
+        tensor (which is not read back) it yields classes -1, score NaN and maps of an all-zero seed."""
+        wanted = M.check(methods, M.LRP_NEEDS)
+        _refuse_before_forward(input, wanted)
+        if input.dtype == torch.float16:
+            raise ops._lib.TeError(f"{ops.DTYPES_MSG}; got {input.dtype} here")
+        request = _ClassRequest(classes, topk, seeds)
+        request.check(input.shape[0], _num_classes(self.model), ops.relevance_dtype(input.dtype), input.device)
+        model = self.model
+
+        def row(m):
+            return M.needs((m,), M.LRP_NEEDS, is_ablation, M.LRP_ABLATION_NEEDS)
+        once = tuple(m for m in wanted if row(m).forward_only)               # read the forward pass alone
+        per_class = tuple(m for m in wanted if m not in once)
+        need = M.needs(per_class, M.LRP_NEEDS, is_ablation, M.LRP_ABLATION_NEEDS)
+        pruned = bool((self.prune or model.prune_below_start_layer) and need.relprop and M.prunable(wanted, M.LRP_NEEDS))
+        ours = tuple(m for m in per_class if m not in M.BASELINE_METHODS)    # the tails of model.relprop
+        with _x6_bracket(input):
+            with ops.gelu_backward_plane_handoff():  # this call drives the backward passes itself (attention tensors only)
+                output = model(input, **_masked(head_mask))
+            cls, scores, seed_stack = request.targets(output)
+            B, K = scores.shape
+            shared = {m: attn_rollout_tail(model, start_layer) if m == "attn_rollout"
+                      else relprop_tail(model, m, None, is_ablation, start_layer) for m in once}
+            blocks = list(model.blocks)
+            grad_blocks = blocks[start_layer if pruned else 0:] if need.all_grads else blocks[-1:] if need.last_grad else []
+
+            def chain_of(seed):
+                if not need.relprop:
+                    return None
+                return lambda: model.relprop(seed, method=ours, is_ablation=is_ablation, start_layer=start_layer, alpha=1)
+
+            def tails(maps):
+                maps = dict(maps or {})
+                if "attn_gradcam" in per_class:
+                    cam = cam_attn_tail(model)
+                    maps["attn_gradcam"] = cam.unsqueeze(0) if B == 1 else cam
+                return maps
+            stacked = {}
+            if per_class:
+                with _prune_flag(model, pruned):
+                    stacked = _stack_classes(self._class_pass(output, seed_stack, [blk.attn for blk in grad_blocks],
+                                                              chain_of, tails, tail_owner=model), per_class)
+            for m, t in shared.items():
+                stacked[m] = t.unsqueeze(1).expand(-1, K, *t.shape[1:])
+            return ClassMaps(cls, scores, {m: stacked[m] for m in wanted})
 
     def _pass(self, input, wanted, index, is_ablation, start_layer, head_mask, need, pruned):
         """One pass for the ``method=`` names ``wanted`` of model.relprop -> {name: map, None for a name it does not know}:
@@ -462,14 +633,61 @@ class Generator(_PassDriver):
         first = lowest_layer if prune else 0
         grad_layers = list(layers)[first:] if grads == "all" else list(layers)[-1:] if grads == "last" else []
 
-        def chain():                # pruned: layer ``first`` ends the chain once its attn_cam is stored; nothing is returned
+        return layers, self._gradients_and_chain(loss, [lay.attention.self for lay in grad_layers],
+                                                 self._chain(one_hot, first, prune) if relprop else None)
+
+    def _chain(self, seed, first, prune):
+        """The relprop chain of ``seed``.  prune: layer ``first`` ends it once its attn_cam is stored; nothing is returned."""
+        layers = self.model.bert.encoder.layer
+
+        def chain():
             with stop_after_attn_cam(layers[first].attention.self if prune else None):
                 try:
-                    return self.model.relprop(one_hot, alpha=1)
+                    return self.model.relprop(seed, alpha=1)
                 except StopRelprop:
                     return None
-        return layers, self._gradients_and_chain(loss, [lay.attention.self for lay in grad_layers],
-                                                 chain if relprop else None)
+        return chain
+
+    def generate_classes(self, input_ids, attention_mask, classes=None, topk=None, seeds=None, methods=("LRP",),
+                         start_layer=11, rollout_start_layer=0, head_mask=None) -> ClassMaps:
+        """(extension) The vectors of several CLASSES (and several methods) of the same batch from ONE forward pass: the
+        class arguments, the result and the order of the work as in LRP.generate_classes, the methods and ``start_layer`` /
+        ``rollout_start_layer`` as in generate_all.  ``maps[m][:, k]`` has the bits of the generate_* method of that name on a
+        fresh forward pass with ``index=classes[:, k]``.  Afterwards the model's accessors hold the LAST class's state."""
+        wanted = M.check(methods, M.GENERATOR_NEEDS)
+        request = _ClassRequest(classes, topk, seeds)
+        par = next(self.model.parameters(), None)
+        rel = ops.relevance_dtype(par.dtype) if par is not None else torch.float32
+        request.check(input_ids.shape[0], _num_classes(self.model), rel, input_ids.device)
+        once = tuple(m for m in wanted if M.GENERATOR_NEEDS[m].forward_only)
+        per_class = tuple(m for m in wanted if m not in once)
+        need = M.needs(per_class, M.GENERATOR_NEEDS)
+        pruned = bool(self.prune and M.prunable(wanted, M.GENERATOR_NEEDS))
+        model = self.model
+        with _x6_bracket(input_ids):
+            with ops.gelu_backward_plane_handoff():  # this call drives the backward passes itself (attention tensors only)
+                output = model(input_ids=input_ids, attention_mask=attention_mask, **_masked(head_mask))[0]
+            layers = model.bert.encoder.layer
+            lowest = start_layer if "LRP" in wanted else self._last_layer()
+            cls, scores, seed_stack = request.targets(output)
+            K = scores.shape[1]
+            shared = {m: attn_last_layer_tail(model) if m == "attn_last_layer" else rollout_tail(model, rollout_start_layer)
+                      for m in once}
+            first = lowest if pruned else 0
+            grad_layers = list(layers)[first:] if need.all_grads else list(layers)[-1:] if need.last_grad else []
+            tail_of = {"LRP": lambda cam: lrp_tail(model, start_layer, pruned),
+                       "LRP_last_layer": lambda cam: lrp_last_layer_tail(model),
+                       "full_lrp": full_lrp_tail,
+                       "attn_gradcam": lambda cam: attn_gradcam_tail(model)}
+            stacked = {}
+            if per_class:
+                stacked = _stack_classes(self._class_pass(
+                    output, seed_stack, [lay.attention.self for lay in grad_layers],
+                    lambda seed: self._chain(seed, first, pruned) if need.relprop else None,
+                    lambda cam: {m: tail_of[m](cam) for m in per_class}), per_class)
+            for m, t in shared.items():
+                stacked[m] = t.unsqueeze(1).expand(-1, K, *t.shape[1:])
+            return ClassMaps(cls, scores, {m: stacked[m] for m in wanted})
 
     def generate_all(self, input_ids, attention_mask, methods, index=None, start_layer=11, rollout_start_layer=0,
                      head_mask=None):

@@ -423,8 +423,36 @@ def post_x_abs_planes(cache: dict, X: Tensor, T: int, K: int, xa: Tensor):
 def take_x_abs_planes(cache: dict, X: Tensor, T: int, K: int) -> Optional[Tensor]:
     """The planes of |X| if the forward product of exactly this X left them, else None.  Consumed once: 6 B per input
     element (0.4 GB per ViT-B block at batch 64) must not outlive the rule."""
-    hit = cache.pop("x_abs_planes", None)
+    keep = _X_ABS_KEPT
+    hit = cache.get("x_abs_planes") if keep is not None and not keep.last else cache.pop("x_abs_planes", None)
     return hit[1] if hit is not None and hit[0] == _x_abs_key(X, T, K) else None
+
+
+_X_ABS_KEPT = None
+
+
+class x_abs_planes_kept:
+    """Around the relprop chains of SEVERAL classes over one forward pass (generators._PassDriver._class_pass): while open,
+    take_x_abs_planes leaves the entry where it is, so that every class's rule reads the planes the forward product left;
+    the caller sets ``last = True`` in front of the last class's chain, whose rules pop them as a single call's do.  On exit
+    -- however the chains ended -- the ``x_abs_planes`` entry of every dict in ``caches`` is dropped: 6 B per input element
+    must not outlive the call.  The planes are a function of X alone, so a rule that takes them and one that splits |X| itself
+    write the same bits."""
+
+    def __init__(self, caches):
+        self.caches, self.last = list(caches), False
+
+    def __enter__(self):
+        global _X_ABS_KEPT
+        self._outer, _X_ABS_KEPT = _X_ABS_KEPT, self
+        return self
+
+    def __exit__(self, *exc):
+        global _X_ABS_KEPT
+        _X_ABS_KEPT = self._outer
+        for c in self.caches:
+            c.pop("x_abs_planes", None)
+        return False
 
 
 def post_dy_planes(cache: dict, planes: Tensor, like: Tensor) -> Tensor:
@@ -1995,3 +2023,77 @@ def head_relevance(R_heads: Tensor) -> Tensor:
         _lib.check(getattr(lib, "te_head_relevance_" + sfx)(_ptr(R), sb, sh, sn, _ptr(out), B, H, N, D, _stream(R)),
                    "te_head_relevance_" + sfx)
     return out
+
+
+# ---------------------------------------------------------------------------------------- class targets
+def relevance_dtype(dtype) -> torch.dtype:
+    """The dtype of a model's relevance (seeds, scores, maps): fp32 for fp32 and bf16 models, fp64 for fp64 models."""
+    return torch.float32 if dtype == torch.bfloat16 else dtype
+
+
+def host_classes(classes, B: int, C: int, device) -> Tensor:
+    """``classes`` ([B,K] or, for every sample alike, [K]; a tensor, an array or a list) as an int64 [B,K] tensor on
+    ``device``.  Host data is checked here -- a class outside [0, C) is a ValueError, before anything is launched; a device
+    tensor is not read back (te_class_targets_* marks such a class: -1, NaN score, all-zero seed)."""
+    on_device = torch.is_tensor(classes) and classes.device.type != "cpu"
+    idx = classes if torch.is_tensor(classes) else torch.as_tensor(classes)
+    if idx.is_floating_point() or idx.dtype == torch.bool or idx.dim() not in (1, 2) or idx.numel() == 0:
+        raise ValueError(f"classes must be integers of shape [B,K] or [K], got {idx.dtype} {tuple(idx.shape)}")
+    if idx.dim() == 1:
+        idx = idx.view(1, -1).expand(B, -1)
+    if idx.shape[0] != B:
+        raise ValueError(f"classes has {idx.shape[0]} rows, the batch has {B}")
+    if not on_device and (int(idx.min()) < 0 or int(idx.max()) >= C):
+        raise ValueError(f"classes must lie in [0, {C}), got values from {int(idx.min())} to {int(idx.max())}")
+    return idx.to(device=device, dtype=torch.int64).contiguous()
+
+
+def class_targets(logits: Tensor, classes: Optional[Tensor] = None, topk: Optional[int] = None, with_seeds: bool = True,
+                  out: Optional[tuple] = None):
+    """logits [B,C] (fp32 / bf16 / fp64, rows ``stride(0) >= C`` apart, read in place) -> (classes int64 [B,K], scores [B,K],
+    seeds [K,B,C] or None) on te_class_targets_*: the ``topk`` largest logits per sample (descending; ties in ascending class
+    index; NaN largest), or the given ``classes`` (a device int64 [B,K]; one outside [0, C) comes back as -1 / NaN / a zero
+    row) with their logits and one-hot seeds in the relevance dtype.  ``out``: (classes, scores, seeds) to write into
+    (contiguous, of those shapes and dtypes; seeds may be None).  One kernel; never synchronises; graph-capturable."""
+    if logits.dim() != 2 or logits.numel() == 0 or logits.stride(1) != 1:
+        raise _lib.TeError(f"class_targets: logits must be [B,C] with a contiguous last dimension, got {tuple(logits.shape)} "
+                           f"strides {tuple(logits.stride())}")
+    sfx = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float64: "f64"}.get(logits.dtype)
+    if sfx is None:
+        raise _lib.TeError(f"{DTYPES_MSG}; class_targets got {logits.dtype} logits")
+    if (classes is None) == (topk is None):
+        raise ValueError("class_targets: give exactly one of classes / topk")
+    B, C = logits.shape
+    ld = logits.stride(0) if B > 1 else C
+    if topk is not None:
+        K = int(topk)
+        if not 1 <= K <= C:
+            raise ValueError(f"topk must lie in [1, {C}] (the number of classes), got {topk}")
+    else:
+        if (not torch.is_tensor(classes) or classes.dtype != torch.int64 or classes.dim() != 2 or classes.shape[0] != B
+                or classes.device != logits.device or not classes.is_contiguous() or classes.shape[1] == 0):
+            raise _lib.TeError(f"class_targets: classes must be a contiguous int64 [{B},K] tensor on {logits.device} "
+                               "(ops.host_classes makes one)")
+        K = classes.shape[1]
+    rel = relevance_dtype(logits.dtype)
+    if out is None:
+        cls_out = torch.empty((B, K), dtype=torch.int64, device=logits.device)
+        scores = torch.empty((B, K), dtype=rel, device=logits.device)
+        seeds = torch.empty((K, B, C), dtype=rel, device=logits.device) if with_seeds else None
+    else:
+        cls_out, scores, seeds = out
+        for t, shape, dt, name in ((cls_out, (B, K), torch.int64, "classes"), (scores, (B, K), rel, "scores"),
+                                   (seeds, (K, B, C), rel, "seeds")):
+            if t is None and name == "seeds":
+                continue
+            if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()
+                    or t.device != logits.device):
+                raise _lib.TeError(f"class_targets: out {name} must be a contiguous {dt} {shape} on {logits.device}")
+    if not logits.is_cuda:
+        raise _lib.TeError("relprop kernels need tensors on the MI355X (got a CPU tensor); there is no CPU fallback")
+    with _on_device(logits) as lib, _timed("class_targets", 0.0, float(logits.numel()) * logits.element_size()
+                                               + (0.0 if seeds is None else float(seeds.numel()) * seeds.element_size())):
+        _lib.check(getattr(lib, "te_class_targets_" + sfx)(_ptr(logits.detach()), ld, B, C, K, _ptr(classes), _ptr(cls_out),
+                                                           _ptr(scores), _ptr(seeds), _stream(logits)),
+                   "te_class_targets_" + sfx)
+    return cls_out, scores, seeds

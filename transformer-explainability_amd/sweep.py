@@ -234,6 +234,11 @@ class SaliencySweepAll:
         bad = [m for m in methods if m not in METHODS]
         if bad or not methods:
             raise ValueError(f"methods must be a non-empty subset of {METHODS}, got {bad or methods}")
+        if not isinstance(vis_class, str):
+            # (extension) several classes per image from one forward pass: ("top", "target"), in the order given
+            vis_class = tuple(vis_class)
+            if not vis_class or len(set(vis_class)) != len(vis_class) or any(v not in ("top", "target") for v in vis_class):
+                raise ValueError(f"vis_class must be 'top', 'target' or a tuple of the two, got {vis_class!r}")
         self.methods, self.vis_class, self.is_ablation = methods, vis_class, bool(is_ablation)
         self.lrp, self.orig_lrp, self.baselines, self.device = lrp, orig_lrp, baselines, device
         self.groups = self._group()
@@ -262,7 +267,10 @@ class SaliencySweepAll:
         return groups
 
     def explain(self, data, target=None):
-        """One batch of normalised images -> {method: min-max normalised maps [B,1,H,W] at image resolution}."""
+        """One batch of normalised images -> {method: min-max normalised maps [B,1,H,W] at image resolution}; with a tuple
+        ``vis_class`` -> {(method, vis_class): maps}."""
+        if not isinstance(self.vis_class, str):
+            return self._explain_classes(data, target)
         index = target if self.vis_class == "target" else None
         B, H = data.shape[0], data.shape[-1]
         out = {}
@@ -286,17 +294,59 @@ class SaliencySweepAll:
                 out[m] = heats[name]
         return {m: out[m] for m in self.methods}
 
+    def _explain_classes(self, data, target):
+        """explain for a tuple ``vis_class``: per group ONE generate_classes call, whose class columns are the entries of
+        vis_class in order -- "top" the per-sample argmax, found on the device after the forward pass and merged with the
+        target column there (generators.TopAnd).  A ``baselines`` object on a model of its own has no generate_classes: it
+        keeps its single calls, one per class column that its method depends on."""
+        from .generators import TopAnd
+        if "target" in self.vis_class and target is None:
+            raise ValueError("vis_class contains 'target': a target per sample is needed")
+        B, H = data.shape[0], data.shape[-1]
+        if self.vis_class == ("top",):
+            request = {"topk": 1}
+        elif self.vis_class == ("target",):
+            request = {"classes": target.reshape(B, 1)}
+        else:
+            request = {"classes": TopAnd(target, top_first=self.vis_class[0] == "top")}
+        out = {}
+        for kind, gen, names in self.groups:
+            x = _to_model_dtype(data, gen, kind == "orig_lrp", f"the sweep methods {tuple(names)}")
+            wanted = tuple(dict.fromkeys(names.values()))
+            if kind == "lrp":
+                res = gen.generate_classes(x, methods=wanted, start_layer=1, **request).maps
+            elif kind == "orig_lrp":
+                res = gen.generate_classes(x, methods=wanted, is_ablation=self.is_ablation, **request).maps
+            else:
+                res = {}
+                if "rollout" in names:
+                    r = gen.generate_rollout(x, start_layer=1)
+                    res["attn_rollout"] = torch.stack([r] * len(self.vis_class), 1)
+                if "attn_gradcam" in names:
+                    res["attn_gradcam"] = torch.stack(
+                        [gen.generate_cam_attn(x, index=target if v == "target" else None).reshape(B, -1)
+                         for v in self.vis_class], 1)
+            heats = {}
+            for m, name in names.items():
+                for k, v in enumerate(self.vis_class):
+                    if (name, v) not in heats:
+                        heats[name, v] = _heat(res[name][:, k], B, H)
+                    out[m, v] = heats[name, v]
+        return {(m, v): out[m, v] for m in self.methods for v in self.vis_class}
+
     def run(self, loader_batches, stores, rank=0, world=1):
-        """loader_batches as SaliencySweep.run; stores: {method: ResultsStore}, one per requested method."""
-        missing = [m for m in self.methods if m not in stores]
+        """loader_batches as SaliencySweep.run; stores: {method: ResultsStore}, one per requested method -- with a tuple
+        ``vis_class``, {(method, vis_class): ResultsStore}."""
+        keys = list(self.methods) if isinstance(self.vis_class, str) else [(m, v) for m in self.methods for v in self.vis_class]
+        missing = [k for k in keys if k not in stores]
         if missing:
             raise ValueError(f"no store for the methods {missing}")
         for data, target in loader_batches:
             dev = self.device if self.device is not None else data.device
             vis = self.explain(normalize(data.to(dev)), target.to(dev))
             _x6_check_before_append(vis.values())
-            for m in self.methods:
-                stores[m].append(data, target, vis[m])
+            for k in keys:
+                stores[k].append(data, target, vis[k])
         return stores
 
 
