@@ -498,6 +498,39 @@ size_t te_seg_metrics_workspace_bytes(int64_t B, int64_t H, int64_t W);
 int te_seg_metrics_f32(const float* heat, const float* fg_mask, const int64_t* labels, int64_t* counts, double* ap,
                        double* f1, int64_t B, int64_t H, int64_t W, void* ws, size_t ws_bytes, te_stream_t stream);
 
+/* ---- map similarity (the sanity-check protocol: Adebayo et al., Sanity Checks for Saliency Maps, NeurIPS 2018) ----
+ * compares, per sample, two relevance maps a, b fp32 [B,n] (contiguous rows) in TWO launches with no host synchronisation, no
+ * allocation and no memset node (a HIP graph captures the call).  H, W: the image the n values are (H*W == n) when flags has
+ * TE_MAPSIM_SSIM, else 0, 0.
+ *   rank_sums [B,2,3] int64 = (cov, va, vb) for the plain values (index 0) and the absolute values (index 1).  Ranks: the n
+ *                  values ascending in the order of te_key (-0 == +0); a run of equal values at the 0-based sorted positions
+ *                  s .. e-1 gets the average rank (s + e + 1) / 2 (scipy.stats.rankdata(method="average")); the kernels keep
+ *                  the integer d = 2 rank - (n + 1) = s + e - n, |d| < n; cov = sum d_a d_b, va = sum d_a^2, vb = sum d_b^2.
+ *                  For n <= 2^20 every sum is below 2^60: exact, whatever the order.
+ *   sim [B,4]    fp64 = pearson, spearman, spearman_abs, ssim.
+ *                  spearman = (double)cov / (sqrt((double)va) * sqrt((double)vb)) clamped to [-1, 1]; NaN when va == 0 or
+ *                  vb == 0 (a constant map, n == 1); exactly +-1 when |cov| == va == vb (the same or the reversed ranking:
+ *                  sqrt(va) * sqrt(va) == va is not promised in floating point).  spearman_abs: the same on |a|, |b|.
+ *                  pearson: two passes in fp64 over the fp32 values -- the means, then sab, saa, sbb of the centred values --
+ *                  sab / (sqrt(saa) * sqrt(sbb)) clamped; NaN when saa == 0 or sbb == 0.
+ *                  ssim: scikit-image's structural_similarity at its defaults for a 2-D image: 7x7 uniform window, sample
+ *                  covariance (cov_norm = 49/48), C1 = (0.01 L)^2, C2 = (0.03 L)^2 with L = data_range; per window ux, uy,
+ *                  vx = cov_norm (uxx - ux^2), vy, vxy = cov_norm (uxy - ux uy), S = ((2 ux uy + C1)(2 vxy + C2)) /
+ *                  ((ux^2 + uy^2 + C1)(vx + vy + C2)); the mean of S over the (H-6)(W-6) windows inside the image (what
+ *                  the border crop leaves), window statistics in fp64.  NaN without TE_MAPSIM_SSIM.
+ * NaN rule: a sample with a NaN anywhere in a or b gives an all-NaN sim row and an all-zero rank_sums row (scipy's
+ * nan_policy="propagate"); its neighbours in the batch are unaffected.  +-inf are ordinary values for the ranks.
+ * The integers are exact; every fp64 sum runs in an order fixed by the sample alone, without floating-point atomics: every
+ * output of sample b is the same bit pattern alone or in any batch, wherever the workspace lies.
+ * Refused on the host before any HIP call: null pointers, sizes <= 0, unknown flag bits, SSIM with H*W != n or H < 7 or
+ * W < 7 TE_ERR_INVALID_ARG; n > 2^20 or B > 65535 TE_ERR_UNSUPPORTED; a workspace smaller than
+ * te_map_similarity_workspace_bytes TE_ERR_WORKSPACE (the query gives 0 for sizes the entry point refuses).
+ * ws: 8-byte aligned. */
+#define TE_MAPSIM_SSIM 1
+size_t te_map_similarity_workspace_bytes(int64_t B, int64_t n);
+int te_map_similarity_f32(const float* a, const float* b, int64_t* rank_sums, double* sim, int64_t B, int64_t n, int64_t H,
+                          int64_t W, int flags, double data_range, void* ws, size_t ws_bytes, te_stream_t stream);
+
 /* ---- rationale test of a BERT relevance vector (ERASER Movie Reviews) ---------------------
  * replaces, per document, the rationale production of BERT_rationale_benchmark/models/pipeline/bert_pipeline.py:547-582
  * (clamp(min=0) :552, scores_per_word_from_scores_per_token :96-138, sixteen topk calls :567-569) and the per-document

@@ -14,6 +14,7 @@ directory name carries a hyphen).  Layout:
   parallel.py                       one-process-per-GPU sharding + RCCL gather of the finished maps
   sweep.py, perturbation.py, segmentation.py   the evaluation protocols around the maps
   rationale.py                                 the rationale test on BERT (ERASER: token F1 at top-k, AUPRC, AOPC)
+  sanity.py                                    map similarity (Pearson, Spearman, SSIM), cascading randomisation, class sensitivity
   tuning/                           PyTorch TunableOp selection of the stock fp32 GEMMs of forward + backward
 """
 from . import _lib, ops, rules, rules_lrp  # noqa: F401

@@ -17,7 +17,9 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TE_RELPROP_LIB") or os.path.join(_PKG, "lib", "libte_relprop.so")
 
 TE_OK = 0
-MIN_LIB_VERSION = 700      # te_version(): 0.7.0, the fp64 rules (0.6.1: te_conv2d_zb_relprop_bf16, 0.6.0: te_build_id)
+MIN_LIB_VERSION = 701      # te_version(): 0.7.1, te_map_similarity_f32 (0.7.0: the fp64 rules, 0.6.1: te_conv2d_zb_relprop_bf16, 0.6.0: te_build_id)
+TE_ERR_INVALID_ARG = -1
+TE_ERR_WORKSPACE = -2
 TE_ERR_UNSUPPORTED = -3
 TE_VARIANT_OURS = 0
 TE_VARIANT_LRP = 1
@@ -28,6 +30,7 @@ TE_ROLLOUT_ROW0 = 4
 TE_HEADMEAN_CLAMP = 1
 TE_HEADMEAN_ROW0 = 2
 TE_RATIONALE_CLAMP = 1
+TE_MAPSIM_SSIM = 1
 TE_RATIONALE_MAX_KS = 16
 TE_TOKEN_ERASE_MAX_FRACTIONS = 8
 
@@ -118,6 +121,8 @@ SIGNATURES = {
     "te_heatmap_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, _P]),
     "te_seg_metrics_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "te_seg_metrics_f32": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
+    "te_map_similarity_workspace_bytes": (_SZ, [_I64, _I64]),
+    "te_map_similarity_f32": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _D, _P, _SZ, _P]),
     "te_rationale_metrics_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "te_rationale_metrics_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _I64, _I, _P, _SZ, _P]),
     "te_token_erase": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _I64, _I64, _P]),

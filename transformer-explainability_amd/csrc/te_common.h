@@ -127,6 +127,35 @@ __device__ __forceinline__ double te_wave_sum(double v) {
   return v;
 }
 
+// The radix sorts (te_segmetrics.hip, te_mapsim.hip): the lanes of the wave that hold the same 8-bit digit as this lane, among the `live` ones
+__device__ __forceinline__ uint64_t match_digit(uint32_t digit, bool live) {
+  uint64_t m = __ballot(live);
+#pragma unroll
+  for (int bit = 0; bit < 8; ++bit) {
+    const bool one = (digit >> bit) & 1u;
+    const uint64_t b = __ballot(live && one);
+    m &= one ? b : ~b;
+  }
+  return m;
+}
+
+// exclusive prefix of v over the block's threads; wtot: one word of LDS per wave
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wtot) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t incl = v;
+#pragma unroll
+  for (int off = 1; off < TE_WAVE; off <<= 1) {
+    const uint32_t n = __shfl_up(incl, off, TE_WAVE);
+    if (lane >= off) incl += n;
+  }
+  if (lane == TE_WAVE - 1) wtot[wave] = incl;
+  __syncthreads();
+  uint32_t before = 0;
+  for (int w = 0; w < wave; ++w) before += wtot[w];
+  __syncthreads();
+  return before + incl - v;
+}
+
 // Block-wide sum of up to 3 doubles; result valid in thread 0.  `smem` holds 3*(blockDim/64) doubles.
 __device__ __forceinline__ void te_block_sum3(double& a, double& b, double& c, double* smem) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;

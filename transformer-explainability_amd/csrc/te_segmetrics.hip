@@ -26,35 +26,6 @@ constexpr int kDigits = 256;
 constexpr int64_t kMaxPixels = (int64_t)1 << 20;
 constexpr int64_t kMaxBatch = 65535;
 
-// the lanes of the wave that hold the same 8-bit digit as this lane, among the `live` ones
-__device__ __forceinline__ uint64_t match_digit(uint32_t digit, bool live) {
-  uint64_t m = __ballot(live);
-#pragma unroll
-  for (int bit = 0; bit < 8; ++bit) {
-    const bool one = (digit >> bit) & 1u;
-    const uint64_t b = __ballot(live && one);
-    m &= one ? b : ~b;
-  }
-  return m;
-}
-
-// exclusive prefix of v over the block's threads; wtot: kWaves words of LDS
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wtot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int off = 1; off < TE_WAVE; off <<= 1) {
-    const uint32_t n = __shfl_up(incl, off, TE_WAVE);
-    if (lane >= off) incl += n;
-  }
-  if (lane == TE_WAVE - 1) wtot[wave] = incl;
-  __syncthreads();
-  uint32_t before = 0;
-  for (int w = 0; w < wave; ++w) before += wtot[w];
-  __syncthreads();
-  return before + incl - v;
-}
-
 __global__ __launch_bounds__(kThreads) void seg_metrics_kernel(const float* __restrict__ heat,
                                                                const float* __restrict__ mask,
                                                                const int64_t* __restrict__ labels,

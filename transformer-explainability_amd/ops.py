@@ -1387,6 +1387,56 @@ def seg_metrics(heat: Tensor, mask: Tensor, labels: Tensor):
     return seg_metrics_packed(heat, mask, labels)[:3]
 
 
+# ---------------------------------------------------------------------------------------- map similarity (sanity.py)
+def _map_pair(a: Tensor, b: Tensor, shape):
+    """The checks of map_similarity that need no device -> (B, n, H, W, ssim): raises TeError before any HIP call."""
+    if not (torch.is_tensor(a) and torch.is_tensor(b)):
+        raise _lib.TeError("map_similarity takes two tensors")
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise _lib.TeError(f"map_similarity takes float32 maps, got {a.dtype} / {b.dtype}")
+    if a.shape != b.shape or a.dim() not in (2, 3) or a.numel() == 0:
+        raise _lib.TeError(f"map_similarity: the maps must be [B,n] or [B,H,W] alike and not empty, got {tuple(a.shape)} and "
+                           f"{tuple(b.shape)}")
+    if a.dim() == 3 and shape is not None and tuple(shape) != tuple(a.shape[1:]):
+        raise _lib.TeError(f"map_similarity: shape={tuple(shape)} does not match the maps {tuple(a.shape)}")
+    B, n = a.shape[0], a[0].numel()
+    hw = tuple(a.shape[1:]) if a.dim() == 3 else None if shape is None else tuple(int(s) for s in shape)
+    if hw is not None:
+        if len(hw) != 2 or hw[0] * hw[1] != n:
+            raise _lib.TeError(f"map_similarity: shape={hw} does not match maps of {n} values")
+        if min(hw) < 7:
+            raise _lib.TeError(f"map_similarity: SSIM needs maps of at least 7x7 (the window), got {hw[0]}x{hw[1]}")
+    if not (a.is_cuda and b.is_cuda):
+        raise _lib.TeError("map_similarity needs tensors on the MI355X (got a CPU tensor); there is no CPU fallback here -- "
+                           "sanity.map_similarity is the torch restatement")
+    return (B, n, 0, 0, False) if hw is None else (B, n, hw[0], hw[1], True)
+
+
+def map_similarity_packed(a: Tensor, b: Tensor, shape=None, data_range: float = 1.0):
+    """``map_similarity`` and the flat int64 buffer its results are views of -- rank_sums [B*6], then the bits of sim [B*4]:
+    one device-to-host copy of it brings both over."""
+    B, n, H, W, ssim = _map_pair(a, b, shape)
+    a, b = _c(a).reshape(B, n), _c(b).reshape(B, n)
+    flat = torch.empty((B * 10,), dtype=torch.int64, device=a.device)
+    rank_sums = flat[:6 * B].view(B, 2, 3)
+    sim = flat[6 * B:].view(torch.float64).view(B, 4)
+    with _on_device(a) as lib:
+        ws = _ws(lib.te_map_similarity_workspace_bytes(B, n), a)
+        _lib.check(lib.te_map_similarity_f32(_ptr(a), _ptr(b), _ptr(rank_sums), _ptr(sim), B, n, H, W,
+                                             _lib.TE_MAPSIM_SSIM if ssim else 0, float(data_range), _ptr(ws), ws.numel(),
+                                             _stream(a)), "te_map_similarity_f32")
+    return rank_sums, sim, flat
+
+
+def map_similarity(a: Tensor, b: Tensor, shape=None, data_range: float = 1.0):
+    """How similar two relevance maps are, per sample, two launches, no synchronisation: a, b fp32 [B,n] or [B,H,W] (3-D maps or
+    ``shape=(H, W)`` turn SSIM on) -> (rank_sums int64 [B,2,3] = (cov, va, vb) of the rank deviations d = 2 rank - (n + 1)
+    of the values and of the absolute values; sim float64 [B,4] = pearson, spearman, spearman_abs, ssim), as
+    sanity.rank_sums / pearson / ssim define them (include/te_relprop.h, "map similarity").  A NaN anywhere in a sample
+    gives a NaN row and zero sums; n <= 2^20."""
+    return map_similarity_packed(a, b, shape, data_range)[:2]
+
+
 # ---------------------------------------------------------------------------------------- 8f rationale test (BERT)
 def _is_integer(t: Tensor) -> bool:
     return not (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool)
