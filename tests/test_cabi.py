@@ -1,5 +1,6 @@
 """C-ABI surface checks that need no GPU: the library is built, loads through ctypes, exports every
-symbol include/te_relprop.h declares, and the host-side workspace queries / argument validation work."""
+symbol include/te_relprop.h declares, and the host-side workspace queries / argument validation work; the parser that
+derives the ctypes binding from that header (_cabi.py) reads every kind of declaration and refuses what it does not know."""
 import os
 import re
 
@@ -33,6 +34,132 @@ def test_header_symbols_exported(lib):
 def test_binding_covers_header():
     from transformer_explainability_amd import _lib
     assert sorted(_lib.SIGNATURES) == declared_symbols()
+
+
+SYNTHETIC = """
+/* te_fake.h -- int te_in_a_comment(int x); is not a declaration,
+ * nor is size_t te_another_one(void); on a continuation line */
+#ifndef TE_FAKE_H
+#define TE_FAKE_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+typedef void* te_stream_t; /* hipStream_t */
+typedef uint16_t te_bf16_t;
+enum {
+  TE_OK = 0,
+  TE_ERR_BAD = -7,   /* trailing comment, with a comma */
+  TE_IMPL_FLAG = 0x1F0, // hex
+  TE_NEXT        /* no value: the one before, plus one */
+};
+enum { TE_ONE_LINE_A = 1, TE_ONE_LINE_B = -0x10 };
+#define TE_LIMIT 16   /* at most, see te_in_a_comment(int) */
+#define TE_BIG (1 << 20)
+#define TE_NEG -3
+#define TE_TILE_128x128 3
+#define TE_SPANS 0x4000   /* a comment that
+                             runs over two lines */
+#define TE_FN_LIKE(x) ((x) + 1)
+const char* te_name(void);
+size_t te_bytes();
+int
+te_split_over_lines(const te_bf16_t* W,
+                    void* ws,   /* scratch */
+                    te_stream_t stream,
+                    double eps, float alpha,
+                    int flags, int64_t n, size_t ws_bytes);
+int te_more(const int64_t* ks, unsigned* status, const float * const x, int64_t W_);
+#ifdef __cplusplus
+}
+#endif
+#endif /* TE_FAKE_H */
+"""
+
+
+def _cabi():
+    from transformer_explainability_amd import _cabi
+    return _cabi
+
+
+def test_parser_every_kind_of_declaration():
+    from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
+    protos, consts = _cabi().parse(SYNTHETIC)
+    assert protos == {
+        "te_name": (c_char_p, []),
+        "te_bytes": (c_size_t, []),
+        "te_split_over_lines": (c_int, [("W", c_void_p), ("ws", c_void_p), ("stream", c_void_p), ("eps", c_double),
+                                        ("alpha", c_float), ("flags", c_int), ("n", c_int64), ("ws_bytes", c_size_t)]),
+        "te_more": (c_int, [("ks", c_void_p), ("status", c_void_p), ("x", c_void_p), ("W_", c_int64)]),
+    }
+    assert consts == {"TE_OK": 0, "TE_ERR_BAD": -7, "TE_IMPL_FLAG": 0x1F0, "TE_NEXT": 0x1F1, "TE_ONE_LINE_A": 1,
+                      "TE_ONE_LINE_B": -16, "TE_LIMIT": 16, "TE_BIG": 1 << 20, "TE_NEG": -3, "TE_TILE_128x128": 3,
+                      "TE_SPANS": 0x4000}
+    assert all(type(v) is int for v in consts.values())
+
+
+@pytest.mark.parametrize("text, names", [
+    ("int te_f(int a, long b);", ["te_f", "b", "long"]),                       # unknown parameter type
+    ("int te_f(int64_t);", ["te_f", "int64_t"]),                               # a parameter without a name
+    ("int te_f(int a[4]);", ["te_f", "a[4]"]),
+    ("int te_f(int a, void (*cb)(int));", ["te_f"]),                           # nothing the grammar has
+    ("long te_f(int a);", ["te_f", "long"]),                                   # unknown return type
+    ("te_f(int a);", ["te_f"]),                                                # no return type
+    ("int te_ok(int a);\nint te_f(int a)\nint te_g(int b);", ["te_f"]),        # no ';'
+    ("int te_f(int a, int b;", ["te_f"]),                                      # no ')'
+    ("int te_f(int a) { return a; }", ["te_f"]),                               # a definition
+    ("int te_f(int a);\nint te_f(int a);", ["te_f", "twice"]),
+    ("#define TE_A (1 + 2)\n", ["TE_A", "1 + 2"]),                             # outside the fixed grammar: never eval'ed
+    ("#define TE_A __import__('os')\n", ["TE_A"]),
+    ("enum { TE_A = TE_B };", ["TE_A", "TE_B"]),
+])
+def test_parser_refuses_what_it_does_not_understand(text, names):
+    cabi = _cabi()
+    with pytest.raises(cabi.HeaderError) as e:
+        cabi.parse(text)
+    for n in names:
+        assert n in str(e.value), (n, str(e.value))
+
+
+def test_binding_pinned_facts():
+    """Facts of include/te_relprop.h written out here, not read through the parser."""
+    from ctypes import c_char_p, c_double, c_int, c_int64, c_size_t, c_void_p
+    from transformer_explainability_amd import _lib, ops
+    S = _lib.SIGNATURES
+    assert S["te_status_string"] == (c_char_p, [c_int])
+    assert S["te_build_id"] == (c_char_p, []) and S["te_version"] == (c_int, [])
+    assert S["te_linear_relprop_workspace_bytes"] == (c_size_t, [c_int64, c_int64, c_int64, c_int])
+    args = S["te_map_similarity_f32"][1]
+    assert len(args) == 13 and [i for i, t in enumerate(args) if t is c_double] == [9]
+    assert _lib.PARAMS["te_map_similarity_f32"][9] == "data_range"
+    res, args = S["te_attention_backward_strided_out_f32"]
+    assert res is c_int and len(args) == 43 and args[-4:] == [c_int, c_void_p, c_size_t, c_void_p]
+    assert _lib.PARAMS["te_attention_backward_strided_out_f32"][-4:] == ("need_qk", "ws", "ws_bytes", "stream")
+    assert all(len(_lib.PARAMS[n]) == len(S[n][1]) for n in S) and sorted(_lib.PARAMS) == sorted(S)
+    assert _lib.TE_OK == 0 and _lib.TE_ERR_NO_DEVICE == -4 and _lib.TE_IMPL_SIMPLE == 0x100
+    assert _lib.TE_X6_WHOLE_TILES == 0x10000 and ops.TE_X6_WHOLE_TILES == 0x10000
+    assert (ops.TE_X6_PHASE_SPLIT, ops.TE_X6_PHASE_Z, ops.TE_X6_PHASE_C) == (4, 8, 16)
+    assert (ops.TE_X6_TEST_DROP_HANDOVER, ops.TE_X6_TILE_Z_SHIFT, ops.TE_X6_TILE_C_SHIFT, ops.TE_X6_TEST_SMALL_GRID) == \
+        (0x200, 10, 12, 0x4000)
+    assert _lib.TE_CLASS_TARGETS_MAX_CLASSES == 1 << 20
+    assert "TE_RELPROP_H" not in _lib.CONSTANTS                                # the include guard is no constant
+
+
+def test_binding_follows_the_header():
+    """One int64_t fewer in one prototype of the real header: that entry's argtypes change, no other entry does."""
+    from ctypes import c_int64
+    cabi = _cabi()
+    text = open(HEADER).read()
+    victim, gone = "te_attention_backward_strided_out_f32", "int64_t dk_sh, "
+    at = text.index(gone, text.index(f"int {victim}("))
+    assert at < text.index(";", text.index(f"int {victim}("))                   # inside the victim's argument list
+    before, consts = cabi.parse(text)
+    after, consts_after = cabi.parse(text[:at] + text[at + len(gone):])
+    assert consts_after == consts and set(after) == set(before)
+    assert [n for n in before if after[n] != before[n]] == [victim]
+    params = before[victim][1]
+    i = [p for p, _ in params].index("dk_sh")
+    assert params[i][1] is c_int64 and after[victim][1] == params[:i] + params[i + 1:]
 
 
 def test_version_and_status_strings(lib):

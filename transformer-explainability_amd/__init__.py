@@ -5,7 +5,7 @@ Importable as ``transformer_explainability_amd`` (see the alias module at the re
 directory name carries a hyphen).  Layout:
 
   csrc/ + ../include/te_relprop.h   hand-written HIP kernels (gfx950) and the C ABI
-  _lib.py, ops.py                   ctypes binding, tensor-level wrappers (no CPU fallback)
+  _cabi.py, _lib.py, ops.py         the header's prototypes and constants as ctypes, the binding, tensor-level wrappers (no CPU fallback)
   rules.py, rules_lrp.py            rule classes = modules/layers_ours.py / layers_lrp.py of the reference
   vit.py, bert.py                   LRP-instrumented models = baselines/ViT/ViT_LRP.py, BERT.py ... of the reference
   generators.py                     LRP.generate_LRP / Generator.generate_LRP; generate_all: several methods, one pass

@@ -16,6 +16,9 @@ import torch
 from . import _lib
 from ._lib import (TE_HEADMEAN_CLAMP, TE_HEADMEAN_ROW0, TE_IMPL_SIMPLE, TE_RATIONALE_CLAMP, TE_ROLLOUT_CLS_FIXUP,
                    TE_ROLLOUT_NORMALISE, TE_ROLLOUT_ROW0, TE_VARIANT_LRP, TE_VARIANT_OURS)
+# te_relprop.h's x6 flag bits (TE_X6_WHOLE_TILES: whole-tile ranges always, for callers that keep several streams busy; same bits)
+from ._lib import (TE_X6_PHASE_C, TE_X6_PHASE_SPLIT, TE_X6_PHASE_Z, TE_X6_TEST_DROP_HANDOVER,  # noqa: F401
+                   TE_X6_TEST_SMALL_GRID, TE_X6_TILE_C_SHIFT, TE_X6_TILE_Z_SHIFT, TE_X6_WHOLE_TILES)
 
 Tensor = torch.Tensor
 _VARIANTS = {"ours": TE_VARIANT_OURS, "lrp": TE_VARIANT_LRP}
@@ -181,9 +184,6 @@ USE_LINEAR_X6 = os.environ.get("TE_LINEAR_X6", "1") not in ("", "0")
 X6_CHECK = False     # tests: synchronise after every x6 rule and raise if a bounded hand-over wait expired
 X6_TILE = 0          # te_relprop.h TE_X6_TILE_*: 0 auto, 1 = 128-row weight tiles (measurement knob; results are identical)
 X6_FLAGS = int(os.environ.get("TE_X6_FLAGS", "0"), 0)   # extra te_relprop.h flag bits for every x6 launch (per-pass tile pins, test hooks)
-TE_X6_PHASE_SPLIT, TE_X6_PHASE_Z, TE_X6_PHASE_C = 4, 8, 16
-TE_X6_TEST_DROP_HANDOVER, TE_X6_TILE_Z_SHIFT, TE_X6_TILE_C_SHIFT, TE_X6_TEST_SMALL_GRID = 0x200, 10, 12, 0x4000
-TE_X6_WHOLE_TILES = 0x10000     # whole-tile ranges always (callers that keep several streams busy); same bits
 
 
 # A workgroup of an x6 kernel that continues a tile another workgroup started waits for that one's accumulators; the wait
