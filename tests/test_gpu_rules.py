@@ -332,6 +332,109 @@ def test_linear_x6_variant_lrp_and_alpha(variant, alpha, T, in_f, out_f):
         ops.USE_LINEAR_X6, ops.X6_CHECK, ops.X6_TILE, ops.X6_FLAGS = was, False, 0, 0
 
 
+# The smallest feature counts the x6 kernels tile, a partial second 32-row block, and in_f != out_f both ways round: a plane
+# size taken for the other side's moves every later offset of the workspace.
+X6_SMALL_SHAPES = [(33, 128, 256), (33, 256, 128)]
+X6_FILL = 0xA5
+
+
+def _x6_filled(nbytes):
+    return torch.full((int(nbytes),), X6_FILL, dtype=torch.uint8, device=dev())
+
+
+def _x6_untouched(*buffers):
+    torch.cuda.synchronize()
+    return all(bool((b == X6_FILL).all()) for b in buffers)
+
+
+@pytest.mark.parametrize("entry", ["te_linear_relprop_x6_f32", "te_gemm_x6_f32", "te_linear_relprop_x6_general_f32"])
+def test_linear_x6_refused_call_writes_nothing(entry):
+    """A call the C ABI refuses has launched nothing: workspace and out keep a byte pattern, bit for bit.  The retired study
+    flags 0x100 and 0x8000 are unknown bits to the default rule, the plain product and the general rule."""
+    from transformer_explainability_amd import _lib, ops
+    T, in_f, out_f = X6_SMALL_SHAPES[0]
+    Xd, Wd, bd, Rd, Y = _x6_operands(T, in_f, out_f, 340)
+    lib = ops._lib.load()
+    wp, wg = ops.x6_weight_planes(Wd), ops.x6_matrix_planes(Wd, False)
+    st = torch.cuda.current_stream().cuda_stream
+    p = lambda t: t.data_ptr()      # noqa: E731
+    calls = {
+        "te_linear_relprop_x6_f32": (lib.te_linear_relprop_x6_workspace_bytes(T, in_f, out_f), T * in_f, lambda fl, out, ws: (
+            lib.te_linear_relprop_x6_f32(p(Rd), None, 0, 1, p(Xd), p(Wd), p(wp), None, p(Y), p(bd), p(out), T, in_f, out_f, fl,
+                                         None, p(ws), ws.numel(), st))),
+        "te_gemm_x6_f32": (lib.te_gemm_x6_workspace_bytes(T, in_f, out_f), T * out_f, lambda fl, out, ws: (
+            lib.te_gemm_x6_f32(p(Xd), None, p(wg), p(bd), p(out), T, in_f, out_f, fl, None, p(ws), ws.numel(), st))),
+        "te_linear_relprop_x6_general_f32": (
+            lib.te_linear_relprop_x6_general_workspace_bytes(T, in_f, out_f, _lib.TE_VARIANT_OURS), T * in_f, lambda fl, out, ws: (
+                lib.te_linear_relprop_x6_general_f32(p(Rd), None, 0, 1, p(Xd), p(Wd), p(wp), None, None, p(Y), p(bd), p(out), T,
+                                                     in_f, out_f, 2.0, _lib.TE_VARIANT_OURS, fl, None, p(ws), ws.numel(), st))),
+    }
+    ws_bytes, out_floats, call = calls[entry]
+    assert ws_bytes > 0
+    ws, out = _x6_filled(ws_bytes), _x6_filled(4 * out_floats)
+    for fl in (0x100, 0x8000):
+        assert call(fl, out, ws) == _lib.TE_ERR_INVALID_ARG, hex(fl)
+        assert _x6_untouched(ws, out), hex(fl)
+
+
+def test_linear_x6_plane_producer_refusals():
+    """The five plane producers refuse the same arguments with the same codes: TE_ERR_INVALID_ARG (a missing pointer, no rows)
+    before TE_ERR_UNSUPPORTED (K not in steps of 16, a misaligned fp32 operand) before TE_ERR_WORKSPACE (planes too small)."""
+    from transformer_explainability_amd import _lib, ops
+    rows, K = 33, 128
+    lib = ops._lib.load()
+    a, b = rnd((rows * K + 4,), 350).to(dev()), rnd((rows * K + 4,), 351).to(dev())
+    nb = lib.te_linear_x6_planes_bytes(rows, K)
+    assert nb == 64 * K * 6
+    pl, pa = _x6_filled(nb), _x6_filled(nb)
+    st = torch.cuda.current_stream().cuda_stream
+    # (fp32 operands of the entry point, call(operand pointers, rows, K, planes_bytes))
+    P, PA = pl.data_ptr(), pa.data_ptr()
+    producers = {
+        "te_linear_x6_split_abs_f32": (1, lambda s, r, k, n: lib.te_linear_x6_split_abs_f32(s[0], r, k, P, n, st)),
+        "te_linear_x6_split_matrix_f32": (1, lambda s, r, k, n: lib.te_linear_x6_split_matrix_f32(s[0], r, k, 0, P, n, st)),
+        "te_linear_x6_split_dual_f32": (1, lambda s, r, k, n: lib.te_linear_x6_split_dual_f32(s[0], r, k, P, PA, n, st)),
+        "te_gelu_backward_x6_planes_f32": (2, lambda s, r, k, n: lib.te_gelu_backward_x6_planes_f32(s[0], s[1], r, k, P, n, st)),
+        "te_gelu_forward_x6_planes_f32": (2, lambda s, r, k, n: lib.te_gelu_forward_x6_planes_f32(s[0], s[1], r, k, P, PA, n, st)),
+    }
+    nb24 = 64 * 24 * 6                                  # what [33, 24] would need, were K = 24 a plane shape
+    for name, (nsrc, call) in producers.items():
+        src = [a.data_ptr(), b.data_ptr()][:nsrc]
+        assert call(src, 0, K, nb) == _lib.TE_ERR_INVALID_ARG, name
+        assert call(src, rows, 24, nb) == _lib.TE_ERR_UNSUPPORTED, name
+        for i in range(nsrc):                           # each fp32 operand in turn, 4 bytes off
+            off = [s + 4 * (i == j) for j, s in enumerate(src)]
+            assert call(off, rows, K, nb) == _lib.TE_ERR_UNSUPPORTED, (name, i)
+        assert call(src, rows, K, nb - 1) == _lib.TE_ERR_WORKSPACE, name
+        assert call(src, rows, 24, nb24 - 1) == _lib.TE_ERR_UNSUPPORTED, name
+        assert call(src, 0, 24, nb) == _lib.TE_ERR_INVALID_ARG, name
+    assert _x6_untouched(pl, pa)
+
+
+@pytest.mark.parametrize("T,in_f,out_f", X6_SMALL_SHAPES)
+def test_linear_x6_check_reads_the_layout_the_call_wrote(T, in_f, out_f):
+    """te_linear_relprop_x6_check finds the two flag regions where te_linear_relprop_x6_f32 put them: in a workspace that
+    held a byte pattern everywhere, a clean call on the 16-workgroup grid (cut tiles, so hand-over flags go up and down)
+    leaves every word the check reads at zero -- and the bits of the default grid."""
+    from transformer_explainability_amd import ops
+    Xd, Wd, bd, Rd, Y = _x6_operands(T, in_f, out_f, 360)
+    lib = ops._lib.load()
+    wp = ops.x6_weight_planes(Wd)
+    st = torch.cuda.current_stream().cuda_stream
+    outs = []
+    for fl in (ops.TE_X6_TEST_SMALL_GRID, 0):
+        ws = _x6_filled(lib.te_linear_relprop_x6_workspace_bytes(T, in_f, out_f))
+        out = torch.empty((T, in_f), dtype=torch.float32, device=dev())
+        rc = lib.te_linear_relprop_x6_f32(Rd.data_ptr(), None, 0, 1, Xd.data_ptr(), Wd.data_ptr(), wp.data_ptr(), None,
+                                          Y.data_ptr(), bd.data_ptr(), out.data_ptr(), T, in_f, out_f, fl, None, ws.data_ptr(),
+                                          ws.numel(), st)
+        assert rc == 0, (fl, rc)
+        assert lib.te_linear_relprop_x6_check(ws.data_ptr(), T, in_f, out_f, st) == 0, fl
+        outs.append(out)
+    assert torch.isfinite(outs[0]).all()
+    assert torch.equal(outs[0], outs[1])
+
+
 @pytest.mark.parametrize("tile", [1, 2, 3], ids=["128x256", "256x256", "128x128"])
 def test_linear_x6_lost_handover_is_loud(tile):
     """VERDICT r3 item 2 / ADVICE r3: a stream-K hand-over that never arrives must not yield a plausible result.  The test

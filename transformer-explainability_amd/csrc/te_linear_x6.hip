@@ -272,7 +272,8 @@ struct X6Params {
   int nks;                     // K / 16
   // pad0_ / pad1_: bytes no kernel reads, which keep every field at its offset in the kernel arguments.  Without them hipcc
   // merges the scalar loads of nks and ntm / ntn, allocates SGPRs differently and changes the spills of the 128 x 256 Z- and
-  // C-pass kernels: a kernel change that would need its own same-box measurement.
+  // C-pass kernels: a kernel change that would need its own same-box measurement.  The static_asserts on sizeof / offsetof
+  // below x6_kernel pin the block.
   unsigned char pad0_[20];
   int ntm, ntn;                // tiles along the weight side / the activation side (set by launch_x6 from rows_w, T)
   int rows_w;                  // weight-side rows of the product: out_f (Z-pass, plain product), 2 in_f (C-pass: +/- pairs)
@@ -1029,14 +1030,68 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
   }
 }
 
+// The kernel-argument block of x6_kernel, pinned (the comment at pad0_): the values of the build the spills were measured on.
+static_assert(sizeof(X6Params) == 248, "X6Params is the kernel-argument block of x6_kernel");
+static_assert(offsetof(X6Params, ntm) == 56 && offsetof(X6Params, ncb) == 80 && offsetof(X6Params, T) == 88 &&
+              offsetof(X6Params, partial) == 104 && offsetof(X6Params, R) == 152 && offsetof(X6Params, out) == 224,
+              "a field of X6Params moved in the kernel arguments");
+
 inline size_t planes_bytes(int64_t rows, int64_t K) {
   return (size_t)te_ceil_div(rows, 32) * 32 * (size_t)K * 6;
 }
+inline bool bad_k(int64_t K) { return K < 16 || K % 16; }         // planes are cut in K16 steps
 // (A fixed K split -- two k-ordered chains per output for long-K, few-row products -- was measured and not shipped:
 // 5 % over the 128 x 128 geometry in isolated launches, nothing in the step)
 constexpr size_t kPartialBytes = (size_t)512 * 256 * 128 * 4;       // grid x threads x accumulators: 64 MiB covers every geometry
 constexpr double kWholeTileSlack = 1.15;                          // whole tiles if ceil(r) <= 1.15 r (launch_x6)
 constexpr size_t kFlagBytes = 65536;                                 // 512 flags + the error word, per pass
+constexpr int kFlagWords = kFlagBytes / 4;                           // one pass's flag region, in words ...
+constexpr int kUsedFlagWords = kErrWord + 1;                         // ... of which a launch touches these (the check reads them)
+constexpr int kRulePasses = 2;                                       // default rule: Z-pass, C-pass
+constexpr int kGeneralPasses = 8;                                    // general rule: four per half + the per-call error word's
+
+// ---- where things lie: ONE statement per buffer, read by the *_bytes query, the call that writes and the call that reads ----
+// Workspace of a call, byte offsets (every region 256-byte aligned): `xsets` plane sets of the input side ([T, K] each) from 0,
+// `ssets` of the output side ([T, M] each) from s, the accumulators of cut tiles, one flag region per pass.
+struct X6Workspace {
+  size_t x_stride, s, s_stride, partial, flags, total;
+  unsigned char* x(void* ws, int set) const { return (unsigned char*)ws + set * x_stride; }
+  unsigned char* sp(void* ws, int set) const { return (unsigned char*)ws + s + set * s_stride; }
+  float* acc(void* ws) const { return (float*)((unsigned char*)ws + partial); }
+  unsigned* flag_region(const void* ws, int pass) const { return (unsigned*)((unsigned char*)ws + flags) + (size_t)pass * kFlagWords; }
+};
+inline X6Workspace x6_workspace(int64_t T, int64_t K, int64_t M, int xsets, int ssets, int passes) {
+  X6Workspace l;
+  l.x_stride = te_align_up(planes_bytes(T, K), 256);
+  l.s_stride = te_align_up(planes_bytes(T, M), 256);
+  l.s = xsets * l.x_stride;
+  l.partial = l.s + ssets * l.s_stride;
+  l.flags = l.partial + kPartialBytes;
+  l.total = l.flags + passes * kFlagBytes;
+  return l;
+}
+// plain product: X planes | default rule: |X| planes, S planes | general rule: |X| or X+, X-, then S / S' or S1, S2
+inline X6Workspace gemm_workspace(int64_t T, int64_t K, int64_t M) { return x6_workspace(T, K, M, 1, 0, 1); }
+inline X6Workspace rule_workspace(int64_t T, int64_t in_f, int64_t out_f) { return x6_workspace(T, in_f, out_f, 1, 1, kRulePasses); }
+inline X6Workspace general_workspace(int64_t T, int64_t in_f, int64_t out_f) { return x6_workspace(T, in_f, out_f, 2, 2, kGeneralPasses); }
+
+// weight planes of the default rule: P3 of |W| (rows = out_f, K = in_f) at 0, P6 of W+^T / W-^T (rows = in_f, K = out_f) at c
+struct X6WeightPlanes { size_t c, total; };
+inline X6WeightPlanes weight_planes(int64_t in_f, int64_t out_f) {
+  const size_t c = te_align_up(planes_bytes(out_f, in_f), 256);
+  return {c, c + te_align_up(2 * planes_bytes(in_f, out_f), 256)};
+}
+// weight planes of variant lrp: P3 of W+ at 0 and of W- at wn (rows = out_f, K = in_f), of W+^T at wpT and of W-^T at wnT (rows = in_f, K = out_f)
+struct X6WeightPlanesLrp { size_t wn, wpT, wnT, total; };
+inline X6WeightPlanesLrp weight_planes_lrp(int64_t in_f, int64_t out_f) {
+  const size_t za = te_align_up(planes_bytes(out_f, in_f), 256), ca = te_align_up(planes_bytes(in_f, out_f), 256);
+  return {za, 2 * za, 2 * za + ca, 2 * za + 2 * ca};
+}
+
+// ---- flags (te_relprop.h) ----
+constexpr int kTileMask = TE_X6_TILE_128 | TE_X6_TILE_256 | TE_X6_TILE_128x128;
+constexpr int kProductFlags = kTileMask | TE_X6_WHOLE_TILES | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID;   // plain product, general rule
+constexpr int kRuleFlags = kProductFlags | TE_X6_PHASE_MASK | (kTileMask << TE_X6_TILE_Z_SHIFT) | (kTileMask << TE_X6_TILE_C_SHIFT);
 
 inline int pick_wm(int64_t in_f, int64_t out_f) {
   if (out_f % 256 == 0 && in_f % 128 == 0) return 2;
@@ -1115,6 +1170,76 @@ inline int choose_geo(int wm_max, int64_t T, int64_t rows_w, int pin, int min_ti
   return 1;
 }
 
+// ---- X6Params: what every launch of a call shares, then what one pass adds ----
+// shape, accumulators, the operands of the plain product's epilogue, the status word and the schedule flags
+inline X6Params call_params(int64_t T, float* partial, const float* bias, float* out, unsigned* status, int flags) {
+  X6Params p{};
+  p.T = T;
+  p.ncb = (int)te_ceil_div(T, 32);
+  p.partial = partial;
+  p.bias = bias;
+  p.out = out;
+  p.status = status;
+  p.drop_handover = (flags & TE_X6_TEST_DROP_HANDOVER) ? 1 : 0;
+  p.small_grid = (flags & TE_X6_TEST_SMALL_GRID) ? 1 : 0;
+  p.prefer_whole = (flags & TE_X6_WHOLE_TILES) ? 1 : 0;
+  return p;
+}
+// + the fp32 operands of a rule's epilogues
+inline X6Params rule_params(X6Params p, const float* R, const float* r_scale, int64_t r_scale_stride, int64_t rows_per_sample,
+                            const float* X, const float* W, const float* Y) {
+  p.R = R;
+  p.Y = Y;
+  p.X = X;
+  p.W = W;
+  p.rs = r_scale;
+  p.rs_stride = r_scale_stride;
+  p.rps = (int)(r_scale ? rows_per_sample : 1);
+  return p;
+}
+inline bool bad_r_scale(const float* r_scale, int64_t rows_per_sample, int64_t T) {
+  return r_scale && (rows_per_sample <= 0 || rows_per_sample > 0x7fffffff || T % rows_per_sample);
+}
+
+// One launch of a Linear layer [T, in_f] -> [T, out_f] on tile geometry wm, with its own flag region.  The mode fixes the shape
+// of the product:  Z-like (MODE_Z / ZI / Z1) and the plain product (in_f = K, out_f = M): sums over in_f, out_f weight-side rows;
+// C-like (MODE_C / CI): sums over out_f, weight side = the (+, -) pairs of P6 planes, 2 in_f rows;
+// MODE_X (out (+)= scale * (X^sign . (S W^t))): sums over out_f, in_f weight-side rows, and the kernel's plain-product naming (K, M).
+template <int MODE>
+int launch_pass(X6Params p, int wm, const unsigned char* A, const unsigned char* B, unsigned char* S, int64_t in_f,
+                int64_t out_f, unsigned* flag_region, hipStream_t stream, float scale = 0.0f, int accum = 0, int x_sign = 0) {
+  constexpr bool c_like = MODE == MODE_C || MODE == MODE_CI;
+  constexpr bool over_out = c_like || MODE == MODE_X;
+  p.A = A, p.B = B, p.S = S;
+  p.nks = (int)((over_out ? out_f : in_f) / 16);
+  p.a_group_stride = (int64_t)p.nks * (c_like ? 2 : 1) * kRB;
+  p.b_rb_stride = (int64_t)p.nks * kRB;
+  p.rows_w = (int)(c_like ? 2 * in_f : MODE == MODE_X ? in_f : out_f);
+  p.in_f = (int)(MODE == MODE_X ? out_f : in_f);
+  p.out_f = (int)(MODE == MODE_X ? in_f : out_f);
+  p.scale = scale, p.accum = accum, p.x_sign = x_sign;
+  p.flags = flag_region;
+  return launch_x6_mode<MODE>(wm, p, stream);
+}
+
+// the hand-over flags of `passes` passes start from zero (a kernel, not a memset node: a rule stays a chain of kernel nodes
+// when it is captured in a HIP graph)
+inline void zero_flag_regions(unsigned* flag_words, int passes, hipStream_t stream) {
+  zero_words_kernel<<<dim3(passes * kFlagBytes / 16 / 256), dim3(256), 0, stream>>>(reinterpret_cast<u32x4*>(flag_words));
+}
+
+// ---- the plane producers: one argument check, one grid ----
+// have_all: no NULL among the pointers; rows >= 1: else INVALID_ARG.  K in K16 steps, the fp32 side 16-byte aligned, rows <= 2^26:
+// else UNSUPPORTED.  planes_bytes_ covers [rows, K], the planes 16-byte aligned: else WORKSPACE.
+inline int check_producer(bool have_all, bool f32_aligned, bool planes_aligned, int64_t rows, int64_t K, size_t planes_bytes_) {
+  if (!have_all || rows < 1) return TE_ERR_INVALID_ARG;
+  if (bad_k(K) || !f32_aligned || rows > ((int64_t)1 << 26)) return TE_ERR_UNSUPPORTED;
+  if (planes_bytes_ < planes_bytes(rows, K) || !planes_aligned) return TE_ERR_WORKSPACE;
+  return TE_OK;
+}
+// one 256-thread workgroup per 32-row block and eight K16 steps
+inline dim3 producer_grid(int64_t rows, int64_t K) { return dim3((unsigned)te_ceil_div(rows, 32), (unsigned)te_ceil_div(K / 16, 8)); }
+
 }  // namespace
 
 // ----------------------------------------------------------------------------------------------------------------------
@@ -1124,9 +1249,7 @@ extern "C" int te_linear_relprop_x6_supported(int64_t T, int64_t in_f, int64_t o
 }
 
 extern "C" size_t te_linear_x6_weight_planes_bytes(int64_t in_f, int64_t out_f) {
-  if (!te_linear_relprop_x6_supported(1, in_f, out_f)) return 0;
-  // P3 of |W| (rows = out_f, K = in_f) followed by P6 of W+^T / W-^T (rows = in_f, K = out_f)
-  return te_align_up(planes_bytes(out_f, in_f), 256) + te_align_up(2 * planes_bytes(in_f, out_f), 256);
+  return te_linear_relprop_x6_supported(1, in_f, out_f) ? weight_planes(in_f, out_f).total : 0;
 }
 
 extern "C" int te_linear_x6_prepare_weights_f32(const float* W, int64_t in_f, int64_t out_f, void* planes,
@@ -1136,10 +1259,9 @@ extern "C" int te_linear_x6_prepare_weights_f32(const float* W, int64_t in_f, in
   if (planes_bytes_ < te_linear_x6_weight_planes_bytes(in_f, out_f) || !te_aligned16(planes)) return TE_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   unsigned char* pz = (unsigned char*)planes;
-  unsigned char* pc = pz + te_align_up(planes_bytes(out_f, in_f), 256);
-  split_kernel<OP_ABS, false><<<dim3((unsigned)(out_f / 32), (unsigned)te_ceil_div(in_f / 16, 8)), dim3(256), 0, stream>>>(
-      W, pz, out_f, in_f, 3, 0);
-  const dim3 gc((unsigned)(in_f / 32), (unsigned)te_ceil_div(out_f / 16, 8));
+  unsigned char* pc = pz + weight_planes(in_f, out_f).c;
+  split_kernel<OP_ABS, false><<<producer_grid(out_f, in_f), dim3(256), 0, stream>>>(W, pz, out_f, in_f, 3, 0);
+  const dim3 gc = producer_grid(in_f, out_f);
   split_kernel<OP_POS, true><<<gc, dim3(256), 0, stream>>>(W, pc, in_f, out_f, 6, 0);
   split_kernel<OP_NEG, true><<<gc, dim3(256), 0, stream>>>(W, pc, in_f, out_f, 6, 1);
   TE_RETURN_IF_LAUNCH_FAILED();
@@ -1147,16 +1269,14 @@ extern "C" int te_linear_x6_prepare_weights_f32(const float* W, int64_t in_f, in
 }
 
 extern "C" size_t te_linear_x6_planes_bytes(int64_t rows, int64_t K) {
-  return (rows < 1 || K < 16 || K % 16) ? 0 : planes_bytes(rows, K);
+  return (rows < 1 || bad_k(K)) ? 0 : planes_bytes(rows, K);
 }
 
 extern "C" int te_linear_x6_split_abs_f32(const float* X, int64_t rows, int64_t K, void* planes, size_t planes_bytes_,
                                           te_stream_t stream_) {
-  if (!X || !planes || rows < 1) return TE_ERR_INVALID_ARG;
-  if (K < 16 || K % 16 || !te_aligned16(X) || rows > ((int64_t)1 << 26)) return TE_ERR_UNSUPPORTED;
-  if (planes_bytes_ < planes_bytes(rows, K) || !te_aligned16(planes)) return TE_ERR_WORKSPACE;
-  split_kernel<OP_ABS, false><<<dim3((unsigned)te_ceil_div(rows, 32), (unsigned)te_ceil_div(K / 16, 8)), dim3(256), 0,
-                                (hipStream_t)stream_>>>(X, (unsigned char*)planes, rows, K, 3, 0);
+  const int rc = check_producer(X && planes, te_aligned16(X), te_aligned16(planes), rows, K, planes_bytes_);
+  if (rc != TE_OK) return rc;
+  split_kernel<OP_ABS, false><<<producer_grid(rows, K), dim3(256), 0, (hipStream_t)stream_>>>(X, (unsigned char*)planes, rows, K, 3, 0);
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
 }
@@ -1171,10 +1291,9 @@ extern "C" int te_gemm_x6_supported(int64_t T, int64_t K, int64_t M) {
 
 extern "C" int te_linear_x6_split_matrix_f32(const float* A, int64_t rows, int64_t K, int transposed, void* planes,
                                              size_t planes_bytes_, te_stream_t stream_) {
-  if (!A || !planes || rows < 1) return TE_ERR_INVALID_ARG;
-  if (K < 16 || K % 16 || !te_aligned16(A) || rows > ((int64_t)1 << 26)) return TE_ERR_UNSUPPORTED;
-  if (planes_bytes_ < planes_bytes(rows, K) || !te_aligned16(planes)) return TE_ERR_WORKSPACE;
-  const dim3 grid((unsigned)te_ceil_div(rows, 32), (unsigned)te_ceil_div(K / 16, 8));
+  const int rc = check_producer(A && planes, te_aligned16(A), te_aligned16(planes), rows, K, planes_bytes_);
+  if (rc != TE_OK) return rc;
+  const dim3 grid = producer_grid(rows, K);
   if (transposed)       // A is [K, rows] in memory
     split_kernel<OP_ID, true><<<grid, dim3(256), 0, (hipStream_t)stream_>>>(A, (unsigned char*)planes, rows, K, 3, 0);
   else
@@ -1187,12 +1306,10 @@ extern "C" int te_linear_x6_split_matrix_f32(const float* A, int64_t rows, int64
 // relprop rule the second: te_linear_relprop_x6_f32's x_planes)
 extern "C" int te_linear_x6_split_dual_f32(const float* A, int64_t rows, int64_t K, void* planes, void* planes_abs,
                                            size_t planes_bytes_, te_stream_t stream_) {
-  if (!A || !planes || !planes_abs || rows < 1) return TE_ERR_INVALID_ARG;
-  if (K < 16 || K % 16 || !te_aligned16(A) || rows > ((int64_t)1 << 26)) return TE_ERR_UNSUPPORTED;
-  if (planes_bytes_ < planes_bytes(rows, K) || !te_aligned16(planes) || !te_aligned16(planes_abs)) return TE_ERR_WORKSPACE;
-  const dim3 grid((unsigned)te_ceil_div(rows, 32), (unsigned)te_ceil_div(K / 16, 8));
-  split_kernel<OP_ID, false><<<grid, dim3(256), 0, (hipStream_t)stream_>>>(A, (unsigned char*)planes, rows, K, 3, 0,
-                                                                          (unsigned char*)planes_abs);
+  const int rc = check_producer(A && planes && planes_abs, te_aligned16(A), te_aligned16(planes) && te_aligned16(planes_abs), rows, K, planes_bytes_);
+  if (rc != TE_OK) return rc;
+  split_kernel<OP_ID, false><<<producer_grid(rows, K), dim3(256), 0, (hipStream_t)stream_>>>(A, (unsigned char*)planes, rows, K, 3, 0,
+                                                                                           (unsigned char*)planes_abs);
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
 }
@@ -1200,78 +1317,50 @@ extern "C" int te_linear_x6_split_dual_f32(const float* A, int64_t rows, int64_t
 // GELU producers that write operand planes (gelu_split_lds_kernel above); planes / planes_abs: te_linear_x6_planes_bytes(rows, K)
 extern "C" int te_gelu_backward_x6_planes_f32(const float* dy, const float* x, int64_t rows, int64_t K, void* planes,
                                               size_t planes_bytes_, te_stream_t stream_) {
-  if (!dy || !x || !planes || rows < 1) return TE_ERR_INVALID_ARG;
-  if (K < 16 || K % 16 || !te_aligned16(dy) || !te_aligned16(x) || rows > ((int64_t)1 << 26)) return TE_ERR_UNSUPPORTED;
-  if (planes_bytes_ < planes_bytes(rows, K) || !te_aligned16(planes)) return TE_ERR_WORKSPACE;
-  const dim3 grid((unsigned)te_ceil_div(rows, 32), (unsigned)te_ceil_div(K / 16, 8));
-  gelu_split_lds_kernel<SRC_GELU_BWD><<<grid, dim3(256), 0, (hipStream_t)stream_>>>(dy, x, nullptr, (unsigned char*)planes,
-                                                                                   nullptr, rows, K);
+  const int rc = check_producer(dy && x && planes, te_aligned16(dy) && te_aligned16(x), te_aligned16(planes), rows, K, planes_bytes_);
+  if (rc != TE_OK) return rc;
+  gelu_split_lds_kernel<SRC_GELU_BWD><<<producer_grid(rows, K), dim3(256), 0, (hipStream_t)stream_>>>(
+      dy, x, nullptr, (unsigned char*)planes, nullptr, rows, K);
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
 }
 
 extern "C" int te_gelu_forward_x6_planes_f32(const float* x, float* y, int64_t rows, int64_t K, void* planes, void* planes_abs,
                                              size_t planes_bytes_, te_stream_t stream_) {
-  if (!x || !y || !planes || !planes_abs || rows < 1) return TE_ERR_INVALID_ARG;
-  if (K < 16 || K % 16 || !te_aligned16(x) || !te_aligned16(y) || rows > ((int64_t)1 << 26)) return TE_ERR_UNSUPPORTED;
-  if (planes_bytes_ < planes_bytes(rows, K) || !te_aligned16(planes) || !te_aligned16(planes_abs)) return TE_ERR_WORKSPACE;
-  const dim3 grid((unsigned)te_ceil_div(rows, 32), (unsigned)te_ceil_div(K / 16, 8));
-  gelu_split_lds_kernel<SRC_GELU_FWD><<<grid, dim3(256), 0, (hipStream_t)stream_>>>(nullptr, x, y, (unsigned char*)planes,
-                                                                                   (unsigned char*)planes_abs, rows, K);
+  const int rc = check_producer(x && y && planes && planes_abs, te_aligned16(x) && te_aligned16(y),
+                                te_aligned16(planes) && te_aligned16(planes_abs), rows, K, planes_bytes_);
+  if (rc != TE_OK) return rc;
+  gelu_split_lds_kernel<SRC_GELU_FWD><<<producer_grid(rows, K), dim3(256), 0, (hipStream_t)stream_>>>(
+      nullptr, x, y, (unsigned char*)planes, (unsigned char*)planes_abs, rows, K);
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
 }
 
 extern "C" size_t te_gemm_x6_workspace_bytes(int64_t T, int64_t K, int64_t M) {
-  if (!te_gemm_x6_supported(T, K, M)) return 0;
-  return te_align_up(planes_bytes(T, K), 256) + kPartialBytes + kFlagBytes;
+  return te_gemm_x6_supported(T, K, M) ? gemm_workspace(T, K, M).total : 0;
 }
 
 extern "C" int te_gemm_x6_f32(const float* X, const void* x_planes, const void* w_planes, const float* bias, float* out,
                               int64_t T, int64_t K, int64_t M, int flags, unsigned* status, void* ws, size_t ws_bytes,
                               te_stream_t stream_) {
   if ((!X && !x_planes) || !w_planes || !out) return TE_ERR_INVALID_ARG;
-  if ((flags & ~(3 | TE_X6_WHOLE_TILES | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID)) != 0) return TE_ERR_INVALID_ARG;
+  if ((flags & ~kProductFlags) != 0) return TE_ERR_INVALID_ARG;
   if (!te_gemm_x6_supported(T, K, M)) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_gemm_x6_workspace_bytes(T, K, M) || !te_aligned16(ws)) return TE_ERR_WORKSPACE;
   if ((X && !te_aligned16(X)) || !te_aligned16(out) || !te_aligned16(w_planes) || (bias && !te_aligned16(bias)) ||
       (x_planes && !te_aligned16(x_planes)))
     return TE_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
-  unsigned char* q = (unsigned char*)ws;
-  unsigned char* Xs = q;
-  q += te_align_up(planes_bytes(T, K), 256);
-  float* partial = (float*)q;
-  q += kPartialBytes;
-  unsigned* flag_words = (unsigned*)q;
-  q += kFlagBytes;
-  zero_words_kernel<<<dim3(kFlagBytes / 16 / 256), dim3(256), 0, stream>>>(reinterpret_cast<u32x4*>(flag_words));
+  const X6Workspace l = gemm_workspace(T, K, M);
+  zero_flag_regions(l.flag_region(ws, 0), 1, stream);
   if (!x_planes) {
-    int rc = te_linear_x6_split_matrix_f32(X, T, K, 0, Xs, planes_bytes(T, K), stream_);
+    int rc = te_linear_x6_split_matrix_f32(X, T, K, 0, l.x(ws, 0), planes_bytes(T, K), stream_);
     if (rc != TE_OK) return rc;
-    x_planes = Xs;
+    x_planes = l.x(ws, 0);
   }
-  const int wm = choose_geo((M % 256 == 0) ? 2 : 1, T, M, flags & 3, 192, true);
-  X6Params p{};
-  p.status = status;
-  p.drop_handover = (flags & TE_X6_TEST_DROP_HANDOVER) ? 1 : 0;
-  p.small_grid = (flags & TE_X6_TEST_SMALL_GRID) ? 1 : 0;
-  p.prefer_whole = (flags & TE_X6_WHOLE_TILES) ? 1 : 0;
-  p.T = T;
-  p.in_f = (int)K;
-  p.out_f = (int)M;
-  p.ncb = (int)te_ceil_div(T, 32);
-  p.rows_w = (int)M;
-  p.partial = partial;
-  p.flags = flag_words;
-  p.bias = bias;
-  p.out = out;
-  p.A = (const unsigned char*)w_planes;
-  p.B = (const unsigned char*)x_planes;
-  p.nks = (int)(K / 16);
-  p.a_group_stride = (int64_t)p.nks * kRB;
-  p.b_rb_stride = (int64_t)p.nks * kRB;
-  const int rc = launch_x6_mode<MODE_G>(wm, p, stream);
+  const int wm = choose_geo((M % 256 == 0) ? 2 : 1, T, M, flags & kTileMask, 192, true);
+  const int rc = launch_pass<MODE_G>(call_params(T, l.acc(ws), bias, out, status, flags), wm, (const unsigned char*)w_planes,
+                                     (const unsigned char*)x_planes, nullptr, K, M, l.flag_region(ws, 0), stream);
   if (rc != TE_OK) return rc;
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
@@ -1279,8 +1368,7 @@ extern "C" int te_gemm_x6_f32(const float* X, const void* x_planes, const void* 
 
 // workspace: |X| planes, S planes, the accumulators of cut tiles, flags (Z-pass, C-pass)
 extern "C" size_t te_linear_relprop_x6_workspace_bytes(int64_t T, int64_t in_f, int64_t out_f) {
-  if (!te_linear_relprop_x6_supported(T, in_f, out_f)) return 0;
-  return te_align_up(planes_bytes(T, in_f), 256) + te_align_up(planes_bytes(T, out_f), 256) + kPartialBytes + 2 * kFlagBytes;
+  return te_linear_relprop_x6_supported(T, in_f, out_f) ? rule_workspace(T, in_f, out_f).total : 0;
 }
 
 extern "C" int te_linear_relprop_x6_f32(const float* R, const float* r_scale, int64_t r_scale_stride,
@@ -1288,92 +1376,45 @@ extern "C" int te_linear_relprop_x6_f32(const float* R, const float* r_scale, in
                                         const void* x_planes, const float* Y, const float* bias, float* out, int64_t T,
                                         int64_t in_f, int64_t out_f, int flags, unsigned* status, void* ws,
                                         size_t ws_bytes, te_stream_t stream_) {
+  // every refusal comes before the first launch: a refused call leaves workspace and out as they were
   if (!R || !X || !W || !w_planes || !Y || !out || T <= 0) return TE_ERR_INVALID_ARG;
   if (!te_linear_relprop_x6_supported(T, in_f, out_f)) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_linear_relprop_x6_workspace_bytes(T, in_f, out_f) || !te_aligned16(ws)) return TE_ERR_WORKSPACE;
   if (!te_aligned16(X) || !te_aligned16(W) || !te_aligned16(R) || !te_aligned16(Y) || !te_aligned16(out) ||
       !te_aligned16(w_planes) || (bias && !te_aligned16(bias)) || (x_planes && !te_aligned16(x_planes)))
     return TE_ERR_UNSUPPORTED;
-  if (r_scale && (rows_per_sample <= 0 || rows_per_sample > 0x7fffffff || T % rows_per_sample)) return TE_ERR_INVALID_ARG;
+  if (bad_r_scale(r_scale, rows_per_sample, T)) return TE_ERR_INVALID_ARG;
+  if ((flags & ~kRuleFlags) != 0) return TE_ERR_INVALID_ARG;
   const int phases = (flags & TE_X6_PHASE_MASK) ? (flags & TE_X6_PHASE_MASK) : TE_X6_PHASE_MASK;
   hipStream_t stream = (hipStream_t)stream_;
-  unsigned char* q = (unsigned char*)ws;
-  unsigned char* Xs = q;
-  q += te_align_up(planes_bytes(T, in_f), 256);
-  unsigned char* Ss = q;
-  q += te_align_up(planes_bytes(T, out_f), 256);
-  float* partial = (float*)q;
-  q += kPartialBytes;
-  unsigned* flag_words = (unsigned*)q;
-  q += 2 * kFlagBytes;
+  const X6Workspace l = rule_workspace(T, in_f, out_f);
+  unsigned char* Ss = l.sp(ws, 0);
   const unsigned char* wz = (const unsigned char*)w_planes;
-  const unsigned char* wc = wz + te_align_up(planes_bytes(out_f, in_f), 256);
+  const unsigned char* wc = wz + weight_planes(in_f, out_f).c;
 
-  if (phases & TE_X6_PHASE_SPLIT) {
-    // the hand-over flags of both passes start from zero (a kernel, not a memset node: the whole rule stays a chain of
-    // kernel nodes when it is captured in a HIP graph)
-    zero_words_kernel<<<dim3(2 * kFlagBytes / 16 / 256), dim3(256), 0, stream>>>(reinterpret_cast<u32x4*>(flag_words));
-  }
+  if (phases & TE_X6_PHASE_SPLIT) zero_flag_regions(l.flag_region(ws, 0), kRulePasses, stream);
   if (!x_planes) {
     if (phases & TE_X6_PHASE_SPLIT) {
-      int rc = te_linear_x6_split_abs_f32(X, T, in_f, Xs, planes_bytes(T, in_f), stream_);
+      int rc = te_linear_x6_split_abs_f32(X, T, in_f, l.x(ws, 0), planes_bytes(T, in_f), stream_);
       if (rc != TE_OK) return rc;
     }
-    x_planes = Xs;
+    x_planes = l.x(ws, 0);
   }
   // Tile geometry per pass (the result does not depend on it, bit for bit): 256 weight rows / one 512-thread workgroup per
   // CU where that gives every CU at least one tile, else 128 rows / two 256-thread workgroups per CU.
   const int wm_max = pick_wm(in_f, out_f);
-  const int pin_z = ((flags >> TE_X6_TILE_Z_SHIFT) & 3) ? ((flags >> TE_X6_TILE_Z_SHIFT) & 3) : (flags & 3);      // per-pass pins win
-  const int pin_c = ((flags >> TE_X6_TILE_C_SHIFT) & 3) ? ((flags >> TE_X6_TILE_C_SHIFT) & 3) : (flags & 3);
-  const int wm_z = choose_geo(wm_max, T, out_f, pin_z, 256, true);
-  const int wm_c = choose_geo(wm_max, T, 2 * in_f, pin_c);
-  if ((flags & ~(0x1f | TE_X6_WHOLE_TILES | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID | 0x3c00)) != 0) return TE_ERR_INVALID_ARG;
-  int wm = 0;
-  X6Params p{};
-  p.T = T;
-  p.in_f = (int)in_f;
-  p.out_f = (int)out_f;
-  p.ncb = (int)te_ceil_div(T, 32);
-  p.partial = partial;
-  p.R = R;
-  p.Y = Y;
-  p.bias = bias;
-  p.X = X;
-  p.W = W;
-  p.S = Ss;
-  p.rs = r_scale;
-  p.rs_stride = r_scale_stride;
-  p.rps = (int)(r_scale ? rows_per_sample : 1);
-  p.out = out;
-  p.scale = 1.0f;
-  p.status = status;
-  p.drop_handover = (flags & TE_X6_TEST_DROP_HANDOVER) ? 1 : 0;
-  p.small_grid = (flags & TE_X6_TEST_SMALL_GRID) ? 1 : 0;
-  p.prefer_whole = (flags & TE_X6_WHOLE_TILES) ? 1 : 0;
+  const int pz = (flags >> TE_X6_TILE_Z_SHIFT) & kTileMask, pc = (flags >> TE_X6_TILE_C_SHIFT) & kTileMask;
+  const int wm_z = choose_geo(wm_max, T, out_f, pz ? pz : (flags & kTileMask), 256, true);      // per-pass pins win
+  const int wm_c = choose_geo(wm_max, T, 2 * in_f, pc ? pc : (flags & kTileMask));
+  const X6Params p = rule_params(call_params(T, l.acc(ws), bias, out, status, flags), R, r_scale, r_scale_stride, rows_per_sample,
+                                 X, W, Y);
   int rc;
   if (phases & TE_X6_PHASE_Z) {   // Z-pass: D[j][t] = sum_k |W|[j][k] |X|[t][k]
-    p.A = wz;
-    p.B = (const unsigned char*)x_planes;
-    p.nks = (int)(in_f / 16);
-    p.a_group_stride = (int64_t)p.nks * kRB;
-    p.b_rb_stride = (int64_t)p.nks * kRB;
-    wm = wm_z;
-    p.rows_w = (int)out_f;
-    p.flags = flag_words;
-    rc = launch_x6_mode<MODE_Z>(wm, p, stream);
+    rc = launch_pass<MODE_Z>(p, wm_z, wz, (const unsigned char*)x_planes, Ss, in_f, out_f, l.flag_region(ws, 0), stream, 1.0f);
     if (rc != TE_OK) return rc;
   }
   if (phases & TE_X6_PHASE_C) {   // C-pass: D[(i, +-)][t] = sum_j W+-[j][i] S[t][j]
-    p.A = wc;
-    p.B = Ss;
-    p.nks = (int)(out_f / 16);
-    p.a_group_stride = (int64_t)p.nks * 2 * kRB;
-    p.b_rb_stride = (int64_t)p.nks * kRB;
-    wm = wm_c;
-    p.rows_w = (int)(2 * in_f);
-    p.flags = flag_words + kFlagBytes / 4;
-    rc = launch_x6_mode<MODE_C>(wm, p, stream);
+    rc = launch_pass<MODE_C>(p, wm_c, wc, Ss, Ss, in_f, out_f, l.flag_region(ws, 1), stream, 1.0f);
     if (rc != TE_OK) return rc;
   }
   TE_RETURN_IF_LAUNCH_FAILED();
@@ -1397,9 +1438,7 @@ extern "C" int te_linear_relprop_x6_general_supported(int64_t T, int64_t in_f, i
 }
 
 extern "C" size_t te_linear_x6_weight_planes_lrp_bytes(int64_t in_f, int64_t out_f) {
-  if (!te_linear_relprop_x6_general_supported(1, in_f, out_f, TE_VARIANT_LRP)) return 0;
-  // P3 of W+ and W- (rows = out_f, K = in_f), then P3 of W+^T and W-^T (rows = in_f, K = out_f)
-  return 2 * te_align_up(planes_bytes(out_f, in_f), 256) + 2 * te_align_up(planes_bytes(in_f, out_f), 256);
+  return te_linear_relprop_x6_general_supported(1, in_f, out_f, TE_VARIANT_LRP) ? weight_planes_lrp(in_f, out_f).total : 0;
 }
 
 extern "C" int te_linear_x6_prepare_weights_lrp_f32(const float* W, int64_t in_f, int64_t out_f, void* planes,
@@ -1409,23 +1448,19 @@ extern "C" int te_linear_x6_prepare_weights_lrp_f32(const float* W, int64_t in_f
   if (planes_bytes_ < te_linear_x6_weight_planes_lrp_bytes(in_f, out_f) || !te_aligned16(planes)) return TE_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   unsigned char* q = (unsigned char*)planes;
-  const size_t za = te_align_up(planes_bytes(out_f, in_f), 256), ca = te_align_up(planes_bytes(in_f, out_f), 256);
-  const dim3 gz((unsigned)(out_f / 32), (unsigned)te_ceil_div(in_f / 16, 8)), gc((unsigned)(in_f / 32), (unsigned)te_ceil_div(out_f / 16, 8));
+  const X6WeightPlanesLrp wl = weight_planes_lrp(in_f, out_f);
+  const dim3 gz = producer_grid(out_f, in_f), gc = producer_grid(in_f, out_f);
   split_kernel<OP_POS, false><<<gz, dim3(256), 0, stream>>>(W, q, out_f, in_f, 3, 0);
-  split_kernel<OP_NEG, false><<<gz, dim3(256), 0, stream>>>(W, q + za, out_f, in_f, 3, 0);
-  split_kernel<OP_POS, true><<<gc, dim3(256), 0, stream>>>(W, q + 2 * za, in_f, out_f, 3, 0);
-  split_kernel<OP_NEG, true><<<gc, dim3(256), 0, stream>>>(W, q + 2 * za + ca, in_f, out_f, 3, 0);
+  split_kernel<OP_NEG, false><<<gz, dim3(256), 0, stream>>>(W, q + wl.wn, out_f, in_f, 3, 0);
+  split_kernel<OP_POS, true><<<gc, dim3(256), 0, stream>>>(W, q + wl.wpT, in_f, out_f, 3, 0);
+  split_kernel<OP_NEG, true><<<gc, dim3(256), 0, stream>>>(W, q + wl.wnT, in_f, out_f, 3, 0);
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;
 }
 
-constexpr int kGeneralPasses = 8;
-
+// workspace: two plane sets of the input side (|X|, or X+ and X-), two of the output side (S / S', or S1 and S2), ...
 extern "C" size_t te_linear_relprop_x6_general_workspace_bytes(int64_t T, int64_t in_f, int64_t out_f, int variant) {
-  if (!te_linear_relprop_x6_general_supported(T, in_f, out_f, variant)) return 0;
-  // two plane sets of the input side (|X|, or X+ and X-), two of the output side (S / S', or S1 and S2)
-  return 2 * te_align_up(planes_bytes(T, in_f), 256) + 2 * te_align_up(planes_bytes(T, out_f), 256) + kPartialBytes +
-         kGeneralPasses * kFlagBytes;
+  return te_linear_relprop_x6_general_supported(T, in_f, out_f, variant) ? general_workspace(T, in_f, out_f).total : 0;
 }
 
 extern "C" int te_linear_relprop_x6_general_f32(const float* R, const float* r_scale, int64_t r_scale_stride,
@@ -1444,113 +1479,53 @@ extern "C" int te_linear_relprop_x6_general_f32(const float* R, const float* r_s
       (w_planes && !te_aligned16(w_planes)) || (w_planes_lrp && !te_aligned16(w_planes_lrp)) ||
       (bias && !te_aligned16(bias)) || (x_abs_planes && !te_aligned16(x_abs_planes)))
     return TE_ERR_UNSUPPORTED;
-  if (r_scale && (rows_per_sample <= 0 || rows_per_sample > 0x7fffffff || T % rows_per_sample)) return TE_ERR_INVALID_ARG;
-  if ((flags & ~(3 | TE_X6_WHOLE_TILES | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID)) != 0) return TE_ERR_INVALID_ARG;
+  if (bad_r_scale(r_scale, rows_per_sample, T)) return TE_ERR_INVALID_ARG;
+  if ((flags & ~kProductFlags) != 0) return TE_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   const float beta = alpha - 1.0f;
-  unsigned char* q = (unsigned char*)ws;
-  unsigned char* Xa = q;                                   // |X|   or X+
-  q += te_align_up(planes_bytes(T, in_f), 256);
-  unsigned char* Xb = q;                                   //        or X-
-  q += te_align_up(planes_bytes(T, in_f), 256);
-  unsigned char* Sa = q;                                   // S / S' or S1
-  q += te_align_up(planes_bytes(T, out_f), 256);
-  unsigned char* Sb = q;                                   //        or S2
-  q += te_align_up(planes_bytes(T, out_f), 256);
-  float* partial = (float*)q;
-  q += kPartialBytes;
-  unsigned* flag_words = (unsigned*)q;
-  q += kGeneralPasses * kFlagBytes;
-  zero_words_kernel<<<dim3(kGeneralPasses * kFlagBytes / 16 / 256), dim3(256), 0, stream>>>(reinterpret_cast<u32x4*>(flag_words));
+  const X6Workspace l = general_workspace(T, in_f, out_f);
+  unsigned char* Xa = l.x(ws, 0), *Xb = l.x(ws, 1);        // |X|, -      or X+, X-
+  unsigned char* Sa = l.sp(ws, 0), *Sb = l.sp(ws, 1);      // S / S', -   or S1, S2
+  zero_flag_regions(l.flag_region(ws, 0), kGeneralPasses, stream);
 
-  X6Params base{};
-  base.T = T;
-  base.ncb = (int)te_ceil_div(T, 32);
-  base.partial = partial;
-  base.R = R;
-  base.Y = Y;
-  base.bias = bias;
-  base.X = X;
-  base.W = W;
-  base.rs = r_scale;
-  base.rs_stride = r_scale_stride;
-  base.rps = (int)(r_scale ? rows_per_sample : 1);
-  base.out = out;
   // status = NULL: ONE per-call error word for all launches of the rule, in the last flag region -- which no launch uses (at
   // most four passes per half) and which the reset between the two halves of variant lrp leaves alone, so a failure of the
   // first half is not lost
-  base.status = status ? status : flag_words + (size_t)(kGeneralPasses - 1) * (kFlagBytes / 4) + kErrWord;
-  base.drop_handover = (flags & TE_X6_TEST_DROP_HANDOVER) ? 1 : 0;
-  base.small_grid = (flags & TE_X6_TEST_SMALL_GRID) ? 1 : 0;
-  base.prefer_whole = (flags & TE_X6_WHOLE_TILES) ? 1 : 0;
-  const int pin = flags & 3;
-  int pass = 0;
-  // one launch: a Z-like pass (K = in_f, weight-side rows = out_f) or an output-side pass (K = out_f)
-  auto z_like = [&](auto mode_tag, const unsigned char* A, const unsigned char* B, unsigned char* S) -> int {
-    constexpr int MODE = decltype(mode_tag)::value;
-    X6Params p = base;
-    p.in_f = (int)in_f, p.out_f = (int)out_f;
-    p.A = A, p.B = B, p.S = S;
-    p.nks = (int)(in_f / 16);
-    p.a_group_stride = (int64_t)p.nks * kRB;
-    p.b_rb_stride = (int64_t)p.nks * kRB;
-    p.rows_w = (int)out_f;
-    p.flags = flag_words + (size_t)(pass++) * (kFlagBytes / 4);
-    const int wm = choose_geo(pick_wm(in_f, out_f), T, out_f, pin, 256, true);
-    return launch_x6_mode<MODE>(wm, p, stream);
-  };
+  const X6Params p = rule_params(call_params(T, l.acc(ws), bias, out, status ? status : l.flag_region(ws, kGeneralPasses - 1) + kErrWord, flags),
+                                 R, r_scale, r_scale_stride, rows_per_sample, X, W, Y);
+  const int pin = flags & kTileMask;
+  const int wm_z = choose_geo(pick_wm(in_f, out_f), T, out_f, pin, 256, true);
+  int pass = 0;          // every launch takes the next flag region
   int rc;
   if (!lrp) {
     const unsigned char* wz = (const unsigned char*)w_planes;
-    const unsigned char* wc = wz + te_align_up(planes_bytes(out_f, in_f), 256);
+    const unsigned char* wc = wz + weight_planes(in_f, out_f).c;
     if (!x_abs_planes) {
       rc = te_linear_x6_split_abs_f32(X, T, in_f, Xa, planes_bytes(T, in_f), stream_);
       if (rc != TE_OK) return rc;
       x_abs_planes = Xa;
     }
-    auto c_like = [&](auto mode_tag, float scale) -> int {
-      constexpr int MODE = decltype(mode_tag)::value;
-      X6Params p = base;
-      p.in_f = (int)in_f, p.out_f = (int)out_f;
-      p.A = wc, p.B = Sa;
-      p.nks = (int)(out_f / 16);
-      p.a_group_stride = (int64_t)p.nks * 2 * kRB;
-      p.b_rb_stride = (int64_t)p.nks * kRB;
-      p.rows_w = (int)(2 * in_f);
-      p.scale = scale;
-      p.flags = flag_words + (size_t)(pass++) * (kFlagBytes / 4);
-      return launch_x6_mode<MODE>(choose_geo(pick_wm(in_f, out_f), T, 2 * in_f, pin), p, stream);
-    };
-    rc = z_like(std::integral_constant<int, MODE_Z>{}, wz, (const unsigned char*)x_abs_planes, Sa);
+    const int wm_c = choose_geo(pick_wm(in_f, out_f), T, 2 * in_f, pin);
+    rc = launch_pass<MODE_Z>(p, wm_z, wz, (const unsigned char*)x_abs_planes, Sa, in_f, out_f, l.flag_region(ws, pass++), stream);
     if (rc != TE_OK) return rc;
-    rc = c_like(std::integral_constant<int, MODE_C>{}, alpha);
+    rc = launch_pass<MODE_C>(p, wm_c, wc, Sa, nullptr, in_f, out_f, l.flag_region(ws, pass++), stream, alpha);
     if (rc != TE_OK) return rc;
     if (beta != 0.0f) {
-      rc = z_like(std::integral_constant<int, MODE_ZI>{}, wz, (const unsigned char*)x_abs_planes, Sa);      // S' over S
+      rc = launch_pass<MODE_ZI>(p, wm_z, wz, (const unsigned char*)x_abs_planes, Sa, in_f, out_f, l.flag_region(ws, pass++), stream);      // S' over S
       if (rc != TE_OK) return rc;
-      rc = c_like(std::integral_constant<int, MODE_CI>{}, -beta);
+      rc = launch_pass<MODE_CI>(p, wm_c, wc, Sa, nullptr, in_f, out_f, l.flag_region(ws, pass++), stream, -beta);
       if (rc != TE_OK) return rc;
     }
   } else {
-    const size_t za = te_align_up(planes_bytes(out_f, in_f), 256), ca = te_align_up(planes_bytes(in_f, out_f), 256);
-    const unsigned char* wq = (const unsigned char*)w_planes_lrp;
-    const unsigned char* Wp = wq, *Wn = wq + za, *WpT = wq + 2 * za, *WnT = wq + 2 * za + ca;
-    const dim3 gx((unsigned)te_ceil_div(T, 32), (unsigned)te_ceil_div(in_f / 16, 8));
-    split_kernel<OP_POS, false><<<gx, dim3(256), 0, stream>>>(X, Xa, T, in_f, 3, 0);
-    split_kernel<OP_NEG, false><<<gx, dim3(256), 0, stream>>>(X, Xb, T, in_f, 3, 0);
+    const X6WeightPlanesLrp wl = weight_planes_lrp(in_f, out_f);
+    const unsigned char* Wp = (const unsigned char*)w_planes_lrp;
+    const unsigned char* Wn = Wp + wl.wn, *WpT = Wp + wl.wpT, *WnT = Wp + wl.wnT;
+    split_kernel<OP_POS, false><<<producer_grid(T, in_f), dim3(256), 0, stream>>>(X, Xa, T, in_f, 3, 0);
+    split_kernel<OP_NEG, false><<<producer_grid(T, in_f), dim3(256), 0, stream>>>(X, Xb, T, in_f, 3, 0);
     // out (+)= scale * (X^sign . (S W^t)):  product [T, out_f] x [out_f, in_f], weight-side rows = in_f
-    auto x_like = [&](const unsigned char* AT, const unsigned char* S, int sign, float scale, int accum) -> int {
-      X6Params p = base;
-      p.in_f = (int)out_f, p.out_f = (int)in_f;           // (plain-product naming: K, M)
-      p.A = AT, p.B = S;
-      p.nks = (int)(out_f / 16);
-      p.a_group_stride = (int64_t)p.nks * kRB;
-      p.b_rb_stride = (int64_t)p.nks * kRB;
-      p.rows_w = (int)in_f;
-      p.scale = scale, p.accum = accum, p.x_sign = sign;
-      p.flags = flag_words + (size_t)(pass++ % kGeneralPasses) * (kFlagBytes / 4);
-      const int wm = choose_geo((in_f % 256 == 0) ? 2 : 1, T, in_f, pin, 192, true);
-      return launch_x6_mode<MODE_X>(wm, p, stream);
+    const int wm_x = choose_geo((in_f % 256 == 0) ? 2 : 1, T, in_f, pin, 192, true);
+    auto x_pass = [&](const unsigned char* AT, const unsigned char* S, int sign, float scale, int accum) -> int {
+      return launch_pass<MODE_X>(p, wm_x, AT, S, nullptr, in_f, out_f, l.flag_region(ws, pass++), stream, scale, accum, sign);
     };
     for (int half = 0; half < (beta != 0.0f ? 2 : 1); ++half) {
       // half 0: f(pw, nw, px, nx) (activator); half 1: f(nw, pw, px, nx) (inhibitor) -- the weight signs cross
@@ -1559,15 +1534,15 @@ extern "C" int te_linear_relprop_x6_general_f32(const float* R, const float* r_s
       if (half) {       // the second half reuses the flag regions of the first: reset them (stream-ordered after their use)
         pass = 0;
         static_assert(kGeneralPasses >= 5, "four passes per half + the region of the per-call error word");
-        zero_words_kernel<<<dim3(4 * kFlagBytes / 16 / 256), dim3(256), 0, stream>>>(reinterpret_cast<u32x4*>(flag_words));
+        zero_flag_regions(l.flag_region(ws, 0), 4, stream);
       }
-      rc = z_like(std::integral_constant<int, MODE_Z1>{}, w1, Xa, Sa);
+      rc = launch_pass<MODE_Z1>(p, wm_z, w1, Xa, Sa, in_f, out_f, l.flag_region(ws, pass++), stream);
       if (rc != TE_OK) return rc;
-      rc = z_like(std::integral_constant<int, MODE_Z1>{}, w2, Xb, Sb);
+      rc = launch_pass<MODE_Z1>(p, wm_z, w2, Xb, Sb, in_f, out_f, l.flag_region(ws, pass++), stream);
       if (rc != TE_OK) return rc;
-      rc = x_like(w1T, Sa, +1, sc, half);
+      rc = x_pass(w1T, Sa, +1, sc, half);
       if (rc != TE_OK) return rc;
-      rc = x_like(w2T, Sb, -1, sc, 1);
+      rc = x_pass(w2T, Sb, -1, sc, 1);
       if (rc != TE_OK) return rc;
     }
   }
@@ -1579,17 +1554,16 @@ extern "C" int te_linear_relprop_x6_general_f32(const float* R, const float* r_s
 // published its accumulators): the result of that call is invalid.  Synchronises the stream.
 extern "C" int te_linear_relprop_x6_check(const void* ws, int64_t T, int64_t in_f, int64_t out_f, te_stream_t stream_) {
   if (!ws || !te_linear_relprop_x6_supported(T, in_f, out_f)) return TE_ERR_INVALID_ARG;
-  const unsigned char* q = (const unsigned char*)ws + te_align_up(planes_bytes(T, in_f), 256) +
-                           te_align_up(planes_bytes(T, out_f), 256) + kPartialBytes;
-  unsigned host[2][1024];      // the 512 flags + the error word of each pass
+  const X6Workspace l = rule_workspace(T, in_f, out_f);
+  unsigned host[kRulePasses][kUsedFlagWords];      // the 512 flags + the error word of each pass
   hipError_t e = hipSuccess;
-  for (int pass = 0; pass < 2 && e == hipSuccess; ++pass)
-    e = hipMemcpyAsync(host[pass], q + pass * kFlagBytes, sizeof(host[pass]), hipMemcpyDeviceToHost, (hipStream_t)stream_);
+  for (int pass = 0; pass < kRulePasses && e == hipSuccess; ++pass)
+    e = hipMemcpyAsync(host[pass], l.flag_region(ws, pass), sizeof(host[pass]), hipMemcpyDeviceToHost, (hipStream_t)stream_);
   if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream_);
   if (e != hipSuccess) return (int)e;
   // any non-zero word after a completed call is an error (a flag nobody consumed, or the error word)
-  for (int pass = 0; pass < 2; ++pass)
-    for (unsigned i = 0; i < 1024; ++i)
+  for (int pass = 0; pass < kRulePasses; ++pass)
+    for (int i = 0; i < kUsedFlagWords; ++i)
       if (host[pass][i]) return 1;
   return 0;
 }
