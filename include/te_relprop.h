@@ -618,6 +618,55 @@ int te_perturb_f32(const float* vis, const float* data, float* out, int64_t B, i
                    const int64_t* ks, int64_t n_steps, const float* mean, const float* std_, void* ws,
                    size_t ws_bytes, te_stream_t stream);
 
+/* ---- deletion / insertion curves (RISE: Petsiuk et al., BMVC 2018, CausalMetric) ----------------------------------
+ * THE REFERENCE TREE HAS NO SUCH PROTOCOL: what follows is this project's definition, restated in torch by curves.py.
+ * Inputs: data [B,C,H,W] fp32 in [0,1]; vis [B,HW] fp32 relevance; target [B] int64; mean[c], std[c] HOST arrays [C] (NULL =
+ * 0 / 1), C <= TE_PERTURB_MAX_CHANNELS.  z = (data - mean[c]) / std[c] is the normalised image (the fp32 expression of
+ * te_perturb_f32).  No entry synchronises, reads back or issues a memset node: a HIP graph captures every call.
+ *
+ * Order.  rank [B,n] int32: rank[b,p] = the position of pixel p when vis[b] is sorted by DESCENDING value, equal values in
+ *   ASCENDING pixel index; the comparison is te_perturb_f32's (-0 == +0, a positive NaN is largest, a negative NaN
+ *   smallest); rank 0 is the most relevant pixel.  torch.sort(vis, 1, descending=True, stable=True), scattered back.
+ *   n <= 2^20, B <= 65535; integers only.  One workgroup per sample: four stable 8-bit passes over ~key << 32 | index,
+ *   ping-pong in the workspace (8-byte aligned).
+ * Steps.  step >= 1 pixels per step, S = ceil(HW / step); image i (0 <= i <= S) has the k_i = min(i step, HW) top-ranked
+ *   pixels switched: S + 1 images per sample and curve.
+ * Substrate sub [B,C,HW] in normalised space: a device tensor (te_blur_normalised_f32 gives RISE's blur) or, when
+ *   substrate == NULL, the constant fill[c] (HOST array [C], already normalised: 0 = the mean colour, (0 - mean[c]) / std[c]
+ *   = black).
+ * Images.  deletion (insertion == 0): x_i[b,c,p] = rank[b,p] < k_i ? sub : z;  insertion (== 1): rank[b,p] < k_i ? z : sub.
+ *   te_curve_inputs_* writes the images s0 .. s0 + n_s - 1 to out [n_s,B,C,HW], fp32 or bf16 (the fp32 value rounded once,
+ *   to nearest even).  HW <= 2^20.
+ * Blur.  taps: HOST array of klen fp32 values (curves.gaussian_taps: RISE's gkern computed in fp64), klen odd,
+ *   <= TE_BLUR_MAX_TAPS; r = klen / 2.  out[y,x] = sum_i t_i sum_j t_j z[y+i-r, x+j-r], out-of-image terms 0 (zero padding in
+ *   normalised space, conv2d(..., padding=klen//2)).  fp32: the horizontal pass first, then the vertical one, taps in index
+ *   order from a zero accumulator, one FMA per tap, out-of-image terms included as zeros: the bits of a pixel do not depend
+ *   on tiling, batch or grid.  H W <= 2^20.
+ * Scores.  logits [n_s B, K] fp32 or bf16, row (s - s0) B + b; prob fp64 [S+1,B] (the base of the table: the call writes rows
+ *   s0 .. s0 + n_s - 1): prob[i,b] = softmax(logits_i[b])[target[b]] in fp64, max-subtracted, summed in a fixed order; NaN for
+ *   a target outside [0, K).
+ * AUC.  auc[b] = (sum_i prob[i,b] - prob[0,b] / 2 - prob[S,b] / 2) / S, S = S1 - 1 >= 1, summed in step order in fp64.
+ * Refused on the host before any HIP call: null pointers (substrate AND fill NULL), sizes <= 0, klen even or < 1, step < 1,
+ *   s0 < 0, n_s < 1, s0 + n_s > S + 1, insertion not 0 / 1, S1 < 2 TE_ERR_INVALID_ARG; klen > TE_BLUR_MAX_TAPS, n or HW > 2^20,
+ *   B > 65535, C > TE_PERTURB_MAX_CHANNELS TE_ERR_UNSUPPORTED; a workspace smaller than te_pixel_rank_workspace_bytes
+ *   TE_ERR_WORKSPACE (the query gives 0 for sizes the entry point refuses). */
+#define TE_BLUR_MAX_TAPS 63
+int te_blur_normalised_f32(const float* data, float* out, int64_t B, int64_t C, int64_t H, int64_t W, const float* taps,
+                           int64_t klen, const float* mean, const float* std_, te_stream_t stream);
+size_t te_pixel_rank_workspace_bytes(int64_t B, int64_t n);
+int te_pixel_rank_f32(const float* vis, int32_t* rank, int64_t B, int64_t n, void* ws, size_t ws_bytes, te_stream_t stream);
+int te_curve_inputs_f32(const float* data, const float* substrate, const float* fill, const int32_t* rank, float* out,
+                        int64_t B, int64_t C, int64_t HW, int64_t step, int64_t s0, int64_t n_s, int insertion,
+                        const float* mean, const float* std_, te_stream_t stream);
+int te_curve_inputs_bf16(const float* data, const float* substrate, const float* fill, const int32_t* rank, te_bf16_t* out,
+                         int64_t B, int64_t C, int64_t HW, int64_t step, int64_t s0, int64_t n_s, int insertion,
+                         const float* mean, const float* std_, te_stream_t stream);
+int te_curve_scores_f32(const float* logits, const int64_t* target, double* prob, int64_t B, int64_t K, int64_t s0,
+                        int64_t n_s, te_stream_t stream);
+int te_curve_scores_bf16(const te_bf16_t* logits, const int64_t* target, double* prob, int64_t B, int64_t K, int64_t s0,
+                         int64_t n_s, te_stream_t stream);
+int te_curve_auc_f64(const double* prob, double* auc, int64_t S1, int64_t B, te_stream_t stream);
+
 /* ---- bf16 operands (a bf16 ViT / DeiT or BERT model: model.to(torch.bfloat16)) ----------------------------
  * The rules of variant "ours", alpha = 1, evaluated in fp32 on the model's own bf16 tensors (te_bf16_t, read exactly:
  * bf16 -> fp32 is exact).  Relevance operands and outputs, safe_divide, per-sample sums and factors are fp32 as in the

@@ -15,6 +15,7 @@ directory name carries a hyphen).  Layout:
   sweep.py, perturbation.py, segmentation.py   the evaluation protocols around the maps
   rationale.py                                 the rationale test on BERT (ERASER: token F1 at top-k, AUPRC, AOPC)
   sanity.py                                    map similarity (Pearson, Spearman, SSIM), cascading randomisation, class sensitivity
+  curves.py                                    deletion / insertion curves (RISE): blur, pixel ranks, step images, class probability, AUC
   tuning/                           PyTorch TunableOp selection of the stock fp32 GEMMs of forward + backward
 """
 from . import _lib, ops, rules, rules_lrp  # noqa: F401

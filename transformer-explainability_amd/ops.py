@@ -1557,6 +1557,156 @@ def perturb(vis: Tensor, data: Tensor, ks: Sequence[int], mean: Optional[Sequenc
     return out
 
 
+# ---------------------------------------------------------------------------------------- deletion / insertion curves (curves.py)
+def _curve_tensor(what: str, name: str, t, dtypes) -> Tensor:
+    """A check that needs no device: raises TeError before any HIP call."""
+    if not torch.is_tensor(t):
+        raise _lib.TeError(f"{what}: {name} must be a tensor")
+    if t.dtype not in dtypes:
+        raise _lib.TeError(f"{what} takes {' or '.join(str(d) for d in dtypes)} for {name}, got {t.dtype}")
+    if not t.is_cuda:
+        raise _lib.TeError(f"{what} needs tensors on the MI355X (got a CPU tensor for {name}); there is no CPU fallback here -- "
+                           f"curves.py has the torch restatement")
+    return t
+
+
+def _floats(values, C: int, what: str, name: str):
+    import ctypes
+    if values is None:
+        return None
+    values = [float(v) for v in values]
+    if len(values) != C:
+        raise _lib.TeError(f"{what}: {name} has {len(values)} values for {C} channels")
+    return (ctypes.c_float * C)(*values)
+
+
+def gaussian_blur(data: Tensor, klen: int = 11, nsig: float = 5.0, mean: Optional[Sequence[float]] = None,
+                  std: Optional[Sequence[float]] = None) -> Tensor:
+    """RISE's blurred image in normalised space: data [B,C,H,W] fp32 -> blur((data - mean[c]) / std[c]) [B,C,H,W] fp32 with the
+    separable klen x klen kernel of ``curves.gaussian_taps(klen, nsig)`` and zero padding (include/te_relprop.h, "deletion /
+    insertion curves"; ``curves.reference_blur`` is the restatement)."""
+    import ctypes
+    from .curves import gaussian_taps
+    data = _curve_tensor("gaussian_blur", "data", data, (torch.float32,))
+    if data.dim() != 4 or data.numel() == 0:
+        raise _lib.TeError(f"gaussian_blur: data must be [B,C,H,W] and not empty, got {tuple(data.shape)}")
+    klen = int(klen)
+    if klen < 1 or klen % 2 == 0 or klen > _lib.TE_BLUR_MAX_TAPS:
+        raise _lib.TeError(f"gaussian_blur: klen must be odd and at most {_lib.TE_BLUR_MAX_TAPS}, got {klen}")
+    B, C, H, W = data.shape
+    # (a view that is dense but starts at an odd element offset stays a view: the kernel has an element-wise form)
+    data = data if data.is_contiguous() else data.contiguous()
+    taps = gaussian_taps(klen, nsig)
+    t_arr = (ctypes.c_float * klen)(*[float(v) for v in taps])
+    m_arr, s_arr = _floats(mean, C, "gaussian_blur", "mean"), _floats(std, C, "gaussian_blur", "std")
+    out = torch.empty((B, C, H, W), dtype=torch.float32, device=data.device)
+    with _on_device(data) as lib:
+        _lib.check(lib.te_blur_normalised_f32(_ptr(data), _ptr(out), B, C, H, W, t_arr, klen, m_arr, s_arr, _stream(data)),
+                   "te_blur_normalised_f32")
+    return out
+
+
+def pixel_ranks(vis: Tensor) -> Tensor:
+    """vis [B,n] (or [B,1,H,W]) fp32 relevance -> rank int32 [B,n]: the position of every pixel when its row is sorted by
+    descending value, equal values in ascending pixel index (rank 0 = the most relevant pixel; ``curves.reference_ranks``).
+    One launch, n <= 2^20."""
+    vis = _curve_tensor("pixel_ranks", "vis", vis, (torch.float32,))
+    if vis.dim() < 2 or vis.numel() == 0:
+        raise _lib.TeError(f"pixel_ranks: vis must be [B,n] and not empty, got {tuple(vis.shape)}")
+    B = vis.shape[0]
+    vis = vis.reshape(B, -1)
+    vis = vis if vis.is_contiguous() else vis.contiguous()
+    n = vis.shape[1]
+    rank = torch.empty((B, n), dtype=torch.int32, device=vis.device)
+    with _on_device(vis) as lib:
+        ws = _ws(lib.te_pixel_rank_workspace_bytes(B, n), vis)
+        _lib.check(lib.te_pixel_rank_f32(_ptr(vis), _ptr(rank), B, n, _ptr(ws), ws.numel(), _stream(vis)), "te_pixel_rank_f32")
+    return rank
+
+
+def curve_inputs(data: Tensor, ranks: Tensor, step: int, s0: int, n_s: int, mode: str, substrate: Optional[Tensor] = None,
+                 fill: Optional[Sequence[float]] = None, mean: Optional[Sequence[float]] = None,
+                 std: Optional[Sequence[float]] = None, out_dtype: torch.dtype = torch.float32) -> Tensor:
+    """The images s0 .. s0 + n_s - 1 of a deletion or insertion curve, one launch: data [B,C,H,W] fp32, ranks int32 [B,HW]
+    (``pixel_ranks``) -> [n_s,B,C,H,W].  Image i has the min(i step, HW) top-ranked pixels switched: mode "deletion" from
+    z = (data - mean[c]) / std[c] to the substrate, "insertion" from the substrate to z.  The substrate is a [B,C,H,W] fp32
+    tensor in normalised space, or (substrate=None) the per-channel constants ``fill``, already normalised.
+    out_dtype=torch.bfloat16: the fp32 values rounded once, to nearest even (``curves.reference_inputs``)."""
+    what = "curve_inputs"
+    if mode not in ("deletion", "insertion"):
+        raise _lib.TeError(f"{what}: mode must be 'deletion' or 'insertion', got {mode!r}")
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.TeError(f"{what}: out_dtype must be float32 or bfloat16, got {out_dtype}")
+    data = _curve_tensor(what, "data", data, (torch.float32,))
+    ranks = _curve_tensor(what, "ranks", ranks, (torch.int32,))
+    if data.dim() != 4 or data.numel() == 0:
+        raise _lib.TeError(f"{what}: data must be [B,C,H,W] and not empty, got {tuple(data.shape)}")
+    B, C, H, W = data.shape
+    HW = H * W
+    if tuple(ranks.shape) != (B, HW):
+        raise _lib.TeError(f"{what}: ranks {tuple(ranks.shape)} does not cover the {H}x{W} pixels of data {tuple(data.shape)}")
+    if (substrate is None) == (fill is None):
+        raise _lib.TeError(f"{what}: give a substrate tensor or the fill constants, one of the two")
+    if substrate is not None:
+        substrate = _curve_tensor(what, "substrate", substrate, (torch.float32,))
+        if substrate.shape != data.shape:
+            raise _lib.TeError(f"{what}: substrate {tuple(substrate.shape)} is not shaped like data {tuple(data.shape)}")
+        substrate = substrate if substrate.is_contiguous() else substrate.contiguous()
+    step, s0, n_s = int(step), int(s0), int(n_s)
+    S = -(-HW // step) if step >= 1 else 0
+    if step < 1 or s0 < 0 or n_s < 1 or s0 + n_s > S + 1:
+        raise _lib.TeError(f"{what}: step {step}, s0 {s0}, n_s {n_s} do not name images of the {S + 1} of {HW} pixels")
+    data = data if data.is_contiguous() else data.contiguous()
+    ranks = ranks if ranks.is_contiguous() else ranks.contiguous()
+    f_arr, m_arr, s_arr = _floats(fill, C, what, "fill"), _floats(mean, C, what, "mean"), _floats(std, C, what, "std")
+    out = torch.empty((n_s, B, C, H, W), dtype=out_dtype, device=data.device)
+    name = "te_curve_inputs_f32" if out_dtype == torch.float32 else "te_curve_inputs_bf16"
+    with _on_device(data) as lib:
+        _lib.check(getattr(lib, name)(_ptr(data), _ptr(substrate), f_arr, _ptr(ranks), _ptr(out), B, C, HW, step, s0, n_s,
+                                      1 if mode == "insertion" else 0, m_arr, s_arr, _stream(data)), name)
+    return out
+
+
+def curve_scores(logits: Tensor, target: Tensor, prob: Tensor, s0: int) -> Tensor:
+    """logits [n_s B, K] (or [n_s,B,K]) fp32 or bf16 of the images s0 .. s0 + n_s - 1, target int64 [B], prob float64 [S+1,B]:
+    writes prob[s0 + i, b] = softmax(logits[i, b])[target[b]], evaluated in fp64, in place (one launch) and returns prob
+    (``curves.reference_scores``)."""
+    what = "curve_scores"
+    logits = _curve_tensor(what, "logits", logits, (torch.float32, torch.bfloat16))
+    target = _curve_tensor(what, "target", target, (torch.int64,))
+    prob = _curve_tensor(what, "prob", prob, (torch.float64,))
+    if prob.dim() != 2 or not prob.is_contiguous() or target.dim() != 1 or target.shape[0] != prob.shape[1]:
+        raise _lib.TeError(f"{what}: prob must be a contiguous [S+1,B] table and target [B], got {tuple(prob.shape)} and "
+                           f"{tuple(target.shape)}")
+    B = prob.shape[1]
+    if logits.dim() not in (2, 3) or logits.numel() == 0 or logits[..., 0].numel() % B != 0:
+        raise _lib.TeError(f"{what}: logits must be [n_s*B,K] or [n_s,B,K] with B = {B}, got {tuple(logits.shape)}")
+    K = logits.shape[-1]
+    n_s = logits[..., 0].numel() // B
+    s0 = int(s0)
+    if s0 < 0 or s0 + n_s > prob.shape[0]:
+        raise _lib.TeError(f"{what}: rows {s0} .. {s0 + n_s - 1} are outside the {prob.shape[0]} rows of prob")
+    logits = logits if logits.is_contiguous() else logits.contiguous()
+    target = target if target.is_contiguous() else target.contiguous()
+    name = "te_curve_scores_f32" if logits.dtype == torch.float32 else "te_curve_scores_bf16"
+    with _on_device(logits) as lib:
+        _lib.check(getattr(lib, name)(_ptr(logits), _ptr(target), _ptr(prob), B, K, s0, n_s, _stream(logits)), name)
+    return prob
+
+
+def curve_auc(prob: Tensor) -> Tensor:
+    """prob float64 [S+1,B] -> auc float64 [B]: the trapezoid over x = i / S (``curves.reference_auc``), one launch."""
+    prob = _curve_tensor("curve_auc", "prob", prob, (torch.float64,))
+    if prob.dim() != 2 or prob.shape[0] < 2 or prob.shape[1] == 0:
+        raise _lib.TeError(f"curve_auc: prob must be [S+1,B] with S >= 1, got {tuple(prob.shape)}")
+    prob = prob if prob.is_contiguous() else prob.contiguous()
+    S1, B = prob.shape
+    auc = torch.empty((B,), dtype=torch.float64, device=prob.device)
+    with _on_device_of_ids(prob) as lib:
+        _lib.check(lib.te_curve_auc_f64(_ptr(prob), _ptr(auc), S1, B, _stream(prob)), "te_curve_auc_f64")
+    return auc
+
+
 # ---------------------------------------------------------------------------------------- bf16 operands
 # A bf16 model's rules: the reference's algorithm evaluated in fp32 on the model's own bf16 tensors (read exactly: bf16 ->
 # fp32 is exact).  Relevance, safe_divide, per-sample sums and the rollout stay fp32; Linear's Z is X+ W+^T + X- W-^T from
