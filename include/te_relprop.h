@@ -667,6 +667,44 @@ int te_curve_scores_bf16(const te_bf16_t* logits, const int64_t* target, double*
                          int64_t n_s, te_stream_t stream);
 int te_curve_auc_f64(const double* prob, double* auc, int64_t S1, int64_t B, te_stream_t stream);
 
+/* ---- localisation test (pointing game: Zhang et al., IJCV 2018; energy-based pointing game / relevance mass accuracy: Wang
+ * et al., CVPRW 2020, Arras et al., Information Fusion 2022; relevance rank accuracy: Arras et al. 2022) --------------------
+ * THE REFERENCE TREE HAS NO SUCH PROTOCOL: what follows is this project's definition, restated in torch by localisation.py.
+ * Scores P (image, class) pairs, each a heat map against a ground-truth region, in ONE launch (one workgroup per pair) with no
+ * host synchronisation, no allocation and no memset node: a HIP graph captures the call.
+ * Inputs, all contiguous: heat fp32 [P,H,W], one map per pair; EXACTLY ONE of labels int64 [B,H,W] (mask mode) and boxes int64
+ *   [P,M,4] = x0, y0, x1, y1 (box mode), the other NULL; image_index int64 [P] or NULL: pair p reads labels[image_index[p]]
+ *   (NULL: labels[p]), so the K pairs of one image share one label map and nothing is materialised as [P,H,W]; target_id
+ *   int64 [P] (mask mode; not read in box mode).
+ * Valid and target pixels.  Mask mode: a pixel is valid iff label >= 0, and a target iff it is valid and label == target_id[p].
+ *   Box mode: every pixel is valid; a pixel (x, y) is a target iff it lies in the union of the pair's M boxes, x0 <= x < x1 and
+ *   y0 <= y < y1 (half-open pixel coordinates: that test clips a box to the image); a row with x1 <= x0 or y1 <= y0 is empty
+ *   (the padding row).
+ * Heat values: a NaN counts as +0.0 everywhere (the clean-up of te_seg_metrics_f32), -0 == +0, the order is te_key's.
+ *   stats [P,5] int64 = n_valid, n_target, argmax, d2_min, topk_hits.
+ *     argmax    = the flat index y W + x of the largest valid pixel, ties to the lowest index; -1 when no pixel is valid.
+ *     d2_min    = the minimum over the target pixels of dy^2 + dx^2 from the argmax pixel, an exact integer: a distance, not a
+ *                 flag -- the caller picks the tolerance afterwards, a pointing-game hit is 0 <= d2_min <= tol^2; -1 when there
+ *                 is no target or no valid pixel.
+ *     topk_hits = the number of target pixels among the n_target highest-ranked valid pixels, ranked by descending value with
+ *                 ties in ascending pixel index (the order of te_pixel_rank_f32 and te_perturb_f32); rank accuracy is
+ *                 topk_hits / n_target.
+ *   energy [P,2] fp64 = e_target, e_valid: the sums of max(h, 0) over the target and over the valid pixels; the quotient and its
+ *                 0/0 rule are the caller's.
+ * Skipped pairs: target_id[p] < 0 (mask mode) or image_index[p] outside [0, B) (either mode; never used as an address) gives
+ *   the rows {0, 0, -1, -1, 0} and {0, 0}; the neighbours of the pair are unaffected.  Box mode without image_index skips nothing.
+ * The integers are exact; the fp64 sums run in an order fixed by the image size alone, without floating-point atomics: every
+ * output of pair p is the same 64-bit pattern alone or in any batch, wherever the workspace lies.
+ * Refused on the host before any HIP call, in this order: null pointers (heat, stats, energy; target_id with labels),
+ *   sizes <= 0, both or neither of labels / boxes, M <= 0 with boxes, a workspace address that is not 8-byte aligned
+ *   TE_ERR_INVALID_ARG; H*W > 2^20, P > 65535 or M > 64
+ *   TE_ERR_UNSUPPORTED; a workspace smaller than te_localisation_workspace_bytes TE_ERR_WORKSPACE (the query gives 0 for sizes
+ *   the entry point refuses).  ws: per pair H*W 4-byte keys and H*W mask bits. */
+size_t te_localisation_workspace_bytes(int64_t P, int64_t H, int64_t W);
+int te_localisation_f32(const float* heat, const int64_t* labels, const int64_t* image_index, const int64_t* target_id,
+                        const int64_t* boxes, int64_t M, int64_t* stats, double* energy, int64_t P, int64_t B, int64_t H,
+                        int64_t W, void* ws, size_t ws_bytes, te_stream_t stream);
+
 /* ---- bf16 operands (a bf16 ViT / DeiT or BERT model: model.to(torch.bfloat16)) ----------------------------
  * The rules of variant "ours", alpha = 1, evaluated in fp32 on the model's own bf16 tensors (te_bf16_t, read exactly:
  * bf16 -> fp32 is exact).  Relevance operands and outputs, safe_divide, per-sample sums and factors are fp32 as in the

@@ -1442,6 +1442,76 @@ def _is_integer(t: Tensor) -> bool:
     return not (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool)
 
 
+# ---------------------------------------------------------------------------------------- localisation test (localisation.py)
+def _localisation_args(heat, labels, target_id, image_index, boxes):
+    """The checks of localisation_metrics that need no device -> (P, B, H, W, M): raises TeError before any HIP call."""
+    given = {"heat": heat, "labels": labels, "target_id": target_id, "image_index": image_index, "boxes": boxes}
+    for name, t in given.items():
+        if t is not None and not torch.is_tensor(t):
+            raise _lib.TeError(f"localisation_metrics: {name} must be a tensor, got {type(t).__name__}")
+    if heat is None or heat.dtype != torch.float32:
+        raise _lib.TeError(f"localisation_metrics takes a float32 heat map, got {None if heat is None else heat.dtype}")
+    if (labels is None) == (boxes is None):
+        raise _lib.TeError("localisation_metrics: give exactly one of labels= (a label map per image) and boxes=")
+    for name in ("labels", "target_id", "image_index", "boxes"):
+        if given[name] is not None and not _is_integer(given[name]):
+            raise _lib.TeError(f"localisation_metrics takes an integer {name}, got {given[name].dtype}")
+    if heat.dim() != 3 or heat.numel() == 0:
+        raise _lib.TeError(f"localisation_metrics: heat must be [P,H,W] and not empty, got {tuple(heat.shape)}")
+    P, H, W = heat.shape
+    B, M = P, 0
+    if labels is not None:
+        if target_id is None:
+            raise _lib.TeError("localisation_metrics: labels= needs target_id= [P], the class of every pair")
+        if labels.dim() != 3 or tuple(labels.shape[1:]) != (H, W) or labels.shape[0] == 0:
+            raise _lib.TeError(f"localisation_metrics: labels must be [B,{H},{W}] like the heat maps, got {tuple(labels.shape)}")
+        B = labels.shape[0]
+        if image_index is None and B != P:
+            raise _lib.TeError(f"localisation_metrics: {B} label maps for {P} pairs need image_index= [P]")
+    else:
+        if boxes.dim() != 3 or boxes.shape[0] != P or boxes.shape[1] == 0 or boxes.shape[2] != 4:
+            raise _lib.TeError(f"localisation_metrics: boxes must be [{P},M,4] = x0, y0, x1, y1 with M >= 1, got "
+                               f"{tuple(boxes.shape)}")
+        M = boxes.shape[1]
+    for name in ("target_id", "image_index"):
+        if given[name] is not None and tuple(given[name].shape) != (P,):
+            raise _lib.TeError(f"localisation_metrics: {name} must be [{P}], one entry per pair, got {tuple(given[name].shape)}")
+    if not all(t.is_cuda for t in given.values() if t is not None):
+        raise _lib.TeError("localisation_metrics needs tensors on the MI355X (got a CPU tensor); there is no CPU fallback "
+                           "here -- localisation.reference_metrics is the torch restatement")
+    return P, B, H, W, M
+
+
+def localisation_metrics_packed(heat: Tensor, labels: Optional[Tensor] = None, target_id: Optional[Tensor] = None,
+                                image_index: Optional[Tensor] = None, boxes: Optional[Tensor] = None):
+    """``localisation_metrics`` and the flat int64 buffer its results are views of -- stats [P*5], then the bits of energy
+    [P*2]: one device-to-host copy of it brings both over."""
+    P, B, H, W, M = _localisation_args(heat, labels, target_id, image_index, boxes)
+    heat = _c(heat)
+    labels, target_id, image_index, boxes = (None if t is None else t.to(device=heat.device, dtype=torch.int64).contiguous()
+                                             for t in (labels, target_id, image_index, boxes))
+    flat = torch.empty((P * 7,), dtype=torch.int64, device=heat.device)
+    stats = flat[:5 * P].view(P, 5)
+    energy = flat[5 * P:].view(torch.float64).view(P, 2)
+    with _on_device(heat) as lib:
+        ws = _ws(lib.te_localisation_workspace_bytes(P, H, W), heat)
+        _lib.check(lib.te_localisation_f32(_ptr(heat), _ptr(labels), _ptr(image_index), _ptr(target_id), _ptr(boxes), M,
+                                           _ptr(stats), _ptr(energy), P, B, H, W, _ptr(ws), ws.numel(), _stream(heat)),
+                   "te_localisation_f32")
+    return stats, energy, flat
+
+
+def localisation_metrics(heat: Tensor, labels: Optional[Tensor] = None, target_id: Optional[Tensor] = None,
+                         image_index: Optional[Tensor] = None, boxes: Optional[Tensor] = None):
+    """The localisation test per (image, class) pair, one launch, no synchronisation: heat fp32 [P,H,W] against either
+    ``labels`` [B,H,W] of an integer dtype (< 0 = ignore; a pixel is a target iff label == ``target_id[p]``; pair p reads the
+    label map ``image_index[p]``, p itself when image_index is None) or ``boxes`` [P,M,4] = x0, y0, x1, y1 (half-open; an empty
+    row pads) -> (stats int64 [P,5] = n_valid, n_target, argmax, d2_min, topk_hits; energy float64 [P,2] = e_target, e_valid),
+    as localisation.reference_metrics defines them (include/te_relprop.h, "localisation test").  A pair with target_id < 0
+    or an image_index outside [0, B) is skipped: rows {0, 0, -1, -1, 0} and {0, 0}.  H*W <= 2^20, P <= 65535, M <= 64."""
+    return localisation_metrics_packed(heat, labels, target_id, image_index, boxes)[:2]
+
+
 class _on_device_of_ids(_on_device):
     """``_on_device`` for a call whose tensors are all integers (te_token_erase): no dtype rule to apply."""
 
