@@ -705,6 +705,50 @@ int te_localisation_f32(const float* heat, const int64_t* labels, const int64_t*
                         const int64_t* boxes, int64_t M, int64_t* stats, double* energy, int64_t P, int64_t B, int64_t H,
                         int64_t W, void* ws, size_t ws_bytes, te_stream_t stream);
 
+/* ---- robustness and complexity (max- / average-sensitivity: Yeh et al., NeurIPS 2019; local Lipschitz estimate: Alvarez-Melis
+ * & Jaakkola, 2018; Gini sparseness: Chalasani et al., ICML 2020; entropy: Bhatt et al., IJCAI 2020; effective complexity:
+ * Nguyen & Martinez, 2020) -------------------------------------------------------------------------------------------------
+ * THE REFERENCE TREE HAS NO SUCH PROTOCOL: what follows is this project's definition, restated in numpy / torch by
+ * robustness.py.  No entry synchronises, reads back or issues a memset node: a HIP graph captures every call.  There are no
+ * floating-point atomics: every output of sample b is the same bit pattern alone or in any batch.
+ *
+ * Noise.  x [B,n] fp32: the model's input, already normalised, n = C H W.  out [B,n_d,n], fp32 or bf16: row b n_d + j is draw
+ *   d = d0 + j of the sample whose global id is id0 + b (64-bit, wrapping).  Element e takes word e & 3 of Philox4x32-10
+ *   (Salmon et al., SC 2011: multipliers 0xD2511F53, 0xCD9E8D57, Weyl increments 0x9E3779B9, 0xBB67AE85, ten rounds) with the
+ *   counter (e >> 2, d, low32(id), high32(id)) and the key (low32(seed), high32(seed)); the 64 bits of seed are read as
+ *   unsigned.  From the word w, in this order: u = float(w >> 8) * 2^-24 (exact); s = 2 u - 1 (exact); delta = s * radius (one
+ *   fp32 rounding); y = x + delta (one fp32 rounding) -- never an FMA: torch's x + s * radius gives the same bits.  _bf16
+ *   rounds y once more, to nearest even.  radius == 0 gives exact copies.  The draws are uniform in the L-infinity ball of
+ *   that radius (s in [-1, 1 - 2^-23]).  A sample's copies depend on (element, draw, id, seed) alone: the same bits alone, in
+ *   any batch and in any chunking (d0, n_d) of the draws.  16-byte accesses where n % 4 == 0 (bf16: n % 8 == 0) and x, out
+ *   are 16-byte aligned; an element-wise form otherwise.
+ * Distance.  a [B,n] fp32, b [B,D,n] fp32 or bf16, sums [B,D,3] fp64 = sum_e (b - a)^2, sum_e a^2, sum_e b^2, every term
+ *   formed in fp64 from the exact upcasts.  Thread t of 256 takes the groups of four elements t, t + 256, ... in order, then
+ *   the 64 lanes of a wave and the four waves meet in a fixed order: the order depends on n alone.
+ * Complexity.  maps [B,n] fp32; v = |maps[b]|, S = sum v (fp64).  out [B,2] fp64 = gini, entropy; counts [B,2] int64.
+ *     gini    = sum_k (2k - n - 1) v_(k) / (n S) over v sorted ascending, k = 1 .. n (ties do not change it; every product is
+ *               exact in fp64); 0 for n == 1.
+ *     entropy = 0 - sum p ln p, p = v / S in fp64, 0 ln 0 = 0 (natural logarithm).
+ *     counts  = the number of v > eps max v, compared in fp64 as (double)v > eps * (double)max v (the effective complexity at
+ *               the relative threshold eps), and the number of v > 0.
+ *   S == 0 gives NaN, NaN, 0, 0.  A NaN anywhere in the row gives a NaN row and zero counts; its neighbours are unaffected.
+ *   One workgroup per sample; the order is that of te_key on te_key(v) << 32 | index, four stable 8-bit passes ping-pong in
+ *   the workspace (8-byte aligned), as te_map_similarity_f32.  n <= 2^20, B <= 65535.
+ * Refused on the host before any HIP call: null pointers, sizes <= 0, radius or eps negative or not finite, d0 < 0,
+ *   d0 + n_d > 2^32 TE_ERR_INVALID_ARG; B > 65535, n > 2^20 (complexity), n > 2^31 - 1 (noise, distance), D > 2^31 - 1
+ *   TE_ERR_UNSUPPORTED; a workspace smaller than te_map_complexity_workspace_bytes TE_ERR_WORKSPACE (the query gives 0 for
+ *   sizes the entry point refuses). */
+int te_noise_inputs_f32(const float* x, float* out, int64_t B, int64_t n, int64_t d0, int64_t n_d, float radius, int64_t seed,
+                        int64_t id0, te_stream_t stream);
+int te_noise_inputs_bf16(const float* x, te_bf16_t* out, int64_t B, int64_t n, int64_t d0, int64_t n_d, float radius,
+                         int64_t seed, int64_t id0, te_stream_t stream);
+int te_map_distance_f32(const float* a, const float* b, double* sums, int64_t B, int64_t D, int64_t n, te_stream_t stream);
+int te_map_distance_bf16(const float* a, const te_bf16_t* b, double* sums, int64_t B, int64_t D, int64_t n,
+                         te_stream_t stream);
+size_t te_map_complexity_workspace_bytes(int64_t B, int64_t n);
+int te_map_complexity_f32(const float* maps, double* out, int64_t* counts, int64_t B, int64_t n, double eps, void* ws,
+                          size_t ws_bytes, te_stream_t stream);
+
 /* ---- bf16 operands (a bf16 ViT / DeiT or BERT model: model.to(torch.bfloat16)) ----------------------------
  * The rules of variant "ours", alpha = 1, evaluated in fp32 on the model's own bf16 tensors (te_bf16_t, read exactly:
  * bf16 -> fp32 is exact).  Relevance operands and outputs, safe_divide, per-sample sums and factors are fp32 as in the

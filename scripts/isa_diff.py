@@ -12,7 +12,8 @@ entry of build.SOURCES (or only the files named) both trees' file is compiled wi
     such as `Strided` out of an anonymous namespace renames the kernel and changes nothing else.
 
 One line per file: lines, sha256 of the old and of the new normalised listing, `same` / `DIFFERENT` (`new`: a file OLD_TREE
-does not have).  Exit status 1 on any difference (the normalised listings of a differing file are kept in --keep DIR for `diff`).  Flags and the file list are the
+does not have).  A differing file gets a second line that says how it differs (`classify`): whether the line counts agree, how
+many lines only have the source operands of a commutative integer opcode in another order, and how many differ otherwise.  Exit status 1 on any difference (the normalised listings of a differing file are kept in --keep DIR for `diff`).  Flags and the file list are the
 flags and the list of NEW_TREE's build.py.
 """
 import argparse
@@ -40,6 +41,31 @@ def normalise(text):
     text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", text)
     names = {}
     return re.sub(r"_Z[A-Za-z0-9_]+", lambda m: names.setdefault(m.group(0), "SYM%d" % len(names)), text)
+
+
+COMMUTATIVE = ("v_add_u32", "v_add3_u32", "v_add_co_u32", "v_mul_lo_u32", "v_mul_hi_u32", "v_and_b32", "v_or_b32", "v_xor_b32",
+               "s_add_u32", "s_add_i32", "s_and_b32", "s_and_b64", "s_or_b32", "s_or_b64", "s_xor_b32", "s_xor_b64")
+
+
+def classify(old, new):
+    """How two normalised listings differ, line by line: None if their line counts differ; else ({opcode: lines that have the
+    same opcode, the same destination and the same source operands in another order (commutative integer opcodes only)},
+    the number of lines that differ in any other way)."""
+    a, b = old.split("\n"), new.split("\n")
+    if len(a) != len(b):
+        return None
+    swapped, other = {}, 0
+    for x, y in zip(a, b):
+        if x == y:
+            continue
+        px, py = x.split(None, 1), y.split(None, 1)
+        if len(px) == 2 and len(py) == 2 and px[0] == py[0] and px[0].split("_e32")[0].split("_e64")[0] in COMMUTATIVE:
+            ox, oy = ([s.strip() for s in p[1].split(",")] for p in (px, py))
+            if ox[0] == oy[0] and sorted(ox[1:]) == sorted(oy[1:]):
+                swapped[px[0]] = swapped.get(px[0], 0) + 1
+                continue
+        other += 1
+    return swapped, other
 
 
 def listing(build, tree, src, out):
@@ -84,6 +110,12 @@ def main():
             same = old == new
             different += not same
             print("%-22s %8d  %-16s %-16s %s" % (s, new.count("\n"), h_old, h_new, "same" if same else "DIFFERENT"), flush=True)
+            if not same:
+                kind = classify(old, new)
+                print("    " + ("the listings have different numbers of lines" if kind is None else
+                                "same number of lines; lines with the same opcode and destination and the source operands of a "
+                                "commutative integer opcode in another order: %s; lines that differ in any other way: %d"
+                                % (dict(sorted(kind[0].items())) or "none", kind[1])), flush=True)
             if not same and a.keep:
                 os.makedirs(a.keep, exist_ok=True)
                 for side, t in (("old", old), ("new", new)):

@@ -17,6 +17,7 @@ directory name carries a hyphen).  Layout:
   sanity.py                                    map similarity (Pearson, Spearman, SSIM), cascading randomisation, class sensitivity
   curves.py                                    deletion / insertion curves (RISE): blur, pixel ranks, step images, class probability, AUC
   localisation.py                              pointing game, energy-based pointing game, relevance rank accuracy per (image, class) pair
+  robustness.py                                max- / average-sensitivity, local Lipschitz estimate (Philox noise), Gini, entropy, effective complexity
   tuning/                           PyTorch TunableOp selection of the stock fp32 GEMMs of forward + backward
 """
 from . import _lib, ops, rules, rules_lrp  # noqa: F401

@@ -127,7 +127,7 @@ __device__ __forceinline__ double te_wave_sum(double v) {
   return v;
 }
 
-// The radix sorts (te_segmetrics.hip, te_mapsim.hip): the lanes of the wave that hold the same 8-bit digit as this lane, among the `live` ones
+// The radix sorts (te_segmetrics.hip, te_curves.hip, te_block_sort_passes below): the lanes of the wave that hold the same 8-bit digit as this lane, among the `live` ones
 __device__ __forceinline__ uint64_t match_digit(uint32_t digit, bool live) {
   uint64_t m = __ballot(live);
 #pragma unroll
@@ -154,6 +154,65 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* w
   for (int w = 0; w < wave; ++w) before += wtot[w];
   __syncthreads();
   return before + incl - v;
+}
+
+// The four stable 8-bit passes of the per-sample LSD radix sort (te_mapsim.hip, te_robust.hip), one workgroup of 1024 threads
+// = 16 waves: n elements `key << 32 | index` ascending by key, equal keys in index order.  The caller has built src[0 .. n)
+// and counted, in cnt[0][digit * 16 + j / S], the elements of every lowest digit in every wave segment of S = ceil(n / 1024)
+// * 64 positions, cnt[1] zeroed, a barrier behind it.  A pass turns the (digit, wave) counts into the start of each wave's
+// elements of each digit, ranks the lanes of a digit by ballots and counts the next digit at the destination; src and dst
+// swap after every pass, so on return src is the caller's first buffer again and holds the sorted elements, dst is idle.
+// tid, lane, wave and below = (1 << lane) - 1 are the caller's own values (it needs them before and after the passes).
+constexpr int kTeSortThreads = 1024;
+constexpr int kTeSortWaves = kTeSortThreads / TE_WAVE;
+constexpr int kTeSortDigits = 256;
+__device__ __forceinline__ void te_block_sort_passes(uint64_t*& src, uint64_t*& dst, uint32_t n, uint32_t S,
+                                                     uint32_t (*cnt)[kTeSortDigits * kTeSortWaves], uint32_t* wtot,
+                                                     int tid, int lane, int wave, uint64_t below) {
+  for (int pass = 0; pass < 4; ++pass) {
+    volatile uint32_t* cur = cnt[pass & 1];
+    uint32_t* nxt = cnt[(pass + 1) & 1];
+    const int shift = 32 + 8 * pass;
+    {                                              // (digit, wave) counts -> start of each wave's elements of each digit
+      uint32_t v[4], sum = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        v[k] = cur[4 * tid + k];
+        sum += v[k];
+      }
+      uint32_t off = block_exclusive_scan(sum, wtot);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        cur[4 * tid + k] = off;
+        off += v[k];
+      }
+      for (int k = 0; k < 4; ++k) nxt[4 * tid + k] = 0;
+    }
+    __syncthreads();
+    const uint32_t seg0 = (uint32_t)wave * S, seg1 = min(seg0 + S, n);
+    uint32_t idx = seg0 + lane;
+    uint64_t e_next = idx < seg1 ? src[idx] : 0ull;
+    for (uint32_t base = seg0; base < seg1; base += TE_WAVE) {
+      const uint64_t e = e_next;
+      const bool live = idx < seg1;
+      idx += TE_WAVE;
+      e_next = idx < seg1 ? src[idx] : 0ull;
+      const uint32_t digit = (uint32_t)(e >> shift) & 0xffu;
+      const uint64_t m = match_digit(digit, live);
+      const uint32_t rank = (uint32_t)__popcll(m & below), same = (uint32_t)__popcll(m);
+      if (live) {
+        const uint32_t at = cur[digit * kTeSortWaves + wave];
+        const uint32_t pos = at + rank;
+        dst[pos] = e;
+        if (rank == same - 1) cur[digit * kTeSortWaves + wave] = at + same;      // after every lane of the digit has read it
+        if (pass < 3) atomicAdd(&nxt[((uint32_t)(e >> (shift + 8)) & 0xffu) * kTeSortWaves + pos / S], 1u);
+      }
+    }
+    __syncthreads();
+    uint64_t* t = src;
+    src = dst;
+    dst = t;
+  }
 }
 
 // Block-wide sum of up to 3 doubles; result valid in thread 0.  `smem` holds 3*(blockDim/64) doubles.

@@ -56,50 +56,7 @@ __global__ __launch_bounds__(kThreads) void mapsim_rank_kernel(const float* __re
   __syncthreads();
 
   // ---- sort (ascending, stable: equal keys stay in index order)
-  for (int pass = 0; pass < 4; ++pass) {
-    volatile uint32_t* cur = cnt[pass & 1];
-    uint32_t* nxt = cnt[(pass + 1) & 1];
-    const int shift = 32 + 8 * pass;
-    {                                              // (digit, wave) counts -> start of each wave's elements of each digit
-      uint32_t v[4], sum = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        v[k] = cur[4 * tid + k];
-        sum += v[k];
-      }
-      uint32_t off = block_exclusive_scan(sum, wtot);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        cur[4 * tid + k] = off;
-        off += v[k];
-      }
-      for (int k = 0; k < 4; ++k) nxt[4 * tid + k] = 0;
-    }
-    __syncthreads();
-    const uint32_t seg0 = (uint32_t)wave * S, seg1 = min(seg0 + S, n);
-    uint32_t idx = seg0 + lane;
-    uint64_t e_next = idx < seg1 ? src[idx] : 0ull;
-    for (uint32_t base = seg0; base < seg1; base += TE_WAVE) {
-      const uint64_t e = e_next;
-      const bool live = idx < seg1;
-      idx += TE_WAVE;
-      e_next = idx < seg1 ? src[idx] : 0ull;
-      const uint32_t digit = (uint32_t)(e >> shift) & 0xffu;
-      const uint64_t m = match_digit(digit, live);
-      const uint32_t rank = (uint32_t)__popcll(m & below), same = (uint32_t)__popcll(m);
-      if (live) {
-        const uint32_t at = cur[digit * kWaves + wave];
-        const uint32_t pos = at + rank;
-        dst[pos] = e;
-        if (rank == same - 1) cur[digit * kWaves + wave] = at + same;      // after every lane of the digit has read it
-        if (pass < 3) atomicAdd(&nxt[((uint32_t)(e >> (shift + 8)) & 0xffu) * kWaves + pos / S], 1u);
-      }
-    }
-    __syncthreads();
-    uint64_t* t = src;
-    src = dst;
-    dst = t;
-  }
+  te_block_sort_passes(src, dst, n, S, cnt, wtot, tid, lane, wave, below);
 
   // ---- runs of equal keys: after four passes src is the job's first buffer again and holds the sorted elements; the second
   // one is idle: its first n words take the sorted positions where a run starts, its last n words the d of every index

@@ -1777,6 +1777,119 @@ def curve_auc(prob: Tensor) -> Tensor:
     return auc
 
 
+# ---------------------------------------------------------------------------------------- robustness and complexity (robustness.py)
+def _robust_tensor(what: str, name: str, t, dtypes) -> Tensor:
+    """A check that needs no device: raises TeError before any HIP call."""
+    if not torch.is_tensor(t):
+        raise _lib.TeError(f"{what}: {name} must be a tensor")
+    if t.dtype not in dtypes:
+        raise _lib.TeError(f"{what} takes {' or '.join(str(d) for d in dtypes)} for {name}, got {t.dtype}")
+    if not t.is_cuda:
+        raise _lib.TeError(f"{what} needs tensors on the MI355X (got a CPU tensor for {name}); there is no CPU fallback here -- "
+                           f"robustness.py has the numpy / torch restatement")
+    return t
+
+
+def _finite_not_negative(what: str, name: str, value) -> float:
+    value = float(value)
+    if not (value >= 0.0) or value == float("inf"):
+        raise _lib.TeError(f"{what}: {name} must be finite and not negative, got {value}")
+    return value
+
+
+def noise_inputs(x: Tensor, n_draws: int, radius: float, seed: int, id0: int = 0, d0: int = 0,
+                 out_dtype: torch.dtype = torch.float32) -> Tensor:
+    """The noisy copies of the sensitivity protocol, one launch: x [B,...] fp32 (the model's normalised input) ->
+    [B,n_draws,...] in ``out_dtype`` (float32, or bfloat16: the fp32 value rounded once more, to nearest even).  Copy j of
+    sample b is draw d0 + j of the sample with the global id id0 + b: x + s * radius in fp32 with s uniform in [-1, 1) from
+    Philox4x32-10 keyed by ``seed`` (include/te_relprop.h, "robustness and complexity"; ``robustness.reference_noise``).
+    The bits of a sample's copies do not depend on the batch or on the chunk (d0, n_draws) they are made in."""
+    what = "noise_inputs"
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.TeError(f"{what}: out_dtype must be float32 or bfloat16, got {out_dtype}")
+    x = _robust_tensor(what, "x", x, (torch.float32,))
+    if x.dim() < 2 or x.numel() == 0:
+        raise _lib.TeError(f"{what}: x must be [B,...] and not empty, got {tuple(x.shape)}")
+    n_draws = int(n_draws)
+    if n_draws < 1:
+        raise _lib.TeError(f"{what}: n_draws must be at least 1, got {n_draws}")
+    # (a view that is dense but starts off a 16-byte boundary stays a view: the kernel has an element-wise form)
+    x = x if x.is_contiguous() else x.contiguous()
+    out = torch.empty((x.shape[0], n_draws) + tuple(x.shape[1:]), dtype=out_dtype, device=x.device)
+    return _noise_inputs_into(x, out, radius, seed, id0, d0)
+
+
+def _noise_inputs_into(x: Tensor, out: Tensor, radius: float, seed: int, id0: int = 0, d0: int = 0) -> Tensor:
+    """The launch of ``noise_inputs``, into out [B,n_draws,...] fp32 or bf16, dense.  Not part of the interface: the tests
+    call it to hand the kernel an output view that starts off a 16-byte boundary."""
+    what = "noise_inputs"
+    x = _robust_tensor(what, "x", x, (torch.float32,))
+    out = _robust_tensor(what, "out", out, (torch.float32, torch.bfloat16))
+    if x.dim() < 2 or out.dim() != x.dim() + 1 or out.shape[0] != x.shape[0] or out.shape[2:] != x.shape[1:] or \
+            out.numel() == 0 or not x.is_contiguous() or not out.is_contiguous():
+        raise _lib.TeError(f"{what}: x must be a dense [B,...] and out a dense [B,n_draws,...], got {tuple(x.shape)} and "
+                           f"{tuple(out.shape)}")
+    radius = _finite_not_negative(what, "radius", radius)
+    B, n_draws = out.shape[0], out.shape[1]
+    d0, seed, id0 = int(d0), int(seed), int(id0)
+    if d0 < 0 or d0 + n_draws > 1 << 32:
+        raise _lib.TeError(f"{what}: draws {d0} .. {d0 + n_draws - 1} are not draws 0 .. 2^32 - 1")
+    if not (-(1 << 63) <= seed < 1 << 64) or not (-(1 << 63) <= id0 < 1 << 64):
+        raise _lib.TeError(f"{what}: seed and id0 are 64-bit integers, got {seed} and {id0}")
+    # (the 64 bits are read as unsigned on the device: the ABI carries them in an int64_t)
+    seed, id0 = (v - (1 << 64) if v >= 1 << 63 else v for v in (seed, id0))
+    name = "te_noise_inputs_f32" if out.dtype == torch.float32 else "te_noise_inputs_bf16"
+    with _on_device(x) as lib:
+        _lib.check(getattr(lib, name)(_ptr(x), _ptr(out), B, x[0].numel(), d0, n_draws, radius, seed, id0, _stream(x)), name)
+    return out
+
+
+def map_distance(a: Tensor, b: Tensor) -> Tensor:
+    """a fp32 [B,...] and b fp32 or bf16 [B,D,...] with as many values per sample -> sums float64 [B,D,3] = sum (b - a)^2,
+    sum a^2, sum b^2, every term in fp64 from the exact upcasts, in an order fixed by the size alone; one launch, no
+    synchronisation (``robustness.reference_distance``).  Serves the map pairs and the input pairs of the sensitivity
+    protocol."""
+    what = "map_distance"
+    a = _robust_tensor(what, "a", a, (torch.float32,))
+    b = _robust_tensor(what, "b", b, (torch.float32, torch.bfloat16))
+    if a.dim() < 2 or b.dim() < 3 or a.numel() == 0 or b.numel() == 0 or a.shape[0] != b.shape[0] or \
+            a[0].numel() != b[0, 0].numel():
+        raise _lib.TeError(f"{what}: a must be [B,n] and b [B,D,n] and not empty, got {tuple(a.shape)} and {tuple(b.shape)}")
+    B, D, n = b.shape[0], b.shape[1], a[0].numel()
+    a = a if a.is_contiguous() else a.contiguous()
+    b = b if b.is_contiguous() else b.contiguous()
+    out = torch.empty((B, D, 3), dtype=torch.float64, device=a.device)
+    name = "te_map_distance_f32" if b.dtype == torch.float32 else "te_map_distance_bf16"
+    with _on_device(a) as lib:
+        _lib.check(getattr(lib, name)(_ptr(a), _ptr(b), _ptr(out), B, D, n, _stream(a)), name)
+    return out
+
+
+def map_complexity(maps: Tensor, eps: float = 1e-5):
+    """maps fp32 [B,...] -> (out float64 [B,2] = Gini sparseness, entropy of v = |maps[b]|; counts int64 [B,2] = the number of
+    v > eps max v, the number of v > 0), one launch, no synchronisation (include/te_relprop.h, "robustness and complexity";
+    ``robustness.reference_complexity``).  A zero map or a NaN anywhere in a sample gives a NaN row and zero counts;
+    n <= 2^20."""
+    what = "map_complexity"
+    maps = _robust_tensor(what, "maps", maps, (torch.float32,))
+    if maps.dim() < 2 or maps.numel() == 0:
+        raise _lib.TeError(f"{what}: maps must be [B,n] and not empty, got {tuple(maps.shape)}")
+    eps = _finite_not_negative(what, "eps", eps)
+    B = maps.shape[0]
+    maps = maps.reshape(B, -1)
+    maps = maps if maps.is_contiguous() else maps.contiguous()
+    n = maps.shape[1]
+    if n > 1 << 20 or B > 65535:
+        raise _lib.TeError(f"{what}: at most 2^20 values per map and 65535 maps, got {tuple(maps.shape)}")
+    out = torch.empty((B, 2), dtype=torch.float64, device=maps.device)
+    counts = torch.empty((B, 2), dtype=torch.int64, device=maps.device)
+    with _on_device(maps) as lib:
+        ws = _ws(lib.te_map_complexity_workspace_bytes(B, n), maps)
+        _lib.check(lib.te_map_complexity_f32(_ptr(maps), _ptr(out), _ptr(counts), B, n, eps, _ptr(ws), ws.numel(),
+                                             _stream(maps)), "te_map_complexity_f32")
+    return out, counts
+
+
 # ---------------------------------------------------------------------------------------- bf16 operands
 # A bf16 model's rules: the reference's algorithm evaluated in fp32 on the model's own bf16 tensors (read exactly: bf16 ->
 # fp32 is exact).  Relevance, safe_divide, per-sample sums and the rollout stay fp32; Linear's Z is X+ W+^T + X- W-^T from
