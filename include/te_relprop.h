@@ -749,6 +749,55 @@ size_t te_map_complexity_workspace_bytes(int64_t B, int64_t n);
 int te_map_complexity_f32(const float* maps, double* out, int64_t* counts, int64_t B, int64_t n, double eps, void* ws,
                           size_t ws_bytes, te_stream_t stream);
 
+/* ---- faithfulness (infidelity: Yeh et al., NeurIPS 2019, captum's `infidelity`; faithfulness correlation: Bhatt et al.,
+ * IJCAI 2020) -- csrc/te_faithful.hip -------------------------------------------------------------------------------------
+ * THE REFERENCE TREE HAS NO SUCH PROTOCOL: what follows is this project's definition, restated in numpy / torch by
+ * faithfulness.py.  Parity with captum or quantus is not claimed.  No entry synchronises, reads back or issues a memset node:
+ * a HIP graph captures every call.  There are no floating-point atomics: every output of sample b is the same bit pattern
+ * alone, in any batch and in any chunking (d0, n_d) of the draws.
+ *
+ * Subsets.  The image [C,H,W] is cut into G = g_h g_w cells of p x p pixels, H = g_h p, W = g_w p; cell c = row g_w + col.
+ *   Draw d of the sample with the global 64-bit id `id` (id0 + b, wrapping) gives cell c the key (w_c << 32) | c, where w_c
+ *   is word c & 3 of Philox4x32-10 (the generator of the noise above) with the counter (0x80000000 | (c >> 2), d, low32(id),
+ *   high32(id)) and the key (low32(seed), high32(seed)); the 64 bits of seed are read as unsigned.  The set top bit of the
+ *   first counter word keeps this stream apart from the noise stream, whose first word stays below 2^29.  S(id, d) is the k
+ *   cells with the smallest keys, 1 <= k <= G; ties cannot occur, because the index is part of the key.
+ * Subset inputs.  x [B,C,H,W] fp32: the normalised input the model saw, upcast.  The substrate, in normalised space, is a
+ *   [B,C,H,W] fp32 tensor or, when that pointer is NULL, the C per-channel constants `fill` (C <= TE_PERTURB_MAX_CHANNELS
+ *   then).  out [B,n_d,C,H,W], fp32 or bf16: row b n_d + j is draw d0 + j of sample id0 + b; a pixel whose cell is in
+ *   S(id0 + b, d0 + j) takes the substrate's value, every other pixel x's.  The bits are copied; _bf16 rounds once, to
+ *   nearest even.  member [B,n_d,G] uint8: 1 for the cells of S, else 0.  attr [B,G] fp32 (the token-level map) may be NULL;
+ *   when it is given, attr_sum [B,n_d] fp64 = sum over c in S of (double)attr[b,c]: thread t of 256 adds its cells t, t + 256,
+ *   ... in order, then the 64 lanes of a wave and the four waves meet in a fixed order -- an order fixed by G alone.
+ *   Two launches on the stream: one workgroup per (sample, draw) ranks the keys in LDS by counting and writes member and
+ *   attr_sum; a store-shaped pass then writes the images, 16-byte accesses where p % 4 == 0 (bf16: p % 8 == 0) and x, out and
+ *   the substrate are 16-byte aligned, an element-wise form otherwise.
+ * Perturbation dot.  x [B,n] fp32, y [B,D,n] fp32 or bf16, w [B,m] fp32 with n % m == 0 (the pixel-level attribution, shared
+ *   by the n / m channels).  sums [B,D,2] fp64 = sum_e (x_e - y_e) w_(e mod m), sum_e (x_e - y_e)^2, every term formed in
+ *   fp64 from the exact upcasts.  The summation order is that of te_map_distance_*: thread, then lane, then wave; it depends
+ *   on n alone, and the second sum has the bits of te_map_distance_*'s first.
+ * Scores (torch, fp64, on the device: faithfulness.scores_from_sums) from ip [B,D] = the first sum, delta [B,D] = f(clean) -
+ *   f(copy) and, in subset mode, attr_sum [B,D]:
+ *     infidelity      = mean_d (ip - delta)^2
+ *     beta            = sum_d ip delta / sum_d ip^2, or 1 when the denominator is 0 (captum's normalize=True)
+ *     infidelity_norm = mean_d (beta ip - delta)^2
+ *     faith_corr      = Pearson_d(attr_sum, delta) from centred sums, clamped to [-1, 1]; NaN for D < 2 or a constant side.
+ * Refused on the host before any HIP call: null pointers (x, out, member; substrate and fill both; attr without attr_sum; x, y,
+ *   w, sums), sizes <= 0, k outside [1, G], d0 < 0, d0 + n_d > 2^32, n % m != 0 TE_ERR_INVALID_ARG; G > TE_SUBSET_MAX_CELLS,
+ *   B > 65535, C H W > 2^31 - 1, n_d > 2^31 - 1, constants for C > TE_PERTURB_MAX_CHANNELS, n > 2^31 - 1, D > 2^31 - 1
+ *   TE_ERR_UNSUPPORTED. */
+#define TE_SUBSET_MAX_CELLS 4096
+int te_subset_inputs_f32(const float* x, const float* substrate, const float* fill, const float* attr, float* out,
+                         uint8_t* member, double* attr_sum, int64_t B, int64_t C, int64_t g_h, int64_t g_w, int64_t p,
+                         int64_t k, int64_t d0, int64_t n_d, int64_t seed, int64_t id0, te_stream_t stream);
+int te_subset_inputs_bf16(const float* x, const float* substrate, const float* fill, const float* attr, te_bf16_t* out,
+                          uint8_t* member, double* attr_sum, int64_t B, int64_t C, int64_t g_h, int64_t g_w, int64_t p,
+                          int64_t k, int64_t d0, int64_t n_d, int64_t seed, int64_t id0, te_stream_t stream);
+int te_perturbation_dot_f32(const float* x, const float* y, const float* w, double* sums, int64_t B, int64_t D, int64_t n,
+                            int64_t m, te_stream_t stream);
+int te_perturbation_dot_bf16(const float* x, const te_bf16_t* y, const float* w, double* sums, int64_t B, int64_t D, int64_t n,
+                             int64_t m, te_stream_t stream);
+
 /* ---- bf16 operands (a bf16 ViT / DeiT or BERT model: model.to(torch.bfloat16)) ----------------------------
  * The rules of variant "ours", alpha = 1, evaluated in fp32 on the model's own bf16 tensors (te_bf16_t, read exactly:
  * bf16 -> fp32 is exact).  Relevance operands and outputs, safe_divide, per-sample sums and factors are fp32 as in the

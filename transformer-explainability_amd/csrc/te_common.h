@@ -240,6 +240,28 @@ __device__ __forceinline__ void te_block_sum3(double& a, double& b, double& c, d
   }
 }
 
+// The counter-based random stream of the noisy copies (te_robust.hip) and of the random subsets (te_faithful.hip).
+// Philox4x32-10 (Salmon et al., SC 2011): counter c[4], key (k0, k1) -> c[4]
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0;
+    c[1] = lo1;
+    c[2] = n2;
+    c[3] = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
+// fp32 -> the bits of the nearest bf16, ties to even (te_robust.hip, te_faithful.hip)
+__device__ __forceinline__ uint16_t bf16_bits(float v) {      // to nearest even
+  return (uint16_t)(__builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{v, 0.0f}, bf16x2)) & 0xffffu);
+}
+
 // Patch geometry of a stride == kernel convolution (ViT patch embedding): row t = (b, py, px) of the im2col matrix,
 // column k = (c, dy, dx); te_zb_index maps (t, k) to the element's offset in the NCHW image.
 struct TeZbGeom {

@@ -28,32 +28,12 @@ constexpr int64_t kMaxBatch = 65535;
 constexpr int kDistThreads = 256;
 
 // ------------------------------------------------------------------------------------------------ noise
-// Philox4x32-10 (Salmon et al., SC 2011): counter c[4], key (k0, k1) -> c[4]
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0;
-    c[1] = lo1;
-    c[2] = n2;
-    c[3] = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
 // y = x + (2 u - 1) radius with u = (w >> 8) 2^-24: u and 2 u - 1 are exact, the product and the sum round once each and
 // are never contracted into an FMA (torch's x + s * radius)
 __device__ __forceinline__ float noisy(float x, uint32_t w, float radius) {
   const float u = (float)(w >> 8) * 0x1p-24f;
   const float s = __fsub_rn(__fmul_rn(2.0f, u), 1.0f);
   return __fadd_rn(x, __fmul_rn(s, radius));
-}
-
-__device__ __forceinline__ uint16_t bf16_bits(float v) {      // to nearest even
-  return (uint16_t)(__builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{v, 0.0f}, bf16x2)) & 0xffffu);
 }
 
 // out[b n_d + j][e] = noisy(x[b][e], word e & 3 of philox(e >> 2, d0 + j, id0 + b; seed)).  OutT float: a thread owns 4

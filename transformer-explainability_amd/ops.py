@@ -1890,6 +1890,122 @@ def map_complexity(maps: Tensor, eps: float = 1e-5):
     return out, counts
 
 
+# ---------------------------------------------------------------------------------------- faithfulness (faithfulness.py)
+def _grid_of(what: str, x: Tensor, grid):
+    """(C, g_h, g_w, p) of x [B,C,H,W] cut into grid = g or (g_h, g_w) cells of p x p pixels."""
+    if x.dim() != 4 or x.numel() == 0:
+        raise _lib.TeError(f"{what}: x must be [B,C,H,W] and not empty, got {tuple(x.shape)}")
+    g_h, g_w = (int(v) for v in grid) if isinstance(grid, (tuple, list)) else (int(grid), int(grid))
+    _, C, H, W = x.shape
+    if g_h < 1 or g_w < 1 or H % g_h or W % g_w or H // g_h != W // g_w:
+        raise _lib.TeError(f"{what}: a grid of {g_h} x {g_w} does not cut x {tuple(x.shape)} into square cells")
+    if g_h * g_w > _lib.TE_SUBSET_MAX_CELLS:
+        raise _lib.TeError(f"{what}: at most {_lib.TE_SUBSET_MAX_CELLS} cells, got a grid of {g_h} x {g_w} for x "
+                           f"{tuple(x.shape)}")
+    return C, g_h, g_w, H // g_h
+
+
+def subset_inputs(x: Tensor, k: int, grid, seed: int, id0: int = 0, d0: int = 0, n_draws: int = 1,
+                  substrate: Optional[Tensor] = None, fill: Optional[Sequence[float]] = None, attr: Optional[Tensor] = None,
+                  out_dtype: torch.dtype = torch.float32):
+    """The perturbed images of the faithfulness correlation: x [B,C,H,W] fp32 (the model's normalised input), cut into
+    grid = g or (g_h, g_w) square cells -> (out [B,n_draws,C,H,W] in ``out_dtype``, member uint8 [B,n_draws,G], attr_sum
+    float64 [B,n_draws] or None).  Copy j of sample b is draw d0 + j of the sample with the global id id0 + b: the k cells
+    with the smallest Philox keys take the substrate's value -- a [B,C,H,W] fp32 tensor in normalised space, or the
+    per-channel constants ``fill`` -- and every other pixel x's, bit for bit (bfloat16: rounded once, to nearest even).
+    attr [B,G] fp32, the token-level map, adds attr_sum = its sum over the chosen cells in fp64 (include/te_relprop.h,
+    "faithfulness"; ``faithfulness.reference_subset_inputs``).  A sample's outputs do not depend on the batch or on the chunk
+    (d0, n_draws) they are made in."""
+    what = "subset_inputs"
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.TeError(f"{what}: out_dtype must be float32 or bfloat16, got {out_dtype}")
+    x = _robust_tensor(what, "x", x, (torch.float32,))
+    C, g_h, g_w, _ = _grid_of(what, x, grid)
+    n_draws = int(n_draws)
+    if n_draws < 1:
+        raise _lib.TeError(f"{what}: n_draws must be at least 1, got {n_draws}")
+    # (a view that is dense but starts off a 16-byte boundary stays a view: the kernel has an element-wise form)
+    x = x if x.is_contiguous() else x.contiguous()
+    out = torch.empty((x.shape[0], n_draws) + tuple(x.shape[1:]), dtype=out_dtype, device=x.device)
+    return _subset_inputs_into(x, out, k, (g_h, g_w), seed, id0, d0, substrate, fill, attr)
+
+
+def _subset_inputs_into(x: Tensor, out: Tensor, k: int, grid, seed: int, id0: int = 0, d0: int = 0,
+                        substrate: Optional[Tensor] = None, fill: Optional[Sequence[float]] = None,
+                        attr: Optional[Tensor] = None):
+    """The launches of ``subset_inputs``, into out [B,n_draws,C,H,W] fp32 or bf16, dense.  Not part of the interface: the
+    tests call it to hand the kernel an output view that starts off a 16-byte boundary."""
+    what = "subset_inputs"
+    x = _robust_tensor(what, "x", x, (torch.float32,))
+    out = _robust_tensor(what, "out", out, (torch.float32, torch.bfloat16))
+    C, g_h, g_w, p = _grid_of(what, x, grid)
+    if out.dim() != 5 or out.shape[0] != x.shape[0] or out.shape[2:] != x.shape[1:] or out.numel() == 0 or \
+            not x.is_contiguous() or not out.is_contiguous():
+        raise _lib.TeError(f"{what}: x must be a dense [B,C,H,W] and out a dense [B,n_draws,C,H,W], got {tuple(x.shape)} and "
+                           f"{tuple(out.shape)}")
+    B, n_draws, G = out.shape[0], out.shape[1], g_h * g_w
+    k, d0, seed, id0 = int(k), int(d0), int(seed), int(id0)
+    if k < 1 or k > G:
+        raise _lib.TeError(f"{what}: k must name 1 .. {G} of the {g_h} x {g_w} cells of x {tuple(x.shape)}, got {k}")
+    if B > 65535:
+        raise _lib.TeError(f"{what}: at most 65535 samples, got x {tuple(x.shape)}")
+    if d0 < 0 or d0 + n_draws > 1 << 32:
+        raise _lib.TeError(f"{what}: draws {d0} .. {d0 + n_draws - 1} are not draws 0 .. 2^32 - 1")
+    if not (-(1 << 63) <= seed < 1 << 64) or not (-(1 << 63) <= id0 < 1 << 64):
+        raise _lib.TeError(f"{what}: seed and id0 are 64-bit integers, got {seed} and {id0}")
+    seed, id0 = (v - (1 << 64) if v >= 1 << 63 else v for v in (seed, id0))      # (read as unsigned on the device)
+    if (substrate is None) == (fill is None):
+        raise _lib.TeError(f"{what}: give a substrate tensor or the fill constants, one of the two")
+    if substrate is not None:
+        substrate = _robust_tensor(what, "substrate", substrate, (torch.float32,))
+        if substrate.shape != x.shape:
+            raise _lib.TeError(f"{what}: substrate {tuple(substrate.shape)} is not shaped like x {tuple(x.shape)}")
+        substrate = substrate if substrate.is_contiguous() else substrate.contiguous()
+    elif C > _lib.TE_PERTURB_MAX_CHANNELS:
+        raise _lib.TeError(f"{what}: fill constants serve at most {_lib.TE_PERTURB_MAX_CHANNELS} channels, x is "
+                           f"{tuple(x.shape)}; give a substrate tensor")
+    f_arr = _floats(fill, C, what, "fill")
+    attr_sum = None
+    if attr is not None:
+        attr = _robust_tensor(what, "attr", attr, (torch.float32,))
+        if attr.numel() != B * G or attr.shape[0] != B:
+            raise _lib.TeError(f"{what}: attr {tuple(attr.shape)} is not a [B,G] map of the {g_h} x {g_w} cells of x "
+                               f"{tuple(x.shape)}")
+        attr = attr.reshape(B, G)
+        attr = attr if attr.is_contiguous() else attr.contiguous()
+        attr_sum = torch.empty((B, n_draws), dtype=torch.float64, device=x.device)
+    member = torch.empty((B, n_draws, G), dtype=torch.uint8, device=x.device)
+    name = "te_subset_inputs_f32" if out.dtype == torch.float32 else "te_subset_inputs_bf16"
+    with _on_device(x) as lib:
+        _lib.check(getattr(lib, name)(_ptr(x), _ptr(substrate), f_arr, _ptr(attr), _ptr(out), _ptr(member), _ptr(attr_sum),
+                                      B, C, g_h, g_w, p, k, d0, n_draws, seed, id0, _stream(x)), name)
+    return out, member, attr_sum
+
+
+def perturbation_dot(x: Tensor, y: Tensor, w: Tensor) -> Tensor:
+    """x fp32 [B,...] of n values per sample, y fp32 or bf16 [B,D,...] with as many, w fp32 [B,...] of m values with n % m == 0
+    (the pixel-level attribution, shared by the n / m channels) -> sums float64 [B,D,2] = sum_e (x_e - y_e) w_(e mod m),
+    sum_e (x_e - y_e)^2, every term in fp64 from the exact upcasts, in the order of ``map_distance``; one launch, no
+    synchronisation (``faithfulness.reference_dot``)."""
+    what = "perturbation_dot"
+    x = _robust_tensor(what, "x", x, (torch.float32,))
+    y = _robust_tensor(what, "y", y, (torch.float32, torch.bfloat16))
+    w = _robust_tensor(what, "w", w, (torch.float32,))
+    if x.dim() < 2 or y.dim() < 3 or w.dim() < 2 or x.numel() == 0 or y.numel() == 0 or w.numel() == 0 or \
+            x.shape[0] != y.shape[0] or w.shape[0] != x.shape[0] or x[0].numel() != y[0, 0].numel():
+        raise _lib.TeError(f"{what}: x must be [B,n], y [B,D,n] and w [B,m] and not empty, got {tuple(x.shape)}, "
+                           f"{tuple(y.shape)} and {tuple(w.shape)}")
+    B, D, n, m = y.shape[0], y.shape[1], x[0].numel(), w[0].numel()
+    if n % m != 0:
+        raise _lib.TeError(f"{what}: the {m} weights of w {tuple(w.shape)} do not divide the {n} values of x {tuple(x.shape)}")
+    x, y, w = (t if t.is_contiguous() else t.contiguous() for t in (x, y, w))
+    out = torch.empty((B, D, 2), dtype=torch.float64, device=x.device)
+    name = "te_perturbation_dot_f32" if y.dtype == torch.float32 else "te_perturbation_dot_bf16"
+    with _on_device(x) as lib:
+        _lib.check(getattr(lib, name)(_ptr(x), _ptr(y), _ptr(w), _ptr(out), B, D, n, m, _stream(x)), name)
+    return out
+
+
 # ---------------------------------------------------------------------------------------- bf16 operands
 # A bf16 model's rules: the reference's algorithm evaluated in fp32 on the model's own bf16 tensors (read exactly: bf16 ->
 # fp32 is exact).  Relevance, safe_divide, per-sample sums and the rollout stay fp32; Linear's Z is X+ W+^T + X- W-^T from

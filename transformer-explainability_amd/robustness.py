@@ -23,6 +23,9 @@ PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
 PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
 _MASK32 = np.uint64(0xFFFFFFFF)
 SCORE_NAMES = ("max_sens", "avg_sens", "lipschitz", "gini", "entropy", "n_eff")
+# what integer inputs are refused with, here and by faithfulness.FaithfulnessEvaluator
+DISCRETE_MSG = ("SensitivityEvaluator: noise on discrete inputs (BERT's token ids) is not defined here; "
+                "the protocol takes the float images of a ViT / DeiT")
 
 
 # ------------------------------------------------------------------------------------------------ the definitions
@@ -213,8 +216,7 @@ class SensitivityEvaluator:
 
     def update(self, images, index=None):
         if not torch.is_tensor(images) or not images.is_floating_point():
-            raise ops._lib.TeError("SensitivityEvaluator: noise on discrete inputs (BERT's token ids) is not defined here; "
-                                   "the protocol takes the float images of a ViT / DeiT")
+            raise ops._lib.TeError(DISCRETE_MSG)
         B = images.shape[0]
         dtype = self._input_dtype(images)
         device = images.is_cuda
