@@ -6,6 +6,11 @@ same operands; checks: x6 vs fp64 (error no larger than the fp32-MFMA path's), t
 a half batch bit for bit (rows independent of the stream-K cut), no expired hand-over wait.
 
     python benchmarks/x6_bench.py [--config vit_b16|vit_l16|bert_base|all] [--iters 20] [--check-rows 1024]
+    python benchmarks/x6_bench.py --zpass-ab [--config vit_b16] [--iters 40]
+
+--zpass-ab: the Z-pass alone on the planes of |X| (MODE_Z) against the Z-pass on the signed planes of X
+(TE_X6_X_PLANES_SIGNED: the sign is applied while the activation blocks are staged), per shape and tile geometry, the two
+variants alternating launch by launch in one process; `out` of the whole rule compared bit for bit.
 """
 import argparse
 import json
@@ -127,6 +132,50 @@ def check_shape(T, in_f, out_f, dev):
                 max_abs_x6_vs_fp32=float((outs[0] - fp32).abs().max()) / scale)
 
 
+def zpass_ab(T, in_f, out_f, iters, dev):
+    """us per Z-pass launch, |X| planes against signed planes, for the geometry the library picks and the three pins."""
+    lib = _lib.load()
+    X, W, b, R, Y = operands(T, in_f, out_f, 1, dev)
+    wp = ops.x6_weight_planes(W)
+    st = torch.cuda.current_stream().cuda_stream
+    nb = lib.te_linear_x6_planes_bytes(T, in_f)
+    planes = {"abs": torch.empty(nb, dtype=torch.uint8, device=dev), "signed": torch.empty(nb, dtype=torch.uint8, device=dev)}
+    _lib.check(lib.te_linear_x6_split_abs_f32(X.data_ptr(), T, in_f, planes["abs"].data_ptr(), nb, st), "split_abs")
+    _lib.check(lib.te_linear_x6_split_matrix_f32(X.data_ptr(), T, in_f, 0, planes["signed"].data_ptr(), nb, st), "split_matrix")
+    ws = torch.zeros(lib.te_linear_relprop_x6_workspace_bytes(T, in_f, out_f), dtype=torch.uint8, device=dev)
+    outs = {k: torch.empty((T, in_f), dtype=torch.float32, device=dev) for k in planes}
+
+    def call(kind, flags):
+        fl = flags | (ops.TE_X6_X_PLANES_SIGNED if kind == "signed" else 0)
+        _lib.check(lib.te_linear_relprop_x6_f32(R.data_ptr(), None, 0, 1, X.data_ptr(), W.data_ptr(), wp.data_ptr(),
+                                                planes[kind].data_ptr(), Y.data_ptr(), b.data_ptr(), outs[kind].data_ptr(), T, in_f,
+                                                out_f, fl, None, ws.data_ptr(), ws.numel(), st), "te_linear_relprop_x6_f32")
+
+    rows = []
+    for geo, pin in (("auto", 0), ("128x256", _lib.TE_X6_TILE_128), ("256x256", _lib.TE_X6_TILE_256), ("128x128", _lib.TE_X6_TILE_128x128)):
+        zpin = pin << ops.TE_X6_TILE_Z_SHIFT
+        for kind in planes:                                   # the whole rule once: warm-up and the bitwise comparison
+            call(kind, zpin)
+        torch.cuda.synchronize()
+        same = bool(torch.equal(outs["abs"], outs["signed"]))
+        clean = lib.te_linear_relprop_x6_check(ws.data_ptr(), T, in_f, out_f, st) == 0
+        ev = {k: [] for k in planes}
+        for _ in range(iters):
+            for kind in planes:
+                call(kind, zpin | ops.TE_X6_PHASE_SPLIT)       # (planes given: this phase only resets the hand-over flags)
+                a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                call(kind, zpin | ops.TE_X6_PHASE_Z)
+                e.record()
+                ev[kind].append((a, e))
+        torch.cuda.synchronize()
+        us = {k: sorted(a.elapsed_time(e) * 1e3 for a, e in v) for k, v in ev.items()}
+        rows.append(dict(T=T, in_f=in_f, out_f=out_f, geometry=geo, out_bitwise=same, check_clean=clean,
+                         abs_us_med=us["abs"][iters // 2], abs_us_min=us["abs"][0], signed_us_med=us["signed"][iters // 2],
+                         signed_us_min=us["signed"][0], delta_us_med=us["signed"][iters // 2] - us["abs"][iters // 2]))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="vit_b16")
@@ -134,10 +183,18 @@ def main():
     ap.add_argument("--check-rows", type=int, default=1100)
     ap.add_argument("--tiles", default="0,1")
     ap.add_argument("--skip-checks", action="store_true")
+    ap.add_argument("--zpass-ab", action="store_true", help="Z-pass on |X| planes against signed planes, per shape and geometry")
     a = ap.parse_args()
     _lib.require_device()
     dev = torch.device("cuda:0")
     names = list(CONFIGS) if a.config == "all" else a.config.split(",")
+    if a.zpass_ab:
+        for name in names:
+            T, shapes = CONFIGS[name]
+            for (lname, in_f, out_f) in shapes:
+                for r in zpass_ab(T, in_f, out_f, a.iters, dev):
+                    print("ZPASS " + json.dumps(dict(config=name, layer=lname, **r)), flush=True)
+        return
     if not a.skip_checks:
         for (T, i, o) in [(a.check_rows, 768, 2304), (a.check_rows, 3072, 768), (394, 768, 768), (300, 128, 384),
                           (70, 192, 128), (2 * 197, 1024, 4096)]:

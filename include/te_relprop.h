@@ -300,6 +300,10 @@ int te_rollout_f32(const float* cams, int64_t L, int64_t start_layer, int64_t B,
                                           keep several streams busy (the idle CUs of a last round are used by their other kernels,
                                           and no tile is handed over between workgroups).  Same results, bit for bit */
 #define TE_X6_TEST_SMALL_GRID 0x4000   /* tests: a persistent grid of 16 workgroups, so that small shapes get stream-K cuts */
+#define TE_X6_X_PLANES_SIGNED 0x20000   /* te_linear_relprop_x6_f32: x_planes holds the SIGNED planes of X (te_gemm_x6_f32's x_planes, what
+                                          the layer's forward product read) instead of the planes of |X|: the Z-pass clears the sign of
+                                          plane 0 and flips the low planes as it stages them.  Same results, bit for bit; with
+                                          x_planes = NULL the split into the workspace writes signed planes */
 #define TE_X6_TILE_Z_SHIFT 10
 #define TE_X6_TILE_C_SHIFT 12
 /* optional phase mask (measurement: one phase per call on the same workspace, in this order); 0 = the whole rule */
@@ -366,7 +370,8 @@ int te_linear_x6_split_dual_f32(const float* A, int64_t rows, int64_t K, void* p
  *                                   written.
  *   te_gelu_forward_x6_planes_f32   y = gelu(x) as fp32 (te_gelu_forward_f32's bits) AND the two plane sets
  *                                   te_linear_x6_split_dual_f32 builds from y (fc2's forward product, fc2's rule).
- * K % 16 == 0; planes / planes_abs: te_linear_x6_planes_bytes(rows, K) bytes each = planes_bytes. */
+ * K % 16 == 0; planes / planes_abs: te_linear_x6_planes_bytes(rows, K) bytes each = planes_bytes.  planes_abs = NULL (forward): the
+ * second set is not written (fc2's rule then takes the signed planes with TE_X6_X_PLANES_SIGNED). */
 int te_gelu_backward_x6_planes_f32(const float* dy, const float* x, int64_t rows, int64_t K, void* planes,
                                    size_t planes_bytes, te_stream_t stream);
 int te_gelu_forward_x6_planes_f32(const float* x, float* y, int64_t rows, int64_t K, void* planes, void* planes_abs,

@@ -67,7 +67,9 @@ constexpr int kErrWord = 1023;                 // flags[0 .. 767] = hand-over fl
 // = X+ W-^T + X- W+^T; MODE_Z1 = a one-sided Z-pass, S = sd(R, acc) (acc = X+ W+^T ...: same-sign terms, no cancellation);
 // MODE_CI = the C-pass with the signs crossed, out += scale (X+ . (S W-) + X- . (S W+)); MODE_X = a product masked by one
 // sign of X, out (+)= scale (X+- . acc).
-enum { MODE_Z = 0, MODE_C = 1, MODE_G = 2, MODE_ZI = 3, MODE_Z1 = 4, MODE_CI = 5, MODE_X = 6 };
+// MODE_ZS = MODE_Z whose activation operand is the SIGNED planes of X (what the forward product read): |X| is formed while the
+// planes are staged (x6_kernel: SGN), so no producer has to store a second plane set.
+enum { MODE_Z = 0, MODE_C = 1, MODE_G = 2, MODE_ZI = 3, MODE_Z1 = 4, MODE_CI = 5, MODE_X = 6, MODE_ZS = 7 };
 
 __device__ __forceinline__ float bf16_f32(unsigned b) { return __uint_as_float(b << 16); }
 
@@ -226,7 +228,7 @@ __global__ __launch_bounds__(256) void gelu_split_lds_kernel(const float* __rest
       }
   };
   store(dst + ((rb * nks + ks) * 3) * kFrag + r * 16);
-  if constexpr (SRC == SRC_GELU_FWD) {
+  if (SRC == SRC_GELU_FWD && dst_abs) {        // (dst_abs = NULL: the consumer's rule takes the signed planes)
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const unsigned m = p[e][0] & 0x80008000u;
@@ -349,7 +351,7 @@ struct X6Geo {
 template <int WM, int MODE>
 struct X6Lds {
   using GEO = X6Geo<WM>;
-  static constexpr bool STAGED = (MODE == MODE_Z || MODE == MODE_ZI || MODE == MODE_Z1) && GEO::MI == 4;
+  static constexpr bool STAGED = (MODE == MODE_Z || MODE == MODE_ZS || MODE == MODE_ZI || MODE == MODE_Z1) && GEO::MI == 4;
   static constexpr int STAGES = kStages * (GEO::NPA + GEO::NPB) * kFrag;
   static constexpr int MAIN = (STAGED && GEO::NW * 16384 > STAGES) ? GEO::NW * 16384 : STAGES;
   static constexpr int TOTAL = MAIN + GEO::NW * 512 + 16;
@@ -359,7 +361,9 @@ template <int WM, int MODE>
 __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(const X6Params p) {
   using GEO = X6Geo<WM>;
   constexpr int NW = GEO::NW, NWM = GEO::NWM, NWN = GEO::NWN, MI = GEO::MI;
-  constexpr bool IS_Z = (MODE == MODE_Z || MODE == MODE_ZI || MODE == MODE_Z1);
+  constexpr bool SGN = MODE == MODE_ZS;              // B holds the planes of X, not of |X|: the sign goes while staging
+  constexpr bool Z_ABS = MODE == MODE_Z || SGN;      // Z from (Y - b) + |X||W|^T
+  constexpr bool IS_Z = (Z_ABS || MODE == MODE_ZI || MODE == MODE_Z1);
   constexpr bool IS_C = (MODE == MODE_C || MODE == MODE_CI);
   constexpr int G = IS_C ? 6 : 3;                    // pieces of one A group (32 rows [x 2 signs]) per K16 step
   constexpr int NPA = GEO::NPA, NPB = GEO::NPB;      // 1-KiB pieces of one stage: weight side, activation side
@@ -439,6 +443,10 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
     unsigned char* const ldsB = smem + NPA * kFrag + wave * (PBW * kRB);
     // adv = 0 re-requests the step already staged (branch-free last step: no control-flow join between the fragment
     // reads and the MFMAs, which is what lets hipcc wait for the reads piecemeal)
+    // SGN: the activation blocks go through registers (plain loads, requested where the direct-to-LDS loads are) and reach the
+    // stage through sign_and_store after the step's MFMAs: each block is fixed once per workgroup, by the wave that stages it,
+    // and the pinned read / MFMA body below is that of MODE_Z.
+    u32x4 breg[SGN ? PBW : 1][3];
     auto stage_in = [&](int stg, int adv) __attribute__((always_inline)) {
       srcA += adv * (G * kFrag);
 #pragma unroll
@@ -448,7 +456,26 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
 #pragma unroll
       for (int u = 0; u < PBW; ++u)
 #pragma unroll
-        for (int q = 0; q < 3; ++q) glds16(srcB[u] + q * kFrag + lane16, ldsB + stg * STAGE + (u * 3 + q) * kFrag);
+        for (int q = 0; q < 3; ++q) {
+          if constexpr (SGN) breg[u][q] = *reinterpret_cast<const u32x4*>(srcB[u] + q * kFrag + lane16);
+          else glds16(srcB[u] + q * kFrag + lane16, ldsB + stg * STAGE + (u * 3 + q) * kFrag);
+        }
+    };
+    // planes of x -> planes of |x| (split_kernel's dst_abs without its zero-residual mask: a low plane may hold -0 where
+    // split3(|x|) has +0, and a -0 product leaves every accumulator -- which starts from +0 -- as it is), then into the stage
+    auto sign_and_store = [&](int stg) __attribute__((always_inline)) {
+#pragma unroll
+      for (int u = 0; u < (SGN ? PBW : 0); ++u) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const unsigned m = breg[u][0][e] & 0x80008000u;
+          breg[u][0][e] &= 0x7fff7fffu;
+          breg[u][1][e] ^= m;
+          breg[u][2][e] ^= m;
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) *reinterpret_cast<u32x4*>(ldsB + stg * STAGE + (u * 3 + q) * kFrag + lane16) = breg[u][q];
+      }
     };
 
     // Bounded, loud wait for a flag another workgroup raises (release) once its accumulators are in memory; uniform
@@ -511,6 +538,7 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
 
     // ---- main loop: stage ks + 1 lands while stage ks is multiplied ----
     stage_in(0, 0);
+    if constexpr (SGN) sign_and_store(0);
     int st = 0;
     bf16x8 a[MI][3], b[2][3];
     for (int ks = k0; ks < k1; ++ks) {
@@ -612,8 +640,12 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
 #undef X6_MM
 #undef X6_RD_HEAD
 #undef X6_RD_TAIL
+      // (the stage of step ks - 1: every wave left it before this step's barrier; the next barrier's lgkmcnt(0) covers the writes)
+      if constexpr (SGN) sign_and_store((st + 1) % kStages);
       st = (st + 1 == kStages) ? 0 : st + 1;
     }
+    // (the last step staged itself again: those writes are in the LDS before the epilogue's barrier lets anything reuse the stages)
+    if constexpr (SGN) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
     // ---- accumulators to memory + flag (guide: plain stores -> vmcnt(0) -> barrier -> release -> flag) ----
     auto publish = [&](float* dst, unsigned* flag) __attribute__((always_inline)) {
@@ -736,7 +768,7 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
           unsigned long long any_cancel = 0;
           auto z_of = [&](int g, int c0, f32x2& z2, f32x2& a2) __attribute__((always_inline)) {
             a2 = f32x2{acc[mi][ni][4 * g + c0], acc[mi][ni][4 * g + c0 + 1]};
-            if constexpr (MODE == MODE_Z)            // Z  = X+ W+^T + X- W-^T = ((Y - b) + |X||W|^T) / 2  (>= 0)
+            if constexpr (Z_ABS)                     // Z  = X+ W+^T + X- W-^T = ((Y - b) + |X||W|^T) / 2  (>= 0)
               z2 = f32x2{0.5f, 0.5f} * ((f32x2{y4[g][c0], y4[g][c0 + 1]} - f32x2{b4[g][c0], b4[g][c0 + 1]}) + a2);
             else if constexpr (MODE == MODE_ZI)      // Z' = X+ W-^T + X- W+^T = ((Y - b) - |X||W|^T) / 2  (<= 0)
               z2 = f32x2{0.5f, 0.5f} * ((f32x2{y4[g][c0], y4[g][c0 + 1]} - f32x2{b4[g][c0], b4[g][c0 + 1]}) - a2);
@@ -744,7 +776,7 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
               z2 = a2;
           };
           auto cancels = [&](float z, float a_abs) __attribute__((always_inline)) -> bool {
-            if constexpr (MODE == MODE_Z) return !(z > kCancelTol * a_abs);
+            if constexpr (Z_ABS) return !(z > kCancelTol * a_abs);
             else if constexpr (MODE == MODE_ZI) return !(-z > kCancelTol * a_abs);
             else return false;
           };
@@ -863,7 +895,7 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
             const float a_abs = acc[mi][ni][4 * g + c];
             float z;
             bool cancel;
-            if constexpr (MODE == MODE_Z) {              // Z  = X+ W+^T + X- W-^T = ((Y - b) + |X||W|^T) / 2  (>= 0)
+            if constexpr (Z_ABS) {                       // Z  = X+ W+^T + X- W-^T = ((Y - b) + |X||W|^T) / 2  (>= 0)
               z = 0.5f * ((y4[buf][g][c] - b4[c]) + a_abs);
               cancel = !(z > kCancelTol * a_abs);
             } else if constexpr (MODE == MODE_ZI) {      // Z' = X+ W-^T + X- W+^T = ((Y - b) - |X||W|^T) / 2  (<= 0)
@@ -1091,7 +1123,7 @@ inline X6WeightPlanesLrp weight_planes_lrp(int64_t in_f, int64_t out_f) {
 // ---- flags (te_relprop.h) ----
 constexpr int kTileMask = TE_X6_TILE_128 | TE_X6_TILE_256 | TE_X6_TILE_128x128;
 constexpr int kProductFlags = kTileMask | TE_X6_WHOLE_TILES | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID;   // plain product, general rule
-constexpr int kRuleFlags = kProductFlags | TE_X6_PHASE_MASK | (kTileMask << TE_X6_TILE_Z_SHIFT) | (kTileMask << TE_X6_TILE_C_SHIFT);
+constexpr int kRuleFlags = kProductFlags | TE_X6_PHASE_MASK | TE_X6_X_PLANES_SIGNED | (kTileMask << TE_X6_TILE_Z_SHIFT) | (kTileMask << TE_X6_TILE_C_SHIFT);
 
 inline int pick_wm(int64_t in_f, int64_t out_f) {
   if (out_f % 256 == 0 && in_f % 128 == 0) return 2;
@@ -1327,8 +1359,9 @@ extern "C" int te_gelu_backward_x6_planes_f32(const float* dy, const float* x, i
 
 extern "C" int te_gelu_forward_x6_planes_f32(const float* x, float* y, int64_t rows, int64_t K, void* planes, void* planes_abs,
                                              size_t planes_bytes_, te_stream_t stream_) {
-  const int rc = check_producer(x && y && planes && planes_abs, te_aligned16(x) && te_aligned16(y),
-                                te_aligned16(planes) && te_aligned16(planes_abs), rows, K, planes_bytes_);
+  // planes_abs = NULL: only the signed planes are written (te_linear_relprop_x6_f32 takes them with TE_X6_X_PLANES_SIGNED)
+  const int rc = check_producer(x && y && planes, te_aligned16(x) && te_aligned16(y),
+                                te_aligned16(planes) && (!planes_abs || te_aligned16(planes_abs)), rows, K, planes_bytes_);
   if (rc != TE_OK) return rc;
   gelu_split_lds_kernel<SRC_GELU_FWD><<<producer_grid(rows, K), dim3(256), 0, (hipStream_t)stream_>>>(
       nullptr, x, y, (unsigned char*)planes, (unsigned char*)planes_abs, rows, K);
@@ -1393,9 +1426,11 @@ extern "C" int te_linear_relprop_x6_f32(const float* R, const float* r_scale, in
   const unsigned char* wc = wz + weight_planes(in_f, out_f).c;
 
   if (phases & TE_X6_PHASE_SPLIT) zero_flag_regions(l.flag_region(ws, 0), kRulePasses, stream);
+  const bool x_signed = (flags & TE_X6_X_PLANES_SIGNED) != 0;      // x_planes = the planes of X: the Z-pass forms |X| as it stages them
   if (!x_planes) {
     if (phases & TE_X6_PHASE_SPLIT) {
-      int rc = te_linear_x6_split_abs_f32(X, T, in_f, l.x(ws, 0), planes_bytes(T, in_f), stream_);
+      int rc = x_signed ? te_linear_x6_split_matrix_f32(X, T, in_f, 0, l.x(ws, 0), planes_bytes(T, in_f), stream_)
+                        : te_linear_x6_split_abs_f32(X, T, in_f, l.x(ws, 0), planes_bytes(T, in_f), stream_);
       if (rc != TE_OK) return rc;
     }
     x_planes = l.x(ws, 0);
@@ -1410,7 +1445,8 @@ extern "C" int te_linear_relprop_x6_f32(const float* R, const float* r_scale, in
                                  X, W, Y);
   int rc;
   if (phases & TE_X6_PHASE_Z) {   // Z-pass: D[j][t] = sum_k |W|[j][k] |X|[t][k]
-    rc = launch_pass<MODE_Z>(p, wm_z, wz, (const unsigned char*)x_planes, Ss, in_f, out_f, l.flag_region(ws, 0), stream, 1.0f);
+    rc = x_signed ? launch_pass<MODE_ZS>(p, wm_z, wz, (const unsigned char*)x_planes, Ss, in_f, out_f, l.flag_region(ws, 0), stream, 1.0f)
+                  : launch_pass<MODE_Z>(p, wm_z, wz, (const unsigned char*)x_planes, Ss, in_f, out_f, l.flag_region(ws, 0), stream, 1.0f);
     if (rc != TE_OK) return rc;
   }
   if (phases & TE_X6_PHASE_C) {   // C-pass: D[(i, +-)][t] = sum_j W+-[j][i] S[t][j]

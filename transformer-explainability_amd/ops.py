@@ -18,7 +18,7 @@ from ._lib import (TE_HEADMEAN_CLAMP, TE_HEADMEAN_ROW0, TE_IMPL_SIMPLE, TE_RATIO
                    TE_ROLLOUT_NORMALISE, TE_ROLLOUT_ROW0, TE_VARIANT_LRP, TE_VARIANT_OURS)
 # te_relprop.h's x6 flag bits (TE_X6_WHOLE_TILES: whole-tile ranges always, for callers that keep several streams busy; same bits)
 from ._lib import (TE_X6_PHASE_C, TE_X6_PHASE_SPLIT, TE_X6_PHASE_Z, TE_X6_TEST_DROP_HANDOVER,  # noqa: F401
-                   TE_X6_TEST_SMALL_GRID, TE_X6_TILE_C_SHIFT, TE_X6_TILE_Z_SHIFT, TE_X6_WHOLE_TILES)
+                   TE_X6_TEST_SMALL_GRID, TE_X6_TILE_C_SHIFT, TE_X6_TILE_Z_SHIFT, TE_X6_WHOLE_TILES, TE_X6_X_PLANES_SIGNED)
 
 Tensor = torch.Tensor
 _VARIANTS = {"ours": TE_VARIANT_OURS, "lrp": TE_VARIANT_LRP}
@@ -384,6 +384,20 @@ def gemm_x6_supported(T: int, K: int, M: int) -> bool:
 
 
 X6_KEEP_ABS = os.environ.get("TE_X6_KEEP_ABS", "1") not in ("", "0")     # measurement switch for the plane reuse below
+# The plane set a layer's forward product leaves for its rule: True = the SIGNED planes the product itself read (the rule's
+# Z-pass forms |X| while it stages them: TE_X6_X_PLANES_SIGNED), so that no producer stores a second set; False = the planes
+# of |X| from a dual split / a producer's second store.  Same results, bit for bit (tests, A/B runs).
+X6_SIGNED_PLANES = True
+
+
+def _signed(planes: Tensor) -> Tensor:
+    """Marks a plane set in the ``x_abs_planes`` mailbox as the signed planes of X."""
+    planes._te_signed_planes = True
+    return planes
+
+
+def planes_are_signed(planes: Optional[Tensor]) -> bool:
+    return planes is not None and getattr(planes, "_te_signed_planes", False)
 
 
 def _x_abs_key(X: Tensor, T: int, K: int):
@@ -393,15 +407,16 @@ def _x_abs_key(X: Tensor, T: int, K: int):
 # The three plane hand-overs between layers, each a mailbox in the consuming layer's scratch dict: one function posts, one
 # takes (pops the entry, validates it, returns the planes or None).  Who calls them, and how long an entry may live:
 # DESIGN.md "The layer's scratch dict".
-def post_x_planes(cache: dict, X: Tensor, xs: Tensor, xa: Tensor):
-    """A producer of X leaves the signed planes of X [T, K] and the planes of |X| for the Linear that consumes X.  The entry
-    HOLDS X: while it exists, X's address cannot be recycled for a tensor that would meet the key by accident."""
+def post_x_planes(cache: dict, X: Tensor, xs: Tensor, xa: Optional[Tensor] = None):
+    """A producer of X leaves the signed planes of X [T, K] for the Linear that consumes X (xa: with X6_SIGNED_PLANES off, the
+    planes of |X| as well).  The entry HOLDS X: while it exists, X's address cannot be recycled for a tensor that would meet the
+    key by accident."""
     K = X.shape[-1]
     cache["x_planes_from_producer"] = (_x_abs_key(X, X.numel() // K, K), xs, xa, X)
 
 
 def take_x_planes(cache: dict, X: Tensor, T: int, K: int):
-    """(xs, xa) if a producer posted the planes of exactly this X, else None."""
+    """(xs, xa) if a producer posted the planes of exactly this X (xa = None: it posted the signed planes only), else None."""
     hit = cache.pop("x_planes_from_producer", None)
     if hit is not None and hit[0] == _x_abs_key(X, T, K) and hit[3].data_ptr() == X.data_ptr():
         return hit[1], hit[2]
@@ -416,13 +431,14 @@ def drop_x_planes(cache: dict, with_abs: bool = False):
 
 
 def post_x_abs_planes(cache: dict, X: Tensor, T: int, K: int, xa: Tensor):
-    """The layer's forward product leaves the planes of |X| for its own relprop rule."""
+    """The layer's forward product leaves the plane set its own relprop rule reads: the planes of |X|, or the signed planes
+    the product read, marked as such (_signed)."""
     cache["x_abs_planes"] = (_x_abs_key(X, T, K), xa)
 
 
 def take_x_abs_planes(cache: dict, X: Tensor, T: int, K: int) -> Optional[Tensor]:
-    """The planes of |X| if the forward product of exactly this X left them, else None.  Consumed once: 6 B per input
-    element (0.4 GB per ViT-B block at batch 64) must not outlive the rule."""
+    """The plane set (of |X|, or signed: planes_are_signed) if the forward product of exactly this X left one, else None.
+    Consumed once: 6 B per input element (0.4 GB per ViT-B block at batch 64) must not outlive the rule."""
     keep = _X_ABS_KEPT
     hit = cache.get("x_abs_planes") if keep is not None and not keep.last else cache.pop("x_abs_planes", None)
     return hit[1] if hit is not None and hit[0] == _x_abs_key(X, T, K) else None
@@ -482,8 +498,9 @@ def gemm_x6(X: Tensor, w_planes: Tensor, bias: Optional[Tensor], M: int, timer_n
             keep_abs: Optional[dict] = None, x_planes: Optional[Tensor] = None) -> Tensor:
     """out [..., M] = X [..., K] . W^T + bias with W as signed planes of an [M, K] matrix (x6_matrix_planes).
     keep_abs: the layer's scratch dict -- the signed planes of X are taken from X's producer if it posted them there, else
-    split here, together with the planes of |X| where the layer's rule will read them (te_linear_x6_split_dual_f32: bit for
-    bit those of a split of |X|); the planes of |X| are posted for that rule (DESIGN.md "The layer's scratch dict").
+    split here, and where the layer's rule will read planes they are posted for that rule and live until it has run (DESIGN.md
+    "The layer's scratch dict").  X6_SIGNED_PLANES off: the rule gets the planes of |X| instead, from the producer's second
+    set or te_linear_x6_split_dual_f32 (bit for bit those of a split of |X|).
     x_planes: the signed planes of X from its producer (gelu_backward_planes) -- X is then used for its shape only and never
     read (it may be the zero-stride placeholder the producer returned instead of an fp32 tensor)."""
     K = X.shape[-1]
@@ -501,17 +518,26 @@ def gemm_x6(X: Tensor, w_planes: Tensor, bias: Optional[Tensor], M: int, timer_n
             got = take_x_planes(keep_abs, X, T, K)
             if got is not None:
                 xs, x_bytes = got[0], 6.0 * T * K
-                post_x_abs_planes(keep_abs, X, T, K, got[1])
+                post_x_abs_planes(keep_abs, X, T, K, got[1] if got[1] is not None else _signed(xs))
         if xs is not None and xs.numel() * xs.element_size() < lib.te_linear_x6_planes_bytes(T, K):
             raise _lib.TeError(f"gemm_x6: the operand planes handed in hold {xs.numel() * xs.element_size()} bytes, "
                                f"[{T}, {K}] needs {lib.te_linear_x6_planes_bytes(T, K)}")
+        for_rule = xs is None and keep_abs is not None and rule_takes_abs_planes(T, K, M)
+        if for_rule and not X6_SIGNED_PLANES:
+            x_bytes += 6.0 * T * K                                     # the dual split writes two plane sets
         with _timed(timer_name, 12.0 * T * K * M, x_bytes + 6.0 * K * M + 4.0 * T * M):
-            if xs is None and keep_abs is not None and rule_takes_abs_planes(T, K, M):
+            if for_rule:
                 nb = lib.te_linear_x6_planes_bytes(T, K)
-                xs, xa = _ws(nb, Xc), _ws(nb, Xc)
-                _lib.check(lib.te_linear_x6_split_dual_f32(_ptr(Xc), T, K, _ptr(xs), _ptr(xa), nb, _stream(Xc)),
-                           "te_linear_x6_split_dual_f32")
-                post_x_abs_planes(keep_abs, X, T, K, xa)
+                if X6_SIGNED_PLANES:      # the single split, into a buffer that outlives the call: the rule reads it too
+                    xs = _signed(_ws(nb, Xc))
+                    _lib.check(lib.te_linear_x6_split_matrix_f32(_ptr(Xc), T, K, 0, _ptr(xs), nb, _stream(Xc)),
+                               "te_linear_x6_split_matrix_f32")
+                    post_x_abs_planes(keep_abs, X, T, K, xs)
+                else:
+                    xs, xa = _ws(nb, Xc), _ws(nb, Xc)
+                    _lib.check(lib.te_linear_x6_split_dual_f32(_ptr(Xc), T, K, _ptr(xs), _ptr(xa), nb, _stream(Xc)),
+                               "te_linear_x6_split_dual_f32")
+                    post_x_abs_planes(keep_abs, X, T, K, xa)
             _lib.check(lib.te_gemm_x6_f32(_ptr(Xc) if Xc is not None else None, _ptr(xs), _ptr(w_planes), _ptr(bc), _ptr(out),
                                           T, K, M, (X6_TILE | X6_FLAGS) & ~0x3c00, _ptr(x6_status(X.device)), _ptr(ws),
                                           ws.numel(), _stream(like)), "te_gemm_x6_f32")
@@ -564,6 +590,8 @@ def linear_relprop(R: Tensor, X: Tensor, W: Tensor, alpha: float = 1.0, variant=
         wp = x6_weight_planes(W, cache) if var_code == TE_VARIANT_OURS else None
         wpl = x6_weight_planes_lrp(W, cache) if var_code == TE_VARIANT_LRP else None
         xa = take_x_abs_planes(cache, X, T, in_f) if cache is not None and var_code == TE_VARIANT_OURS else None
+        if planes_are_signed(xa):      # (this entry point takes the planes of |X| only: it splits them itself)
+            xa = None
         gemm = 2.0 * T * in_f * out_f
         halves = 2 if alpha != 1 else 1
         units = (18.0 if var_code == TE_VARIANT_OURS else 24.0) * halves
@@ -587,7 +615,9 @@ def linear_relprop(R: Tensor, X: Tensor, W: Tensor, alpha: float = 1.0, variant=
             and _lib.load().te_linear_relprop_x6_supported(T, in_f, out_f)):
         planes = x6_weight_planes(W, cache)           # (keyed on W as the caller holds it, not on a contiguous copy)
         # the planes of |X| the layer's own forward product left behind (gemm_x6 keep_abs), if X is that tensor
+        # (or the signed planes that product read: TE_X6_X_PLANES_SIGNED)
         xa = take_x_abs_planes(cache, X, T, in_f) if cache is not None else None
+        x_signed = TE_X6_X_PLANES_SIGNED if planes_are_signed(xa) else 0
         with _on_device(Xc) as lib:
             ws = _ws(lib.te_linear_relprop_x6_workspace_bytes(T, in_f, out_f), Xc)
             status = x6_status(Xc.device)
@@ -595,7 +625,7 @@ def linear_relprop(R: Tensor, X: Tensor, W: Tensor, alpha: float = 1.0, variant=
             def call(flags):
                 _lib.check(lib.te_linear_relprop_x6_f32(_ptr(Rc), rs_ptr, rs_stride, rps, _ptr(Xc), _ptr(Wc), _ptr(planes),
                                                         _ptr(xa), _ptr(Yc), _ptr(bc), _ptr(out), T, in_f, out_f,
-                                                        X6_TILE | X6_FLAGS | flags, _ptr(status), _ptr(ws), ws.numel(),
+                                                        X6_TILE | X6_FLAGS | x_signed | flags, _ptr(status), _ptr(ws), ws.numel(),
                                                         _stream(Xc)),
                            "te_linear_relprop_x6_f32")
             if KERNEL_TIMER is None:
@@ -908,11 +938,12 @@ def attention_forward_planes_supported(qkv: Tensor, num_heads: int) -> bool:
             and bool(_lib.load().te_attention_forward_supported(N, 64)))
 
 
-def attention_forward(qkv: Tensor, num_heads: int, scale: float, planes: bool = False):
+def attention_forward(qkv: Tensor, num_heads: int, scale: float, planes: bool = False, planes_abs: bool = True):
     """qkv [B,N,3C] ('b n (qkv h d)') -> (out [B,N,C] = softmax(q k^T * scale) v as 'b n (h d)', attn [B,H,N,N],
     z_qk [B,H,N,N] = the unscaled q k^T).  ViT_LRP.py:132-152 without the q/k/v, scale, softmax and transpose passes.
     planes=True (attention_forward_planes_supported): additionally the signed planes of out [B N, C] and the planes of |out| --
-    what gemm_x6's split pass over out would build -- as a fourth and fifth result.
+    what gemm_x6's split pass over out would build -- as a fourth and fifth result (planes_abs=False: the second set is not
+    stored, the fifth result is None).
     A bf16 qkv (a bf16 model) runs on csrc/te_attn_bf16.hip and returns bf16 tensors; planes=True is fp32-only."""
     if _is_bf16(qkv):
         if planes:
@@ -933,11 +964,11 @@ def attention_forward(qkv: Tensor, num_heads: int, scale: float, planes: bool = 
     out = torch.empty((B, N, C), dtype=torch.float32, device=qkv.device)
     attn = torch.empty((B, H, N, N), dtype=torch.float32, device=qkv.device)
     zqk = torch.empty((B, H, N, N), dtype=torch.float32, device=qkv.device)
-    extra = 12.0 * B * N * C if planes else 0.0
+    extra = (12.0 if planes_abs else 6.0) * B * N * C if planes else 0.0
     with _on_device(qkv) as lib, _timed("attention_forward", 4.0 * B * H * N * N * D, 4.0 * B * (2 * H * N * N + 4 * N * C) + extra):
         if planes:
             nb = lib.te_linear_x6_planes_bytes(B * N, C)
-            xs, xa = _ws(nb, qkv), _ws(nb, qkv)
+            xs, xa = _ws(nb, qkv), _ws(nb, qkv) if planes_abs else None
             _lib.check(lib.te_attention_forward_planes_f32(_ptr(qkv), _ptr(zqk), _ptr(attn), _ptr(out), _ptr(xs), _ptr(xa), nb,
                                                            B, H, N, D, float(scale), _stream(qkv)),
                        "te_attention_forward_planes_f32")
@@ -1063,16 +1094,17 @@ def gelu_planes_supported(x: Tensor) -> bool:
     return bool(X6_FUSE_GELU and x.dim() >= 2 and x.shape[-1] >= 16 and x.shape[-1] % 16 == 0)
 
 
-def gelu_forward_planes(x: Tensor):
+def gelu_forward_planes(x: Tensor, planes_abs: bool = True):
     """y = gelu(x) (gelu_forward's bits) plus the signed planes of y and the planes of |y| -- what gemm_x6's split pass
-    over y would build (te_gelu_forward_x6_planes_f32).  Returns (y, planes, planes_abs)."""
+    over y would build (te_gelu_forward_x6_planes_f32).  Returns (y, planes, planes_abs); planes_abs=False: the second set is
+    not stored and comes back as None."""
     x = _c(x)
     K = x.shape[-1]
     T = x.numel() // K
     y = torch.empty_like(x)
-    with _on_device(x) as lib, _timed("gelu_forward", 0.0, (4.0 * 2 + 12.0) * x.numel()):
+    with _on_device(x) as lib, _timed("gelu_forward", 0.0, (4.0 * 2 + (12.0 if planes_abs else 6.0)) * x.numel()):
         nb = lib.te_linear_x6_planes_bytes(T, K)
-        xs, xa = _ws(nb, x), _ws(nb, x)
+        xs, xa = _ws(nb, x), _ws(nb, x) if planes_abs else None
         _lib.check(lib.te_gelu_forward_x6_planes_f32(_ptr(x), _ptr(y), T, K, _ptr(xs), _ptr(xa), nb, _stream(x)),
                    "te_gelu_forward_x6_planes_f32")
     return y, xs, xa

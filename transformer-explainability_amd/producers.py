@@ -71,7 +71,7 @@ class _Gelu(torch.autograd.Function):
         ctx.save_for_backward(x)
         ctx.source = source
         if feeds is not None:
-            y, xs, xa = ops.gelu_forward_planes(x)
+            y, xs, xa = ops.gelu_forward_planes(x, not ops.X6_SIGNED_PLANES)
             ops.post_x_planes(feeds, y, xs, xa)
             return y
         return ops.gelu_forward(x)
@@ -124,7 +124,8 @@ def linear_plan(x: torch.Tensor, lin):
 
 def takes_producer_planes(lin, T: int, K: int) -> bool:
     """Will `lin` (a rules.Linear) take the operand planes of a [T, K] fp32 device tensor from the tensor's producer: forward
-    product on gemm_x6 (linear_plan) AND rule on the x6 kernel that reads the planes of |X|?  The ONE answer the emitting
+    product on gemm_x6 (linear_plan) AND rule on the x6 kernel that reads the planes that product leaves (the signed ones, or --
+    ops.X6_SIGNED_PLANES off -- those of |X|)?  The ONE answer the emitting
     producers (gelu, vit.Attention) and the consumer (ops.gemm_x6) share -- DESIGN.md "The layer's scratch dict"."""
     out_f, in_f = lin.weight.shape
     return bool(K == in_f and ops.USE_FUSED_PRODUCERS and ops.X6_GEMM != "off" and not lin.training

@@ -197,7 +197,9 @@ def linear_rule(m, R, alpha, rows=None, variant=None):
     """The one route from a Linear layer `m` to ops.linear_relprop.  m.Y (the forward output, cached by forward_hook like
     the reference does) lets the kernel derive Z = X+ W+^T + X- W-^T from one product instead of two -- while it is what
     the forward pass wrote (_cached_y) and has X's rows.  rows: a selector applied to X and Y (``t[:, :1]``: the cls slice
-    of Block.relprop_cls_only / BertLayer.relprop_cls_only, which also pass the variant their other rules run under)."""
+    of Block.relprop_cls_only / BertLayer.relprop_cls_only, which also pass the variant their other rules run under).
+    The layer's scratch dict carries the operand planes its forward product left for this rule: the signed planes of X, which
+    ops.linear_relprop hands to the kernel with TE_X6_X_PLANES_SIGNED (or, ops.X6_SIGNED_PLANES off, the planes of |X|)."""
     X, Y = m.X, _cached_y(m)
     if Y is not None and Y.shape[:-1] != X.shape[:-1]:
         Y = None

@@ -140,7 +140,7 @@ class _FusedAttention(torch.autograd.Function):
         # feeds: the scratch dict of the projection layer if that layer takes the operand planes of `out` from this node
         # (producers.takes_producer_planes; DESIGN.md "The layer's scratch dict")
         if feeds is not None:
-            out, attn, zqk, xs, xa = ops.attention_forward(qkv, num_heads, scale, planes=True)
+            out, attn, zqk, xs, xa = ops.attention_forward(qkv, num_heads, scale, planes=True, planes_abs=not ops.X6_SIGNED_PLANES)
             ops.post_x_planes(feeds, out, xs, xa)
         else:
             out, attn, zqk = ops.attention_forward(qkv, num_heads, scale)
