@@ -123,7 +123,9 @@ def test_against_torch_on_cpu_224(heat_kind, labels_kind):
     compare(f"seg_metrics_{heat_kind}_{labels_kind}", run(heat, mask, labels), ref)
 
 
-@pytest.mark.parametrize("B,H,W", [(3, 30, 34), (2, 1, 1), (1, 224, 224)])
+# the seams of the sort's wave segments, in its 2*H*W elements: (16,32) 1024, the last size with one 64-element step per wave;
+# (19,27) 1026, the first with two (waves 9 .. 15 get an empty segment); (1,33) 66: wave 1 holds 2 elements, waves 2 .. 15 none
+@pytest.mark.parametrize("B,H,W", [(3, 30, 34), (2, 1, 1), (1, 224, 224), (2, 16, 32), (2, 19, 27), (1, 1, 33)])
 @pytest.mark.parametrize("heat_kind", ["distinct", "quantised"])
 def test_against_torch_on_cpu_shapes(heat_kind, B, H, W):
     heat, mask = make_heat(heat_kind, B, H, W, seed=5)

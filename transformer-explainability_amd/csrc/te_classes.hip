@@ -36,7 +36,7 @@ struct Logit<te_bf16_t> {
   typedef uint32_t Key;
   typedef float Rel;
   typedef f32x4 Vec;
-  static __device__ __forceinline__ Rel up(te_bf16_t v) { return __uint_as_float((unsigned)v << 16); }
+  static __device__ __forceinline__ Rel up(te_bf16_t v) { return te_bf16_up(v); }
   static __device__ __forceinline__ Key key(te_bf16_t v) { return te_key(up(v)); }
 };
 template <>

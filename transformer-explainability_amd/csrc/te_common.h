@@ -113,7 +113,12 @@ __device__ __forceinline__ double te_sd(double a, double b) {
   return q * ((b != 0.0) ? 1.0 : 0.0);
 }
 
-// order-preserving key of the radix select (te_perturb.hip) and the radix sort (te_segmetrics.hip):
+// The limits the evaluation kernels share: the values of one map (one per-sample sort; te_segmetrics.hip sorts two elements
+// per pixel), and the samples of one launch (a grid dimension)
+constexpr int64_t kTeMaxSortN = (int64_t)1 << 20;
+constexpr int64_t kTeMaxBatch = 65535;
+
+// order-preserving key of the radix selects (te_perturb.hip, te_localise.hip, te_classes.hip) and of the radix sort below:
 // a > b (as floats, -0 == +0, NaN largest as in torch.topk) <=> key(a) > key(b)
 __device__ __forceinline__ uint32_t te_key(float v) {
   uint32_t u = __float_as_uint(v);
@@ -126,8 +131,13 @@ __device__ __forceinline__ double te_wave_sum(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, TE_WAVE);
   return v;
 }
+__device__ __forceinline__ uint32_t te_wave_sum_u32(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, TE_WAVE);
+  return v;
+}
 
-// The radix sorts (te_segmetrics.hip, te_curves.hip, te_block_sort_passes below): the lanes of the wave that hold the same 8-bit digit as this lane, among the `live` ones
+// te_block_sort_passes below: the lanes of the wave that hold the same 8-bit digit as this lane, among the `live` ones
 __device__ __forceinline__ uint64_t match_digit(uint32_t digit, bool live) {
   uint64_t m = __ballot(live);
 #pragma unroll
@@ -156,23 +166,54 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* w
   return before + incl - v;
 }
 
-// The four stable 8-bit passes of the per-sample LSD radix sort (te_mapsim.hip, te_robust.hip), one workgroup of 1024 threads
-// = 16 waves: n elements `key << 32 | index` ascending by key, equal keys in index order.  The caller has built src[0 .. n)
-// and counted, in cnt[0][digit * 16 + j / S], the elements of every lowest digit in every wave segment of S = ceil(n / 1024)
-// * 64 positions, cnt[1] zeroed, a barrier behind it.  A pass turns the (digit, wave) counts into the start of each wave's
-// elements of each digit, ranks the lanes of a digit by ballots and counts the next digit at the destination; src and dst
-// swap after every pass, so on return src is the caller's first buffer again and holds the sorted elements, dst is idle.
-// tid, lane, wave and below = (1 << lane) - 1 are the caller's own values (it needs them before and after the passes).
+// The per-sample LSD radix sort of the evaluation kernels (te_mapsim.hip, te_robust.hip, te_curves.hip, te_segmetrics.hip),
+// one workgroup of 1024 threads = 16 waves per job: n <= 2 kTeMaxSortN 8-byte elements whose 32-bit key starts at bit KEY_BIT
+// (32 for `key << 32 | index`, 1 for te_segmetrics.hip's `key << 1 | truth`) come out ascending by key, equal keys in the
+// order of their positions.  Four stable passes of 8 bits, ping-pong between the job's two buffers in the workspace (L2).
+// Every wave owns a contiguous segment of S = ceil(n / 1024) * 64 source positions; a (digit, wave) table in LDS, scanned
+// digit-major, gives each wave its destination per digit, and inside a 64-element step the lanes of one digit are ranked by
+// ballots -- so every pass is stable.  The table of the next pass is counted while this pass scatters (integer LDS atomics:
+// the counts do not depend on the order of arrival).  A kernel keeps its own key construction and what it does with the
+// sorted elements, and writes
+//     __shared__ uint32_t cnt[2][kTeSortDigits * kTeSortWaves], wtot[kTeSortWaves];
+//     TeSortJob job = te_sort_begin(ws, j, n, cnt, tid);      job j of the launch: its buffers, S, the table zeroed
+//     __syncthreads();
+//     te_sort_put<KEY_BIT>(job, cnt, pos, element);           every position 0 .. n - 1 once, by whichever thread
+//     __syncthreads();
+//     te_block_sort_passes<KEY_BIT>(job, cnt, wtot, tid, lane, wave);
+// The buffers swap after every pass, so after four job.src, the job's first buffer, holds the sorted elements and job.dst
+// is idle.  A wave's segment is [wave S, min(wave S + S, n)) with no min() on its start: n <= 2^21 keeps wave S <=
+// 15 * 131072 far inside 32 bits, and a wave whose start is >= n gets the end n, runs no trip and reads nothing.
 constexpr int kTeSortThreads = 1024;
 constexpr int kTeSortWaves = kTeSortThreads / TE_WAVE;
 constexpr int kTeSortDigits = 256;
-__device__ __forceinline__ void te_block_sort_passes(uint64_t*& src, uint64_t*& dst, uint32_t n, uint32_t S,
-                                                     uint32_t (*cnt)[kTeSortDigits * kTeSortWaves], uint32_t* wtot,
-                                                     int tid, int lane, int wave, uint64_t below) {
+struct TeSortJob {
+  uint64_t *src, *dst;      // n elements each
+  uint32_t n, S;
+};
+__device__ __forceinline__ uint64_t* te_sort_buffers(uint64_t* ws, size_t j, uint32_t n) { return ws + j * 2 * (size_t)n; }
+__device__ __forceinline__ TeSortJob te_sort_begin(uint64_t* ws, size_t j, uint32_t n,
+                                                   uint32_t (*cnt)[kTeSortDigits * kTeSortWaves], int tid) {
+  for (int i = tid; i < 2 * kTeSortDigits * kTeSortWaves; i += kTeSortThreads) (&cnt[0][0])[i] = 0;
+  uint64_t* src = te_sort_buffers(ws, j, n);
+  return TeSortJob{src, src + n, n, (n + kTeSortThreads - 1) / kTeSortThreads * TE_WAVE};
+}
+template <int KEY_BIT>
+__device__ __forceinline__ void te_sort_put(const TeSortJob& job, uint32_t (*cnt)[kTeSortDigits * kTeSortWaves], uint32_t pos,
+                                            uint64_t e) {
+  job.src[pos] = e;
+  atomicAdd(&cnt[0][((uint32_t)(e >> KEY_BIT) & 0xffu) * kTeSortWaves + pos / job.S], 1u);
+}
+template <int KEY_BIT>
+__device__ __forceinline__ void te_block_sort_passes(const TeSortJob& job, uint32_t (*cnt)[kTeSortDigits * kTeSortWaves],
+                                                     uint32_t* wtot, int tid, int lane, int wave) {
+  uint64_t *src = job.src, *dst = job.dst;
+  const uint32_t n = job.n, S = job.S;
+  const uint64_t below = (1ull << lane) - 1;
   for (int pass = 0; pass < 4; ++pass) {
     volatile uint32_t* cur = cnt[pass & 1];
     uint32_t* nxt = cnt[(pass + 1) & 1];
-    const int shift = 32 + 8 * pass;
+    const int shift = KEY_BIT + 8 * pass;
     {                                              // (digit, wave) counts -> start of each wave's elements of each digit
       uint32_t v[4], sum = 0;
 #pragma unroll
@@ -215,7 +256,20 @@ __device__ __forceinline__ void te_block_sort_passes(uint64_t*& src, uint64_t*& 
   }
 }
 
-// Block-wide sum of up to 3 doubles; result valid in thread 0.  `smem` holds 3*(blockDim/64) doubles.
+// Block-wide sum of one double; result valid in thread 0.  `smem` holds blockDim/64 doubles.  The order of every fp64 sum of
+// the evaluation kernels: te_wave_sum's shuffle-down tree, then the waves in index order in thread 0.
+__device__ __forceinline__ void te_block_sum(double& a, double* smem) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  a = te_wave_sum(a);
+  if (lane == 0) smem[wave] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double sa = 0;
+    for (int w = 0; w < nw; ++w) sa += smem[w];
+    a = sa;
+  }
+}
+// ... and of up to 3 doubles, each in that order.  `smem` holds 3*(blockDim/64) doubles.
 __device__ __forceinline__ void te_block_sum3(double& a, double& b, double& c, double* smem) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   a = te_wave_sum(a);
@@ -257,9 +311,37 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
   }
 }
 
-// fp32 -> the bits of the nearest bf16, ties to even (te_robust.hip, te_faithful.hip)
-__device__ __forceinline__ uint16_t bf16_bits(float v) {      // to nearest even
-  return (uint16_t)(__builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{v, 0.0f}, bf16x2)) & 0xffffu);
+// bf16 outputs of the evaluation kernels: two fp32 -> the bits of their nearest bf16, ties to even (v_cvt_pk_bf16_f32), a in
+// the low half; and of one
+__device__ __forceinline__ uint32_t te_pack_bf16(float a, float b) {
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
+}
+__device__ __forceinline__ uint16_t bf16_bits(float v) { return (uint16_t)(te_pack_bf16(v, 0.0f) & 0xffffu); }
+
+// fp32 / bf16 operands of the fp64 sums (map_distance, perturbation_dot, curve_scores): element i by its exact upcast ...
+__device__ __forceinline__ float te_bf16_up(te_bf16_t v) { return __uint_as_float((uint32_t)v << 16); }
+__device__ __forceinline__ double te_load_f64(const float* p, int64_t i) { return (double)p[i]; }
+__device__ __forceinline__ double te_load_f64(const te_bf16_t* p, int64_t i) { return (double)te_bf16_up(p[i]); }
+// ... and the group of four consecutive elements e0 .. e0 + 3 of p[0 .. n).  VEC: one 16-byte (fp32) or 8-byte (bf16) access
+// -- the group lies inside the row and on that boundary; otherwise element by element, 0.0 for an element past the end.  The
+// values and their order are the same either way, so a sum over them has the same bits.
+template <bool VEC, typename T, typename I>
+__device__ __forceinline__ void te_load4_f64(const T* __restrict__ p, I e0, I n, double (&v)[4]) {
+  if constexpr (!VEC) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (e0 + j < n) ? te_load_f64(p, e0 + j) : 0.0;
+  } else if constexpr (std::is_same<T, float>::value) {
+    const f32x4 q = *reinterpret_cast<const f32x4*>(p + e0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (double)q[j];
+  } else {
+    const u32x2 q = *reinterpret_cast<const u32x2*>(p + e0);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {                  // element 2j in the low half
+      v[2 * j] = (double)__uint_as_float(q[j] << 16);
+      v[2 * j + 1] = (double)__uint_as_float(q[j] & 0xffff0000u);
+    }
+  }
 }
 
 // Patch geometry of a stride == kernel convolution (ViT patch embedding): row t = (b, py, px) of the im2col matrix,
@@ -279,3 +361,32 @@ __host__ __device__ __forceinline__ int64_t te_zb_index(const TeZbGeom& g, int64
 static inline bool te_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 static inline int64_t te_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t te_align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
+
+// the workspace of `jobs` sorts of n elements (te_sort_begin): two buffers of n 8-byte elements each
+static inline size_t te_sort_workspace_bytes(size_t jobs, size_t n) { return te_align_up(jobs * 2 * n * sizeof(uint64_t), 256); }
+
+// The per-channel constants of the kernels that write model inputs (te_perturb.hip, te_curves.hip, te_faithful.hip), passed
+// by value: normalisation z = (x - mean[c]) / std[c] and the substrate's constant fill[c]; a null array gives 0 / 1 / 0.  A
+// kernel reads the members it needs: the others cost nothing but bytes of its argument block.
+struct TeChannels {
+  float mean[TE_PERTURB_MAX_CHANNELS], std[TE_PERTURB_MAX_CHANNELS], fill[TE_PERTURB_MAX_CHANNELS];
+};
+static inline TeChannels te_channels(int64_t C, const float* mean, const float* std_, const float* fill) {
+  TeChannels ch;
+  for (int c = 0; c < TE_PERTURB_MAX_CHANNELS; ++c) {
+    ch.mean[c] = (mean && c < C) ? mean[c] : 0.0f;
+    ch.std[c] = (std_ && c < C) ? std_[c] : 1.0f;
+    ch.fill[c] = (fill && c < C) ? fill[c] : 0.0f;
+  }
+  return ch;
+}
+
+// The launch shape of the kernels that write n_d random copies of every sample (te_robust.hip, te_faithful.hip): all draws
+// of the call inside one thread once the `blocks` = B * bx workgroups of one draw fill the chip (256 CUs x 4 resident
+// blocks), else one draw per workgroup -- more where the grid's z would pass 65535.  -> draws per workgroup, *grid_z
+static inline int64_t te_draws_per_block(int64_t blocks, int64_t n_d, unsigned* grid_z) {
+  int64_t dpg = (blocks >= 1024) ? n_d : 1;
+  if (te_ceil_div(n_d, dpg) > 65535) dpg = te_ceil_div(n_d, 65535);
+  *grid_z = (unsigned)te_ceil_div(n_d, dpg);
+  return dpg;
+}

@@ -8,7 +8,7 @@
 //             Every output runs the same klen + klen FMAs in tap order whatever tile it falls in: its bits do not depend on
 //             tiling, batch or grid.  LDS: (32 + 2r)(32 + 2 r4) + (32 + 2r) 32 floats, r4 = r rounded up to 4 -- 13.1 KiB at
 //             klen = 11 (occupancy is then bound by the 32 waves of a CU: 8 workgroups of 256), 47 KiB at klen = 63 (3 per CU).
-//   rank    : the LSD radix sort of te_mapsim.hip / te_segmetrics.hip on the COMPLEMENTED key: a stable ascending sort of
+//   rank    : the per-sample LSD radix sort of te_common.h on the COMPLEMENTED key: a stable ascending sort of
 //             ~te_key(v) << 32 | index is descending by value with ties in index order; every element then writes its
 //             sorted position to its original index.
 //   compose : store-bound.  A thread owns 8 consecutive pixels (4 for fp32 output), reads rank, image and substrate once
@@ -20,17 +20,12 @@
 
 namespace {
 
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / TE_WAVE;
-constexpr int kDigits = 256;
-constexpr int64_t kMaxN = (int64_t)1 << 20;
-constexpr int64_t kMaxBatch = 65535;
+constexpr int kThreads = kTeSortThreads;           // rank
+constexpr int kWaves = kTeSortWaves;
+constexpr int kDigits = kTeSortDigits;
 constexpr int kMaxC = TE_PERTURB_MAX_CHANNELS;
 constexpr int kTile = 32;                          // blur: outputs per tile side
 
-struct Norm {
-  float mean[kMaxC], std[kMaxC], fill[kMaxC];
-};
 struct Taps {
   float t[TE_BLUR_MAX_TAPS];
 };
@@ -39,7 +34,7 @@ struct Taps {
 // VEC: 16-byte global accesses (W % 4 == 0, aligned bases); otherwise element-wise.  LDS: in[rows][inw], then hz[rows][kTile]
 template <bool VEC>
 __global__ __launch_bounds__(256) void blur_kernel(const float* __restrict__ data, float* __restrict__ out, int C, int H,
-                                                   int W, int tiles_x, int tiles_y, int klen, Taps taps, Norm nm) {
+                                                   int W, int tiles_x, int tiles_y, int klen, Taps taps, TeChannels nm) {
   extern __shared__ float lds[];
   const int r = klen / 2, r4 = (r + 3) & ~3;
   const int rows = kTile + 2 * r, inw = kTile + 2 * r4;
@@ -119,70 +114,18 @@ __global__ __launch_bounds__(kThreads) void pixel_rank_kernel(const float* __res
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t sample = blockIdx.x;
   const float* x = vis + (size_t)sample * n;
-  const uint32_t S = (n + kThreads - 1) / kThreads * TE_WAVE;      // elements per wave segment, a multiple of 64
-  const uint64_t below = (1ull << lane) - 1;
-  uint64_t* src = ws + (size_t)sample * 2 * (size_t)n;
-  uint64_t* dst = src + n;
-
-  for (int i = tid; i < 2 * kDigits * kWaves; i += kThreads) (&cnt[0][0])[i] = 0;
+  const TeSortJob job = te_sort_begin(ws, (size_t)sample, n, cnt, tid);
   __syncthreads();
 
   // ---- build: the complemented key, so that ascending is descending by value
-  for (uint32_t j = tid; j < n; j += kThreads) {
-    const uint32_t key = ~te_key(x[j]);
-    src[j] = ((uint64_t)key << 32) | j;
-    atomicAdd(&cnt[0][(key & 0xffu) * kWaves + j / S], 1u);
-  }
+  for (uint32_t j = tid; j < n; j += kThreads) te_sort_put<32>(job, cnt, j, ((uint64_t)~te_key(x[j]) << 32) | j);
   __syncthreads();
 
   // ---- sort (ascending, stable: equal keys stay in index order)
-  for (int pass = 0; pass < 4; ++pass) {
-    volatile uint32_t* cur = cnt[pass & 1];
-    uint32_t* nxt = cnt[(pass + 1) & 1];
-    const int shift = 32 + 8 * pass;
-    {                                              // (digit, wave) counts -> start of each wave's elements of each digit
-      uint32_t v[4], sum = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        v[k] = cur[4 * tid + k];
-        sum += v[k];
-      }
-      uint32_t off = block_exclusive_scan(sum, wtot);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        cur[4 * tid + k] = off;
-        off += v[k];
-      }
-      for (int k = 0; k < 4; ++k) nxt[4 * tid + k] = 0;
-    }
-    __syncthreads();
-    const uint32_t seg0 = min((uint32_t)wave * S, n), seg1 = min(seg0 + S, n);
-    uint32_t idx = seg0 + lane;
-    uint64_t e_next = idx < seg1 ? src[idx] : 0ull;
-    for (uint32_t base = seg0; base < seg1; base += TE_WAVE) {
-      const uint64_t e = e_next;
-      const bool live = idx < seg1;
-      idx += TE_WAVE;
-      e_next = idx < seg1 ? src[idx] : 0ull;
-      const uint32_t digit = (uint32_t)(e >> shift) & 0xffu;
-      const uint64_t m = match_digit(digit, live);
-      const uint32_t before = (uint32_t)__popcll(m & below), same = (uint32_t)__popcll(m);
-      if (live) {
-        const uint32_t at = cur[digit * kWaves + wave];
-        const uint32_t pos = at + before;
-        dst[pos] = e;
-        if (before == same - 1) cur[digit * kWaves + wave] = at + same;      // after every lane of the digit has read it
-        if (pass < 3) atomicAdd(&nxt[((uint32_t)(e >> (shift + 8)) & 0xffu) * kWaves + pos / S], 1u);
-      }
-    }
-    __syncthreads();
-    uint64_t* t = src;
-    src = dst;
-    dst = t;
-  }
+  te_block_sort_passes<32>(job, cnt, wtot, tid, lane, wave);
 
-  // ---- after four passes src is the sample's first buffer again: position j holds the j-th most relevant pixel
-  for (uint32_t j = tid; j < n; j += kThreads) rank[(size_t)sample * n + (uint32_t)src[j]] = (int32_t)j;
+  // ---- position j of the sorted elements holds the j-th most relevant pixel
+  for (uint32_t j = tid; j < n; j += kThreads) rank[(size_t)sample * n + (uint32_t)job.src[j]] = (int32_t)j;
 }
 
 // ------------------------------------------------------------------------------------------------ compose
@@ -193,7 +136,7 @@ template <typename OutT, int VEC>
 __global__ __launch_bounds__(256) void curve_inputs_kernel(const float* __restrict__ data, const float* __restrict__ substrate,
                                                            const int32_t* __restrict__ rank, OutT* __restrict__ out, int64_t B,
                                                            int64_t C, int64_t HW, uint32_t step, int s0, int n_s, int spg,
-                                                           int insertion, Norm nm) {
+                                                           int insertion, TeChannels nm) {
   const int64_t b = blockIdx.y;
   const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * VEC;
   if (i0 >= HW) return;
@@ -252,11 +195,10 @@ __global__ __launch_bounds__(256) void curve_inputs_kernel(const float* __restri
         if constexpr (VEC == 8) {
           u32x4 p;
 #pragma unroll
-          for (int j = 0; j < 4; ++j)            // y[2j] in the low half
-            p[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{y[2 * j], y[2 * j + 1]}, bf16x2));
+          for (int j = 0; j < 4; ++j) p[j] = te_pack_bf16(y[2 * j], y[2 * j + 1]);
           __builtin_nontemporal_store(p, reinterpret_cast<u32x4*>(dst));
         } else {
-          dst[0] = (te_bf16_t)(__builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{y[0], 0.0f}, bf16x2)) & 0xffffu);
+          dst[0] = bf16_bits(y[0]);
         }
       }
     }
@@ -264,11 +206,6 @@ __global__ __launch_bounds__(256) void curve_inputs_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ scores
-__device__ __forceinline__ double curve_logit(const float* p, int64_t i) { return (double)p[i]; }
-__device__ __forceinline__ double curve_logit(const te_bf16_t* p, int64_t i) {
-  return (double)__uint_as_float((uint32_t)p[i] << 16);
-}
-
 // one wave per row of logits [rows, K]: prob[s0 + row / B][row % B] = softmax(row)[target[row % B]] in fp64.  Lane l takes the
 // classes l, l + 64, ... in order; the 64 partial sums meet in te_wave_sum: an order fixed by K alone.
 template <typename T>
@@ -282,15 +219,15 @@ __global__ __launch_bounds__(256) void curve_scores_kernel(const T* __restrict__
   const int64_t b = row % B;
   const int64_t t = target[b];
   double m = -__builtin_huge_val();
-  for (int64_t k = lane; k < K; k += TE_WAVE) m = fmax(m, curve_logit(x, k));
+  for (int64_t k = lane; k < K; k += TE_WAVE) m = fmax(m, te_load_f64(x, k));
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, TE_WAVE));
   double sum = 0.0;
-  for (int64_t k = lane; k < K; k += TE_WAVE) sum += exp(curve_logit(x, k) - m);
+  for (int64_t k = lane; k < K; k += TE_WAVE) sum += exp(te_load_f64(x, k) - m);
   sum = te_wave_sum(sum);
   if (lane == 0) {
     double p = __longlong_as_double(0x7ff8000000000000ll);      // a target outside [0, K): NaN
-    if (t >= 0 && t < K) p = exp(curve_logit(x, t) - m) / sum;
+    if (t >= 0 && t < K) p = exp(te_load_f64(x, t) - m) / sum;
     prob[(s0 + row / B) * B + b] = p;
   }
 }
@@ -307,14 +244,6 @@ __global__ __launch_bounds__(256) void curve_auc_kernel(const double* __restrict
   auc[b] = sum / (double)(S1 - 1);
 }
 
-void fill_norm(Norm* nm, int64_t C, const float* mean, const float* std_, const float* fill) {
-  for (int c = 0; c < kMaxC; ++c) {
-    nm->mean[c] = (mean && c < C) ? mean[c] : 0.0f;
-    nm->std[c] = (std_ && c < C) ? std_[c] : 1.0f;
-    nm->fill[c] = (fill && c < C) ? fill[c] : 0.0f;
-  }
-}
-
 template <typename OutT>
 int curve_inputs(const float* data, const float* substrate, const float* fill, const int32_t* rank, OutT* out, int64_t B,
                  int64_t C, int64_t HW, int64_t step, int64_t s0, int64_t n_s, int insertion, const float* mean,
@@ -322,11 +251,10 @@ int curve_inputs(const float* data, const float* substrate, const float* fill, c
   if (!data || !rank || !out || (!substrate && !fill) || B <= 0 || C <= 0 || HW <= 0 || step < 1 || s0 < 0 || n_s < 1 ||
       (insertion != 0 && insertion != 1))
     return TE_ERR_INVALID_ARG;
-  if (B > kMaxBatch || C > kMaxC || HW > kMaxN) return TE_ERR_UNSUPPORTED;
+  if (B > kTeMaxBatch || C > kMaxC || HW > kTeMaxSortN) return TE_ERR_UNSUPPORTED;
   const int64_t S = te_ceil_div(HW, step);
   if (s0 > S || n_s > S + 1 - s0) return TE_ERR_INVALID_ARG;      // images s0 .. s0 + n_s - 1 of the S + 1
-  Norm nm;
-  fill_norm(&nm, C, mean, std_, fill);
+  const TeChannels nm = te_channels(C, mean, std_, fill);
   constexpr int V = std::is_same<OutT, float>::value ? 4 : 8;
   // 16-B accesses: a row of the output starts on a 16-B boundary when HW % V == 0; anything else, and unaligned bases, take
   // the element-wise form
@@ -337,7 +265,7 @@ int curve_inputs(const float* data, const float* substrate, const float* fill, c
   const int spg = (bx * B >= 1024) ? (int)n_s : 1;
   const dim3 grid((unsigned)bx, (unsigned)B, (unsigned)te_ceil_div(n_s, spg));
   if (grid.z > 65535u) return TE_ERR_UNSUPPORTED;
-  const uint32_t st = (uint32_t)(step > kMaxN ? kMaxN : step);      // step >= HW: S = 1 whatever the value
+  const uint32_t st = (uint32_t)(step > kTeMaxSortN ? kTeMaxSortN : step);      // step >= HW: S = 1 whatever the value
   if (vec)
     curve_inputs_kernel<OutT, V><<<grid, dim3(256), 0, stream>>>(data, substrate, rank, out, B, C, HW, st, (int)s0, (int)n_s,
                                                                   spg, insertion, nm);
@@ -352,7 +280,7 @@ template <typename T>
 int curve_scores(const T* logits, const int64_t* target, double* prob, int64_t B, int64_t K, int64_t s0, int64_t n_s,
                  hipStream_t stream) {
   if (!logits || !target || !prob || B <= 0 || K <= 0 || s0 < 0 || n_s < 1) return TE_ERR_INVALID_ARG;
-  if (B > kMaxBatch || s0 > kMaxN || n_s > kMaxN + 1) return TE_ERR_UNSUPPORTED;      // S <= HW <= 2^20
+  if (B > kTeMaxBatch || s0 > kTeMaxSortN || n_s > kTeMaxSortN + 1) return TE_ERR_UNSUPPORTED;      // S <= HW <= 2^20
   const int64_t rows = n_s * B;
   curve_scores_kernel<T><<<dim3((unsigned)te_ceil_div(rows, 4)), dim3(256), 0, stream>>>(logits, target, prob, B, K, s0, rows);
   TE_RETURN_IF_LAUNCH_FAILED();
@@ -365,10 +293,9 @@ extern "C" int te_blur_normalised_f32(const float* data, float* out, int64_t B, 
                                       const float* taps, int64_t klen, const float* mean, const float* std_,
                                       te_stream_t stream) {
   if (!data || !out || !taps || B <= 0 || C <= 0 || H <= 0 || W <= 0 || klen < 1 || klen % 2 == 0) return TE_ERR_INVALID_ARG;
-  if (klen > TE_BLUR_MAX_TAPS || B > kMaxBatch || C > kMaxC || H > kMaxN || W > kMaxN || H * W > kMaxN)
+  if (klen > TE_BLUR_MAX_TAPS || B > kTeMaxBatch || C > kMaxC || H > kTeMaxSortN || W > kTeMaxSortN || H * W > kTeMaxSortN)
     return TE_ERR_UNSUPPORTED;
-  Norm nm;
-  fill_norm(&nm, C, mean, std_, nullptr);
+  const TeChannels nm = te_channels(C, mean, std_, nullptr);
   Taps tp;
   for (int j = 0; j < TE_BLUR_MAX_TAPS; ++j) tp.t[j] = j < klen ? taps[j] : 0.0f;
   const int tiles_x = (int)te_ceil_div(W, kTile), tiles_y = (int)te_ceil_div(H, kTile);
@@ -388,14 +315,14 @@ extern "C" int te_blur_normalised_f32(const float* data, float* out, int64_t B, 
 }
 
 extern "C" size_t te_pixel_rank_workspace_bytes(int64_t B, int64_t n) {
-  if (B <= 0 || n <= 0 || B > kMaxBatch || n > kMaxN) return 0;
-  return te_align_up((size_t)B * 2 * (size_t)n * sizeof(uint64_t), 256);      // per sample two buffers of n 8-byte elements
+  if (B <= 0 || n <= 0 || B > kTeMaxBatch || n > kTeMaxSortN) return 0;
+  return te_sort_workspace_bytes((size_t)B, (size_t)n);
 }
 
 extern "C" int te_pixel_rank_f32(const float* vis, int32_t* rank, int64_t B, int64_t n, void* ws, size_t ws_bytes,
                                  te_stream_t stream) {
   if (!vis || !rank || B <= 0 || n <= 0) return TE_ERR_INVALID_ARG;
-  if (B > kMaxBatch || n > kMaxN) return TE_ERR_UNSUPPORTED;
+  if (B > kTeMaxBatch || n > kTeMaxSortN) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_pixel_rank_workspace_bytes(B, n)) return TE_ERR_WORKSPACE;
   if (((uintptr_t)ws) & 7u) return TE_ERR_INVALID_ARG;
   pixel_rank_kernel<<<dim3((unsigned)B), dim3(kThreads), 0, (hipStream_t)stream>>>(vis, rank, (uint32_t)n, (uint64_t*)ws);
@@ -429,7 +356,7 @@ extern "C" int te_curve_scores_bf16(const te_bf16_t* logits, const int64_t* targ
 
 extern "C" int te_curve_auc_f64(const double* prob, double* auc, int64_t S1, int64_t B, te_stream_t stream) {
   if (!prob || !auc || B <= 0 || S1 < 2) return TE_ERR_INVALID_ARG;
-  if (B > kMaxBatch || S1 > kMaxN + 1) return TE_ERR_UNSUPPORTED;
+  if (B > kTeMaxBatch || S1 > kTeMaxSortN + 1) return TE_ERR_UNSUPPORTED;
   curve_auc_kernel<<<dim3((unsigned)te_ceil_div(B, 256)), dim3(256), 0, (hipStream_t)stream>>>(prob, auc, S1, B);
   TE_RETURN_IF_LAUNCH_FAILED();
   return TE_OK;

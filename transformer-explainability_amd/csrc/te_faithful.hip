@@ -8,7 +8,7 @@
 //   select  : one workgroup of 256 per (sample, draw).  The G <= 4096 keys `philox word << 32 | cell` go to LDS (one Philox
 //             call per four cells); a thread then ranks its cells t, t + 256, ... by counting the smaller keys (every lane
 //             reads the same LDS address: a broadcast) and writes member = rank < k.  attr_sum: the thread's own cells in
-//             order, then te_block_sum3 -- an order fixed by G alone.
+//             order, then te_block_sum -- an order fixed by G alone.
 //   compose : store-shaped, the form of noise_inputs_kernel.  A thread owns 4 (fp32 output) or 8 (bf16) consecutive elements
 //             of one sample -- one cell when p is a multiple of that --, reads x and the substrate once and walks the draws
 //             of its block: one member byte and one 16-byte non-temporal store per draw.  Element-wise otherwise.
@@ -20,13 +20,8 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int64_t kMaxCells = TE_SUBSET_MAX_CELLS;
-constexpr int64_t kMaxBatch = 65535;
 constexpr int64_t kMaxInt = 0x7fffffff;
 constexpr int kMaxC = TE_PERTURB_MAX_CHANNELS;
-
-struct Fill {
-  float v[kMaxC];
-};
 
 // ------------------------------------------------------------------------------------------------ select
 // member[b][j][c] = (the rank of key_c among the G keys of draw d0 + j of sample id0 + b) < k;
@@ -49,7 +44,7 @@ __global__ __launch_bounds__(kThreads) void subset_select_kernel(const float* __
   }
   __syncthreads();
   uint8_t* mrow = member + (b * n_d + j) * (int64_t)G;
-  double s = 0.0, unused = 0.0, unused2 = 0.0;
+  double s = 0.0;
   for (uint32_t cell = tid; cell < G; cell += kThreads) {
     const uint64_t key = keys[cell];
     uint32_t rank = 0;
@@ -59,7 +54,7 @@ __global__ __launch_bounds__(kThreads) void subset_select_kernel(const float* __
     if (attr != nullptr && in) s += (double)attr[b * (int64_t)G + cell];
   }
   if (attr != nullptr) {                             // (uniform: the barrier inside is reached by all or by none)
-    te_block_sum3(s, unused, unused2, red);
+    te_block_sum(s, red);
     if (tid == 0) attr_sum[b * n_d + j] = s;
   }
 }
@@ -71,14 +66,14 @@ template <typename OutT, int VEC>
 __global__ __launch_bounds__(256) void subset_inputs_kernel(const float* __restrict__ x, const float* __restrict__ substrate,
                                                             const uint8_t* __restrict__ member, OutT* __restrict__ out,
                                                             uint32_t n, uint32_t HW, uint32_t W, uint32_t p, uint32_t g_w,
-                                                            uint32_t G, int64_t n_d, int dpg, Fill fill) {
+                                                            uint32_t G, int64_t n_d, int dpg, TeChannels ch) {
   const int64_t b = blockIdx.y;
   const int64_t e0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * VEC;
   if (e0 >= (int64_t)n) return;
-  const uint32_t e = (uint32_t)e0, ch = e / HW, pix = e - ch * HW, row = pix / W, col = pix - row * W;
+  const uint32_t e = (uint32_t)e0, c = e / HW, pix = e - c * HW, row = pix / W, col = pix - row * W;
   const uint32_t cell = (row / p) * g_w + col / p;   // (VEC > 1: p % VEC == 0, the thread's elements share the cell)
   const float* src = x + b * (int64_t)n + e0;
-  const float fv = substrate ? 0.0f : fill.v[ch];    // (constants: C <= kMaxC; with a tensor ch may be larger and is not used)
+  const float fv = substrate ? 0.0f : ch.fill[c];    // (constants: C <= kMaxC; with a tensor c may be larger and is not used)
   float xv[VEC], sv[VEC];
   if constexpr (VEC == 1) {
     xv[0] = src[0];
@@ -112,8 +107,7 @@ __global__ __launch_bounds__(256) void subset_inputs_kernel(const float* __restr
       if constexpr (VEC == 8) {
         u32x4 pk;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)                // y[2i] in the low half
-          pk[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{y[2 * i], y[2 * i + 1]}, bf16x2));
+        for (int i = 0; i < 4; ++i) pk[i] = te_pack_bf16(y[2 * i], y[2 * i + 1]);
         __builtin_nontemporal_store(pk, reinterpret_cast<u32x4*>(dst));
       } else {
         dst[0] = bf16_bits(y[0]);
@@ -131,7 +125,7 @@ int subset_inputs(const float* x, const float* substrate, const float* fill, con
     return TE_ERR_INVALID_ARG;
   if (d0 > ((int64_t)1 << 32) || n_d > ((int64_t)1 << 32) - d0) return TE_ERR_INVALID_ARG;      // draws are 32-bit counters
   if (g_h <= kMaxCells && g_w <= kMaxCells && k > g_h * g_w) return TE_ERR_INVALID_ARG;
-  if (g_h > kMaxCells || g_w > kMaxCells || g_h * g_w > kMaxCells || B > kMaxBatch || n_d > kMaxInt) return TE_ERR_UNSUPPORTED;
+  if (g_h > kMaxCells || g_w > kMaxCells || g_h * g_w > kMaxCells || B > kTeMaxBatch || n_d > kMaxInt) return TE_ERR_UNSUPPORTED;
   const int64_t G = g_h * g_w;
   if (p > kMaxInt || p * p > kMaxInt || C > kMaxInt || G * p * p > kMaxInt || C * G * p * p > kMaxInt)
     return TE_ERR_UNSUPPORTED;                       // (every product is formed after its factors are known to be small)
@@ -141,15 +135,13 @@ int subset_inputs(const float* x, const float* substrate, const float* fill, con
   subset_select_kernel<<<dim3((unsigned)n_d, (unsigned)B), dim3(kThreads), 0, stream>>>(
       attr, member, attr_sum, (uint32_t)G, (uint32_t)k, (uint32_t)d0, n_d, (uint32_t)key, (uint32_t)(key >> 32), (uint64_t)id0);
   TE_RETURN_IF_LAUNCH_FAILED();
-  Fill f;
-  for (int c = 0; c < kMaxC; ++c) f.v[c] = (fill && c < C) ? fill[c] : 0.0f;
+  const TeChannels f = te_channels(C, nullptr, nullptr, fill);
   constexpr int V = std::is_same<OutT, float>::value ? 4 : 8;
   const bool vec = (p % V == 0) && te_aligned16(x) && te_aligned16(out) && (!substrate || te_aligned16(substrate));
   const int64_t bx = te_ceil_div(vec ? n / V : n, 256);
-  // all draws of the call inside one thread once B * bx blocks fill the chip (256 CUs x 4 resident blocks); else one per block
-  int64_t dpg = (bx * B >= 1024) ? n_d : 1;
-  if (te_ceil_div(n_d, dpg) > 65535) dpg = te_ceil_div(n_d, 65535);
-  const dim3 grid((unsigned)bx, (unsigned)B, (unsigned)te_ceil_div(n_d, dpg));
+  unsigned gz;
+  const int64_t dpg = te_draws_per_block(bx * B, n_d, &gz);      // (<= n_d <= kMaxInt)
+  const dim3 grid((unsigned)bx, (unsigned)B, gz);
   if (vec)
     subset_inputs_kernel<OutT, V><<<grid, dim3(256), 0, stream>>>(x, substrate, member, out, (uint32_t)n, (uint32_t)HW,
                                                                   (uint32_t)W, (uint32_t)p, (uint32_t)g_w, (uint32_t)G, n_d,
@@ -163,11 +155,6 @@ int subset_inputs(const float* x, const float* substrate, const float* fill, con
 }
 
 // ------------------------------------------------------------------------------------------------ dot
-__device__ __forceinline__ double dot_value(const float* p, int64_t i) { return (double)p[i]; }
-__device__ __forceinline__ double dot_value(const te_bf16_t* p, int64_t i) {
-  return (double)__uint_as_float((uint32_t)p[i] << 16);
-}
-
 // sums[b][d] = (sum (x - y) w[e mod m], sum (x - y)^2) over the n elements of x[b] and y = yy[b][d].  Thread t takes the groups
 // of four elements t, t + 256, ... and the elements of a group in order: VEC only changes how they are loaded (VEC: m % 4 ==
 // 0, so that a group's weights are consecutive).
@@ -185,34 +172,13 @@ __global__ __launch_bounds__(kThreads) void perturbation_dot_kernel(const float*
   const uint32_t wstep = (kThreads * 4u) % m;
   for (uint32_t e0 = threadIdx.x * 4u; e0 < n; e0 += kThreads * 4u) {
     double va[4], vb[4], vw[4];
+    te_load4_f64<VEC>(xa, e0, n, va);              // (n <= 2^31 - 1 and e0 < n: e0 + 3 does not wrap)
+    te_load4_f64<VEC>(yb, e0, n, vb);
     if constexpr (VEC) {
-      const f32x4 pa = *reinterpret_cast<const f32x4*>(xa + e0);
-      const f32x4 pw = *reinterpret_cast<const f32x4*>(wb + wi);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        va[j] = (double)pa[j];
-        vw[j] = (double)pw[j];
-      }
-      if constexpr (std::is_same<T, float>::value) {
-        const f32x4 pb = *reinterpret_cast<const f32x4*>(yb + e0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) vb[j] = (double)pb[j];
-      } else {
-        const u32x2 pb = *reinterpret_cast<const u32x2*>(yb + e0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {              // element 2j in the low half
-          vb[2 * j] = (double)__uint_as_float(pb[j] << 16);
-          vb[2 * j + 1] = (double)__uint_as_float(pb[j] & 0xffff0000u);
-        }
-      }
+      te_load4_f64<true>(wb, wi, m, vw);
     } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool in = e0 + j < n;                // (n <= 2^31 - 1 and e0 < n: no wrap)
-        va[j] = in ? (double)xa[e0 + j] : 0.0;
-        vb[j] = in ? dot_value(yb, e0 + j) : 0.0;
-        vw[j] = in ? (double)wb[(wi + j) % m] : 0.0;
-      }
+      for (int j = 0; j < 4; ++j) vw[j] = (e0 + j < n) ? (double)wb[(wi + j) % m] : 0.0;
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -235,7 +201,7 @@ template <typename T>
 int perturbation_dot(const float* x, const T* y, const float* w, double* sums, int64_t B, int64_t D, int64_t n, int64_t m,
                      hipStream_t stream) {
   if (!x || !y || !w || !sums || B <= 0 || D <= 0 || n <= 0 || m <= 0 || n % m != 0) return TE_ERR_INVALID_ARG;
-  if (B > kMaxBatch || D > kMaxInt || n > kMaxInt) return TE_ERR_UNSUPPORTED;
+  if (B > kTeMaxBatch || D > kMaxInt || n > kMaxInt) return TE_ERR_UNSUPPORTED;
   const bool vec = (n % 4 == 0) && (m % 4 == 0) && te_aligned16(x) && te_aligned16(y) && te_aligned16(w);
   const dim3 grid((unsigned)D, (unsigned)B);
   if (vec)

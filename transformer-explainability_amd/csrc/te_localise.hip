@@ -28,8 +28,6 @@ namespace {
 
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / TE_WAVE;
-constexpr int64_t kMaxPixels = (int64_t)1 << 20;
-constexpr int64_t kMaxPairs = 65535;
 constexpr int64_t kMaxBoxes = 64;
 constexpr int kBatch = 8;                          // trips of a loop whose loads are issued together: the loops are latency-bound
 
@@ -49,12 +47,6 @@ __device__ __forceinline__ void hist_add(uint32_t* hist, uint32_t digit, bool li
   const uint64_t same = __ballot(live && digit == d0);
   if (lane == first) atomicAdd(&hist[d0], (uint32_t)__popcll(same));
   if (live && digit != d0) atomicAdd(&hist[digit], 1u);
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, TE_WAVE);
-  return v;
 }
 
 __global__ __launch_bounds__(kThreads) void localisation_kernel(const float* __restrict__ heat,
@@ -157,8 +149,8 @@ __global__ __launch_bounds__(kThreads) void localisation_kernel(const float* __r
       hist_add(hist, key >> 24, valid, lane);
     }
   }
-  nv = wave_sum_u32(nv);
-  nt = wave_sum_u32(nt);
+  nv = te_wave_sum_u32(nv);
+  nt = te_wave_sum_u32(nt);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const unsigned long long o = __shfl_down(best, off, TE_WAVE);
@@ -297,7 +289,7 @@ __global__ __launch_bounds__(kThreads) void localisation_kernel(const float* __r
 #pragma unroll
         for (int u = 0; u < kBatch; ++u) ties += kv[u] == thr ? 1u : 0u;
       }
-      ties = wave_sum_u32(ties);
+      ties = te_wave_sum_u32(ties);
       if (lane == 0) wave_ties[wave] = ties;
       __syncthreads();
       for (int w = 0; w < wave; ++w) before += wave_ties[w];
@@ -321,7 +313,7 @@ __global__ __launch_bounds__(kThreads) void localisation_kernel(const float* __r
         before += (uint32_t)__popcll(tb);
       }
     }
-    mine = wave_sum_u32(mine);
+    mine = te_wave_sum_u32(mine);
     if (lane == 0) atomicAdd(&hits, mine);
   }
   __syncthreads();
@@ -342,7 +334,7 @@ __global__ __launch_bounds__(kThreads) void localisation_kernel(const float* __r
 }  // namespace
 
 extern "C" size_t te_localisation_workspace_bytes(int64_t P, int64_t H, int64_t W) {
-  if (P <= 0 || H <= 0 || W <= 0 || P > kMaxPairs || H > kMaxPixels || W > kMaxPixels || H * W > kMaxPixels) return 0;
+  if (P <= 0 || H <= 0 || W <= 0 || P > kTeMaxBatch || H > kTeMaxSortN || W > kTeMaxSortN || H * W > kTeMaxSortN) return 0;
   return te_align_up((size_t)P * pair_ws_words((uint32_t)(H * W)) * sizeof(uint64_t), 256);
 }
 
@@ -354,7 +346,7 @@ extern "C" int te_localisation_f32(const float* heat, const int64_t* labels, con
   if (labels && !target_id) return TE_ERR_INVALID_ARG;
   if (boxes && M <= 0) return TE_ERR_INVALID_ARG;
   if (((uintptr_t)ws) & 7u) return TE_ERR_INVALID_ARG;                           // (a null workspace: TE_ERR_WORKSPACE below)
-  if (H > kMaxPixels || W > kMaxPixels || H * W > kMaxPixels || P > kMaxPairs || (boxes && M > kMaxBoxes))
+  if (H > kTeMaxSortN || W > kTeMaxSortN || H * W > kTeMaxSortN || P > kTeMaxBatch || (boxes && M > kMaxBoxes))
     return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_localisation_workspace_bytes(P, H, W)) return TE_ERR_WORKSPACE;
   localisation_kernel<<<dim3((unsigned)P), dim3(kThreads), 0, (hipStream_t)stream>>>(

@@ -4,9 +4,7 @@
 //
 // Two launches, no host involvement:
 //   1. rank  : one workgroup of 16 waves per (sample, which of a, b, |a|, |b|): 4B sort jobs.  The n elements
-//              (te_key(value) << 32 | index) are sorted by the LSD radix sort of te_segmetrics.hip -- 4 passes of 8 bits over the
-//              key, ping-pong in the workspace, a (digit, wave) table in LDS, lanes of a digit ranked by ballots, every pass
-//              stable.  Then the runs of equal keys: the sorted positions where a run starts are compacted into the idle
+//              (te_key(value) << 32 | index) are sorted by the per-sample LSD radix sort of te_common.h.  Then the runs of equal keys: the sorted positions where a run starts are compacted into the idle
 //              buffer, and every element of a run s .. e-1 writes d = s + e - n = 2 rank - (n + 1) as int32 to its ORIGINAL
 //              index, in the other half of that buffer.  Integers only.
 //   2. reduce: one workgroup per sample: the fp64 means and centred sums of Pearson (two passes over a, b), the int64 sums
@@ -16,17 +14,13 @@
 
 namespace {
 
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / TE_WAVE;
-constexpr int kDigits = 256;
-constexpr int64_t kMaxN = (int64_t)1 << 20;
-constexpr int64_t kMaxBatch = 65535;
+constexpr int kThreads = kTeSortThreads;
+constexpr int kWaves = kTeSortWaves;
+constexpr int kDigits = kTeSortDigits;
 constexpr int kWin = 7;                            // scikit-image's default window
 
-// the two sort buffers of job (sample, which): n elements each
-__device__ __forceinline__ uint64_t* job_buffers(uint64_t* ws, int64_t sample, int which, uint32_t n) {
-  return ws + ((size_t)sample * 4 + (size_t)which) * 2 * (size_t)n;
-}
+// the sort job of (sample, which)
+__device__ __forceinline__ size_t job_index(int64_t sample, int which) { return (size_t)sample * 4 + (size_t)which; }
 
 __global__ __launch_bounds__(kThreads) void mapsim_rank_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                                uint32_t n, uint64_t* ws) {
@@ -37,31 +31,27 @@ __global__ __launch_bounds__(kThreads) void mapsim_rank_kernel(const float* __re
   const int64_t sample = blockIdx.y;
   const float* x = ((which & 1) ? b : a) + (size_t)sample * n;
   const bool magnitude = which >= 2;
-  const uint32_t S = (n + kThreads - 1) / kThreads * TE_WAVE;      // elements per wave segment, a multiple of 64
   const uint64_t below = (1ull << lane) - 1;
-  uint64_t* src = job_buffers(ws, sample, which, n);
-  uint64_t* dst = src + n;
-
-  for (int i = tid; i < 2 * kDigits * kWaves; i += kThreads) (&cnt[0][0])[i] = 0;
+  const TeSortJob job = te_sort_begin(ws, job_index(sample, which), n, cnt, tid);
+  const uint32_t S = job.S;
   __syncthreads();
 
   // ---- build
   for (uint32_t j = tid; j < n; j += kThreads) {
     float v = x[j];
     if (magnitude) v = fabsf(v);
-    const uint32_t key = te_key(v);
-    src[j] = ((uint64_t)key << 32) | j;
-    atomicAdd(&cnt[0][(key & 0xffu) * kWaves + j / S], 1u);
+    te_sort_put<32>(job, cnt, j, ((uint64_t)te_key(v) << 32) | j);
   }
   __syncthreads();
 
   // ---- sort (ascending, stable: equal keys stay in index order)
-  te_block_sort_passes(src, dst, n, S, cnt, wtot, tid, lane, wave, below);
+  te_block_sort_passes<32>(job, cnt, wtot, tid, lane, wave);
 
-  // ---- runs of equal keys: after four passes src is the job's first buffer again and holds the sorted elements; the second
-  // one is idle: its first n words take the sorted positions where a run starts, its last n words the d of every index
-  uint32_t* starts = reinterpret_cast<uint32_t*>(dst);
-  int32_t* d = reinterpret_cast<int32_t*>(dst) + n;
+  // ---- runs of equal keys: the job's first buffer holds the sorted elements; the second one is idle: its first n words take
+  // the sorted positions where a run starts, its last n words the d of every index
+  const uint64_t* src = job.src;
+  uint32_t* starts = reinterpret_cast<uint32_t*>(job.dst);
+  int32_t* d = reinterpret_cast<int32_t*>(job.dst) + n;
   const uint32_t seg0 = (uint32_t)wave * S, seg1 = min(seg0 + S, n);
   {
     uint32_t ns = 0;
@@ -115,19 +105,6 @@ __global__ __launch_bounds__(kThreads) void mapsim_rank_kernel(const float* __re
 
 __device__ __forceinline__ double clamp_unit(double v) { return v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v); }      // keeps NaN
 
-// sum of v over the block in thread 0: te_wave_sum, then the wave sums in order
-__device__ __forceinline__ double block_sum(double v, double* smem) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = te_wave_sum(v);
-  __syncthreads();
-  if (lane == 0) smem[wave] = v;
-  __syncthreads();
-  double tot = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kWaves; ++w) tot += smem[w];
-  return tot;
-}
-
 __global__ __launch_bounds__(kThreads) void mapsim_reduce_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                                  uint32_t n, int H, int W, int flags, double data_range,
                                                                  uint64_t* ws, int64_t* __restrict__ rank_sums,
@@ -178,8 +155,8 @@ __global__ __launch_bounds__(kThreads) void mapsim_reduce_kernel(const float* __
   // ---- Spearman on the values (pair 0) and on the absolute values (pair 1): exact integers
   double rho[2] = {nan, nan};
   for (int pair = 0; pair < 2; ++pair) {
-    const int32_t* da = reinterpret_cast<const int32_t*>(job_buffers(ws, sample, 2 * pair, n) + n) + n;
-    const int32_t* db = reinterpret_cast<const int32_t*>(job_buffers(ws, sample, 2 * pair + 1, n) + n) + n;
+    const int32_t* da = reinterpret_cast<const int32_t*>(te_sort_buffers(ws, job_index(sample, 2 * pair), n) + n) + n;
+    const int32_t* db = reinterpret_cast<const int32_t*>(te_sort_buffers(ws, job_index(sample, 2 * pair + 1), n) + n) + n;
     long long cov = 0, va = 0, vb = 0;
     for (uint32_t j = tid; j < n; j += kThreads) {
       const long long p = da[j], q = db[j];
@@ -247,7 +224,7 @@ __global__ __launch_bounds__(kThreads) void mapsim_reduce_kernel(const float* __
       const double vx = cov_norm * (uxx - ux * ux), vy = cov_norm * (uyy - uy * uy), vxy = cov_norm * (uxy - ux * uy);
       acc += ((2.0 * ux * uy + c1) * (2.0 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2));
     }
-    acc = block_sum(acc, red);
+    te_block_sum(acc, red);                        // (the barriers of the rank sums lie between this use of red and the last)
     if (tid == 0) ssim = acc / (double)nwin;
   }
 
@@ -263,9 +240,8 @@ __global__ __launch_bounds__(kThreads) void mapsim_reduce_kernel(const float* __
 }  // namespace
 
 extern "C" size_t te_map_similarity_workspace_bytes(int64_t B, int64_t n) {
-  if (B <= 0 || n <= 0 || B > kMaxBatch || n > kMaxN) return 0;
-  // per sample four sort jobs (a, b, |a|, |b|), each two buffers of n 8-byte elements
-  return te_align_up((size_t)B * 4 * 2 * (size_t)n * sizeof(uint64_t), 256);
+  if (B <= 0 || n <= 0 || B > kTeMaxBatch || n > kTeMaxSortN) return 0;
+  return te_sort_workspace_bytes((size_t)B * 4, (size_t)n);      // per sample four sort jobs (a, b, |a|, |b|)
 }
 
 extern "C" int te_map_similarity_f32(const float* a, const float* b, int64_t* rank_sums, double* sim, int64_t B, int64_t n,
@@ -273,7 +249,7 @@ extern "C" int te_map_similarity_f32(const float* a, const float* b, int64_t* ra
                                      te_stream_t stream) {
   if (!a || !b || !rank_sums || !sim || B <= 0 || n <= 0 || (flags & ~TE_MAPSIM_SSIM)) return TE_ERR_INVALID_ARG;
   if ((flags & TE_MAPSIM_SSIM) && (H < kWin || W < kWin || n % W != 0 || n / W != H)) return TE_ERR_INVALID_ARG;      // H * W != n
-  if (B > kMaxBatch || n > kMaxN) return TE_ERR_UNSUPPORTED;
+  if (B > kTeMaxBatch || n > kTeMaxSortN) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_map_similarity_workspace_bytes(B, n)) return TE_ERR_WORKSPACE;
   if (((uintptr_t)ws) & 7u) return TE_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;

@@ -24,9 +24,6 @@ struct Steps {
   int n;
   int64_t k[kMaxSteps];
 };
-struct Norm {
-  float mean[TE_PERTURB_MAX_CHANNELS], std[TE_PERTURB_MAX_CHANNELS];
-};
 
 // sel[b][s] = {threshold key, cut}: pixel i of sample b is removed at step s iff
 //   key_i > thr  ||  (key_i == thr && i < cut)
@@ -129,7 +126,7 @@ template <int VEC>
 __global__ __launch_bounds__(256) void perturb_apply_kernel(const float* __restrict__ vis,
                                                             const float* __restrict__ data,
                                                             const uint32_t* __restrict__ sel, float* __restrict__ out,
-                                                            int64_t B, int64_t C, int64_t HW, int S, Norm nm) {
+                                                            int64_t B, int64_t C, int64_t HW, int S, TeChannels nm) {
   const int64_t b = blockIdx.y;
   const int s = blockIdx.z;
   const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * VEC;
@@ -168,16 +165,12 @@ __global__ __launch_bounds__(256) void perturb_apply_kernel(const float* __restr
 // per channel and step) and walks the steps itself: the image and the relevance row are read once, not once per step, and
 // the S stores of a wave go to S streams of 1 KiB each.  blockIdx.z selects a group of `spg` steps (the host takes one
 // group when the batch alone fills the chip, one step per group otherwise).
-__device__ __forceinline__ uint32_t te_pack_bf16(float a, float b) {       // a in the low half
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-
 template <int VEC>
 __global__ __launch_bounds__(256) void perturb_apply_bf16_kernel(const float* __restrict__ vis,
                                                                  const float* __restrict__ data,
                                                                  const uint32_t* __restrict__ sel,
                                                                  te_bf16_t* __restrict__ out, int64_t B, int64_t C,
-                                                                 int64_t HW, int S, int spg, Norm nm) {
+                                                                 int64_t HW, int S, int spg, TeChannels nm) {
   const int64_t b = blockIdx.y;
   const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * VEC;
   if (i0 >= HW) return;
@@ -225,7 +218,7 @@ __global__ __launch_bounds__(256) void perturb_apply_bf16_kernel(const float* __
                          te_pack_bf16(y[6], y[7])};
         __builtin_nontemporal_store(p, reinterpret_cast<u32x4*>(dst));
       } else {
-        dst[0] = (te_bf16_t)(te_pack_bf16(y[0], 0.0f) & 0xffffu);
+        dst[0] = bf16_bits(y[0]);
       }
     }
   }
@@ -242,7 +235,7 @@ namespace {
 // argument checks + the selection kernel, shared by the fp32 and the bf16-output entry points
 int perturb_select(const float* vis, const float* data, const void* out, int64_t B, int64_t C, int64_t HW,
                    const int64_t* ks, int64_t n_steps, const float* mean, const float* std_, void* ws, size_t ws_bytes,
-                   hipStream_t stream, Norm* nm) {
+                   hipStream_t stream, TeChannels* nm) {
   if (!vis || !data || !out || !ks || B <= 0 || C <= 0 || HW <= 0 || n_steps <= 0) return TE_ERR_INVALID_ARG;
   if (n_steps > kMaxSteps || C > TE_PERTURB_MAX_CHANNELS || HW > (int64_t)0x7fffffff) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_perturb_workspace_bytes(B, n_steps)) return TE_ERR_WORKSPACE;
@@ -250,10 +243,7 @@ int perturb_select(const float* vis, const float* data, const void* out, int64_t
   st.n = (int)n_steps;
   for (int s = 0; s < kMaxSteps; ++s) st.k[s] = 0;
   for (int s = 0; s < st.n; ++s) st.k[s] = ks[s] < 0 ? 0 : (ks[s] > HW ? HW : ks[s]);
-  for (int c = 0; c < TE_PERTURB_MAX_CHANNELS; ++c) {
-    nm->mean[c] = (mean && c < C) ? mean[c] : 0.0f;
-    nm->std[c] = (std_ && c < C) ? std_[c] : 1.0f;
-  }
+  *nm = te_channels(C, mean, std_, nullptr);
   perturb_select_kernel<<<dim3((unsigned)B), dim3(kSelThreads), 0, stream>>>(vis, (uint32_t*)ws, HW, st);
   return TE_OK;
 }
@@ -263,7 +253,7 @@ extern "C" int te_perturb_f32(const float* vis, const float* data, float* out, i
                               const int64_t* ks, int64_t n_steps, const float* mean, const float* std_, void* ws,
                               size_t ws_bytes, te_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  Norm nm;
+  TeChannels nm;
   const int rc = perturb_select(vis, data, out, B, C, HW, ks, n_steps, mean, std_, ws, ws_bytes, stream, &nm);
   if (rc != TE_OK) return rc;
   const uint32_t* sel = (const uint32_t*)ws;
@@ -282,7 +272,7 @@ extern "C" int te_perturb_bf16(const float* vis, const float* data, te_bf16_t* o
                                const int64_t* ks, int64_t n_steps, const float* mean, const float* std_, void* ws,
                                size_t ws_bytes, te_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  Norm nm;
+  TeChannels nm;
   const int rc = perturb_select(vis, data, out, B, C, HW, ks, n_steps, mean, std_, ws, ws_bytes, stream, &nm);
   if (rc != TE_OK) return rc;
   const uint32_t* sel = (const uint32_t*)ws;

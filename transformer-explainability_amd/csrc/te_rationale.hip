@@ -27,7 +27,6 @@ namespace {
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / TE_WAVE;
 constexpr int kMaxLen = 2048;                      // tokens and words per document
-constexpr int64_t kMaxBatch = 65535;
 
 struct Ks {
   int n;
@@ -259,7 +258,7 @@ __global__ __launch_bounds__(kThreads) void token_erase_kernel(
 }  // namespace
 
 extern "C" size_t te_rationale_metrics_workspace_bytes(int64_t B, int64_t N, int64_t Wmax) {
-  if (B <= 0 || N <= 0 || Wmax <= 0 || B > kMaxBatch || N > kMaxLen || Wmax > kMaxLen) return 0;
+  if (B <= 0 || N <= 0 || Wmax <= 0 || B > kTeMaxBatch || N > kMaxLen || Wmax > kMaxLen) return 0;
   // one (tp, n) pair of 8 bytes per run of equal word scores, at most Wmax runs per document
   return te_align_up((size_t)B * (size_t)Wmax * sizeof(uint64_t), 256);
 }
@@ -278,7 +277,7 @@ extern "C" int te_rationale_metrics_f32(const float* scores, const int32_t* word
     if (ks[s] <= 0) return TE_ERR_INVALID_ARG;
     k.k[s] = (int)(ks[s] > kMaxLen ? kMaxLen : ks[s]);       // pred_k = min(k, n_words) and n_words <= 2048
   }
-  if (B > kMaxBatch || N > kMaxLen || Wmax > kMaxLen) return TE_ERR_UNSUPPORTED;
+  if (B > kTeMaxBatch || N > kMaxLen || Wmax > kMaxLen) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_rationale_metrics_workspace_bytes(B, N, Wmax)) return TE_ERR_WORKSPACE;
   if (((uintptr_t)ws) & 7u) return TE_ERR_INVALID_ARG;
   rationale_metrics_kernel<<<dim3((unsigned)B), dim3(kThreads), 0, (hipStream_t)stream>>>(
@@ -302,7 +301,7 @@ extern "C" int te_token_erase(const int64_t* input_ids, const int64_t* attention
     if (!(fractions[s] > 0.0) || fractions[s] > 1.0) return TE_ERR_INVALID_ARG;      // (NaN included)
     fr.t[s] = fractions[s];
   }
-  if (B > kMaxBatch || N > kMaxLen || Wmax > kMaxLen) return TE_ERR_UNSUPPORTED;
+  if (B > kTeMaxBatch || N > kMaxLen || Wmax > kMaxLen) return TE_ERR_UNSUPPORTED;
   token_erase_kernel<<<dim3((unsigned)B, (unsigned)n_t), dim3(kThreads), 0, (hipStream_t)stream>>>(
       input_ids, attention_mask, word_ids, order, n_words, ids_out, mask_out, n_rationale, (int)B, (int)N, (int)Wmax,
       fr, pad_id);

@@ -23,8 +23,6 @@ namespace {
 constexpr int kThreads = kTeSortThreads;           // complexity
 constexpr int kWaves = kTeSortWaves;
 constexpr int kDigits = kTeSortDigits;
-constexpr int64_t kMaxN = (int64_t)1 << 20;        // complexity: the limits of te_pixel_rank_f32
-constexpr int64_t kMaxBatch = 65535;
 constexpr int kDistThreads = 256;
 
 // ------------------------------------------------------------------------------------------------ noise
@@ -85,8 +83,7 @@ __global__ __launch_bounds__(256) void noise_inputs_kernel(const float* __restri
       if constexpr (VEC) {
         u32x4 p;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)              // y[2i] in the low half
-          p[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{y[2 * i], y[2 * i + 1]}, bf16x2));
+        for (int i = 0; i < 4; ++i) p[i] = te_pack_bf16(y[2 * i], y[2 * i + 1]);
         __builtin_nontemporal_store(p, reinterpret_cast<u32x4*>(dst));
       } else {
 #pragma unroll
@@ -103,15 +100,14 @@ int noise_inputs(const float* x, OutT* out, int64_t B, int64_t n, int64_t d0, in
   if (!x || !out || B <= 0 || n <= 0 || n_d <= 0 || d0 < 0 || !(radius >= 0.0f) || radius > 3.402823466e+38f)
     return TE_ERR_INVALID_ARG;                       // (!(radius >= 0): negative or NaN; above FLT_MAX: infinite)
   if (d0 > ((int64_t)1 << 32) || n_d > ((int64_t)1 << 32) - d0) return TE_ERR_INVALID_ARG;      // draws are 32-bit counters
-  if (B > kMaxBatch || n > (int64_t)0x7fffffff) return TE_ERR_UNSUPPORTED;
+  if (B > kTeMaxBatch || n > (int64_t)0x7fffffff) return TE_ERR_UNSUPPORTED;
   constexpr int E = std::is_same<OutT, float>::value ? 4 : 8;
   const bool vec = (n % E == 0) && te_aligned16(x) && te_aligned16(out);
   const int64_t bx = te_ceil_div(te_ceil_div(n, E), 256);
-  // all draws of the call inside one thread once B * bx blocks fill the chip (256 CUs x 4 resident blocks); else one per block
-  int64_t dpg = (bx * B >= 1024) ? n_d : 1;
-  if (te_ceil_div(n_d, dpg) > 65535) dpg = te_ceil_div(n_d, 65535);
+  unsigned gz;
+  const int64_t dpg = te_draws_per_block(bx * B, n_d, &gz);
   if (dpg > (int64_t)0x7fffffff) return TE_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)bx, (unsigned)B, (unsigned)te_ceil_div(n_d, dpg));
+  const dim3 grid((unsigned)bx, (unsigned)B, gz);
   const uint64_t key = (uint64_t)seed;
   if (vec)
     noise_inputs_kernel<OutT, true><<<grid, dim3(256), 0, stream>>>(x, out, n, (uint32_t)d0, n_d, (int)dpg, radius,
@@ -124,11 +120,6 @@ int noise_inputs(const float* x, OutT* out, int64_t B, int64_t n, int64_t d0, in
 }
 
 // ------------------------------------------------------------------------------------------------ distance
-__device__ __forceinline__ double dist_value(const float* p, int64_t i) { return (double)p[i]; }
-__device__ __forceinline__ double dist_value(const te_bf16_t* p, int64_t i) {
-  return (double)__uint_as_float((uint32_t)p[i] << 16);
-}
-
 // sums[b][d] = (sum (y - a)^2, sum a^2, sum y^2) over the n elements of a[b] and y = bb[b][d].  Thread t takes the groups of
 // four elements t, t + 256, ... and the elements of a group in order: VEC only changes how they are loaded.
 template <typename T, bool VEC>
@@ -141,30 +132,8 @@ __global__ __launch_bounds__(kDistThreads) void map_distance_kernel(const float*
   double sd = 0.0, sa = 0.0, sb = 0.0;
   for (int64_t e0 = (int64_t)threadIdx.x * 4; e0 < n; e0 += (int64_t)kDistThreads * 4) {
     double va[4], vb[4];
-    if constexpr (VEC) {
-      const f32x4 pa = *reinterpret_cast<const f32x4*>(xa + e0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) va[j] = (double)pa[j];
-      if constexpr (std::is_same<T, float>::value) {
-        const f32x4 pb = *reinterpret_cast<const f32x4*>(xb + e0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) vb[j] = (double)pb[j];
-      } else {
-        const u32x2 pb = *reinterpret_cast<const u32x2*>(xb + e0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {            // element 2j in the low half
-          vb[2 * j] = (double)__uint_as_float(pb[j] << 16);
-          vb[2 * j + 1] = (double)__uint_as_float(pb[j] & 0xffff0000u);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool in = e0 + j < n;
-        va[j] = in ? (double)xa[e0 + j] : 0.0;
-        vb[j] = in ? dist_value(xb, e0 + j) : 0.0;
-      }
-    }
+    te_load4_f64<VEC>(xa, e0, n, va);
+    te_load4_f64<VEC>(xb, e0, n, vb);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {                  // (a missing element adds +0.0 to non-negative sums: no bit changes)
       const double df = vb[j] - va[j];
@@ -185,7 +154,7 @@ __global__ __launch_bounds__(kDistThreads) void map_distance_kernel(const float*
 template <typename T>
 int map_distance(const float* a, const T* b, double* sums, int64_t B, int64_t D, int64_t n, hipStream_t stream) {
   if (!a || !b || !sums || B <= 0 || D <= 0 || n <= 0) return TE_ERR_INVALID_ARG;
-  if (B > kMaxBatch || D > (int64_t)0x7fffffff || n > (int64_t)0x7fffffff) return TE_ERR_UNSUPPORTED;
+  if (B > kTeMaxBatch || D > (int64_t)0x7fffffff || n > (int64_t)0x7fffffff) return TE_ERR_UNSUPPORTED;
   const bool vec = (n % 4 == 0) && te_aligned16(a) && te_aligned16(b);
   const dim3 grid((unsigned)D, (unsigned)B);
   if (vec)
@@ -213,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void map_complexity_kernel(const float* _
   int64_t* c = counts + sample * 2;
 
   // ---- S = sum v, max v, the number of v > 0; a NaN anywhere
-  double s = 0.0, npos = 0.0, unused = 0.0, unused2 = 0.0;      // (a count below 2^20 is exact in fp64, whatever the order)
+  double s = 0.0, npos = 0.0, unused = 0.0;      // (a count below 2^20 is exact in fp64, whatever the order)
   float mx = 0.0f;
   int bad = 0;
   for (uint32_t j = tid; j < n; j += kThreads) {
@@ -266,26 +235,19 @@ __global__ __launch_bounds__(kThreads) void map_complexity_kernel(const float* _
   }
 
   // ---- sort v ascending
-  const uint32_t Sg = (n + kThreads - 1) / kThreads * TE_WAVE;      // elements per wave segment, a multiple of 64
-  uint64_t* src = ws + (size_t)sample * 2 * (size_t)n;
-  uint64_t* dst = src + n;
-  for (int i = tid; i < 2 * kDigits * kWaves; i += kThreads) (&cnt[0][0])[i] = 0;
+  const TeSortJob job = te_sort_begin(ws, (size_t)sample, n, cnt, tid);
   __syncthreads();
-  for (uint32_t j = tid; j < n; j += kThreads) {
-    const uint32_t key = te_key(fabsf(x[j]));
-    src[j] = ((uint64_t)key << 32) | j;
-    atomicAdd(&cnt[0][(key & 0xffu) * kWaves + j / Sg], 1u);
-  }
+  for (uint32_t j = tid; j < n; j += kThreads) te_sort_put<32>(job, cnt, j, ((uint64_t)te_key(fabsf(x[j])) << 32) | j);
   __syncthreads();
-  te_block_sort_passes(src, dst, n, Sg, cnt, wtot, tid, lane, wave, (1ull << lane) - 1);
+  te_block_sort_passes<32>(job, cnt, wtot, tid, lane, wave);
 
   // ---- Gini = sum_k (2k - n - 1) v_(k) / (n S), k = j + 1 the 1-based sorted position; every product is exact in fp64
   double g = 0.0;
   for (uint32_t j = tid; j < n; j += kThreads) {
-    const float v = __uint_as_float((uint32_t)(src[j] >> 32) & 0x7fffffffu);      // te_key of v >= 0 sets the top bit
+    const float v = __uint_as_float((uint32_t)(job.src[j] >> 32) & 0x7fffffffu);      // te_key of v >= 0 sets the top bit
     g += (double)(2 * (int64_t)j + 1 - (int64_t)n) * (double)v;
   }
-  te_block_sum3(g, unused, unused2, red);
+  te_block_sum(g, red);
   if (tid == 0) o[0] = g / ((double)n * S);
 }
 
@@ -312,14 +274,14 @@ extern "C" int te_map_distance_bf16(const float* a, const te_bf16_t* b, double* 
 }
 
 extern "C" size_t te_map_complexity_workspace_bytes(int64_t B, int64_t n) {
-  if (B <= 0 || n <= 0 || B > kMaxBatch || n > kMaxN) return 0;
-  return te_align_up((size_t)B * 2 * (size_t)n * sizeof(uint64_t), 256);      // per sample two buffers of n 8-byte elements
+  if (B <= 0 || n <= 0 || B > kTeMaxBatch || n > kTeMaxSortN) return 0;
+  return te_sort_workspace_bytes((size_t)B, (size_t)n);
 }
 
 extern "C" int te_map_complexity_f32(const float* maps, double* out, int64_t* counts, int64_t B, int64_t n, double eps,
                                      void* ws, size_t ws_bytes, te_stream_t stream) {
   if (!maps || !out || !counts || B <= 0 || n <= 0 || !(eps >= 0.0) || eps > 1.7976931348623157e308) return TE_ERR_INVALID_ARG;
-  if (B > kMaxBatch || n > kMaxN) return TE_ERR_UNSUPPORTED;
+  if (B > kTeMaxBatch || n > kTeMaxSortN) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_map_complexity_workspace_bytes(B, n)) return TE_ERR_WORKSPACE;
   if (((uintptr_t)ws) & 7u) return TE_ERR_INVALID_ARG;
   map_complexity_kernel<<<dim3((unsigned)B), dim3(kThreads), 0, (hipStream_t)stream>>>(maps, out, counts, (uint32_t)n, eps,

@@ -7,11 +7,8 @@
 //   1. build : a wave per image row reads heat / mask / labels once: the six counts, the row's F1, and the 2*H*W sort
 //              elements (te_key(score) << 1 | truth) -- class 0 scores the fp32 value 1 - h, class 1 scores h.  A pixel with
 //              label < 0 gets key 0, which no cleaned score has: it sorts behind every real score and is never scanned.
-//   2. sort  : LSD radix sort of the elements, 4 passes of 8 bits over the key, ping-pong in the workspace (L2).  Every wave
-//              owns a contiguous segment of the source; a (digit, wave) table in LDS, scanned digit-major, gives each wave
-//              its destination per digit, and inside a 64-element step the lanes of one digit are ranked by ballots -- so
-//              every pass is stable.  The table of the next pass is counted while this pass scatters (integer LDS atomics:
-//              the counts do not depend on the order of arrival).
+//   2. sort  : the per-sample LSD radix sort of te_common.h on the 32 key bits above the truth bit; stable, so equal scores
+//              stay in pixel order, class 0 before class 1.
 //   3. scan  : over the sorted scores in descending order, the runs of equal keys: (tp_i, n_i) at the end of every run,
 //              compacted into the idle half of the workspace -- integers only.
 //   4. sum   : AP = sum_i (R_i - R_{i-1}) P_i in fp64, P_i = tp_i / n_i, R_i = tp_i / npos: thread t adds the runs t, t + 1024,
@@ -20,11 +17,9 @@
 
 namespace {
 
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / TE_WAVE;
-constexpr int kDigits = 256;
-constexpr int64_t kMaxPixels = (int64_t)1 << 20;
-constexpr int64_t kMaxBatch = 65535;
+constexpr int kThreads = kTeSortThreads;
+constexpr int kWaves = kTeSortWaves;
+constexpr int kDigits = kTeSortDigits;
 
 __global__ __launch_bounds__(kThreads) void seg_metrics_kernel(const float* __restrict__ heat,
                                                                const float* __restrict__ mask,
@@ -38,15 +33,13 @@ __global__ __launch_bounds__(kThreads) void seg_metrics_kernel(const float* __re
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t b = blockIdx.x;
   const uint32_t N = (uint32_t)H * (uint32_t)W, T2 = 2 * N;
-  const uint32_t S = (T2 + kThreads - 1) / kThreads * TE_WAVE;      // elements per wave segment, a multiple of 64
   const uint64_t below = (1ull << lane) - 1;
-  uint64_t* src = ws + (size_t)b * 2 * T2;
-  uint64_t* dst = src + T2;
   const float* hb = heat + b * N;
   const float* mb = mask + b * N;
   const int64_t* lb = labels + b * N;
 
-  for (int i = tid; i < 2 * kDigits * kWaves; i += kThreads) (&cnt[0][0])[i] = 0;
+  const TeSortJob job = te_sort_begin(ws, (size_t)b, T2, cnt, tid);
+  const uint32_t S = job.S;
   if (tid < 8) tally[tid] = 0;
   __syncthreads();
 
@@ -88,10 +81,8 @@ __global__ __launch_bounds__(kThreads) void seg_metrics_kernel(const float* __re
       if (live) {
         const uint64_t e0 = valid ? (((uint64_t)te_key(1.0f - h) << 1) | (lab == 0 ? 1u : 0u)) : 0ull;
         const uint64_t e1 = valid ? (((uint64_t)te_key(h) << 1) | (lab == 1 ? 1u : 0u)) : 0ull;
-        src[p] = e0;
-        src[N + p] = e1;
-        atomicAdd(&cnt[0][((uint32_t)(e0 >> 1) & 0xffu) * kWaves + p / S], 1u);
-        atomicAdd(&cnt[0][((uint32_t)(e1 >> 1) & 0xffu) * kWaves + (N + p) / S], 1u);
+        te_sort_put<1>(job, cnt, p, e0);
+        te_sort_put<1>(job, cnt, N + p, e1);
       }
     }
     if (lane == 0) {
@@ -101,9 +92,7 @@ __global__ __launch_bounds__(kThreads) void seg_metrics_kernel(const float* __re
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    uint32_t v = acc[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, TE_WAVE);
+    const uint32_t v = te_wave_sum_u32(acc[k]);
     if (lane == 0) atomicAdd(&tally[k], v);
   }
   __syncthreads();
@@ -114,50 +103,9 @@ __global__ __launch_bounds__(kThreads) void seg_metrics_kernel(const float* __re
   const uint32_t M = 2 * tally[1];                 // scores that take part in AP
 
   // ---- 2. sort (ascending; the ignored pixels' key 0 comes first)
-  for (int pass = 0; pass < 4; ++pass) {
-    volatile uint32_t* cur = cnt[pass & 1];
-    uint32_t* nxt = cnt[(pass + 1) & 1];
-    const int shift = 1 + 8 * pass;
-    {                                              // (digit, wave) counts -> start of each wave's elements of each digit
-      uint32_t v[4], sum = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        v[k] = cur[4 * tid + k];
-        sum += v[k];
-      }
-      uint32_t off = block_exclusive_scan(sum, wtot);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        cur[4 * tid + k] = off;
-        off += v[k];
-      }
-      for (int k = 0; k < 4; ++k) nxt[4 * tid + k] = 0;
-    }
-    __syncthreads();
-    const uint32_t seg0 = (uint32_t)wave * S, seg1 = min(seg0 + S, T2);
-    uint32_t idx = seg0 + lane;
-    uint64_t e_next = idx < seg1 ? src[idx] : 0ull;
-    for (uint32_t base = seg0; base < seg1; base += TE_WAVE) {
-      const uint64_t e = e_next;
-      const bool live = idx < seg1;
-      idx += TE_WAVE;
-      e_next = idx < seg1 ? src[idx] : 0ull;
-      const uint32_t digit = (uint32_t)(e >> shift) & 0xffu;
-      const uint64_t m = match_digit(digit, live);
-      const uint32_t rank = (uint32_t)__popcll(m & below), same = (uint32_t)__popcll(m);
-      if (live) {
-        const uint32_t at = cur[digit * kWaves + wave];
-        const uint32_t pos = at + rank;
-        dst[pos] = e;
-        if (rank == same - 1) cur[digit * kWaves + wave] = at + same;      // after every lane of the digit has read it
-        if (pass < 3) atomicAdd(&nxt[((uint32_t)(e >> (shift + 8)) & 0xffu) * kWaves + pos / S], 1u);
-      }
-    }
-    __syncthreads();
-    uint64_t* t = src;
-    src = dst;
-    dst = t;
-  }
+  te_block_sort_passes<1>(job, cnt, wtot, tid, lane, wave);
+  const uint64_t* src = job.src;
+  uint64_t* dst = job.dst;
 
   // ---- 3. runs of equal scores, descending: element j is src[T2 - 1 - j], j < M
   const uint32_t seg0 = (uint32_t)wave * S, seg1 = min(seg0 + S, M);
@@ -221,29 +169,22 @@ __global__ __launch_bounds__(kThreads) void seg_metrics_kernel(const float* __re
       sum += (recall - prev) * precision;
     }
   }
-  sum = te_wave_sum(sum);
-  if (lane == 0) red[wave] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    double tot = 0.0;
-    for (int w = 0; w < kWaves; ++w) tot += red[w];
-    ap[b] = tot;
-  }
+  te_block_sum(sum, red);
+  if (tid == 0) ap[b] = sum;
 }
 
 }  // namespace
 
 extern "C" size_t te_seg_metrics_workspace_bytes(int64_t B, int64_t H, int64_t W) {
-  if (B <= 0 || H <= 0 || W <= 0 || B > kMaxBatch || H > kMaxPixels || W > kMaxPixels || H * W > kMaxPixels) return 0;
-  // two buffers of 2*H*W 8-byte sort elements per image
-  return te_align_up((size_t)B * 2 * 2 * (size_t)(H * W) * sizeof(uint64_t), 256);
+  if (B <= 0 || H <= 0 || W <= 0 || B > kTeMaxBatch || H > kTeMaxSortN || W > kTeMaxSortN || H * W > kTeMaxSortN) return 0;
+  return te_sort_workspace_bytes((size_t)B, 2 * (size_t)(H * W));      // per image one sort of 2*H*W elements
 }
 
 extern "C" int te_seg_metrics_f32(const float* heat, const float* fg_mask, const int64_t* labels, int64_t* counts,
                                   double* ap, double* f1, int64_t B, int64_t H, int64_t W, void* ws, size_t ws_bytes,
                                   te_stream_t stream) {
   if (!heat || !fg_mask || !labels || !counts || !ap || !f1 || B <= 0 || H <= 0 || W <= 0) return TE_ERR_INVALID_ARG;
-  if (B > kMaxBatch || H > kMaxPixels || W > kMaxPixels || H * W > kMaxPixels) return TE_ERR_UNSUPPORTED;
+  if (B > kTeMaxBatch || H > kTeMaxSortN || W > kTeMaxSortN || H * W > kTeMaxSortN) return TE_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < te_seg_metrics_workspace_bytes(B, H, W)) return TE_ERR_WORKSPACE;
   if (((uintptr_t)ws) & 7u) return TE_ERR_INVALID_ARG;
   seg_metrics_kernel<<<dim3((unsigned)B), dim3(kThreads), 0, (hipStream_t)stream>>>(heat, fg_mask, labels, counts, ap, f1,

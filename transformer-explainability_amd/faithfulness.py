@@ -198,15 +198,6 @@ class FaithfulnessEvaluator:
         self.samples = 0                              # the id of the next sample
         self._scores = {name: [] for name in SCORE_NAMES}
 
-    def _input_dtype(self, images):
-        model = getattr(self.lrp, "model", None)
-        par = next(model.parameters(), None) if hasattr(model, "parameters") else None
-        dtype = par.dtype if par is not None and par.is_floating_point() else images.dtype
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ops._lib.TeError(f"FaithfulnessEvaluator: {ops.DTYPES_MSG}; the perturbed copies are made in float32 or "
-                                   f"bfloat16, the model is {dtype}")
-        return dtype
-
     def _substrate(self, clean, device):
         """dict(substrate=tensor) or dict(fill=constants) in normalised space: curves.py's own resolution"""
         C = clean.shape[1]
@@ -238,7 +229,7 @@ class FaithfulnessEvaluator:
         if images.dim() != 4:
             raise ops._lib.TeError(f"FaithfulnessEvaluator: images must be [B,C,H,W], got {tuple(images.shape)}")
         B, C, H, W = images.shape
-        dtype = self._input_dtype(images)
+        dtype = robustness._input_dtype(self.lrp, images, "FaithfulnessEvaluator", "perturbed")
         device = images.is_cuda
         seen = images.to(dtype)                                        # the tensor the model sees
         clean = seen.float()                                           # ... upcast exactly

@@ -1384,12 +1384,22 @@ def heatmap(maps: Tensor, scale: int = 16, normalise: bool = True, with_mask: bo
     return (heat, mask) if with_mask else heat
 
 
+def _is_integer(t: Tensor) -> bool:
+    return not (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool)
+
+
+def _dense(t: Tensor) -> Tensor:
+    """t itself when it is contiguous (a dense view that starts off a 16-byte boundary stays a view: the kernels have an
+    element-wise form), else a contiguous copy; never a cast (that is ``_c``)."""
+    return t if t.is_contiguous() else t.contiguous()
+
+
 def seg_metrics_packed(heat: Tensor, mask: Tensor, labels: Tensor):
     """``seg_metrics`` and the flat int64 buffer its results are views of -- counts [B*6], then the bits of ap [B], then
     the bits of f1 [B*H]: one device-to-host copy of it brings all three over."""
     if heat.dtype != torch.float32 or mask.dtype != torch.float32:
         raise _lib.TeError(f"seg_metrics takes a float32 heat map and a float32 0/1 mask, got {heat.dtype} / {mask.dtype}")
-    if labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+    if not _is_integer(labels):
         raise _lib.TeError(f"seg_metrics takes integer labels, got {labels.dtype}")
     if not (heat.is_cuda and mask.is_cuda and labels.is_cuda):
         raise _lib.TeError("seg_metrics needs tensors on the MI355X (got a CPU tensor); there is no CPU fallback")
@@ -1469,11 +1479,6 @@ def map_similarity(a: Tensor, b: Tensor, shape=None, data_range: float = 1.0):
     return map_similarity_packed(a, b, shape, data_range)[:2]
 
 
-# ---------------------------------------------------------------------------------------- 8f rationale test (BERT)
-def _is_integer(t: Tensor) -> bool:
-    return not (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool)
-
-
 # ---------------------------------------------------------------------------------------- localisation test (localisation.py)
 def _localisation_args(heat, labels, target_id, image_index, boxes):
     """The checks of localisation_metrics that need no device -> (P, B, H, W, M): raises TeError before any HIP call."""
@@ -1544,6 +1549,7 @@ def localisation_metrics(heat: Tensor, labels: Optional[Tensor] = None, target_i
     return localisation_metrics_packed(heat, labels, target_id, image_index, boxes)[:2]
 
 
+# ---------------------------------------------------------------------------------------- 8f rationale test (BERT)
 class _on_device_of_ids(_on_device):
     """``_on_device`` for a call whose tensors are all integers (te_token_erase): no dtype rule to apply."""
 
@@ -1660,15 +1666,19 @@ def perturb(vis: Tensor, data: Tensor, ks: Sequence[int], mean: Optional[Sequenc
 
 
 # ---------------------------------------------------------------------------------------- deletion / insertion curves (curves.py)
-def _curve_tensor(what: str, name: str, t, dtypes) -> Tensor:
-    """A check that needs no device: raises TeError before any HIP call."""
+_RESTATED_IN = {"curves": "curves.py has the torch restatement",
+                "robustness": "robustness.py has the numpy / torch restatement"}
+
+
+def _eval_tensor(module: str, what: str, name: str, t, dtypes) -> Tensor:
+    """A check that needs no device: raises TeError before any HIP call.  module: where the protocol is restated."""
     if not torch.is_tensor(t):
         raise _lib.TeError(f"{what}: {name} must be a tensor")
     if t.dtype not in dtypes:
         raise _lib.TeError(f"{what} takes {' or '.join(str(d) for d in dtypes)} for {name}, got {t.dtype}")
     if not t.is_cuda:
         raise _lib.TeError(f"{what} needs tensors on the MI355X (got a CPU tensor for {name}); there is no CPU fallback here -- "
-                           f"curves.py has the torch restatement")
+                           f"{_RESTATED_IN[module]}")
     return t
 
 
@@ -1689,15 +1699,14 @@ def gaussian_blur(data: Tensor, klen: int = 11, nsig: float = 5.0, mean: Optiona
     insertion curves"; ``curves.reference_blur`` is the restatement)."""
     import ctypes
     from .curves import gaussian_taps
-    data = _curve_tensor("gaussian_blur", "data", data, (torch.float32,))
+    data = _eval_tensor("curves", "gaussian_blur", "data", data, (torch.float32,))
     if data.dim() != 4 or data.numel() == 0:
         raise _lib.TeError(f"gaussian_blur: data must be [B,C,H,W] and not empty, got {tuple(data.shape)}")
     klen = int(klen)
     if klen < 1 or klen % 2 == 0 or klen > _lib.TE_BLUR_MAX_TAPS:
         raise _lib.TeError(f"gaussian_blur: klen must be odd and at most {_lib.TE_BLUR_MAX_TAPS}, got {klen}")
     B, C, H, W = data.shape
-    # (a view that is dense but starts at an odd element offset stays a view: the kernel has an element-wise form)
-    data = data if data.is_contiguous() else data.contiguous()
+    data = _dense(data)
     taps = gaussian_taps(klen, nsig)
     t_arr = (ctypes.c_float * klen)(*[float(v) for v in taps])
     m_arr, s_arr = _floats(mean, C, "gaussian_blur", "mean"), _floats(std, C, "gaussian_blur", "std")
@@ -1712,12 +1721,12 @@ def pixel_ranks(vis: Tensor) -> Tensor:
     """vis [B,n] (or [B,1,H,W]) fp32 relevance -> rank int32 [B,n]: the position of every pixel when its row is sorted by
     descending value, equal values in ascending pixel index (rank 0 = the most relevant pixel; ``curves.reference_ranks``).
     One launch, n <= 2^20."""
-    vis = _curve_tensor("pixel_ranks", "vis", vis, (torch.float32,))
+    vis = _eval_tensor("curves", "pixel_ranks", "vis", vis, (torch.float32,))
     if vis.dim() < 2 or vis.numel() == 0:
         raise _lib.TeError(f"pixel_ranks: vis must be [B,n] and not empty, got {tuple(vis.shape)}")
     B = vis.shape[0]
     vis = vis.reshape(B, -1)
-    vis = vis if vis.is_contiguous() else vis.contiguous()
+    vis = _dense(vis)
     n = vis.shape[1]
     rank = torch.empty((B, n), dtype=torch.int32, device=vis.device)
     with _on_device(vis) as lib:
@@ -1739,8 +1748,8 @@ def curve_inputs(data: Tensor, ranks: Tensor, step: int, s0: int, n_s: int, mode
         raise _lib.TeError(f"{what}: mode must be 'deletion' or 'insertion', got {mode!r}")
     if out_dtype not in (torch.float32, torch.bfloat16):
         raise _lib.TeError(f"{what}: out_dtype must be float32 or bfloat16, got {out_dtype}")
-    data = _curve_tensor(what, "data", data, (torch.float32,))
-    ranks = _curve_tensor(what, "ranks", ranks, (torch.int32,))
+    data = _eval_tensor("curves", what, "data", data, (torch.float32,))
+    ranks = _eval_tensor("curves", what, "ranks", ranks, (torch.int32,))
     if data.dim() != 4 or data.numel() == 0:
         raise _lib.TeError(f"{what}: data must be [B,C,H,W] and not empty, got {tuple(data.shape)}")
     B, C, H, W = data.shape
@@ -1750,16 +1759,16 @@ def curve_inputs(data: Tensor, ranks: Tensor, step: int, s0: int, n_s: int, mode
     if (substrate is None) == (fill is None):
         raise _lib.TeError(f"{what}: give a substrate tensor or the fill constants, one of the two")
     if substrate is not None:
-        substrate = _curve_tensor(what, "substrate", substrate, (torch.float32,))
+        substrate = _eval_tensor("curves", what, "substrate", substrate, (torch.float32,))
         if substrate.shape != data.shape:
             raise _lib.TeError(f"{what}: substrate {tuple(substrate.shape)} is not shaped like data {tuple(data.shape)}")
-        substrate = substrate if substrate.is_contiguous() else substrate.contiguous()
+        substrate = _dense(substrate)
     step, s0, n_s = int(step), int(s0), int(n_s)
     S = -(-HW // step) if step >= 1 else 0
     if step < 1 or s0 < 0 or n_s < 1 or s0 + n_s > S + 1:
         raise _lib.TeError(f"{what}: step {step}, s0 {s0}, n_s {n_s} do not name images of the {S + 1} of {HW} pixels")
-    data = data if data.is_contiguous() else data.contiguous()
-    ranks = ranks if ranks.is_contiguous() else ranks.contiguous()
+    data = _dense(data)
+    ranks = _dense(ranks)
     f_arr, m_arr, s_arr = _floats(fill, C, what, "fill"), _floats(mean, C, what, "mean"), _floats(std, C, what, "std")
     out = torch.empty((n_s, B, C, H, W), dtype=out_dtype, device=data.device)
     name = "te_curve_inputs_f32" if out_dtype == torch.float32 else "te_curve_inputs_bf16"
@@ -1774,9 +1783,9 @@ def curve_scores(logits: Tensor, target: Tensor, prob: Tensor, s0: int) -> Tenso
     writes prob[s0 + i, b] = softmax(logits[i, b])[target[b]], evaluated in fp64, in place (one launch) and returns prob
     (``curves.reference_scores``)."""
     what = "curve_scores"
-    logits = _curve_tensor(what, "logits", logits, (torch.float32, torch.bfloat16))
-    target = _curve_tensor(what, "target", target, (torch.int64,))
-    prob = _curve_tensor(what, "prob", prob, (torch.float64,))
+    logits = _eval_tensor("curves", what, "logits", logits, (torch.float32, torch.bfloat16))
+    target = _eval_tensor("curves", what, "target", target, (torch.int64,))
+    prob = _eval_tensor("curves", what, "prob", prob, (torch.float64,))
     if prob.dim() != 2 or not prob.is_contiguous() or target.dim() != 1 or target.shape[0] != prob.shape[1]:
         raise _lib.TeError(f"{what}: prob must be a contiguous [S+1,B] table and target [B], got {tuple(prob.shape)} and "
                            f"{tuple(target.shape)}")
@@ -1788,8 +1797,8 @@ def curve_scores(logits: Tensor, target: Tensor, prob: Tensor, s0: int) -> Tenso
     s0 = int(s0)
     if s0 < 0 or s0 + n_s > prob.shape[0]:
         raise _lib.TeError(f"{what}: rows {s0} .. {s0 + n_s - 1} are outside the {prob.shape[0]} rows of prob")
-    logits = logits if logits.is_contiguous() else logits.contiguous()
-    target = target if target.is_contiguous() else target.contiguous()
+    logits = _dense(logits)
+    target = _dense(target)
     name = "te_curve_scores_f32" if logits.dtype == torch.float32 else "te_curve_scores_bf16"
     with _on_device(logits) as lib:
         _lib.check(getattr(lib, name)(_ptr(logits), _ptr(target), _ptr(prob), B, K, s0, n_s, _stream(logits)), name)
@@ -1798,10 +1807,10 @@ def curve_scores(logits: Tensor, target: Tensor, prob: Tensor, s0: int) -> Tenso
 
 def curve_auc(prob: Tensor) -> Tensor:
     """prob float64 [S+1,B] -> auc float64 [B]: the trapezoid over x = i / S (``curves.reference_auc``), one launch."""
-    prob = _curve_tensor("curve_auc", "prob", prob, (torch.float64,))
+    prob = _eval_tensor("curves", "curve_auc", "prob", prob, (torch.float64,))
     if prob.dim() != 2 or prob.shape[0] < 2 or prob.shape[1] == 0:
         raise _lib.TeError(f"curve_auc: prob must be [S+1,B] with S >= 1, got {tuple(prob.shape)}")
-    prob = prob if prob.is_contiguous() else prob.contiguous()
+    prob = _dense(prob)
     S1, B = prob.shape
     auc = torch.empty((B,), dtype=torch.float64, device=prob.device)
     with _on_device_of_ids(prob) as lib:
@@ -1810,23 +1819,23 @@ def curve_auc(prob: Tensor) -> Tensor:
 
 
 # ---------------------------------------------------------------------------------------- robustness and complexity (robustness.py)
-def _robust_tensor(what: str, name: str, t, dtypes) -> Tensor:
-    """A check that needs no device: raises TeError before any HIP call."""
-    if not torch.is_tensor(t):
-        raise _lib.TeError(f"{what}: {name} must be a tensor")
-    if t.dtype not in dtypes:
-        raise _lib.TeError(f"{what} takes {' or '.join(str(d) for d in dtypes)} for {name}, got {t.dtype}")
-    if not t.is_cuda:
-        raise _lib.TeError(f"{what} needs tensors on the MI355X (got a CPU tensor for {name}); there is no CPU fallback here -- "
-                           f"robustness.py has the numpy / torch restatement")
-    return t
-
-
 def _finite_not_negative(what: str, name: str, value) -> float:
     value = float(value)
     if not (value >= 0.0) or value == float("inf"):
         raise _lib.TeError(f"{what}: {name} must be finite and not negative, got {value}")
     return value
+
+
+def _philox_args(what: str, seed, id0, d0, n_draws: int):
+    """(seed, id0, d0) of the draws d0 .. d0 + n_draws - 1 as the ABI carries them: checked, and the 64 bits of seed and id0,
+    which the device reads as unsigned, wrapped into an int64_t."""
+    d0, seed, id0 = int(d0), int(seed), int(id0)
+    if d0 < 0 or d0 + n_draws > 1 << 32:
+        raise _lib.TeError(f"{what}: draws {d0} .. {d0 + n_draws - 1} are not draws 0 .. 2^32 - 1")
+    if not (-(1 << 63) <= seed < 1 << 64) or not (-(1 << 63) <= id0 < 1 << 64):
+        raise _lib.TeError(f"{what}: seed and id0 are 64-bit integers, got {seed} and {id0}")
+    seed, id0 = (v - (1 << 64) if v >= 1 << 63 else v for v in (seed, id0))
+    return seed, id0, d0
 
 
 def noise_inputs(x: Tensor, n_draws: int, radius: float, seed: int, id0: int = 0, d0: int = 0,
@@ -1839,14 +1848,13 @@ def noise_inputs(x: Tensor, n_draws: int, radius: float, seed: int, id0: int = 0
     what = "noise_inputs"
     if out_dtype not in (torch.float32, torch.bfloat16):
         raise _lib.TeError(f"{what}: out_dtype must be float32 or bfloat16, got {out_dtype}")
-    x = _robust_tensor(what, "x", x, (torch.float32,))
+    x = _eval_tensor("robustness", what, "x", x, (torch.float32,))
     if x.dim() < 2 or x.numel() == 0:
         raise _lib.TeError(f"{what}: x must be [B,...] and not empty, got {tuple(x.shape)}")
     n_draws = int(n_draws)
     if n_draws < 1:
         raise _lib.TeError(f"{what}: n_draws must be at least 1, got {n_draws}")
-    # (a view that is dense but starts off a 16-byte boundary stays a view: the kernel has an element-wise form)
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _dense(x)
     out = torch.empty((x.shape[0], n_draws) + tuple(x.shape[1:]), dtype=out_dtype, device=x.device)
     return _noise_inputs_into(x, out, radius, seed, id0, d0)
 
@@ -1855,21 +1863,15 @@ def _noise_inputs_into(x: Tensor, out: Tensor, radius: float, seed: int, id0: in
     """The launch of ``noise_inputs``, into out [B,n_draws,...] fp32 or bf16, dense.  Not part of the interface: the tests
     call it to hand the kernel an output view that starts off a 16-byte boundary."""
     what = "noise_inputs"
-    x = _robust_tensor(what, "x", x, (torch.float32,))
-    out = _robust_tensor(what, "out", out, (torch.float32, torch.bfloat16))
+    x = _eval_tensor("robustness", what, "x", x, (torch.float32,))
+    out = _eval_tensor("robustness", what, "out", out, (torch.float32, torch.bfloat16))
     if x.dim() < 2 or out.dim() != x.dim() + 1 or out.shape[0] != x.shape[0] or out.shape[2:] != x.shape[1:] or \
             out.numel() == 0 or not x.is_contiguous() or not out.is_contiguous():
         raise _lib.TeError(f"{what}: x must be a dense [B,...] and out a dense [B,n_draws,...], got {tuple(x.shape)} and "
                            f"{tuple(out.shape)}")
     radius = _finite_not_negative(what, "radius", radius)
     B, n_draws = out.shape[0], out.shape[1]
-    d0, seed, id0 = int(d0), int(seed), int(id0)
-    if d0 < 0 or d0 + n_draws > 1 << 32:
-        raise _lib.TeError(f"{what}: draws {d0} .. {d0 + n_draws - 1} are not draws 0 .. 2^32 - 1")
-    if not (-(1 << 63) <= seed < 1 << 64) or not (-(1 << 63) <= id0 < 1 << 64):
-        raise _lib.TeError(f"{what}: seed and id0 are 64-bit integers, got {seed} and {id0}")
-    # (the 64 bits are read as unsigned on the device: the ABI carries them in an int64_t)
-    seed, id0 = (v - (1 << 64) if v >= 1 << 63 else v for v in (seed, id0))
+    seed, id0, d0 = _philox_args(what, seed, id0, d0, n_draws)
     name = "te_noise_inputs_f32" if out.dtype == torch.float32 else "te_noise_inputs_bf16"
     with _on_device(x) as lib:
         _lib.check(getattr(lib, name)(_ptr(x), _ptr(out), B, x[0].numel(), d0, n_draws, radius, seed, id0, _stream(x)), name)
@@ -1882,14 +1884,14 @@ def map_distance(a: Tensor, b: Tensor) -> Tensor:
     synchronisation (``robustness.reference_distance``).  Serves the map pairs and the input pairs of the sensitivity
     protocol."""
     what = "map_distance"
-    a = _robust_tensor(what, "a", a, (torch.float32,))
-    b = _robust_tensor(what, "b", b, (torch.float32, torch.bfloat16))
+    a = _eval_tensor("robustness", what, "a", a, (torch.float32,))
+    b = _eval_tensor("robustness", what, "b", b, (torch.float32, torch.bfloat16))
     if a.dim() < 2 or b.dim() < 3 or a.numel() == 0 or b.numel() == 0 or a.shape[0] != b.shape[0] or \
             a[0].numel() != b[0, 0].numel():
         raise _lib.TeError(f"{what}: a must be [B,n] and b [B,D,n] and not empty, got {tuple(a.shape)} and {tuple(b.shape)}")
     B, D, n = b.shape[0], b.shape[1], a[0].numel()
-    a = a if a.is_contiguous() else a.contiguous()
-    b = b if b.is_contiguous() else b.contiguous()
+    a = _dense(a)
+    b = _dense(b)
     out = torch.empty((B, D, 3), dtype=torch.float64, device=a.device)
     name = "te_map_distance_f32" if b.dtype == torch.float32 else "te_map_distance_bf16"
     with _on_device(a) as lib:
@@ -1903,13 +1905,13 @@ def map_complexity(maps: Tensor, eps: float = 1e-5):
     ``robustness.reference_complexity``).  A zero map or a NaN anywhere in a sample gives a NaN row and zero counts;
     n <= 2^20."""
     what = "map_complexity"
-    maps = _robust_tensor(what, "maps", maps, (torch.float32,))
+    maps = _eval_tensor("robustness", what, "maps", maps, (torch.float32,))
     if maps.dim() < 2 or maps.numel() == 0:
         raise _lib.TeError(f"{what}: maps must be [B,n] and not empty, got {tuple(maps.shape)}")
     eps = _finite_not_negative(what, "eps", eps)
     B = maps.shape[0]
     maps = maps.reshape(B, -1)
-    maps = maps if maps.is_contiguous() else maps.contiguous()
+    maps = _dense(maps)
     n = maps.shape[1]
     if n > 1 << 20 or B > 65535:
         raise _lib.TeError(f"{what}: at most 2^20 values per map and 65535 maps, got {tuple(maps.shape)}")
@@ -1951,13 +1953,12 @@ def subset_inputs(x: Tensor, k: int, grid, seed: int, id0: int = 0, d0: int = 0,
     what = "subset_inputs"
     if out_dtype not in (torch.float32, torch.bfloat16):
         raise _lib.TeError(f"{what}: out_dtype must be float32 or bfloat16, got {out_dtype}")
-    x = _robust_tensor(what, "x", x, (torch.float32,))
+    x = _eval_tensor("robustness", what, "x", x, (torch.float32,))
     C, g_h, g_w, _ = _grid_of(what, x, grid)
     n_draws = int(n_draws)
     if n_draws < 1:
         raise _lib.TeError(f"{what}: n_draws must be at least 1, got {n_draws}")
-    # (a view that is dense but starts off a 16-byte boundary stays a view: the kernel has an element-wise form)
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _dense(x)
     out = torch.empty((x.shape[0], n_draws) + tuple(x.shape[1:]), dtype=out_dtype, device=x.device)
     return _subset_inputs_into(x, out, k, (g_h, g_w), seed, id0, d0, substrate, fill, attr)
 
@@ -1968,43 +1969,39 @@ def _subset_inputs_into(x: Tensor, out: Tensor, k: int, grid, seed: int, id0: in
     """The launches of ``subset_inputs``, into out [B,n_draws,C,H,W] fp32 or bf16, dense.  Not part of the interface: the
     tests call it to hand the kernel an output view that starts off a 16-byte boundary."""
     what = "subset_inputs"
-    x = _robust_tensor(what, "x", x, (torch.float32,))
-    out = _robust_tensor(what, "out", out, (torch.float32, torch.bfloat16))
+    x = _eval_tensor("robustness", what, "x", x, (torch.float32,))
+    out = _eval_tensor("robustness", what, "out", out, (torch.float32, torch.bfloat16))
     C, g_h, g_w, p = _grid_of(what, x, grid)
     if out.dim() != 5 or out.shape[0] != x.shape[0] or out.shape[2:] != x.shape[1:] or out.numel() == 0 or \
             not x.is_contiguous() or not out.is_contiguous():
         raise _lib.TeError(f"{what}: x must be a dense [B,C,H,W] and out a dense [B,n_draws,C,H,W], got {tuple(x.shape)} and "
                            f"{tuple(out.shape)}")
     B, n_draws, G = out.shape[0], out.shape[1], g_h * g_w
-    k, d0, seed, id0 = int(k), int(d0), int(seed), int(id0)
+    k = int(k)
     if k < 1 or k > G:
         raise _lib.TeError(f"{what}: k must name 1 .. {G} of the {g_h} x {g_w} cells of x {tuple(x.shape)}, got {k}")
     if B > 65535:
         raise _lib.TeError(f"{what}: at most 65535 samples, got x {tuple(x.shape)}")
-    if d0 < 0 or d0 + n_draws > 1 << 32:
-        raise _lib.TeError(f"{what}: draws {d0} .. {d0 + n_draws - 1} are not draws 0 .. 2^32 - 1")
-    if not (-(1 << 63) <= seed < 1 << 64) or not (-(1 << 63) <= id0 < 1 << 64):
-        raise _lib.TeError(f"{what}: seed and id0 are 64-bit integers, got {seed} and {id0}")
-    seed, id0 = (v - (1 << 64) if v >= 1 << 63 else v for v in (seed, id0))      # (read as unsigned on the device)
+    seed, id0, d0 = _philox_args(what, seed, id0, d0, n_draws)
     if (substrate is None) == (fill is None):
         raise _lib.TeError(f"{what}: give a substrate tensor or the fill constants, one of the two")
     if substrate is not None:
-        substrate = _robust_tensor(what, "substrate", substrate, (torch.float32,))
+        substrate = _eval_tensor("robustness", what, "substrate", substrate, (torch.float32,))
         if substrate.shape != x.shape:
             raise _lib.TeError(f"{what}: substrate {tuple(substrate.shape)} is not shaped like x {tuple(x.shape)}")
-        substrate = substrate if substrate.is_contiguous() else substrate.contiguous()
+        substrate = _dense(substrate)
     elif C > _lib.TE_PERTURB_MAX_CHANNELS:
         raise _lib.TeError(f"{what}: fill constants serve at most {_lib.TE_PERTURB_MAX_CHANNELS} channels, x is "
                            f"{tuple(x.shape)}; give a substrate tensor")
     f_arr = _floats(fill, C, what, "fill")
     attr_sum = None
     if attr is not None:
-        attr = _robust_tensor(what, "attr", attr, (torch.float32,))
+        attr = _eval_tensor("robustness", what, "attr", attr, (torch.float32,))
         if attr.numel() != B * G or attr.shape[0] != B:
             raise _lib.TeError(f"{what}: attr {tuple(attr.shape)} is not a [B,G] map of the {g_h} x {g_w} cells of x "
                                f"{tuple(x.shape)}")
         attr = attr.reshape(B, G)
-        attr = attr if attr.is_contiguous() else attr.contiguous()
+        attr = _dense(attr)
         attr_sum = torch.empty((B, n_draws), dtype=torch.float64, device=x.device)
     member = torch.empty((B, n_draws, G), dtype=torch.uint8, device=x.device)
     name = "te_subset_inputs_f32" if out.dtype == torch.float32 else "te_subset_inputs_bf16"
@@ -2020,9 +2017,9 @@ def perturbation_dot(x: Tensor, y: Tensor, w: Tensor) -> Tensor:
     sum_e (x_e - y_e)^2, every term in fp64 from the exact upcasts, in the order of ``map_distance``; one launch, no
     synchronisation (``faithfulness.reference_dot``)."""
     what = "perturbation_dot"
-    x = _robust_tensor(what, "x", x, (torch.float32,))
-    y = _robust_tensor(what, "y", y, (torch.float32, torch.bfloat16))
-    w = _robust_tensor(what, "w", w, (torch.float32,))
+    x = _eval_tensor("robustness", what, "x", x, (torch.float32,))
+    y = _eval_tensor("robustness", what, "y", y, (torch.float32, torch.bfloat16))
+    w = _eval_tensor("robustness", what, "w", w, (torch.float32,))
     if x.dim() < 2 or y.dim() < 3 or w.dim() < 2 or x.numel() == 0 or y.numel() == 0 or w.numel() == 0 or \
             x.shape[0] != y.shape[0] or w.shape[0] != x.shape[0] or x[0].numel() != y[0, 0].numel():
         raise _lib.TeError(f"{what}: x must be [B,n], y [B,D,n] and w [B,m] and not empty, got {tuple(x.shape)}, "
@@ -2030,7 +2027,7 @@ def perturbation_dot(x: Tensor, y: Tensor, w: Tensor) -> Tensor:
     B, D, n, m = y.shape[0], y.shape[1], x[0].numel(), w[0].numel()
     if n % m != 0:
         raise _lib.TeError(f"{what}: the {m} weights of w {tuple(w.shape)} do not divide the {n} values of x {tuple(x.shape)}")
-    x, y, w = (t if t.is_contiguous() else t.contiguous() for t in (x, y, w))
+    x, y, w = (_dense(t) for t in (x, y, w))
     out = torch.empty((B, D, 2), dtype=torch.float64, device=x.device)
     name = "te_perturbation_dot_f32" if y.dtype == torch.float32 else "te_perturbation_dot_bf16"
     with _on_device(x) as lib:

@@ -160,6 +160,17 @@ def reference_scores(map0, maps, x0, xs, ref=None):
 
 
 # ------------------------------------------------------------------------------------------------ the protocol
+def _input_dtype(lrp, images, who: str, copies: str):
+    """The dtype evaluator ``who`` makes its ``copies`` ("noisy" / "perturbed") in: the model's, else the images'."""
+    model = getattr(lrp, "model", None)
+    par = next(model.parameters(), None) if hasattr(model, "parameters") else None
+    dtype = par.dtype if par is not None and par.is_floating_point() else images.dtype
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ops._lib.TeError(f"{who}: {ops.DTYPES_MSG}; the {copies} copies are made in float32 or "
+                               f"bfloat16, the model is {dtype}")
+    return dtype
+
+
 class SensitivityEvaluator:
     """Sensitivity, local Lipschitz estimate and complexity of the maps of ``method`` over a dataset, batch by batch.
 
@@ -201,15 +212,6 @@ class SensitivityEvaluator:
         self.samples = 0                              # the id of the next sample
         self._scores = {name: [] for name in SCORE_NAMES}
 
-    def _input_dtype(self, images):
-        model = getattr(self.lrp, "model", None)
-        par = next(model.parameters(), None) if hasattr(model, "parameters") else None
-        dtype = par.dtype if par is not None and par.is_floating_point() else images.dtype
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ops._lib.TeError(f"SensitivityEvaluator: {ops.DTYPES_MSG}; the noisy copies are made in float32 or "
-                                   f"bfloat16, the model is {dtype}")
-        return dtype
-
     def _explain(self, x, **which):
         got = self.lrp.generate_classes(x, methods=(self.method,), **which, **self.generate_kwargs)
         return got.classes, got.maps[self.method][:, 0]
@@ -218,7 +220,7 @@ class SensitivityEvaluator:
         if not torch.is_tensor(images) or not images.is_floating_point():
             raise ops._lib.TeError(DISCRETE_MSG)
         B = images.shape[0]
-        dtype = self._input_dtype(images)
+        dtype = _input_dtype(self.lrp, images, "SensitivityEvaluator", "noisy")
         device = images.is_cuda
         seen = images.to(dtype)                                        # the tensor the model sees
         clean = seen.float()                                           # ... upcast exactly
