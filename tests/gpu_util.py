@@ -77,6 +77,44 @@ def check_conditioned(name, got, ref32, ref64, base_tol, k=8.0, k_max=16.0, q=0.
     assert err <= tol, (name, dict(err=err, floor=floor, ref_max=mx, tol=tol))
 
 
+def group_stats(got, ref32, ref64, group_dims):
+    """Per independent problem (the dims in `group_dims` are reduced inside one): err_g = max|got - ref64|,
+    scale_g = max|ref64|, floor_g = max|ref32 - ref64|, and whether `got` has a non-zero element in the group."""
+    got, ref32, ref64 = (t.detach().cpu().double() for t in (got, ref32, ref64))
+    dims = tuple(d % ref64.dim() for d in ((group_dims,) if isinstance(group_dims, int) else group_dims))
+    return ((got - ref64).abs().amax(dims), ref64.abs().amax(dims), (ref32 - ref64).abs().amax(dims),
+            got.abs().amax(dims) != 0)
+
+
+def check_groups(name, got, ref32, ref64, group_dims, base_tol):
+    """Comparison that weighs every independent problem of a tensor by its OWN magnitude (check() and check_conditioned()
+    scale every error by the maximum of the whole tensor, so they only ever judge the largest row / head / sample).
+    For every group g (a row of a Linear output, a (b,h) slice of cam_v, a sample of an Add ...), against the fp64 oracle:
+        err_g <= base_tol x scale_g           wherever scale_g > 0,
+        got is exactly zero on the group      wherever ref64 is exactly zero on it,
+    and got is finite.  No group is left out.  The worst err_g / scale_g, the fp32 oracle's worst floor_g / scale_g and
+    the index of the worst group go to the parity report."""
+    assert tuple(got.shape) == tuple(ref64.shape) == tuple(ref32.shape), (name, got.shape, ref32.shape, ref64.shape)
+    finite = bool(torch.isfinite(got).all())
+    err, scale, floor, got_nz = group_stats(torch.nan_to_num(got.detach().cpu().double(), 0.0, 0.0, 0.0), ref32, ref64,
+                                            group_dims)
+    live = scale > 0
+    ratio = torch.where(live, err / scale.clamp_min(1e-300), torch.zeros_like(err))
+    fratio = torch.where(live, floor / scale.clamp_min(1e-300), torch.zeros_like(err))
+    worst = int(ratio.argmax()) if ratio.numel() else 0
+    widx = [int(i) for i in torch.unravel_index(torch.tensor(worst), ratio.shape)] if ratio.dim() else []
+    nonzero_on_zero = int((got_nz & ~live).sum())
+    s = dict(groups=int(ratio.numel()), live_groups=int(live.sum()), worst_ratio=float(ratio.max()) if ratio.numel() else 0.0,
+             oracle32_worst_ratio=float(fratio.max()) if ratio.numel() else 0.0, worst_group=widx,
+             worst_group_scale=float(scale.flatten()[worst]) if ratio.numel() else 0.0,
+             nonzero_on_zero_groups=nonzero_on_zero, base_tol=base_tol, finite=finite)
+    record(name, **s)
+    assert finite, (name, s)
+    assert nonzero_on_zero == 0, (name, s)
+    assert s["worst_ratio"] <= base_tol, (name, s)
+    return s
+
+
 from oracle.model_cache import bert_cache_from_model, vit_cache_from_model  # noqa: E402,F401
 
 

@@ -113,6 +113,21 @@ __device__ __forceinline__ double te_sd(double a, double b) {
   return q * ((b != 0.0) ? 1.0 : 0.0);
 }
 
+// The one-product Z of the Linear rule (te_linear.hip K1f, te_linear_x6.hip MODE_Z / MODE_ZS / MODE_ZI) is formed from the
+// cached forward output, Z = ((Y - b) +- |X||W|^T) / 2, and is only as good as Y - b.  Two things spoil it, and either sends
+// the element to the exact k-ordered part sum (exact_z / exact_zi):
+//   kCancelTol      |Z| <= 2^-7 |X||W|^T: the two halves cancel (nearly every product has the other sign, or the row is zero);
+//   kCancelBiasTol  |Z| <= 2^-4 |b_j|: Y was rounded at the magnitude of X W^T + b, so Y - b carries ~2^-24 |b_j| of absolute
+//                   error whatever the size of X W^T (a small row of X, an outlier bias element), i.e. 2^-25 |b_j| / |Z| of
+//                   Z after the halving -- 2^-21 at the threshold, a thirtieth of the rule's 2e-5 bar; below it the error
+//                   grows without bound (measured 1e-1 for a row of X at 2^-30) while the reference's Z stays exact.
+constexpr float kCancelTol = 0.0078125f;
+constexpr float kCancelBiasTol = 0.0625f;
+// mag = |Z| (Z itself for MODE_Z, -Z' for the inhibitor's Z' <= 0); written so that a NaN falls back too
+__device__ __forceinline__ bool te_z_cancels(float mag, float a_abs, float b) {
+  return !(mag > kCancelTol * a_abs) || !(mag > kCancelBiasTol * fabsf(b));
+}
+
 // The limits the evaluation kernels share: the values of one map (one per-sample sort; te_segmetrics.hip sorts two elements
 // per pixel), and the samples of one launch (a grid dimension)
 constexpr int64_t kTeMaxSortN = (int64_t)1 << 20;

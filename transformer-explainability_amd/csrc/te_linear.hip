@@ -9,9 +9,11 @@
 //   K1f ("Z-pass from the forward output", variant ours, alpha = 1): with Y = X W^T + b cached by the forward pass
 //        (forward_hook stores self.Y, layers_ours.py:16-27)   X+W+^T + X-W-^T = ( (Y - b) + |X||W|^T ) / 2,
 //        because the same-sign products sum to Z and the opposite-sign ones to XW^T - Z, while |X||W|^T is their
-//        difference.  ONE GEMM (|X||W|^T, K = in_f) instead of two; where the two halves cancel (Z < 2^-7 |X||W|^T:
-//        nearly every product negative) the element is recomputed as the plain positive-part sum, so exact zeros and
-//        tiny Z behave like the reference.  Measured on ViT-B maps: moves the result by 3-8e-7 relative, the same as
+//        difference.  ONE GEMM (|X||W|^T, K = in_f) instead of two; where the two halves cancel (Z <= 2^-7 |X||W|^T:
+//        nearly every product negative) or Z drowns in the rounding Y inherited from the bias (Z <= 2^-4 |b_j|: a small
+//        row of X, an outlier bias element; Y - b is only good to ~2^-24 |b_j|) the element is recomputed as the plain
+//        positive-part sum, so exact zeros and tiny Z behave like the reference (te_common.h: te_z_cancels).
+//        Measured on ViT-B maps: moves the result by 3-8e-7 relative, the same as
 //        permuting the summation order of the two-GEMM form (profiles/r01_zpass_from_forward_probe.log).
 //
 // The positive / negative parts are formed in registers right before the MFMA (one VALU op on the fragment that
@@ -181,7 +183,6 @@ __device__ __forceinline__ void load_kn_tile_fast(const float* __restrict__ M, i
 //     ZM_FWD: S = sd(R, ((Y - bias) + |X| |W|^T) / 2)  -- one product; Y = forward output, bias may be NULL
 // ------------------------------------------------------------------------------------------------
 enum { ZM_OURS = 0, ZM_LRP = 1, ZM_FWD = 2 };
-constexpr float kCancelTol = 0.0078125f;   // 2^-7: below this share of |X||W|^T the split sum is recomputed exactly
 
 // plain positive-part sum of one output element (the reference's Z), k-ordered
 __device__ __noinline__ float exact_z(const float* __restrict__ x, const float* __restrict__ w, int64_t K) {
@@ -465,7 +466,7 @@ __global__ __launch_bounds__(kThreads, 2) void linear_k1_kernel(
             const int64_t gr = gr0 + (e & 3) + 8 * (e >> 2);
             const float a_abs = acc[0][mi][ni][e];
             float z = 0.5f * ((yy[e] - bb) + a_abs);
-            if (!(z > kCancelTol * a_abs)) z = exact_z(X + gr * K, W + gc * K, K);
+            if (te_z_cancels(z, a_abs, bb)) z = exact_z(X + gr * K, W + gc * K, K);
             S1[gr * Nn + gc] = te_sd(rr[e], z);
           }
         }
@@ -488,9 +489,10 @@ __global__ __launch_bounds__(kThreads, 2) void linear_k1_kernel(
             S2[gr * Nn + gc] = te_sd(r, acc[1][mi][ni][e]);
           } else if constexpr (FWD) {
             const float a_abs = acc[0][mi][ni][e];                          // |X| |W|^T  >= 0
-            const float lin = Y[gr * Nn + gc] - (bias ? bias[gc] : 0.0f);   // X W^T
+            const float bb = bias ? bias[gc] : 0.0f;
+            const float lin = Y[gr * Nn + gc] - bb;                         // X W^T
             float z = 0.5f * (lin + a_abs);
-            if (!(z > kCancelTol * a_abs)) z = exact_z(X + gr * K, W + gc * K, K);   // cancellation / all-zero row
+            if (te_z_cancels(z, a_abs, bb)) z = exact_z(X + gr * K, W + gc * K, K);  // cancellation / all-zero row / Z << |b|
             S1[gr * Nn + gc] = te_sd(r, z);
           } else {
             S1[gr * Nn + gc] = te_sd(r, acc[0][mi][ni][e]);

@@ -57,14 +57,14 @@ namespace {
 // (te_x6.h: TE_MFMA_BF16, kFrag = one plane fragment, the split -- split3_pk, split3 --, sd2, swap_halves, PA / PB)
 constexpr int kRB = 3 * kFrag;                // one 32-row block, one K16 step
 constexpr int kMinFrag = 4;                   // a cut closer than this many K-steps to a tile boundary snaps onto it
-constexpr float kCancelTol = 0.0078125f;      // as te_linear.hip
 constexpr int kSpinMillis = 250;               // bounded wait for a predecessor's accumulators: never hang the GPU
 constexpr int kErrWord = 1023;                 // flags[0 .. 767] = hand-over flags of a pass, flags[kErrWord] = its error word
 
 
 // Z-pass, C-pass, plain GEMM out = B A^T + bias; round 4, for variant lrp and alpha != 1 (layers_lrp.py:188-211,
 // layers_ours.py:225-228): MODE_ZI = the inhibitor's Z-pass of variant ours from the same product, Z' = ((Y - b) - |X||W|^T)/2
-// = X+ W-^T + X- W+^T; MODE_Z1 = a one-sided Z-pass, S = sd(R, acc) (acc = X+ W+^T ...: same-sign terms, no cancellation);
+// = X+ W-^T + X- W+^T (exact k-ordered sum, exact_zi, where te_z_cancels(-Z', |X||W|^T, b_j): the two criteria of MODE_Z);
+// MODE_Z1 = a one-sided Z-pass, S = sd(R, acc) (acc = X+ W+^T ...: same-sign terms, no cancellation);
 // MODE_CI = the C-pass with the signs crossed, out += scale (X+ . (S W-) + X- . (S W+)); MODE_X = a product masked by one
 // sign of X, out (+)= scale (X+- . acc).
 // MODE_ZS = MODE_Z whose activation operand is the SIGNED planes of X (what the forward product read): |X| is formed while the
@@ -775,9 +775,10 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
             else                                     // one-sided product: the accumulator is Z
               z2 = a2;
           };
-          auto cancels = [&](float z, float a_abs) __attribute__((always_inline)) -> bool {
-            if constexpr (Z_ABS) return !(z > kCancelTol * a_abs);
-            else if constexpr (MODE == MODE_ZI) return !(-z > kCancelTol * a_abs);
+          // (te_common.h: te_z_cancels -- the halves cancel, or Z drowns in the rounding Y inherited from the bias)
+          auto cancels = [&](float z, float a_abs, float b) __attribute__((always_inline)) -> bool {
+            if constexpr (Z_ABS) return te_z_cancels(z, a_abs, b);
+            else if constexpr (MODE == MODE_ZI) return te_z_cancels(-z, a_abs, b);
             else return false;
           };
 #pragma unroll
@@ -792,7 +793,7 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
               const f32x2 sv = sd2(rr, z2);
 #pragma unroll
               for (int e = 0; e < 2; ++e) {
-                const bool cancel = cancels(z2[e], a2[e]);
+                const bool cancel = cancels(z2[e], a2[e], b4[g][c0 + e]);
                 if constexpr (MODE != MODE_Z1) any_cancel |= __builtin_amdgcn_ballot_w64(cancel);
                 sv4[c0 + e] = (live[ni] && !cancel) ? sv[e] : 0.0f;
               }
@@ -814,8 +815,8 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
               for (int c0 = 0; c0 < 4; c0 += 2) {
                 f32x2 z2, a2;
                 z_of(g, c0, z2, a2);
-                bad |= (cancels(z2[0], a2[0]) ? 1u : 0u) << (4 * g + c0);
-                bad |= (cancels(z2[1], a2[1]) ? 1u : 0u) << (4 * g + c0 + 1);
+                bad |= (cancels(z2[0], a2[0], b4[g][c0]) ? 1u : 0u) << (4 * g + c0);
+                bad |= (cancels(z2[1], a2[1], b4[g][c0 + 1]) ? 1u : 0u) << (4 * g + c0 + 1);
               }
           }
 #pragma unroll
@@ -897,10 +898,10 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
             bool cancel;
             if constexpr (Z_ABS) {                       // Z  = X+ W+^T + X- W-^T = ((Y - b) + |X||W|^T) / 2  (>= 0)
               z = 0.5f * ((y4[buf][g][c] - b4[c]) + a_abs);
-              cancel = !(z > kCancelTol * a_abs);
+              cancel = te_z_cancels(z, a_abs, b4[c]);
             } else if constexpr (MODE == MODE_ZI) {      // Z' = X+ W-^T + X- W+^T = ((Y - b) - |X||W|^T) / 2  (<= 0)
               z = 0.5f * ((y4[buf][g][c] - b4[c]) - a_abs);
-              cancel = !(-z > kCancelTol * a_abs);
+              cancel = te_z_cancels(-z, a_abs, b4[c]);
             } else {                                     // one-sided product: the accumulator is Z
               z = a_abs;
               cancel = false;
@@ -940,8 +941,9 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
               u32x4 v = {w[c][q][0], w[c][q][1], w[c + 2][q][0], w[c + 2][q][1]};
               *reinterpret_cast<u32x4*>(sp + q * kFrag + c * 512) = v;
             }
-          // rare: (Y - b) and |X||W|^T cancel (nearly every product of the element is negative): the reference's plain
-          // positive-part sum, k-ordered, written over the element's three plane values
+          // rare: (Y - b) and |X||W|^T cancel (nearly every product of the element is negative), or |Z| <= 2^-4 |b_j| (Y - b
+          // carries the bias's rounding; te_common.h: te_z_cancels): the reference's plain positive-part sum, k-ordered,
+          // written over the element's three plane values
           if (!live[ni]) bad = 0;
           if (__builtin_amdgcn_ballot_w64(bad != 0) != 0) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the 16-B pieces above are in memory first
