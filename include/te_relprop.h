@@ -1044,6 +1044,68 @@ int te_class_targets_bf16(const te_bf16_t* logits, int64_t ld, int64_t B, int64_
 int te_class_targets_f64(const double* logits, int64_t ld, int64_t B, int64_t C, int64_t K, const int64_t* classes_in,
                          int64_t* classes_out, double* scores, double* seeds, te_stream_t stream);
 
+/* ---- AttnLRP (csrc/te_attnlrp.hip) ------------------------------------------------------------------------------------
+ * A second explanation method beside the reference's: AttnLRP (Achtibat et al., "AttnLRP: Attention-Aware Layer-Wise
+ * Relevance Propagation for Transformers", ICML 2024) for the ViT / DeiT and BERT models of this package, fp32 only.  The
+ * reference has no such method and no parity with the authors' library (LXT) is claimed: THIS SECTION IS THE SPECIFICATION,
+ * and tests/attnlrp_ref.py restates it with torch autograd.
+ *
+ * The chain carries G, relevance per unit of activation: the relevance of an activation a is a (.) G_a.  Write
+ *     stab(y) = y + eps sgn(y), sgn(+-0) = +1          damp(G, y) = G y / stab(y)
+ * eps >= 0 is an argument (default 1e-6); eps = 0 means damp(G, y) = G, for every y.
+ *   Seed       G_logits = the one-hot of the class.
+ *   Linear     y = x W^T + b:  G_x = damp(G_y, y) W, y the cached output WITH the bias -- the bias absorbs its share.  The
+ *              product is te_gemm_x6_f32 on the planes of W^T wherever te_gemm_x6_supported, the stock fp32 GEMM elsewhere.
+ *   Add        o = a + b (residual):  G_a = G_b = damp(G_o, o).  Two paths that meet at one tensor add their G (plain).
+ *   LayerNorm  y = gamma (x - mu) rstd + beta with rstd held constant:  G_x[i] = rstd (gamma_i G_y[i] - mean_j(gamma_j G_y[j])),
+ *              rstd = 1 / sqrt(var + the layer's own eps).  No damping; beta absorbs its share.
+ *   GELU, tanh y = f(x):  G_x = G_y (f(x) / x), the factor f'(0) at x == +-0 (0.5 / 1).  f = te_gelu (te_gelu_forward_f32's
+ *              bits) / tanhf; one IEEE division, one multiply, no contraction.
+ *   Attention  s = scale q k^T (+ mask), p = softmax(s), o = p v: each operand of a product takes half (uniform rule), softmax
+ *              is plain gradient, the additive mask is a constant and absorbs nothing, no damping.  With d_* the gradients
+ *              of the block for d_out = G_o:  G_v = d_v / 2, G_q = d_q / 4, G_k = d_k / 4 (G_p = d_attn / 2) -- the existing
+ *              backward (te_attention_backward_strided_f32 where te_attention_strided_supported) and exact scalings.
+ *   Others     class-token select, position-embedding Add (a parameter), dropout in eval mode: plain gradient.
+ *   Result     ViT / DeiT: R[b][t] = sum_c x0[b][t][c] G[b][t][c] over the patch tokens, x0 the patch embedding (with the class
+ *              token in front) BEFORE the position embedding is added, the class token dropped: fp32 [B, N - 1].  BERT: x0 the
+ *              input of the embedding LayerNorm (word + position + type): fp32 [B, N].
+ *   Relevance is absorbed by: biases (Linear, LayerNorm beta), eps, the mean subtraction of LayerNorm, softmax, the additive
+ *   mask, the position embedding.  With all of them absent the chain conserves sum_t R = logit_c.
+ *
+ * The entries: contiguous fp32 tensors, pointers 4-byte aligned (TE_ERR_UNSUPPORTED otherwise); 16-byte accesses where the
+ * alignment allows, single elements elsewhere, and the same bits either way; no atomics, no workspace; every refusal comes
+ * before the launch.  TE_ERR_INVALID_ARG: a null pointer, a size <= 0, and what each entry names.
+ *   te_alrp_damp_f32            out[i] = (G[i] Y[i]) / stab(Y[i]): one multiply, one add, one IEEE division; eps == 0: out = G.
+ *                               out == G is allowed.  Vectors where G, Y and out share one 16-byte phase, from the first
+ *                               boundary on.  TE_ERR_INVALID_ARG: eps negative, NaN or infinite.
+ *   te_alrp_act_f32             out[i] = G[i] r, r = f(x[i]) / x[i] or f'(0); kind TE_ALRP_ACT_GELU / TE_ALRP_ACT_TANH (another
+ *                               kind: TE_ERR_INVALID_ARG).  out == G is allowed.  Vectors as in te_alrp_damp_f32.
+ *   te_alrp_scale3_f32          in place: rows t < T of C elements at q + t ld, k + t ld, v + t ld are multiplied by 1/4, 1/4,
+ *                               1/2 (exact).  A fused [T, 3C] gradient: q = g, k = g + C, v = g + 2C, ld = 3C; BERT's three
+ *                               tensors: ld = C.  The three row sets must not overlap.  TE_ERR_INVALID_ARG: ld < C.
+ *   te_alrp_row_rstd_f32        rstd[r] = 1 / sqrt(var_r + eps), var_r the biased variance of row r of x [rows, C], two passes
+ *                               (mean, then the squared distances), each an fp32 row sum in the lane order below, each
+ *                               divided by C once; IEEE sqrt and division.  Any C >= 1.
+ *   te_alrp_layernorm_f32       out[r][i] = rstd[r] (t_i - m), t_i = gamma[i] G[r][i] rounded, m = (fp32 row sum of t) / C.
+ *                               One row per wave.  LANE ORDER of the row sum: lane l adds t of the groups l, l + 64, ... (a
+ *                               group: elements 4g .. 4g + 3, in index order) to an accumulator that starts at +0; then the
+ *                               shuffle-down tree, offsets 32, 16, .. 1: lane j adds lane j + offset's value; lane 0 holds the
+ *                               sum.  A row's result does not depend on its position or on its neighbours: a row alone
+ *                               equals the same row in a batch.  out == G is allowed.  Any C >= 1.
+ *   te_alrp_token_relevance_f32 out[b][t - skip_first] = sum_c x0[b][t][c] G[b][t][c] for skip_first <= t < N; x0, G [B,N,C], out
+ *                               [B, N - skip_first].  The products are exact in fp64; thread i of the token's 64 adds the groups
+ *                               i, i + 64, ... of four elements in index order in fp64, then te_block_sum's order; one rounding
+ *                               to fp32.  TE_ERR_INVALID_ARG: skip_first not 0 or 1, N - skip_first == 0. */
+enum { TE_ALRP_ACT_GELU = 0, TE_ALRP_ACT_TANH = 1 };
+int te_alrp_damp_f32(const float* G, const float* Y, float* out, int64_t n, float eps, te_stream_t stream);
+int te_alrp_act_f32(const float* G, const float* x, float* out, int64_t n, int kind, te_stream_t stream);
+int te_alrp_scale3_f32(float* q, float* k, float* v, int64_t ld, int64_t T, int64_t C, te_stream_t stream);
+int te_alrp_row_rstd_f32(const float* x, float* rstd, int64_t rows, int64_t C, float eps, te_stream_t stream);
+int te_alrp_layernorm_f32(const float* G, const float* gamma, const float* rstd, float* out, int64_t rows, int64_t C,
+                          te_stream_t stream);
+int te_alrp_token_relevance_f32(const float* x0, const float* G, float* out, int64_t B, int64_t N, int64_t C, int skip_first,
+                                te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

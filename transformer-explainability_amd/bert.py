@@ -231,6 +231,20 @@ def make_bert_module(L):
             rv = self.value.relprop(rv, **kwargs)
             return self.clone.relprop((rq, rk, rv), **kwargs)
 
+        def attnlrp(self, G_o, eps):
+            """(extension) AttnLRP: the block's own backward for d_out = G_o on the three cached Linear outputs and the
+            cached probabilities (the additive mask is a constant), the uniform rule's 1/4, 1/4, 1/2, then the three Linear
+            rules, whose results add up at the Clone."""
+            if self.head_mask is not None:
+                raise ops._lib.TeError("BertSelfAttention.attnlrp: head_mask is not implemented for AttnLRP")
+            q, k, v = self.query.Y.detach(), self.key.Y.detach(), self.value.Y.detach()
+            d_q, d_k, d_v = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+            R_ours.attention_attnlrp(G_o, q, k, v, self.get_attn().detach(), self.num_attention_heads,
+                                     1.0 / math.sqrt(self.attention_head_size), d_q, d_k, d_v)
+            ops.alrp_scale3(d_q, d_k, d_v)
+            return self.clone.attnlrp((self.query.attnlrp(d_q, eps), self.key.attnlrp(d_k, eps),
+                                       self.value.attnlrp(d_v, eps)), eps)
+
     class BertSelfOutput(nn.Module):
         def __init__(self, config):
             super().__init__()
@@ -246,6 +260,11 @@ def make_bert_module(L):
             # (deferred: the Add's per-sample rescale rides with cam1 / cam2 into dense.relprop / the Clone rule)
             cam1, cam2 = self.add.relprop(cam, deferred=True, **kwargs)
             return self.dense.relprop(cam1, **kwargs), cam2
+
+        def attnlrp(self, G, eps):
+            """-> (G of hidden_states, G of input_tensor): LayerNorm rule, then the residual Add damps once for both."""
+            Gd = self.add.attnlrp(self.LayerNorm.attnlrp(G, eps), eps)
+            return self.dense.attnlrp(Gd, eps), Gd
 
     class BertAttention(nn.Module):
         def __init__(self, config):
@@ -263,6 +282,10 @@ def make_bert_module(L):
             cam1 = self.self.relprop(cam1, **kwargs)
             return self.clone.relprop((cam1, cam2), **kwargs)
 
+        def attnlrp(self, G, eps):
+            G1, G2 = self.output.attnlrp(G, eps)
+            return self.clone.attnlrp((self.self.attnlrp(G1, eps), G2), eps)
+
     class BertIntermediate(nn.Module):
         def __init__(self, config):
             super().__init__()
@@ -275,6 +298,9 @@ def make_bert_module(L):
 
         def relprop(self, cam, **kwargs):        # BERT.py:451-456 (activation rule = identity)
             return self.dense.relprop(cam, **kwargs)
+
+        def attnlrp(self, G, eps):
+            return self.dense.attnlrp(self.intermediate_act_fn.attnlrp(G, eps), eps)
 
     class BertOutput(nn.Module):
         def __init__(self, config):
@@ -290,6 +316,10 @@ def make_bert_module(L):
         def relprop(self, cam, **kwargs):        # BERT.py:474-487
             cam1, cam2 = self.add.relprop(cam, deferred=True, **kwargs)
             return self.dense.relprop(cam1, **kwargs), cam2
+
+        def attnlrp(self, G, eps):
+            Gd = self.add.attnlrp(self.LayerNorm.attnlrp(G, eps), eps)
+            return self.dense.attnlrp(Gd, eps), Gd
 
     class BertLayer(nn.Module):
         def __init__(self, config):
@@ -312,6 +342,11 @@ def make_bert_module(L):
             cam1 = self.intermediate.relprop(cam1, **kwargs)
             cam = self.clone.relprop((cam1, cam2), **kwargs)
             return self.attention.relprop(cam, **kwargs)
+
+        def attnlrp(self, G, eps):
+            G1, G2 = self.output.attnlrp(G, eps)
+            G = self.clone.attnlrp((self.intermediate.attnlrp(G1, eps), G2), eps)
+            return self.attention.attnlrp(G, eps)
 
         def relprop_cls_only(self, cam_cls, **kwargs):
             """BertLayer.relprop for relevance that lives on token 0 only (cam_cls [B,1,C]) -- the state right after
@@ -357,6 +392,11 @@ def make_bert_module(L):
                 cam = layer.relprop(cam, **kwargs)
             return cam
 
+        def attnlrp(self, G, eps):
+            for layer in reversed(self.layer):
+                G = layer.attnlrp(G, eps)
+            return G
+
     class BertPooler(nn.Module):
         def __init__(self, config):
             super().__init__()
@@ -372,6 +412,10 @@ def make_bert_module(L):
         def relprop(self, cam, **kwargs):        # BERT.py:181-191 (tanh rule = identity)
             cam = self.dense.relprop(cam, **kwargs)
             return self.pool.relprop(cam.unsqueeze(1), **kwargs)
+
+        def attnlrp(self, G, eps):
+            G = self.dense.attnlrp(self.activation.attnlrp(G, eps), eps)
+            return self.pool.attnlrp(G, eps)
 
     class BertModel(nn.Module):
         def __init__(self, config):
@@ -424,6 +468,13 @@ def make_bert_module(L):
                 cam = layer.relprop(cam, **kwargs)
             return cam
 
+        def attnlrp(self, G, eps):
+            """-> fp32 [B, N]: the chain down to the input of the embedding LayerNorm (word + position + type), then the
+            token sums of x0 (.) G."""
+            G = self.encoder.attnlrp(self.pooler.attnlrp(G, eps), eps)
+            norm = self.embeddings.LayerNorm
+            return ops.alrp_token_relevance(norm.X, norm.attnlrp(G, eps), skip_first=False)
+
     class BertForSequenceClassification(nn.Module):
         def __init__(self, config):
             super().__init__()
@@ -459,6 +510,11 @@ def make_bert_module(L):
         def relprop(self, cam=None, **kwargs):   # BertForSequenceClassification.py:83-88
             cam = self.classifier.relprop(cam, **kwargs)
             return self.bert.relprop(cam, **kwargs)
+
+        def attnlrp(self, seed, eps=1e-6):
+            """(extension) AttnLRP (te_relprop.h, section "AttnLRP"): ``seed`` [B, num_labels] -> fp32 [B, N] over the caches
+            of the last forward pass; no backward pass."""
+            return self.bert.attnlrp(self.classifier.attnlrp(seed, eps), eps)
 
     return dict(BertEmbeddings=BertEmbeddings, BertSelfAttention=BertSelfAttention, BertSelfOutput=BertSelfOutput,
                 BertAttention=BertAttention, BertIntermediate=BertIntermediate, BertOutput=BertOutput,

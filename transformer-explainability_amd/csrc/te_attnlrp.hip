@@ -1,0 +1,278 @@
+// te_attnlrp.hip -- the rule kernels of AttnLRP (include/te_relprop.h, section "AttnLRP"): streaming fp32 kernels, no atomics,
+// every reduction in an order fixed by the indices alone.  The products of the chain (Linear input gradient, attention backward)
+// are the package's existing kernels; what lives here is what sits between them.
+#include "te_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kRowsPerBlock = kThreads / TE_WAVE;      // the row kernels: one row per wave
+constexpr int64_t kMaxGrid = (int64_t)0x7fffffff;
+
+static inline bool aligned4(const void* p) { return (((uintptr_t)p) & 3u) == 0; }
+static inline unsigned off16(const void* p) { return (unsigned)(((uintptr_t)p) & 15u); }
+
+// ------------------------------------------------------------------------------------------------ element-wise rules
+// stab(y) = y + eps sgn(y), sgn(+-0) = +1; damp = (g y) / stab(y): one multiply, one add, one IEEE division.  eps == 0: g itself.
+struct DampOp {
+  float eps;
+  __device__ __forceinline__ float operator()(float g, float y) const {
+    if (eps == 0.0f) return g;
+    const float st = y + ((y >= 0.0f) ? eps : -eps);
+    return (g * y) / st;
+  }
+};
+// the identity rule: g (f(x) / x), f'(0) at x == +-0: one IEEE division, one multiply
+struct ActOp {
+  int kind;
+  __device__ __forceinline__ float operator()(float g, float x) const {
+    float r;
+    if (kind == TE_ALRP_ACT_GELU)
+      r = (x == 0.0f) ? 0.5f : te_gelu(x) / x;
+    else
+      r = (x == 0.0f) ? 1.0f : tanhf(x) / x;
+    return g * r;
+  }
+};
+
+// out[i] = op(a[i], b[i]).  Items 0 .. nvec - 1 are the 16-byte groups that start at element `head`; the items behind them are
+// the single elements in front of the first group and behind the last one.  nvec == 0: every element on its own.
+template <class Op>
+__global__ __launch_bounds__(kThreads) void binary_kernel(const float* a, const float* b, float* out,
+                                                           int64_t n, int64_t head, int64_t nvec, Op op) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i < nvec) {
+    const int64_t e = head + 4 * i;
+    const f32x4 va = *reinterpret_cast<const f32x4*>(a + e), vb = *reinterpret_cast<const f32x4*>(b + e);
+    f32x4 r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = op(va[j], vb[j]);
+    *reinterpret_cast<f32x4*>(out + e) = r;
+    return;
+  }
+  const int64_t s = i - nvec;
+  const int64_t e = (s < head) ? s : s + 4 * nvec;
+  if (e < n) out[e] = op(a[e], b[e]);
+}
+
+template <class Op>
+int binary_launch(const float* a, const float* b, float* out, int64_t n, Op op, hipStream_t stream) {
+  if (!a || !b || !out || n <= 0) return TE_ERR_INVALID_ARG;
+  if (!aligned4(a) || !aligned4(b) || !aligned4(out)) return TE_ERR_UNSUPPORTED;
+  int64_t head = 0, nvec = 0;
+  if (off16(a) == off16(b) && off16(a) == off16(out)) {      // one 16-byte phase: vectors from the first boundary on
+    head = ((16 - off16(a)) & 15) / 4;
+    if (head > n) head = n;
+    nvec = (n - head) / 4;
+  }
+  const int64_t items = nvec + (n - 4 * nvec);
+  const int64_t blocks = te_ceil_div(items, kThreads);
+  if (blocks > kMaxGrid) return TE_ERR_UNSUPPORTED;
+  binary_kernel<Op><<<dim3((unsigned)blocks), dim3(kThreads), 0, stream>>>(a, b, out, n, head, nvec, op);
+  TE_RETURN_IF_LAUNCH_FAILED();
+  return TE_OK;
+}
+
+// q *= 1/4, k *= 1/4, v *= 1/2 on rows of C elements, row t of each at pointer + t ld.  One item = one element (VEC: four).
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void scale3_kernel(float* q, float* k, float* v, int64_t ld, int64_t T, int64_t C) {
+  const int64_t per_row = VEC ? C / 4 : C;
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= 3 * T * per_row) return;
+  const int64_t t = i / (3 * per_row), r = i - t * 3 * per_row;
+  const int third = (int)(r / per_row);
+  const int64_t c = (r - third * per_row) * (VEC ? 4 : 1);
+  float* p = (third == 0 ? q : third == 1 ? k : v) + t * ld + c;
+  const float f = (third == 2) ? 0.5f : 0.25f;
+  if constexpr (VEC) {
+    f32x4 x = *reinterpret_cast<f32x4*>(p);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x[j] = x[j] * f;
+    *reinterpret_cast<f32x4*>(p) = x;
+  } else {
+    *p = *p * f;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ row kernels
+// The fp32 row sum of the LayerNorm rule and of the row statistics: lane l adds the terms of the groups l, l + 64, ... (a
+// group = four consecutive elements, added in index order) to one accumulator that starts at +0; then the shuffle-down tree
+// (offsets 32, 16, .. 1), whose lane 0 holds the sum, which every lane receives.  VEC only changes how a group is loaded.
+template <bool VEC, class Term>
+__device__ __forceinline__ float wave_row_sum(int lane, int64_t C, Term term) {
+  float acc = 0.0f;
+  for (int64_t c = (int64_t)lane * 4; c < C; c += TE_WAVE * 4) {
+    float t[4];
+    term(c, t);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (VEC || c + j < C) acc = acc + t[j];
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc = acc + __shfl_down(acc, off, TE_WAVE);
+  return __shfl(acc, 0, TE_WAVE);
+}
+
+template <bool VEC>
+__device__ __forceinline__ void load_group(const float* __restrict__ p, int64_t c, int64_t C, float (&v)[4]) {
+  if constexpr (VEC) {
+    const f32x4 q = *reinterpret_cast<const f32x4*>(p + c);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = q[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (c + j < C) ? p[c + j] : 0.0f;
+  }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void store_group(float* p, int64_t c, int64_t C, const float (&v)[4]) {
+  if constexpr (VEC) {
+    *reinterpret_cast<f32x4*>(p + c) = f32x4{v[0], v[1], v[2], v[3]};
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (c + j < C) p[c + j] = v[j];
+  }
+}
+
+// out[r][i] = rstd[r] (gamma_i G[r][i] - mean_j(gamma_j G[r][j]))
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void layernorm_rule_kernel(const float* G, const float* __restrict__ gamma,
+                                                                   const float* __restrict__ rstd, float* out, int64_t rows,
+                                                                   int64_t C) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const float* g = G + r * C;
+  float* o = out + r * C;
+  auto term = [&](int64_t c, float (&t)[4]) {
+    float a[4], w[4];
+    load_group<VEC>(g, c, C, a);
+    load_group<VEC>(gamma, c, C, w);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) t[j] = w[j] * a[j];
+  };
+  const float mean = wave_row_sum<VEC>(lane, C, term) / (float)C;
+  const float rs = rstd[r];
+  for (int64_t c = (int64_t)lane * 4; c < C; c += TE_WAVE * 4) {
+    float t[4];
+    term(c, t);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) t[j] = rs * (t[j] - mean);
+    store_group<VEC>(o, c, C, t);
+  }
+}
+
+// rstd[r] = 1 / sqrt(mean_j((x[r][j] - mean_j x[r][j])^2) + eps): the biased variance of nn.LayerNorm, two passes
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void row_rstd_kernel(const float* __restrict__ x, float* __restrict__ rstd, int64_t rows,
+                                                             int64_t C, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const float* xr = x + r * C;
+  const float mean = wave_row_sum<VEC>(lane, C, [&](int64_t c, float (&t)[4]) { load_group<VEC>(xr, c, C, t); }) / (float)C;
+  const float var = wave_row_sum<VEC>(lane, C, [&](int64_t c, float (&t)[4]) {
+    load_group<VEC>(xr, c, C, t);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float d = t[j] - mean;
+      t[j] = d * d;
+    }
+  }) / (float)C;
+  if (lane == 0) rstd[r] = 1.0f / sqrtf(var + eps);
+}
+
+// out[b][t - skip] = sum_c x0[b][t][c] G[b][t][c]: exact fp64 products, thread i adds the groups i, i + 64, ... of four
+// elements in index order, then te_block_sum; rounded to fp32 once.  One workgroup of one wave per token.
+template <bool VEC>
+__global__ __launch_bounds__(TE_WAVE) void token_relevance_kernel(const float* __restrict__ x0, const float* __restrict__ G,
+                                                                  float* __restrict__ out, int64_t N, int64_t C, int64_t skip) {
+  __shared__ double red[1];
+  const int64_t row = blockIdx.x, per = N - skip;
+  const int64_t b = row / per, t = row - b * per + skip;
+  const float* xr = x0 + (b * N + t) * C;
+  const float* gr = G + (b * N + t) * C;
+  double acc = 0.0;
+  for (int64_t e0 = (int64_t)threadIdx.x * 4; e0 < C; e0 += TE_WAVE * 4) {
+    double vx[4], vg[4];
+    te_load4_f64<VEC>(xr, e0, C, vx);
+    te_load4_f64<VEC>(gr, e0, C, vg);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc += vx[j] * vg[j];      // (an element past the end adds +0.0 * +0.0)
+  }
+  te_block_sum(acc, red);
+  if (threadIdx.x == 0) out[row] = (float)acc;
+}
+
+bool finite_not_negative(float v) { return v >= 0.0f && v <= 3.402823466e+38f; }
+
+}  // namespace
+
+extern "C" int te_alrp_damp_f32(const float* G, const float* Y, float* out, int64_t n, float eps, te_stream_t stream) {
+  if (!finite_not_negative(eps)) return TE_ERR_INVALID_ARG;
+  return binary_launch(G, Y, out, n, DampOp{eps}, (hipStream_t)stream);
+}
+
+extern "C" int te_alrp_act_f32(const float* G, const float* x, float* out, int64_t n, int kind, te_stream_t stream) {
+  if (kind != TE_ALRP_ACT_GELU && kind != TE_ALRP_ACT_TANH) return TE_ERR_INVALID_ARG;
+  return binary_launch(G, x, out, n, ActOp{kind}, (hipStream_t)stream);
+}
+
+extern "C" int te_alrp_scale3_f32(float* q, float* k, float* v, int64_t ld, int64_t T, int64_t C, te_stream_t stream) {
+  if (!q || !k || !v || T <= 0 || C <= 0 || ld < C) return TE_ERR_INVALID_ARG;
+  if (!aligned4(q) || !aligned4(k) || !aligned4(v)) return TE_ERR_UNSUPPORTED;
+  if (T > kMaxGrid || C > kMaxGrid || 3 * T * C > kMaxGrid * kThreads) return TE_ERR_UNSUPPORTED;
+  const bool vec = C % 4 == 0 && ld % 4 == 0 && te_aligned16(q) && te_aligned16(k) && te_aligned16(v);
+  const int64_t blocks = te_ceil_div(3 * T * (vec ? C / 4 : C), kThreads);
+  if (vec)
+    scale3_kernel<true><<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream>>>(q, k, v, ld, T, C);
+  else
+    scale3_kernel<false><<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream>>>(q, k, v, ld, T, C);
+  TE_RETURN_IF_LAUNCH_FAILED();
+  return TE_OK;
+}
+
+extern "C" int te_alrp_layernorm_f32(const float* G, const float* gamma, const float* rstd, float* out, int64_t rows, int64_t C,
+                                     te_stream_t stream) {
+  if (!G || !gamma || !rstd || !out || rows <= 0 || C <= 0) return TE_ERR_INVALID_ARG;
+  if (!aligned4(G) || !aligned4(gamma) || !aligned4(rstd) || !aligned4(out)) return TE_ERR_UNSUPPORTED;
+  const int64_t blocks = te_ceil_div(rows, kRowsPerBlock);
+  if (blocks > kMaxGrid || C > kMaxGrid) return TE_ERR_UNSUPPORTED;
+  const bool vec = C % 4 == 0 && te_aligned16(G) && te_aligned16(gamma) && te_aligned16(out);
+  if (vec)
+    layernorm_rule_kernel<true><<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream>>>(G, gamma, rstd, out, rows, C);
+  else
+    layernorm_rule_kernel<false><<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream>>>(G, gamma, rstd, out, rows, C);
+  TE_RETURN_IF_LAUNCH_FAILED();
+  return TE_OK;
+}
+
+extern "C" int te_alrp_row_rstd_f32(const float* x, float* rstd, int64_t rows, int64_t C, float eps, te_stream_t stream) {
+  if (!x || !rstd || rows <= 0 || C <= 0 || !finite_not_negative(eps)) return TE_ERR_INVALID_ARG;
+  if (!aligned4(x) || !aligned4(rstd)) return TE_ERR_UNSUPPORTED;
+  const int64_t blocks = te_ceil_div(rows, kRowsPerBlock);
+  if (blocks > kMaxGrid || C > kMaxGrid) return TE_ERR_UNSUPPORTED;
+  if (C % 4 == 0 && te_aligned16(x))
+    row_rstd_kernel<true><<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream>>>(x, rstd, rows, C, eps);
+  else
+    row_rstd_kernel<false><<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream>>>(x, rstd, rows, C, eps);
+  TE_RETURN_IF_LAUNCH_FAILED();
+  return TE_OK;
+}
+
+extern "C" int te_alrp_token_relevance_f32(const float* x0, const float* G, float* out, int64_t B, int64_t N, int64_t C,
+                                           int skip_first, te_stream_t stream) {
+  if (!x0 || !G || !out || B <= 0 || N <= 0 || C <= 0 || (skip_first != 0 && skip_first != 1) || N - skip_first <= 0)
+    return TE_ERR_INVALID_ARG;
+  if (!aligned4(x0) || !aligned4(G) || !aligned4(out)) return TE_ERR_UNSUPPORTED;
+  if (B > kMaxGrid / N || C > kMaxGrid) return TE_ERR_UNSUPPORTED;
+  const int64_t rows = B * (N - skip_first);
+  if (C % 4 == 0 && te_aligned16(x0) && te_aligned16(G))
+    token_relevance_kernel<true><<<dim3((unsigned)rows), dim3(TE_WAVE), 0, (hipStream_t)stream>>>(x0, G, out, N, C, skip_first);
+  else
+    token_relevance_kernel<false><<<dim3((unsigned)rows), dim3(TE_WAVE), 0, (hipStream_t)stream>>>(x0, G, out, N, C, skip_first);
+  TE_RETURN_IF_LAUNCH_FAILED();
+  return TE_OK;
+}

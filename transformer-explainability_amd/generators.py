@@ -129,6 +129,33 @@ def _refuse_before_forward(input, wanted):
                                "torch.float64 model: run it on a float32 or bfloat16 model")
 
 
+def _refuse_attnlrp(model, eps, head_mask, *inputs):
+    """The refusals of generate_attnlrp, raised before the forward pass: AttnLRP (te_relprop.h, section "AttnLRP") is
+    implemented for float32 models in eval mode without a head mask."""
+    if head_mask is not None:
+        raise ops._lib.TeError("generate_attnlrp: head_mask is not implemented for AttnLRP (the chain has no Mul rule); "
+                               "pass head_mask=None")
+    if model.training:
+        raise ops._lib.TeError("generate_attnlrp: the model is in train mode; AttnLRP reads the caches of an eval-mode "
+                               "forward pass (dropout is the identity): call model.eval()")
+    dtypes = [p.dtype for p in model.parameters()] + [t.dtype for t in inputs if torch.is_tensor(t) and t.is_floating_point()]
+    for dt in dtypes:
+        if dt != torch.float32:
+            raise ops._lib.TeError(f"generate_attnlrp: AttnLRP is implemented for torch.float32 models and inputs only, "
+                                   f"got {dt}: run it on a float32 copy of the model")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < float("inf"):
+        raise ValueError(f"generate_attnlrp: eps must be a finite number >= 0, got {eps!r}")
+
+
+def _drop_rule_planes(model):
+    """The operand planes the x6 forward products left for the relprop rules of their layers (ops.post_x_abs_planes: 6 B per
+    input element) have no reader in a call that runs no such rule: drop them with the forward pass behind."""
+    for m in model.modules():
+        cache = m.__dict__.get("_te_cache")
+        if cache:
+            ops.drop_x_planes(cache, with_abs=True)
+
+
 @contextlib.contextmanager
 def _x6_bracket(t):
     """Around a public call on the batch ``t``: a lost x6 hand-over of an EARLIER call is raised before it, once, without
@@ -344,6 +371,24 @@ class LRP(_PassDriver):
         pruned = bool((self.prune or self.model.prune_below_start_layer) and method in M.SINGLE_CALL_PRUNED)
         name = self.model.default_method if method is None else method
         return self._pass(input, (name,), index, is_ablation, start_layer, head_mask, self._SINGLE_CALL_NEED, pruned)[name]
+
+    def generate_attnlrp(self, input, index=None, eps=1e-6, head_mask=None):
+        """(extension) AttnLRP (Achtibat et al., ICML 2024; the rules: te_relprop.h, section "AttnLRP") -> fp32 [B, N-1],
+        the shape of generate_LRP: the relevance of the patch tokens for the class ``index`` (None: the per-sample argmax).
+        One forward pass, no backward pass, one chain; ``eps`` (>= 0) stabilises the Linear and residual-Add rules.  float32
+        models in eval mode only; bf16 / fp16 / fp64 models, train mode and ``head_mask`` raise TeError before the forward
+        pass.  The x6 status poll / post as in generate_LRP; capturable by GraphedCall."""
+        with _x6_bracket(input):
+            return self._attnlrp(input, index, eps, head_mask)
+
+    def _attnlrp(self, input, index=None, eps=1e-6, head_mask=None):
+        """generate_attnlrp without the x6 bracket."""
+        _refuse_attnlrp(self.model, eps, head_mask, input)
+        with torch.no_grad():
+            output = self.model(input)
+            _drop_rule_planes(self.model)
+            seed = _one_hot(output, index)
+            return self._gradients_and_chain(output, [], lambda: self.model.attnlrp(seed, eps=eps))
 
     def generate_all(self, input, methods, index=None, is_ablation=False, start_layer=0, head_mask=None):
         """(extension) The maps of several methods of the SAME batch from one pass: ``methods`` is any subset of the
@@ -723,6 +768,19 @@ class Generator(_PassDriver):
         with _x6_bracket(input_ids):
             self._pass(input_ids, attention_mask, index, lowest_layer=start_layer, head_mask=head_mask)
             return self.attribution_tail(start_layer)
+
+    def generate_attnlrp(self, input_ids, attention_mask, index=None, eps=1e-6, head_mask=None):
+        """(extension) AttnLRP (Achtibat et al., ICML 2024; the rules: te_relprop.h, section "AttnLRP") -> fp32 [B, N]: the
+        relevance of every token (the sum over the hidden dimension of x0 (.) G at the input of the embedding LayerNorm) for
+        the class ``index`` (None: the per-sample argmax).  One forward pass, no backward pass, one chain.  float32 models in
+        eval mode only; bf16 / fp16 / fp64 models, train mode and ``head_mask`` raise TeError before the forward pass."""
+        with _x6_bracket(input_ids):
+            _refuse_attnlrp(self.model, eps, head_mask, input_ids, attention_mask)
+            with torch.no_grad():
+                output = self.model(input_ids=input_ids, attention_mask=attention_mask)[0]
+                _drop_rule_planes(self.model)
+                seed = _one_hot(output, index)
+                return self._gradients_and_chain(output, [], lambda: self.model.attnlrp(seed, eps=eps))
 
     def attribution_tail(self, start_layer=11):
         """ExplanationGenerator.py:47-59 on the attn_cam / attention gradients cached by relprop + backward."""

@@ -2625,3 +2625,117 @@ def class_targets(logits: Tensor, classes: Optional[Tensor] = None, topk: Option
                                                            _ptr(scores), _ptr(seeds), _stream(logits)),
                    "te_class_targets_" + sfx)
     return cls_out, scores, seeds
+
+
+# ---------------------------------------------------------------------------------------- AttnLRP
+# The rule kernels of csrc/te_attnlrp.hip (te_relprop.h, section "AttnLRP": the specification of the method).  fp32 device
+# tensors only; every binding refuses anything else with DTYPES_MSG before a launch.
+_ALRP_KINDS = {"gelu": _lib.TE_ALRP_ACT_GELU, "tanh": _lib.TE_ALRP_ACT_TANH}
+
+
+def _alrp_out(out: Optional[Tensor], like: Tensor, what: str) -> Tensor:
+    if out is None:
+        return torch.empty(like.shape, dtype=torch.float32, device=like.device)
+    if _prep(out).shape != like.shape or not out.is_contiguous():
+        raise _lib.TeError(f"{what}: out must be a contiguous float32 tensor of shape {tuple(like.shape)}")
+    return out
+
+
+def alrp_damp(G: Tensor, Y: Tensor, eps: float = 1e-6, out: Optional[Tensor] = None) -> Tensor:
+    """damp(G, Y) = G Y / stab(Y), stab(y) = y + eps sgn(y) with sgn(0) = +1; eps = 0: G itself.  ``out`` may be G."""
+    G, Y = _c(G), _c(Y)
+    if G.shape != Y.shape:
+        raise _lib.TeError(f"alrp_damp: G {tuple(G.shape)} and Y {tuple(Y.shape)} differ in shape")
+    out = _alrp_out(out, G, "alrp_damp")
+    with _on_device(G) as lib, _timed("alrp_damp", 0.0, 12.0 * G.numel()):
+        _lib.check(lib.te_alrp_damp_f32(_ptr(G), _ptr(Y), _ptr(out), G.numel(), float(eps), _stream(G)), "te_alrp_damp_f32")
+    return out
+
+
+def alrp_act(G: Tensor, x: Tensor, kind: str = "gelu", out: Optional[Tensor] = None) -> Tensor:
+    """The identity rule through y = f(x), f = GELU (te_gelu) or tanh: G (f(x) / x), f'(0) at x == 0.  ``out`` may be G."""
+    if kind not in _ALRP_KINDS:
+        raise ValueError(f"alrp_act: kind must be one of {sorted(_ALRP_KINDS)}, got {kind!r}")
+    G, x = _c(G), _c(x)
+    if G.shape != x.shape:
+        raise _lib.TeError(f"alrp_act: G {tuple(G.shape)} and x {tuple(x.shape)} differ in shape")
+    out = _alrp_out(out, G, "alrp_act")
+    with _on_device(G) as lib, _timed("alrp_act", 0.0, 12.0 * G.numel()):
+        _lib.check(lib.te_alrp_act_f32(_ptr(G), _ptr(x), _ptr(out), G.numel(), _ALRP_KINDS[kind], _stream(G)),
+                   "te_alrp_act_f32")
+    return out
+
+
+def alrp_scale3(q: Tensor, k: Optional[Tensor] = None, v: Optional[Tensor] = None):
+    """IN PLACE: the uniform rule's exact factors on the gradients of an attention block.  One argument: a fused [..., 3C]
+    gradient whose thirds are multiplied by 1/4, 1/4, 1/2 (returned).  Three: the gradients of q, k, v, each [..., C]."""
+    ts = (q,) if k is None and v is None else (q, k, v)
+    if any(t is None for t in ts):
+        raise ValueError("alrp_scale3: give the fused gradient alone, or all of q, k, v")
+    for t in ts:
+        if not _prep(t).is_contiguous() or t.shape != ts[0].shape or t.dim() < 1:
+            raise _lib.TeError("alrp_scale3 works in place: contiguous float32 tensors of one shape")
+    if len(ts) == 1:
+        C3 = q.shape[-1]
+        if C3 % 3:
+            raise _lib.TeError(f"alrp_scale3: the last dimension of a fused gradient is 3C, got {C3}")
+        C, ld, T = C3 // 3, C3, q.numel() // C3
+        ptrs = [q.data_ptr() + 4 * i * C for i in range(3)]
+    else:
+        C = q.shape[-1]
+        ld, T = C, q.numel() // C
+        ptrs = [t.data_ptr() for t in ts]
+    with _on_device(q) as lib, _timed("alrp_scale3", 0.0, 24.0 * T * C):
+        _lib.check(lib.te_alrp_scale3_f32(*ptrs, ld, T, C, _stream(q)), "te_alrp_scale3_f32")
+    return q if len(ts) == 1 else ts
+
+
+def alrp_row_rstd(x: Tensor, eps: float) -> Tensor:
+    """x [..., C] -> fp32 [...]: 1 / sqrt(biased variance of the row + eps), the constant of the LayerNorm rule."""
+    x = _c(x)
+    C = x.shape[-1]
+    rstd = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+    with _on_device(x) as lib, _timed("alrp_row_rstd", 0.0, 4.0 * x.numel()):
+        _lib.check(lib.te_alrp_row_rstd_f32(_ptr(x), _ptr(rstd), x.numel() // C, C, float(eps), _stream(x)),
+                   "te_alrp_row_rstd_f32")
+    return rstd
+
+
+def alrp_layernorm(G: Tensor, gamma: Tensor, rstd: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """The LayerNorm rule with rstd held constant: G [..., C], gamma [C], rstd [...] -> rstd (gamma G - mean(gamma G))."""
+    G, gamma, rstd = _c(G), _c(gamma.detach()), _c(rstd)
+    C = G.shape[-1]
+    if tuple(gamma.shape) != (C,) or rstd.numel() != G.numel() // C:
+        raise _lib.TeError(f"alrp_layernorm: G {tuple(G.shape)} needs gamma [{C}] and one rstd per row, got "
+                           f"{tuple(gamma.shape)} and {tuple(rstd.shape)}")
+    out = _alrp_out(out, G, "alrp_layernorm")
+    with _on_device(G) as lib, _timed("alrp_layernorm", 0.0, 8.0 * G.numel()):
+        _lib.check(lib.te_alrp_layernorm_f32(_ptr(G), _ptr(gamma), _ptr(rstd), _ptr(out), G.numel() // C, C, _stream(G)),
+                   "te_alrp_layernorm_f32")
+    return out
+
+
+def alrp_token_relevance(x0: Tensor, G: Tensor, skip_first: bool = False) -> Tensor:
+    """x0, G [B,N,C] -> fp32 [B, N - skip_first]: sum_c x0 G per token in fp64, rounded once; skip_first drops token 0."""
+    x0, G = _c(x0), _c(G)
+    if x0.dim() != 3 or x0.shape != G.shape:
+        raise _lib.TeError(f"alrp_token_relevance: x0 and G must both be [B,N,C], got {tuple(x0.shape)} and {tuple(G.shape)}")
+    B, N, C = x0.shape
+    skip = int(bool(skip_first))
+    out = torch.empty((B, N - skip), dtype=torch.float32, device=x0.device)
+    with _on_device(x0) as lib, _timed("alrp_token_relevance", 0.0, 8.0 * x0.numel()):
+        _lib.check(lib.te_alrp_token_relevance_f32(_ptr(x0), _ptr(G), _ptr(out), B, N, C, skip, _stream(x0)),
+                   "te_alrp_token_relevance_f32")
+    return out
+
+
+def alrp_linear(G: Tensor, W: Tensor, cache: Optional[dict] = None) -> Tensor:
+    """The Linear rule's product G [..., out] . W [out, in] -> [..., in]: te_gemm_x6_f32 on the cached planes of W^T wherever
+    it takes the shape (gemm_x6_supported; X6_GEMM = "off" switches it off), the stock fp32 GEMM elsewhere -- the two
+    routes of the package's own input-gradient product (producers._Linear.backward).  Whatever USE_FUSED_PRODUCERS says."""
+    G = _prep(G)
+    out_f, in_f = W.shape
+    T = G.numel() // out_f
+    if X6_GEMM != "off" and gemm_x6_supported(T, out_f, in_f):
+        return gemm_x6(G, x6_matrix_planes(W, True, cache), None, in_f, "alrp_linear_x6")
+    return torch.matmul(G, W.detach())

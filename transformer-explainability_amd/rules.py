@@ -99,6 +99,11 @@ class RelProp(nn.Module):
     def relprop(self, R, alpha):
         return R
 
+    def attnlrp(self, G, eps):
+        """(extension) The module's AttnLRP rule (te_relprop.h, section "AttnLRP") on G, the relevance per unit of this
+        module's output, from the tensors forward_hook cached -> G of its input."""
+        raise NotImplementedError(f"{type(self).__name__}.attnlrp: AttnLRP has no rule for this module")
+
 
 class _Identity(RelProp):
     """Rules that pass relevance through unchanged (layers_ours.py:67-80,86-87) need no cached input."""
@@ -127,6 +132,11 @@ class GELU(nn.GELU, RelProp):
             return producers.gelu(x, nxt, x6_cache(nxt) if isinstance(nxt, Linear) else None)
         return super().forward(x)
 
+    def attnlrp(self, G, eps):
+        if getattr(self, "approximate", "none") != "none":
+            raise NotImplementedError("GELU.attnlrp: the identity rule is implemented for the exact (erf) GELU")
+        return ops.alrp_act(G, self.X, "gelu")
+
 
 class Softmax(nn.Softmax, RelProp):
     pass
@@ -139,13 +149,21 @@ class LayerNorm(nn.LayerNorm, RelProp):
             return producers.layer_norm(x, self)
         return super().forward(x)
 
+    def attnlrp(self, G, eps):
+        """rstd held constant (from the cached input and the layer's own eps); no damping: ``eps`` is not read."""
+        if len(self.normalized_shape) != 1:
+            raise NotImplementedError("LayerNorm.attnlrp: normalisation over the last dimension only")
+        gamma = self.weight if self.weight is not None else torch.ones(self.normalized_shape, device=G.device)
+        return ops.alrp_layernorm(G, gamma, ops.alrp_row_rstd(self.X, self.eps))
+
 
 class Dropout(nn.Dropout, RelProp):
     pass
 
 
 class Tanh(nn.Tanh, RelProp):
-    pass
+    def attnlrp(self, G, eps):
+        return ops.alrp_act(G, self.X, "tanh")
 
 
 # ------------------------------------------------------------------------------------------ hot path
@@ -192,6 +210,14 @@ class Linear(_ScratchCache, nn.Linear, RelProp):
     def relprop(self, R, alpha):
         return linear_rule(self, R, alpha)
 
+    def attnlrp(self, G, eps):
+        """G_x = damp(G_y, y) W on the cached output y (bias included)."""
+        Y = self.Y.detach()
+        if Y.shape != G.shape:
+            raise ops._lib.TeError(f"Linear.attnlrp: G {tuple(G.shape)} does not have the shape of the cached output "
+                                   f"{tuple(Y.shape)}")
+        return ops.alrp_linear(ops.alrp_damp(G, Y, eps), self.weight, x6_cache(self))
+
 
 def linear_rule(m, R, alpha, rows=None, variant=None):
     """The one route from a Linear layer `m` to ops.linear_relprop.  m.Y (the forward output, cached by forward_hook like
@@ -225,6 +251,10 @@ class Add(RelProp):
         a, b = ops.add_relprop(R, x0, x1, variant=self.variant,
                                deferred=deferred and ops.USE_DEFERRED_ADD and (x0.shape == x1.shape or bcast_mask))
         return [a, b]
+
+    def attnlrp(self, G, eps):
+        """A residual Add o = a + b: both operands receive damp(G_o, o) -- ONE tensor is returned."""
+        return ops.alrp_damp(G, self.Y.detach(), eps)
 
 
 class einsum(RelProp):
@@ -280,6 +310,25 @@ class MatMul(RelProp):
         raise NotImplementedError("MatMul.relprop: operand shapes are not an attention product")
 
 
+def attention_attnlrp(G_o, q, k, v, attn, num_heads, scale, d_q, d_k, d_v):
+    """The AttnLRP rule of o = softmax(scale q k^T (+ mask)) v for G_o [B,N,C] ('b n (h d)'): the block's own backward for
+    d_out = G_o, written into d_q / d_k / d_v ([B,N,C] views, like q / k / v), which the caller then scales by 1/4, 1/4, 1/2
+    (ops.alrp_scale3: the uniform rule).  On te_attention_backward_strided_f32 where it takes the shape, else the torch
+    expression of the same backward.  Reads cached tensors only: ops.USE_FUSED_PRODUCERS plays no part."""
+    B, N, C = G_o.shape
+    H, D = num_heads, C // num_heads
+    if ops._lib.load().te_attention_strided_supported(N, D):
+        ops.attention_backward_qkv(G_o, q, k, v, attn, H, scale, d_q, d_k, d_v, need_qk=True)
+        return
+    heads = lambda t: t.view(B, N, H, D).permute(0, 2, 1, 3)      # noqa: E731
+    go = heads(ops._c(G_o))
+    d_attn = torch.matmul(go, heads(v).transpose(-1, -2))
+    heads(d_v).copy_(torch.matmul(attn.transpose(-1, -2), go))
+    d_s = attn * (d_attn - (d_attn * attn).sum(dim=-1, keepdim=True))
+    heads(d_q).copy_(torch.matmul(d_s, heads(k)) * scale)
+    heads(d_k).copy_(torch.matmul(d_s.transpose(-1, -2), heads(q)) * scale)
+
+
 class Clone(RelProp):
     """layers_ours.py:151-169 -> te_clone_relprop_f32."""
 
@@ -289,6 +338,14 @@ class Clone(RelProp):
 
     def relprop(self, R, alpha):
         return ops.clone_relprop(list(R), self.X)
+
+    def attnlrp(self, G, eps):
+        """The paths that met at the cloned tensor add their G."""
+        G = list(G)
+        out = G[0] + G[1]
+        for g in G[2:]:
+            out += g
+        return out
 
 
 class IndexSelect(RelProp):
@@ -320,6 +377,16 @@ class IndexSelect(RelProp):
                                                       or getattr(self, "_index_version", idx._version) != idx._version)):
             host = int(idx)                                        # (device sync; not capturable)
         return ops.index_select_relprop(R, self.X, host)
+
+    def attnlrp(self, G, eps):
+        """Plain gradient of the class-token select: G [B,C] of the selected token -> [B,N,C], zero elsewhere."""
+        idx = self.indices
+        if self.dim != 1 or self.X.dim() != 3 or (torch.is_tensor(idx) and idx.numel() != 1):
+            raise NotImplementedError("IndexSelect.attnlrp: only dim=1 with a single index")
+        out = torch.zeros(self.X.shape, dtype=G.dtype, device=G.device)
+        out.index_copy_(1, idx.reshape(1) if torch.is_tensor(idx) else torch.tensor([int(idx)], device=G.device),
+                        G.reshape(G.shape[0], 1, -1))
+        return out
 
 
 class Sequential(nn.Sequential):

@@ -225,6 +225,11 @@ def make_vit_module(L):
             cam = self.fc2.relprop(cam, **kwargs)
             return self.fc1.relprop(cam, **kwargs)
 
+        def attnlrp(self, G, eps):
+            """(extension) AttnLRP: epsilon rule on both layers, identity rule through the activation, dropout plain."""
+            G = self.act.attnlrp(self.fc2.attnlrp(G, eps), eps)
+            return self.fc1.attnlrp(G, eps)
+
     class Attention(nn.Module):
         def __init__(self, dim, num_heads=8, qkv_bias=False, attn_drop=0., proj_drop=0.):
             super().__init__()
@@ -334,6 +339,21 @@ def make_vit_module(L):
                                   z=R_ours._cached_y(self.matmul1))
             return self.qkv.relprop(cam_qkv, **kwargs)
 
+        def attnlrp(self, G, eps):
+            """(extension) AttnLRP through proj, the attention block (its own backward for d_out = G_o, then the uniform
+            rule's 1/4, 1/4, 1/2) and qkv.  q / k / v are the thirds of the cached qkv activation, read in place; the
+            probabilities are the ones the accessor holds: the same tensors whichever forward produced them."""
+            if self.head_mask is not None:
+                raise ops._lib.TeError("Attention.attnlrp: head_mask is not implemented for AttnLRP")
+            G_o = self.proj.attnlrp(G, eps)
+            B, N, C = G_o.shape
+            qkv = self.qkv.Y.detach()
+            d_qkv = torch.empty_like(qkv)
+            third = lambda t, i: t[..., i * C:(i + 1) * C]      # noqa: E731
+            R_ours.attention_attnlrp(G_o, third(qkv, 0), third(qkv, 1), third(qkv, 2), self.get_attn().detach(),
+                                     self.num_heads, self.scale, third(d_qkv, 0), third(d_qkv, 1), third(d_qkv, 2))
+            return self.qkv.attnlrp(ops.alrp_scale3(d_qkv), eps)
+
     class Block(nn.Module):
         def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., norm_eps=1e-6):
             super().__init__()
@@ -373,6 +393,13 @@ def make_vit_module(L):
             cam1, cam2 = self.add1.relprop(cam, deferred=True, **kwargs)
             cam2 = self.attn.relprop(cam2, **kwargs)
             return self.clone1.relprop((cam1, cam2), **kwargs)
+
+        def attnlrp(self, G, eps):
+            """(extension) AttnLRP: each residual Add damps once and feeds both paths; the paths add up at the Clone."""
+            Gd = self.add2.attnlrp(G, eps)
+            G = self.clone2.attnlrp((Gd, self.norm2.attnlrp(self.mlp.attnlrp(Gd, eps), eps)), eps)
+            Gd = self.add1.attnlrp(G, eps)
+            return self.clone1.attnlrp((Gd, self.norm1.attnlrp(self.attn.attnlrp(Gd, eps), eps)), eps)
 
         def relprop_cls_only(self, cam_cls, **kwargs):
             """Block.relprop for relevance that lives on token 0 only (cam_cls [B,1,C]) -- the state right after
@@ -535,6 +562,16 @@ def make_vit_module(L):
 
             maps = {m: relprop_tail(self, m, cam, is_ablation, start_layer, prune, **kwargs) for m in wanted}
             return maps if several else maps[method]
+
+        def attnlrp(self, seed, eps=1e-6):
+            """(extension) AttnLRP (te_relprop.h, section "AttnLRP"): ``seed`` [B, num_classes] (the one-hot of the class) ->
+            fp32 [B, N-1], the relevance of the patch tokens.  One chain over the caches of the last forward pass; no
+            backward pass.  The position-embedding Add is a parameter Add: plain."""
+            G = self.head.attnlrp(seed, eps)
+            G = self.norm.attnlrp(self.pool.attnlrp(G, eps), eps)
+            for blk in reversed(self.blocks):
+                G = blk.attnlrp(G, eps)
+            return ops.alrp_token_relevance(self.add.X[0], G, skip_first=True)
 
     def vit_base_patch16_224(pretrained=False, **kwargs):
         model = VisionTransformer(patch_size=16, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4, qkv_bias=True,
