@@ -86,9 +86,9 @@ def main():
         if not args.lib or "prev" in args.lib:
             lib.te_linear_zpass_fwd_f32.restype = ctypes.c_int
             lib.te_linear_zpass_fwd_f32.argtypes = _lib.SIGNATURES["te_linear_zpass_fwd_f32"][1]
-            legs.insert(1, ("zfwd", lib.te_linear_zpass_fwd_f32, (R, X, W, Y, bias, S), 2.0 * T * in_f * out_f))
+            legs.insert(1, ("zfwd", lib.te_linear_zpass_fwd_f32, (R, None, 0, 1, X, W, Y, bias, S), 2.0 * T * in_f * out_f))      # no r_scale
         for kname, fn, a, flops in legs:
-            ptrs = [t.data_ptr() for t in a]
+            ptrs = [t.data_ptr() if torch.is_tensor(t) else t for t in a]
             for _ in range(2):
                 _lib.check(fn(*ptrs, T, in_f, out_f, st), kname)
             torch.cuda.synchronize()

@@ -91,24 +91,19 @@ int te_linear_cpass_f32(const float* S, const float* X, const float* W, float* o
  * sum, so zero rows and near-zero Z behave as in layers_ours.py:216-219.  in_f, out_f multiples of 4 and 16-byte
  * aligned pointers (else TE_ERR_UNSUPPORTED: use te_linear_relprop_f32).  Workspace: te_linear_relprop_workspace_bytes
  * (T, in_f, out_f, TE_VARIANT_OURS).
- *   zpass_fwd: S [T,out_f] = sd(R, Z)          relprop_fwd: zpass_fwd, then te_linear_cpass_f32 */
-int te_linear_zpass_fwd_f32(const float* R, const float* X, const float* W, const float* Y, const float* bias,
-                            float* S, int64_t T, int64_t in_f, int64_t out_f, te_stream_t stream);
-int te_linear_relprop_fwd_f32(const float* R, const float* X, const float* W, const float* Y, const float* bias,
-                              float* out, int64_t T, int64_t in_f, int64_t out_f,
-                              void* ws, size_t ws_bytes, te_stream_t stream);
-
-/* The same with a DEFERRED per-sample factor on the relevance operand: row t of R enters the rule as
+ *   zpass_fwd: S [T,out_f] = sd(R, Z)          relprop_fwd: zpass_fwd, then te_linear_cpass_f32
+ * r_scale (optional, NULL = plain R): a DEFERRED per-sample factor on the relevance operand.  Row t of R enters the rule as
  * R[t,:] * r_scale[(t / rows_per_sample) * r_scale_stride] (the fp32 product Add.relprop's rescale would have stored,
- * layers_ours.py:117-118) -- the consumer side of te_add_relprop_deferred_f32.  r_scale == NULL: plain R. */
-int te_linear_zpass_fwd_scaled_f32(const float* R, const float* r_scale, int64_t r_scale_stride,
-                                   int64_t rows_per_sample, const float* X, const float* W, const float* Y,
-                                   const float* bias, float* S, int64_t T, int64_t in_f, int64_t out_f,
-                                   te_stream_t stream);
-int te_linear_relprop_fwd_scaled_f32(const float* R, const float* r_scale, int64_t r_scale_stride,
-                                     int64_t rows_per_sample, const float* X, const float* W, const float* Y,
-                                     const float* bias, float* out, int64_t T, int64_t in_f, int64_t out_f,
-                                     void* ws, size_t ws_bytes, te_stream_t stream);
+ * layers_ours.py:117-118) -- the consumer side of te_add_relprop_deferred_f32.  Without it r_scale_stride and
+ * rows_per_sample are ignored. */
+int te_linear_zpass_fwd_f32(const float* R, const float* r_scale, int64_t r_scale_stride,
+                            int64_t rows_per_sample, const float* X, const float* W, const float* Y,
+                            const float* bias, float* S, int64_t T, int64_t in_f, int64_t out_f,
+                            te_stream_t stream);
+int te_linear_relprop_fwd_f32(const float* R, const float* r_scale, int64_t r_scale_stride,
+                              int64_t rows_per_sample, const float* X, const float* W, const float* Y,
+                              const float* bias, float* out, int64_t T, int64_t in_f, int64_t out_f,
+                              void* ws, size_t ws_bytes, te_stream_t stream);
 
 /* ---- a4  einsum / MatMul relprop (RelPropSimple) ---------------------------------------------
  * replaces modules/layers_ours.py:48-60,122-127 and BERT_explainability/modules/layers_ours.py:89-91
@@ -123,62 +118,35 @@ int te_linear_relprop_fwd_scaled_f32(const float* R, const float* r_scale, int64
  *   Z = attn v ; S = sd(R,Z) ; cam_attn = attn .(S v^T) ; cam_v = v .(attn^T S)
  * QK  (einsum 'bhid,bhjd->bhij'; BERT MatMul([Q, K^T])), Z uses the UNSCALED q k^T:
  *   Z = q k^T ; S = sd(R_nn,Z) ; cam_q = q .(S k) ; cam_k = k .(S^T q)
+ *
+ * Optional operands (NULL = absent; the strides of an absent operand are ignored):
+ *   Z        the FORWARD output of the product whose rule is evaluated (einsum / MatMul modules cache it as self.Y,
+ *            forward_hook layers_ours.py:16-27).  The reference's autograd re-evaluates that product and gets the same
+ *            bits, so the rule needs two products instead of three and S matches the forward pass exactly.  Absent: the
+ *            product is formed in the workspace.
+ *            AV: element (b,h,n,d) at Z + b*z_sb + h*z_sh + n*z_sn + d.  The product attn v usually lives only as the
+ *            'b n (h d)' activation that feeds the output projection (ViT_LRP.py:148): z_sb = N*C, z_sh = D, z_sn = C
+ *            reads it in place; a contiguous [B,H,N,D] copy has z_sb = H*N*D, z_sh = N*D, z_sn = D.  Only the one-pass
+ *            kernels (head dim 64) take other strides than the contiguous ones: TE_ERR_UNSUPPORTED otherwise.
+ *            QK: contiguous [B,H,N,N].
+ *   r_scale  (QK) a DEFERRED per-sample factor on the relevance operand: sample b's R_nn enters as
+ *            R_nn[b] * r_scale[b * r_scale_stride] -- the consumer side of te_add_bcast_relprop_deferred_f32
+ *            (BERT.py:386-393).  One-pass kernels only (head dim 64): TE_ERR_UNSUPPORTED otherwise.
  */
 size_t te_matmul_relprop_av_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t D);
 int te_matmul_relprop_av_f32(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn,
                              const float* attn,
                              const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                             const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn,
                              float* cam_attn,
                              float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn,
                              int64_t B, int64_t H, int64_t N, int64_t D, float out_scale, int variant,
                              void* ws, size_t ws_bytes, te_stream_t stream);
 size_t te_matmul_relprop_qk_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t D);
-/* The same two rules with Z supplied by the caller: Z is the FORWARD output of the product whose rule is evaluated
- * (einsum / MatMul modules cache it as self.Y, forward_hook layers_ours.py:16-27; contiguous [B,H,N,D] for AV,
- * [B,H,N,N] = unscaled q k^T for QK).  The reference's autograd re-evaluates that product and gets the same bits, so
- * the rule needs two products instead of three and S matches the forward pass exactly.  Z == NULL computes it. */
-int te_matmul_relprop_av_fwd_f32(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn,
-                                 const float* attn,
-                                 const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sn,
-                                 const float* Z,
-                                 float* cam_attn,
-                                 float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn,
-                                 int64_t B, int64_t H, int64_t N, int64_t D, float out_scale, int variant,
-                                 void* ws, size_t ws_bytes, te_stream_t stream);
-/* te_matmul_relprop_av_fwd_f32 with a STRIDED Z (element (b,h,n,d) at Z + b*z_sb + h*z_sh + n*z_sn + d): the forward
- * product attn v usually lives only as the 'b n (h d)' activation that feeds the output projection (ViT_LRP.py:148);
- * z_sb = N*C, z_sh = D, z_sn = C reads it in place.  One-pass kernels only (head dim 64): TE_ERR_UNSUPPORTED otherwise
- * (callers then pass a contiguous copy to te_matmul_relprop_av_fwd_f32). */
-int te_matmul_relprop_av_fwdz_f32(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn,
-                                  const float* attn,
-                                  const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sn,
-                                  const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn,
-                                  float* cam_attn,
-                                  float* cam_v, int64_t cv_sb, int64_t cv_sh, int64_t cv_sn,
-                                  int64_t B, int64_t H, int64_t N, int64_t D, float out_scale, int variant,
-                                  void* ws, size_t ws_bytes, te_stream_t stream);
-int te_matmul_relprop_qk_fwd_f32(const float* R_nn,
-                                 const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
-                                 const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
-                                 const float* Z,
-                                 float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn,
-                                 float* cam_k, int64_t ck_sb, int64_t ck_sh, int64_t ck_sn,
-                                 int64_t B, int64_t H, int64_t N, int64_t D, float out_scale, int variant,
-                                 void* ws, size_t ws_bytes, te_stream_t stream);
-/* te_matmul_relprop_qk_fwd_f32 whose relevance operand carries a DEFERRED per-sample factor: sample b's R_nn enters as
- * R_nn[b] * r_scale[b * r_scale_stride] -- the consumer side of te_add_bcast_relprop_deferred_f32 (BERT.py:386-393).
- * r_scale == NULL: plain.  One-pass kernels only (head dim 64): TE_ERR_UNSUPPORTED otherwise. */
-int te_matmul_relprop_qk_fwd_scaled_f32(const float* R_nn, const float* r_scale, int64_t r_scale_stride,
-                                        const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
-                                        const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
-                                        const float* Z,
-                                        float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn,
-                                        float* cam_k, int64_t ck_sb, int64_t ck_sh, int64_t ck_sn,
-                                        int64_t B, int64_t H, int64_t N, int64_t D, float out_scale, int variant,
-                                        void* ws, size_t ws_bytes, te_stream_t stream);
-int te_matmul_relprop_qk_f32(const float* R_nn,
+int te_matmul_relprop_qk_f32(const float* R_nn, const float* r_scale, int64_t r_scale_stride,
                              const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
                              const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                             const float* Z,
                              float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn,
                              float* cam_k, int64_t ck_sb, int64_t ck_sh, int64_t ck_sn,
                              int64_t B, int64_t H, int64_t N, int64_t D, float out_scale, int variant,
@@ -200,7 +168,7 @@ int te_add_relprop_f32(const float* R, const float* X0, const float* X1, float* 
  * algorithmic 5 n floats per sample) writes a = X0.S and b = X1.S unscaled and fac [B,2] = {fa, fb} per sample, where
  * te_add_relprop_f32 would have stored out0 = a*fa, out1 = b*fb (layers_ours.py:117-118).  The consumers take the
  * factor with the operand and form the identical product in registers: te_clone_relprop_scaled_f32,
- * te_linear_relprop_fwd_scaled_f32.  Workspace: te_add_relprop_deferred_workspace_bytes. */
+ * te_linear_relprop_fwd_f32.  Workspace: te_add_relprop_deferred_workspace_bytes. */
 size_t te_add_relprop_deferred_workspace_bytes(int64_t B, int64_t n);
 int te_add_relprop_deferred_f32(const float* R, const float* X0, const float* X1, float* a, float* b, float* fac,
                                 int64_t B, int64_t n, int64_t x1_batch_stride,
@@ -218,7 +186,7 @@ int te_add_bcast_relprop_f32(const float* R, const float* X0, const float* mask,
 
 /* The same rule (variant ours) with the rescale deferred: ONE pass over R and X0 writes a = X0.S unscaled and
  * fac [B,2] = {fa, fb}; out1 [B,N] (optional) is written scaled.  a * fa is bitwise te_add_bcast_relprop_f32's out0;
- * the consumer is te_matmul_relprop_qk_fwd_scaled_f32.  Workspace: te_add_bcast_relprop_workspace_bytes. */
+ * the consumer is te_matmul_relprop_qk_f32.  Workspace: te_add_bcast_relprop_workspace_bytes. */
 int te_add_bcast_relprop_deferred_f32(const float* R, const float* X0, const float* mask, float* a, float* out1,
                                       float* fac, int64_t B, int64_t H, int64_t N,
                                       void* ws, size_t ws_bytes, te_stream_t stream);
@@ -263,7 +231,7 @@ size_t te_rollout_row0_workspace_bytes(int64_t B, int64_t N);
 int te_rollout_f32(const float* cams, int64_t L, int64_t start_layer, int64_t B, int64_t N,
                    int flags, float* joint, void* ws, size_t ws_bytes, te_stream_t stream);
 
-/* te_linear_relprop_fwd_scaled_f32 (same rule: modules/layers_ours.py:207-230, variant ours, alpha = 1, Z from the
+/* te_linear_relprop_fwd_f32 (same rule: modules/layers_ours.py:207-230, variant ours, alpha = 1, Z from the
  * forward output, optional per-sample factor on R) with its three products on bf16 MFMAs at fp32 accuracy: every fp32
  * operand is used as the exact sum of three bf16 parts and the six partial products above 2^-24 are accumulated in fp32
  * (csrc/te_linear_x6.hip).  in_f, out_f >= 128, out_f % 128 == 0, in_f % 64 == 0.
@@ -386,26 +354,24 @@ int te_gelu_forward_x6_planes_f32(const float* x, float* y, int64_t rows, int64_
  *   backward: d_attn [B,H,N,N] = d_out v^T (the attention gradient of the explanation) ; d_qkv [B,N,3*H*D]:
  *             d_v = attn^T d_out always ; need_qk != 0 additionally d_s = attn .(d_attn - rowsum(d_attn . attn)) * scale,
  *             d_q = d_s k, d_k = d_s^T q (need_qk == 0: the q / k thirds of d_qkv are left untouched -- the lowest
- *             block whose attention gradient is wanted has no consumer for them). */
+ *             block whose attention gradient is wanted has no consumer for them).
+ * Optional operands (NULL = absent):
+ *   out_planes (forward, round 6): the operand planes of `out` for the projection layer's x6 kernels -- the signed planes of
+ *             out [B N, H D]; out_abs_planes (optional with them; alone it is TE_ERR_INVALID_ARG) = the planes of |out|.  Each
+ *             te_linear_x6_planes_bytes(B N, H D) bytes = planes_bytes (else TE_ERR_WORKSPACE), bit for bit what
+ *             te_linear_x6_split_dual_f32 writes from the fp32 tensor (te_gemm_x6_f32's x_planes / the rule's x_abs_planes).
+ *             Absent: no planes are written and planes_bytes is ignored.
+ *   out (backward, round 6): the block's forward output [B,N,H*D] (what te_attention_forward_f32 wrote).  The row sums of the
+ *             softmax backward are then taken as sum_d d_out[i][d] out[i][d] (= sum_j attn[i][j] d_attn[i][j]: out = attn v,
+ *             d_attn = d_out v^T) instead of from a pass over the two N x N tensors.  The two agree to fp32 rounding
+ *             (another summation of the same quantity), not bit for bit. */
 int te_attention_forward_supported(int64_t N, int64_t D);
-int te_attention_forward_f32(const float* qkv, float* z_qk, float* attn, float* out,
-                             int64_t B, int64_t H, int64_t N, int64_t D, float scale, te_stream_t stream);
-/* te_attention_forward_f32 that also writes the operand planes of `out` for the projection layer's x6 kernels (round 6): out_planes =
- * the signed planes of out [B N, H D], out_abs_planes (optional) = the planes of |out|, each te_linear_x6_planes_bytes(B N, H D)
- * bytes, bit for bit what te_linear_x6_split_dual_f32 writes from the fp32 tensor (te_gemm_x6_f32's x_planes / the rule's
- * x_abs_planes).  N <= 224. */
-int te_attention_forward_planes_f32(const float* qkv, float* z_qk, float* attn, float* out, void* out_planes,
-                                    void* out_abs_planes, size_t planes_bytes, int64_t B, int64_t H, int64_t N, int64_t D,
-                                    float scale, te_stream_t stream);
-int te_attention_backward_f32(const float* d_out, const float* qkv, const float* attn, float* d_attn, float* d_qkv,
-                              int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk, te_stream_t stream);
-/* The same with the block's forward output `out` [B,N,H*D] (what te_attention_forward_f32 wrote) at hand (round 6): the row
- * sums of the softmax backward are then taken as sum_d d_out[i][d] out[i][d] (= sum_j attn[i][j] d_attn[i][j]: out = attn v,
- * d_attn = d_out v^T) instead of from a pass over the two N x N tensors.  Results agree with te_attention_backward_f32 to
- * fp32 rounding (another summation of the same quantity), not bit for bit. */
-int te_attention_backward_out_f32(const float* d_out, const float* out, const float* qkv, const float* attn, float* d_attn,
-                                  float* d_qkv, int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk,
-                                  te_stream_t stream);
+int te_attention_forward_f32(const float* qkv, float* z_qk, float* attn, float* out, void* out_planes,
+                             void* out_abs_planes, size_t planes_bytes, int64_t B, int64_t H, int64_t N, int64_t D,
+                             float scale, te_stream_t stream);
+int te_attention_backward_f32(const float* d_out, const float* out, const float* qkv, const float* attn, float* d_attn,
+                              float* d_qkv, int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk,
+                              te_stream_t stream);
 
 /* The same producers for the shapes the one-workgroup-per-head kernels cannot hold (csrc/te_attn_long.hip): head dim 64,
  * N <= 640 (ViT-L/16 at 384^2: 577, baselines/ViT/ViT_LRP.py:419-425; BERT: 512), q / k / v / out / gradients as
@@ -415,7 +381,11 @@ int te_attention_backward_out_f32(const float* d_out, const float* out, const fl
  *             the Add module, BERT.py:339-342 (Add.relprop divides by x_scaled + mask: the mask must not be in it twice) ;
  *             x = x_scaled + mask[b, key] (mask [B,N] additive, NULL = none) ; attn = softmax(x) ; out = attn v
  *   backward: d_attn = d_out v^T ; d_v = attn^T d_out ; need_qk: d_q = d_s k, d_k = d_s^T q with
- *             d_s = ((d_attn - rowsum(d_attn . attn)) . attn) * scale.  Workspace: B*H*N floats. */
+ *             d_s = ((d_attn - rowsum(d_attn . attn)) . attn) * scale.  Workspace: B*H*N floats.
+ *             out (optional, NULL = absent and o_sb / o_sh / o_sn ignored): the block's forward output, the [B,H,N,64] view
+ *             te_attention_forward_strided_f32 wrote.  The row sums sum_j d_attn . attn are then taken as d_out . out
+ *             (out = attn v, d_attn = d_out v^T), which lets the row side run in ONE walk over the keys on bf16 MFMAs
+ *             (csrc/te_attn_bwd6l.hip, 64 < N <= 640; other lengths: the same kernels as without it). */
 int te_attention_strided_supported(int64_t N, int64_t D);
 size_t te_attention_backward_strided_workspace_bytes(int64_t B, int64_t H, int64_t N);
 int te_attention_forward_strided_f32(const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
@@ -425,6 +395,7 @@ int te_attention_forward_strided_f32(const float* q, int64_t q_sb, int64_t q_sh,
                                      float* out, int64_t o_sb, int64_t o_sh, int64_t o_sn,
                                      int64_t B, int64_t H, int64_t N, int64_t D, float scale, te_stream_t stream);
 int te_attention_backward_strided_f32(const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn,
+                                      const float* out, int64_t o_sb, int64_t o_sh, int64_t o_sn,
                                       const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
                                       const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
                                       const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sn,
@@ -434,22 +405,6 @@ int te_attention_backward_strided_f32(const float* d_out, int64_t do_sb, int64_t
                                       float* d_v, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
                                       int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk,
                                       void* ws, size_t ws_bytes, te_stream_t stream);
-/* te_attention_backward_strided_f32 with the block's forward output `out` ([B,H,N,64] view, the tensor
- * te_attention_forward_strided_f32 wrote) as one more operand: the softmax backward's row sums sum_j d_attn . attn are taken
- * as d_out . out (out = attn v, d_attn = d_out v^T), which lets the row side run in ONE walk over the keys on bf16 MFMAs
- * (csrc/te_attn_bwd6l.hip, 64 < N <= 640; other lengths: the kernels of te_attention_backward_strided_f32).  Replaces the same
- * autograd nodes (ViT_LRP.py:144-145, BERT.py:349-350). */
-int te_attention_backward_strided_out_f32(const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn,
-                                          const float* out, int64_t o_sb, int64_t o_sh, int64_t o_sn,
-                                          const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
-                                          const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
-                                          const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sn,
-                                          const float* attn, float* d_attn,
-                                          float* d_q, int64_t dq_sb, int64_t dq_sh, int64_t dq_sn,
-                                          float* d_k, int64_t dk_sb, int64_t dk_sh, int64_t dk_sn,
-                                          float* d_v, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
-                                          int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk,
-                                          void* ws, size_t ws_bytes, te_stream_t stream);
 
 /* The LayerNorm and GELU layers around the Linear rules (modules/layers_ours.py:70-77; ViT_LRP.py:57,184,187,266;
  * BERT.py:18,52,416,463): their relprop rules are the identity, the path needs their forward values (the X / Y the
@@ -822,8 +777,8 @@ int te_linear_bf16_prepare_weights(const te_bf16_t* W, int64_t in_f, int64_t out
 int te_linear_relprop_bf16(const float* R, int64_t r_ld, const float* r_scale, int64_t r_scale_stride,
                            int64_t rows_per_scale, const te_bf16_t* X, int64_t x_ld, const void* w_planes, float* out,
                            int64_t T, int64_t in_f, int64_t out_f, void* ws, size_t ws_bytes, te_stream_t stream);
-/* The two attention rules with bf16 operands: the argument lists of te_matmul_relprop_av_fwdz_f32 and
- * te_matmul_relprop_qk_fwd_scaled_f32.  attn, Z (QK) contiguous; q / k / v / Z (AV) strided with a contiguous last dim
+/* The two attention rules with bf16 operands: the argument lists of te_matmul_relprop_av_f32 and
+ * te_matmul_relprop_qk_f32.  attn, Z (QK) contiguous; q / k / v / Z (AV) strided with a contiguous last dim
  * (views of the fused qkv activation are read in place).  Z == NULL: recomputed in fp32 from the bf16 operands.
  * Shapes: te_matmul_relprop_bf16_supported (head dim 64, N <= 1024); variant ours only. */
 int te_matmul_relprop_bf16_supported(int64_t N, int64_t D);
@@ -952,7 +907,7 @@ size_t te_linear_relprop_f64_workspace_bytes(int64_t T, int64_t in_f, int64_t ou
 int te_linear_relprop_f64(const double* R, int64_t r_ld, const double* X, int64_t x_ld, const double* W, int64_t w_ld,
                           double* out, int64_t T, int64_t in_f, int64_t out_f, void* ws, size_t ws_bytes,
                           te_stream_t stream);
-/* The two attention rules: the arguments of te_matmul_relprop_av_fwdz_f32 / te_matmul_relprop_qk_fwd_scaled_f32 without a
+/* The two attention rules: the arguments of te_matmul_relprop_av_f32 / te_matmul_relprop_qk_f32 without a
  * variant and a relevance factor.  Z (the product whose rule is evaluated: attn v [B,H,N,D] strided, the UNSCALED q k^T
  * [B,H,N,N] contiguous) is always an operand.  attn, R (QK) and cam_attn contiguous; R (AV), q, k, v and the cam_q / cam_k /
  * cam_v outputs strided with a contiguous last dim.  S = sd(R, Z) in ws;

@@ -29,9 +29,15 @@ def test_entry_points_declared_bound_and_exported(lib):
         assert re.search(r"\b%s\s*\(" % name, header), f"{name} is not declared in te_relprop.h"
         assert name in _lib.SIGNATURES, f"{name} is not bound in _lib.SIGNATURES"
         assert hasattr(lib, name), f"{name} is not exported by libte_relprop.so"
-    # the argument lists of the _strided_f32 entry points
-    for kind in ("forward", "backward"):
-        assert _lib.SIGNATURES[f"te_attention_{kind}_strided_bf16"] == _lib.SIGNATURES[f"te_attention_{kind}_strided_f32"]
+    # the argument lists of the _strided_f32 entry points; the backward without the fp32 form's optional forward output `out`
+    # and its three strides, which the bf16 kernels do not take
+    assert _lib.SIGNATURES["te_attention_forward_strided_bf16"] == _lib.SIGNATURES["te_attention_forward_strided_f32"]
+    assert _lib.PARAMS["te_attention_forward_strided_bf16"] == _lib.PARAMS["te_attention_forward_strided_f32"]
+    f32 = _lib.PARAMS["te_attention_backward_strided_f32"]
+    assert f32[4:8] == ("out", "o_sb", "o_sh", "o_sn")
+    assert _lib.PARAMS["te_attention_backward_strided_bf16"] == f32[:4] + f32[8:]
+    types = _lib.SIGNATURES["te_attention_backward_strided_f32"]
+    assert _lib.SIGNATURES["te_attention_backward_strided_bf16"] == (types[0], types[1][:4] + types[1][8:])
     assert "te_attn_bf16.hip" in open(os.path.join(ROOT, "transformer-explainability_amd", "build.py")).read()
 
 

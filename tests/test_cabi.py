@@ -132,9 +132,9 @@ def test_binding_pinned_facts():
     args = S["te_map_similarity_f32"][1]
     assert len(args) == 13 and [i for i, t in enumerate(args) if t is c_double] == [9]
     assert _lib.PARAMS["te_map_similarity_f32"][9] == "data_range"
-    res, args = S["te_attention_backward_strided_out_f32"]
+    res, args = S["te_attention_backward_strided_f32"]
     assert res is c_int and len(args) == 43 and args[-4:] == [c_int, c_void_p, c_size_t, c_void_p]
-    assert _lib.PARAMS["te_attention_backward_strided_out_f32"][-4:] == ("need_qk", "ws", "ws_bytes", "stream")
+    assert _lib.PARAMS["te_attention_backward_strided_f32"][-4:] == ("need_qk", "ws", "ws_bytes", "stream")
     assert all(len(_lib.PARAMS[n]) == len(S[n][1]) for n in S) and sorted(_lib.PARAMS) == sorted(S)
     assert _lib.TE_OK == 0 and _lib.TE_ERR_NO_DEVICE == -4 and _lib.TE_IMPL_SIMPLE == 0x100
     assert _lib.TE_X6_WHOLE_TILES == 0x10000 and ops.TE_X6_WHOLE_TILES == 0x10000
@@ -150,7 +150,7 @@ def test_binding_follows_the_header():
     from ctypes import c_int64
     cabi = _cabi()
     text = open(HEADER).read()
-    victim, gone = "te_attention_backward_strided_out_f32", "int64_t dk_sh, "
+    victim, gone = "te_attention_backward_strided_f32", "int64_t dk_sh, "
     at = text.index(gone, text.index(f"int {victim}("))
     assert at < text.index(";", text.index(f"int {victim}("))                   # inside the victim's argument list
     before, consts = cabi.parse(text)
@@ -160,6 +160,65 @@ def test_binding_follows_the_header():
     params = before[victim][1]
     i = [p for p, _ in params].index("dk_sh")
     assert params[i][1] is c_int64 and after[victim][1] == params[:i] + params[i + 1:]
+
+
+# The entry points that replaced a family of names (0.8.0): name -> (what the retired names of its family ended in instead of
+# "_f32", the most general one last; the parameter names of that most general entry as they stood before the merge).  ops.py
+# passes every argument by position: a transposed pair would be a wild pointer on the device.
+_BHND = ("B", "H", "N", "D")
+_WS = ("ws", "ws_bytes", "stream")
+MERGED = {
+    "te_matmul_relprop_av_f32": (("_fwd_f32", "_fwdz_f32"), (
+        "R", "r_sb", "r_sh", "r_sn", "attn", "v", "v_sb", "v_sh", "v_sn", "Z", "z_sb", "z_sh", "z_sn", "cam_attn",
+        "cam_v", "cv_sb", "cv_sh", "cv_sn", *_BHND, "out_scale", "variant", *_WS)),
+    "te_matmul_relprop_qk_f32": (("_fwd_f32", "_fwd_scaled_f32"), (
+        "R_nn", "r_scale", "r_scale_stride", "q", "q_sb", "q_sh", "q_sn", "k", "k_sb", "k_sh", "k_sn", "Z",
+        "cam_q", "cq_sb", "cq_sh", "cq_sn", "cam_k", "ck_sb", "ck_sh", "ck_sn", *_BHND, "out_scale", "variant", *_WS)),
+    "te_linear_zpass_fwd_f32": (("_scaled_f32",), (
+        "R", "r_scale", "r_scale_stride", "rows_per_sample", "X", "W", "Y", "bias", "S", "T", "in_f", "out_f", "stream")),
+    "te_linear_relprop_fwd_f32": (("_scaled_f32",), (
+        "R", "r_scale", "r_scale_stride", "rows_per_sample", "X", "W", "Y", "bias", "out", "T", "in_f", "out_f", *_WS)),
+    "te_attention_forward_f32": (("_planes_f32",), (
+        "qkv", "z_qk", "attn", "out", "out_planes", "out_abs_planes", "planes_bytes", *_BHND, "scale", "stream")),
+    "te_attention_backward_f32": (("_out_f32",), (
+        "d_out", "out", "qkv", "attn", "d_attn", "d_qkv", *_BHND, "scale", "need_qk", "stream")),
+    "te_attention_backward_strided_f32": (("_out_f32",), (
+        "d_out", "do_sb", "do_sh", "do_sn", "out", "o_sb", "o_sh", "o_sn", "q", "q_sb", "q_sh", "q_sn",
+        "k", "k_sb", "k_sh", "k_sn", "v", "v_sb", "v_sh", "v_sn", "attn", "d_attn", "d_q", "dq_sb", "dq_sh", "dq_sn",
+        "d_k", "dk_sb", "dk_sh", "dk_sn", "d_v", "dv_sb", "dv_sh", "dv_sn", *_BHND, "scale", "need_qk", *_WS)),
+}
+RETIRED = sorted(name[:-len("_f32")] + end for name, (ends, _) in MERGED.items() for end in ends)
+
+
+def test_merged_entry_points_keep_the_general_argument_lists():
+    from transformer_explainability_amd import _lib
+    for name, (_, params) in MERGED.items():
+        assert _lib.PARAMS[name] == params, name
+    assert len(MERGED["te_attention_backward_strided_f32"][1]) == 43
+    # the fp32 and the bf16 form of a rule: one argument list under one base name
+    assert _lib.PARAMS["te_matmul_relprop_av_f32"] == _lib.PARAMS["te_matmul_relprop_av_bf16"]
+    assert _lib.PARAMS["te_matmul_relprop_qk_f32"] == _lib.PARAMS["te_matmul_relprop_qk_bf16"]
+
+
+def test_retired_entry_points_are_gone(lib):
+    from transformer_explainability_amd import _lib
+    assert len(RETIRED) == 9 and len(set(RETIRED)) == 9
+    declared = declared_symbols()
+    for name in RETIRED:
+        assert name not in declared and name not in _lib.SIGNATURES and name not in _lib.PARAMS, name
+        assert not hasattr(lib, name), f"{name} is still exported by libte_relprop.so"
+
+
+def test_loader_refuses_an_older_library(lib, monkeypatch):
+    """A library older than MIN_LIB_VERSION is refused by the version check, before the build id is looked at."""
+    from transformer_explainability_amd import _lib
+    assert _lib.MIN_LIB_VERSION == 800 and lib.te_version() >= 800
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "MIN_LIB_VERSION", lib.te_version() + 1)
+    with pytest.raises(_lib.TeError, match=f"needs >= {lib.te_version() + 1}"):
+        _lib.load()
+    monkeypatch.undo()
+    assert _lib.load().te_version() == lib.te_version()
 
 
 def test_version_and_status_strings(lib):
@@ -192,18 +251,25 @@ def test_argument_validation_without_device(lib):
     assert lib.te_clone_relprop_f32(None, None, None, None, None, 16, None) == -1
     assert lib.te_linear_relprop_f32(None, None, None, None, 1, 4, 4, 1.0, 0, None, 0, None) == -1
     assert lib.te_rollout_f32(None, 1, 0, 1, 4, 0, None, None, 0, None) == -1
+    assert lib.te_linear_zpass_fwd_f32(None, None, 0, 1, None, None, None, None, None, 1, 4, 4, None) == -1
+    assert lib.te_linear_relprop_fwd_f32(None, None, 0, 1, None, None, None, None, None, 1, 4, 4, None, 0, None) == -1
+    assert lib.te_matmul_relprop_av_f32(None, 64, 64, 64, None, None, 64, 64, 64, None, 0, 0, 0, None, None, 64, 64, 64,
+                                        1, 1, 4, 64, 1.0, 0, None, 0, None) == -1
+    assert lib.te_matmul_relprop_qk_f32(None, None, 0, None, 64, 64, 64, None, 64, 64, 64, None, None, 64, 64, 64,
+                                        None, 64, 64, 64, 1, 1, 4, 64, 1.0, 0, None, 0, None) == -1
 
 
 def test_attention_entry_points_reject_on_the_host(lib):
     """What every fp32 attention entry point answers before it touches a device: the status of each refusal.  P is a fake non-null,
     16-byte-aligned address that the host never dereferences; every call below returns before the first HIP call."""
+    from transformer_explainability_amd._lib import PARAMS
     P, B, H, N, D = 4096, 2, 2, 100, 64
     C = H * D
     view = lambda name: {name + "_sb": N * C, name + "_sh": 64, name + "_sn": C}      # noqa: E731
     dims = dict(B=B, H=H, N=N, D=D)
 
     def status(fn, base, **changed):
-        assert set(changed) <= set(base), changed
+        assert set(changed) <= set(base) and len(base) == len(PARAMS[fn]), (fn, changed)
         return getattr(lib, fn)(*{**base, **changed}.values())
 
     fwd_s = dict(q=P, **view("q"), k=P, **view("k"), v=P, **view("v"), mask=None, z_qk=P, x_scaled=None, attn=P, out=P, **view("o"),
@@ -213,45 +279,54 @@ def test_attention_entry_points_reject_on_the_host(lib):
     assert [status(f, fwd_s, N=641), status(f, fwd_s, D=80), status(f, fwd_s, q_sn=66)] == [-3, -3, -3]
 
     ws_bytes = lib.te_attention_backward_strided_workspace_bytes(B, H, N)
-    bwd_s = dict(d_out=P, **view("do"), q=P, **view("q"), k=P, **view("k"), v=P, **view("v"), attn=P, d_attn=P, d_q=P, **view("dq"),
+    bwd_s = dict(d_out=P, **view("do"), out=P, **view("o"), q=P, **view("q"), k=P, **view("k"), v=P, **view("v"), attn=P, d_attn=P, d_q=P, **view("dq"),
                  d_k=P, **view("dk"), d_v=P, **view("dv"), **dims, scale=0.125, need_qk=1, ws=P, ws_bytes=ws_bytes, stream=None)
     f = "te_attention_backward_strided_f32"
     assert [status(f, bwd_s, d_out=None), status(f, bwd_s, d_q=None)] == [-1, -1]
     assert [status(f, bwd_s, N=641), status(f, bwd_s, D=80), status(f, bwd_s, dv_sn=66)] == [-3, -3, -3]
     assert [status(f, bwd_s, ws=None), status(f, bwd_s, ws_bytes=16), status(f, bwd_s, d_q=None, need_qk=0, ws=None)] == [-2, -2, -2]
-    bwd_so = dict(d_out=P, **view("do"), out=P, **view("o"), **{k: v for k, v in bwd_s.items() if k not in ("d_out", "do_sb", "do_sh", "do_sn")})
-    assert status("te_attention_backward_strided_out_f32", bwd_so, out=None) == -1
+    # `out` is optional: a NULL passes the null check and the next refusal in order answers; present, its view is validated
+    assert [status(f, bwd_s, out=None, ws=None), status(f, bwd_s, o_sn=66)] == [-2, -3]
+    b = dict(bwd_s, out=None, o_sb=0, o_sh=0, o_sn=0)      # every refusal above without the operand: its strides are ignored
+    assert [status(f, b, d_out=None), status(f, b, d_q=None), status(f, b, N=641), status(f, b, D=80), status(f, b, dv_sn=66),
+            status(f, b, ws=None), status(f, b, ws_bytes=16), status(f, b, d_q=None, need_qk=0, ws=None)] == [-1, -1, -3, -3, -3, -2, -2, -2]
 
-    fwd = dict(qkv=P, z_qk=P, attn=P, out=P, **dims, scale=0.125, stream=None)
-    f = "te_attention_forward_f32"
-    assert status(f, fwd, qkv=None) == -1
-    assert [status(f, fwd, N=225), status(f, fwd, D=80)] == [-3, -3]
     planes_bytes = lib.te_linear_x6_planes_bytes(B * N, H * D)
     assert planes_bytes > 16
     fwd_p = dict(qkv=P, z_qk=P, attn=P, out=P, out_planes=P, out_abs_planes=None, planes_bytes=planes_bytes, **dims, scale=0.125, stream=None)
-    f = "te_attention_forward_planes_f32"
-    assert status(f, fwd_p, out_planes=None) == -1
-    assert status(f, fwd_p, N=225) == -3
+    fwd = dict(fwd_p, out_planes=None, planes_bytes=0)      # no planes: planes_bytes is ignored
+    f = "te_attention_forward_f32"
+    assert status(f, fwd, qkv=None) == -1
+    assert [status(f, fwd, N=225), status(f, fwd, D=80)] == [-3, -3]
+    assert status(f, fwd_p, qkv=None) == -1
+    assert [status(f, fwd_p, N=225), status(f, fwd_p, D=80)] == [-3, -3]
+    # `out_planes` is optional: a NULL passes the null check (the next refusal answers); |out| planes alone are refused, and the
+    # planes are validated when present
+    assert status(f, fwd_p, out_planes=None, N=225) == -3
+    assert status(f, fwd_p, out_planes=None, out_abs_planes=P) == -1
     assert [status(f, fwd_p, planes_bytes=16), status(f, fwd_p, out_planes=P + 4)] == [-2, -2]
-    bwd = dict(d_out=P, qkv=P, attn=P, d_attn=P, d_qkv=P, **dims, scale=0.125, need_qk=1, stream=None)
+    assert status(f, fwd_p, out_abs_planes=P + 4) == -2
+    bwd = dict(d_out=P, out=P, qkv=P, attn=P, d_attn=P, d_qkv=P, **dims, scale=0.125, need_qk=1, stream=None)
     f = "te_attention_backward_f32"
-    assert status(f, bwd, d_out=None) == -1
-    assert status(f, bwd, N=225) == -3
-    bwd_o = dict(d_out=P, out=P, **{k: v for k, v in bwd.items() if k != "d_out"})
-    assert status("te_attention_backward_out_f32", bwd_o, out=None) == -1
+    for out in (P, None):      # `out` is optional: with a NULL the next refusal in order answers
+        assert status(f, bwd, out=out, d_out=None) == -1
+        assert status(f, bwd, out=out, N=225) == -3
 
     ws_bytes = lib.te_matmul_relprop_av_workspace_bytes(B, H, N, D)
     av = dict(R=P, **view("r"), attn=P, v=P, **view("v"), Z=P, z_sb=H * N * D, z_sh=N * D, z_sn=D, cam_attn=P, cam_v=P, **view("cv"),
               **dims, scale=1.0, variant=0, ws=P, ws_bytes=ws_bytes, stream=None)
-    f = "te_matmul_relprop_av_fwdz_f32"
-    assert [status(f, av, R=None), status(f, av, r_sb=-1), status(f, av, r_sn=0), status(f, av, D=0)] == [-1, -1, -1, -1]
-    assert [status(f, av, ws=None), status(f, av, ws_bytes=ws_bytes - 256)] == [-2, -2]
+    f = "te_matmul_relprop_av_f32"
+    for Z in (P, None):      # Z is optional: the same refusals with and without it
+        assert [status(f, av, Z=Z, R=None), status(f, av, Z=Z, r_sb=-1), status(f, av, Z=Z, r_sn=0), status(f, av, Z=Z, D=0)] == [-1, -1, -1, -1]
+        assert [status(f, av, Z=Z, ws=None), status(f, av, Z=Z, ws_bytes=ws_bytes - 256)] == [-2, -2]
     ws_bytes = lib.te_matmul_relprop_qk_workspace_bytes(B, H, N, D)
     qk = dict(R=P, r_scale=None, r_scale_stride=0, q=P, **view("q"), k=P, **view("k"), Z=P, cam_q=P, **view("cq"), cam_k=P, **view("ck"),
               **dims, scale=1.0, variant=0, ws=P, ws_bytes=ws_bytes, stream=None)
-    f = "te_matmul_relprop_qk_fwd_scaled_f32"
-    assert [status(f, qk, R=None), status(f, qk, q_sb=-1)] == [-1, -1]
-    assert [status(f, qk, ws=None), status(f, qk, ws_bytes=ws_bytes - 256)] == [-2, -2]
+    f = "te_matmul_relprop_qk_f32"
+    for Z, r_scale in ((P, None), (None, None), (P, P), (None, P)):      # Z and r_scale are optional: the same refusals in each state
+        o = dict(Z=Z, r_scale=r_scale)
+        assert [status(f, qk, **o, R=None), status(f, qk, **o, q_sb=-1)] == [-1, -1]
+        assert [status(f, qk, **o, ws=None), status(f, qk, **o, ws_bytes=ws_bytes - 256)] == [-2, -2]
 
     assert [lib.te_attention_forward_supported(n, 64) for n in (0, 1, 224, 225)] == [0, 1, 1, 0]
     assert [lib.te_attention_strided_supported(n, 64) for n in (0, 1, 640, 641)] == [0, 1, 1, 0]

@@ -336,7 +336,7 @@ def test_entry_points_are_declared_exported_and_bound(lib):
         assert len(re.findall(r"\bint\s+%s\s*\(" % name, header)) == 1 and header.index(name + "(") > section
         fn = getattr(lib, name)
         assert fn.argtypes is not None and len(fn.argtypes) == (18 if "subset" in name else 9), name
-    assert lib.te_version() >= 705 and _lib.MIN_LIB_VERSION == 705 and _lib.TE_SUBSET_MAX_CELLS == 4096
+    assert lib.te_version() >= 705 and _lib.MIN_LIB_VERSION == 800 and _lib.TE_SUBSET_MAX_CELLS == 4096
     assert hasattr(_cabi, "CTYPES")                                      # bound from the header, not from a table kept by hand
     with open(os.path.join(ROOT, "transformer-explainability_amd", "ops.py")) as f:
         assert "argtypes" not in f.read()

@@ -206,6 +206,39 @@ def test_av_rule_reads_z_in_place(B, H, N):
     assert torch.equal(a0, a1) and torch.equal(v0, v1)
 
 
+def test_av_rule_strided_z_on_kernels_that_read_it_contiguous():
+    """Head dim 32 (the simple kernels, which read Z as a contiguous [B,H,N,D] tensor): the entry point refuses the strided view
+    and ops calls it again with a contiguous copy and the contiguous strides == the call on that copy, bitwise."""
+    from transformer_explainability_amd import ops
+    d = dev()
+    B, H, N, D = 2, 2, 17, 32
+    v = rnd((B, H, N, D), 171).to(d)
+    attn = torch.softmax(rnd((B, H, N, N), 172).to(d), -1).contiguous()
+    R = rnd((B, H, N, D), 173, 0.01).to(d)
+    z_view = (attn @ v).permute(0, 2, 1, 3).reshape(B, N, H * D).view(B, N, H, D).permute(0, 2, 1, 3)
+    assert not z_view.is_contiguous() and z_view.stride(2) == H * D
+    a0, v0 = ops.matmul_relprop_av(R, attn, v, out_scale=0.5, z=z_view)
+    a1, v1 = ops.matmul_relprop_av(R, attn, v, out_scale=0.5, z=z_view.contiguous())
+    assert torch.isfinite(a0).all() and torch.isfinite(v0).all()
+    assert torch.equal(a0, a1) and torch.equal(v0, v1)
+
+
+@pytest.mark.parametrize("B,H,N", [(2, 2, 17), (2, 2, 65)])
+def test_qk_rule_deferred_factor_without_z(B, H, N):
+    """The deferred factor with no cached forward product (Z formed in the workspace first) == the QK rule on the materialised
+    operand, bitwise."""
+    from transformer_explainability_amd import ops
+    d = dev()
+    R = rnd((B, H, N, N), 181, 0.01).to(d)
+    fac = (rnd((B, 2), 182).abs() + 0.5).to(d)
+    q, k = rnd((B, H, N, 64), 183).to(d), rnd((B, H, N, 64), 184).to(d)
+    Rd = ops.Deferred(R, fac[:, 1])
+    cq, ck = ops.matmul_relprop_qk(Rd, q, k, out_scale=0.5)
+    rq, rk = ops.matmul_relprop_qk(Rd.materialise(), q, k, out_scale=0.5)
+    assert torch.isfinite(cq).all() and torch.isfinite(ck).all()
+    assert torch.equal(cq, rq) and torch.equal(ck, rk)
+
+
 @pytest.mark.parametrize("B,H,N", [(3, 2, 257), (2, 2, 771), (2, 1, 209), (2, 1, 4100)])
 def test_qk_rule_deferred_factor(B, H, N):
     """The QK rule taking the deferred per-sample factor == the QK rule on the materialised operand, bitwise.  Beyond

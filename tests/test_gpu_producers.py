@@ -84,7 +84,7 @@ def test_attention_backward_producer(B, H, N, need_qk):
         check(f"producer.bwd.d_q({B},{H},{N})", d_qkv[..., :C], qkv.grad[..., :C], 1e-5)
         check(f"producer.bwd.d_k({B},{H},{N})", d_qkv[..., C:2 * C], qkv.grad[..., C:2 * C], 1e-5)
         # round 6: with the forward output at hand the row sums of the softmax backward come from d_out . out
-        # (te_attention_backward_out_f32; N <= 224: the rc kernel for every such N) -- same bars, same d_attn / d_v bits,
+        # (the `out` operand of te_attention_backward_f32; N <= 224: the rc kernel for every such N) -- same bars, same d_attn / d_v bits,
         # and a batch equals its samples bit for bit
         out_k, attn_k2, _ = ops.attention_forward(qkv.detach(), H, scale)
         d_attn2, d_qkv2 = ops.attention_backward(g_out, qkv.detach(), attn_k2, H, scale, need_qk=True, out=out_k)
@@ -108,6 +108,32 @@ def test_attention_backward_producer(B, H, N, need_qk):
                                      need_qk=True, out=out_k[:1].contiguous())
         assert torch.equal(one[1], d_qkv2[:1])
     # (need_qk=False: the q / k thirds of d_qkv are scratch -- the block has no consumer for them)
+
+
+@pytest.mark.parametrize("B,H,N", [(2, 2, 17), (2, 2, 65)])
+def test_attention_backward_qkv_with_out_and_no_qk(B, H, N):
+    """The strided backward with the forward output at hand and need_qk=False (the lowest block whose attention gradient is
+    wanted, in a model that holds `out`): d_attn and d_v against stock PyTorch, the bars of test_attention_producer_bert_layout;
+    d_q / d_k are not asked for and not given."""
+    import math
+    from transformer_explainability_amd import ops
+    D = 64
+    C = H * D
+    d = dev()
+    q, k, v = (rnd((B, N, C), 91 + i).to(d).requires_grad_(True) for i in range(3))
+    scale = 1.0 / math.sqrt(D)
+    heads = lambda t: t.view(B, N, H, D).permute(0, 2, 1, 3)      # noqa: E731
+    probs = torch.softmax(heads(q) @ heads(k).transpose(-1, -2) * scale, dim=-1)
+    probs.retain_grad()
+    ctx = (probs @ heads(v)).permute(0, 2, 1, 3).reshape(B, N, C)
+    g_out = rnd((B, N, C), 95).to(d)
+    ctx.backward(g_out)
+    out, attn, _, _ = ops.attention_forward_qkv(q.detach(), k.detach(), v.detach(), H, scale)
+    d_v = torch.full_like(v, float("nan"))
+    d_attn = ops.attention_backward_qkv(g_out, q.detach(), k.detach(), v.detach(), attn, H, scale, None, None, d_v, need_qk=False,
+                                        out=out)
+    check(f"producer.bert_out_noqk.d_attn({B},{H},{N})", d_attn, probs.grad, 3e-6)
+    check(f"producer.bert_out_noqk.d_v({B},{H},{N})", d_v, v.grad, 3e-6)
 
 
 @pytest.mark.parametrize("B,H,N,masked", [(2, 12, 512, True), (2, 2, 128, True), (1, 3, 577, False), (3, 2, 40, True),
@@ -156,7 +182,7 @@ def test_attention_producer_bert_layout(B, H, N, masked):
         if need_qk:
             check("producer.bert.d_q" + tag, d_q, q.grad, 1e-5)
             check("producer.bert.d_k" + tag, d_k, k.grad, 1e-5)
-    # with the forward output at hand (te_attention_backward_strided_out_f32: row sums from d_out . out; beyond 64 tokens the row
+    # with the forward output at hand (the `out` operand of te_attention_backward_strided_f32: row sums from d_out . out; beyond 64 tokens the row
     # side on te_attn_bwd6l.hip): the same bars, and sample 0 alone == sample 0 of the batch, bitwise
     d_q, d_k, d_v = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
     d_attn = ops.attention_backward_qkv(g_out, q.detach(), k.detach(), v.detach(), attn, H, scale, d_q, d_k, d_v, need_qk=True, out=out)
@@ -567,7 +593,7 @@ def test_residual_layernorm_node(fused):
 
 @pytest.mark.parametrize("B,H,N", [(2, 12, 197), (3, 2, 50), (1, 4, 224), (5, 2, 33), (2, 1, 1)])
 def test_attention_forward_emits_the_projection_planes(B, H, N):
-    """Round 6: te_attention_forward_planes_f32 = te_attention_forward_f32's bits plus the two plane sets
+    """Round 6: te_attention_forward_f32 with out_planes = its bits without them plus the two plane sets
     te_linear_x6_split_dual_f32 builds from `out` -- bit for bit, ragged last row block (B N not a multiple of 32) included."""
     from transformer_explainability_amd import _lib, ops
     d = dev()

@@ -137,7 +137,7 @@ def test_gelu_forward_without_abs_planes():
 @gpu
 @pytest.mark.parametrize("N", [17, 197])
 def test_attention_forward_without_abs_planes(N):
-    """te_attention_forward_planes_f32 with a NULL |out| plane buffer: out, attn, z_qk and the signed planes of the dual call."""
+    """te_attention_forward_f32 with out_planes and a NULL |out| plane buffer: out, attn, z_qk and the signed planes of the dual call."""
     from transformer_explainability_amd import ops
     B, H = 2, 2
     qkv = rnd((B, N, 3 * H * 64), 720 + N).to(dev())

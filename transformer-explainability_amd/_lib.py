@@ -23,7 +23,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # (TE_RELPROP_LIB: measurement builds of the same sources under another name, e.g. an A/B of two -D variants in one process tree)
 LIB_PATH = os.environ.get("TE_RELPROP_LIB") or os.path.join(_PKG, "lib", "libte_relprop.so")
 
-MIN_LIB_VERSION = 705      # te_version(): 0.7.5, the faithfulness entries of te_faithful.hip (0.7.6 adds a flag and no entry point: TE_X6_X_PLANES_SIGNED, which the build id below covers; 0.7.4: the robustness / complexity entries of te_robust.hip, 0.7.3: te_localisation_f32, 0.7.2: the curve entry points of te_curves.hip, 0.7.1: te_map_similarity_f32, 0.7.0: the fp64 rules, 0.6.1: te_conv2d_zb_relprop_bf16, 0.6.0: te_build_id)
+MIN_LIB_VERSION = 800      # te_version(): 0.8.0, argument lists changed under existing names (one entry point per rule, optional operands NULL)
 
 _PROTOTYPES, CONSTANTS = _cabi.load(os.path.join(INCLUDE, "te_relprop.h"))
 SIGNATURES = {name: (res, [t for _, t in params]) for name, (res, params) in _PROTOTYPES.items()}

@@ -3,7 +3,7 @@
 
 #include <string.h>
 
-extern "C" int te_version(void) { return 707; /* 0.7.7: the AttnLRP entries of te_attnlrp.hip (0.7.6: TE_X6_X_PLANES_SIGNED, NULL |X| plane buffers of the producers, 0.7.5: the faithfulness entries of te_faithful.hip, 0.7.4: the robustness / complexity entries of te_robust.hip, 0.7.3: te_localisation_f32 of te_localise.hip, 0.7.2: the deletion / insertion curves of te_curves.hip, 0.7.1: te_map_similarity_f32, 0.7.0: the fp64 rules of te_f64.hip, 0.6.1: te_conv2d_zb_relprop_bf16, 0.6.0: te_build_id()) */ }
+extern "C" int te_version(void) { return 800; /* 0.8.0: one entry point per rule and producer, optional operands are NULL pointers (argument lists changed under existing names) */ }
 
 #ifndef TE_BUILD_ID
 #define TE_BUILD_ID "unstamped"      // a build that did not go through build.py: _lib.load() refuses it

@@ -139,33 +139,14 @@ extern "C" size_t te_matmul_relprop_av_workspace_bytes(int64_t B, int64_t H, int
   return te_align_up((size_t)2 * B * H * N * D * sizeof(float), 256);
 }
 
+// Z (optional): the cached forward product attn v, element (b,h,n,d) at Z + b*z_sb + h*z_sh + n*z_sn + d
 extern "C" int te_matmul_relprop_av_f32(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn,
                                         const float* attn, const float* v, int64_t v_sb, int64_t v_sh,
-                                        int64_t v_sn, float* cam_attn, float* cam_v, int64_t cv_sb,
-                                        int64_t cv_sh, int64_t cv_sn, int64_t B, int64_t H, int64_t N,
-                                        int64_t D, float out_scale, int variant, void* ws, size_t ws_bytes,
+                                        int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn,
+                                        float* cam_attn, float* cam_v, int64_t cv_sb, int64_t cv_sh,
+                                        int64_t cv_sn, int64_t B, int64_t H, int64_t N, int64_t D,
+                                        float out_scale, int variant, void* ws, size_t ws_bytes,
                                         te_stream_t stream_) {
-  return te_matmul_relprop_av_fwd_f32(R, r_sb, r_sh, r_sn, attn, v, v_sb, v_sh, v_sn, nullptr, cam_attn, cam_v, cv_sb,
-                                      cv_sh, cv_sn, B, H, N, D, out_scale, variant, ws, ws_bytes, stream_);
-}
-
-extern "C" int te_matmul_relprop_av_fwd_f32(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn,
-                                            const float* attn, const float* v, int64_t v_sb, int64_t v_sh,
-                                            int64_t v_sn, const float* Z, float* cam_attn, float* cam_v,
-                                            int64_t cv_sb, int64_t cv_sh, int64_t cv_sn, int64_t B, int64_t H,
-                                            int64_t N, int64_t D, float out_scale, int variant, void* ws,
-                                            size_t ws_bytes, te_stream_t stream_) {
-  return te_matmul_relprop_av_fwdz_f32(R, r_sb, r_sh, r_sn, attn, v, v_sb, v_sh, v_sn, Z, H * N * D, N * D, D, cam_attn,
-                                       cam_v, cv_sb, cv_sh, cv_sn, B, H, N, D, out_scale, variant, ws, ws_bytes, stream_);
-}
-
-extern "C" int te_matmul_relprop_av_fwdz_f32(const float* R, int64_t r_sb, int64_t r_sh, int64_t r_sn,
-                                             const float* attn, const float* v, int64_t v_sb, int64_t v_sh,
-                                             int64_t v_sn, const float* Z, int64_t z_sb, int64_t z_sh, int64_t z_sn,
-                                             float* cam_attn, float* cam_v, int64_t cv_sb, int64_t cv_sh,
-                                             int64_t cv_sn, int64_t B, int64_t H, int64_t N, int64_t D,
-                                             float out_scale, int variant, void* ws, size_t ws_bytes,
-                                             te_stream_t stream_) {
   if (!R || !attn || !v || !cam_attn || !cam_v || B <= 0 || H <= 0 || N <= 0 || D <= 0)
     return TE_ERR_INVALID_ARG;
   const Strided rs{r_sb, r_sh, r_sn}, vs{v_sb, v_sh, v_sn}, cs{cv_sb, cv_sh, cv_sn}, contig{H * N * D, N * D, D};
@@ -206,37 +187,15 @@ extern "C" size_t te_matmul_relprop_qk_workspace_bytes(int64_t B, int64_t H, int
   return te_align_up((size_t)2 * B * H * N * N * sizeof(float), 256);
 }
 
-extern "C" int te_matmul_relprop_qk_f32(const float* R_nn, const float* q, int64_t q_sb, int64_t q_sh,
-                                        int64_t q_sn, const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
-                                        float* cam_q, int64_t cq_sb, int64_t cq_sh, int64_t cq_sn, float* cam_k,
-                                        int64_t ck_sb, int64_t ck_sh, int64_t ck_sn, int64_t B, int64_t H,
-                                        int64_t N, int64_t D, float out_scale, int variant, void* ws,
-                                        size_t ws_bytes, te_stream_t stream_) {
-  return te_matmul_relprop_qk_fwd_f32(R_nn, q, q_sb, q_sh, q_sn, k, k_sb, k_sh, k_sn, nullptr, cam_q, cq_sb, cq_sh,
-                                      cq_sn, cam_k, ck_sb, ck_sh, ck_sn, B, H, N, D, out_scale, variant, ws, ws_bytes,
-                                      stream_);
-}
-
-extern "C" int te_matmul_relprop_qk_fwd_f32(const float* R_nn, const float* q, int64_t q_sb, int64_t q_sh,
-                                            int64_t q_sn, const float* k, int64_t k_sb, int64_t k_sh,
-                                            int64_t k_sn, const float* Z, float* cam_q, int64_t cq_sb,
-                                            int64_t cq_sh, int64_t cq_sn, float* cam_k, int64_t ck_sb,
-                                            int64_t ck_sh, int64_t ck_sn, int64_t B, int64_t H, int64_t N,
-                                            int64_t D, float out_scale, int variant, void* ws, size_t ws_bytes,
-                                            te_stream_t stream_) {
-  return te_matmul_relprop_qk_fwd_scaled_f32(R_nn, nullptr, 0, q, q_sb, q_sh, q_sn, k, k_sb, k_sh, k_sn, Z, cam_q, cq_sb,
-                                             cq_sh, cq_sn, cam_k, ck_sb, ck_sh, ck_sn, B, H, N, D, out_scale, variant, ws,
-                                             ws_bytes, stream_);
-}
-
-extern "C" int te_matmul_relprop_qk_fwd_scaled_f32(const float* R_nn, const float* r_scale, int64_t r_scale_stride,
-                                                   const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
-                                                   const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
-                                                   const float* Z, float* cam_q, int64_t cq_sb, int64_t cq_sh,
-                                                   int64_t cq_sn, float* cam_k, int64_t ck_sb, int64_t ck_sh,
-                                                   int64_t ck_sn, int64_t B, int64_t H, int64_t N, int64_t D,
-                                                   float out_scale, int variant, void* ws, size_t ws_bytes,
-                                                   te_stream_t stream_) {
+// r_scale (optional): the deferred per-sample factor of R_nn ; Z (optional): the cached forward product q k^T, contiguous
+extern "C" int te_matmul_relprop_qk_f32(const float* R_nn, const float* r_scale, int64_t r_scale_stride,
+                                        const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                                        const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                                        const float* Z, float* cam_q, int64_t cq_sb, int64_t cq_sh,
+                                        int64_t cq_sn, float* cam_k, int64_t ck_sb, int64_t ck_sh,
+                                        int64_t ck_sn, int64_t B, int64_t H, int64_t N, int64_t D,
+                                        float out_scale, int variant, void* ws, size_t ws_bytes,
+                                        te_stream_t stream_) {
   if (!R_nn || !q || !k || !cam_q || !cam_k || B <= 0 || H <= 0 || N <= 0 || D <= 0) return TE_ERR_INVALID_ARG;
   const Strided qs{q_sb, q_sh, q_sn}, ks{k_sb, k_sh, k_sn}, cqs{cq_sb, cq_sh, cq_sn}, cks{ck_sb, ck_sh, ck_sn};
   if (!view_ok(qs) || !view_ok(ks) || !view_ok(cqs) || !view_ok(cks)) return TE_ERR_INVALID_ARG;
@@ -283,30 +242,26 @@ extern "C" int te_matmul_relprop_qk_fwd_scaled_f32(const float* R_nn, const floa
 // ================================================================================================
 extern "C" int te_attention_forward_supported(int64_t N, int64_t D) { return te_attn_fwd6::supported(1, 1, N, D) ? 1 : 0; }
 
-extern "C" int te_attention_forward_f32(const float* qkv, float* z_qk, float* attn, float* out, int64_t B, int64_t H,
-                                        int64_t N, int64_t D, float scale, te_stream_t stream_) {
-  if (!qkv || !z_qk || !attn || !out || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
+// out_planes (optional; round 6): the operand planes of `out` for the projection layer's x6 kernels = the signed
+// planes of out [B N, H D] (te_linear_x6_planes_bytes(B N, H D) bytes each), out_abs_planes (optional with them) = the planes of
+// |out| -- bit for bit what te_linear_x6_split_dual_f32 writes from the fp32 tensor.
+extern "C" int te_attention_forward_f32(const float* qkv, float* z_qk, float* attn, float* out, void* out_planes,
+                                        void* out_abs_planes, size_t planes_bytes, int64_t B, int64_t H, int64_t N,
+                                        int64_t D, float scale, te_stream_t stream_) {
+  if (!qkv || !z_qk || !attn || !out || (out_abs_planes && !out_planes) || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
   if (!te_attn_fwd6::supported(B, H, N, D)) return TE_ERR_UNSUPPORTED;
-  return finish(te_attn_fwd6::launch(qkv, z_qk, attn, out, B, H, N, scale, (hipStream_t)stream_));
-}
-
-// The forward producer that also writes the operand planes of `out` for the projection layer's x6 kernels (round 6):
-// out_planes = the signed planes of out [B N, H D] (te_linear_x6_planes_bytes(B N, H D) bytes each), out_abs_planes (optional) = the
-// planes of |out| -- bit for bit what te_linear_x6_split_dual_f32 writes from the fp32 tensor.
-extern "C" int te_attention_forward_planes_f32(const float* qkv, float* z_qk, float* attn, float* out, void* out_planes,
-                                               void* out_abs_planes, size_t planes_bytes, int64_t B, int64_t H, int64_t N,
-                                               int64_t D, float scale, te_stream_t stream_) {
-  if (!qkv || !z_qk || !attn || !out || !out_planes || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
-  if (!te_attn_fwd6::supported(B, H, N, D)) return TE_ERR_UNSUPPORTED;
-  const size_t need = te_linear_x6_planes_bytes(B * N, H * D);
-  if (need == 0) return TE_ERR_UNSUPPORTED;
-  if (planes_bytes < need || !te_aligned16(out_planes) || (out_abs_planes && !te_aligned16(out_abs_planes))) return TE_ERR_WORKSPACE;
+  if (out_planes) {
+    const size_t need = te_linear_x6_planes_bytes(B * N, H * D);
+    if (need == 0) return TE_ERR_UNSUPPORTED;
+    if (planes_bytes < need || !te_aligned16(out_planes) || (out_abs_planes && !te_aligned16(out_abs_planes))) return TE_ERR_WORKSPACE;
+  }
   return finish(te_attn_fwd6::launch(qkv, z_qk, attn, out, B, H, N, scale, (hipStream_t)stream_, out_planes, out_abs_planes));
 }
 
-// `out` (optional): the block's forward output [B,N,C]
-static int attention_backward(const float* d_out, const float* out, const float* qkv, const float* attn, float* d_attn, float* d_qkv,
-                              int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk, te_stream_t stream_) {
+// `out` (optional): the block's forward output [B,N,C]; without it the row sums of the softmax backward come from the N x N tensors
+extern "C" int te_attention_backward_f32(const float* d_out, const float* out, const float* qkv, const float* attn,
+                                         float* d_attn, float* d_qkv, int64_t B, int64_t H, int64_t N, int64_t D,
+                                         float scale, int need_qk, te_stream_t stream_) {
   if (!d_out || !qkv || !attn || !d_attn || !d_qkv || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
   if (!te_attn_fwd6::supported(B, H, N, D)) return TE_ERR_UNSUPPORTED;      // (the backward serves what the forward serves)
   hipStream_t stream = (hipStream_t)stream_;
@@ -329,19 +284,6 @@ static int attention_backward(const float* d_out, const float* out, const float*
   // the one-pass kernel with every key of a row in its one group
   return finish(te_attn_rules::qk_launch(TE_ATTN_BWD, d_attn, q, fused, k, fused, attn, d_q, fused, d_k, fused, B, H, N, scale, nullptr, nullptr, 0,
                                          stream));
-}
-
-extern "C" int te_attention_backward_f32(const float* d_out, const float* qkv, const float* attn, float* d_attn,
-                                         float* d_qkv, int64_t B, int64_t H, int64_t N, int64_t D, float scale,
-                                         int need_qk, te_stream_t stream_) {
-  return attention_backward(d_out, nullptr, qkv, attn, d_attn, d_qkv, B, H, N, D, scale, need_qk, stream_);
-}
-
-extern "C" int te_attention_backward_out_f32(const float* d_out, const float* out, const float* qkv, const float* attn,
-                                             float* d_attn, float* d_qkv, int64_t B, int64_t H, int64_t N, int64_t D,
-                                             float scale, int need_qk, te_stream_t stream_) {
-  if (!out) return TE_ERR_INVALID_ARG;
-  return attention_backward(d_out, out, qkv, attn, d_attn, d_qkv, B, H, N, D, scale, need_qk, stream_);
 }
 
 // ================================================================================================
@@ -374,11 +316,19 @@ extern "C" int te_attention_forward_strided_f32(const float* q, int64_t q_sb, in
 }
 
 // out (optional): the forward output attention_forward returned for these inputs ([B,H,N,64] view)
-static int backward_strided(const float* d_out, Strided dos, const float* out, Strided os, const float* q, Strided qs, const float* k,
-                            Strided ks, const float* v, Strided vs, const float* attn, float* d_attn, float* d_q, Strided dqs, float* d_k,
-                            Strided dks, float* d_v, Strided dvs, int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk,
-                            void* ws, size_t ws_bytes, te_stream_t stream_) {
+extern "C" int te_attention_backward_strided_f32(const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn,
+                                                 const float* out, int64_t o_sb, int64_t o_sh, int64_t o_sn, const float* q,
+                                                 int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb,
+                                                 int64_t k_sh, int64_t k_sn, const float* v, int64_t v_sb, int64_t v_sh,
+                                                 int64_t v_sn, const float* attn, float* d_attn, float* d_q, int64_t dq_sb,
+                                                 int64_t dq_sh, int64_t dq_sn, float* d_k, int64_t dk_sb, int64_t dk_sh,
+                                                 int64_t dk_sn, float* d_v, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
+                                                 int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk, void* ws,
+                                                 size_t ws_bytes, te_stream_t stream_) {
   using te_attn_long::strides_ok;
+  const Strided dos{do_sb, do_sh, do_sn}, qs{q_sb, q_sh, q_sn}, ks{k_sb, k_sh, k_sn}, vs{v_sb, v_sh, v_sn};
+  const Strided dqs{dq_sb, dq_sh, dq_sn}, dks{dk_sb, dk_sh, dk_sn}, dvs{dv_sb, dv_sh, dv_sn};
+  const Strided os = out ? Strided{o_sb, o_sh, o_sn} : Strided();
   if (!d_out || !k || !v || !attn || !d_attn || !d_v || B <= 0 || H <= 0 || N <= 0) return TE_ERR_INVALID_ARG;
   if (need_qk && (!q || !d_q || !d_k)) return TE_ERR_INVALID_ARG;
   if (!te_attn_long::supported(B, H, N, D)) return TE_ERR_UNSUPPORTED;
@@ -401,32 +351,4 @@ static int backward_strided(const float* d_out, Strided dos, const float* out, S
   // The column side: d_v = attn^T d_out, d_k = d_s^T q from attn, d_attn and rowdot, whichever kernel left them
   if (l6) return finish(te_attn_bwd6l::launch_cols(attn, d_attn, rowdot, d_out, dos, q, qs, d_v, dvs, d_k, dks, B, H, N, scale, need_qk, stream));
   return finish(te_attn_long::bwd_cols_launch(attn, d_attn, rowdot, d_out, dos, q, qs, d_v, dvs, d_k, dks, B, H, N, scale, need_qk, stream));
-}
-
-extern "C" int te_attention_backward_strided_f32(const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn,
-                                                 const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k,
-                                                 int64_t k_sb, int64_t k_sh, int64_t k_sn, const float* v, int64_t v_sb,
-                                                 int64_t v_sh, int64_t v_sn, const float* attn, float* d_attn, float* d_q,
-                                                 int64_t dq_sb, int64_t dq_sh, int64_t dq_sn, float* d_k, int64_t dk_sb,
-                                                 int64_t dk_sh, int64_t dk_sn, float* d_v, int64_t dv_sb, int64_t dv_sh,
-                                                 int64_t dv_sn, int64_t B, int64_t H, int64_t N, int64_t D, float scale,
-                                                 int need_qk, void* ws, size_t ws_bytes, te_stream_t stream_) {
-  return backward_strided(d_out, {do_sb, do_sh, do_sn}, nullptr, Strided(), q, {q_sb, q_sh, q_sn}, k, {k_sb, k_sh, k_sn}, v, {v_sb, v_sh, v_sn},
-                          attn, d_attn, d_q, {dq_sb, dq_sh, dq_sn}, d_k, {dk_sb, dk_sh, dk_sn}, d_v, {dv_sb, dv_sh, dv_sn}, B, H, N, D, scale,
-                          need_qk, ws, ws_bytes, stream_);
-}
-
-extern "C" int te_attention_backward_strided_out_f32(const float* d_out, int64_t do_sb, int64_t do_sh, int64_t do_sn,
-                                                     const float* out, int64_t o_sb, int64_t o_sh, int64_t o_sn, const float* q,
-                                                     int64_t q_sb, int64_t q_sh, int64_t q_sn, const float* k, int64_t k_sb,
-                                                     int64_t k_sh, int64_t k_sn, const float* v, int64_t v_sb, int64_t v_sh,
-                                                     int64_t v_sn, const float* attn, float* d_attn, float* d_q, int64_t dq_sb,
-                                                     int64_t dq_sh, int64_t dq_sn, float* d_k, int64_t dk_sb, int64_t dk_sh,
-                                                     int64_t dk_sn, float* d_v, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
-                                                     int64_t B, int64_t H, int64_t N, int64_t D, float scale, int need_qk, void* ws,
-                                                     size_t ws_bytes, te_stream_t stream_) {
-  if (!out) return TE_ERR_INVALID_ARG;
-  return backward_strided(d_out, {do_sb, do_sh, do_sn}, out, {o_sb, o_sh, o_sn}, q, {q_sb, q_sh, q_sn}, k, {k_sb, k_sh, k_sn}, v,
-                          {v_sb, v_sh, v_sn}, attn, d_attn, d_q, {dq_sb, dq_sh, dq_sn}, d_k, {dk_sb, dk_sh, dk_sn}, d_v, {dv_sb, dv_sh, dv_sn}, B,
-                          H, N, D, scale, need_qk, ws, ws_bytes, stream_);
 }

@@ -803,7 +803,7 @@ extern "C" int te_add_bcast_relprop_bf16(const float* R, const te_bf16_t* X0, co
 }
 
 // Deferred form (variant ours): ONE pass over R and X0 writes the unscaled a = X0 . S; fac [B,2] = {fa, fb} goes to the
-// consumer (te_matmul_relprop_qk_fwd_scaled_f32 multiplies the relevance operand by fa in its S tile); out1 [B,N]
+// consumer (te_matmul_relprop_qk_f32 multiplies the relevance operand by fa in its S tile); out1 [B,N]
 // (optional) = the mask's relevance, already scaled.  a * fa is bitwise te_add_bcast_relprop_f32's out0.
 extern "C" int te_add_bcast_relprop_deferred_f32(const float* R, const float* X0, const float* mask, float* a,
                                                  float* out1, float* fac, int64_t B, int64_t H, int64_t N, void* ws,

@@ -873,10 +873,10 @@ extern "C" int te_linear_cpass_f32(const float* S, const float* X, const float* 
 }
 
 // ---- Z-pass from the forward output (see K1f in the file header), alone and composed with the C-pass
-extern "C" int te_linear_zpass_fwd_scaled_f32(const float* R, const float* r_scale, int64_t r_scale_stride,
-                                              int64_t rows_per_sample, const float* X, const float* W, const float* Y,
-                                              const float* bias, float* S, int64_t T, int64_t in_f, int64_t out_f,
-                                              te_stream_t stream_) {
+extern "C" int te_linear_zpass_fwd_f32(const float* R, const float* r_scale, int64_t r_scale_stride,
+                                       int64_t rows_per_sample, const float* X, const float* W, const float* Y,
+                                       const float* bias, float* S, int64_t T, int64_t in_f, int64_t out_f,
+                                       te_stream_t stream_) {
   if (!R || !X || !W || !Y || !S || T <= 0 || in_f <= 0 || out_f <= 0) return TE_ERR_INVALID_ARG;
   if (r_scale && (rows_per_sample <= 0 || rows_per_sample > 0x7fffffff || T % rows_per_sample)) return TE_ERR_INVALID_ARG;
   if ((in_f % 4) || (out_f % 4) || !te_aligned16(R) || !te_aligned16(X) || !te_aligned16(W) || !te_aligned16(S))
@@ -890,31 +890,19 @@ extern "C" int te_linear_zpass_fwd_scaled_f32(const float* R, const float* r_sca
   return TE_OK;
 }
 
-extern "C" int te_linear_zpass_fwd_f32(const float* R, const float* X, const float* W, const float* Y,
-                                       const float* bias, float* S, int64_t T, int64_t in_f, int64_t out_f,
-                                       te_stream_t stream_) {
-  return te_linear_zpass_fwd_scaled_f32(R, nullptr, 0, 1, X, W, Y, bias, S, T, in_f, out_f, stream_);
-}
-
-extern "C" int te_linear_relprop_fwd_scaled_f32(const float* R, const float* r_scale, int64_t r_scale_stride,
-                                                int64_t rows_per_sample, const float* X, const float* W,
-                                                const float* Y, const float* bias, float* out, int64_t T, int64_t in_f,
-                                                int64_t out_f, void* ws, size_t ws_bytes, te_stream_t stream_) {
+extern "C" int te_linear_relprop_fwd_f32(const float* R, const float* r_scale, int64_t r_scale_stride,
+                                         int64_t rows_per_sample, const float* X, const float* W,
+                                         const float* Y, const float* bias, float* out, int64_t T, int64_t in_f,
+                                         int64_t out_f, void* ws, size_t ws_bytes, te_stream_t stream_) {
   if (!R || !X || !W || !Y || !out || T <= 0 || in_f <= 0 || out_f <= 0) return TE_ERR_INVALID_ARG;
   if (!ws || ws_bytes < te_linear_relprop_workspace_bytes(T, in_f, out_f, TE_VARIANT_OURS)) return TE_ERR_WORKSPACE;
   if (!te_aligned16(ws)) return TE_ERR_WORKSPACE;
   if ((in_f % 4) || (out_f % 4) || !te_aligned16(R) || !te_aligned16(X) || !te_aligned16(W) || !te_aligned16(out))
     return TE_ERR_UNSUPPORTED;   // callers fall back to te_linear_relprop_f32 (any shape)
-  int rc = te_linear_zpass_fwd_scaled_f32(R, r_scale, r_scale_stride, rows_per_sample, X, W, Y, bias, (float*)ws, T,
-                                          in_f, out_f, stream_);
+  int rc = te_linear_zpass_fwd_f32(R, r_scale, r_scale_stride, rows_per_sample, X, W, Y, bias, (float*)ws, T, in_f,
+                                   out_f, stream_);
   if (rc != TE_OK) return rc;
   return te_linear_cpass_f32((const float*)ws, X, W, out, T, in_f, out_f, stream_);
-}
-
-extern "C" int te_linear_relprop_fwd_f32(const float* R, const float* X, const float* W, const float* Y,
-                                         const float* bias, float* out, int64_t T, int64_t in_f, int64_t out_f,
-                                         void* ws, size_t ws_bytes, te_stream_t stream_) {
-  return te_linear_relprop_fwd_scaled_f32(R, nullptr, 0, 1, X, W, Y, bias, out, T, in_f, out_f, ws, ws_bytes, stream_);
 }
 
 extern "C" size_t te_linear_relprop_workspace_bytes(int64_t T, int64_t in_f, int64_t out_f, int variant) {

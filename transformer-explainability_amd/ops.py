@@ -659,9 +659,9 @@ def linear_relprop(R: Tensor, X: Tensor, W: Tensor, alpha: float = 1.0, variant=
             st = _stream(Xc)
             if fwd:
                 with _timed("linear_zpass_fwd", 2.0 * T * in_f * out_f, 4.0 * (T * in_f + 3 * T * out_f + in_f * out_f)):
-                    _lib.check(lib.te_linear_zpass_fwd_scaled_f32(_ptr(Rc), rs_ptr, rs_stride, rps, _ptr(Xc), _ptr(Wc),
-                                                                  _ptr(Yc), _ptr(bc), _ptr(S), T, in_f, out_f, st),
-                               "te_linear_zpass_fwd_scaled_f32")
+                    _lib.check(lib.te_linear_zpass_fwd_f32(_ptr(Rc), rs_ptr, rs_stride, rps, _ptr(Xc), _ptr(Wc),
+                                                           _ptr(Yc), _ptr(bc), _ptr(S), T, in_f, out_f, st),
+                               "te_linear_zpass_fwd_f32")
             else:
                 with _timed("linear_zpass", 2.0 * T * (2 * in_f) * out_f, 4.0 * (T * in_f + 2 * T * out_f + in_f * out_f)):
                     _lib.check(lib.te_linear_zpass_f32(_ptr(Rc), _ptr(Xc), _ptr(Wc), _ptr(S), T, in_f, out_f, st),
@@ -673,10 +673,10 @@ def linear_relprop(R: Tensor, X: Tensor, W: Tensor, alpha: float = 1.0, variant=
     with _on_device(Xc) as lib:
         ws = _ws(lib.te_linear_relprop_workspace_bytes(T, in_f, out_f, var), Xc)
         if fwd:
-            _lib.check(lib.te_linear_relprop_fwd_scaled_f32(_ptr(Rc), rs_ptr, rs_stride, rps, _ptr(Xc), _ptr(Wc),
-                                                            _ptr(Yc), _ptr(bc), _ptr(out), T, in_f, out_f, _ptr(ws),
-                                                            ws.numel(), _stream(Xc)),
-                       "te_linear_relprop_fwd_scaled_f32")
+            _lib.check(lib.te_linear_relprop_fwd_f32(_ptr(Rc), rs_ptr, rs_stride, rps, _ptr(Xc), _ptr(Wc),
+                                                     _ptr(Yc), _ptr(bc), _ptr(out), T, in_f, out_f, _ptr(ws),
+                                                     ws.numel(), _stream(Xc)),
+                       "te_linear_relprop_fwd_f32")
         else:
             _lib.check(lib.te_linear_relprop_f32(_ptr(Rc), _ptr(Xc), _ptr(Wc), _ptr(out), T, in_f, out_f, float(alpha),
                                                  var, _ptr(ws), ws.numel(), _stream(Xc)), "te_linear_relprop_f32")
@@ -731,15 +731,14 @@ def matmul_relprop_av(R: Tensor, attn: Tensor, v: Tensor, out_scale: float = 1.0
     with _on_device(attn) as lib, _timed("attention_av_rule", 4.0 * B * H * N * N * D,
                                          4.0 * B * H * (2 * N * N + 5 * N * D)):
         ws = _ws(lib.te_matmul_relprop_av_workspace_bytes(B, H, N, D), attn)
-        args = (_ptr(cam_attn), _ptr(cam_v), cv_sb, cv_sh, cv_sn, B, H, N, D, float(out_scale), _variant(variant),
+        head = (_ptr(R), r_sb, r_sh, r_sn, _ptr(attn), _ptr(v), v_sb, v_sh, v_sn)
+        tail = (_ptr(cam_attn), _ptr(cam_v), cv_sb, cv_sh, cv_sn, B, H, N, D, float(out_scale), _variant(variant),
                 _ptr(ws), ws.numel(), _stream(attn))
-        rc = lib.te_matmul_relprop_av_fwdz_f32(_ptr(R), r_sb, r_sh, r_sn, _ptr(attn), _ptr(v), v_sb, v_sh, v_sn,
-                                               _ptr(zc), z_str[0], z_str[1], z_str[2], *args)
+        rc = lib.te_matmul_relprop_av_f32(*head, _ptr(zc), *z_str, *tail)
         if rc == _lib.TE_ERR_UNSUPPORTED and zc is not None and not zc.is_contiguous():
             zc = zc.contiguous()       # kernels that read Z as a contiguous [B,H,N,D] tensor
-            rc = lib.te_matmul_relprop_av_fwd_f32(_ptr(R), r_sb, r_sh, r_sn, _ptr(attn), _ptr(v), v_sb, v_sh, v_sn,
-                                                  _ptr(zc), *args)
-        _lib.check(rc, "te_matmul_relprop_av_fwdz_f32")
+            rc = lib.te_matmul_relprop_av_f32(*head, _ptr(zc), H * N * D, N * D, D, *tail)
+        _lib.check(rc, "te_matmul_relprop_av_f32")
     return cam_attn, cam_v
 
 
@@ -770,12 +769,11 @@ def matmul_relprop_qk(R: Tensor, q: Tensor, k: Tensor, out_scale: float = 1.0,
         tail = (_ptr(q), q_sb, q_sh, q_sn, _ptr(k), k_sb, k_sh, k_sn, _ptr(zc), _ptr(cam_q), cq[0], cq[1], cq[2],
                 _ptr(cam_k), ck[0], ck[1], ck[2], B, H, N, D, float(out_scale), _variant(variant), _ptr(ws), ws.numel(),
                 _stream(R))
-        rc = lib.te_matmul_relprop_qk_fwd_scaled_f32(_ptr(R), _ptr(r_scale), 0 if r_scale is None else r_scale.stride(0),
-                                                     *tail)
+        rc = lib.te_matmul_relprop_qk_f32(_ptr(R), _ptr(r_scale), 0 if r_scale is None else r_scale.stride(0), *tail)
         if rc == _lib.TE_ERR_UNSUPPORTED and r_scale is not None:
             R = _c(Deferred(R, r_scale).materialise())     # kernels that take a plain relevance operand
-            rc = lib.te_matmul_relprop_qk_fwd_scaled_f32(_ptr(R), None, 0, *tail)
-        _lib.check(rc, "te_matmul_relprop_qk_fwd_scaled_f32")
+            rc = lib.te_matmul_relprop_qk_f32(_ptr(R), None, 0, *tail)
+        _lib.check(rc, "te_matmul_relprop_qk_f32")
     return cam_q, cam_k
 
 
@@ -901,7 +899,7 @@ def attention_backward_qkv(d_out: Tensor, q: Tensor, k: Tensor, v: Tensor, attn:
     """Gradient of attention_forward_qkv: d_out [B,N,C]; d_q / d_k / d_v: [B,N,C] views written in place (d_q, d_k may be
     None with need_qk=False).  Returns d_attn [B,H,N,N].  out: the forward output [B,N,C] attention_forward_qkv returned for
     these inputs, if the caller still holds it -- the softmax backward's row sums are then d_out . out and the row side runs
-    on csrc/te_attn_bwd6l.hip (te_attention_backward_strided_out_f32)."""
+    on csrc/te_attn_bwd6l.hip (the `out` operand of te_attention_backward_strided_f32)."""
     if any(_is_bf16(t) for t in (d_out, q, k, v, attn)):
         return attention_backward_qkv_bf16(d_out, q, k, v, attn, num_heads, scale, d_q, d_k, d_v, need_qk=need_qk)
     B, N, C = d_out.shape
@@ -914,24 +912,19 @@ def attention_backward_qkv(d_out: Tensor, q: Tensor, k: Tensor, v: Tensor, attn:
     with _on_device(d_out) as lib, _timed("attention_backward", (8.0 if need_qk else 4.0) * B * H * N * N * D,
                                           4.0 * B * ((4 if need_qk else 2) * H * N * N + 8 * N * C)):
         ws = _ws(lib.te_attention_backward_strided_workspace_bytes(B, H, N), d_out)
-        if out is not None and tuple(out.shape) == (B, N, C) and out.dtype == d_out.dtype and out.stride(-1) == 1:
-            (o, ob, oh, on) = _heads(_prep(out), H)
-            _lib.check(lib.te_attention_backward_strided_out_f32(_ptr(d_out), N * C, 64, C, _ptr(o), ob, oh, on, _ptr(q), qb, qh, qn,
-                                                                 _ptr(k), kb, kh, kn, _ptr(v), vb, vh, vn, _ptr(attn), _ptr(d_attn),
-                                                                 _ptr(dq), dqb, dqh, dqn, _ptr(dk), dkb, dkh, dkn, _ptr(dv), dvb, dvh,
-                                                                 dvn, B, H, N, D, float(scale), int(bool(need_qk)), _ptr(ws),
-                                                                 ws.numel(), _stream(d_out)), "te_attention_backward_strided_out_f32")
-            return d_attn
-        _lib.check(lib.te_attention_backward_strided_f32(_ptr(d_out), N * C, 64, C, _ptr(q), qb, qh, qn, _ptr(k), kb, kh, kn,
-                                                         _ptr(v), vb, vh, vn, _ptr(attn), _ptr(d_attn), _ptr(dq), dqb, dqh,
-                                                         dqn, _ptr(dk), dkb, dkh, dkn, _ptr(dv), dvb, dvh, dvn, B, H, N, D,
-                                                         float(scale), int(bool(need_qk)), _ptr(ws), ws.numel(),
-                                                         _stream(d_out)), "te_attention_backward_strided_f32")
+        if not (out is not None and tuple(out.shape) == (B, N, C) and out.dtype == d_out.dtype and out.stride(-1) == 1):
+            out = None
+        (o, ob, oh, on) = hd(out)
+        _lib.check(lib.te_attention_backward_strided_f32(_ptr(d_out), N * C, 64, C, _ptr(o), ob, oh, on, _ptr(q), qb, qh, qn,
+                                                         _ptr(k), kb, kh, kn, _ptr(v), vb, vh, vn, _ptr(attn), _ptr(d_attn),
+                                                         _ptr(dq), dqb, dqh, dqn, _ptr(dk), dkb, dkh, dkn, _ptr(dv), dvb, dvh,
+                                                         dvn, B, H, N, D, float(scale), int(bool(need_qk)), _ptr(ws),
+                                                         ws.numel(), _stream(d_out)), "te_attention_backward_strided_f32")
     return d_attn
 
 
 def attention_forward_planes_supported(qkv: Tensor, num_heads: int) -> bool:
-    """Can attention_forward emit the operand planes of its output (te_attention_forward_planes_f32: N <= 224, head dim 64)?"""
+    """Can attention_forward emit the operand planes of its output (the out_planes of te_attention_forward_f32: N <= 224, head dim 64)?"""
     B, N, C3 = qkv.shape
     C = C3 // 3
     return (qkv.is_cuda and qkv.dtype == torch.float32 and C % num_heads == 0 and C // num_heads == 64 and N <= 224
@@ -958,7 +951,7 @@ def attention_forward(qkv: Tensor, num_heads: int, scale: float, planes: bool = 
     H, D = num_heads, C // num_heads
     if not _lib.load().te_attention_forward_supported(N, D):
         if planes:
-            raise _lib.TeError("attention_forward(planes=True): shape not served by te_attention_forward_planes_f32")
+            raise _lib.TeError("attention_forward(planes=True): shape not served by te_attention_forward_f32")
         out, attn, zqk, _ = attention_forward_qkv(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], num_heads, scale)
         return out, attn, zqk
     out = torch.empty((B, N, C), dtype=torch.float32, device=qkv.device)
@@ -966,16 +959,13 @@ def attention_forward(qkv: Tensor, num_heads: int, scale: float, planes: bool = 
     zqk = torch.empty((B, H, N, N), dtype=torch.float32, device=qkv.device)
     extra = (12.0 if planes_abs else 6.0) * B * N * C if planes else 0.0
     with _on_device(qkv) as lib, _timed("attention_forward", 4.0 * B * H * N * N * D, 4.0 * B * (2 * H * N * N + 4 * N * C) + extra):
+        nb, xs, xa = 0, None, None
         if planes:
             nb = lib.te_linear_x6_planes_bytes(B * N, C)
             xs, xa = _ws(nb, qkv), _ws(nb, qkv) if planes_abs else None
-            _lib.check(lib.te_attention_forward_planes_f32(_ptr(qkv), _ptr(zqk), _ptr(attn), _ptr(out), _ptr(xs), _ptr(xa), nb,
-                                                           B, H, N, D, float(scale), _stream(qkv)),
-                       "te_attention_forward_planes_f32")
-            return out, attn, zqk, xs, xa
-        _lib.check(lib.te_attention_forward_f32(_ptr(qkv), _ptr(zqk), _ptr(attn), _ptr(out), B, H, N, D, float(scale),
-                                                _stream(qkv)), "te_attention_forward_f32")
-    return out, attn, zqk
+        _lib.check(lib.te_attention_forward_f32(_ptr(qkv), _ptr(zqk), _ptr(attn), _ptr(out), _ptr(xs), _ptr(xa), nb, B, H, N,
+                                                D, float(scale), _stream(qkv)), "te_attention_forward_f32")
+    return (out, attn, zqk, xs, xa) if planes else (out, attn, zqk)
 
 
 def attention_backward(d_out: Tensor, qkv: Tensor, attn: Tensor, num_heads: int, scale: float,
@@ -983,7 +973,7 @@ def attention_backward(d_out: Tensor, qkv: Tensor, attn: Tensor, num_heads: int,
     """Gradient of attention_forward: d_out [B,N,C] -> (d_attn [B,H,N,N], d_qkv [B,N,3C]).  need_qk=False: nothing below
     consumes d_qkv (the lowest block whose attention gradient is wanted): only d_attn is meaningful, d_qkv is scratch.
     out: the forward output attention_forward returned for these inputs, if the caller still holds it -- the softmax half then
-    takes its row sums from d_out . out (te_attention_backward_out_f32).  bf16 tensors: csrc/te_attn_bf16.hip (`out` unused)."""
+    takes its row sums from d_out . out (the `out` operand of te_attention_backward_f32).  bf16 tensors: csrc/te_attn_bf16.hip (`out` unused)."""
     if _is_bf16(d_out) or _is_bf16(qkv) or _is_bf16(attn):
         qkv = _c16(qkv)
         C = qkv.shape[-1] // 3
@@ -1005,14 +995,12 @@ def attention_backward(d_out: Tensor, qkv: Tensor, attn: Tensor, num_heads: int,
     d_attn = torch.empty_like(attn)
     with _on_device(qkv) as lib, _timed("attention_backward", (8.0 if need_qk else 4.0) * B * H * N * N * D,
                                         4.0 * B * ((4 if need_qk else 2) * H * N * N + 8 * N * C)):
-        if out is not None and need_qk and tuple(out.shape) == tuple(d_out.shape) and out.is_contiguous() and out.dtype == d_out.dtype:
-            _lib.check(lib.te_attention_backward_out_f32(_ptr(d_out), _ptr(out), _ptr(qkv), _ptr(attn), _ptr(d_attn), _ptr(d_qkv),
-                                                         B, H, N, D, float(scale), 1, _stream(qkv)),
-                       "te_attention_backward_out_f32")
-        else:
-            _lib.check(lib.te_attention_backward_f32(_ptr(d_out), _ptr(qkv), _ptr(attn), _ptr(d_attn), _ptr(d_qkv), B, H, N,
-                                                     D, float(scale), int(bool(need_qk)), _stream(qkv)),
-                       "te_attention_backward_f32")
+        if not (out is not None and need_qk and tuple(out.shape) == tuple(d_out.shape) and out.is_contiguous()
+                and out.dtype == d_out.dtype):
+            out = None
+        _lib.check(lib.te_attention_backward_f32(_ptr(d_out), _ptr(out), _ptr(qkv), _ptr(attn), _ptr(d_attn), _ptr(d_qkv), B,
+                                                 H, N, D, float(scale), int(bool(need_qk)), _stream(qkv)),
+                   "te_attention_backward_f32")
     return d_attn, d_qkv
 
 
