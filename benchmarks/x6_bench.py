@@ -7,10 +7,14 @@ a half batch bit for bit (rows independent of the stream-K cut), no expired hand
 
     python benchmarks/x6_bench.py [--config vit_b16|vit_l16|bert_base|all] [--iters 20] [--check-rows 1024]
     python benchmarks/x6_bench.py --zpass-ab [--config vit_b16] [--iters 40]
+    python benchmarks/x6_bench.py --schedule-ab [--config vit_b16] [--iters 30] [--pin 2]
 
 --zpass-ab: the Z-pass alone on the planes of |X| (MODE_Z) against the Z-pass on the signed planes of X
 (TE_X6_X_PLANES_SIGNED: the sign is applied while the activation blocks are staged), per shape and tile geometry, the two
 variants alternating launch by launch in one process; `out` of the whole rule compared bit for bit.
+--schedule-ab: every x6 launch of a layer (Z-pass, C-pass, forward and input-gradient product) under the schedule the cost rule
+picks, the slack rule before it (TE_X6_SLACK_RULE), whole tiles claimed (TE_X6_WHOLE_TILES) and in static ranges
+(+ TE_X6_STATIC_TILES): what te_linear_x6_schedule says each would do, us per launch, us per K16 step, CU-time.
 """
 import argparse
 import json
@@ -176,6 +180,88 @@ def zpass_ab(T, in_f, out_f, iters, dev):
     return rows
 
 
+def x6_schedule(lib, T, in_f, out_f, pass_, flags):
+    """te_linear_x6_schedule as a dict (no launch): what a call with these flags would do."""
+    import ctypes
+    out = (ctypes.c_int * 4)()
+    _lib.check(lib.te_linear_x6_schedule(T, in_f, out_f, pass_, flags, out), "te_linear_x6_schedule")
+    return dict(geometry={1: "128x256", 2: "256x256", 3: "128x128"}[out[0]],
+                schedule={0: "stream-K", 1: "whole static", 2: "whole claimed"}[out[1]], grid=out[2], tiles=out[3])
+
+
+def schedule_ab(T, lname, in_f, out_f, iters, dev, pin):
+    """us per launch of the four x6 launches of a layer (Z-pass, C-pass, forward product, input-gradient product) under the
+    schedule variants, alternating launch by launch in one process; results compared bit for bit.  CU-time (CU us): stream-K
+    holds its whole grid for the launch; a whole-tile launch holds a CU for the tiles it computes, tiles x (launch / rounds)."""
+    import math
+    lib = _lib.load()
+    X, W, b, R, Y = operands(T, in_f, out_f, 1, dev)
+    st = torch.cuda.current_stream().cuda_stream
+    wp = ops.x6_weight_planes(W)
+    status = ops.x6_status(dev)
+    variants = {"slack": ops.TE_X6_SLACK_RULE, "cost": 0, "whole": ops.TE_X6_WHOLE_TILES,
+                "static": ops.TE_X6_WHOLE_TILES | ops.TE_X6_STATIC_TILES}
+
+    def planes_of(A, rows, K, transposed=0):
+        nb = lib.te_linear_x6_planes_bytes(rows, K)
+        p = torch.empty(nb, dtype=torch.uint8, device=dev)
+        _lib.check(lib.te_linear_x6_split_matrix_f32(A.data_ptr(), rows, K, transposed, p.data_ptr(), nb, st), "split_matrix")
+        return p
+
+    xs = planes_of(X, T, in_f)
+    ws = torch.zeros(lib.te_linear_relprop_x6_workspace_bytes(T, in_f, out_f), dtype=torch.uint8, device=dev)
+    out = {v: torch.empty((T, in_f), dtype=torch.float32, device=dev) for v in variants}
+
+    def rule(v, phase):
+        _lib.check(lib.te_linear_relprop_x6_f32(R.data_ptr(), None, 0, 1, X.data_ptr(), W.data_ptr(), wp.data_ptr(), xs.data_ptr(),
+                                                Y.data_ptr(), b.data_ptr(), out[v].data_ptr(), T, in_f, out_f,
+                                                pin | variants[v] | ops.TE_X6_X_PLANES_SIGNED | phase, status.data_ptr(),
+                                                ws.data_ptr(), ws.numel(), st), "te_linear_relprop_x6_f32")
+
+    # the two plain products of the layer: forward [T, in_f] -> [T, out_f], input gradient [T, out_f] -> [T, in_f]
+    dY = R
+    prods = {"forward": (xs, planes_of(W, out_f, in_f), in_f, out_f, b),
+             "input-gradient": (planes_of(dY, T, out_f), planes_of(W, in_f, out_f, 1), out_f, in_f, None)}
+    gws = {k: torch.zeros(lib.te_gemm_x6_workspace_bytes(T, K, M), dtype=torch.uint8, device=dev) for k, (_, _, K, M, _) in prods.items()}
+    gout = {(k, v): torch.empty((T, M), dtype=torch.float32, device=dev) for k, (_, _, K, M, _) in prods.items() for v in variants}
+
+    def product(k, v):
+        xp, wpl, K, M, bias = prods[k]
+        _lib.check(lib.te_gemm_x6_f32(None, xp.data_ptr(), wpl.data_ptr(), None if bias is None else bias.data_ptr(),
+                                      gout[k, v].data_ptr(), T, K, M, pin | variants[v], status.data_ptr(), gws[k].data_ptr(),
+                                      gws[k].numel(), st), "te_gemm_x6_f32")
+
+    launches = {"Z-pass": (ops.TE_X6_PASS_Z, in_f, out_f, in_f // 16, lambda v: rule(v, ops.TE_X6_PHASE_Z)),
+                "C-pass": (ops.TE_X6_PASS_C, in_f, out_f, out_f // 16, lambda v: rule(v, ops.TE_X6_PHASE_C)),
+                "forward product": (ops.TE_X6_PASS_PRODUCT, in_f, out_f, in_f // 16, lambda v: product("forward", v)),
+                "input-gradient product": (ops.TE_X6_PASS_PRODUCT, out_f, in_f, out_f // 16, lambda v: product("input-gradient", v))}
+    rows = []
+    for name, (pass_, k_in, k_out, nks, launch) in launches.items():
+        ev = {v: [] for v in variants}
+        for it in range(iters + 3):
+            for v in variants:
+                if name == "Z-pass":
+                    rule(v, ops.TE_X6_PHASE_SPLIT)
+                a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                launch(v)
+                e.record()
+                if it >= 3:
+                    ev[v].append((a, e))
+        torch.cuda.synchronize()
+        ref = out["slack"] if name in ("Z-pass", "C-pass") else gout[name.split(" product")[0], "slack"]
+        for v in variants:
+            got = out[v] if name in ("Z-pass", "C-pass") else gout[name.split(" product")[0], v]
+            us = sorted(a.elapsed_time(e) * 1e3 for a, e in ev[v])
+            s = x6_schedule(lib, T, k_in, k_out, pass_, pin | variants[v])
+            r = s["tiles"] / s["grid"]
+            per_tile = us[len(us) // 2] / (r if s["schedule"] == "stream-K" else math.ceil(r))
+            rows.append(dict(layer=lname, launch=name, variant=v, nks=nks, **s, us_med=round(us[len(us) // 2], 1), us_min=round(us[0], 1),
+                             us_per_k16=round(per_tile / nks, 3), cu_us=round(s["tiles"] * per_tile),
+                             bitwise=bool(name == "Z-pass" or torch.equal(got, ref))))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="vit_b16")
@@ -184,10 +270,20 @@ def main():
     ap.add_argument("--tiles", default="0,1")
     ap.add_argument("--skip-checks", action="store_true")
     ap.add_argument("--zpass-ab", action="store_true", help="Z-pass on |X| planes against signed planes, per shape and geometry")
+    ap.add_argument("--schedule-ab", action="store_true",
+                    help="the four x6 launches of every layer under the schedule variants (slack rule, cost rule, whole tiles claimed / static)")
+    ap.add_argument("--pin", type=int, default=2, help="--schedule-ab: TE_X6_TILE_* pin (2 = what bench.py pins under concurrent streams)")
     a = ap.parse_args()
     _lib.require_device()
     dev = torch.device("cuda:0")
     names = list(CONFIGS) if a.config == "all" else a.config.split(",")
+    if a.schedule_ab:
+        for name in names:
+            T, shapes = CONFIGS[name]
+            for (lname, in_f, out_f) in shapes:
+                for r in schedule_ab(T, lname, in_f, out_f, a.iters, dev, a.pin):
+                    print("SCHEDULE " + json.dumps(dict(config=name, T=T, **r)), flush=True)
+        return
     if a.zpass_ab:
         for name in names:
             T, shapes = CONFIGS[name]

@@ -267,7 +267,16 @@ int te_rollout_f32(const float* cams, int64_t L, int64_t start_layer, int64_t B,
 #define TE_X6_WHOLE_TILES 0x10000       /* ranges cut at tile boundaries only, whatever the fill of the last round: for callers that
                                           keep several streams busy (the idle CUs of a last round are used by their other kernels,
                                           and no tile is handed over between workgroups).  Same results, bit for bit */
-#define TE_X6_TEST_SMALL_GRID 0x4000   /* tests: a persistent grid of 16 workgroups, so that small shapes get stream-K cuts */
+#define TE_X6_TEST_SMALL_GRID 0x4000   /* tests: a persistent grid of 16 workgroups, so that small shapes get stream-K cuts
+                                          (with TE_X6_WHOLE_TILES: several whole tiles per workgroup) */
+/* The schedule of a launch (same results, bit for bit, whichever is taken).  Default: whole tiles where their wall time is
+ * within a margin of stream-K's by the measured K16 step times of the two schedules (csrc/te_linear_x6.hip, plan_x6), and the
+ * whole tiles of an XCD are claimed by its workgroups from a counter in the workspace, one at a time.  The margin is the
+ * launch-to-launch spread (5 %); a call pinned to TE_X6_TILE_256 -- the pin of a caller that keeps several streams busy, where
+ * CU-time counts and not the length of one launch -- trades up to 20 % of a launch's wall time for the lower CU-time of whole
+ * tiles.  For A/B runs and tests: */
+#define TE_X6_SLACK_RULE 0x100000       /* decide as before the cost rule: whole tiles only if the last round is at least 1/1.15 full */
+#define TE_X6_STATIC_TILES 0x80000      /* whole-tile launches cut the XCD's tiles into one static range per workgroup: no counter */
 #define TE_X6_X_PLANES_SIGNED 0x20000   /* te_linear_relprop_x6_f32: x_planes holds the SIGNED planes of X (te_gemm_x6_f32's x_planes, what
                                           the layer's forward product read) instead of the planes of |X|: the Z-pass clears the sign of
                                           plane 0 and flips the low planes as it stages them.  Same results, bit for bit; with
@@ -293,6 +302,16 @@ int te_linear_relprop_x6_f32(const float* R, const float* r_scale, int64_t r_sca
                              int64_t T, int64_t in_f, int64_t out_f, int flags, unsigned* status, void* ws,
                              size_t ws_bytes, te_stream_t stream);
 int te_linear_relprop_x6_check(const void* ws, int64_t T, int64_t in_f, int64_t out_f, te_stream_t stream);
+/* What a launch would do, without a device: pass = TE_X6_PASS_Z / TE_X6_PASS_C of te_linear_relprop_x6_f32 on [T, in_f] ->
+ * [T, out_f], or TE_X6_PASS_PRODUCT = te_gemm_x6_f32 with K = in_f, M = out_f; flags as that call takes them.  schedule[0 .. 3] =
+ * the tile geometry (TE_X6_TILE_128 / _256 / _128x128), the schedule (TE_X6_SCHEDULE_*), the grid in workgroups, the tiles. */
+#define TE_X6_PASS_Z 0
+#define TE_X6_PASS_C 1
+#define TE_X6_PASS_PRODUCT 2
+#define TE_X6_SCHEDULE_STREAM_K 0
+#define TE_X6_SCHEDULE_WHOLE_STATIC 1
+#define TE_X6_SCHEDULE_WHOLE_CLAIMED 2
+int te_linear_x6_schedule(int64_t T, int64_t in_f, int64_t out_f, int pass, int flags, int* schedule);
 
 /* The same rule for EVERY variant and alpha on the x6 kernels (csrc/te_linear_x6.hip): variant TE_VARIANT_LRP =
  * modules/layers_lrp.py:188-211 (S1 = sd(R, X+ W+^T), S2 = sd(R, X- W-^T), separate denominators), and the inhibitor half

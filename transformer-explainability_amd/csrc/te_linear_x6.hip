@@ -33,9 +33,10 @@
 //                   falls: a batch equals its samples run one by one, bit for bit, and no tile quantisation is left (at
 //                   ViT-B batch 64 the 256-wide tiles of the eight launches of a block fill 59-94 % of whole rounds).
 //                   Waits only ever go to a LOWER workgroup index of the same XCD slot order.
-//                   Where the last round of whole tiles is nearly full (ceil(r) <= 1.15 r, r = tiles per workgroup) the
-//                   ranges are cut at tile boundaries instead (launch_x6): the workgroups of an XCD then walk k in
-//                   lock-step on shared operand panels and a K16 step takes 1.9 us instead of 2.1-2.6 us.
+//                   Where whole tiles cost little or no wall time (plan_x6: rounds x lock-step time against tiles per workgroup
+//                   x skewed step time) the work is handed out in whole tiles instead: the workgroups of an XCD then walk k
+//                   in lock-step on shared operand panels and a K16 step takes 2.0-2.3 us instead of 2.3-2.6 us; each takes
+//                   the XCD's next tile from a counter until none is left (no hand-over, no wait on another workgroup).
 //   plain GEMM      MODE_G: out = X W^T + b on the same loop (te_gemm_x6_f32: the Linear layers' own forward product and
 //                   input gradient); te_linear_x6_split_dual_f32 writes the planes of a layer input and
 //                   of its absolute value in one pass, so the rule reuses what the forward product split.
@@ -59,6 +60,8 @@ constexpr int kRB = 3 * kFrag;                // one 32-row block, one K16 step
 constexpr int kMinFrag = 4;                   // a cut closer than this many K-steps to a tile boundary snaps onto it
 constexpr int kSpinMillis = 250;               // bounded wait for a predecessor's accumulators: never hang the GPU
 constexpr int kErrWord = 1023;                 // flags[0 .. 767] = hand-over flags of a pass, flags[kErrWord] = its error word
+constexpr int kClaimWord = 1024, kClaimStride = 32;   // flags[kClaimWord + 32 xcd] = next unclaimed tile of XCD xcd (a 128-B line each;
+                                                      // beyond the words te_linear_relprop_x6_check reads: a used counter is no error)
 
 
 // Z-pass, C-pass, plain GEMM out = B A^T + bias; round 4, for variant lrp and alpha != 1 (layers_lrp.py:188-211,
@@ -280,7 +283,8 @@ struct X6Params {
   int ntm, ntn;                // tiles along the weight side / the activation side (set by launch_x6 from rows_w, T)
   int rows_w;                  // weight-side rows of the product: out_f (Z-pass, plain product), 2 in_f (C-pass: +/- pairs)
   int t_fast;                  // tile order inside the launch: 0 = weight side fastest, 1 = activation side fastest
-  int whole_tiles;             // 1: ranges are cut at tile boundaries only (all workgroups of a round in k lock-step)
+  int whole_tiles;             // 1: ranges are cut at tile boundaries only (all workgroups of a round in k lock-step);
+                               // 2: whole tiles, claimed from the XCD's counter instead of cut into static ranges
   int pad1_;
   int ncb;                     // 32-row blocks of the activation side = ceil(T / 32)
   int64_t T;
@@ -291,7 +295,7 @@ struct X6Params {
   long long spin_ticks;        // wall_clock64 ticks a workgroup waits for a predecessor before it gives up
   int drop_handover;           // TE_X6_TEST_DROP_HANDOVER: publishers keep their flag down (tests: a wait must expire)
   int small_grid;              // TE_X6_TEST_SMALL_GRID: 16 workgroups (tests: stream-K cuts on small shapes)
-  int prefer_whole;            // TE_X6_WHOLE_TILES: cut the ranges at tile boundaries whatever the fill of the last round
+  int sched_flags;             // host side only: the call's TE_X6_WHOLE_TILES | TE_X6_SLACK_RULE | TE_X6_STATIC_TILES and geometry pin (plan_x6)
   // Z-pass epilogue
   const float* R;
   const float* Y;
@@ -397,8 +401,15 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
     else if (nks - r < kMinFrag) b += nks - r;
     return b;
   };
+  // whole_tiles == 2: the whole tiles of the XCD are CLAIMED, not assigned -- each workgroup takes the next tile index of the
+  // XCD's range from the XCD's counter in the flag region (zero before the launch, like the flags) until the range is empty.
+  // Under concurrent streams the workgroups of a launch become resident whenever a CU frees up: a late one then takes what is
+  // left instead of owning one to three tiles an early one had to leave waiting.  A whole tile has no hand-over, so there is no
+  // wait on another workgroup anywhere on this path, and every output is the same k-ordered chain whoever computes its tile.
+  const bool claim = p.whole_tiles == 2;
+  unsigned* const claim_ctr = p.flags + kClaimWord + xcd * kClaimStride;
   const int64_t ib = cut(slot), ie = cut(slot + 1);
-  if (ib >= ie) return;
+  if (!claim && ib >= ie) return;
   const int f_tile = (int)(ib / nks), kb = (int)(ib - (int64_t)f_tile * nks);
   const int l_tile = (int)((ie - 1) / nks), ke = (int)(ie - (int64_t)l_tile * nks);
   const bool tail = kb > 0;                                            // first tile: its head belongs to slot - 1
@@ -409,9 +420,18 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
   float* my_part = p.partial + (size_t)bid * GEO::THREADS * GEO::ACC;
   const float* in_part = p.partial + (size_t)(bid - 8) * GEO::THREADS * GEO::ACC;
 
-  for (int seq = 0; seq < nseq; ++seq) {
+  for (int seq = 0; claim || seq < nseq; ++seq) {
     int tile, k0, k1;
-    if (head && seq == 0) {
+    if (claim) {
+      // one lane takes the index, the workgroup reads it from LDS behind a barrier (the word after wait_for's; the barrier that
+      // ends the previous tile lies between this store and that tile's reads of it)
+      unsigned* const claimed = reinterpret_cast<unsigned*>(smem + X6Lds<WM, MODE>::MAIN + NW * 512) + 1;
+      if (threadIdx.x == 0) *claimed = __hip_atomic_fetch_add(claim_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __syncthreads();
+      tile = (int)__builtin_amdgcn_readfirstlane(*claimed);
+      if (tile >= ntx) break;
+      k0 = 0, k1 = nks;
+    } else if (head && seq == 0) {
       tile = l_tile, k0 = 0, k1 = ke;
     } else if (tail && seq == nseq - 1) {
       tile = f_tile, k0 = kb, k1 = (f_tile == l_tile) ? ke : nks;
@@ -1077,7 +1097,6 @@ inline bool bad_k(int64_t K) { return K < 16 || K % 16; }         // planes are 
 // (A fixed K split -- two k-ordered chains per output for long-K, few-row products -- was measured and not shipped:
 // 5 % over the 128 x 128 geometry in isolated launches, nothing in the step)
 constexpr size_t kPartialBytes = (size_t)512 * 256 * 128 * 4;       // grid x threads x accumulators: 64 MiB covers every geometry
-constexpr double kWholeTileSlack = 1.15;                          // whole tiles if ceil(r) <= 1.15 r (launch_x6)
 constexpr size_t kFlagBytes = 65536;                                 // 512 flags + the error word, per pass
 constexpr int kFlagWords = kFlagBytes / 4;                           // one pass's flag region, in words ...
 constexpr int kUsedFlagWords = kErrWord + 1;                         // ... of which a launch touches these (the check reads them)
@@ -1124,7 +1143,8 @@ inline X6WeightPlanesLrp weight_planes_lrp(int64_t in_f, int64_t out_f) {
 
 // ---- flags (te_relprop.h) ----
 constexpr int kTileMask = TE_X6_TILE_128 | TE_X6_TILE_256 | TE_X6_TILE_128x128;
-constexpr int kProductFlags = kTileMask | TE_X6_WHOLE_TILES | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID;   // plain product, general rule
+constexpr int kScheduleFlags = TE_X6_WHOLE_TILES | TE_X6_SLACK_RULE | TE_X6_STATIC_TILES;
+constexpr int kProductFlags = kTileMask | kScheduleFlags | TE_X6_TEST_DROP_HANDOVER | TE_X6_TEST_SMALL_GRID;   // plain product, general rule
 constexpr int kRuleFlags = kProductFlags | TE_X6_PHASE_MASK | TE_X6_X_PLANES_SIGNED | (kTileMask << TE_X6_TILE_Z_SHIFT) | (kTileMask << TE_X6_TILE_C_SHIFT);
 
 inline int pick_wm(int64_t in_f, int64_t out_f) {
@@ -1146,9 +1166,60 @@ inline long long spin_ticks_for_current_device() {
   return cached[dev];
 }
 
+// ---- the schedule of one launch: host arithmetic only (te_linear_x6_schedule answers from it without a device) ----
+// Stream-K or whole tiles?  With equal (tile, k) ranges the workgroups of an XCD sit at different k offsets of their tiles and
+// nothing one of them fetches is still in the 4 MB L2 when its neighbour needs it; cut at tile boundaries they run a round in k
+// lock-step on shared operand panels and a K16 step is shorter.  r = tiles per workgroup.  Per K16 step of a tile,
+//   whole tiles cost  ceil(r) t_lock       of wall time and  tiles t_lock  of CU-time (a workgroup that is done leaves its CU),
+//   stream-K costs    r t_skew(nks)        of wall time and  tiles t_skew  of CU-time (8 spx workgroups for the whole launch),
+// so whole tiles always cost less CU-time and are taken where their wall time is within a margin of stream-K's.  Either
+// way every output is the same k-ordered chain: results do not change.
+// The step times: launch time / (rounds x K16 steps) of the plain products and C-passes on 256 x 256 tiles at T = 12 608, MI355X
+// (profiles/x6_schedule_per_launch.log; DESIGN.md section 6 "The x6 schedule"): lock-step 2.27 us at 48 steps (fc1 forward, fc2 input
+// gradient: 327 us in 3 rounds) and 2.00 us at 144 / 192 steps (the C-passes of qkv and fc1 on whole tiles), stream-K 2.60 us (293 us
+// for r = 2.34) and 2.32 us.  Only their ratio enters (1.15), and it is used for every geometry.
+// The margin.  A launch that runs alone pays wall time: kWallMargin = the launch-to-launch spread of those launches (median
+// against minimum, 1-4 %).  A caller that packs whole-chip kernels of several streams pays CU-time and says
+// so by pinning the call to 256 x 256 tiles -- that is what the pin is for: kWallMarginPacked, between the 600-tile launches (whole
+// tiles 12-16 % longer, 13 % less CU-time: the step gains) and the 300-tile C-passes (38-49 % longer: the step loses, 3.1b item 2).
+constexpr double kStepLockShort = 2.27, kStepLockLong = 2.00;      // us per K16 step, workgroups of an XCD in k lock-step: nks <= 48 ... >= 144
+constexpr double kStepSkewShort = 2.60, kStepSkewLong = 2.32;      // us per K16 step under stream-K cuts
+constexpr int kShortSteps = 48, kLongSteps = 144;
+constexpr double kWallMargin = 0.05, kWallMarginPacked = 0.20;
+constexpr double kWholeTileSlack = 1.15;                           // TE_X6_SLACK_RULE: whole tiles if ceil(r) <= 1.15 r (before the cost rule)
+inline double step_time(int nks, double t_short, double t_long) {
+  if (nks <= kShortSteps) return t_short;
+  if (nks >= kLongSteps) return t_long;
+  return t_short + (t_long - t_short) * (nks - kShortSteps) / (kLongSteps - kShortSteps);
+}
+struct X6Schedule { int ntm, ntn, tiles, spx, whole_tiles; };    // whole_tiles: X6Params' (0 stream-K, 1 static ranges, 2 claimed)
+// sched_flags: the call's TE_X6_WHOLE_TILES | TE_X6_SLACK_RULE | TE_X6_STATIC_TILES and its geometry pin (not the per-pass pins)
+inline X6Schedule plan_x6(int wm, int64_t T, int rows_w, int nks, int small_grid, int sched_flags) {
+  const int tm = (wm == 2) ? 256 : 128, tt = (wm == 0) ? 128 : 256, geo_max_spx = (wm == 2) ? 32 : (wm == 1) ? 64 : 96;   // X6Geo<wm>
+  X6Schedule s;
+  s.ntm = rows_w / tm;
+  s.ntn = (int)te_ceil_div(T, tt);
+  const int64_t tiles = (int64_t)s.ntm * s.ntn;
+  s.tiles = (int)tiles;
+  const int max_spx = small_grid ? 2 : geo_max_spx;
+  s.spx = (int)std::min<int64_t>(max_spx, std::max<int64_t>(1, te_ceil_div(tiles, 8)));
+  const double r = (double)tiles / (8.0 * s.spx), rounds = std::ceil(r);
+  bool whole;
+  if (sched_flags & TE_X6_WHOLE_TILES) whole = true;          // the caller runs concurrent streams and wants no hand-over at all
+  else if (small_grid) whole = false;                         // the test hook is there for the cuts
+  else if (sched_flags & TE_X6_SLACK_RULE) whole = rounds <= kWholeTileSlack * r;
+  else {
+    const double margin = ((sched_flags & kTileMask) == TE_X6_TILE_256) ? kWallMarginPacked : kWallMargin;
+    whole = rounds * step_time(nks, kStepLockShort, kStepLockLong) <= (1.0 + margin) * r * step_time(nks, kStepSkewShort, kStepSkewLong);
+  }
+  s.whole_tiles = !whole ? 0 : (sched_flags & TE_X6_STATIC_TILES) ? 1 : 2;
+  return s;
+}
+
 template <int WM, int MODE>
 int launch_x6(const X6Params& p, hipStream_t stream) {
   using GEO = X6Geo<WM>;
+  static_assert(GEO::TM == ((WM == 2) ? 256 : 128) && GEO::TT == ((WM == 0) ? 128 : 256), "plan_x6 restates the tile sizes");
   constexpr int lds = X6Lds<WM, MODE>::TOTAL;
   static_assert(lds * (WM == 0 ? 3 : WM == 1 ? 2 : 1) <= 160 * 1024, "LDS of the workgroups of one CU");
   static_assert((size_t)8 * GEO::MAX_SPX * GEO::THREADS * GEO::ACC * 4 <= kPartialBytes && 8 * GEO::MAX_SPX < kErrWord, "workspace");
@@ -1157,23 +1228,15 @@ int launch_x6(const X6Params& p, hipStream_t stream) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return (int)e;
   X6Params q = p;
-  q.ntm = p.rows_w / GEO::TM;
-  q.ntn = (int)te_ceil_div(p.T, GEO::TT);
-  const int64_t tiles = (int64_t)q.ntm * q.ntn;
-  const int max_spx = p.small_grid ? 2 : GEO::MAX_SPX;
-  const int spx = (int)std::min<int64_t>(max_spx, std::max<int64_t>(1, te_ceil_div(tiles, 8)));
-  // Stream-K or whole tiles?  With equal (tile, k) ranges the workgroups of an XCD sit at different k offsets of their
-  // tiles and nothing one of them fetches is still in the 4 MB L2 when its neighbour needs it; cut at tile boundaries
-  // they run a round in k lock-step on shared operand panels and a K16 step takes 1.9 instead of 2.1-2.6 us (measured,
-  // profiles/r03_x6_whole_tiles.log) -- which pays as long as the last round is nearly full.  r = tiles per workgroup;
-  // whole tiles cost ceil(r) rounds.  Either way every output is the same k-ordered chain: results do not change.
-  const double r = (double)tiles / (8.0 * spx);
-  // TE_X6_WHOLE_TILES (the caller runs concurrent streams): whole tiles always -- the last round's idle CUs are not lost, the
-  // other streams' kernels use them, while stream-K keeps ALL CUs for the whole launch at the slower skewed step
-  q.whole_tiles = ((p.prefer_whole || std::ceil(r) <= kWholeTileSlack * r) && !p.small_grid) ? 1 : 0;
+  // stream-K, static whole-tile ranges or claimed whole tiles: plan_x6 (above), the one place that decides
+  const X6Schedule s = plan_x6(WM, p.T, p.rows_w, p.nks, p.small_grid, p.sched_flags);
+  static_assert(GEO::MAX_SPX == ((WM == 2) ? 32 : (WM == 1) ? 64 : 96), "plan_x6 restates the grid limit");
+  q.ntm = s.ntm;
+  q.ntn = s.ntn;
+  q.whole_tiles = s.whole_tiles;
   if (!q.status) q.status = q.flags + kErrWord;
   q.spin_ticks = spin_ticks_for_current_device();
-  kern<<<dim3(8 * spx), dim3(GEO::THREADS), lds, stream>>>(q);
+  kern<<<dim3(8 * s.spx), dim3(GEO::THREADS), lds, stream>>>(q);
   return TE_OK;
 }
 
@@ -1203,6 +1266,17 @@ inline int choose_geo(int wm_max, int64_t T, int64_t rows_w, int pin, int min_ti
   if (small_ok && t256 * (rows_w / 128) < 448) return 0;
   return 1;
 }
+// the geometry of a rule's Z-pass and C-pass (per-pass pins win over the call's pin) and of the plain product [T, K] -> [T, M]:
+// 256 weight rows / one 512-thread workgroup per CU where that gives every CU at least one tile, else the smaller tiles
+inline int geo_z(int64_t T, int64_t in_f, int64_t out_f, int flags) {
+  const int pz = (flags >> TE_X6_TILE_Z_SHIFT) & kTileMask;
+  return choose_geo(pick_wm(in_f, out_f), T, out_f, pz ? pz : (flags & kTileMask), 256, true);
+}
+inline int geo_c(int64_t T, int64_t in_f, int64_t out_f, int flags) {
+  const int pc = (flags >> TE_X6_TILE_C_SHIFT) & kTileMask;
+  return choose_geo(pick_wm(in_f, out_f), T, 2 * in_f, pc ? pc : (flags & kTileMask));
+}
+inline int geo_product(int64_t T, int64_t M, int flags) { return choose_geo((M % 256 == 0) ? 2 : 1, T, M, flags & kTileMask, 192, true); }
 
 // ---- X6Params: what every launch of a call shares, then what one pass adds ----
 // shape, accumulators, the operands of the plain product's epilogue, the status word and the schedule flags
@@ -1216,7 +1290,7 @@ inline X6Params call_params(int64_t T, float* partial, const float* bias, float*
   p.status = status;
   p.drop_handover = (flags & TE_X6_TEST_DROP_HANDOVER) ? 1 : 0;
   p.small_grid = (flags & TE_X6_TEST_SMALL_GRID) ? 1 : 0;
-  p.prefer_whole = (flags & TE_X6_WHOLE_TILES) ? 1 : 0;
+  p.sched_flags = flags & (kScheduleFlags | kTileMask);
   return p;
 }
 // + the fp32 operands of a rule's epilogues
@@ -1393,7 +1467,7 @@ extern "C" int te_gemm_x6_f32(const float* X, const void* x_planes, const void* 
     if (rc != TE_OK) return rc;
     x_planes = l.x(ws, 0);
   }
-  const int wm = choose_geo((M % 256 == 0) ? 2 : 1, T, M, flags & kTileMask, 192, true);
+  const int wm = geo_product(T, M, flags);
   const int rc = launch_pass<MODE_G>(call_params(T, l.acc(ws), bias, out, status, flags), wm, (const unsigned char*)w_planes,
                                      (const unsigned char*)x_planes, nullptr, K, M, l.flag_region(ws, 0), stream);
   if (rc != TE_OK) return rc;
@@ -1428,6 +1502,10 @@ extern "C" int te_linear_relprop_x6_f32(const float* R, const float* r_scale, in
   const unsigned char* wc = wz + weight_planes(in_f, out_f).c;
 
   if (phases & TE_X6_PHASE_SPLIT) zero_flag_regions(l.flag_region(ws, 0), kRulePasses, stream);
+  else {   // one phase per call: the tile counters of a claimed launch do not clear themselves as the hand-over flags do
+    const int first = (phases & TE_X6_PHASE_Z) ? 0 : 1, last = (phases & TE_X6_PHASE_C) ? 1 : 0;
+    zero_flag_regions(l.flag_region(ws, first), last - first + 1, stream);
+  }
   const bool x_signed = (flags & TE_X6_X_PLANES_SIGNED) != 0;      // x_planes = the planes of X: the Z-pass forms |X| as it stages them
   if (!x_planes) {
     if (phases & TE_X6_PHASE_SPLIT) {
@@ -1437,12 +1515,8 @@ extern "C" int te_linear_relprop_x6_f32(const float* R, const float* r_scale, in
     }
     x_planes = l.x(ws, 0);
   }
-  // Tile geometry per pass (the result does not depend on it, bit for bit): 256 weight rows / one 512-thread workgroup per
-  // CU where that gives every CU at least one tile, else 128 rows / two 256-thread workgroups per CU.
-  const int wm_max = pick_wm(in_f, out_f);
-  const int pz = (flags >> TE_X6_TILE_Z_SHIFT) & kTileMask, pc = (flags >> TE_X6_TILE_C_SHIFT) & kTileMask;
-  const int wm_z = choose_geo(wm_max, T, out_f, pz ? pz : (flags & kTileMask), 256, true);      // per-pass pins win
-  const int wm_c = choose_geo(wm_max, T, 2 * in_f, pc ? pc : (flags & kTileMask));
+  // Tile geometry per pass (the result does not depend on it, bit for bit)
+  const int wm_z = geo_z(T, in_f, out_f, flags), wm_c = geo_c(T, in_f, out_f, flags);
   const X6Params p = rule_params(call_params(T, l.acc(ws), bias, out, status, flags), R, r_scale, r_scale_stride, rows_per_sample,
                                  X, W, Y);
   int rc;
@@ -1585,6 +1659,25 @@ extern "C" int te_linear_relprop_x6_general_f32(const float* R, const float* r_s
     }
   }
   TE_RETURN_IF_LAUNCH_FAILED();
+  return TE_OK;
+}
+
+// What a launch of this shape would do: geometry, schedule and grid, from the same functions the entry points call.  Host arithmetic
+// only: no device is needed or touched.
+extern "C" int te_linear_x6_schedule(int64_t T, int64_t in_f, int64_t out_f, int pass, int flags, int* schedule) {
+  if (!schedule) return TE_ERR_INVALID_ARG;
+  const bool product = pass == TE_X6_PASS_PRODUCT;
+  if (pass != TE_X6_PASS_Z && pass != TE_X6_PASS_C && !product) return TE_ERR_INVALID_ARG;
+  if ((flags & ~(product ? kProductFlags : kRuleFlags)) != 0) return TE_ERR_INVALID_ARG;
+  if (!(product ? te_gemm_x6_supported(T, in_f, out_f) : te_linear_relprop_x6_supported(T, in_f, out_f))) return TE_ERR_UNSUPPORTED;
+  const bool c = pass == TE_X6_PASS_C;
+  const int wm = product ? geo_product(T, out_f, flags) : c ? geo_c(T, in_f, out_f, flags) : geo_z(T, in_f, out_f, flags);
+  const X6Schedule s = plan_x6(wm, T, (int)(c ? 2 * in_f : out_f), (int)((c ? out_f : in_f) / 16),
+                               (flags & TE_X6_TEST_SMALL_GRID) ? 1 : 0, flags & (kScheduleFlags | kTileMask));
+  schedule[0] = wm == 2 ? TE_X6_TILE_256 : wm == 1 ? TE_X6_TILE_128 : TE_X6_TILE_128x128;
+  schedule[1] = s.whole_tiles;
+  schedule[2] = 8 * s.spx;
+  schedule[3] = s.tiles;
   return TE_OK;
 }
 

@@ -19,6 +19,9 @@ from ._lib import (TE_HEADMEAN_CLAMP, TE_HEADMEAN_ROW0, TE_IMPL_SIMPLE, TE_RATIO
 # te_relprop.h's x6 flag bits (TE_X6_WHOLE_TILES: whole-tile ranges always, for callers that keep several streams busy; same bits)
 from ._lib import (TE_X6_PHASE_C, TE_X6_PHASE_SPLIT, TE_X6_PHASE_Z, TE_X6_TEST_DROP_HANDOVER,  # noqa: F401
                    TE_X6_TEST_SMALL_GRID, TE_X6_TILE_C_SHIFT, TE_X6_TILE_Z_SHIFT, TE_X6_WHOLE_TILES, TE_X6_X_PLANES_SIGNED)
+# (A/B and tests: TE_X6_SLACK_RULE = the schedule rule before the cost comparison, TE_X6_STATIC_TILES = whole tiles in static ranges)
+from ._lib import (TE_X6_PASS_C, TE_X6_PASS_PRODUCT, TE_X6_PASS_Z, TE_X6_SCHEDULE_STREAM_K,  # noqa: F401
+                   TE_X6_SCHEDULE_WHOLE_CLAIMED, TE_X6_SCHEDULE_WHOLE_STATIC, TE_X6_SLACK_RULE, TE_X6_STATIC_TILES)
 
 Tensor = torch.Tensor
 _VARIANTS = {"ours": TE_VARIANT_OURS, "lrp": TE_VARIANT_LRP}
