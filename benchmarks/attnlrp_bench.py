@@ -15,39 +15,23 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-
-def _window(fn, steps):
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(steps):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / steps
-
-
-def _summary(ms):
-    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3),
-            "windows": len(ms)}
+from benchmarks._models import vit_b16  # noqa: E402
+from benchmarks._timing import alternate, event_window, summary  # noqa: E402  (the event-window protocol)
 
 
 def _vit_b16(batch):
-    from oracle.ref_harness import seeded_randn, synthetic_init
-    from transformer_explainability_amd import vit
+    from oracle.ref_harness import seeded_randn
     from transformer_explainability_amd.generators import LRP
-    model = vit.vit_base_patch16_224().eval()
-    synthetic_init(model, 0)
-    model.to("cuda:0")
     x = seeded_randn((batch, 3, 224, 224), 1).to("cuda:0")
-    gen = LRP(model)
+    gen = LRP(vit_b16())
     return gen, {"generate_LRP": lambda: gen.generate_LRP(x, start_layer=0), "generate_attnlrp": lambda: gen.generate_attnlrp(x)}
 
 
@@ -100,14 +84,10 @@ def main():
         for _ in range(a.warmup):
             for fn in modes.values():
                 fn()
-        torch.cuda.synchronize()
-        ms = {m: [] for m in modes}
-        for _ in range(a.rounds):
-            for m, fn in modes.items():
-                ms[m].append(_window(fn, a.steps))
+        ts = alternate(modes, a.rounds, partial(event_window, n=a.steps), 0)      # (warmed above, the two calls in turn)
         gen.check()                                            # no x6 hand-over was lost in any timed call
         finite = {m: bool(torch.isfinite(fn()).all()) for m, fn in modes.items()}
-        entry = {"batch": batch, "finite": finite, **{m: _summary(v) for m, v in ms.items()}}
+        entry = {"batch": batch, "finite": finite, **{m: summary(v, 1e3, "ms", 3) for m, v in ts.items()}}
         entry["attnlrp_over_lrp"] = round(entry["generate_attnlrp"]["median_ms"] / entry["generate_LRP"]["median_ms"], 3)
         res["configs"][name] = entry
         del gen, modes

@@ -25,35 +25,24 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchmarks._models import vit_b16  # noqa: E402
+from benchmarks._timing import event_window  # noqa: E402  (event windows, but warmed anew before every window: not `alternate`)
+
 
 def _time(fn, steps, warmup):
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(steps):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / steps
+    return event_window(fn, steps) * 1e3
 
 
-def _alternate(fns, rounds, steps, warmup):
-    """{name: median ms over the rounds}, the paths taking turns inside every round"""
+def _rewarmed_rounds(fns, rounds, steps, warmup):
+    """{name: median ms over the rounds}, the paths taking turns inside every round, each warmed again before its window"""
     ms = {name: [] for name in fns}
     for r in range(rounds):
         for name, fn in fns.items():
             ms[name].append(_time(fn, steps, warmup if r == 0 else 1))
     return {name: round(statistics.median(v), 4) for name, v in ms.items()}, {name: [round(x, 4) for x in v] for name, v in ms.items()}
-
-
-def _model(dtype):
-    from oracle.ref_harness import synthetic_init
-    from transformer_explainability_amd import vit
-    m = vit.vit_base_patch16_224().eval()
-    synthetic_init(m, 0)
-    return m.to("cuda:0").to(dtype)
 
 
 def bench_rule(a, res):
@@ -73,7 +62,7 @@ def bench_rule(a, res):
            "fp32_kernel_on_upcast_operands_ms": lambda: ops.conv2d_zb_relprop(R, Xf, Wf, Yf),
            "fp32_upcast_route_ms": lambda: ops.conv2d_zb_relprop(R, X.float(), W.float(),
                                                                  F.conv2d(X.float(), W.float(), stride=p))}
-    med, runs = _alternate(fns, a.rounds, a.steps, a.warmup)
+    med, runs = _rewarmed_rounds(fns, a.rounds, a.steps, a.warmup)
     T, K = B * 196, 3 * p * p
     res["rule"] = {"shape": {"T": T, "K": K, "E": E}, **med, "rounds_ms": runs,
                    "bf16_vs_fp32_kernel": round(med["fp32_kernel_on_upcast_operands_ms"] / med["bf16_rule_ms"], 3),
@@ -85,10 +74,10 @@ def bench_call(a, res):
     from transformer_explainability_amd.generators import LRP
     x32 = seeded_randn((a.batch, 3, 224, 224), 1).to("cuda:0")
     x16 = x32.to(torch.bfloat16)
-    l16, l32 = LRP(_model(torch.bfloat16)), LRP(_model(torch.float32))
+    l16, l32 = LRP(vit_b16(torch.bfloat16)), LRP(vit_b16(torch.float32))
     fns = {"bf16_model_ms": lambda: l16.generate_LRP(x16, method="full"),
            "fp32_model_ms": lambda: l32.generate_LRP(x32, method="full")}
-    med, runs = _alternate(fns, a.rounds, a.steps, a.warmup)
+    med, runs = _rewarmed_rounds(fns, a.rounds, a.steps, a.warmup)
     res["call"] = {**med, "rounds_ms": runs, "bf16_maps_per_s": round(a.batch / med["bf16_model_ms"] * 1e3, 1),
                    "fp32_maps_per_s": round(a.batch / med["fp32_model_ms"] * 1e3, 1),
                    "bf16_speedup_vs_fp32": round(med["fp32_model_ms"] / med["bf16_model_ms"], 3)}

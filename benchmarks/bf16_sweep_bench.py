@@ -23,43 +23,22 @@ import json
 import os
 import statistics
 import sys
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-HBM_BYTES_PER_S = 8.0e12
+from benchmarks._models import vit_b16  # noqa: E402
+from benchmarks._timing import HBM_BYTES_PER_S, alternate, event_window, summary  # noqa: E402  (the event-window protocol)
+
 BF = torch.bfloat16
-
-
-def _window(fn, inner):
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(inner):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / 1e3 / inner
-
-
-def _alternate(fns, rounds, inner, warmup):
-    """{name: [seconds per call of each of `rounds` windows]}, the versions taking turns."""
-    for fn in fns.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in fns}
-    for _ in range(rounds):
-        for name, fn in fns.items():
-            times[name].append(_window(fn, inner))
-    return times
 
 
 def _summary(ts, nbytes=None):
     med = statistics.median(ts)
-    out = {"median_us": round(med * 1e6, 2), "min_us": round(min(ts) * 1e6, 2), "max_us": round(max(ts) * 1e6, 2),
-           "windows": len(ts)}
+    out = summary(ts)
     if nbytes is not None:
         out["bytes_that_must_move"] = int(nbytes)
         out["GB_per_s"] = round(nbytes / med / 1e9, 1)
@@ -72,8 +51,8 @@ def _ab(new, old, nbytes, rounds, window_s, warmup):
         for _ in range(warmup):
             fn()
     torch.cuda.synchronize()
-    inner = max(20, int(window_s / max(_window(old, 20), 1e-6)))      # calls per window: about window_s of device time
-    t = _alternate({"new": new, "old": old}, rounds, inner, 0)
+    inner = max(20, int(window_s / max(event_window(old, 20), 1e-6)))      # calls per window: about window_s of device time
+    t = alternate({"new": new, "old": old}, rounds, partial(event_window, n=inner), 0)
     return {"new": _summary(t["new"], nbytes), "old": _summary(t["old"]), "calls_per_window": inner,
             "speedup_of_medians": round(statistics.median(t["old"]) / statistics.median(t["new"]), 3),
             "faster_beyond_spread": bool(max(t["new"]) < min(t["old"]))}
@@ -112,25 +91,17 @@ def bench_kernels(rounds, window_s, warmup):
     return res
 
 
-def _vit_b16(dtype):
-    from oracle.ref_harness import synthetic_init
-    from transformer_explainability_amd import vit
-    m = vit.vit_base_patch16_224().eval()
-    synthetic_init(m, 0)
-    return m.to("cuda:0").to(dtype)
-
-
 def bench_models(batches, steps, warmup, rounds):
     from oracle.ref_harness import seeded_randn
     from transformer_explainability_amd.generators import LRP
     from transformer_explainability_amd.perturbation import PerturbationEvaluator
     from transformer_explainability_amd.sweep import SaliencySweep, normalize
-    models = {"bf16": _vit_b16(BF), "fp32": _vit_b16(torch.float32)}
+    models = {"bf16": vit_b16(BF), "fp32": vit_b16(torch.float32)}
     sweeps = {k: SaliencySweep("transformer_attribution", lrp=LRP(m)) for k, m in models.items()}
     res = {"sweep": {}, "perturbation": {}}
     for B in batches:
         x = normalize(torch.rand((B, 3, 224, 224), generator=torch.Generator().manual_seed(B)).to("cuda:0"))
-        t = _alternate({k: (lambda s=s: s.explain(x)) for k, s in sweeps.items()}, rounds, steps, warmup)
+        t = alternate({k: (lambda s=s: s.explain(x)) for k, s in sweeps.items()}, rounds, partial(event_window, n=steps), warmup)
         row = {k: {"maps_per_s": round(B / statistics.median(v), 1), "step_ms_median": round(statistics.median(v) * 1e3, 2),
                    "step_ms_min": round(min(v) * 1e3, 2), "step_ms_max": round(max(v) * 1e3, 2)} for k, v in t.items()}
         row["bf16_over_fp32"] = round(statistics.median(t["fp32"]) / statistics.median(t["bf16"]), 3)
@@ -142,7 +113,8 @@ def bench_models(batches, steps, warmup, rounds):
     vis = seeded_randn((B, 1, 224, 224), 2).to("cuda:0")
     target = torch.arange(B, device="cuda:0") % 1000
     evs = {k: PerturbationEvaluator(m, num_samples=B * (warmup + rounds * steps)) for k, m in models.items()}
-    t = _alternate({k: (lambda e=e: e.update(data, vis, target)) for k, e in evs.items()}, rounds, steps, warmup)
+    t = alternate({k: (lambda e=e: e.update(data, vis, target)) for k, e in evs.items()}, rounds, partial(event_window, n=steps),
+                  warmup)
     row = {k: {"seconds_per_update_median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
            for k, v in t.items()}
     row["bf16_over_fp32"] = round(statistics.median(t["fp32"]) / statistics.median(t["bf16"]), 3)

@@ -28,13 +28,16 @@ import json
 import os
 import statistics
 import sys
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from benchmarks.sweep_all_bench import _alternate, _ms, _same  # noqa: E402
+from benchmarks._models import vit_b16  # noqa: E402
+from benchmarks._timing import alternate, event_window  # noqa: E402  (the event-window protocol)
+from benchmarks.sweep_all_bench import _ms, _same  # noqa: E402
 
 
 def _peak_bytes(fn):
@@ -76,20 +79,17 @@ def _bench(Ks, logits_of, single_of, one_call_of, forward, name, steps, warmup, 
         equal = all(_same(got[:, k], single(k)) for k in range(K))
         del got
         fns = {"k_single_calls": lambda: [single(k) for k in range(K)], "one_call": one_call, "forward": forward}
-        times = _alternate(fns, rounds, steps, warmup)
+        times = alternate(fns, rounds, partial(event_window, n=steps), warmup)
         rows[f"K{K}"] = _row(K, single, one_call, times, equal, steps, warmup, rounds)
         ok = ok and equal
     return rows, ok
 
 
 def bench_vit(dtype, B, Ks, steps, warmup, rounds):
-    from oracle.ref_harness import synthetic_init
     from transformer_explainability_amd import generators as G
-    from transformer_explainability_amd import ops, vit
+    from transformer_explainability_amd import ops
     from transformer_explainability_amd.sweep import normalize
-    model = vit.vit_base_patch16_224().eval()
-    synthetic_init(model, 0)
-    model.to("cuda:0").to(dtype)
+    model = vit_b16(dtype)
     lrp = G.LRP(model)
     x = normalize(torch.rand((B, 3, 224, 224), generator=torch.Generator().manual_seed(B)).to("cuda:0")).to(dtype)
 

@@ -25,52 +25,24 @@ import json
 import os
 import statistics
 import sys
-import time
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-HBM_BYTES_PER_S = 8e12
-MEASURED_COPY_BYTES_PER_S = 6.29e12
+from benchmarks._models import vit_b16  # noqa: E402
+from benchmarks._timing import (HBM_BYTES_PER_S, MEASURED_COPY_BYTES_PER_S, alternate, summary,  # noqa: E402
+                                wall_window)                                  # (the wall-window protocol)
+
 B, C, H, W, STEP, CHUNK = 64, 3, 224, 224, 224, 8
 MEAN = STD = (0.5, 0.5, 0.5)
 BF = torch.bfloat16
 
 
-def _window(fn, min_s):
-    """seconds per call over a window of at least min_s (and at least one call)"""
-    torch.cuda.synchronize()
-    n, t0 = 0, time.perf_counter()
-    while True:
-        fn()
-        n += 1
-        if time.perf_counter() - t0 >= min_s:
-            break
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n
-
-
-def _alternate(fns, rounds, min_s, warmup):
-    for fn in fns.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in fns}
-    for _ in range(rounds):
-        for name, fn in fns.items():
-            times[name].append(_window(fn, min_s))
-    return times
-
-
-def _summary(ts, scale=1e3, unit="ms"):
-    return {f"median_{unit}": round(statistics.median(ts) * scale, 3), f"min_{unit}": round(min(ts) * scale, 3),
-            f"max_{unit}": round(max(ts) * scale, 3), "windows": len(ts)}
-
-
 def _pair(t, new="kernel", old="torch"):
-    return {new: _summary(t[new]), old: _summary(t[old]),
+    return {new: summary(t[new], 1e3, "ms", 3), old: summary(t[old], 1e3, "ms", 3),
             "torch_over_kernel_medians": round(statistics.median(t[old]) / statistics.median(t[new]), 2),
             "kernel_range_below_torch": bool(max(t[new]) < min(t[old]))}
 
@@ -108,21 +80,21 @@ def torch_inputs(data, vis, dtype, consume=None):
             consume(x, s0)
 
 
-def bench_inputs(rounds, min_s, warmup):
+def bench_inputs(rounds, window, warmup):
     from transformer_explainability_amd import curves, ops
     data, vis, _ = inputs()
     res = {}
     same_ranks = bool(torch.equal(ops.pixel_ranks(vis), curves.reference_ranks(vis)))
     for name, dtype in (("fp32", torch.float32), ("bf16", BF)):
-        t = _alternate({"kernel": lambda: kernel_inputs(data, vis, dtype), "torch": lambda: torch_inputs(data, vis, dtype)},
-                       rounds, min_s, warmup)
+        t = alternate({"kernel": lambda: kernel_inputs(data, vis, dtype), "torch": lambda: torch_inputs(data, vis, dtype)},
+                      rounds, window, warmup)
         row = _pair(t)
         row["ranks_equal"] = same_ranks
         res[f"insertion.B{B}.{H}x{W}.step{STEP}.{name}"] = row
     return res
 
 
-def bench_compose(rounds, min_s, warmup):
+def bench_compose(rounds, window, warmup):
     from transformer_explainability_amd import ops
     data, vis, _ = inputs()
     ranks = ops.pixel_ranks(vis)
@@ -131,24 +103,16 @@ def bench_compose(rounds, min_s, warmup):
     for name, dtype, size in (("fp32", torch.float32, 4), ("bf16", BF, 2)):
         fn = lambda: ops.curve_inputs(data, ranks, STEP, 100, CHUNK, "insertion", substrate=blurred, mean=MEAN, std=STD,  # noqa: E731
                                       out_dtype=dtype)
-        t = _alternate({"kernel": fn}, rounds, min_s, warmup)["kernel"]
+        t = alternate({"kernel": fn}, rounds, window, warmup)["kernel"]
         nbytes = CHUNK * B * C * H * W * size + 2 * B * C * H * W * 4 + B * H * W * 4
         med = statistics.median(t)
-        row = _summary(t, 1e6, "us")
+        row = summary(t, 1e6, "us", 3)
         row.update(algorithmic_bytes=nbytes, TB_per_s=round(nbytes / med / 1e12, 3),
                    share_of_8TBps=round(nbytes / med / HBM_BYTES_PER_S, 3),
                    share_of_measured_copy_rate_6_29TBps=round(nbytes / med / MEASURED_COPY_BYTES_PER_S, 3),
                    note="host clock over a window of back-to-back calls: launch and allocation of the output included")
         res[f"curve_inputs.B{B}.{H}x{W}.{CHUNK}steps.{name}"] = row
     return res
-
-
-def _vit_b16(dtype):
-    from oracle.ref_harness import synthetic_init
-    from transformer_explainability_amd import vit
-    m = vit.vit_base_patch16_224().eval()
-    synthetic_init(m, 0)
-    return m.to("cuda:0").to(dtype)
 
 
 @torch.no_grad()
@@ -174,14 +138,15 @@ def bench_update(rounds):
     data, vis, target = inputs()
     res = {}
     for name, dtype in (("bf16", BF), ("fp32", torch.float32)):
-        model = _vit_b16(dtype)
+        model = vit_b16(dtype)
 
         def kernel():
             ev = curves.CurveEvaluator(model, step=STEP, mean=MEAN, std=STD, max_forward_batch=CHUNK * B)
             ev.update(data, vis, target)
             return ev
-        t = _alternate({"kernel": kernel, "torch": lambda: restatement_update(model, data, vis, target, dtype)}, rounds, 0.0, 1)
-        row = {"kernel": _summary(t["kernel"], 1.0, "s"), "torch": _summary(t["torch"], 1.0, "s"),
+        t = alternate({"kernel": kernel, "torch": lambda: restatement_update(model, data, vis, target, dtype)}, rounds,
+                      partial(wall_window, min_s=0.0), 1)
+        row = {"kernel": summary(t["kernel"], 1.0, "s", 3), "torch": summary(t["torch"], 1.0, "s", 3),
                "torch_over_kernel_medians": round(statistics.median(t["torch"]) / statistics.median(t["kernel"]), 3),
                "kernel_range_below_torch": bool(max(t["kernel"]) < min(t["torch"])),
                "forwards_per_update": 2 * 225 * B}
@@ -206,8 +171,9 @@ def main():
     te._lib.require_device()
     res = {"bench": "curves", "rounds": a.rounds, "window_ms": a.window_ms, "warmup": a.warmup,
            "device": torch.cuda.get_device_name(0)}
-    res["inputs"] = bench_inputs(a.rounds, a.window_ms / 1e3, a.warmup)
-    res["compose"] = bench_compose(a.rounds, a.window_ms / 1e3, a.warmup)
+    window = partial(wall_window, min_s=a.window_ms / 1e3)
+    res["inputs"] = bench_inputs(a.rounds, window, a.warmup)
+    res["compose"] = bench_compose(a.rounds, window, a.warmup)
     if not a.skip_model:
         res["update"] = bench_update(a.model_rounds)
     res["build_id"] = te._lib.build_id()

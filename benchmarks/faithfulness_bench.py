@@ -25,21 +25,32 @@ import json
 import os
 import statistics
 import sys
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import torch  # noqa: E402
 
-from robustness_bench import (HBM_BYTES_PER_S, MEASURED_COPY_BYTES_PER_S, _alternate, _pair, _summary, _vit_b16,  # noqa: E402
-                              images)
+from benchmarks._models import vit_b16  # noqa: E402
+from benchmarks._timing import (HBM_BYTES_PER_S, MEASURED_COPY_BYTES_PER_S, alternate, summary,  # noqa: E402
+                                wall_window)                                  # (the wall-window protocol)
 
 B, C, H, W, GRID, P, K = 64, 3, 224, 224, 14, 16, 49
 DRAWS, PASS, RADIUS = 50, 10, 0.02
 N, G = C * H * W, GRID * GRID
 FILL = [-1.0, -1.0, -1.0]                            # "black" under mean = std = 0.5
 BF = torch.bfloat16
+
+
+def _pair(t, scale=1e6, unit="us"):
+    return {"kernel": summary(t["kernel"], scale, unit, 3), "torch": summary(t["torch"], scale, unit, 3),
+            "torch_over_kernel_medians": round(statistics.median(t["torch"]) / statistics.median(t["kernel"]), 2),
+            "kernel_range_below_torch": bool(max(t["kernel"]) < min(t["torch"]))}
+
+
+def images():
+    return torch.randn((B, C, H, W), generator=torch.Generator().manual_seed(0)).to("cuda:0")
 
 
 def torch_subsets(x, attr, n_d, dtype):
@@ -61,23 +72,23 @@ def _shares(row, nbytes, med):
     return row
 
 
-def bench_copies(rounds, min_s, warmup):
+def bench_copies(rounds, window, warmup):
     from transformer_explainability_amd import ops
     x = images()
     attr = torch.randn((B, G), generator=torch.Generator().manual_seed(3)).to("cuda:0")
     res = {}
     for name, dtype, size in (("fp32", torch.float32, 4), ("bf16", BF, 2)):
-        t = _alternate({"kernel": lambda: ops.subset_inputs(x, K, GRID, 0, n_draws=PASS, fill=FILL, attr=attr, out_dtype=dtype),
-                        "torch": lambda: torch_subsets(x, attr, PASS, dtype)}, rounds, min_s, warmup)
+        t = alternate({"kernel": lambda: ops.subset_inputs(x, K, GRID, 0, n_draws=PASS, fill=FILL, attr=attr, out_dtype=dtype),
+                       "torch": lambda: torch_subsets(x, attr, PASS, dtype)}, rounds, window, warmup)
         nbytes = B * PASS * N * size + B * N * 4 + 2 * B * PASS * G
         res[f"subset_inputs.B{B}.n{N}.{PASS}draws.{name}"] = _shares(_pair(t), nbytes, statistics.median(t["kernel"]))
-        t = _alternate({"kernel": lambda: ops.noise_inputs(x, PASS, RADIUS, 0, out_dtype=dtype)}, rounds, min_s, warmup)
-        row = {"kernel": _summary(t["kernel"])}
+        t = alternate({"kernel": lambda: ops.noise_inputs(x, PASS, RADIUS, 0, out_dtype=dtype)}, rounds, window, warmup)
+        row = {"kernel": summary(t["kernel"], digits=3)}
         res[f"noise_inputs.B{B}.n{N}.{PASS}draws.{name}"] = _shares(row, B * PASS * N * size + B * N * 4, statistics.median(t["kernel"]))
     return res
 
 
-def bench_dot(rounds, min_s, warmup):
+def bench_dot(rounds, window, warmup):
     from transformer_explainability_amd import faithfulness, ops
     g = torch.Generator().manual_seed(1)
     x = torch.randn((B, N), generator=g).to("cuda:0")
@@ -85,8 +96,8 @@ def bench_dot(rounds, min_s, warmup):
     res = {}
     for dtype in (torch.float32, BF):
         y = (x[:, None] + 0.02 * torch.randn((B, PASS, N), generator=g).to("cuda:0")).to(dtype)
-        t = _alternate({"kernel": lambda: ops.perturbation_dot(x, y, w), "torch": lambda: faithfulness.reference_dot(x, y, w)},
-                       rounds, min_s, warmup)
+        t = alternate({"kernel": lambda: ops.perturbation_dot(x, y, w), "torch": lambda: faithfulness.reference_dot(x, y, w)},
+                      rounds, window, warmup)
         row = _pair(t)
         nbytes = y.numel() * y.element_size() + x.numel() * 4 + w.numel() * 4
         row.update(algorithmic_bytes=nbytes, TB_per_s=round(nbytes / statistics.median(t["kernel"]) / 1e12, 3))
@@ -116,19 +127,20 @@ def torch_update(lrp, x, dtype):
     return faithfulness.scores_from_sums(torch.cat(ips, 1), torch.cat(deltas, 1), torch.cat(sums, 1))
 
 
-def bench_update(rounds, min_s, warmup):
+def bench_update(rounds, window, warmup):
     from transformer_explainability_amd import faithfulness, ops
     from transformer_explainability_amd.generators import LRP
     x = images()
     res = {}
     for name, dtype in (("bf16", BF), ("fp32", torch.float32)):
-        lrp = LRP(_vit_b16(dtype))
+        lrp = LRP(vit_b16(dtype))
 
         def kernel():
             ev = faithfulness.FaithfulnessEvaluator(lrp, n_draws=DRAWS, subset_size=K, seed=0, draws_per_pass=PASS)
             ev.update(x)
             return ev
-        t = _alternate({"kernel": kernel, "torch": lambda: torch_update(lrp, x, dtype)}, rounds, 0.0, 1)
+        t = alternate({"kernel": kernel, "torch": lambda: torch_update(lrp, x, dtype)}, rounds,
+                      partial(wall_window, min_s=0.0), 1)
         row = _pair(t, 1e3, "ms")
         # the evaluator's own launches of one update, alone, on tensors of the same shapes
         clean = x.to(dtype).float()
@@ -144,8 +156,8 @@ def bench_update(rounds, min_s, warmup):
                 copies, _, _ = ops.subset_inputs(clean, K, GRID, 0, d0=d0, n_draws=PASS, fill=FILL, attr=map0, out_dtype=dtype)
                 ops.curve_scores(logits, target, prob, 0)
                 ops.perturbation_dot(clean.reshape(B, -1), copies.reshape(B, PASS, -1), weight)
-        tk = _alternate({"kernel": launches}, rounds, min_s, warmup)["kernel"]
-        row["kernels_ms"] = _summary(tk, 1e3, "ms")
+        tk = alternate({"kernel": launches}, rounds, window, warmup)["kernel"]
+        row["kernels_ms"] = summary(tk, 1e3, "ms", 3)
         row["kernels_share_of_update"] = round(statistics.median(tk) / statistics.median(t["kernel"]), 5)
         row["forward_rows_per_update"] = (1 + DRAWS // PASS) * B * PASS
         row["summary"] = kernel().summary()
@@ -169,10 +181,11 @@ def main():
     te._lib.require_device()
     res = {"bench": "faithfulness", "rounds": a.rounds, "window_ms": a.window_ms, "warmup": a.warmup,
            "device": torch.cuda.get_device_name(0)}
-    res["copies"] = bench_copies(a.rounds, a.window_ms / 1e3, a.warmup)
-    res["dot"] = bench_dot(a.rounds, a.window_ms / 1e3, a.warmup)
+    window = partial(wall_window, min_s=a.window_ms / 1e3)
+    res["copies"] = bench_copies(a.rounds, window, a.warmup)
+    res["dot"] = bench_dot(a.rounds, window, a.warmup)
     if not a.skip_model:
-        res["update"] = bench_update(a.model_rounds, a.window_ms / 1e3, a.warmup)
+        res["update"] = bench_update(a.model_rounds, window, a.warmup)
     res["build_id"] = te._lib.build_id()
     line = json.dumps(res)
     if a.out:

@@ -17,11 +17,14 @@ import json
 import os
 import statistics
 import sys
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PEAK_BYTES_PER_S = 8.0e12
+from benchmarks._models import vit_b16  # noqa: E402
+from benchmarks._timing import HBM_BYTES_PER_S as PEAK_BYTES_PER_S  # noqa: E402
+from benchmarks._timing import alternate, event_window  # noqa: E402  (the event-window protocol)
 
 
 def main():
@@ -39,26 +42,10 @@ def main():
     d = torch.device("cuda:0")
     res = {"build_id": _lib.build_id(), "peak_bytes_per_s": PEAK_BYTES_PER_S, "windows": args.windows, "reps": args.reps}
 
-    def window(fn, reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / reps * 1e3          # us per call
-
-    def alternate(legs, windows, reps):
+    def alternate_us(legs, windows, reps):
         """legs: {name: fn}; every window times each leg once, in turn -> {name: median us}"""
-        for fn in legs.values():
-            for _ in range(3):
-                fn()
-        torch.cuda.synchronize()
-        times = {n: [] for n in legs}
-        for _ in range(windows):
-            for n, fn in legs.items():
-                times[n].append(window(fn, reps))
-        return {n: {"us": statistics.median(t), "us_min": min(t), "us_max": max(t)} for n, t in times.items()}
+        times = alternate(legs, windows, partial(event_window, n=reps), 3)
+        return {n: {"us": statistics.median(t) * 1e6, "us_min": min(t) * 1e6, "us_max": max(t) * 1e6} for n, t in times.items()}
 
     for B, H, N in ((64, 12, 197), (32, 12, 512)):
         g = torch.Generator().manual_seed(N)
@@ -74,7 +61,7 @@ def main():
             legs = {"kernel": lambda P=P, m=m: ops.mul_head_relprop(R, P, m, out=out), "torch": torch_rule}
             if sfx == "f32":
                 legs["clone_rule"] = lambda: ops.clone_relprop([R, out], P32)
-            t = alternate(legs, args.windows, args.reps)
+            t = alternate_us(legs, args.windows, args.reps)
             nbytes = n * (4 + P.element_size() + 4)
             t["kernel"].update(algorithmic_bytes=nbytes, fraction_of_peak=nbytes / (t["kernel"]["us"] * 1e-6) / PEAK_BYTES_PER_S)
             t["torch"]["kernel_speedup"] = t["torch"]["us"] / t["kernel"]["us"]
@@ -90,12 +77,9 @@ def main():
         del P32, R, out
 
     if not args.skip_model:
-        from oracle.ref_harness import seeded_randn, synthetic_init
-        from transformer_explainability_amd import vit
+        from oracle.ref_harness import seeded_randn
         from transformer_explainability_amd.generators import LRP
-        model = vit.vit_base_patch16_224().eval()
-        synthetic_init(model, 0)
-        model.to(d)
+        model = vit_b16()
         x = seeded_randn((64, 3, 224, 224), 1).to(d)
         ones = torch.ones(12, 12, device=d)
         lrp = LRP(model)
@@ -110,7 +94,7 @@ def main():
             return run
         legs = {"unmasked_stock_forward": step(None, False), "masked_every_head": step(ones, False),
                 "masked_every_head_flag_on": step(ones, True), "unmasked_fused_producers": step(None, True)}
-        t = alternate(legs, args.model_windows, 2)
+        t = alternate_us(legs, args.model_windows, 2)
         lrp.check()
         base = t["unmasked_stock_forward"]["us"]
         for v in t.values():

@@ -24,45 +24,17 @@ import json
 import os
 import statistics
 import sys
-import time
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-HBM_BYTES_PER_S = 8.0e12
+from benchmarks._models import vit_b16  # noqa: E402
+from benchmarks._timing import HBM_BYTES_PER_S, alternate, summary, wall_window  # noqa: E402  (the wall-window protocol)
+
 DEV = "cuda:0"
-
-
-def _window(fn, min_s):
-    """seconds per call over a window of at least min_s (and at least one call)"""
-    torch.cuda.synchronize()
-    n, t0 = 0, time.perf_counter()
-    while True:
-        fn()
-        n += 1
-        if time.perf_counter() - t0 >= min_s:
-            break
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n
-
-
-def _alternate(fns, rounds, min_s, warmup):
-    for fn in fns.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in fns}
-    for _ in range(rounds):
-        for name, fn in fns.items():
-            times[name].append(_window(fn, min_s))
-    return times
-
-
-def _summary(ts, scale=1e6, unit="us"):
-    return {f"median_{unit}": round(statistics.median(ts) * scale, 2), f"min_{unit}": round(min(ts) * scale, 2),
-            f"max_{unit}": round(max(ts) * scale, 2), "windows": len(ts)}
 
 
 def _verdict(old, new):
@@ -88,20 +60,20 @@ def inputs(B, K, seed=0):
                 image_index=torch.arange(B).repeat_interleave(K).to(DEV))
 
 
-def bench_metrics(rounds, min_s, warmup):
+def bench_metrics(rounds, window, warmup):
     from transformer_explainability_amd import localisation as L, ops
     res = {}
     for B, K in ((64, 2), (1, 1)):
         case = inputs(B, K)
         got, ref = ops.localisation_metrics(**case), L.reference_metrics(**case)
-        t = _alternate({"kernel": lambda: ops.localisation_metrics(**case), "torch": lambda: L.reference_metrics(**case)},
-                       rounds, min_s, warmup)
+        t = alternate({"kernel": lambda: ops.localisation_metrics(**case), "torch": lambda: L.reference_metrics(**case)},
+                      rounds, window, warmup)
         P, HW = B * K, 224 * 224
         nbytes = P * HW * 4 + B * HW * 8
-        k = _summary(t["kernel"])
+        k = summary(t["kernel"])
         k.update(bytes_algorithmic=nbytes, hbm_fraction_of_8TBps=round(nbytes / statistics.median(t["kernel"]) / HBM_BYTES_PER_S, 4))
         rel = ((got[1] - ref[1]).abs() / ref[1].abs().clamp(min=1e-300)).max()
-        res[f"pairs{P}.images{B}.224x224"] = {"kernel": k, "torch": _summary(t["torch"]), **_verdict(t["torch"], t["kernel"]),
+        res[f"pairs{P}.images{B}.224x224"] = {"kernel": k, "torch": summary(t["torch"]), **_verdict(t["torch"], t["kernel"]),
                                               "stats_equal": bool(torch.equal(got[0], ref[0])),
                                               "max_rel_energy_kernel_minus_torch": float(rel)}
     return res
@@ -121,14 +93,11 @@ def old_update(ev, lrp, x, labels, classes):
     return stats, energy
 
 
-def bench_evaluator(rounds, min_s, warmup, B=64, K=2):
-    from oracle.ref_harness import synthetic_init
-    from transformer_explainability_amd import localisation as L, vit
+def bench_evaluator(rounds, window, warmup, B=64, K=2):
+    from transformer_explainability_amd import localisation as L
     from transformer_explainability_amd.generators import LRP
     from transformer_explainability_amd.sweep import normalize
-    m = vit.vit_base_patch16_224().eval()
-    synthetic_init(m, 0)
-    lrp = LRP(m.to(DEV))
+    lrp = LRP(vit_b16())
     g = torch.Generator().manual_seed(B)
     x = normalize(torch.rand((B, 3, 224, 224), generator=g).to(DEV))
     labels = regions(B, 224, 1000, g).to(DEV)
@@ -136,12 +105,12 @@ def bench_evaluator(rounds, min_s, warmup, B=64, K=2):
     # that pair is then not counted)
     classes = torch.stack([labels[:, 8, 8].clamp(min=0), labels[:, 120, 120].clamp(min=0)], 1).contiguous()
     ev_new, ev_old = L.LocalisationEvaluator(1000), L.LocalisationEvaluator(1000)
-    t = _alternate({"new": lambda: ev_new.update(lrp, x, labels=labels, classes=classes, start_layer=1),
-                    "old": lambda: old_update(ev_old, lrp, x, labels, classes),
-                    "explain_only": lambda: lrp.generate_classes(x, classes=classes, methods=("transformer_attribution",),
-                                                                 start_layer=1)}, rounds, min_s, warmup)
+    t = alternate({"new": lambda: ev_new.update(lrp, x, labels=labels, classes=classes, start_layer=1),
+                   "old": lambda: old_update(ev_old, lrp, x, labels, classes),
+                   "explain_only": lambda: lrp.generate_classes(x, classes=classes, methods=("transformer_attribution",),
+                                                                start_layer=1)}, rounds, window, warmup)
     lrp.check()
-    row = {k: {"images_per_s": round(B / statistics.median(v), 1), **_summary(v, 1e3, "ms")} for k, v in t.items()}
+    row = {k: {"images_per_s": round(B / statistics.median(v), 1), **summary(v, 1e3, "ms")} for k, v in t.items()}
     row.update(_verdict(t["old"], t["new"]))
     row["summary_new"], row["summary_old"] = ev_new.summary(), ev_old.summary()
     return {f"update.vit_base_patch16_224.batch{B}.classes{K}": row}
@@ -160,9 +129,10 @@ def main():
     te._lib.require_device()
     res = {"bench": "localisation", "rounds": a.rounds, "window_ms": a.window_ms, "warmup": a.warmup,
            "device": torch.cuda.get_device_name(0)}
-    res["metrics"] = bench_metrics(a.rounds, a.window_ms / 1e3, a.warmup)
+    window = partial(wall_window, min_s=a.window_ms / 1e3)
+    res["metrics"] = bench_metrics(a.rounds, window, a.warmup)
     if not a.skip_model:
-        res["evaluator"] = bench_evaluator(a.rounds, a.window_ms / 1e3, a.warmup)
+        res["evaluator"] = bench_evaluator(a.rounds, window, a.warmup)
     res["build_id"] = te._lib.build_id()
     line = json.dumps(res)
     if a.out:

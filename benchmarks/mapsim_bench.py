@@ -21,44 +21,17 @@ import json
 import os
 import statistics
 import sys
-import time
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchmarks._models import vit_b16  # noqa: E402
+from benchmarks._timing import alternate, summary, wall_window  # noqa: E402  (the wall-window protocol)
+
 SHAPES = ((64, 196, None), (64, 50176, (224, 224)), (1, 50176, None))
-
-
-def _window(fn, min_s):
-    """seconds per call over a window of at least min_s (and at least one call)"""
-    torch.cuda.synchronize()
-    n, t0 = 0, time.perf_counter()
-    while True:
-        fn()
-        n += 1
-        if time.perf_counter() - t0 >= min_s:
-            break
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n
-
-
-def _alternate(fns, rounds, min_s, warmup):
-    for fn in fns.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in fns}
-    for _ in range(rounds):
-        for name, fn in fns.items():
-            times[name].append(_window(fn, min_s))
-    return times
-
-
-def _summary(ts, scale=1e6, unit="us"):
-    return {f"median_{unit}": round(statistics.median(ts) * scale, 2), f"min_{unit}": round(min(ts) * scale, 2),
-            f"max_{unit}": round(max(ts) * scale, 2), "windows": len(ts)}
 
 
 def inputs(B, n, seed=0):
@@ -76,11 +49,11 @@ def bench_metrics(rounds, min_s, warmup):
     for B, n, shape in SHAPES:
         a, b = inputs(B, n)
         got, ref = ops.map_similarity(a, b, shape), sanity.map_similarity(a, b, shape)
-        t = _alternate({"kernel": lambda: ops.map_similarity(a, b, shape),
-                        "torch": lambda: sanity.map_similarity(a, b, shape)}, rounds, min_s, warmup)
+        t = alternate({"kernel": lambda: ops.map_similarity(a, b, shape),
+                       "torch": lambda: sanity.map_similarity(a, b, shape)}, rounds, partial(wall_window, min_s=min_s), warmup)
         d = (torch.nan_to_num(got[1]) - torch.nan_to_num(ref[1])).abs().max(0).values
         res[f"B{B}.n{n}" + (".ssim" if shape else "")] = {
-            "kernel": _summary(t["kernel"]), "torch": _summary(t["torch"]),
+            "kernel": summary(t["kernel"]), "torch": summary(t["torch"]),
             "torch_over_kernel_medians": round(statistics.median(t["torch"]) / statistics.median(t["kernel"]), 2),
             "kernel_range_below_torch": bool(max(t["kernel"]) < min(t["torch"])),
             "rank_sums_equal": bool(torch.equal(got[0], ref[0])),
@@ -90,13 +63,11 @@ def bench_metrics(rounds, min_s, warmup):
 
 
 def bench_evaluator(rounds, B):
-    from oracle.ref_harness import synthetic_init
-    from transformer_explainability_amd import sanity, vit
+    from transformer_explainability_amd import sanity
     from transformer_explainability_amd.generators import LRP
     from transformer_explainability_amd.sweep import normalize
-    m = vit.vit_base_patch16_224().eval()
-    synthetic_init(m, 0)
-    lrp = LRP(m.to("cuda:0"))
+    m = vit_b16()
+    lrp = LRP(m)
     g = torch.Generator().manual_seed(B)
     x = normalize(torch.rand((B, 3, 224, 224), generator=g).to("cuda:0"))
     methods = ("transformer_attribution", "attn_rollout")
@@ -113,10 +84,11 @@ def bench_evaluator(rounds, B):
         finally:
             sanity.compare_maps = real
         return ev
-    t = _alternate({"with_metrics": lambda: update(True), "without_metrics": lambda: update(False)}, rounds, 0.0, 1)
+    t = alternate({"with_metrics": lambda: update(True), "without_metrics": lambda: update(False)}, rounds,
+                  partial(wall_window, min_s=0.0), 1)
     lrp.check()
     with_m, without = statistics.median(t["with_metrics"]), statistics.median(t["without_metrics"])
-    row = {k: _summary(v, 1e3, "ms") for k, v in t.items()}
+    row = {k: summary(v, 1e3, "ms") for k, v in t.items()}
     row["metrics_share_of_update"] = round((with_m - without) / with_m, 4)
     row["stages"], row["methods"], row["upsample"] = len(sanity.randomization_stages(m)), methods, True
     s = update(True).summary()

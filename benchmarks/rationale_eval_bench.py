@@ -25,12 +25,15 @@ import json
 import os
 import statistics
 import sys
-import time
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+
+from benchmarks._models import bert_base  # noqa: E402
+from benchmarks._timing import alternate, summary, wall_window  # noqa: E402  (the wall-window protocol)
 
 KS = list(range(5, 85, 5))
 
@@ -57,35 +60,6 @@ def old_update_from_scores(totals, scores, word_ids, truth):
 
 def new_totals():
     return {"tp": [0] * len(KS), "pred": [0] * len(KS), "truth": 0, "soft": []}
-
-
-def _window(fn, min_s):
-    torch.cuda.synchronize()
-    n, t0 = 0, time.perf_counter()
-    while True:
-        fn()
-        n += 1
-        if time.perf_counter() - t0 >= min_s:
-            break
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n
-
-
-def _alternate(fns, rounds, min_s, warmup):
-    for fn in fns.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in fns}
-    for _ in range(rounds):
-        for name, fn in fns.items():
-            times[name].append(_window(fn, min_s))
-    return times
-
-
-def _summary(ts, scale=1e6, unit="us"):
-    return {f"median_{unit}": round(statistics.median(ts) * scale, 2), f"min_{unit}": round(min(ts) * scale, 2),
-            f"max_{unit}": round(max(ts) * scale, 2), "windows": len(ts)}
 
 
 def _verdict(t):
@@ -120,7 +94,7 @@ def _clear(ev):
         getattr(ev, name).clear()
 
 
-def bench_metrics(batches, rounds, min_s, warmup):
+def bench_metrics(batches, rounds, window, warmup):
     from transformer_explainability_amd import ops, rationale as rt
     res = {}
     for B in batches:
@@ -147,30 +121,27 @@ def bench_metrics(batches, rounds, min_s, warmup):
             totals["soft"].clear()
             old_update_from_scores(totals, scores, wid, truth)
 
-        t = _alternate({"new": run_new, "old": run_old, "torch_batched": run_torch,
-                        "kernel_only": lambda: ops.rationale_metrics(scores, wid, truth, KS)}, rounds, min_s, warmup)
+        t = alternate({"new": run_new, "old": run_old, "torch_batched": run_torch,
+                       "kernel_only": lambda: ops.rationale_metrics(scores, wid, truth, KS)}, rounds, window, warmup)
         res[f"update_from_scores.B{B}.512"] = {
-            "new": _summary(t["new"]), "old": _summary(t["old"]), "torch_batched": _summary(t["torch_batched"]),
-            "kernel_only": _summary(t["kernel_only"]), **_verdict(t), "integers_equal": bool(same),
+            "new": summary(t["new"]), "old": summary(t["old"]), "torch_batched": summary(t["torch_batched"]),
+            "kernel_only": summary(t["kernel_only"]), **_verdict(t), "integers_equal": bool(same),
             "max_abs_soft_new_minus_old": float((got["soft"].cpu() - torch.stack(old["soft"])).abs().max())}
         fr = rt.THRESHOLDS
         e_new = ops.token_erase(ids, mask, wid, got["order"], got["n_words"], fr)
         e_old = rt.token_erase_torch(ids, mask, wid, got["order"], got["n_words"], fr)
-        te = _alternate({"new": lambda: ops.token_erase(ids, mask, wid, got["order"], got["n_words"], fr),
-                         "old": lambda: rt.token_erase_torch(ids, mask, wid, got["order"], got["n_words"], fr)},
-                        rounds, min_s, warmup)
-        res[f"token_erase.B{B}.512"] = {"new": _summary(te["new"]), "old": _summary(te["old"]), **_verdict(te),
+        te = alternate({"new": lambda: ops.token_erase(ids, mask, wid, got["order"], got["n_words"], fr),
+                        "old": lambda: rt.token_erase_torch(ids, mask, wid, got["order"], got["n_words"], fr)},
+                       rounds, window, warmup)
+        res[f"token_erase.B{B}.512"] = {"new": summary(te["new"]), "old": summary(te["old"]), **_verdict(te),
                                         "equal": bool(all(torch.equal(a, b) for a, b in zip(e_new, e_old)))}
     return res
 
 
-def bench_evaluator(rounds, min_s, warmup, B=32, N=512):
-    from oracle.ref_harness import synthetic_init
-    from transformer_explainability_amd import bert, rationale as rt
+def bench_evaluator(rounds, window, warmup, B=32, N=512):
+    from transformer_explainability_amd import rationale as rt
     from transformer_explainability_amd.generators import Generator
-    m = bert.BertForSequenceClassification(bert.BertConfigLite(num_labels=2)).eval()
-    synthetic_init(m, 0)
-    gen = Generator(m.to("cuda:0"))
+    gen = Generator(bert_base())
     _, wid, truth, ids, mask = inputs(B, N, seed=7)
     fmask = mask.float()
     explain = lambda i, a, x: gen.generate_LRP(i, a, index=x, start_layer=0)      # noqa: E731
@@ -185,9 +156,9 @@ def bench_evaluator(rounds, min_s, warmup, B=32, N=512):
         totals["soft"].clear()
         old_update_from_scores(totals, explain(ids, fmask, None).detach(), wid, truth)
 
-    t = _alternate({"new": run_new, "old": run_old, "explain_only": lambda: explain(ids, fmask, None)}, rounds, min_s, warmup)
+    t = alternate({"new": run_new, "old": run_old, "explain_only": lambda: explain(ids, fmask, None)}, rounds, window, warmup)
     gen.check()
-    row = {k: {"documents_per_s": round(B / statistics.median(v), 1), **_summary(v, 1e3, "ms")} for k, v in t.items()}
+    row = {k: {"documents_per_s": round(B / statistics.median(v), 1), **summary(v, 1e3, "ms")} for k, v in t.items()}
     row.update(_verdict(t))
     return {f"update.bert_base.batch{B}.{N}": row}
 
@@ -206,9 +177,10 @@ def main():
     te._lib.require_device()
     res = {"bench": "rationale_eval", "rounds": a.rounds, "window_ms": a.window_ms, "warmup": a.warmup,
            "device": torch.cuda.get_device_name(0)}
-    res["metrics"] = bench_metrics([int(b) for b in a.batches.split(",")], a.rounds, a.window_ms / 1e3, a.warmup)
+    window = partial(wall_window, min_s=a.window_ms / 1e3)
+    res["metrics"] = bench_metrics([int(b) for b in a.batches.split(",")], a.rounds, window, a.warmup)
     if not a.skip_model:
-        res["evaluator"] = bench_evaluator(a.rounds, a.window_ms / 1e3, a.warmup)
+        res["evaluator"] = bench_evaluator(a.rounds, window, a.warmup)
     res["build_id"] = te._lib.build_id()
     line = json.dumps(res)
     if a.out:

@@ -27,52 +27,24 @@ import json
 import os
 import statistics
 import sys
-import time
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-HBM_BYTES_PER_S = 8e12
-MEASURED_COPY_BYTES_PER_S = 6.29e12
+from benchmarks._models import vit_b16  # noqa: E402
+from benchmarks._timing import (HBM_BYTES_PER_S, MEASURED_COPY_BYTES_PER_S, alternate, summary,  # noqa: E402
+                                wall_window)                                  # (the wall-window protocol)
+
 B, C, H, W, DRAWS, RADIUS = 64, 3, 224, 224, 10, 0.02
 N = C * H * W
 BF = torch.bfloat16
 
 
-def _window(fn, min_s):
-    """seconds per call over a window of at least min_s (and at least one call)"""
-    torch.cuda.synchronize()
-    n, t0 = 0, time.perf_counter()
-    while True:
-        fn()
-        n += 1
-        if time.perf_counter() - t0 >= min_s:
-            break
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n
-
-
-def _alternate(fns, rounds, min_s, warmup):
-    for fn in fns.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in fns}
-    for _ in range(rounds):
-        for name, fn in fns.items():
-            times[name].append(_window(fn, min_s))
-    return times
-
-
-def _summary(ts, scale=1e6, unit="us"):
-    return {f"median_{unit}": round(statistics.median(ts) * scale, 3), f"min_{unit}": round(min(ts) * scale, 3),
-            f"max_{unit}": round(max(ts) * scale, 3), "windows": len(ts)}
-
-
 def _pair(t, scale=1e6, unit="us"):
-    return {"kernel": _summary(t["kernel"], scale, unit), "torch": _summary(t["torch"], scale, unit),
+    return {"kernel": summary(t["kernel"], scale, unit, 3), "torch": summary(t["torch"], scale, unit, 3),
             "torch_over_kernel_medians": round(statistics.median(t["torch"]) / statistics.median(t["kernel"]), 2),
             "kernel_range_below_torch": bool(max(t["kernel"]) < min(t["torch"]))}
 
@@ -87,13 +59,13 @@ def torch_noise(x, n_d, dtype):
     return (x[:, None] + RADIUS * (2 * u - 1)).to(dtype)
 
 
-def bench_noise(rounds, min_s, warmup):
+def bench_noise(rounds, window, warmup):
     from transformer_explainability_amd import ops
     x = images()
     res = {}
     for name, dtype, size in (("fp32", torch.float32, 4), ("bf16", BF, 2)):
-        t = _alternate({"kernel": lambda: ops.noise_inputs(x, DRAWS, RADIUS, 0, out_dtype=dtype),
-                        "torch": lambda: torch_noise(x, DRAWS, dtype)}, rounds, min_s, warmup)
+        t = alternate({"kernel": lambda: ops.noise_inputs(x, DRAWS, RADIUS, 0, out_dtype=dtype),
+                       "torch": lambda: torch_noise(x, DRAWS, dtype)}, rounds, window, warmup)
         row = _pair(t)
         med = statistics.median(t["kernel"])
         nbytes = B * DRAWS * N * size + B * N * 4
@@ -107,7 +79,7 @@ def bench_noise(rounds, min_s, warmup):
     return res
 
 
-def bench_distance(rounds, min_s, warmup):
+def bench_distance(rounds, window, warmup):
     from transformer_explainability_amd import ops, robustness
     g = torch.Generator().manual_seed(1)
     res = {}
@@ -115,8 +87,8 @@ def bench_distance(rounds, min_s, warmup):
         a = torch.randn((B, n), generator=g).to("cuda:0")
         for dtype in dtypes:
             b = (a[:, None] + 0.02 * torch.randn((B, DRAWS, n), generator=g).to("cuda:0")).to(dtype)
-            t = _alternate({"kernel": lambda: ops.map_distance(a, b), "torch": lambda: robustness.reference_distance(a, b)},
-                           rounds, min_s, warmup)
+            t = alternate({"kernel": lambda: ops.map_distance(a, b), "torch": lambda: robustness.reference_distance(a, b)},
+                          rounds, window, warmup)
             row = _pair(t)
             nbytes = b.numel() * b.element_size() + a.numel() * 4
             row.update(algorithmic_bytes=nbytes, TB_per_s=round(nbytes / statistics.median(t["kernel"]) / 1e12, 3))
@@ -124,24 +96,16 @@ def bench_distance(rounds, min_s, warmup):
     return res
 
 
-def bench_complexity(rounds, min_s, warmup):
+def bench_complexity(rounds, window, warmup):
     from transformer_explainability_amd import ops, robustness
     g = torch.Generator().manual_seed(2)
     res = {}
     for n in (196, H * W):
         m = torch.randn((B, n), generator=g).to("cuda:0")
-        t = _alternate({"kernel": lambda: ops.map_complexity(m), "torch": lambda: robustness.reference_complexity(m)},
-                       rounds, min_s, warmup)
+        t = alternate({"kernel": lambda: ops.map_complexity(m), "torch": lambda: robustness.reference_complexity(m)},
+                      rounds, window, warmup)
         res[f"map_complexity.B{B}.n{n}"] = _pair(t)
     return res
-
-
-def _vit_b16(dtype):
-    from oracle.ref_harness import synthetic_init
-    from transformer_explainability_amd import vit
-    m = vit.vit_base_patch16_224().eval()
-    synthetic_init(m, 0)
-    return m.to("cuda:0").to(dtype)
 
 
 def torch_update(lrp, x, dtype):
@@ -161,19 +125,20 @@ def torch_update(lrp, x, dtype):
     return scores, robustness.reference_complexity(map0)
 
 
-def bench_update(rounds, min_s, warmup):
+def bench_update(rounds, window, warmup):
     from transformer_explainability_amd import ops, robustness
     from transformer_explainability_amd.generators import LRP
     x = images()
     res = {}
     for name, dtype in (("bf16", BF), ("fp32", torch.float32)):
-        lrp = LRP(_vit_b16(dtype))
+        lrp = LRP(vit_b16(dtype))
 
         def kernel():
             ev = robustness.SensitivityEvaluator(lrp, n_draws=DRAWS, radius=RADIUS, seed=0, draws_per_pass=1)
             ev.update(x)
             return ev
-        t = _alternate({"kernel": kernel, "torch": lambda: torch_update(lrp, x, dtype)}, rounds, 0.0, 1)
+        t = alternate({"kernel": kernel, "torch": lambda: torch_update(lrp, x, dtype)}, rounds,
+                      partial(wall_window, min_s=0.0), 1)
         row = _pair(t, 1e3, "ms")
         # the evaluator's own launches of one update, alone, on tensors of the same shapes
         clean = x.to(dtype).float()
@@ -186,8 +151,8 @@ def bench_update(rounds, min_s, warmup):
                 ops.map_distance(maps0, maps1)
                 ops.map_distance(clean.reshape(B, -1), copies.reshape(B, 1, -1))
             ops.map_complexity(maps0)
-        tk = _alternate({"kernel": launches}, rounds, min_s, warmup)["kernel"]
-        row["kernels_ms"] = _summary(tk, 1e3, "ms")
+        tk = alternate({"kernel": launches}, rounds, window, warmup)["kernel"]
+        row["kernels_ms"] = summary(tk, 1e3, "ms", 3)
         row["kernels_share_of_update"] = round(statistics.median(tk) / statistics.median(t["kernel"]), 5)
         row["explanations_per_update"] = (1 + DRAWS) * B
         row["summary"] = kernel().summary()
@@ -211,11 +176,12 @@ def main():
     te._lib.require_device()
     res = {"bench": "robustness", "rounds": a.rounds, "window_ms": a.window_ms, "warmup": a.warmup,
            "device": torch.cuda.get_device_name(0)}
-    res["noise"] = bench_noise(a.rounds, a.window_ms / 1e3, a.warmup)
-    res["distance"] = bench_distance(a.rounds, a.window_ms / 1e3, a.warmup)
-    res["complexity"] = bench_complexity(a.rounds, a.window_ms / 1e3, a.warmup)
+    window = partial(wall_window, min_s=a.window_ms / 1e3)
+    res["noise"] = bench_noise(a.rounds, window, a.warmup)
+    res["distance"] = bench_distance(a.rounds, window, a.warmup)
+    res["complexity"] = bench_complexity(a.rounds, window, a.warmup)
     if not a.skip_model:
-        res["update"] = bench_update(a.model_rounds, a.window_ms / 1e3, a.warmup)
+        res["update"] = bench_update(a.model_rounds, window, a.warmup)
     res["build_id"] = te._lib.build_id()
     line = json.dumps(res)
     if a.out:

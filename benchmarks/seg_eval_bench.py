@@ -25,14 +25,15 @@ import json
 import os
 import statistics
 import sys
-import time
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-HBM_BYTES_PER_S = 8.0e12
+from benchmarks._models import vit_b16  # noqa: E402
+from benchmarks._timing import HBM_BYTES_PER_S, alternate, summary, wall_window  # noqa: E402  (the wall-window protocol)
 
 
 def old_update_from_heat(ev, heat, mask, labels):
@@ -55,36 +56,6 @@ def old_update(ev, image, labels):
     maps = ev.explain(image).detach()
     heat, mask = sg.foreground_split(maps.reshape(maps.shape[0], -1), ev.scale)
     return old_update_from_heat(ev, heat, mask, labels)
-
-
-def _window(fn, min_s):
-    """seconds per call over a window of at least min_s (and at least one call)"""
-    torch.cuda.synchronize()
-    n, t0 = 0, time.perf_counter()
-    while True:
-        fn()
-        n += 1
-        if time.perf_counter() - t0 >= min_s:
-            break
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n
-
-
-def _alternate(fns, rounds, min_s, warmup):
-    for fn in fns.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in fns}
-    for _ in range(rounds):
-        for name, fn in fns.items():
-            times[name].append(_window(fn, min_s))
-    return times
-
-
-def _summary(ts, scale=1e6, unit="us"):
-    return {f"median_{unit}": round(statistics.median(ts) * scale, 2), f"min_{unit}": round(min(ts) * scale, 2),
-            f"max_{unit}": round(max(ts) * scale, 2), "windows": len(ts)}
 
 
 def _verdict(t):
@@ -110,7 +81,7 @@ def _counted(fn, calls, name):
     return run
 
 
-def bench_one_version(batches, rounds, min_s, warmup, only):
+def bench_one_version(batches, rounds, window, warmup, only):
     """--only: one version by itself (for a profiler), with the number of updates it made"""
     from transformer_explainability_amd import segmentation as sg
     res = {}
@@ -119,28 +90,28 @@ def bench_one_version(batches, rounds, min_s, warmup, only):
         ev, calls = sg.SegmentationEvaluator(None), {}
         fn = (lambda: ev.update_from_heat(heat, mask, labels)) if only == "new" else \
             (lambda: old_update_from_heat(ev, heat_c, mask_c, labels))
-        t = _alternate({only: _counted(fn, calls, only)}, rounds, min_s, warmup)
-        res[f"update_from_heat.B{B}.224x224"] = {only: _summary(t[only]), "calls": calls}
+        t = alternate({only: _counted(fn, calls, only)}, rounds, window, warmup)
+        res[f"update_from_heat.B{B}.224x224"] = {only: summary(t[only]), "calls": calls}
     return res
 
 
-def bench_metrics(batches, rounds, min_s, warmup):
+def bench_metrics(batches, rounds, window, warmup):
     from transformer_explainability_amd import ops, segmentation as sg
     res = {}
     for B in batches:
         _, heat, mask, (heat_c, mask_c), labels = inputs(B)
         ev_new, ev_old = sg.SegmentationEvaluator(None), sg.SegmentationEvaluator(None)
         got, ref = ev_new.update_from_heat(heat, mask, labels), old_update_from_heat(ev_old, heat_c, mask_c, labels)
-        t = _alternate({"new": lambda: ev_new.update_from_heat(heat, mask, labels),
-                        "old": lambda: old_update_from_heat(ev_old, heat_c, mask_c, labels),
-                        "kernel_only": lambda: ops.seg_metrics(heat, mask, labels)}, rounds, min_s, warmup)
+        t = alternate({"new": lambda: ev_new.update_from_heat(heat, mask, labels),
+                       "old": lambda: old_update_from_heat(ev_old, heat_c, mask_c, labels),
+                       "kernel_only": lambda: ops.seg_metrics(heat, mask, labels)}, rounds, window, warmup)
         # what the kernel must move: the three inputs once, the sort elements written once and, per radix pass, read and
         # written once (8 B each, 2 H W per image), the run scan's two reads, the outputs
         P = 224 * 224
         nbytes = B * (P * (4 + 4 + 8) + 2 * P * 8 * (1 + 2 * 4 + 2) + (7 + 224) * 8)
-        k = _summary(t["kernel_only"])
+        k = summary(t["kernel_only"])
         k.update(bytes_moved=nbytes, hbm_fraction_of_8TBps=round(nbytes / statistics.median(t["kernel_only"]) / HBM_BYTES_PER_S, 4))
-        row = {"new": _summary(t["new"]), "old": _summary(t["old"]), "kernel_only": k, **_verdict(t),
+        row = {"new": summary(t["new"]), "old": summary(t["old"]), "kernel_only": k, **_verdict(t),
                "integers_equal": bool(all(torch.equal(a, b) for a, b in zip(got[:4], ref[:4])) and torch.equal(got[5], ref[5])),
                "max_abs_ap_new_minus_old": float((got[4] - ref[4]).abs().max())}
         res[f"update_from_heat.B{B}.224x224"] = row
@@ -148,23 +119,20 @@ def bench_metrics(batches, rounds, min_s, warmup):
     return res
 
 
-def bench_evaluator(rounds, min_s, warmup, B=64):
-    from oracle.ref_harness import synthetic_init
-    from transformer_explainability_amd import segmentation as sg, vit
+def bench_evaluator(rounds, window, warmup, B=64):
+    from transformer_explainability_amd import segmentation as sg
     from transformer_explainability_amd.generators import LRP
     from transformer_explainability_amd.sweep import normalize
-    m = vit.vit_base_patch16_224().eval()
-    synthetic_init(m, 0)
-    lrp = LRP(m.to("cuda:0"))
+    lrp = LRP(vit_b16())
     g = torch.Generator().manual_seed(B)
     x = normalize(torch.rand((B, 3, 224, 224), generator=g).to("cuda:0"))
     labels = (torch.rand((B, 224, 224), generator=g) > 0.7).long().to("cuda:0")
     explain = lambda im: lrp.generate_LRP(im, start_layer=1)      # noqa: E731
     ev_new, ev_old = sg.SegmentationEvaluator(explain), sg.SegmentationEvaluator(explain)
-    t = _alternate({"new": lambda: ev_new.update(x, labels), "old": lambda: old_update(ev_old, x, labels),
-                    "explain_only": lambda: explain(x)}, rounds, min_s, warmup)
+    t = alternate({"new": lambda: ev_new.update(x, labels), "old": lambda: old_update(ev_old, x, labels),
+                   "explain_only": lambda: explain(x)}, rounds, window, warmup)
     lrp.check()
-    row = {k: {"images_per_s": round(B / statistics.median(v), 1), **_summary(v, 1e3, "ms")} for k, v in t.items()}
+    row = {k: {"images_per_s": round(B / statistics.median(v), 1), **summary(v, 1e3, "ms")} for k, v in t.items()}
     row.update(_verdict(t))
     row["summary_new"], row["summary_old"] = ev_new.summary(), ev_old.summary()
     return {f"update.vit_base_patch16_224.batch{B}": row}
@@ -186,12 +154,13 @@ def main():
     res = {"bench": "seg_eval", "rounds": a.rounds, "window_ms": a.window_ms, "warmup": a.warmup,
            "device": torch.cuda.get_device_name(0)}
     batches = [int(b) for b in a.batches.split(",")]
+    window = partial(wall_window, min_s=a.window_ms / 1e3)
     if a.only:
-        res["metrics"] = bench_one_version(batches, a.rounds, a.window_ms / 1e3, a.warmup, a.only)
+        res["metrics"] = bench_one_version(batches, a.rounds, window, a.warmup, a.only)
     else:
-        res["metrics"] = bench_metrics(batches, a.rounds, a.window_ms / 1e3, a.warmup)
+        res["metrics"] = bench_metrics(batches, a.rounds, window, a.warmup)
     if not a.skip_model and not a.only:
-        res["evaluator"] = bench_evaluator(a.rounds, a.window_ms / 1e3, a.warmup)
+        res["evaluator"] = bench_evaluator(a.rounds, window, a.warmup)
     res["build_id"] = te._lib.build_id()
     line = json.dumps(res)
     if a.out:

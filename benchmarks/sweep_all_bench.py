@@ -28,37 +28,19 @@ import json
 import os
 import statistics
 import sys
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchmarks._models import bert_base, vit_b16  # noqa: E402
+from benchmarks._timing import alternate, event_window, summary  # noqa: E402  (the event-window protocol)
+
 VIT_METHODS = ("rollout", "lrp", "transformer_attribution", "attn_last_layer", "attn_gradcam")
 BERT_METHODS = ("LRP", "LRP_last_layer", "full_lrp", "attn_last_layer", "rollout", "attn_gradcam")
-
-
-def _window(fn, inner):
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(inner):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / 1e3 / inner
-
-
-def _alternate(fns, rounds, inner, warmup):
-    """{name: [seconds per call of each of `rounds` windows]}, the versions taking turns."""
-    for fn in fns.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in fns}
-    for _ in range(rounds):
-        for name, fn in fns.items():
-            times[name].append(_window(fn, inner))
-    return times
+_ms = partial(summary, scale=1e3, unit="ms", digits=3)
 
 
 def _tails_in_context(pass_fn, tail_fns, rounds, warmup):
@@ -81,11 +63,6 @@ def _tails_in_context(pass_fn, tail_fns, rounds, warmup):
             torch.cuda.synchronize()
             times[name].append(t0.elapsed_time(t1) / 1e3)
     return times
-
-
-def _ms(ts):
-    return {"median_ms": round(statistics.median(ts) * 1e3, 3), "min_ms": round(min(ts) * 1e3, 3),
-            "max_ms": round(max(ts) * 1e3, 3), "windows": len(ts)}
 
 
 def _same(a, b):
@@ -114,13 +91,10 @@ def _report(single, tails, one_pass, equal, steps, warmup, rounds):
 
 
 def bench_vit(dtype, B, steps, warmup, rounds):
-    from oracle.ref_harness import synthetic_init
     from transformer_explainability_amd import generators as G
     from transformer_explainability_amd import sweep as S
     from transformer_explainability_amd import vit
-    model = vit.vit_base_patch16_224().eval()
-    synthetic_init(model, 0)
-    model.to("cuda:0").to(dtype)
+    model = vit_b16(dtype)
     lrp, base = G.LRP(model), G.Baselines(model)
     x = S.normalize(torch.rand((B, 3, 224, 224), generator=torch.Generator().manual_seed(B)).to("cuda:0"))
     singles = {m: S.SaliencySweep(m, lrp=lrp, baselines=base) for m in VIT_METHODS}
@@ -132,7 +106,7 @@ def bench_vit(dtype, B, steps, warmup, rounds):
     del want, got
     fns = {m: (lambda s=s: s.explain(x)) for m, s in singles.items()}
     fns["one_pass"] = lambda: sweep_all.explain(x)
-    t = _alternate(fns, rounds, steps, warmup)
+    t = alternate(fns, rounds, partial(event_window, n=steps), warmup)
     # the tails alone, each behind a pass that has just populated the caches it reads (a tail changes none of them)
     H = x.shape[-1]
     tail_fns = {
@@ -150,12 +124,8 @@ def bench_vit(dtype, B, steps, warmup, rounds):
 
 
 def bench_bert(B, N, steps, warmup, rounds):
-    from oracle.ref_harness import synthetic_init
-    from transformer_explainability_amd import bert
     from transformer_explainability_amd import generators as G
-    model = bert.BertForSequenceClassification(bert.BertConfigLite(num_labels=2)).eval()
-    synthetic_init(model, 0)
-    model.to("cuda:0")
+    model = bert_base()
     g = torch.Generator().manual_seed(N)
     ids = torch.randint(1000, 30000, (B, N), generator=g).to("cuda:0")
     mask = torch.ones((B, N), device="cuda:0")
@@ -169,7 +139,7 @@ def bench_bert(B, N, steps, warmup, rounds):
     equal = {m: _same(got[m], want[m]) for m in BERT_METHODS}
     del want, got
     fns["one_pass"] = lambda: gen.generate_all(ids, mask, BERT_METHODS)
-    t = _alternate(fns, rounds, steps, warmup)
+    t = alternate(fns, rounds, partial(event_window, n=steps), warmup)
     held = {}
 
     def whole_pass():                                # every cache populated + the relevance of the encoder input

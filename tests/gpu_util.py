@@ -1,7 +1,18 @@
-"""Helpers shared by the `-m gpu` parity tests (HIP path through the C ABI vs the CPU oracle)."""
+"""Helpers shared by the `-m gpu` parity tests (HIP path through the C ABI vs the CPU oracle).
+
+Belongs here: what several -m gpu files use alike and what needs the device or the oracle -- the device, seeded inputs, the
+comparisons that write the parity report (check*, map_stats), moving and upcasting caches (move_relprop_state, cache64), fp64
+copies and their rms distance (d, rms), misaligned device views (odd_offset_view) and the seeded bf16 models that several
+files build with the same weights (the vit_b16_bf16 and bert_base_bf16 fixtures, module-scoped: one model per test file).
+
+Does not belong here: tolerances, shapes and expected values (they stay in the test files), helpers that need no device
+(host_util.py: lib, status, header_args, free_port, bits, same_bits, one_hot) and fixtures that build other weights under a
+shared name (the tiny_vit of test_sanity_host, test_host_logic and test_gpu_f64 are three different models).
+"""
 import json
 import os
 
+import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,6 +26,57 @@ def dev():
 def rnd(shape, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(shape, generator=g, dtype=torch.float32) * scale
+
+
+def d(t):
+    return t.detach().double().cpu()
+
+
+def rms(a, b):
+    return float(((d(a) - d(b)) ** 2).mean().sqrt())
+
+
+def cache64(cache, keys=None):
+    """The cache (or its entries `keys`) with every tensor upcast to fp64, exactly"""
+    def conv(v):
+        if torch.is_tensor(v):
+            return v.double()
+        if isinstance(v, list):
+            return [conv(x) for x in v]
+        if isinstance(v, dict):
+            return {k: conv(x) for k, x in v.items()}
+        return v
+    return conv(cache if keys is None else {k: cache[k] for k in keys})
+
+
+def odd_offset_view(t, dtype=None):
+    """t's values (or an uninitialised tensor of t's shape in ``dtype``) in a dense device view that starts one element past a
+    16-byte boundary"""
+    dtype = t.dtype if dtype is None else dtype
+    store = torch.empty(t.numel() + 1, dtype=dtype, device=dev())
+    view = store[1:].view(t.shape)
+    if dtype == t.dtype:
+        view.copy_(t)
+    assert view.data_ptr() % 16 == view.element_size() and view.is_contiguous()
+    return view
+
+
+@pytest.fixture(scope="module")
+def vit_b16_bf16():
+    from oracle.ref_harness import synthetic_init
+    from transformer_explainability_amd import vit
+    model = vit.vit_base_patch16_224().eval()
+    synthetic_init(model, 0)
+    return model.to(dev()).to(torch.bfloat16)
+
+
+@pytest.fixture(scope="module")
+def bert_base_bf16():
+    from oracle.ref_harness import synthetic_init
+    from transformer_explainability_amd import bert
+    model = bert.BertForSequenceClassification(bert.BertConfigLite(num_labels=2)).eval()
+    synthetic_init(model, 0)
+    return model.to(dev()).to(torch.bfloat16)
 
 
 def stats(got, ref):

@@ -13,12 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["te_add_bcast_relprop_bf16", "te_add_bcast_relprop_deferred_bf16"]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
+from host_util import lib  # noqa: E402,F401
 
 
 def _small_bert(dtype=BF, rules=None, seed=0):

@@ -2,32 +2,15 @@
 exported and bound, their argument checks answer before any device call, the Python wrappers refuse what has no kernel
 with a TeError, and the sweep refuses the lrp rule library on a bf16 model before anything reaches the store."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
+from host_util import header_args, lib  # noqa: F401
+
 BF = torch.bfloat16
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["te_perturb_bf16", "te_attn_headmean_bf16"]
 CFG = dict(img_size=32, patch_size=8, embed_dim=64, depth=3, num_heads=4, num_classes=10, qkv_bias=True)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
-
-
-def _header_args(name):
-    """Number of arguments the header declares for ``name``."""
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "te_relprop.h")).read(), flags=re.S)
-    m = re.search(r"\b" + name + r"\s*\(([^)]*)\)", header)
-    assert m, name
-    return len([a for a in m.group(1).split(",") if a.strip()])
 
 
 def test_entry_points_declared_exported_bound(lib):
@@ -35,10 +18,10 @@ def test_entry_points_declared_exported_bound(lib):
     for name in NEW_SYMBOLS:
         assert name in _lib.SIGNATURES, name
         assert hasattr(lib, name), name
-        assert len(_lib.SIGNATURES[name][1]) == _header_args(name), name
+        assert len(_lib.SIGNATURES[name][1]) == header_args(name), name
     # the bf16-output form takes te_perturb_f32's arguments
     assert _lib.SIGNATURES["te_perturb_bf16"] == _lib.SIGNATURES["te_perturb_f32"]
-    assert _header_args("te_perturb_bf16") == _header_args("te_perturb_f32")
+    assert header_args("te_perturb_bf16") == header_args("te_perturb_f32")
 
 
 def test_perturb_bf16_validates_on_the_host(lib):

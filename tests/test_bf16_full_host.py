@@ -13,12 +13,7 @@ SYMBOLS = ["te_conv2d_zb_relprop_bf16_supported", "te_conv2d_zb_relprop_bf16_wor
            "te_conv2d_zb_bf16_weight_planes_bytes", "te_conv2d_zb_bf16_prepare_weights", "te_conv2d_zb_relprop_bf16"]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
+from host_util import lib  # noqa: E402,F401
 
 
 def _up(n, a=256):

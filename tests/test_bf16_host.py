@@ -11,12 +11,7 @@ BF16_SYMBOLS = ["te_linear_relprop_bf16", "te_linear_relprop_bf16_supported", "t
                 "te_clone_relprop_scaled_bf16", "te_index_select_relprop_bf16", "te_gradcam_headmean_bf16"]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
+from host_util import lib  # noqa: E402,F401
 
 
 def test_bf16_entry_points_bound(lib):

@@ -14,12 +14,7 @@ NEW_SYMBOLS = ["te_attention_bf16_supported", "te_attention_forward_strided_bf16
                "te_attention_backward_strided_bf16_workspace_bytes"]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
+from host_util import lib  # noqa: E402,F401
 
 
 def test_entry_points_declared_bound_and_exported(lib):

@@ -8,16 +8,9 @@ import pytest
 import torch
 
 from curves_inputs import MEAN, STD, Stub, images, relevance, tie_example
+from host_util import lib, status  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
 
 
 def curves():
@@ -112,11 +105,6 @@ def test_reference_blur_of_an_impulse_is_the_kernel():
 
 # ------------------------------------------------------------------------------------------------ refusals on the host
 P = 4096      # a fake non-null, 16-byte-aligned address: every call below returns before the first HIP call
-
-
-def status(lib, fn, base, **changed):
-    assert set(changed) <= set(base), changed
-    return getattr(lib, fn)(*{**base, **changed}.values())
 
 
 def test_entry_points_reject_on_the_host(lib):

@@ -4,15 +4,8 @@ import pytest
 import torch
 
 from f64_util import F64, rnd64
+from host_util import lib  # noqa: F401
 from oracle import relprop_oracle as O
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
 
 
 def _lin(dt_r=F64, dt_x=F64, dt_w=F64):

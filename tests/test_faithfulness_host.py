@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from faithfulness_inputs import BALANCE_CASES, BALANCE_IDS, BALANCE_SEEDS, LinearScore, images, inputs, token_maps
+from host_util import lib, same_bits, status  # noqa: F401
 
 U = 2.0 ** -53
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,15 +18,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def fb():
     from transformer_explainability_amd import faithfulness
     return faithfulness
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
 # ------------------------------------------------------------------------------------------------ subsets
@@ -310,19 +302,6 @@ def test_evaluator_refuses_token_ids_and_bad_arguments():
 
 # ------------------------------------------------------------------------------------------------ the entry points, no device
 ENTRIES = ("te_subset_inputs_f32", "te_subset_inputs_bf16", "te_perturbation_dot_f32", "te_perturbation_dot_bf16")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
-
-
-def status(lib, fn, base, **changed):
-    assert set(changed) <= set(base), changed
-    return getattr(lib, fn)(*{**base, **changed}.values())
 
 
 def test_entry_points_are_declared_exported_and_bound(lib):

@@ -5,7 +5,9 @@ kernels on the same upcast operands, for determinism, and for not disturbing fp3
 import pytest
 import torch
 
-from gpu_util import dev, map_stats, record, vit_cache_from_model
+from gpu_util import (cache64, d as _d, dev, map_stats, record, rms as _rms, vit_b16_bf16,  # noqa: F401
+                      vit_cache_from_model)
+from host_util import one_hot
 from oracle import relprop_oracle as O
 from oracle.model_cache import sliced_relprop_state
 from oracle.ref_harness import seeded_randn, synthetic_init
@@ -13,32 +15,6 @@ from oracle.ref_harness import seeded_randn, synthetic_init
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
-
-
-def _d(t):
-    return t.detach().double().cpu()
-
-
-def _cache64(cache):
-    def conv(v):
-        if torch.is_tensor(v):
-            return v.double()
-        if isinstance(v, list):
-            return [conv(x) for x in v]
-        if isinstance(v, dict):
-            return {k: conv(x) for k, x in v.items()}
-        return v
-    return conv(cache)
-
-
-def _rms(a, b):
-    return float(((_d(a) - _d(b)) ** 2).mean().sqrt())
-
-
-def _one_hot(logits):
-    oh = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
-    oh.scatter_(1, logits.float().argmax(-1, keepdim=True), 1.0)
-    return oh
 
 
 def _vit(factory, seed=0, **kw):
@@ -49,14 +25,9 @@ def _vit(factory, seed=0, **kw):
 
 
 # ------------------------------------------------------------------------------------------------ end to end
-@pytest.fixture(scope="module")
-def vit_b16_bf16():
-    return _vit("vit_base_patch16_224")
-
-
 def _oracle_maps(model, oh, i, B, num_heads, start_layers):
     with sliced_relprop_state(model, i, B):
-        cache = _cache64(vit_cache_from_model(model))
+        cache = cache64(vit_cache_from_model(model))
     res = O.vit_relprop(oh[i:i + 1].double().cpu(), cache, num_heads=num_heads, start_layer=0)
     grads = [b["attn_grad"] for b in cache["blocks"]]
     return {sl: O.vit_attribution_tail(grads, res["attn_cams"], sl) for sl in start_layers}
@@ -71,7 +42,7 @@ def test_bf16_vit_b16_batch8_vs_oracle(vit_b16_bf16):
     lrp = LRP(model)
     maps0 = lrp.generate_LRP(x, method="transformer_attribution", start_layer=0)
     assert maps0.dtype == torch.float32 and maps0.shape == (B, 196) and torch.isfinite(maps0).all()
-    oh = _one_hot(model.head.Y)
+    oh = one_hot(model.head.Y)
     maps1 = model.relprop(oh, method="transformer_attribution", start_layer=1, alpha=1)
     worst = {0: 0.0, 1: 0.0}
     for i in range(B):
@@ -94,7 +65,7 @@ def test_bf16_determinism_and_batch_equals_samples(vit_b16_bf16):
     a = lrp.generate_LRP(x, start_layer=1).clone()
     b = lrp.generate_LRP(x, start_layer=1).clone()
     assert torch.equal(a, b)
-    oh = _one_hot(model.head.Y)
+    oh = one_hot(model.head.Y)
     for i in range(B):
         with sliced_relprop_state(model, i, B):
             one = model.relprop(oh[i:i + 1], method="transformer_attribution", start_layer=1, alpha=1)
@@ -133,7 +104,7 @@ def test_bf16_vit_l16_384_vs_oracle():
     x = seeded_randn((B, 3, 384, 384), 11).to(dev()).to(BF)
     maps = LRP(model).generate_LRP(x, start_layer=1)
     assert maps.shape == (B, 576) and maps.dtype == torch.float32
-    oh = _one_hot(model.head.Y)
+    oh = one_hot(model.head.Y)
     ref = _oracle_maps(model, oh, 1, B, 16, (1,))[1]
     s = map_stats(maps[1:2], ref)
     record("bf16.vit_l16_384.map_sl1.1", **s)
@@ -154,7 +125,7 @@ def test_bf16_vit_tiny_fallback_route(golden_vit_tiny):
     assert ops.linear_bf16_route(34, 64, 192) == "fp32-upcast" and ops.attention_bf16_route(17, 16) == "fp32-upcast"
     x = g["x"].to(dev()).to(BF)
     maps = LRP(model).generate_LRP(x, start_layer=0)
-    oh = _one_hot(model.head.Y)
+    oh = one_hot(model.head.Y)
     for i in range(2):
         ref = _oracle_maps(model, oh, i, 2, 4, (0,))[0]
         s = map_stats(maps[i:i + 1], ref)

@@ -7,31 +7,14 @@ only when sqrt(D) is a power of two, hence head dims 16 and 64 below."""
 import pytest
 import torch
 
-from gpu_util import bert_cache_from_model, dev, map_stats, record, sliced_relprop_state, stats
+from gpu_util import (bert_base_bf16, bert_cache_from_model, cache64, dev, map_stats, record,  # noqa: F401
+                      sliced_relprop_state, stats)
+from host_util import one_hot
 from oracle import relprop_oracle as O
-from oracle.ref_harness import synthetic_init
 
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
-
-
-def _cache64(cache):
-    def conv(v):
-        if torch.is_tensor(v):
-            return v.double()
-        if isinstance(v, list):
-            return [conv(x) for x in v]
-        if isinstance(v, dict):
-            return {k: conv(x) for k, x in v.items()}
-        return v
-    return conv(cache)
-
-
-def _one_hot(logits):
-    oh = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
-    oh.scatter_(1, logits.float().argmax(-1, keepdim=True), 1.0)
-    return oh
 
 
 def _bits_equal(name, got, ref):
@@ -121,14 +104,6 @@ def test_bcast_mask_add_bf16_vs_fp64():
 
 
 # ------------------------------------------------------------------------------------------------ BERT-base, N = 512
-@pytest.fixture(scope="module")
-def bert_base_bf16():
-    from transformer_explainability_amd import bert
-    model = bert.BertForSequenceClassification(bert.BertConfigLite(num_labels=2)).eval()
-    synthetic_init(model, 0)
-    return model.to(dev()).to(BF)
-
-
 def _ids_mask(B, N, pad=64, seed=1):
     g = torch.Generator().manual_seed(seed)
     ids = torch.randint(1000, 20000, (B, N), generator=g)
@@ -148,7 +123,7 @@ def test_bf16_bert_base_512_vs_oracle(bert_base_bf16):
     assert torch.equal(gen.generate_LRP(ids, mask, start_layer=0), out)
     sa = model.bert.encoder.layer[0].attention.self
     assert sa.add.X[0].dtype == BF and sa.add.X[1].dtype == BF
-    oh = _one_hot(model.classifier.Y)
+    oh = one_hot(model.classifier.Y)
     cam = model.relprop(oh, alpha=1)
     assert cam.dtype == torch.float32
     sums = cam.double().sum(dim=(1, 2)).cpu()
@@ -156,7 +131,7 @@ def test_bf16_bert_base_512_vs_oracle(bert_base_bf16):
     assert (sums - 1.0).abs().max() < 2e-3, sums
     for i in (0, 1):                               # padded, unpadded
         with sliced_relprop_state(model, i, B):
-            cache = _cache64(bert_cache_from_model(model))
+            cache = cache64(bert_cache_from_model(model))
             model.relprop(oh[i:i + 1], alpha=1)
             one = gen.attribution_tail(start_layer=0)
             assert torch.equal(one, out[i:i + 1]), float((one - out[i:i + 1]).abs().max())
@@ -215,7 +190,7 @@ def test_bf16_bert_graphed_call_replays_eager(bert_base_bf16):
 def _oracle_check(name, model, out, oh, B, num_heads, start_layer=0):
     for i in range(B):
         with sliced_relprop_state(model, i, B):
-            cache = _cache64(bert_cache_from_model(model))
+            cache = cache64(bert_cache_from_model(model))
         ref = O.bert_relprop(oh[i:i + 1].double().cpu(), cache, num_heads=num_heads, start_layer=start_layer)
         s = map_stats(out[i:i + 1], ref["map"])
         record(f"{name}.{i}", **s)
@@ -237,7 +212,7 @@ def test_bf16_bert_tiny_fp32_upcast_routes_vs_oracle(golden_bert_tiny):
     for sl in (0, 2):
         out = Generator(model).generate_LRP(ids, mask, start_layer=sl)
         assert out.dtype == torch.float32 and out.shape == (2, 24)
-        _oracle_check(f"bf16.bert_tiny.map_sl{sl}", model, out, _one_hot(model.classifier.Y), 2, 4, sl)
+        _oracle_check(f"bf16.bert_tiny.map_sl{sl}", model, out, one_hot(model.classifier.Y), 2, 4, sl)
 
 
 def _soft_mask_model(dtype):
@@ -270,7 +245,7 @@ def test_bf16_bert_soft_mask_vs_oracle():
     out = Generator(model).generate_LRP(ids, mask, start_layer=0)
     ext = model.bert.encoder.layer[0].attention.self.add.X[1]
     assert ext.dtype == BF and float(ext[0, 0, 0, 5]) == -39.0 and float(ext[1, 0, 0, 21]) == -9984.0
-    _oracle_check("bf16.bert_soft_mask.map_sl0", model, out, _one_hot(model.classifier.Y), 3, 2)
+    _oracle_check("bf16.bert_soft_mask.map_sl0", model, out, one_hot(model.classifier.Y), 3, 2)
 
 
 def test_bf16_bert_other_methods_fp16_refusal_and_fp32_untouched():

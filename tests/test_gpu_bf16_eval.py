@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_util import check, check_nan_aware, dev, map_stats, record, vit_cache_from_model
+from gpu_util import cache64, check, check_nan_aware, d as _d, dev, map_stats, record, vit_cache_from_model
+from host_util import bits, one_hot
 from oracle import relprop_oracle as O
 from oracle.model_cache import sliced_relprop_state
 from oracle.ref_harness import seeded_randn, synthetic_init
@@ -16,32 +17,6 @@ BF = torch.bfloat16
 TINY = dict(img_size=32, patch_size=8, embed_dim=64, depth=3, num_heads=4, num_classes=10, qkv_bias=True)
 PERT_CFG = dict(img_size=224, patch_size=16, embed_dim=64, depth=2, num_heads=4, num_classes=10, qkv_bias=True,
                 block_norm_eps=1e-5, final_norm_eps=1e-5)        # the classifier of tests/test_perturbation.py
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int16 if t.dtype == BF else torch.int32)
-
-
-def _d(t):
-    return t.detach().double().cpu()
-
-
-def _cache64(cache):
-    def conv(v):
-        if torch.is_tensor(v):
-            return v.double()
-        if isinstance(v, list):
-            return [conv(x) for x in v]
-        if isinstance(v, dict):
-            return {k: conv(x) for k, x in v.items()}
-        return v
-    return conv(cache)
-
-
-def _one_hot(logits):
-    oh = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
-    oh.scatter_(1, logits.float().argmax(-1, keepdim=True), 1.0)
-    return oh
 
 
 def _tiny_vit(golden, dtype=BF):
@@ -108,8 +83,8 @@ def test_perturb_bf16_bit_for_bit(shape, ties):
     assert got.dtype == BF and got.shape == (len(ks), B, C, H, W)
     ref = O.perturb(vis, data, ks, mean, std).to(BF)
     f32 = ops.perturb(vis.to(d), data.to(d), ks, mean, std).to(BF)
-    eq_ref = bool(torch.equal(got.cpu(), ref)) and bool(torch.equal(_bits(got).cpu(), _bits(ref)))
-    eq_f32 = bool(torch.equal(got, f32)) and bool(torch.equal(_bits(got), _bits(f32)))
+    eq_ref = bool(torch.equal(got.cpu(), ref)) and bool(torch.equal(bits(got).cpu(), bits(ref)))
+    eq_f32 = bool(torch.equal(got, f32)) and bool(torch.equal(bits(got), bits(f32)))
     record(f"bf16.perturb.{'x'.join(map(str, shape))}.{ties}", equals_oracle_cast=eq_ref, equals_f32_kernel_cast=eq_f32,
            max_abs_vs_oracle=float((got.cpu().float() - ref.float()).abs().max()))
     assert eq_ref and eq_f32
@@ -126,7 +101,7 @@ def test_perturb_f32_untouched_by_bf16_calls():
     ops.perturb(vis.to(d), data.to(d), ks, mean, std, out_dtype=BF)
     ops.perturb(vis[:1, :63].to(d), data[:1, :, :7, :9].contiguous().to(d), [3, 9], mean, std, out_dtype=BF)
     after = ops.perturb(vis.to(d), data.to(d), ks, mean, std)
-    eq = bool(torch.equal(_bits(before), _bits(after)))
+    eq = bool(torch.equal(bits(before), bits(after)))
     record("bf16.perturb.f32_untouched", bitwise_equal=eq)
     assert eq and after.dtype == torch.float32
     assert torch.equal(after.cpu(), O.perturb(vis, data, ks, mean, std))
@@ -175,23 +150,23 @@ def test_attn_headmean_bf16(B, H, N):
         assert full.shape == (B, N, N)
         _headmean_bound_check(f"{tag}.{name}", full, probs, clamp=False)
         base = full if base is None else base
-        assert torch.equal(_bits(full), _bits(base)), name             # the strides do not change a bit
+        assert torch.equal(bits(full), bits(base)), name             # the strides do not change a bit
         row = ops.attn_headmean(a, row0=True)
-        assert row.shape == (B, N) and torch.equal(_bits(row), _bits(full[:, 0])), name
+        assert row.shape == (B, N) and torch.equal(bits(row), bits(full[:, 0])), name
     for name, a in _views(signed).items():
         full = ops.attn_headmean(a, clamp=True)
         _headmean_bound_check(f"{tag}.clamp.{name}", full, signed, clamp=True)
         assert float(full.min()) >= 0.0
         row = ops.attn_headmean(a, clamp=True, row0=True)
-        assert torch.equal(_bits(row), _bits(full[:, 0])), name
+        assert torch.equal(bits(row), bits(full[:, 0])), name
     # a batch equals its samples, bit for bit; a slice of a rollout stack as destination
     stack = torch.full((2, B, N, N), float("nan"), device=dev())
     ops.attn_headmean(probs, out=stack[1])
-    assert torch.equal(_bits(stack[1]), _bits(base)) and torch.isnan(stack[0]).all()
+    assert torch.equal(bits(stack[1]), bits(base)) and torch.isnan(stack[0]).all()
     same = True
     for b in range(B):
-        same &= bool(torch.equal(_bits(ops.attn_headmean(probs[b:b + 1])), _bits(base[b:b + 1])))
-        same &= bool(torch.equal(_bits(ops.attn_headmean(probs[b:b + 1], row0=True)), _bits(base[b:b + 1, 0])))
+        same &= bool(torch.equal(bits(ops.attn_headmean(probs[b:b + 1])), bits(base[b:b + 1])))
+        same &= bool(torch.equal(bits(ops.attn_headmean(probs[b:b + 1], row0=True)), bits(base[b:b + 1, 0])))
     record(f"{tag}.batch_equals_samples", bitwise_equal=same)
     assert same
 
@@ -370,7 +345,7 @@ def test_sweep_on_a_bf16_model(method, tmp_path):
                     assert bool(torch.isnan(vis).all()), (method, pos)
                 else:
                     assert float(vis.min()) == 0.0 and float(vis.max()) == 1.0, (method, pos)
-                same &= bool(torch.equal(_bits(vis), _bits(again[j].cpu())))
+                same &= bool(torch.equal(bits(vis), bits(again[j].cpu())))
                 pos += 1
     record(f"bf16.sweep.{method}", stored_equals_rerun_bitwise=same, images=pos, reference_0_over_0_maps=nan_maps)
     assert pos == 7 and same and len(nan_maps) <= 2
@@ -378,7 +353,7 @@ def test_sweep_on_a_bf16_model(method, tmp_path):
 
 def _oracle_map(model, oh, i, B, num_heads, start_layer):
     with sliced_relprop_state(model, i, B):
-        cache = _cache64(vit_cache_from_model(model))
+        cache = cache64(vit_cache_from_model(model))
     res = O.vit_relprop(oh[i:i + 1].double().cpu(), cache, num_heads=num_heads, start_layer=0)
     grads = [b["attn_grad"] for b in cache["blocks"]]
     return O.vit_attribution_tail(grads, res["attn_cams"], start_layer)
@@ -399,7 +374,7 @@ def test_sweep_vit_b16_batch8_vs_oracle():
     assert heat.dtype == torch.float32 and heat.shape == (B, 1, 224, 224)
     assert maps.dtype == torch.float32 and maps.shape == (B, 196) and torch.isfinite(maps).all()
     assert model.patch_embed.proj.weight.dtype == BF
-    oh = _one_hot(model.head.Y)
+    oh = one_hot(model.head.Y)
     worst = 0.0
     for i in range(B):
         s = map_stats(maps[i:i + 1], _oracle_map(model, oh, i, B, 12, 1))

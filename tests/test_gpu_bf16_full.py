@@ -10,7 +10,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import dev, map_stats, record, vit_cache_from_model
+from gpu_util import (cache64, d as _d, dev, map_stats, record, rms as _rms, vit_b16_bf16,  # noqa: F401
+                      vit_cache_from_model)
+from host_util import one_hot
 from oracle import relprop_oracle as O
 from oracle.model_cache import sliced_relprop_state
 from oracle.ref_harness import seeded_randn, synthetic_init
@@ -19,14 +21,6 @@ pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
 T147 = (3, 112, 112, 16, 256)          # T = 147: two row tiles, tiles holding rows of three samples, two column tiles
-
-
-def _d(t):
-    return t.detach().double().cpu()
-
-
-def _rms(a, b):
-    return float(((_d(a) - _d(b)) ** 2).mean().sqrt())
 
 
 def _inputs(B, H, W, p, E, seed=0):
@@ -196,33 +190,7 @@ def test_bf16_conv_zb_upcast_route(B, H, W, p, E):
 
 
 # ------------------------------------------------------------------------------------------------ model
-def _one_hot(logits):
-    oh = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
-    oh.scatter_(1, logits.float().argmax(-1, keepdim=True), 1.0)
-    return oh
-
-
-def _cache64(cache, keys=None):
-    def conv(v):
-        if torch.is_tensor(v):
-            return v.double()
-        if isinstance(v, list):
-            return [conv(x) for x in v]
-        if isinstance(v, dict):
-            return {k: conv(x) for k, x in v.items()}
-        return v
-    return conv(cache if keys is None else {k: cache[k] for k in keys})
-
-
 TAIL_KEYS = ("pos_add_x0", "pos_embed", "patch_x", "patch_w")
-
-
-@pytest.fixture(scope="module")
-def vit_b16_bf16():
-    from transformer_explainability_amd import vit
-    model = vit.vit_base_patch16_224().eval()
-    synthetic_init(model, 0)
-    return model.to(dev()).to(BF)
 
 
 def test_bf16_full_tail_vs_oracle(vit_b16_bf16):
@@ -236,7 +204,7 @@ def test_bf16_full_tail_vs_oracle(vit_b16_bf16):
     c, _ = model.add.relprop(cam.to(dev()), alpha=1)
     got = model.patch_embed.relprop(c[:, 1:], alpha=1).sum(dim=1)
     assert got.dtype == torch.float32 and got.shape == (3, 224, 224) and torch.isfinite(got).all()
-    cache = _cache64(vit_cache_from_model(model), TAIL_KEYS)
+    cache = cache64(vit_cache_from_model(model), TAIL_KEYS)
     ref = O.vit_full_tail(cam.double(), cache)
     s = map_stats(got, ref)
     record("bf16.vit_b16.full_tail", **s)
@@ -251,7 +219,7 @@ def test_bf16_full_whole_call(vit_b16_bf16):
     x = seeded_randn((B, 3, 224, 224), 13).to(dev()).to(BF)
     full = LRP(model).generate_LRP(x, method="full").clone()
     assert full.dtype == torch.float32 and full.shape == (B, 224, 224) and torch.isfinite(full).all()
-    oh = _one_hot(model.head.Y)
+    oh = one_hot(model.head.Y)
     for i in range(B):
         with sliced_relprop_state(model, i, B):
             one = model.relprop(oh[i:i + 1], method="full", alpha=1)
@@ -259,7 +227,7 @@ def test_bf16_full_whole_call(vit_b16_bf16):
     # distance to the fp64 oracle over the whole chain, one sample: recorded, not asserted (the chain above the tail is
     # existing code with its own tests)
     with sliced_relprop_state(model, 0, B):
-        cache = _cache64(vit_cache_from_model(model))
+        cache = cache64(vit_cache_from_model(model))
     res = O.vit_relprop(oh[:1].double().cpu(), cache, num_heads=12)
     s = map_stats(full[:1], O.vit_full_tail(res["cam"], cache))
     record("bf16.vit_b16.full.whole_chain.0", **s)

@@ -9,7 +9,8 @@ roundings, so a faithful kernel sits near 1.0 and has the factor as headroom.  E
 import pytest
 import torch
 
-from gpu_util import dev, record, rnd
+from gpu_util import bert_base_bf16, cache64, dev, record, rnd, vit_b16_bf16  # noqa: F401
+from host_util import one_hot
 
 pytestmark = pytest.mark.gpu
 
@@ -180,24 +181,6 @@ def test_bf16_producers_refuse_other_shapes_and_dtypes():
 BF = torch.bfloat16
 
 
-def _cache64(cache):
-    def conv(v):
-        if torch.is_tensor(v):
-            return v.double()
-        if isinstance(v, list):
-            return [conv(x) for x in v]
-        if isinstance(v, dict):
-            return {k: conv(x) for k, x in v.items()}
-        return v
-    return conv(cache)
-
-
-def _one_hot(logits):
-    oh = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
-    oh.scatter_(1, logits.float().argmax(-1, keepdim=True), 1.0)
-    return oh
-
-
 class _fused:
     """ops.USE_FUSED_PRODUCERS = True inside, restored on the way out."""
 
@@ -217,15 +200,6 @@ def vit_b16():
     model = vit.vit_base_patch16_224().eval()
     synthetic_init(model, 0)
     return model.to(dev())
-
-
-@pytest.fixture(scope="module")
-def vit_b16_bf16():
-    from oracle.ref_harness import synthetic_init
-    from transformer_explainability_amd import vit
-    model = vit.vit_base_patch16_224().eval()
-    synthetic_init(model, 0)
-    return model.to(dev()).to(BF)
 
 
 def test_bf16_vit_b16_fused_batch8_vs_oracle(vit_b16_bf16):
@@ -250,11 +224,11 @@ def test_bf16_vit_b16_fused_batch8_vs_oracle(vit_b16_bf16):
                 and k.untyped_storage().data_ptr() == qkv.untyped_storage().data_ptr()       # views of the block's qkv
             assert blk.attn.matmul1.Y.dtype == BF and blk.attn.get_attn().dtype == BF \
                 and blk.attn.get_attn_gradients().dtype == BF
-        oh = _one_hot(model.head.Y)
+        oh = one_hot(model.head.Y)
         maps1 = model.relprop(oh, method="transformer_attribution", start_layer=1, alpha=1)
         for i in range(B):
             with sliced_relprop_state(model, i, B):
-                cache = _cache64(vit_cache_from_model(model))
+                cache = cache64(vit_cache_from_model(model))
             res = O.vit_relprop(oh[i:i + 1].double().cpu(), cache, num_heads=12, start_layer=0)
             grads = [b["attn_grad"] for b in cache["blocks"]]
             for sl, got in ((0, maps0), (1, maps1)):
@@ -278,7 +252,7 @@ def test_bf16_vit_b16_fused_bits(vit_b16_bf16):
         assert all(b.attn._fused_anchor is not None for b in model.blocks)
         assert torch.equal(lrp.generate_LRP(x, start_layer=1), plain)
         lrp.generate_LRP(x, start_layer=1)
-        oh = _one_hot(model.head.Y)
+        oh = one_hot(model.head.Y)
         for i in range(B):                   # the rules on sample i of the batch's own cache
             with sliced_relprop_state(model, i, B):
                 one = model.relprop(oh[i:i + 1], method="transformer_attribution", start_layer=1, alpha=1)
@@ -343,15 +317,6 @@ def test_bf16_fused_vs_stock_distance_to_fp32_maps(vit_b16_bf16):
     assert mf <= 2 * ms, (mf, ms)
 
 
-@pytest.fixture(scope="module")
-def bert_base_bf16():
-    from oracle.ref_harness import synthetic_init
-    from transformer_explainability_amd import bert
-    model = bert.BertForSequenceClassification(bert.BertConfigLite(num_labels=2)).eval()
-    synthetic_init(model, 0)
-    return model.to(dev()).to(BF)
-
-
 def _ids_mask(B, N, pad=64, seed=1):
     g = torch.Generator().manual_seed(seed)
     ids = torch.randint(1000, 20000, (B, N), generator=g)
@@ -381,10 +346,10 @@ def test_bf16_bert_base_512_fused_vs_oracle(bert_base_bf16):
             assert torch.equal(sa.add.X[0], sa.matmul1.Y * 0.125)          # the producer's x = z_qk * scale
             pad = (mask == 0)
             assert bool((sa.get_attn().permute(0, 3, 1, 2)[pad] == 0).all())
-        oh = _one_hot(model.classifier.Y)
+        oh = one_hot(model.classifier.Y)
         for i in (0, 1):                               # padded, unpadded
             with sliced_relprop_state(model, i, B):
-                cache = _cache64(bert_cache_from_model(model))
+                cache = cache64(bert_cache_from_model(model))
                 model.relprop(oh[i:i + 1], alpha=1)
                 one = gen.attribution_tail(start_layer=0)
                 assert torch.equal(one, out[i:i + 1]), float((one - out[i:i + 1]).abs().max())

@@ -19,17 +19,13 @@ import pytest
 import torch
 
 import bf16_rule_inputs as I
-from gpu_util import check, dev, record
+from gpu_util import check, d as _d, dev, record, rms as _rms
 from oracle import relprop_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
 NAN = float("nan")
-
-
-def _d(t):
-    return t.detach().double().cpu()
 
 
 def _at(t, off):
@@ -239,10 +235,6 @@ def test_bf16_streaming_rules_refuse_what_they_do_not_implement():
 
 
 # ================================================================================================ Linear
-def _rms(a, b):
-    return float(((_d(a) - _d(b)) ** 2).mean().sqrt())
-
-
 def _linear_bar(tag, got, f32, ref):
     """The bar of test_bf16_linear_rule_vs_fp64: as close to the fp64 oracle as the fp32 kernel on exact copies."""
     e_bf, e_32 = _rms(got, ref), _rms(f32, ref)

@@ -6,7 +6,8 @@ import pytest
 import torch
 
 from curves_inputs import MEAN, STD, Stub, images, logits as make_logits, relevance, special_rows, tie_example, upsampled_map
-from gpu_util import dev
+from gpu_util import dev, odd_offset_view
+from host_util import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -17,24 +18,6 @@ TILE = 32                                  # csrc/te_curves.hip: kTile, the blur
 def te():
     from transformer_explainability_amd import curves, ops
     return ops, curves
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def odd_offset_view(t):
-    """t's values in a dense device view that starts 4 bytes (one fp32 / int32 element) past a 16-byte boundary"""
-    store = torch.empty(t.numel() + 1, dtype=t.dtype, device=dev())
-    view = store[1:].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
-    return view
 
 
 # ------------------------------------------------------------------------------------------------ rank

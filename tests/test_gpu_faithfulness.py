@@ -8,7 +8,8 @@ import pytest
 import torch
 
 from faithfulness_inputs import images, inputs, token_maps
-from gpu_util import dev
+from gpu_util import dev, odd_offset_view
+from host_util import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -20,27 +21,6 @@ DTYPES = pytest.mark.parametrize("out_dtype", [torch.float32, BF], ids=["f32", "
 def te():
     from transformer_explainability_amd import faithfulness, ops
     return ops, faithfulness
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def odd_offset_view(t, dtype=None):
-    """t's values (or an uninitialised tensor of t's shape in ``dtype``) in a dense device view that starts one element past a
-    16-byte boundary"""
-    dtype = t.dtype if dtype is None else dtype
-    store = torch.empty(t.numel() + 1, dtype=dtype, device=dev())
-    view = store[1:].view(t.shape)
-    if dtype == t.dtype:
-        view.copy_(t)
-    assert view.data_ptr() % 16 == view.element_size() and view.is_contiguous()
-    return view
 
 
 # ------------------------------------------------------------------------------------------------ subset inputs

@@ -11,6 +11,7 @@ import torch
 import head_mask_ref as HR
 from f64_util import bert_cache_f64, bits_equal, cpu64, norm_err, vit_cache_f64
 from gpu_util import (bert_cache_from_model, check, dev, map_stats, record, sliced_relprop_state, vit_cache_from_model)
+from host_util import one_hot
 
 pytestmark = pytest.mark.gpu
 
@@ -207,12 +208,6 @@ def _attn(model):
     return [lay.attention.self for lay in model.bert.encoder.layer]
 
 
-def _one_hot(logits, dtype=torch.float32):
-    oh = torch.zeros(logits.shape, dtype=dtype)
-    oh.scatter_(1, logits.detach().float().cpu().argmax(-1, keepdim=True), 1.0)
-    return oh
-
-
 def _assert_map(name, got, ref, norm_tol, rel_tol):
     """tests/test_gpu_models.py::_assert_map: the project's same-cache bars through gpu_util.map_stats."""
     s = map_stats(got, ref)
@@ -268,7 +263,7 @@ def test_bert_tiny_masked_vs_restatement_on_the_same_cache(bert32, which):
         assert torch.equal(sa.mul.X[0], sa.get_attn().detach()) and torch.equal(sa.matmul2.X[0], sa.mul.X[0] * sa.mul.X[1])
     cache = bert_cache_from_model(model)
     pm, ms = HR.masked_operands(sas, cpu32)
-    ref = HR.bert_relprop(_one_hot(model.classifier.Y), cache, H_, pm, ms, start_layer=0)
+    ref = HR.bert_relprop(one_hot(model.classifier.Y, device="cpu"), cache, H_, pm, ms, start_layer=0)
     _assert_map(f"head_mask.bert_tiny.{which}.map_sl0", out, ref["map"], norm_tol=1e-4, rel_tol=3e-4)
     for i, sa in enumerate(sas):
         check(f"head_mask.bert_tiny.{which}.attn_cam.{i}", sa.get_attn_cam(), ref["attn_cams"][i], 3e-4)
@@ -371,7 +366,7 @@ def test_bert_tiny_bf16_masked_vs_restatement_in_double():
     sas = _attn(model)
     assert all(sa.mul.X[0].dtype == BF and sa.mul.X[1].dtype == BF and sa.get_attn_cam().dtype == torch.float32 for sa in sas)
     assert not sas[0].get_attn_cam()[0, 1].any() and not sas[0].get_attn_gradients()[0, 1].any()
-    oh = _one_hot(model.classifier.Y, F64)
+    oh = one_hot(model.classifier.Y, F64, device="cpu")
     for i in range(B_):
         with sliced_relprop_state(model, i, B_):
             cache = bert_cache_f64(model)
@@ -451,7 +446,7 @@ def test_vit_tiny_masked_vs_restatement_on_the_same_cache(vit_tiny):
     assert out.shape == (B, 16) and not torch.equal(out, fresh)
     cache = vit_cache_from_model(model)
     pm, ms = HR.masked_operands(attns, cpu32)
-    ref = HR.vit_relprop(_one_hot(model.head.Y), cache, VH, pm, ms, start_layer=0)
+    ref = HR.vit_relprop(one_hot(model.head.Y, device="cpu"), cache, VH, pm, ms, start_layer=0)
     _assert_map("head_mask.vit_tiny.map_sl0", out, ref["map"], norm_tol=1e-3, rel_tol=2e-3)
     for i, a in enumerate(attns):
         check(f"head_mask.vit_tiny.attn_cam.{i}", a.get_attn_cam(), ref["attn_cams"][i], 2e-3)

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from gpu_util import dev, record
+from host_util import bits, same_bits
 from localisation_inputs import (ENERGY_EPS, HEATS, SIZES, box_case, energy_bound, heat_maps, label_maps, mask_case, rasterise,
                                  special_cases, to)
 
@@ -22,18 +23,10 @@ def loc():
     return localisation
 
 
-def bits(t):
-    return t.contiguous().view(torch.int64) if t.dtype == torch.float64 else t
-
-
 def run(case):
     stats, energy = ops().localisation_metrics(**to(case, dev()))
     torch.cuda.synchronize()
     return stats.cpu(), energy.cpu()
-
-
-def same_bits(a, b):
-    return all(torch.equal(bits(x), bits(y)) for x, y in zip(a, b))
 
 
 def compare(name, got, ref):
@@ -104,7 +97,7 @@ def test_boxes_equal_the_restatement_and_the_rasterised_union(M):
     compare(f"localisation_boxes_M{M}", got, reference(("boxes", M), case))
     P, H, W = case["heat"].shape
     by_mask = run(dict(heat=case["heat"], labels=rasterise(case["boxes"], H, W), target_id=torch.ones(P, dtype=torch.long)))
-    assert same_bits(got, by_mask)
+    assert all(same_bits(x, y) for x, y in zip(got, by_mask))
     if M == 3:
         assert int(got[0][0, 1]) == 7 * 8 + 8 * 7 - 3 * 3 and got[0][2].tolist()[1:] == [0, int(got[0][2, 2]), -1, 0]
 
@@ -126,7 +119,7 @@ def test_shared_label_maps_equal_per_pair_copies():
     case = mask_case(17, 19, "levels", seed=5)
     shared = run(case)
     copies = run(dict(case, labels=case["labels"][case["image_index"]].contiguous(), image_index=None))
-    assert same_bits(shared, copies)
+    assert all(same_bits(x, y) for x, y in zip(shared, copies))
     compare("localisation_shared_maps", shared, reference(("mask", 17, 19, "levels", 5), case))
 
 
@@ -172,7 +165,7 @@ def five_pairs():
 def test_batch_equals_its_single_calls_bit_for_bit():
     case = five_pairs()
     whole = run(case)
-    assert same_bits(whole, run(case))
+    assert all(same_bits(x, y) for x, y in zip(whole, run(case)))
     for p in range(5):
         alone = run({k: v[p:p + 1] if k != "labels" else v for k, v in case.items()})
         assert torch.equal(alone[0], whole[0][p:p + 1]) and torch.equal(bits(alone[1]), bits(whole[1][p:p + 1])), p

@@ -8,15 +8,12 @@ import pytest
 import torch
 
 from gpu_util import dev
+from host_util import bits
 from mapsim_inputs import FAMILIES, family, images
 
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -53
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int64)
 
 
 def ulps(got, want):

@@ -4,11 +4,12 @@ group (nccl IS RCCL on ROCm) and the collective forced (`force_collective=True` 
 (baselines/ViT/generate_visualizations.py:27-100 is the reference's 50k-image path; it has no collective of its own).
 Runs in a child process: a process group must not outlive the test inside pytest's interpreter."""
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
+
+from host_util import free_port
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -40,18 +41,10 @@ print("RCCL_GATHER_OK")
 '''
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
 def test_rccl_all_gather_branch_on_one_rank():
-    env = dict(os.environ, TE_ROOT=ROOT, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1",
+    env = dict(os.environ, TE_ROOT=ROOT, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     r = subprocess.run([sys.executable, "-c", CHILD], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
                        timeout=280)

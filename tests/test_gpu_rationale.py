@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from gpu_util import dev, record
+from host_util import bits
 from test_rationale_host import GOLDEN, KINDS, SOFT_BAR, golden_documents, kernel_order_soft, make_case
 
 pytestmark = pytest.mark.gpu
@@ -24,11 +25,6 @@ def rt():
 def ops():
     from transformer_explainability_amd import ops as o
     return o
-
-
-def bits(t):
-    return t.contiguous().view(torch.int64) if t.dtype == torch.float64 else (
-        t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t)
 
 
 def restate(scores, word_ids, truth, ks, clamp=True):

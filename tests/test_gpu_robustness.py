@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_util import dev
+from gpu_util import dev, odd_offset_view
+from host_util import same_bits
 from robustness_inputs import inputs, maps, noisy_maps, special_rows
 
 pytestmark = pytest.mark.gpu
@@ -19,27 +20,6 @@ BF = torch.bfloat16
 def te():
     from transformer_explainability_amd import ops, robustness
     return ops, robustness
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def odd_offset_view(t, dtype=None):
-    """t's values (or an uninitialised tensor of t's shape in ``dtype``) in a dense device view that starts one element past a
-    16-byte boundary"""
-    dtype = t.dtype if dtype is None else dtype
-    store = torch.empty(t.numel() + 1, dtype=dtype, device=dev())
-    view = store[1:].view(t.shape)
-    if dtype == t.dtype:
-        view.copy_(t)
-    assert view.data_ptr() % 16 == view.element_size() and view.is_contiguous()
-    return view
 
 
 # ------------------------------------------------------------------------------------------------ noise

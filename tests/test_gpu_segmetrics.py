@@ -9,6 +9,7 @@ import torch
 
 from conftest import load_golden
 from gpu_util import dev, record
+from host_util import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -75,10 +76,6 @@ def restate(heat, mask, labels):
     inter, union = s.intersection_union(mask, labels)
     counts = torch.cat([correct.view(-1, 1), labeled.view(-1, 1), inter, union], 1)
     return counts, s.average_precision(heat, labels), s.row_f1(mask, labels)
-
-
-def bits(t):
-    return t.contiguous().view(torch.int64) if t.dtype == torch.float64 else t
 
 
 def compare(name, got, ref):

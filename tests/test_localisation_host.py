@@ -9,15 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from host_util import lib, status  # noqa: F401
 from localisation_inputs import HEATS, SIZES, box_case, energy_bound, mask_case, rasterise, special_cases
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
 
 
 def loc():
@@ -204,11 +197,6 @@ def test_evaluator_boxes_on_cpu():
 
 # ------------------------------------------------------------------------------------------------ refusals on the host
 P = 4096      # a fake non-null, 16-byte-aligned address: every call below returns before the first HIP call
-
-
-def status(lib, fn, base, **changed):
-    assert set(changed) <= set(base), changed
-    return getattr(lib, fn)(*{**base, **changed}.values())
 
 
 def test_entry_point_rejects_on_the_host(lib):

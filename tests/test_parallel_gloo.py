@@ -3,22 +3,15 @@
 ViT + generators) with the device ops routed to the oracle, so the test checks that any shard layout
 reproduces the single-process maps bit for bit and in global order."""
 import os
-import socket
 import sys
 
 import pytest
 import torch
 import torch.multiprocessing as mp
 
+from host_util import free_port
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _explain(indices):
@@ -68,7 +61,7 @@ def test_world2_gloo_matches_single_process(tmp_path):
     n_items = 5      # odd on purpose: ranks own 3 and 2 samples (ragged shards)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     single = _explain(list(range(n_items)))
-    port = _free_port()
+    port = free_port()
     mp.spawn(_worker, args=(2, port, n_items, str(tmp_path)), nprocs=2, join=True)
     for rank in range(2):
         got = torch.load(os.path.join(str(tmp_path), f"rank{rank}.pt"))
@@ -87,7 +80,7 @@ def test_world8_gloo_matches_single_process(tmp_path):
     n_items, world = 19, 8
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     single = _explain(list(range(n_items)))
-    port = _free_port()
+    port = free_port()
     mp.spawn(_worker, args=(world, port, n_items, str(tmp_path)), nprocs=world, join=True)
     seen = []
     for rank in range(world):
@@ -156,7 +149,7 @@ def test_world2_gloo_sweep_layout_and_single_collective(tmp_path):
     data path; the gathered maps are in global order and equal the stores read back through ImagenetResults."""
     n_items = 7
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    port = _free_port()
+    port = free_port()
     mp.spawn(_sweep_worker, args=(2, port, n_items, str(tmp_path)), nprocs=2, join=True)
     from transformer_explainability_amd.sweep import ImagenetResults
     res = ImagenetResults(str(tmp_path))

@@ -11,11 +11,12 @@ four times that, 8.9e-16 (the margin covers fp64 contraction on the device).  Th
 import ctypes
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
+
+from host_util import header_args, lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "rationale.npz")
@@ -28,14 +29,6 @@ KINDS = ["random", "clamped", "tied"]
 def rt():
     from transformer_explainability_amd import rationale
     return rationale
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
 
 
 @pytest.fixture(scope="module")
@@ -111,20 +104,13 @@ def sklearn_soft(ws, n_words, truth):
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
-def _header_args(name):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "te_relprop.h")).read(), flags=re.S)
-    m = re.search(r"\b" + name + r"\s*\(([^)]*)\)", header)
-    assert m, name
-    return len([a for a in m.group(1).split(",") if a.strip()])
-
-
 def test_entry_points_declared_exported_bound(lib):
     from transformer_explainability_amd import _lib
     for name in NEW_SYMBOLS:
         assert name in _lib.SIGNATURES, name
         assert hasattr(lib, name), name
-        assert len(_lib.SIGNATURES[name][1]) == _header_args(name), name
-    assert _header_args("te_rationale_metrics_f32") == 17 and _header_args("te_token_erase") == 15
+        assert len(_lib.SIGNATURES[name][1]) == header_args(name), name
+    assert header_args("te_rationale_metrics_f32") == 17 and header_args("te_token_erase") == 15
     header = open(os.path.join(ROOT, "include", "te_relprop.h")).read()
     assert "#define TE_RATIONALE_MAX_KS 16" in header and "#define TE_TOKEN_ERASE_MAX_FRACTIONS 8" in header
     assert _lib.TE_RATIONALE_MAX_KS == 16 and _lib.TE_TOKEN_ERASE_MAX_FRACTIONS == 8 and _lib.TE_RATIONALE_CLAMP == 1

@@ -7,21 +7,13 @@ import numpy as np
 import pytest
 import torch
 
+from host_util import lib, same_bits, status  # noqa: F401
 from robustness_inputs import KNOWN_ANSWERS, LinearMaps, inputs, maps, special_rows
 
 
 def rb():
     from transformer_explainability_amd import robustness
     return robustness
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
 # ------------------------------------------------------------------------------------------------ Philox and the noise
@@ -278,19 +270,6 @@ def test_evaluator_refuses_token_ids_and_bad_arguments():
 
 
 # ------------------------------------------------------------------------------------------------ the entry points, no device
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
-
-
-def status(lib, fn, base, **changed):
-    assert set(changed) <= set(base), changed
-    return getattr(lib, fn)(*{**base, **changed}.values())
-
-
 def test_new_entry_points_refuse_on_the_host(lib):
     """P is a fake non-null, 16-byte-aligned address that the host never dereferences: every call returns before any HIP call."""
     P = 4096

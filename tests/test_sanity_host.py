@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from host_util import same_bits
 from mapsim_inputs import FAMILIES, FINITE, family, images
 
 EPS = 2.0 ** -53
@@ -132,12 +133,6 @@ def tiny_bert():
 def full_state(model):
     """Every parameter and buffer, the non-persistent ones included."""
     return {k: v.detach().clone() for k, v in list(model.named_parameters()) + list(model.named_buffers())}
-
-
-def same_bits(a, b):
-    """Bit for bit: -0.0 is not +0.0, and a NaN equals itself."""
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.reshape(-1).contiguous().view(torch.uint8),
-                                                                    b.reshape(-1).contiguous().view(torch.uint8))
 
 
 def changed(model, before):

@@ -10,25 +10,11 @@ import pytest
 import torch
 
 from conftest import load_golden
+from host_util import header_args, lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "transformer-explainability_amd", "csrc")
 NEW_SYMBOLS = ["te_seg_metrics_workspace_bytes", "te_seg_metrics_f32"]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
-
-
-def _header_args(name):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "te_relprop.h")).read(), flags=re.S)
-    m = re.search(r"\b" + name + r"\s*\(([^)]*)\)", header)
-    assert m, name
-    return len([a for a in m.group(1).split(",") if a.strip()])
 
 
 def test_entry_points_declared_exported_bound(lib):
@@ -36,8 +22,8 @@ def test_entry_points_declared_exported_bound(lib):
     for name in NEW_SYMBOLS:
         assert name in _lib.SIGNATURES, name
         assert hasattr(lib, name), name
-        assert len(_lib.SIGNATURES[name][1]) == _header_args(name), name
-    assert _header_args("te_seg_metrics_f32") == 12 and _header_args("te_seg_metrics_workspace_bytes") == 3
+        assert len(_lib.SIGNATURES[name][1]) == header_args(name), name
+    assert header_args("te_seg_metrics_f32") == 12 and header_args("te_seg_metrics_workspace_bytes") == 3
 
 
 def test_header_comment_states_the_semantics():

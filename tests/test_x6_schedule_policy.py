@@ -10,15 +10,9 @@ import math
 
 import pytest
 
+from host_util import lib  # noqa: F401
+
 T_VIT_B = 64 * 197          # 12 608 rows: 50 tile columns of 256 rows
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__
-    __graft_entry__.build()
-    from transformer_explainability_amd import _lib
-    return _lib.load()
 
 
 def schedule(lib, T, in_f, out_f, pass_, flags):
