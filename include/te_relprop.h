@@ -1020,7 +1020,8 @@ int te_class_targets_f64(const double* logits, int64_t ld, int64_t B, int64_t C,
 
 /* ---- AttnLRP (csrc/te_attnlrp.hip) ------------------------------------------------------------------------------------
  * A second explanation method beside the reference's: AttnLRP (Achtibat et al., "AttnLRP: Attention-Aware Layer-Wise
- * Relevance Propagation for Transformers", ICML 2024) for the ViT / DeiT and BERT models of this package, fp32 only.  The
+ * Relevance Propagation for Transformers", ICML 2024) for the ViT / DeiT and BERT models of this package, fp32 or bf16
+ * (below: "AttnLRP, bf16 operands").  The
  * reference has no such method and no parity with the authors' library (LXT) is claimed: THIS SECTION IS THE SPECIFICATION,
  * and tests/attnlrp_ref.py restates it with torch autograd.
  *
@@ -1079,6 +1080,72 @@ int te_alrp_layernorm_f32(const float* G, const float* gamma, const float* rstd,
                           te_stream_t stream);
 int te_alrp_token_relevance_f32(const float* x0, const float* G, float* out, int64_t B, int64_t N, int64_t C, int skip_first,
                                 te_stream_t stream);
+
+/* ---- AttnLRP, bf16 operands (a bf16 model: model.to(torch.bfloat16); csrc/te_attnlrp.hip, csrc/te_bf16.hip) ---------------
+ * The rules above, evaluated in fp32 on the model's own bf16 tensors, which are read exactly (bf16 -> fp32 is exact): the
+ * contract of "bf16 operands" above.  G (relevance per unit of activation), the seed, rstd and the result are fp32; the token
+ * sums are fp64, rounded once.  Nothing of G is ever rounded to bf16, and no cached bf16 tensor is replaced by a recomputation.
+ * The bf16 operands of a rule are the cached tensors the fp32 chain reads: the outputs of Linears and Adds, the inputs of
+ * LayerNorms, GELU and tanh, qkv.Y (BERT: query.Y, key.Y, value.Y), the probabilities the accessor holds, gamma, W and x0.
+ *
+ * Streaming rules: te_attnlrp_damp_bf16, _act_bf16, _row_rstd_bf16, _layernorm_bf16, _token_relevance_bf16 are the _f32 kernels
+ * templated on the operand type.  SPECIFICATION: each gives the bits of its _f32 entry on an exact fp32 copy of the bf16
+ * operand -- the same operations, the same lane order, the same te_block_sum order.  A bf16 pointer needs 2-byte alignment
+ * (TE_ERR_UNSUPPORTED otherwise); a group of four bf16 is read in one 8-byte access where the fp32 operands allow their
+ * 16-byte one and the group lies on an 8-byte boundary, single elements elsewhere, and the bits are the same either way.  The
+ * refusals are those of the _f32 entries.  te_alrp_scale3_f32 works on G and has no bf16 form.
+ *
+ * Linear: out[t][i] = sum_o A[t][o] W[o][i], A = damp(G, Y) with te_attnlrp_damp_bf16's bits.  G [T, g_ld >= out_f] fp32 and Y
+ * [T, y_ld >= out_f] bf16 are read in place (row strides); W bf16 contiguous; out [T, in_f] fp32 contiguous.  A
+ * streaming pass writes A as three exact bf16 planes [3][T][out_f] (the split of csrc/te_x6.h, the layout of the S planes of
+ * te_linear_relprop_bf16) into the workspace; the product is then planes x ONE bf16 operand -- three plane-products, every
+ * bf16 x bf16 product exact in the fp32 accumulator.  THE WEIGHT SIDE: w_transposed == 0: W [out_f, in_f] itself, read in place
+ * as the transposed view (row i of the operand = column i of W, staged through a transposing store); w_transposed != 0: W points
+ * to a contiguous copy of W^T [in_f, out_f] that the caller keeps (ops.alrp_weight_t: cached per weight version), read along k.
+ * The products and their order are the same: the same bits either way.
+ * ACCUMULATION ORDER: one fp32 accumulator per output, which starts at +0; K steps of 32 in index order; inside a K step plane
+ * 2, then plane 1, then plane 0 (smallest first), each adding its 32 exact products by one v_mfma_f32_16x16x32_bf16.  The
+ * order does not depend on T or on the grid: a row alone equals the same row in a batch bit for bit.  Tiles are 128 rows x 64
+ * columns x 32.  Shapes: te_attnlrp_linear_bf16_supported -- in_f and out_f multiples of 128, any T >= 1 (TE_ERR_UNSUPPORTED
+ * otherwise).  TE_ERR_INVALID_ARG: a null pointer, a size <= 0, g_ld or y_ld < out_f, eps negative, NaN or infinite;
+ * TE_ERR_WORKSPACE: ws NULL or smaller than te_attnlrp_linear_bf16_workspace_bytes.
+ *
+ * Attention: the block's backward for d_out = G_o in fp32 on the exact bf16 operands.  G_o fp32, element (b, h, n, d) at
+ * g_sb b + g_sh h + g_sn n + d (a [B,N,C] tensor: sb = N C, sh = D, sn = C); q, k, v bf16 and the fp32 outputs G_q, G_k, G_v with
+ * strides of the same meaning, so the thirds of a fused [B,N,3C] activation (and of a fused gradient) and BERT's three tensors
+ * are read (written) in place; attn bf16 [B,H,N,N] contiguous.  The additive mask is a constant and no argument.
+ *     d_attn = G_o v^T, d_v = attn^T G_o                    (G_o as three planes, one streaming pass)
+ *     d_s = p (.) (d_attn - s), s_i = sum_j t_ij, t_ij = d_attn[i][j] p[i][j] rounded; d_s written as three planes
+ *     d_q = scale (d_s k), d_k = scale (d_s^T q)            (one multiply by scale in the epilogue)
+ * G_q = d_q, G_k = d_k, G_v = d_v: the uniform rule's exact factors 1/4, 1/4, 1/2 are NOT applied here -- the caller runs
+ * te_alrp_scale3_f32 on the outputs afterwards, as the fp32 chain does.  The row sum s_i is the fp32 row sum in the LANE ORDER
+ * of te_alrp_layernorm_f32, fixed by the indices alone.  The four products are planes x one bf16 operand on 64 x 64 x 32 tiles:
+ * one accumulator per plane, plain k loop, summed (plane 2 + plane 1) + plane 0 at the end -- the arrangement of
+ * te_matmul_relprop_av_bf16 / _qk_bf16.  A (b, h) alone equals the same pair in a batch bit for bit.  N == 1: G_v = G_o and
+ * G_q = G_k = 0 exactly.  Shapes: te_attnlrp_attention_bf16_supported where te_matmul_relprop_bf16_supported (head dim 64,
+ * N <= 1024), B H <= 65535; TE_ERR_UNSUPPORTED otherwise. */
+int te_attnlrp_damp_bf16(const float* G, const te_bf16_t* Y, float* out, int64_t n, float eps, te_stream_t stream);
+int te_attnlrp_act_bf16(const float* G, const te_bf16_t* x, float* out, int64_t n, int kind, te_stream_t stream);
+int te_attnlrp_row_rstd_bf16(const te_bf16_t* x, float* rstd, int64_t rows, int64_t C, float eps, te_stream_t stream);
+int te_attnlrp_layernorm_bf16(const float* G, const te_bf16_t* gamma, const float* rstd, float* out, int64_t rows, int64_t C,
+                           te_stream_t stream);
+int te_attnlrp_token_relevance_bf16(const te_bf16_t* x0, const float* G, float* out, int64_t B, int64_t N, int64_t C,
+                                 int skip_first, te_stream_t stream);
+int te_attnlrp_linear_bf16_supported(int64_t T, int64_t in_f, int64_t out_f);
+size_t te_attnlrp_linear_bf16_workspace_bytes(int64_t T, int64_t in_f, int64_t out_f);
+int te_attnlrp_linear_bf16(const float* G, int64_t g_ld, const te_bf16_t* Y, int64_t y_ld, const te_bf16_t* W,
+                        int w_transposed, float* out, int64_t T, int64_t in_f, int64_t out_f, float eps, void* ws, size_t ws_bytes, te_stream_t stream);
+int te_attnlrp_attention_bf16_supported(int64_t N, int64_t D);
+size_t te_attnlrp_attention_bf16_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t D);
+int te_attnlrp_attention_bf16(const float* G_o, int64_t g_sb, int64_t g_sh, int64_t g_sn,
+                           const te_bf16_t* q, int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                           const te_bf16_t* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                           const te_bf16_t* v, int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                           const te_bf16_t* attn, float scale,
+                           float* G_q, int64_t gq_sb, int64_t gq_sh, int64_t gq_sn,
+                           float* G_k, int64_t gk_sb, int64_t gk_sh, int64_t gk_sn,
+                           float* G_v, int64_t gv_sb, int64_t gv_sh, int64_t gv_sn,
+                           int64_t B, int64_t H, int64_t N, int64_t D, void* ws, size_t ws_bytes, te_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,9 @@ entry of build.SOURCES (or only the files named) both trees' file is compiled wi
 
 One line per file: lines, sha256 of the old and of the new normalised listing, `same` / `DIFFERENT` (`new`: a file OLD_TREE
 does not have).  A differing file gets a second line that says how it differs (`classify`): whether the line counts agree, how
-many lines only have the source operands of a commutative integer opcode in another order, and how many differ otherwise.  Exit status 1 on any difference (the normalised listings of a differing file are kept in --keep DIR for `diff`).  Flags and the file list are the
+many lines only have the source operands of a commutative integer opcode in another order, and how many differ otherwise; and a
+third line that compares the files function by function (`gained_only`): a file that only gained kernels keeps the instructions
+of every function it had.  Exit status 1 on any difference (the normalised listings of a differing file are kept in --keep DIR for `diff`).  Flags and the file list are the
 flags and the list of NEW_TREE's build.py.
 """
 import argparse
@@ -68,6 +70,38 @@ def classify(old, new):
     return swapped, other
 
 
+def kernels(text):
+    """The instruction text of every function of a normalised listing (label .. .Lfunc_end), without comments, with the
+    symbol, block and function numbers that depend on the function's position in the file removed."""
+    out, cur = [], None
+    for line in text.split("\n"):
+        if cur is None:
+            if re.match(r"^SYM\d+:", line):
+                cur = []
+        elif re.match(r"^\.Lfunc_end\d+:", line):
+            out.append("\n".join(cur))
+            cur = None
+        else:
+            line = re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"SYM\d+", "SYM", line.split(";")[0])).strip()
+            if line:
+                cur.append(line)
+    return out
+
+
+def gained_only(old, new):
+    """(functions in old, in new, functions of old whose instructions no function of new has): a file that only GAINED
+    kernels has 0 in the last place."""
+    ko, kn = kernels(old), kernels(new)
+    left = list(kn)
+    missing = 0
+    for k in ko:
+        if k in left:
+            left.remove(k)
+        else:
+            missing += 1
+    return len(ko), len(kn), missing
+
+
 def listing(build, tree, src, out):
     csrc = os.path.join(tree, PKG, "csrc")
     cmd = [build._hipcc(), *build.CXXFLAGS, "--cuda-device-only", "-S", "-I", os.path.join(tree, "include"), "-I", csrc,
@@ -116,6 +150,10 @@ def main():
                                 "same number of lines; lines with the same opcode and destination and the source operands of a "
                                 "commutative integer opcode in another order: %s; lines that differ in any other way: %d"
                                 % (dict(sorted(kind[0].items())) or "none", kind[1])), flush=True)
+                n_old, n_new, missing = gained_only(old, new)
+                print("    functions: %d before, %d after; functions of the old listing whose instructions no function of the "
+                      "new listing has: %d%s" % (n_old, n_new, missing, " (the file only gained functions)"
+                                                  if missing == 0 and n_new > n_old else ""), flush=True)
             if not same and a.keep:
                 os.makedirs(a.keep, exist_ok=True)
                 for side, t in (("old", old), ("new", new)):

@@ -238,7 +238,7 @@ def make_bert_module(L):
             if self.head_mask is not None:
                 raise ops._lib.TeError("BertSelfAttention.attnlrp: head_mask is not implemented for AttnLRP")
             q, k, v = self.query.Y.detach(), self.key.Y.detach(), self.value.Y.detach()
-            d_q, d_k, d_v = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+            d_q, d_k, d_v = (torch.empty_like(t, dtype=torch.float32) for t in (q, k, v))      # (G is fp32 on a bf16 model too)
             R_ours.attention_attnlrp(G_o, q, k, v, self.get_attn().detach(), self.num_attention_heads,
                                      1.0 / math.sqrt(self.attention_head_size), d_q, d_k, d_v)
             ops.alrp_scale3(d_q, d_k, d_v)

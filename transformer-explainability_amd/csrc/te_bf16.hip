@@ -15,6 +15,14 @@
 //   (Z of an attention rule is the forward product the model cached; when it is absent it is recomputed in fp32 from the
 //    bf16 operands by the same GEMM loop.)
 //
+// The two products of the AttnLRP chain on a bf16 model (te_relprop.h, "AttnLRP", bf16 operands) run on the same loop: their
+// fp32 operand (damp(G, Y); G_o; d_s) is written as three planes by a streaming pass of te_attnlrp.hip, the other operand is a
+// bf16 tensor of the model read in place, one accumulator per plane, summed smallest first.
+//   Linear     out = A . W, A = damp(G, Y) as planes [3][T][out]; W [out][in] read in place as the transposed view, or its
+//              transpose [in][out] (a cached plane) read along k
+//   Attention  d_attn = G_o . v^T, d_v = attn^T . G_o (G_o as planes); d_s = p (.) (d_attn - rowsum(d_attn (.) p)) as planes;
+//              d_q = scale d_s . k, d_k = scale d_s^T . q
+//
 // One GEMM loop (gemm_kernel): C[m][n] = sum_k A[m][k] B[n][k] over a batch z, every operand a bf16 view with arbitrary
 // strides (row stride sr, k stride sk), so strided views -- q / k / v inside the fused qkv activation, the cls rows of
 // Block.relprop_cls_only -- are read in place.  Tile BM x BN x 32 in LDS, four waves of (BM/2) x (BN/2), 16x16x32 MFMAs.
@@ -23,6 +31,7 @@
 #include <cstring>
 
 #include "te_bf16_tile.h"
+#include "te_internal.h"
 
 namespace {
 
@@ -47,7 +56,7 @@ struct Mat {        // bf16 [rows x K] of batch z: element (r, k) at p + (z / zh
 };
 
 enum { A_PLAIN = 0, A_SIGNS = 1, A_PLANES3 = 3 };
-enum { EPI_F32 = 0, EPI_GATE = 1, EPI_SIGNS = 2, EPI_SPLANES = 3 };
+enum { EPI_F32 = 0, EPI_GATE = 1, EPI_SIGNS = 2, EPI_SPLANES = 3, EPI_SCALE = 4 };
 
 struct GemmArgs {
   Mat A, B[2];
@@ -56,7 +65,7 @@ struct GemmArgs {
   int64_t o_sb, o_sh, o_sm, o_sn;
   const uint16_t* g;                  // EPI_GATE / EPI_SIGNS: bf16 multiplier at (z, m, n)
   int64_t g_sb, g_sh, g_sm, g_sn;
-  float scale;                        // EPI_GATE
+  float scale;                        // EPI_GATE, EPI_SCALE
   const float* R;                     // EPI_SPLANES: R [M][r_ld], optional per-sample factor rs[(m / rps) rs_stride]
   int64_t r_ld;
   const float* rs;
@@ -134,7 +143,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
   constexpr int NPA = (AK == A_PLANES3) ? 3 : 1;
   // accumulators: one per weight sign (Linear C-pass), or -- a single B operand times three planes (attention) -- one
   // per plane, summed smallest first at the end: each plane's products are then rounded against their own magnitude
-  constexpr bool PER_PLANE = (AK == A_PLANES3 && NB == 1);
+  // (64 x 64 tiles; a larger tile keeps the C-pass's arrangement, one accumulator that takes the planes smallest first inside
+  // every K step: three accumulators of it do not fit the 256 registers of two waves per SIMD)
+  constexpr bool PER_PLANE = (AK == A_PLANES3 && NB == 1 && BM * BN <= kAttTile * kAttTile);
   constexpr int NACC = (AK == A_SIGNS) ? 1 : (PER_PLANE ? 3 : NB);
   constexpr int FM = BM / 32, FN = BN / 32;
   __shared__ uint16_t sA[NPA][BM][kLd];
@@ -235,6 +246,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
           float* o = g.out + zb * g.o_sb + zhh * g.o_sh + m * g.o_sm + n * g.o_sn;
           if constexpr (EPI == EPI_F32) {
             *o = v;
+          } else if constexpr (EPI == EPI_SCALE) {
+            *o = v * g.scale;
           } else {
             const float x = bf(g.g[zb * g.g_sb + zhh * g.g_sh + m * g.g_sm + n * g.g_sn]);
             if constexpr (EPI == EPI_GATE) {
@@ -499,4 +512,97 @@ extern "C" int te_matmul_relprop_qk_bf16(const float* R_nn, const float* r_scale
   c.g = k, c.g_sb = k_sb, c.g_sh = k_sh, c.g_sm = k_sn, c.g_sn = 1;
   c.scale = out_scale;
   return launch<kAttTile, kAttTile, A_PLANES3, 1, EPI_GATE>(c, B * H, stream);
+}
+
+// ================================================================================================ AttnLRP
+extern "C" int te_attnlrp_linear_bf16_supported(int64_t T, int64_t in_f, int64_t out_f) {
+  return te_linear_relprop_bf16_supported(T, in_f, out_f);
+}
+
+extern "C" size_t te_attnlrp_linear_bf16_workspace_bytes(int64_t T, int64_t in_f, int64_t out_f) {
+  if (T <= 0 || in_f <= 0 || out_f <= 0) return 0;
+  return planes_bytes(T * out_f);
+}
+
+extern "C" int te_attnlrp_linear_bf16(const float* G, int64_t g_ld, const te_bf16_t* Y, int64_t y_ld, const te_bf16_t* W,
+                                   int w_transposed, float* out, int64_t T, int64_t in_f, int64_t out_f, float eps, void* ws, size_t ws_bytes,
+                                   te_stream_t stream_) {
+  if (!G || !Y || !W || !out || T <= 0 || in_f <= 0 || out_f <= 0) return TE_ERR_INVALID_ARG;
+  if (g_ld < out_f || y_ld < out_f) return TE_ERR_INVALID_ARG;
+  if (!te_attnlrp_linear_bf16_supported(T, in_f, out_f)) return TE_ERR_UNSUPPORTED;
+  if (!ws || ws_bytes < te_attnlrp_linear_bf16_workspace_bytes(T, in_f, out_f)) return TE_ERR_WORKSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  uint16_t* A = (uint16_t*)ws;
+  int rc = te_alrp::damp_planes_launch(G, Strided{0, 0, g_ld}, Y, Strided{0, 0, y_ld}, A, 1, 1, T, out_f, eps, stream);
+  if (rc != TE_OK) return rc;
+  // out[t][i] = sum_o A[t][o] W[o][i]: row i of the second operand is column i of W (sr == 1: staged transposed), or row i of
+  // the contiguous W^T the caller keeps.  The same products in the same order either way.
+  GemmArgs c = blank();
+  c.A = Mat{A, 0, 0, out_f, 1, T * out_f};
+  c.B[0] = w_transposed ? Mat{W, 0, 0, out_f, 1, 0} : Mat{W, 0, 0, 1, in_f, 0};
+  c.M = T, c.N = in_f, c.K = out_f;
+  c.out = out, c.o_sm = in_f, c.o_sn = 1;
+  // (128 rows x 64 columns: with three staged planes of A and the transposed staging of W the 128 x 128 tile spills 63 VGPRs)
+  return launch<kLinTile, kAttTile, A_PLANES3, 1, EPI_F32>(c, 1, stream);
+}
+
+extern "C" int te_attnlrp_attention_bf16_supported(int64_t N, int64_t D) { return te_matmul_relprop_bf16_supported(N, D); }
+
+extern "C" size_t te_attnlrp_attention_bf16_workspace_bytes(int64_t B, int64_t H, int64_t N, int64_t D) {
+  if (B <= 0 || H <= 0 || N <= 0 || D <= 0) return 0;
+  return planes_bytes(B * H * N * D) + planes_bytes(B * H * N * N) + te_align_up((size_t)B * H * N * N * sizeof(float), 256);
+}
+
+extern "C" int te_attnlrp_attention_bf16(const float* G_o, int64_t g_sb, int64_t g_sh, int64_t g_sn, const te_bf16_t* q, int64_t q_sb,
+                                      int64_t q_sh, int64_t q_sn, const te_bf16_t* k, int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                                      const te_bf16_t* v, int64_t v_sb, int64_t v_sh, int64_t v_sn, const te_bf16_t* attn,
+                                      float scale, float* G_q, int64_t gq_sb, int64_t gq_sh, int64_t gq_sn, float* G_k,
+                                      int64_t gk_sb, int64_t gk_sh, int64_t gk_sn, float* G_v, int64_t gv_sb, int64_t gv_sh,
+                                      int64_t gv_sn, int64_t B, int64_t H, int64_t N, int64_t D, void* ws, size_t ws_bytes,
+                                      te_stream_t stream_) {
+  if (!G_o || !q || !k || !v || !attn || !G_q || !G_k || !G_v || B <= 0 || H <= 0 || N <= 0 || D <= 0) return TE_ERR_INVALID_ARG;
+  if (!te_attnlrp_attention_bf16_supported(N, D) || B * H > 65535) return TE_ERR_UNSUPPORTED;
+  if (!ws || ws_bytes < te_attnlrp_attention_bf16_workspace_bytes(B, H, N, D)) return TE_ERR_WORKSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  const int64_t nd = N * D, nn = N * N, BH = B * H;
+  uint16_t* P = (uint16_t*)ws;                                         // G_o   [3][B H][N][D]
+  uint16_t* S = (uint16_t*)((char*)ws + planes_bytes(BH * nd));        // d_s   [3][B H][N][N]
+  float* dA = (float*)((char*)S + planes_bytes(BH * nn));             // d_attn   [B H][N][N]
+  int rc = te_alrp::damp_planes_launch(G_o, Strided{g_sb, g_sh, g_sn}, nullptr, Strided{0, 0, 0}, P, B, H, N, D, 0.0f, stream);
+  if (rc != TE_OK) return rc;
+  // d_attn[i][j] = sum_d G_o[i][d] v[j][d]
+  GemmArgs a = blank();
+  a.A = Mat{P, H * nd, nd, D, 1, BH * nd};
+  a.B[0] = Mat{v, v_sb, v_sh, v_sn, 1, 0};
+  a.M = N, a.N = N, a.K = D, a.zh = H;
+  a.out = dA, a.o_sb = H * nn, a.o_sh = nn, a.o_sm = N, a.o_sn = 1;
+  rc = launch<kAttTile, kAttTile, A_PLANES3, 1, EPI_SCALE>(a, BH, stream);
+  if (rc != TE_OK) return rc;
+  // d_v[j][d] = sum_i attn[i][j] G_o[i][d], evaluated as the transposed product (m = d, n = j)
+  GemmArgs c = blank();
+  c.A = Mat{P, H * nd, nd, 1, D, BH * nd};
+  c.B[0] = Mat{attn, H * nn, nn, 1, N, 0};
+  c.M = D, c.N = N, c.K = N, c.zh = H;
+  c.out = G_v, c.o_sb = gv_sb, c.o_sh = gv_sh, c.o_sm = 1, c.o_sn = gv_sn;
+  rc = launch<kAttTile, kAttTile, A_PLANES3, 1, EPI_SCALE>(c, BH, stream);
+  if (rc != TE_OK) return rc;
+  rc = te_alrp::softmax_bwd_planes_launch(dA, attn, S, BH * N, N, stream);
+  if (rc != TE_OK) return rc;
+  // d_q[i][d] = scale sum_j d_s[i][j] k[j][d]
+  GemmArgs e = blank();
+  e.A = Mat{S, H * nn, nn, N, 1, BH * nn};
+  e.B[0] = Mat{k, k_sb, k_sh, 1, k_sn, 0};
+  e.M = N, e.N = D, e.K = N, e.zh = H;
+  e.out = G_q, e.o_sb = gq_sb, e.o_sh = gq_sh, e.o_sm = gq_sn, e.o_sn = 1;
+  e.scale = scale;
+  rc = launch<kAttTile, kAttTile, A_PLANES3, 1, EPI_SCALE>(e, BH, stream);
+  if (rc != TE_OK) return rc;
+  // d_k[j][d] = scale sum_i d_s[i][j] q[i][d]
+  GemmArgs f = blank();
+  f.A = Mat{S, H * nn, nn, 1, N, BH * nn};
+  f.B[0] = Mat{q, q_sb, q_sh, 1, q_sn, 0};
+  f.M = N, f.N = D, f.K = N, f.zh = H;
+  f.out = G_k, f.o_sb = gk_sb, f.o_sh = gk_sh, f.o_sm = gk_sn, f.o_sn = 1;
+  f.scale = scale;
+  return launch<kAttTile, kAttTile, A_PLANES3, 1, EPI_SCALE>(f, BH, stream);
 }

@@ -78,3 +78,11 @@ int bwd_cols_launch(const float* attn, const float* d_attn, const float* rowdot,
                     float* d_v, Strided dvs, float* d_k, Strided dks, int64_t B, int64_t H, int64_t N, float scale, int need_qk,
                     hipStream_t stream);
 }  // namespace te_attn_long
+
+namespace te_alrp {      // te_attnlrp.hip: the streaming passes that hand an fp32 operand to a product on bf16 MFMAs as three exact bf16 planes (caller: te_bf16.hip)
+// planes [3][B H N][C] of damp(G, Y) (Y == nullptr: of G itself); row (b, h, n) of G / Y at the strides, C contiguous elements
+int damp_planes_launch(const float* G, Strided gs, const te_bf16_t* Y, Strided ys, uint16_t* planes, int64_t B, int64_t H, int64_t N,
+                       int64_t C, float eps, hipStream_t stream);
+// planes [3][rows][N] of d_s = p (.) (d_attn - sum_j d_attn (.) p): d_attn fp32 [rows][N], p bf16 [rows][N], both contiguous
+int softmax_bwd_planes_launch(const float* d_attn, const te_bf16_t* p, uint16_t* planes, int64_t rows, int64_t N, hipStream_t stream);
+}  // namespace te_alrp

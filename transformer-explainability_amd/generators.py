@@ -129,20 +129,34 @@ def _refuse_before_forward(input, wanted):
                                "torch.float64 model: run it on a float32 or bfloat16 model")
 
 
-def _refuse_attnlrp(model, eps, head_mask, *inputs):
+def _refuse_attnlrp(model, eps, head_mask, *inputs, cast=()):
     """The refusals of generate_attnlrp, raised before the forward pass: AttnLRP (te_relprop.h, section "AttnLRP") is
-    implemented for float32 models in eval mode without a head mask."""
+    implemented for float32 models, and for bfloat16 models on the GPU, in eval mode without a head mask.  ``inputs`` share
+    the parameters' dtype; ``cast`` are inputs a bfloat16 model casts to its own dtype itself (BERT's attention_mask, which
+    generate_LRP takes in any dtype): they only have to be on the GPU."""
     if head_mask is not None:
         raise ops._lib.TeError("generate_attnlrp: head_mask is not implemented for AttnLRP (the chain has no Mul rule); "
                                "pass head_mask=None")
     if model.training:
         raise ops._lib.TeError("generate_attnlrp: the model is in train mode; AttnLRP reads the caches of an eval-mode "
                                "forward pass (dropout is the identity): call model.eval()")
-    dtypes = [p.dtype for p in model.parameters()] + [t.dtype for t in inputs if torch.is_tensor(t) and t.is_floating_point()]
+    floats = lambda ts: [t for t in ts if torch.is_tensor(t) and t.is_floating_point()]      # noqa: E731
+    params = list(model.parameters())
+    bf16_model = bool(params) and all(p.dtype == torch.bfloat16 for p in params)
+    strict = params + floats(inputs) + ([] if bf16_model else floats(cast))
+    dtypes = [t.dtype for t in strict]
     for dt in dtypes:
-        if dt != torch.float32:
-            raise ops._lib.TeError(f"generate_attnlrp: AttnLRP is implemented for torch.float32 models and inputs only, "
-                                   f"got {dt}: run it on a float32 copy of the model")
+        if dt not in (torch.float32, torch.bfloat16):
+            raise ops._lib.TeError(f"generate_attnlrp: AttnLRP is implemented for torch.float32 and torch.bfloat16 models "
+                                   f"and inputs only, got {dt}: run it on a float32 or bfloat16 copy of the model")
+    if torch.bfloat16 in dtypes:
+        if torch.float32 in dtypes:
+            raise ops._lib.TeError("generate_attnlrp: torch.bfloat16 mixed with torch.float32 among the model's parameters and "
+                                   "its inputs; the chain reads the caches of ONE format: convert the model and its inputs "
+                                   "alike (model.to(torch.bfloat16), input.to(torch.bfloat16))")
+        if any(not t.is_cuda for t in strict + [t for t in list(inputs) + list(cast) if torch.is_tensor(t)]):
+            raise ops._lib.TeError("generate_attnlrp: a torch.bfloat16 model and its inputs must be on the GPU -- the chain on "
+                                   "bf16 operands runs in the HIP kernels only, there is no host chain")
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < float("inf"):
         raise ValueError(f"generate_attnlrp: eps must be a finite number >= 0, got {eps!r}")
 
@@ -376,7 +390,8 @@ class LRP(_PassDriver):
         """(extension) AttnLRP (Achtibat et al., ICML 2024; the rules: te_relprop.h, section "AttnLRP") -> fp32 [B, N-1],
         the shape of generate_LRP: the relevance of the patch tokens for the class ``index`` (None: the per-sample argmax).
         One forward pass, no backward pass, one chain; ``eps`` (>= 0) stabilises the Linear and residual-Add rules.  float32
-        models in eval mode only; bf16 / fp16 / fp64 models, train mode and ``head_mask`` raise TeError before the forward
+        models, and bfloat16 models with bfloat16 images on the GPU (the chain in fp32 on the cached bf16 tensors), in eval
+        mode; fp16 / fp64 models, a mix of bf16 and fp32, train mode and ``head_mask`` raise TeError before the forward
         pass.  The x6 status poll / post as in generate_LRP; capturable by GraphedCall."""
         with _x6_bracket(input):
             return self._attnlrp(input, index, eps, head_mask)
@@ -772,10 +787,11 @@ class Generator(_PassDriver):
     def generate_attnlrp(self, input_ids, attention_mask, index=None, eps=1e-6, head_mask=None):
         """(extension) AttnLRP (Achtibat et al., ICML 2024; the rules: te_relprop.h, section "AttnLRP") -> fp32 [B, N]: the
         relevance of every token (the sum over the hidden dimension of x0 (.) G at the input of the embedding LayerNorm) for
-        the class ``index`` (None: the per-sample argmax).  One forward pass, no backward pass, one chain.  float32 models in
-        eval mode only; bf16 / fp16 / fp64 models, train mode and ``head_mask`` raise TeError before the forward pass."""
+        the class ``index`` (None: the per-sample argmax).  One forward pass, no backward pass, one chain.  float32 models, and
+        bfloat16 models on the GPU (attention_mask in any dtype, as for generate_LRP), in eval mode; fp16 / fp64 models, a mix
+        of bf16 and fp32 parameters, train mode and ``head_mask`` raise TeError before the forward pass."""
         with _x6_bracket(input_ids):
-            _refuse_attnlrp(self.model, eps, head_mask, input_ids, attention_mask)
+            _refuse_attnlrp(self.model, eps, head_mask, input_ids, cast=(attention_mask,))
             with torch.no_grad():
                 output = self.model(input_ids=input_ids, attention_mask=attention_mask)[0]
                 _drop_rule_planes(self.model)

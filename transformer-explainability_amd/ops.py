@@ -2619,9 +2619,16 @@ def class_targets(logits: Tensor, classes: Optional[Tensor] = None, topk: Option
 
 
 # ---------------------------------------------------------------------------------------- AttnLRP
-# The rule kernels of csrc/te_attnlrp.hip (te_relprop.h, section "AttnLRP": the specification of the method).  fp32 device
-# tensors only; every binding refuses anything else with DTYPES_MSG before a launch.
+# The rule kernels of csrc/te_attnlrp.hip (te_relprop.h, section "AttnLRP": the specification of the method).  G and every
+# result are fp32 device tensors; the cached operand of a rule (Y, x, gamma, x0) is fp32, or bf16 on a bf16 model (the
+# te_attnlrp_*_bf16 entry: the _f32 entry's bits on an exact fp32 copy).  Every binding refuses anything else with DTYPES_MSG before a launch.
 _ALRP_KINDS = {"gelu": _lib.TE_ALRP_ACT_GELU, "tanh": _lib.TE_ALRP_ACT_TANH}
+
+
+def _alrp_operand(t: Tensor, rule: str) -> Tuple[Tensor, str]:
+    """The cached operand of a rule, contiguous, and the name of the entry that reads it: te_alrp_<rule>_f32, or, a bf16
+    operand, te_attnlrp_<rule>_bf16."""
+    return (_c16(t), f"te_attnlrp_{rule}_bf16") if _is_bf16(t) else (_c(t), f"te_alrp_{rule}_f32")
 
 
 def _alrp_out(out: Optional[Tensor], like: Tensor, what: str) -> Tensor:
@@ -2634,12 +2641,12 @@ def _alrp_out(out: Optional[Tensor], like: Tensor, what: str) -> Tensor:
 
 def alrp_damp(G: Tensor, Y: Tensor, eps: float = 1e-6, out: Optional[Tensor] = None) -> Tensor:
     """damp(G, Y) = G Y / stab(Y), stab(y) = y + eps sgn(y) with sgn(0) = +1; eps = 0: G itself.  ``out`` may be G."""
-    G, Y = _c(G), _c(Y)
+    G, (Y, name) = _c(G), _alrp_operand(Y, "damp")
     if G.shape != Y.shape:
         raise _lib.TeError(f"alrp_damp: G {tuple(G.shape)} and Y {tuple(Y.shape)} differ in shape")
     out = _alrp_out(out, G, "alrp_damp")
-    with _on_device(G) as lib, _timed("alrp_damp", 0.0, 12.0 * G.numel()):
-        _lib.check(lib.te_alrp_damp_f32(_ptr(G), _ptr(Y), _ptr(out), G.numel(), float(eps), _stream(G)), "te_alrp_damp_f32")
+    with _on_device(G) as lib, _timed("alrp_damp", 0.0, (8.0 + Y.element_size()) * G.numel()):
+        _lib.check(getattr(lib, name)(_ptr(G), _ptr(Y), _ptr(out), G.numel(), float(eps), _stream(G)), name)
     return out
 
 
@@ -2647,13 +2654,12 @@ def alrp_act(G: Tensor, x: Tensor, kind: str = "gelu", out: Optional[Tensor] = N
     """The identity rule through y = f(x), f = GELU (te_gelu) or tanh: G (f(x) / x), f'(0) at x == 0.  ``out`` may be G."""
     if kind not in _ALRP_KINDS:
         raise ValueError(f"alrp_act: kind must be one of {sorted(_ALRP_KINDS)}, got {kind!r}")
-    G, x = _c(G), _c(x)
+    G, (x, name) = _c(G), _alrp_operand(x, "act")
     if G.shape != x.shape:
         raise _lib.TeError(f"alrp_act: G {tuple(G.shape)} and x {tuple(x.shape)} differ in shape")
     out = _alrp_out(out, G, "alrp_act")
-    with _on_device(G) as lib, _timed("alrp_act", 0.0, 12.0 * G.numel()):
-        _lib.check(lib.te_alrp_act_f32(_ptr(G), _ptr(x), _ptr(out), G.numel(), _ALRP_KINDS[kind], _stream(G)),
-                   "te_alrp_act_f32")
+    with _on_device(G) as lib, _timed("alrp_act", 0.0, (8.0 + x.element_size()) * G.numel()):
+        _lib.check(getattr(lib, name)(_ptr(G), _ptr(x), _ptr(out), G.numel(), _ALRP_KINDS[kind], _stream(G)), name)
     return out
 
 
@@ -2683,50 +2689,121 @@ def alrp_scale3(q: Tensor, k: Optional[Tensor] = None, v: Optional[Tensor] = Non
 
 def alrp_row_rstd(x: Tensor, eps: float) -> Tensor:
     """x [..., C] -> fp32 [...]: 1 / sqrt(biased variance of the row + eps), the constant of the LayerNorm rule."""
-    x = _c(x)
+    x, name = _alrp_operand(x, "row_rstd")
     C = x.shape[-1]
     rstd = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
-    with _on_device(x) as lib, _timed("alrp_row_rstd", 0.0, 4.0 * x.numel()):
-        _lib.check(lib.te_alrp_row_rstd_f32(_ptr(x), _ptr(rstd), x.numel() // C, C, float(eps), _stream(x)),
-                   "te_alrp_row_rstd_f32")
+    with _on_device(x) as lib, _timed("alrp_row_rstd", 0.0, float(x.element_size()) * x.numel()):
+        _lib.check(getattr(lib, name)(_ptr(x), _ptr(rstd), x.numel() // C, C, float(eps), _stream(x)), name)
     return rstd
 
 
 def alrp_layernorm(G: Tensor, gamma: Tensor, rstd: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """The LayerNorm rule with rstd held constant: G [..., C], gamma [C], rstd [...] -> rstd (gamma G - mean(gamma G))."""
-    G, gamma, rstd = _c(G), _c(gamma.detach()), _c(rstd)
+    G, (gamma, name), rstd = _c(G), _alrp_operand(gamma.detach(), "layernorm"), _c(rstd)
     C = G.shape[-1]
     if tuple(gamma.shape) != (C,) or rstd.numel() != G.numel() // C:
         raise _lib.TeError(f"alrp_layernorm: G {tuple(G.shape)} needs gamma [{C}] and one rstd per row, got "
                            f"{tuple(gamma.shape)} and {tuple(rstd.shape)}")
     out = _alrp_out(out, G, "alrp_layernorm")
     with _on_device(G) as lib, _timed("alrp_layernorm", 0.0, 8.0 * G.numel()):
-        _lib.check(lib.te_alrp_layernorm_f32(_ptr(G), _ptr(gamma), _ptr(rstd), _ptr(out), G.numel() // C, C, _stream(G)),
-                   "te_alrp_layernorm_f32")
+        _lib.check(getattr(lib, name)(_ptr(G), _ptr(gamma), _ptr(rstd), _ptr(out), G.numel() // C, C, _stream(G)), name)
     return out
 
 
 def alrp_token_relevance(x0: Tensor, G: Tensor, skip_first: bool = False) -> Tensor:
     """x0, G [B,N,C] -> fp32 [B, N - skip_first]: sum_c x0 G per token in fp64, rounded once; skip_first drops token 0."""
-    x0, G = _c(x0), _c(G)
+    (x0, name), G = _alrp_operand(x0, "token_relevance"), _c(G)
     if x0.dim() != 3 or x0.shape != G.shape:
         raise _lib.TeError(f"alrp_token_relevance: x0 and G must both be [B,N,C], got {tuple(x0.shape)} and {tuple(G.shape)}")
     B, N, C = x0.shape
     skip = int(bool(skip_first))
     out = torch.empty((B, N - skip), dtype=torch.float32, device=x0.device)
-    with _on_device(x0) as lib, _timed("alrp_token_relevance", 0.0, 8.0 * x0.numel()):
-        _lib.check(lib.te_alrp_token_relevance_f32(_ptr(x0), _ptr(G), _ptr(out), B, N, C, skip, _stream(x0)),
-                   "te_alrp_token_relevance_f32")
+    with _on_device(x0) as lib, _timed("alrp_token_relevance", 0.0, (4.0 + x0.element_size()) * x0.numel()):
+        _lib.check(getattr(lib, name)(_ptr(x0), _ptr(G), _ptr(out), B, N, C, skip, _stream(x0)), name)
     return out
 
 
-def alrp_linear(G: Tensor, W: Tensor, cache: Optional[dict] = None) -> Tensor:
-    """The Linear rule's product G [..., out] . W [out, in] -> [..., in]: te_gemm_x6_f32 on the cached planes of W^T wherever
-    it takes the shape (gemm_x6_supported; X6_GEMM = "off" switches it off), the stock fp32 GEMM elsewhere -- the two
-    routes of the package's own input-gradient product (producers._Linear.backward).  Whatever USE_FUSED_PRODUCERS says."""
+def alrp_linear_bf16_route(T: int, in_f: int, out_f: int) -> str:
+    """'bf16' (te_attnlrp_linear_bf16: in_f and out_f multiples of 128) or 'fp32-upcast' (the fp32 chain's damp and product on
+    exact fp32 copies of Y and W, on the GPU)."""
+    return "bf16" if _lib.load().te_attnlrp_linear_bf16_supported(int(T), int(in_f), int(out_f)) else "fp32-upcast"
+
+
+def alrp_attention_bf16_route(N: int, D: int) -> str:
+    """'bf16' (te_attnlrp_attention_bf16: head dim 64, N <= 1024) or 'fp32-upcast' (rules.attention_attnlrp's fp32 route on exact
+    fp32 copies of q, k, v and the probabilities, on the GPU)."""
+    return "bf16" if _lib.load().te_attnlrp_attention_bf16_supported(int(N), int(D)) else "fp32-upcast"
+
+
+# The weight side of te_attnlrp_linear_bf16: True: a contiguous bf16 W^T per layer, cached under the _weight_key scheme
+# (2 B per weight element, read along k in 16-byte pieces); False: W read in place through the transposing staging of the
+# GEMM loop (no extra memory).  The same bits either way; DESIGN.md section 3 "AttnLRP" has the measurement behind the default.
+ALRP_WEIGHT_T = True
+
+
+def alrp_weight_t(W: Tensor, cache: Optional[dict] = None) -> Tensor:
+    """The contiguous transpose [in, out] of a bf16 Linear weight [out, in]; cached like x6_weight_planes."""
+    return _cached_planes(W, cache, "alrp_weight_t", lambda Wd: (_c16(Wd).t().contiguous(),))[0]
+
+
+def alrp_linear(G: Tensor, W: Tensor, cache: Optional[dict] = None, Y: Optional[Tensor] = None, eps: float = 0.0) -> Tensor:
+    """The Linear rule's product G [..., out] . W [out, in] -> [..., in].
+    fp32 W (``G`` is damp(G_y, y) already; Y is not given): te_gemm_x6_f32 on the cached planes of W^T wherever it takes the
+    shape (gemm_x6_supported; X6_GEMM = "off" switches it off), the stock fp32 GEMM elsewhere -- the two routes of the
+    package's own input-gradient product (producers._Linear.backward).
+    bf16 W, with the layer's cached bf16 output Y and eps: damp(G, Y) W in one call -- te_attnlrp_linear_bf16 where
+    alrp_linear_bf16_route says 'bf16', else the fp32 route above on exact fp32 copies of Y and W.
+    Whatever USE_FUSED_PRODUCERS says."""
     G = _prep(G)
     out_f, in_f = W.shape
     T = G.numel() // out_f
+    if _is_bf16(W):
+        if not _is_bf16(Y) or Y.shape != G.shape:
+            raise _lib.TeError("alrp_linear: a bf16 W needs the layer's cached bf16 output Y, of G's shape "
+                               f"(got {None if Y is None else (Y.dtype, tuple(Y.shape))} for G {tuple(G.shape)})")
+        if alrp_linear_bf16_route(T, in_f, out_f) != "bf16":
+            return alrp_linear(alrp_damp(G, Y.float(), eps), W.detach().float())
+        W2 = alrp_weight_t(W, cache) if ALRP_WEIGHT_T else _c16(W.detach())
+        G2 = G.reshape(T, out_f)                 # G and Y: rows at a uniform stride are read in place
+        if G2.stride(1) != 1 or (T > 1 and G2.stride(0) < out_f):
+            G2 = G2.contiguous()
+        g_ld = G2.stride(0) if T > 1 else out_f
+        Y2, y_ld = _rows(Y, out_f)
+        out = torch.empty((T, in_f), dtype=torch.float32, device=G.device)
+        with _on_device(G2) as lib, _timed("alrp_linear_bf16", 6.0 * T * in_f * out_f,
+                                           6.0 * T * out_f + 12.0 * T * out_f + 2.0 * in_f * out_f + 4.0 * T * in_f):
+            ws = _ws(lib.te_attnlrp_linear_bf16_workspace_bytes(T, in_f, out_f), G2)
+            _lib.check(lib.te_attnlrp_linear_bf16(_ptr(G2), g_ld, _ptr(Y2), y_ld, _ptr(W2), int(ALRP_WEIGHT_T), _ptr(out), T, in_f, out_f,
+                                               float(eps), _ptr(ws), ws.numel(), _stream(G2)), "te_attnlrp_linear_bf16")
+        return out.reshape(*G.shape[:-1], in_f)
+    if Y is not None:
+        raise _lib.TeError("alrp_linear: Y is an argument of the bf16 route; with an fp32 W pass damp(G, Y) as G")
     if X6_GEMM != "off" and gemm_x6_supported(T, out_f, in_f):
         return gemm_x6(G, x6_matrix_planes(W, True, cache), None, in_f, "alrp_linear_x6")
     return torch.matmul(G, W.detach())
+
+
+def alrp_attention_bf16(G_o: Tensor, q: Tensor, k: Tensor, v: Tensor, attn: Tensor, num_heads: int, scale: float,
+                        d_q: Tensor, d_k: Tensor, d_v: Tensor) -> None:
+    """te_attnlrp_attention_bf16: the attention block's backward for d_out = G_o [B,N,C] fp32 on the bf16 q / k / v ([B,N,C]
+    views, read in place) and probabilities attn [B,H,N,N], written into the fp32 [B,N,C] views d_q / d_k / d_v."""
+    B, N, C = G_o.shape
+    H, D = int(num_heads), C // int(num_heads)
+
+    def view(t, bf16):
+        t = _prep_bf16(t) if bf16 else _prep(t)
+        if tuple(t.shape) != (B, N, C) or t.stride(2) != 1 or t.stride(0) < 0 or t.stride(1) < 0:
+            raise _lib.TeError(f"alrp_attention_bf16: operands and outputs are [B,N,C] views with a contiguous last dimension, "
+                               f"got shape {tuple(t.shape)}, strides {t.stride()}")
+        return t.data_ptr(), t.stride(0), D, t.stride(1)
+
+    G_o = _c(G_o)
+    attn = _c16(attn)
+    if tuple(attn.shape) != (B, H, N, N):
+        raise _lib.TeError(f"alrp_attention_bf16: attn must be [B,H,N,N] = {(B, H, N, N)}, got {tuple(attn.shape)}")
+    args = [*view(G_o, False), *view(q, True), *view(k, True), *view(v, True), _ptr(attn), float(scale),
+            *view(d_q, False), *view(d_k, False), *view(d_v, False)]
+    with _on_device(G_o) as lib, _timed("alrp_attention_bf16", 24.0 * B * H * N * N * D,
+                                        B * H * (22.0 * N * N + 44.0 * N * D)):
+        ws = _ws(lib.te_attnlrp_attention_bf16_workspace_bytes(B, H, N, D), G_o)
+        _lib.check(lib.te_attnlrp_attention_bf16(*args, B, H, N, D, _ptr(ws), ws.numel(), _stream(G_o)), "te_attnlrp_attention_bf16")

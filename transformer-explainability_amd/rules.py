@@ -216,6 +216,8 @@ class Linear(_ScratchCache, nn.Linear, RelProp):
         if Y.shape != G.shape:
             raise ops._lib.TeError(f"Linear.attnlrp: G {tuple(G.shape)} does not have the shape of the cached output "
                                    f"{tuple(Y.shape)}")
+        if ops._is_bf16(self.weight):      # damp and product in one call: the damped G goes to the product as bf16 planes
+            return ops.alrp_linear(G, self.weight, x6_cache(self), Y=Y, eps=eps)
         return ops.alrp_linear(ops.alrp_damp(G, Y, eps), self.weight, x6_cache(self))
 
 
@@ -314,9 +316,20 @@ def attention_attnlrp(G_o, q, k, v, attn, num_heads, scale, d_q, d_k, d_v):
     """The AttnLRP rule of o = softmax(scale q k^T (+ mask)) v for G_o [B,N,C] ('b n (h d)'): the block's own backward for
     d_out = G_o, written into d_q / d_k / d_v ([B,N,C] views, like q / k / v), which the caller then scales by 1/4, 1/4, 1/2
     (ops.alrp_scale3: the uniform rule).  On te_attention_backward_strided_f32 where it takes the shape, else the torch
-    expression of the same backward.  Reads cached tensors only: ops.USE_FUSED_PRODUCERS plays no part."""
+    expression of the same backward.  bf16 q / k / v / attn (a bf16 model; G_o and the results stay fp32):
+    te_attnlrp_attention_bf16 where ops.alrp_attention_bf16_route says 'bf16', else this function's fp32 routes on exact fp32
+    copies of the operands.  Reads cached tensors only: ops.USE_FUSED_PRODUCERS plays no part."""
     B, N, C = G_o.shape
     H, D = num_heads, C // num_heads
+    if any(ops._is_bf16(t) for t in (q, k, v, attn)):
+        if not all(ops._is_bf16(t) for t in (q, k, v, attn)):
+            raise ops._lib.TeError(f"attention_attnlrp: q, k, v and attn must share one dtype, got "
+                                   f"{[t.dtype for t in (q, k, v, attn)]}")
+        if ops.alrp_attention_bf16_route(N, D) == "bf16":
+            ops.alrp_attention_bf16(G_o, q, k, v, attn, H, scale, d_q, d_k, d_v)
+        else:
+            attention_attnlrp(G_o, q.float(), k.float(), v.float(), attn.float(), H, scale, d_q, d_k, d_v)
+        return
     if ops._lib.load().te_attention_strided_supported(N, D):
         ops.attention_backward_qkv(G_o, q, k, v, attn, H, scale, d_q, d_k, d_v, need_qk=True)
         return

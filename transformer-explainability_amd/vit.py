@@ -348,7 +348,7 @@ def make_vit_module(L):
             G_o = self.proj.attnlrp(G, eps)
             B, N, C = G_o.shape
             qkv = self.qkv.Y.detach()
-            d_qkv = torch.empty_like(qkv)
+            d_qkv = torch.empty_like(qkv, dtype=torch.float32)      # (G is fp32 on a bf16 model too)
             third = lambda t, i: t[..., i * C:(i + 1) * C]      # noqa: E731
             R_ours.attention_attnlrp(G_o, third(qkv, 0), third(qkv, 1), third(qkv, 2), self.get_attn().detach(),
                                      self.num_heads, self.scale, third(d_qkv, 0), third(d_qkv, 1), third(d_qkv, 2))
