@@ -1147,6 +1147,47 @@ int te_attnlrp_attention_bf16(const float* G_o, int64_t g_sb, int64_t g_sh, int6
                            float* G_v, int64_t gv_sb, int64_t gv_sh, int64_t gv_sn,
                            int64_t B, int64_t H, int64_t N, int64_t D, void* ws, size_t ws_bytes, te_stream_t stream);
 
+/* ---- AttnLRP, pixel level (csrc/te_attnlrp_patch.hip) -------------------------------------------------------------------
+ * The last step of the chain on a ViT / DeiT: the eps-rule through the patch-embedding convolution, then input x G per pixel
+ * -- an fp32 [B, H, W] map, the shape of the z^B rule's (te_conv2d_zb_relprop_f32).  The convolution has stride == kernel and
+ * no padding, so it is a Linear layer on non-overlapping patches.  Notation: X [B,C,H,W] the image, W [E,C,p,p] the weight
+ * (W.view(E, C p p) is the row-major operand: no transposed copy), P = (H/p)(W_/p) patches per sample; y[b,t,e] the cached
+ * output of the convolution WITH its bias = the patch rows of x0 (the patch embedding before the position embedding is
+ * added), token-major; G[b,t,e] the chain's G at x0 (the position-embedding Add is plain).  Token t = hp (W_/p) + wp covers
+ * the pixels (hp p + i, wp p + j).
+ *     A[b,t,e]               = damp(G[b,t,e], y[b,t,e])     te_alrp_damp_f32's bits; eps == 0: A = G
+ *     acc_c[b,t,i,j]         = the fp32 fma chain over e = 0 .. E-1 ASCENDING of A[b,t,e] W[e,c,i,j], from +0
+ *     out[b, hp p+i, wp p+j] = fp32( sum_c (double)X[b,c,h,w] (double)acc_c ): c ascending from +0.0, every product exact in
+ *                              fp64, every add rounded in fp64, one rounding to fp32
+ * The bias absorbs its share, as in the Linear rule; nothing else is damped; there is no mean or zero-point term: this is
+ * eps-LRP, input x G in the normalised input space.  Conservation: with a zero bias and eps = 0 the sum of out over the pixels
+ * of patch t equals the token relevance sum_e x0[b,t,e] G[b,t,e] (both are sum_e A_e (y_e - b_e)).
+ * An fp32-input MFMA is exactly the k-ordered chain, so the result depends on no tiling decision: the tiled kernel, the
+ * one-thread-per-pixel kernel, a sample alone and the same sample in a batch give the same bits.  No split along e, no
+ * atomics, no workspace.
+ *   G, Y      point at the first PATCH row (a caller that holds [B, P+1, E] tensors adds E to skip the class token); g_bs, y_bs
+ *             >= P E are the batch strides in elements.  G and out are fp32; Y, X, W are fp32 (_f32) or bf16 read exactly
+ *             (_bf16: the _f32 entry's bits on exact fp32 copies, the convention of "AttnLRP, bf16 operands").
+ *   Kernels   te_patch_alrp_relevance_supported(C, E, p) == 1: the tiled kernel (fp32 MFMA 32x32x2; a workgroup owns 64 tokens x
+ *             64 pixel columns (i, j) of every channel, stages G and y through LDS and damps while staging, walks e in chunks
+ *             of 32 once per channel -- G and y are read and damped again on every channel's walk, C times in all -- and folds
+ *             X acc into fp64 pixel sums, c ascending) -- E a multiple of 32, p a multiple of 8,
+ *             any C >= 1, any B, H, W_.  Otherwise, and with flags = TE_IMPL_SIMPLE, one thread per pixel with literal fmaf
+ *             chains: any C, E, p >= 1.
+ *   Alignment pointers on their element's boundary (4 bytes; bf16: 2), TE_ERR_UNSUPPORTED otherwise.  The tiled kernel stages
+ *             G, Y and W in groups of four elements (16 bytes; bf16: 8) where G, Y, W lie on that boundary and g_bs, y_bs are
+ *             multiples of 4, single elements elsewhere: the same bits either way.
+ *   TE_ERR_INVALID_ARG: a null pointer, a size <= 0, H or W_ not a multiple of p, g_bs or y_bs < P E, eps negative, NaN or
+ *             infinite, unknown flag bits.  TE_ERR_UNSUPPORTED: sizes beyond 2^31 - 1 (B P, H W_, C p p, P E).  Every refusal
+ *             comes before the launch. */
+int te_patch_alrp_relevance_supported(int64_t C, int64_t E, int64_t p);
+int te_patch_alrp_relevance_f32(const float* G, int64_t g_bs, const float* Y, int64_t y_bs, const float* X, const float* W,
+                                float* out, int64_t B, int64_t C, int64_t H, int64_t W_, int64_t E, int64_t p, float eps,
+                                int flags, te_stream_t stream);
+int te_patch_attnlrp_relevance_bf16(const float* G, int64_t g_bs, const te_bf16_t* Y, int64_t y_bs, const te_bf16_t* X,
+                                    const te_bf16_t* W, float* out, int64_t B, int64_t C, int64_t H, int64_t W_, int64_t E,
+                                    int64_t p, float eps, int flags, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,26 +22,9 @@ static inline unsigned off16(const void* p) { return (unsigned)(((uintptr_t)p) &
 static inline bool aligned_group(const float* p) { return te_aligned16(p); }
 static inline bool aligned_group(const te_bf16_t* p) { return (((uintptr_t)p) & 7u) == 0; }
 
-// the operand as fp32: one element, and four consecutive ones in one access (element 2j of a bf16 pair in the low half)
-__device__ __forceinline__ float up(float v) { return v; }
-__device__ __forceinline__ float up(te_bf16_t v) { return te_bf16_up(v); }
-__device__ __forceinline__ f32x4 up4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 up4(const te_bf16_t* p) {
-  const u32x2 q = *reinterpret_cast<const u32x2*>(p);
-  return f32x4{__uint_as_float(q[0] << 16), __uint_as_float(q[0] & 0xffff0000u), __uint_as_float(q[1] << 16),
-               __uint_as_float(q[1] & 0xffff0000u)};
-}
-
 // ------------------------------------------------------------------------------------------------ element-wise rules
-// stab(y) = y + eps sgn(y), sgn(+-0) = +1; damp = (g y) / stab(y): one multiply, one add, one IEEE division.  eps == 0: g itself.
-struct DampOp {
-  float eps;
-  __device__ __forceinline__ float operator()(float g, float y) const {
-    if (eps == 0.0f) return g;
-    const float st = y + ((y >= 0.0f) ? eps : -eps);
-    return (g * y) / st;
-  }
-};
+// damp(g, y): the one definition of te_common.h, shared with te_attnlrp_patch.hip
+using DampOp = TeAlrpDamp;
 // the identity rule: g (f(x) / x), f'(0) at x == +-0: one IEEE division, one multiply
 struct ActOp {
   int kind;
@@ -63,7 +46,7 @@ __global__ __launch_bounds__(kThreads) void binary_kernel(const float* a, const 
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i < nvec) {
     const int64_t e = head + 4 * i;
-    const f32x4 va = *reinterpret_cast<const f32x4*>(a + e), vb = up4(b + e);
+    const f32x4 va = *reinterpret_cast<const f32x4*>(a + e), vb = te_up4(b + e);
     f32x4 r;
 #pragma unroll
     for (int j = 0; j < 4; ++j) r[j] = op(va[j], vb[j]);
@@ -72,7 +55,7 @@ __global__ __launch_bounds__(kThreads) void binary_kernel(const float* a, const 
   }
   const int64_t s = i - nvec;
   const int64_t e = (s < head) ? s : s + 4 * nvec;
-  if (e < n) out[e] = op(a[e], up(b[e]));
+  if (e < n) out[e] = op(a[e], te_up(b[e]));
 }
 
 template <class T, class Op>
@@ -140,12 +123,12 @@ __device__ __forceinline__ float wave_row_sum(int lane, int64_t C, Term term) {
 template <bool VEC, class T>
 __device__ __forceinline__ void load_group(const T* __restrict__ p, int64_t c, int64_t C, float (&v)[4]) {
   if constexpr (VEC) {
-    const f32x4 q = up4(p + c);
+    const f32x4 q = te_up4(p + c);
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = q[j];
   } else {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (c + j < C) ? up(p[c + j]) : 0.0f;
+    for (int j = 0; j < 4; ++j) v[j] = (c + j < C) ? te_up(p[c + j]) : 0.0f;
   }
 }
 

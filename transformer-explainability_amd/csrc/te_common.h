@@ -359,6 +359,28 @@ __device__ __forceinline__ void te_load4_f64(const T* __restrict__ p, I e0, I n,
   }
 }
 
+// fp32 / bf16 operands of the fp32 rules (te_attnlrp.hip, te_attnlrp_patch.hip): one element as fp32, and four consecutive
+// ones in one access (element 2j of a bf16 pair in the low half)
+__device__ __forceinline__ float te_up(float v) { return v; }
+__device__ __forceinline__ float te_up(te_bf16_t v) { return te_bf16_up(v); }
+__device__ __forceinline__ f32x4 te_up4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 te_up4(const te_bf16_t* p) {
+  const u32x2 q = *reinterpret_cast<const u32x2*>(p);
+  return f32x4{__uint_as_float(q[0] << 16), __uint_as_float(q[0] & 0xffff0000u), __uint_as_float(q[1] << 16),
+               __uint_as_float(q[1] & 0xffff0000u)};
+}
+
+// AttnLRP (te_relprop.h, section "AttnLRP"): stab(y) = y + eps sgn(y), sgn(+-0) = +1; damp = (g y) / stab(y): one multiply, one
+// add, one IEEE division.  eps == 0: g itself.  te_alrp_damp_f32's bits wherever a kernel damps while it stages.
+struct TeAlrpDamp {
+  float eps;
+  __device__ __forceinline__ float operator()(float g, float y) const {
+    if (eps == 0.0f) return g;
+    const float st = y + ((y >= 0.0f) ? eps : -eps);
+    return (g * y) / st;
+  }
+};
+
 // Patch geometry of a stride == kernel convolution (ViT patch embedding): row t = (b, py, px) of the im2col matrix,
 // column k = (c, dy, dx); te_zb_index maps (t, k) to the element's offset in the NCHW image.
 struct TeZbGeom {

@@ -386,24 +386,30 @@ class LRP(_PassDriver):
         name = self.model.default_method if method is None else method
         return self._pass(input, (name,), index, is_ablation, start_layer, head_mask, self._SINGLE_CALL_NEED, pruned)[name]
 
-    def generate_attnlrp(self, input, index=None, eps=1e-6, head_mask=None):
+    def generate_attnlrp(self, input, index=None, eps=1e-6, head_mask=None, method="tokens"):
         """(extension) AttnLRP (Achtibat et al., ICML 2024; the rules: te_relprop.h, section "AttnLRP") -> fp32 [B, N-1],
         the shape of generate_LRP: the relevance of the patch tokens for the class ``index`` (None: the per-sample argmax).
         One forward pass, no backward pass, one chain; ``eps`` (>= 0) stabilises the Linear and residual-Add rules.  float32
         models, and bfloat16 models with bfloat16 images on the GPU (the chain in fp32 on the cached bf16 tensors), in eval
         mode; fp16 / fp64 models, a mix of bf16 and fp32, train mode and ``head_mask`` raise TeError before the forward
-        pass.  The x6 status poll / post as in generate_LRP; capturable by GraphedCall."""
+        pass.  The x6 status poll / post as in generate_LRP; capturable by GraphedCall.
+        method="full": the same chain, then the eps-rule through the patch embedding and input x G per pixel (te_relprop.h,
+        "AttnLRP, pixel level") -> fp32 [B, H, W], the shape of generate_LRP(method="full").  Any other name than "tokens" /
+        "full" is a ValueError before the forward pass."""
         with _x6_bracket(input):
-            return self._attnlrp(input, index, eps, head_mask)
+            return self._attnlrp(input, index, eps, head_mask, method)
 
-    def _attnlrp(self, input, index=None, eps=1e-6, head_mask=None):
+    def _attnlrp(self, input, index=None, eps=1e-6, head_mask=None, method="tokens"):
         """generate_attnlrp without the x6 bracket."""
+        if method not in ("tokens", "full"):
+            raise ValueError(f"generate_attnlrp: method must be 'tokens' (patch tokens, [B, N-1]) or 'full' (pixels, [B,H,W]), "
+                             f"got {method!r}")
         _refuse_attnlrp(self.model, eps, head_mask, input)
         with torch.no_grad():
             output = self.model(input)
             _drop_rule_planes(self.model)
             seed = _one_hot(output, index)
-            return self._gradients_and_chain(output, [], lambda: self.model.attnlrp(seed, eps=eps))
+            return self._gradients_and_chain(output, [], lambda: self.model.attnlrp(seed, eps=eps, method=method))
 
     def generate_all(self, input, methods, index=None, is_ablation=False, start_layer=0, head_mask=None):
         """(extension) The maps of several methods of the SAME batch from one pass: ``methods`` is any subset of the

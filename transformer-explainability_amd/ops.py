@@ -2723,6 +2723,47 @@ def alrp_token_relevance(x0: Tensor, G: Tensor, skip_first: bool = False) -> Ten
     return out
 
 
+def alrp_patch_route(C: int, E: int, p: int) -> str:
+    """'tiled' (the fp32-MFMA kernel of csrc/te_attnlrp_patch.hip: E a multiple of 32, p a multiple of 8) or 'simple' (one
+    thread per pixel, any shape).  The same bits either way."""
+    return "tiled" if _lib.load().te_patch_alrp_relevance_supported(int(C), int(E), int(p)) else "simple"
+
+
+def alrp_patch_relevance(G: Tensor, x0: Tensor, X: Tensor, W: Tensor, eps: float = 1e-6, simple: bool = False) -> Tensor:
+    """The eps-rule through a patch-embedding convolution, then input x G per pixel (te_relprop.h, "AttnLRP, pixel level"):
+    G fp32 and x0 [B, P+1, E] (the chain's G at x0 and the cached patch embedding, class token in row 0, which is skipped),
+    X [B,C,H,W] the image, W [E,C,p,p] the weight -> fp32 [B,H,W].  x0, X, W are all fp32 or all bf16 (read exactly: the
+    fp32 call's bits on exact copies); ``simple`` forces the one-thread-per-pixel kernel (the same bits)."""
+    dtypes = {"x0": x0.dtype, "X": X.dtype, "W": W.dtype}
+    if len(set(dtypes.values())) != 1:
+        raise _lib.TeError("alrp_patch_relevance: x0, X and W must share one dtype (all float32 or all bfloat16), got "
+                           + ", ".join(f"{n}: {d}" for n, d in dtypes.items()))
+    bf16 = _is_bf16(W)
+    prep = _prep_bf16 if bf16 else _prep
+    G, x0, X, W = _prep(G), prep(x0), _c16(X) if bf16 else _c(X), _c16(W.detach()) if bf16 else _c(W.detach())
+    if X.dim() != 4 or W.dim() != 4 or W.shape[2] != W.shape[3] or W.shape[1] != X.shape[1]:
+        raise _lib.TeError(f"alrp_patch_relevance: not a patch convolution: X {tuple(X.shape)}, W {tuple(W.shape)}")
+    (B, C, H, Wd), (E, p) = X.shape, (W.shape[0], W.shape[2])
+    if H % p or Wd % p:
+        raise _lib.TeError(f"alrp_patch_relevance: the image {H} x {Wd} is not a whole number of {p} x {p} patches")
+    P = (H // p) * (Wd // p)
+    if tuple(G.shape) != (B, P + 1, E) or tuple(x0.shape) != (B, P + 1, E):
+        raise _lib.TeError(f"alrp_patch_relevance: G {tuple(G.shape)} and x0 {tuple(x0.shape)} must both be [B, P+1, E] = "
+                           f"{(B, P + 1, E)}")
+    # token-major rows read in place behind the class token; any batch stride
+    rows = lambda t: t if (t.stride(2) == 1 and t.stride(1) == E and t.stride(0) >= (P + 1) * E) else t.contiguous()  # noqa: E731
+    G, x0 = rows(G), rows(x0)
+    name = "te_patch_attnlrp_relevance_bf16" if bf16 else "te_patch_alrp_relevance_f32"
+    out = torch.empty((B, H, Wd), dtype=torch.float32, device=X.device)
+    T, K, es = B * P, C * p * p, X.element_size()
+    with _on_device(X) as lib, _timed("alrp_patch_relevance", 2.0 * T * E * K + 2.0 * T * K,
+                                      (4.0 + es) * T * E + es * (E * K + T * K) + 4.0 * T * p * p):
+        _lib.check(getattr(lib, name)(G.data_ptr() + 4 * E, G.stride(0), x0.data_ptr() + es * E, x0.stride(0), _ptr(X), _ptr(W),
+                                      _ptr(out), B, C, H, Wd, E, p, float(eps),
+                                      TE_IMPL_SIMPLE if (simple or FORCE_SIMPLE) else 0, _stream(X)), name)
+    return out
+
+
 def alrp_linear_bf16_route(T: int, in_f: int, out_f: int) -> str:
     """'bf16' (te_attnlrp_linear_bf16: in_f and out_f multiples of 128) or 'fp32-upcast' (the fp32 chain's damp and product on
     exact fp32 copies of Y and W, on the GPU)."""

@@ -507,3 +507,17 @@ class Conv2d(_ScratchCache, nn.Conv2d, RelProp):
             # a bf16 layer: conv(X, W) is recomputed from the bf16 operands; its rounded output self.Y is not read
             return ops.conv2d_zb_relprop_bf16(R, self.X, self.weight.detach(), cache=x6_cache(self))
         return ops.conv2d_zb_relprop(R, self.X, self.weight, self.Y, self.bias)
+
+    def attnlrp(self, G_tokens, x0, eps):
+        """AttnLRP through the patch embedding, then input x G per pixel (te_relprop.h, "AttnLRP, pixel level"): G_tokens and
+        x0 [B, P+1, E] (the chain's G at x0 and the cached patch embedding, the class token in row 0) -> fp32 [B,H,W].  The
+        geometry test of relprop without the 3-channel condition; reads the layer's cached input X."""
+        k = self.kernel_size
+        patch = (k[0] == k[1] and tuple(self.stride) == tuple(k) and tuple(self.padding) == (0, 0)
+                 and tuple(self.dilation) == (1, 1) and self.groups == 1)
+        if not patch:
+            raise NotImplementedError(f"Conv2d.attnlrp: only a patch-embedding convolution (square kernel, stride == kernel, no "
+                                      f"padding, no dilation, one group) has a pixel rule; got kernel {tuple(k)}, stride "
+                                      f"{tuple(self.stride)}, padding {tuple(self.padding)}, dilation {tuple(self.dilation)}, "
+                                      f"groups {self.groups}")
+        return ops.alrp_patch_relevance(G_tokens, x0, self.X.detach(), self.weight.detach(), eps)

@@ -448,6 +448,10 @@ def make_vit_module(L):
             cam = cam.unflatten(1, (self.img_size[0] // self.patch_size[0], self.img_size[1] // self.patch_size[1]))
             return self.proj.relprop(cam.permute(0, 3, 1, 2), **kwargs)
 
+        def attnlrp(self, G, x0, eps):
+            """G, x0 [B, P+1, E] token-major (class token first) -> fp32 [B,H,W]: the kernel reads the token rows in place."""
+            return self.proj.attnlrp(G, x0, eps)
+
     class VisionTransformer(nn.Module):
         default_method = "transformer_attribution" if L.RelProp.variant == "ours" else "grad"
 
@@ -563,14 +567,19 @@ def make_vit_module(L):
             maps = {m: relprop_tail(self, m, cam, is_ablation, start_layer, prune, **kwargs) for m in wanted}
             return maps if several else maps[method]
 
-        def attnlrp(self, seed, eps=1e-6):
+        def attnlrp(self, seed, eps=1e-6, method="tokens"):
             """(extension) AttnLRP (te_relprop.h, section "AttnLRP"): ``seed`` [B, num_classes] (the one-hot of the class) ->
             fp32 [B, N-1], the relevance of the patch tokens.  One chain over the caches of the last forward pass; no
-            backward pass.  The position-embedding Add is a parameter Add: plain."""
+            backward pass.  The position-embedding Add is a parameter Add: plain.  method="full": the same chain, then the
+            eps-rule through the patch embedding and input x G per pixel ("AttnLRP, pixel level") -> fp32 [B,H,W]."""
+            if method not in ("tokens", "full"):
+                raise ValueError(f"attnlrp: method must be 'tokens' or 'full', got {method!r}")
             G = self.head.attnlrp(seed, eps)
             G = self.norm.attnlrp(self.pool.attnlrp(G, eps), eps)
             for blk in reversed(self.blocks):
                 G = blk.attnlrp(G, eps)
+            if method == "full":
+                return self.patch_embed.attnlrp(G, self.add.X[0], eps)
             return ops.alrp_token_relevance(self.add.X[0], G, skip_first=True)
 
     def vit_base_patch16_224(pretrained=False, **kwargs):
