@@ -177,6 +177,44 @@ def check_groups(name, got, ref32, ref64, group_dims, base_tol):
     return s
 
 
+def check_producer_groups(name, got, stock, ref64, group_dims, tol, xmax=None, scale_floor=None, sink=None):
+    """check_groups for a PRODUCER (a kernel with a stock torch counterpart), the form of test_layernorm_per_row: for every
+    group g, against the fp64 chain,
+        err_g <= 2 x err_stock_g + (tol + 4 x 2^-24 x xmax_g) x scale_g ,     scale_g = max(max|ref64| of g, scale_floor_g)
+    with err_stock_g the error of the stock chain in the operands' dtype and xmax_g the largest score magnitude that decides
+    the group (None: no score enters the output).  xmax and scale_floor are shaped like the groups.  No group is left out; a
+    group whose bound is zero must be exactly right.  The worst err / bound, its group and the stock chain's worst
+    err / scale go to the parity report -- as a line of their own, or into the dict `sink` under `name` for a caller that
+    writes one line per test."""
+    assert tuple(got.shape) == tuple(stock.shape) == tuple(ref64.shape), (name, got.shape, stock.shape, ref64.shape)
+    finite = bool(torch.isfinite(got).all())
+    err, scale, err_stock, _ = group_stats(torch.nan_to_num(got.detach().cpu().double(), 0.0, 0.0, 0.0), stock, ref64, group_dims)
+    if scale_floor is not None:
+        scale = torch.maximum(scale, scale_floor.detach().cpu().double())
+    rel = torch.full_like(scale, float(tol))
+    if xmax is not None:
+        rel = rel + 4.0 * 2.0 ** -24 * xmax.detach().cpu().double()
+    bound = 2.0 * err_stock + rel * scale
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")),
+                                                                             torch.zeros_like(err)))
+    worst = int(ratio.argmax())
+    widx = [int(i) for i in torch.unravel_index(torch.tensor(worst), ratio.shape)] if ratio.dim() else []
+    live = scale > 0
+    sratio = torch.where(live, err_stock / scale.clamp_min(1e-300), torch.zeros_like(err))
+    s = dict(groups=int(ratio.numel()), worst_over_bound=float(ratio.max()), worst_group=widx,
+             worst_group_err=float(err.flatten()[worst]), worst_group_scale=float(scale.flatten()[worst]),
+             worst_group_stock_err=float(err_stock.flatten()[worst]), stock_worst_ratio=float(sratio.max()),
+             worst_ratio=float(torch.where(live, err / scale.clamp_min(1e-300), torch.zeros_like(err)).max()), tol=float(tol),
+             finite=finite)
+    if sink is None:
+        record(name, **s)
+    else:
+        sink[name] = s
+    assert finite, (name, s)
+    assert s["worst_over_bound"] <= 1.0, (name, s)
+    return s
+
+
 from oracle.model_cache import bert_cache_from_model, vit_cache_from_model  # noqa: E402,F401
 
 
