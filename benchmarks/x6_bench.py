@@ -8,6 +8,7 @@ a half batch bit for bit (rows independent of the stream-K cut), no expired hand
     python benchmarks/x6_bench.py [--config vit_b16|vit_l16|bert_base|all] [--iters 20] [--check-rows 1024]
     python benchmarks/x6_bench.py --zpass-ab [--config vit_b16] [--iters 40]
     python benchmarks/x6_bench.py --schedule-ab [--config vit_b16] [--iters 30] [--pin 2]
+    python benchmarks/x6_bench.py --ragged-ab [--iters 30] [--pin 2]
 
 --zpass-ab: the Z-pass alone on the planes of |X| (MODE_Z) against the Z-pass on the signed planes of X
 (TE_X6_X_PLANES_SIGNED: the sign is applied while the activation blocks are staged), per shape and tile geometry, the two
@@ -15,6 +16,8 @@ variants alternating launch by launch in one process; `out` of the whole rule co
 --schedule-ab: every x6 launch of a layer (Z-pass, C-pass, forward and input-gradient product) under the schedule the cost rule
 picks, the slack rule before it (TE_X6_SLACK_RULE), whole tiles claimed (TE_X6_WHOLE_TILES) and in static ranges
 (+ TE_X6_STATIC_TILES): what te_linear_x6_schedule says each would do, us per launch, us per K16 step, CU-time.
+--ragged-ab: the same four launches of every ViT-B layer at T = 12 544 (49 full tile columns of 256 rows), 12 608 (ViT-B batch 64:
+the last column holds 64 live rows) and 12 800 (50 full columns), alternating launch by launch: what a ragged column costs.
 """
 import argparse
 import json
@@ -262,6 +265,77 @@ def schedule_ab(T, lname, in_f, out_f, iters, dev, pin):
     return rows
 
 
+RAGGED_TS = (12544, 12608, 12800)      # 49 full tile columns of 256 rows, ViT-B batch 64 (49.25), 50 full columns
+
+
+def ragged_ab(lname, in_f, out_f, iters, dev, pin):
+    """us per launch of the four x6 launches of a layer at 49 full tile columns, at the 49.25 of ViT-B batch 64 and at 50 full columns,
+    the three row counts alternating launch by launch in one process.  `position` = (t[12608] - t[12544]) / (t[12800] - t[12544]):
+    1 where the ragged column costs what a full one costs, 0.25 where it costs its live rows."""
+    lib = _lib.load()
+    Tmax = max(RAGGED_TS)
+    assert all(T % 32 == 0 for T in RAGGED_TS)      # (the planes of the first T rows are then the first blocks of the planes of Tmax rows)
+    X, W, b, R, Y = operands(Tmax, in_f, out_f, 1, dev)
+    st = torch.cuda.current_stream().cuda_stream
+    wp = ops.x6_weight_planes(W)
+    status = ops.x6_status(dev)
+
+    def planes_of(A, rows, K, transposed=0):
+        nb = lib.te_linear_x6_planes_bytes(rows, K)
+        p = torch.empty(nb, dtype=torch.uint8, device=dev)
+        _lib.check(lib.te_linear_x6_split_matrix_f32(A.data_ptr(), rows, K, transposed, p.data_ptr(), nb, st), "split_matrix")
+        return p
+
+    xs = planes_of(X, Tmax, in_f)
+    # (a workspace per row count: where the S planes lie depends on T, and a C-pass reads those of its own Z-pass)
+    wss = {T: torch.zeros(lib.te_linear_relprop_x6_workspace_bytes(T, in_f, out_f), dtype=torch.uint8, device=dev) for T in RAGGED_TS}
+    out = torch.empty((Tmax, in_f), dtype=torch.float32, device=dev)
+
+    def rule(T, phase):
+        ws = wss[T]
+        _lib.check(lib.te_linear_relprop_x6_f32(R.data_ptr(), None, 0, 1, X.data_ptr(), W.data_ptr(), wp.data_ptr(), xs.data_ptr(),
+                                                Y.data_ptr(), b.data_ptr(), out.data_ptr(), T, in_f, out_f,
+                                                pin | ops.TE_X6_X_PLANES_SIGNED | phase, status.data_ptr(), ws.data_ptr(), ws.numel(), st),
+                   "te_linear_relprop_x6_f32")
+
+    prods = {"forward": (xs, planes_of(W, out_f, in_f), in_f, out_f, b),
+             "input-gradient": (planes_of(R, Tmax, out_f), planes_of(W, in_f, out_f, 1), out_f, in_f, None)}
+    gws = {k: torch.zeros(lib.te_gemm_x6_workspace_bytes(Tmax, K, M), dtype=torch.uint8, device=dev) for k, (_, _, K, M, _) in prods.items()}
+    gout = {k: torch.empty((Tmax, M), dtype=torch.float32, device=dev) for k, (_, _, K, M, _) in prods.items()}
+
+    def product(k, T):
+        xp, wpl, K, M, bias = prods[k]
+        _lib.check(lib.te_gemm_x6_f32(None, xp.data_ptr(), wpl.data_ptr(), None if bias is None else bias.data_ptr(), gout[k].data_ptr(),
+                                      T, K, M, pin, status.data_ptr(), gws[k].data_ptr(), gws[k].numel(), st), "te_gemm_x6_f32")
+
+    for T in RAGGED_TS:            # the whole rule once per row count: warm-up, and the S planes the C-pass launches read
+        rule(T, 0)
+    launches = {"Z-pass": lambda T: rule(T, ops.TE_X6_PHASE_Z), "C-pass": lambda T: rule(T, ops.TE_X6_PHASE_C),
+                "forward product": lambda T: product("forward", T), "input-gradient product": lambda T: product("input-gradient", T)}
+    rows = []
+    for name, launch in launches.items():
+        ev = {T: [] for T in RAGGED_TS}
+        for it in range(iters + 3):
+            for T in RAGGED_TS:
+                if name == "Z-pass":
+                    rule(T, ops.TE_X6_PHASE_SPLIT)           # (planes given: this phase only resets the hand-over flags)
+                a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                launch(T)
+                e.record()
+                if it >= 3:
+                    ev[T].append((a, e))
+        torch.cuda.synchronize()
+        us = {T: sorted(a.elapsed_time(e) * 1e3 for a, e in v) for T, v in ev.items()}
+        med = {T: v[len(v) // 2] for T, v in us.items()}
+        lo, mid, hi = (med[T] for T in RAGGED_TS)
+        rows.append(dict(layer=lname, launch=name, **{f"us_med_{T}": round(med[T], 1) for T in RAGGED_TS},
+                         **{f"us_spread_{T}": round(us[T][-1] - us[T][0], 1) for T in RAGGED_TS},
+                         position=round((mid - lo) / (hi - lo), 2) if hi > lo else None))
+    assert int(status[0].item()) == 0
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="vit_b16")
@@ -273,10 +347,17 @@ def main():
     ap.add_argument("--schedule-ab", action="store_true",
                     help="the four x6 launches of every layer under the schedule variants (slack rule, cost rule, whole tiles claimed / static)")
     ap.add_argument("--pin", type=int, default=2, help="--schedule-ab: TE_X6_TILE_* pin (2 = what bench.py pins under concurrent streams)")
+    ap.add_argument("--ragged-ab", action="store_true",
+                    help="the four x6 launches of every ViT-B layer at 49, 49.25 and 50 tile columns of activation rows (--pin as --schedule-ab)")
     a = ap.parse_args()
     _lib.require_device()
     dev = torch.device("cuda:0")
     names = list(CONFIGS) if a.config == "all" else a.config.split(",")
+    if a.ragged_ab:
+        for (lname, in_f, out_f) in CONFIGS["vit_b16"][1]:
+            for r in ragged_ab(lname, in_f, out_f, a.iters, dev, a.pin):
+                print("RAGGED " + json.dumps(r), flush=True)
+        return
     if a.schedule_ab:
         for name in names:
             T, shapes = CONFIGS[name]

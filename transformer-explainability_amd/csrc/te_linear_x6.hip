@@ -382,7 +382,9 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave / NWN, wn = wave % NWN;
+  // Wave -> block of the tile: the NWM waves of one 64-row activation column are CONSECUTIVE waves, i.e. they sit on different
+  // SIMDs (wave w runs on SIMD w % 4), and the activation blocks a wave stages (wave * PBW ...) are those of its own column.
+  const int wm = wave % NWM, wn = wave / NWM;
   const int lane16 = lane * 16;
 
   // ---- this workgroup's range of the (tile, K-step) space: whole tiles per XCD, equal ranges inside one ----
@@ -445,6 +447,11 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
     } else {
       tn = tile / p.ntm, tm = tile - tn * p.ntm;
     }
+    // A ragged tile (fewer than TT live rows): a wave whose whole 64-row column lies at or beyond T is DEAD for this tile -- nothing it
+    // would compute is ever stored.  It stages its weight-side block and keeps every barrier, and does nothing else: no activation
+    // loads (the blocks it would stage are those of its own column), no fragment reads, no MFMAs, no hand-over traffic, no epilogue.
+    // Wave-uniform, and the same on both sides of a cut.
+    const bool dead = (int64_t)tn * GEO::TT + wn * 64 >= p.T;
 
     // ---- what this wave stages per step: the three planes of ONE weight-side 32-row block [one sign] and of PBW
     //      activation-side blocks -- each 3 KiB contiguous in memory and in the stage; wave-uniform pointers ----
@@ -467,6 +474,11 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
     // stage through sign_and_store after the step's MFMAs: each block is fixed once per workgroup, by the wave that stages it,
     // and the pinned read / MFMA body below is that of MODE_Z.
     u32x4 breg[SGN ? PBW : 1][3];
+    auto stage_a = [&](int stg, int adv) __attribute__((always_inline)) {       // the weight side alone: all a dead wave stages
+      srcA += adv * (G * kFrag);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) glds16(srcA + q * kFrag + lane16, ldsA + stg * STAGE + q * kFrag);
+    };
     auto stage_in = [&](int stg, int adv) __attribute__((always_inline)) {
       srcA += adv * (G * kFrag);
 #pragma unroll
@@ -532,7 +544,9 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
       // workgroup ORs the caller's sticky status word and its pass's error word and continues from NaN accumulators, so
       // the C-pass / plain-GEMM outputs of the tile are NaN (the Z-pass then takes its exact fallback for every element
       // of the tile: correct values, slowly).  Once any workgroup of any launch has failed, later waits give up at once.
+      // (a dead wave keeps the wait's barrier and skips the loads, as the publishing side skipped the stores)
       const bool handed_over = wait_for(p.flags + bid - 8);
+      if (!dead) {
       const f32x4* ip = reinterpret_cast<const f32x4*>(in_part) + (size_t)wave * (GEO::ACC / 4) * 64 + lane;
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
@@ -547,6 +561,7 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
           ip += 4 * 64;
           asm volatile("" : "+v"(ip));      // one running pointer, not 32 precomputed ones
         }
+      }
     } else {
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
@@ -557,9 +572,21 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
     }
 
     // ---- main loop: stage ks + 1 lands while stage ks is multiplied ----
+    int st = 0;
+    if (dead) {
+      // the same waits and barriers, step for step, around the weight-side loads alone.  Nothing is requested in the last step: a
+      // dead wave goes straight on to the epilogue's barrier, behind which the live waves reuse the stages, so no load of its own
+      // may still be on its way into them.
+      stage_a(0, 0);
+      for (int ks = k0; ks < k1; ++ks) {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        if (ks + 1 < k1) stage_a((st + 1) % kStages, 1);
+        st = (st + 1 == kStages) ? 0 : st + 1;
+      }
+    } else {
     stage_in(0, 0);
     if constexpr (SGN) sign_and_store(0);
-    int st = 0;
     bf16x8 a[MI][3], b[2][3];
     for (int ks = k0; ks < k1; ++ks) {
       // This step's stage has landed (own loads: vmcnt; every wave's: the barrier), and the stage of step ks - 1 is free
@@ -664,12 +691,14 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
       if constexpr (SGN) sign_and_store((st + 1) % kStages);
       st = (st + 1 == kStages) ? 0 : st + 1;
     }
+    }
     // (the last step staged itself again: those writes are in the LDS before the epilogue's barrier lets anything reuse the stages)
     if constexpr (SGN) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
     // ---- accumulators to memory + flag (guide: plain stores -> vmcnt(0) -> barrier -> release -> flag) ----
     auto publish = [&](float* dst, unsigned* flag) __attribute__((always_inline)) {
       f32x4* op = reinterpret_cast<f32x4*>(dst) + (size_t)wave * (GEO::ACC / 4) * 64 + lane;
+      if (!dead) {
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -684,6 +713,7 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
           op += 4 * 64;
           asm volatile("" : "+v"(op));
         }
+      }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (threadIdx.x == 0) {
@@ -702,7 +732,10 @@ __global__ __launch_bounds__(X6Geo<WM>::THREADS, X6Geo<WM>::WPS) void x6_kernel(
     // The loads of a block are issued as one batch BEFORE the previous block's stores (hipcc keeps loads behind stores
     // that may alias, and a store then costs a full round trip per `s_waitcnt vmcnt`): first light of this kernel spent
     // 110 us per tile in a load -> wait -> store -> wait chain.
-    if constexpr (IS_Z) {
+    if (dead) {
+      // the barrier of the staged Z epilogue below ("the stages are free"); everything else there is private to its wave
+      if constexpr (X6Lds<WM, MODE>::STAGED) __builtin_amdgcn_s_barrier();
+    } else if constexpr (IS_Z) {
       const int nksS = p.out_f >> 4;
       int64_t tl[2];
       bool live[2], blk[2];
