@@ -1188,6 +1188,53 @@ int te_patch_attnlrp_relevance_bf16(const float* G, int64_t g_bs, const te_bf16_
                                     const te_bf16_t* W, float* out, int64_t B, int64_t C, int64_t H, int64_t W_, int64_t E,
                                     int64_t p, float eps, int flags, te_stream_t stream);
 
+/* ---- AttnLRP, a class axis (csrc/te_attnlrp.hip) ------------------------------------------------------------------------
+ * The chain is linear in the seed: every rule is G_in = (something of the cached activations) . G_out, and the cached
+ * operands do not depend on the class.  K classes of the same inputs therefore share ONE forward pass and one read of every
+ * cached operand: G carries a leading class axis.
+ *   G and out are [K, *shape], class-major and contiguous; the cached operand of a rule has `shape` and is shared by the K
+ *   slices.  SPECIFICATION: for every k, slice k of a rule's output has the bits of the entry without a class axis (above)
+ *   on (G[k], operand) -- the same operations in the same order per element, the same lane order per row, the same fp64
+ *   order per token.  K = 1 is that entry, bit for bit.
+ * Because te_gemm_x6_f32 and the row / token kernels give a row the same bits alone and in a batch, the map of class k from
+ * a chain with a class axis has the bits of the chain of that class alone wherever "a batch equals its samples" holds for
+ * the single chain: every product on this library's kernels, and one-hot seeds at a stock head product.  Not covered:
+ * general seeds where the head's product runs on the stock GEMM (its order may depend on the number of rows), and shapes
+ * whose Linear products run on the stock GEMM.
+ *   te_alrpk_damp_f32             out[k][i] = (G[k][i] Y[i]) / stab(Y[i]), Y [n]: an item is one 16-byte group of Y (or one
+ *                                 element); it loads Y and forms stab(Y) ONCE, then walks k: load G[k], one multiply, one IEEE
+ *                                 division, store out[k].  eps == 0: out = G.  out == G is allowed.  Vectors where G, Y and
+ *                                 out share one 16-byte phase AND the class stride n is a multiple of 4 (or K == 1); single
+ *                                 elements elsewhere; the same bits either way.
+ *   te_alrpk_act_f32              out[k][i] = G[k][i] r_i, r_i = f(x[i]) / x[i] or f'(0) formed ONCE per element (the GELU /
+ *                                 tanh evaluation and the division); per class one multiply.  Items and vectors as above.
+ *   te_alrpk_layernorm_f32        G, out [K, rows, C], gamma [C], rstd [rows] (te_alrp_row_rstd_f32, computed once, not K times):
+ *                                 one wave per operand row r, which walks k; per (k, r) the loads, LANE ORDER and shuffle tree
+ *                                 of te_alrp_layernorm_f32.  out == G is allowed.
+ *   te_alrpk_token_relevance_f32  x0 [B,N,C], G [K,B,N,C] -> out [B, K, N - skip_first]: batch-major, the layout the callers
+ *                                 return, so no permuted copy follows.  Per (k, b, t) the fp64 order of
+ *                                 te_alrp_token_relevance_f32.
+ *   _bf16: the operand (Y, x, gamma, x0) is bf16, read exactly: the _f32 entry's bits on an exact fp32 copy, the convention
+ *   of "AttnLRP, bf16 operands".
+ * te_alrp_scale3_f32 runs on K T rows and te_alrp_row_rstd_f32 has no class dependence: neither has a class form.  The Linear
+ * product is one te_gemm_x6_f32 over the K T rows (bf16: K calls of te_attnlrp_linear_bf16), the attention rule K calls of
+ * its entry.
+ * Alignment and refusals as for the entries without a class axis, all before the launch.  TE_ERR_INVALID_ARG: a null pointer,
+ * K <= 0, a size <= 0, eps negative, NaN or infinite, an unknown kind, skip_first not 0 or 1, N - skip_first == 0.
+ * TE_ERR_UNSUPPORTED: a pointer off its element's boundary, sizes beyond the grid limit (2^31 - 1 workgroups; K, C). */
+int te_alrpk_damp_f32(const float* G, const float* Y, float* out, int64_t K, int64_t n, float eps, te_stream_t stream);
+int te_alrpk_damp_bf16(const float* G, const te_bf16_t* Y, float* out, int64_t K, int64_t n, float eps, te_stream_t stream);
+int te_alrpk_act_f32(const float* G, const float* x, float* out, int64_t K, int64_t n, int kind, te_stream_t stream);
+int te_alrpk_act_bf16(const float* G, const te_bf16_t* x, float* out, int64_t K, int64_t n, int kind, te_stream_t stream);
+int te_alrpk_layernorm_f32(const float* G, const float* gamma, const float* rstd, float* out, int64_t K, int64_t rows,
+                           int64_t C, te_stream_t stream);
+int te_alrpk_layernorm_bf16(const float* G, const te_bf16_t* gamma, const float* rstd, float* out, int64_t K, int64_t rows,
+                            int64_t C, te_stream_t stream);
+int te_alrpk_token_relevance_f32(const float* x0, const float* G, float* out, int64_t K, int64_t B, int64_t N, int64_t C,
+                                 int skip_first, te_stream_t stream);
+int te_alrpk_token_relevance_bf16(const te_bf16_t* x0, const float* G, float* out, int64_t K, int64_t B, int64_t N, int64_t C,
+                                  int skip_first, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

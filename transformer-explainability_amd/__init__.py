@@ -10,6 +10,7 @@ directory name carries a hyphen).  Layout:
   vit.py, bert.py                   LRP-instrumented models = baselines/ViT/ViT_LRP.py, BERT.py ... of the reference
   generators.py                     LRP.generate_LRP / Generator.generate_LRP; generate_all: several methods, one pass
                                     generate_attnlrp: AttnLRP, a second method (one forward pass, one chain, no backward pass)
+                                    generate_attnlrp_classes: AttnLRP for K classes, one forward pass, one chain with a class axis
   methods.py                        what each method's tail reads after the forward pass (the table generate_all plans by)
   dropin/                           the reference's import paths (modules.layers_ours, baselines.ViT.ViT_LRP, ...)
   parallel.py                       one-process-per-GPU sharding + RCCL gather of the finished maps

@@ -238,9 +238,11 @@ def make_bert_module(L):
             if self.head_mask is not None:
                 raise ops._lib.TeError("BertSelfAttention.attnlrp: head_mask is not implemented for AttnLRP")
             q, k, v = self.query.Y.detach(), self.key.Y.detach(), self.value.Y.detach()
-            d_q, d_k, d_v = (torch.empty_like(t, dtype=torch.float32) for t in (q, k, v))      # (G is fp32 on a bf16 model too)
-            R_ours.attention_attnlrp(G_o, q, k, v, self.get_attn().detach(), self.num_attention_heads,
-                                     1.0 / math.sqrt(self.attention_head_size), d_q, d_k, d_v)
+            classes = G_o.dim() == q.dim() + 1      # [K,B,N,C]: the rule per class into the slices of three [K,B,N,C] gradients
+            d_q, d_k, d_v = (torch.empty(G_o.shape, dtype=torch.float32, device=G_o.device) for _ in range(3))      # (fp32 on a bf16 model too)
+            for g_o, dq, dk, dv in (zip(G_o, d_q, d_k, d_v) if classes else ((G_o, d_q, d_k, d_v),)):
+                R_ours.attention_attnlrp(g_o, q, k, v, self.get_attn().detach(), self.num_attention_heads,
+                                         1.0 / math.sqrt(self.attention_head_size), dq, dk, dv)
             ops.alrp_scale3(d_q, d_k, d_v)
             return self.clone.attnlrp((self.query.attnlrp(d_q, eps), self.key.attnlrp(d_k, eps),
                                        self.value.attnlrp(d_v, eps)), eps)

@@ -3,7 +3,7 @@
 
 #include <string.h>
 
-extern "C" int te_version(void) { return 802; /* 0.8.2: AttnLRP at pixel level (te_patch_alrp_relevance_f32 / te_patch_attnlrp_relevance_bf16); 0.8.1: the AttnLRP chain on bf16 operands (te_alrp_*_bf16); 0.8.0: one entry point per rule and producer, optional operands are NULL pointers (argument lists changed under existing names) */ }
+extern "C" int te_version(void) { return 803; /* 0.8.3: AttnLRP with a class axis (te_alrpk_*); 0.8.2: AttnLRP at pixel level (te_patch_alrp_relevance_f32 / te_patch_attnlrp_relevance_bf16); 0.8.1: the AttnLRP chain on bf16 operands (te_alrp_*_bf16); 0.8.0: one entry point per rule and producer, optional operands are NULL pointers (argument lists changed under existing names) */ }
 
 #ifndef TE_BUILD_ID
 #define TE_BUILD_ID "unstamped"      // a build that did not go through build.py: _lib.load() refuses it

@@ -345,6 +345,175 @@ int token_relevance(const T* x0, const float* G, float* out, int64_t B, int64_t 
   return TE_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ a class axis
+// te_relprop.h, "AttnLRP, a class axis": G and out are [K, *shape] class-major, the cached operand has `shape` and is read
+// once for the K slices.  Slice k of a result has the bits of the kernel above on (G[k], operand): the same operations in the
+// same order per element, the same lane order per row.  The part of a rule that does not depend on G is formed once per item.
+struct DampClassesOp {      // TeAlrpDamp: st = stab(y) once; per class (g y) / st
+  float eps;
+  __device__ __forceinline__ float prepare(float y) const { return y + ((y >= 0.0f) ? eps : -eps); }
+  __device__ __forceinline__ float operator()(float g, float y, float st) const { return (eps == 0.0f) ? g : (g * y) / st; }
+};
+struct ActClassesOp {       // ActOp: r = f(x) / x or f'(0) once; per class g r
+  int kind;
+  __device__ __forceinline__ float prepare(float x) const {
+    if (kind == TE_ALRP_ACT_GELU) return (x == 0.0f) ? 0.5f : te_gelu(x) / x;
+    return (x == 0.0f) ? 1.0f : tanhf(x) / x;
+  }
+  __device__ __forceinline__ float operator()(float g, float, float r) const { return g * r; }
+};
+
+// out[k][i] = op(a[k][i], b[i]) for k < K: the items of binary_kernel over the n elements of b; slice k of a and out at + k n.
+template <class T, class Op>
+__global__ __launch_bounds__(kThreads) void binary_classes_kernel(const float* a, const T* b, float* out, int64_t n, int64_t K,
+                                                                   int64_t head, int64_t nvec, Op op) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i < nvec) {
+    const int64_t e = head + 4 * i;
+    const f32x4 vb = te_up4(b + e);
+    f32x4 pre;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pre[j] = op.prepare(vb[j]);
+    for (int64_t k = 0; k < K; ++k) {
+      const f32x4 va = *reinterpret_cast<const f32x4*>(a + k * n + e);
+      f32x4 r;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r[j] = op(va[j], vb[j], pre[j]);
+      *reinterpret_cast<f32x4*>(out + k * n + e) = r;
+    }
+    return;
+  }
+  const int64_t s = i - nvec;
+  const int64_t e = (s < head) ? s : s + 4 * nvec;
+  if (e >= n) return;
+  const float vb = te_up(b[e]), pre = op.prepare(vb);
+  for (int64_t k = 0; k < K; ++k) out[k * n + e] = op(a[k * n + e], vb, pre);
+}
+
+template <class T, class Op>
+int binary_classes_launch(const float* a, const T* b, float* out, int64_t K, int64_t n, Op op, hipStream_t stream) {
+  if (!a || !b || !out || K <= 0 || n <= 0) return TE_ERR_INVALID_ARG;
+  if (!aligned4(a) || !aligned_elem(b) || !aligned4(out)) return TE_ERR_UNSUPPORTED;
+  if (K > kMaxGrid || n > INT64_MAX / K) return TE_ERR_UNSUPPORTED;
+  int64_t head = 0, nvec = 0;
+  // binary_launch's phase rule, and every slice on slice 0's phase: the class stride n a multiple of 4 (or one slice)
+  if (off16(a) == off16(out) && (K == 1 || n % 4 == 0)) {
+    head = ((16 - off16(a)) & 15) / 4;
+    if (aligned_group(b + head)) {
+      if (head > n) head = n;
+      nvec = (n - head) / 4;
+    } else {
+      head = 0;
+    }
+  }
+  const int64_t items = nvec + (n - 4 * nvec);
+  const int64_t blocks = te_ceil_div(items, kThreads);
+  if (blocks > kMaxGrid) return TE_ERR_UNSUPPORTED;
+  binary_classes_kernel<T, Op><<<dim3((unsigned)blocks), dim3(kThreads), 0, stream>>>(a, b, out, n, K, head, nvec, op);
+  TE_RETURN_IF_LAUNCH_FAILED();
+  return TE_OK;
+}
+
+// out[k][r][i] = rstd[r] (gamma_i G[k][r][i] - mean_j(gamma_j G[k][r][j])): one wave per operand row r, which walks the K slices;
+// per (k, r) the loads, the lane order and the shuffle tree of layernorm_rule_kernel
+template <bool VEC, class T>
+__global__ __launch_bounds__(kThreads) void layernorm_rule_classes_kernel(const float* G, const T* __restrict__ gamma,
+                                                                           const float* __restrict__ rstd, float* out, int64_t K,
+                                                                           int64_t rows, int64_t C) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const float rs = rstd[r];
+  for (int64_t k = 0; k < K; ++k) {
+    const float* g = G + (k * rows + r) * C;
+    float* o = out + (k * rows + r) * C;
+    auto term = [&](int64_t c, float (&t)[4]) {
+      float a[4], w[4];
+      load_group<VEC>(g, c, C, a);
+      load_group<VEC>(gamma, c, C, w);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t[j] = w[j] * a[j];
+    };
+    const float mean = wave_row_sum<VEC>(lane, C, term) / (float)C;
+    for (int64_t c = (int64_t)lane * 4; c < C; c += TE_WAVE * 4) {
+      float t[4];
+      term(c, t);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t[j] = rs * (t[j] - mean);
+      store_group<VEC>(o, c, C, t);
+    }
+  }
+}
+
+// out[b][k][t - skip] = sum_c x0[b][t][c] G[k][b][t][c]: one workgroup of one wave per token (b, t), which walks the K slices;
+// per (k, b, t) the fp64 order of token_relevance_kernel
+template <bool VEC, class T>
+__global__ __launch_bounds__(TE_WAVE) void token_relevance_classes_kernel(const T* __restrict__ x0, const float* __restrict__ G,
+                                                                          float* __restrict__ out, int64_t K, int64_t B, int64_t N,
+                                                                          int64_t C, int64_t skip) {
+  __shared__ double red[1];
+  const int64_t row = blockIdx.x, per = N - skip;
+  const int64_t b = row / per, t = row - b * per + skip;
+  const T* xr = x0 + (b * N + t) * C;
+  for (int64_t k = 0; k < K; ++k) {
+    const float* gr = G + ((k * B + b) * N + t) * C;
+    double acc = 0.0;
+    for (int64_t e0 = (int64_t)threadIdx.x * 4; e0 < C; e0 += TE_WAVE * 4) {
+      double vx[4], vg[4];
+      te_load4_f64<VEC>(xr, e0, C, vx);
+      te_load4_f64<VEC>(gr, e0, C, vg);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc += vx[j] * vg[j];
+    }
+    te_block_sum(acc, red);      // (one wave: thread 0 alone writes and reads red[0])
+    if (threadIdx.x == 0) out[(b * K + k) * per + (t - skip)] = (float)acc;
+  }
+}
+
+template <class T>
+int damp_classes(const float* G, const T* Y, float* out, int64_t K, int64_t n, float eps, hipStream_t stream) {
+  if (!finite_not_negative(eps)) return TE_ERR_INVALID_ARG;
+  return binary_classes_launch(G, Y, out, K, n, DampClassesOp{eps}, stream);
+}
+
+template <class T>
+int act_classes(const float* G, const T* x, float* out, int64_t K, int64_t n, int kind, hipStream_t stream) {
+  if (kind != TE_ALRP_ACT_GELU && kind != TE_ALRP_ACT_TANH) return TE_ERR_INVALID_ARG;
+  return binary_classes_launch(G, x, out, K, n, ActClassesOp{kind}, stream);
+}
+
+template <class T>
+int layernorm_classes(const float* G, const T* gamma, const float* rstd, float* out, int64_t K, int64_t rows, int64_t C,
+                      hipStream_t stream) {
+  if (!G || !gamma || !rstd || !out || K <= 0 || rows <= 0 || C <= 0) return TE_ERR_INVALID_ARG;
+  if (!aligned4(G) || !aligned_elem(gamma) || !aligned4(rstd) || !aligned4(out)) return TE_ERR_UNSUPPORTED;
+  const int64_t blocks = te_ceil_div(rows, kRowsPerBlock);
+  if (blocks > kMaxGrid || C > kMaxGrid || K > kMaxGrid || rows > INT64_MAX / C / K) return TE_ERR_UNSUPPORTED;
+  const bool vec = C % 4 == 0 && te_aligned16(G) && aligned_group(gamma) && te_aligned16(out);
+  if (vec)
+    layernorm_rule_classes_kernel<true, T><<<dim3((unsigned)blocks), dim3(kThreads), 0, stream>>>(G, gamma, rstd, out, K, rows, C);
+  else
+    layernorm_rule_classes_kernel<false, T><<<dim3((unsigned)blocks), dim3(kThreads), 0, stream>>>(G, gamma, rstd, out, K, rows, C);
+  TE_RETURN_IF_LAUNCH_FAILED();
+  return TE_OK;
+}
+
+template <class T>
+int token_relevance_classes(const T* x0, const float* G, float* out, int64_t K, int64_t B, int64_t N, int64_t C, int skip_first,
+                            hipStream_t stream) {
+  if (!x0 || !G || !out || K <= 0 || B <= 0 || N <= 0 || C <= 0 || (skip_first != 0 && skip_first != 1) || N - skip_first <= 0)
+    return TE_ERR_INVALID_ARG;
+  if (!aligned_elem(x0) || !aligned4(G) || !aligned4(out)) return TE_ERR_UNSUPPORTED;
+  if (B > kMaxGrid / N || C > kMaxGrid || K > kMaxGrid || B * N > INT64_MAX / C / K) return TE_ERR_UNSUPPORTED;
+  const int64_t rows = B * (N - skip_first);
+  if (C % 4 == 0 && aligned_group(x0) && te_aligned16(G))
+    token_relevance_classes_kernel<true, T><<<dim3((unsigned)rows), dim3(TE_WAVE), 0, stream>>>(x0, G, out, K, B, N, C, skip_first);
+  else
+    token_relevance_classes_kernel<false, T><<<dim3((unsigned)rows), dim3(TE_WAVE), 0, stream>>>(x0, G, out, K, B, N, C, skip_first);
+  TE_RETURN_IF_LAUNCH_FAILED();
+  return TE_OK;
+}
+
 }  // namespace
 
 int te_alrp::damp_planes_launch(const float* G, Strided gs, const te_bf16_t* Y, Strided ys, uint16_t* planes, int64_t B, int64_t H,
@@ -435,4 +604,39 @@ extern "C" int te_alrp_token_relevance_f32(const float* x0, const float* G, floa
 extern "C" int te_attnlrp_token_relevance_bf16(const te_bf16_t* x0, const float* G, float* out, int64_t B, int64_t N, int64_t C,
                                             int skip_first, te_stream_t stream) {
   return token_relevance(x0, G, out, B, N, C, skip_first, (hipStream_t)stream);
+}
+
+// ---- a class axis (te_relprop.h, "AttnLRP, a class axis"): G and out [K, *shape], the operand shared by the K slices
+extern "C" int te_alrpk_damp_f32(const float* G, const float* Y, float* out, int64_t K, int64_t n, float eps, te_stream_t stream) {
+  return damp_classes(G, Y, out, K, n, eps, (hipStream_t)stream);
+}
+extern "C" int te_alrpk_damp_bf16(const float* G, const te_bf16_t* Y, float* out, int64_t K, int64_t n, float eps,
+                                  te_stream_t stream) {
+  return damp_classes(G, Y, out, K, n, eps, (hipStream_t)stream);
+}
+
+extern "C" int te_alrpk_act_f32(const float* G, const float* x, float* out, int64_t K, int64_t n, int kind, te_stream_t stream) {
+  return act_classes(G, x, out, K, n, kind, (hipStream_t)stream);
+}
+extern "C" int te_alrpk_act_bf16(const float* G, const te_bf16_t* x, float* out, int64_t K, int64_t n, int kind,
+                                 te_stream_t stream) {
+  return act_classes(G, x, out, K, n, kind, (hipStream_t)stream);
+}
+
+extern "C" int te_alrpk_layernorm_f32(const float* G, const float* gamma, const float* rstd, float* out, int64_t K, int64_t rows,
+                                      int64_t C, te_stream_t stream) {
+  return layernorm_classes(G, gamma, rstd, out, K, rows, C, (hipStream_t)stream);
+}
+extern "C" int te_alrpk_layernorm_bf16(const float* G, const te_bf16_t* gamma, const float* rstd, float* out, int64_t K,
+                                       int64_t rows, int64_t C, te_stream_t stream) {
+  return layernorm_classes(G, gamma, rstd, out, K, rows, C, (hipStream_t)stream);
+}
+
+extern "C" int te_alrpk_token_relevance_f32(const float* x0, const float* G, float* out, int64_t K, int64_t B, int64_t N,
+                                            int64_t C, int skip_first, te_stream_t stream) {
+  return token_relevance_classes(x0, G, out, K, B, N, C, skip_first, (hipStream_t)stream);
+}
+extern "C" int te_alrpk_token_relevance_bf16(const te_bf16_t* x0, const float* G, float* out, int64_t K, int64_t B, int64_t N,
+                                             int64_t C, int skip_first, te_stream_t stream) {
+  return token_relevance_classes(x0, G, out, K, B, N, C, skip_first, (hipStream_t)stream);
 }

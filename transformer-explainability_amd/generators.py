@@ -274,6 +274,24 @@ class _ClassRequest:
         return None, scores, seeds
 
 
+def _check_chunk(chunk):
+    """``chunk`` of generate_attnlrp_classes: None (all classes in one chain pass) or an integer >= 1."""
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1):
+        raise ValueError(f"generate_attnlrp_classes: chunk must be None or an integer >= 1, got {chunk!r}")
+
+
+def _attnlrp_class_chain(chain, seeds, chunk):
+    """``chain`` (model.attnlrp on the caches of one forward pass) over the seeds [K,B,C], ``chunk`` classes per pass -> [B,K,...].
+    A pass of several classes carries them as a class axis (te_relprop.h, "AttnLRP, a class axis"); chunk == 1 runs K chains
+    without one, on the kernels of generate_attnlrp.  Slice k has the same bits either way."""
+    K = seeds.shape[0]
+    if chunk == 1:
+        return torch.stack([chain(seeds[k]) for k in range(K)], 1)
+    if chunk is None or chunk >= K:
+        return chain(seeds)
+    return torch.cat([chain(seeds[k0:k0 + chunk]) for k0 in range(0, K, chunk)], 1)
+
+
 def _stack_classes(per_class, names):
     """[{name: map of class k}] -> {name: [B,K,...]}."""
     return {m: torch.stack([d[m] for d in per_class], 1) for m in names}
@@ -410,6 +428,38 @@ class LRP(_PassDriver):
             _drop_rule_planes(self.model)
             seed = _one_hot(output, index)
             return self._gradients_and_chain(output, [], lambda: self.model.attnlrp(seed, eps=eps, method=method))
+
+    def generate_attnlrp_classes(self, input, classes=None, topk=None, seeds=None, eps=1e-6, method="tokens",
+                                 chunk=None) -> ClassMaps:
+        """(extension) AttnLRP for several CLASSES of the same batch from ONE forward pass and one chain with a class axis
+        (te_relprop.h, "AttnLRP, a class axis": the chain is linear in the seed and its cached operands do not depend on the
+        class).  Exactly one of ``classes`` / ``topk`` / ``seeds``, as in generate_classes (``TopAnd``, [K] for all samples,
+        duplicates; device tensors are not read back, an out-of-range class in one yields class -1, score NaN and the map of
+        an all-zero seed); ``seeds`` [B,C] or [B,K,C] are float32, for bf16 models too (G is fp32), e.g. onehot(c) - onehot(c')
+        for a contrastive map.  Returns ClassMaps(classes [B,K] or None, scores [B,K], {"attnlrp": M}), M fp32 [B,K,N-1]
+        (method="tokens") or [B,K,H,W] (method="full").  ``M[:, k]`` has the bits of generate_attnlrp(input,
+        index=classes[:, k], eps, method) on a fresh forward pass wherever a batch equals its samples for that call: every
+        product on the package's kernels, and one-hot seeds at a stock head product; general seeds at a stock head product
+        and models whose Linear products run on the stock GEMM agree to rounding.  ``chunk``: classes per chain pass (default:
+        all K; bounds the memory of G, K times a single chain's); the same bits for every chunk; chunk=1 runs K chains on
+        the kernels of generate_attnlrp after the one forward pass.  The refusals of generate_attnlrp (there is no
+        ``head_mask`` argument), a bad ``method`` / ``chunk`` (ValueError) and a bad class request are raised before the
+        forward pass.  The x6 status poll / post happens once; capturable by GraphedCall."""
+        with _x6_bracket(input):
+            if method not in ("tokens", "full"):
+                raise ValueError(f"generate_attnlrp_classes: method must be 'tokens' (patch tokens, [B,K,N-1]) or 'full' (pixels, "
+                                 f"[B,K,H,W]), got {method!r}")
+            _check_chunk(chunk)
+            _refuse_attnlrp(self.model, eps, None, input)
+            request = _ClassRequest(classes, topk, seeds)
+            request.check(input.shape[0], _num_classes(self.model), torch.float32, input.device)
+            with torch.no_grad():
+                output = self.model(input)
+                _drop_rule_planes(self.model)
+                cls, scores, seed_stack = request.targets(output)
+                chain = lambda seed: self.model.attnlrp(seed, eps=eps, method=method)      # noqa: E731
+                maps = self._gradients_and_chain(output, [], lambda: _attnlrp_class_chain(chain, seed_stack, chunk))
+            return ClassMaps(cls, scores, {"attnlrp": maps})
 
     def generate_all(self, input, methods, index=None, is_ablation=False, start_layer=0, head_mask=None):
         """(extension) The maps of several methods of the SAME batch from one pass: ``methods`` is any subset of the
@@ -803,6 +853,26 @@ class Generator(_PassDriver):
                 _drop_rule_planes(self.model)
                 seed = _one_hot(output, index)
                 return self._gradients_and_chain(output, [], lambda: self.model.attnlrp(seed, eps=eps))
+
+    def generate_attnlrp_classes(self, input_ids, attention_mask, classes=None, topk=None, seeds=None, eps=1e-6,
+                                 chunk=None) -> ClassMaps:
+        """(extension) AttnLRP for several CLASSES of the same batch from ONE forward pass and one chain with a class axis: the
+        class arguments, ``chunk``, the result and its bit-for-bit statement as in LRP.generate_attnlrp_classes; the map is
+        fp32 [B,K,N], ``maps["attnlrp"][:, k]`` the bits of generate_attnlrp(input_ids, attention_mask, index=classes[:, k],
+        eps).  The refusals of generate_attnlrp (there is no ``head_mask`` argument), a bad ``chunk`` and a bad class request
+        are raised before the forward pass."""
+        with _x6_bracket(input_ids):
+            _check_chunk(chunk)
+            _refuse_attnlrp(self.model, eps, None, input_ids, cast=(attention_mask,))
+            request = _ClassRequest(classes, topk, seeds)
+            request.check(input_ids.shape[0], _num_classes(self.model), torch.float32, input_ids.device)
+            with torch.no_grad():
+                output = self.model(input_ids=input_ids, attention_mask=attention_mask)[0]
+                _drop_rule_planes(self.model)
+                cls, scores, seed_stack = request.targets(output)
+                chain = lambda seed: self.model.attnlrp(seed, eps=eps)      # noqa: E731
+                maps = self._gradients_and_chain(output, [], lambda: _attnlrp_class_chain(chain, seed_stack, chunk))
+            return ClassMaps(cls, scores, {"attnlrp": maps})
 
     def attribution_tail(self, start_layer=11):
         """ExplanationGenerator.py:47-59 on the attn_cam / attention gradients cached by relprop + backward."""

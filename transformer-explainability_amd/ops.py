@@ -2625,10 +2625,17 @@ def class_targets(logits: Tensor, classes: Optional[Tensor] = None, topk: Option
 _ALRP_KINDS = {"gelu": _lib.TE_ALRP_ACT_GELU, "tanh": _lib.TE_ALRP_ACT_TANH}
 
 
-def _alrp_operand(t: Tensor, rule: str) -> Tuple[Tensor, str]:
+def _alrp_operand(t: Tensor, rule: str, classes: bool = False) -> Tuple[Tensor, str]:
     """The cached operand of a rule, contiguous, and the name of the entry that reads it: te_alrp_<rule>_f32, or, a bf16
-    operand, te_attnlrp_<rule>_bf16."""
+    operand, te_attnlrp_<rule>_bf16.  classes: the entry that takes G with a class axis, te_alrpk_<rule>_f32 / _bf16."""
+    if classes:
+        return (_c16(t), f"te_alrpk_{rule}_bf16") if _is_bf16(t) else (_c(t), f"te_alrpk_{rule}_f32")
     return (_c16(t), f"te_attnlrp_{rule}_bf16") if _is_bf16(t) else (_c(t), f"te_alrp_{rule}_f32")
+
+
+def _alrp_classes(G: Tensor, operand: Tensor) -> bool:
+    """G [K, *shape] against a cached operand of ``shape`` (te_relprop.h, "AttnLRP, a class axis"): one more dimension."""
+    return G.dim() == operand.dim() + 1
 
 
 def _alrp_out(out: Optional[Tensor], like: Tensor, what: str) -> Tensor:
@@ -2640,13 +2647,16 @@ def _alrp_out(out: Optional[Tensor], like: Tensor, what: str) -> Tensor:
 
 
 def alrp_damp(G: Tensor, Y: Tensor, eps: float = 1e-6, out: Optional[Tensor] = None) -> Tensor:
-    """damp(G, Y) = G Y / stab(Y), stab(y) = y + eps sgn(y) with sgn(0) = +1; eps = 0: G itself.  ``out`` may be G."""
-    G, (Y, name) = _c(G), _alrp_operand(Y, "damp")
-    if G.shape != Y.shape:
+    """damp(G, Y) = G Y / stab(Y), stab(y) = y + eps sgn(y) with sgn(0) = +1; eps = 0: G itself.  ``out`` may be G.
+    G [K, *Y.shape]: K classes on one read of Y (te_alrpk_damp_*), slice k the bits of this call on (G[k], Y)."""
+    classes = _alrp_classes(G, Y)
+    G, (Y, name) = _c(G), _alrp_operand(Y, "damp", classes)
+    if (G.shape[1:] if classes else G.shape) != Y.shape:
         raise _lib.TeError(f"alrp_damp: G {tuple(G.shape)} and Y {tuple(Y.shape)} differ in shape")
     out = _alrp_out(out, G, "alrp_damp")
-    with _on_device(G) as lib, _timed("alrp_damp", 0.0, (8.0 + Y.element_size()) * G.numel()):
-        _lib.check(getattr(lib, name)(_ptr(G), _ptr(Y), _ptr(out), G.numel(), float(eps), _stream(G)), name)
+    size = (G.shape[0], Y.numel()) if classes else (G.numel(),)
+    with _on_device(G) as lib, _timed("alrp_damp", 0.0, 8.0 * G.numel() + Y.element_size() * Y.numel()):
+        _lib.check(getattr(lib, name)(_ptr(G), _ptr(Y), _ptr(out), *size, float(eps), _stream(G)), name)
     return out
 
 
@@ -2654,12 +2664,14 @@ def alrp_act(G: Tensor, x: Tensor, kind: str = "gelu", out: Optional[Tensor] = N
     """The identity rule through y = f(x), f = GELU (te_gelu) or tanh: G (f(x) / x), f'(0) at x == 0.  ``out`` may be G."""
     if kind not in _ALRP_KINDS:
         raise ValueError(f"alrp_act: kind must be one of {sorted(_ALRP_KINDS)}, got {kind!r}")
-    G, (x, name) = _c(G), _alrp_operand(x, "act")
-    if G.shape != x.shape:
+    classes = _alrp_classes(G, x)      # G [K, *x.shape]: te_alrpk_act_*, f(x) / x formed once for the K classes
+    G, (x, name) = _c(G), _alrp_operand(x, "act", classes)
+    if (G.shape[1:] if classes else G.shape) != x.shape:
         raise _lib.TeError(f"alrp_act: G {tuple(G.shape)} and x {tuple(x.shape)} differ in shape")
     out = _alrp_out(out, G, "alrp_act")
-    with _on_device(G) as lib, _timed("alrp_act", 0.0, (8.0 + x.element_size()) * G.numel()):
-        _lib.check(getattr(lib, name)(_ptr(G), _ptr(x), _ptr(out), G.numel(), _ALRP_KINDS[kind], _stream(G)), name)
+    size = (G.shape[0], x.numel()) if classes else (G.numel(),)
+    with _on_device(G) as lib, _timed("alrp_act", 0.0, 8.0 * G.numel() + x.element_size() * x.numel()):
+        _lib.check(getattr(lib, name)(_ptr(G), _ptr(x), _ptr(out), *size, _ALRP_KINDS[kind], _stream(G)), name)
     return out
 
 
@@ -2698,28 +2710,38 @@ def alrp_row_rstd(x: Tensor, eps: float) -> Tensor:
 
 
 def alrp_layernorm(G: Tensor, gamma: Tensor, rstd: Tensor, out: Optional[Tensor] = None) -> Tensor:
-    """The LayerNorm rule with rstd held constant: G [..., C], gamma [C], rstd [...] -> rstd (gamma G - mean(gamma G))."""
-    G, (gamma, name), rstd = _c(G), _alrp_operand(gamma.detach(), "layernorm"), _c(rstd)
+    """The LayerNorm rule with rstd held constant: G [..., C], gamma [C], rstd [...] -> rstd (gamma G - mean(gamma G)).
+    G [K, ..., C] with rstd [...] of the operand's rows (one more dimension than rstd's + 1): K classes on one rstd
+    (te_alrpk_layernorm_*), slice k the bits of this call on (G[k], gamma, rstd)."""
+    classes = G.dim() == rstd.dim() + 2
+    G, (gamma, name), rstd = _c(G), _alrp_operand(gamma.detach(), "layernorm", classes), _c(rstd)
     C = G.shape[-1]
-    if tuple(gamma.shape) != (C,) or rstd.numel() != G.numel() // C:
+    rows = G.numel() // C // (G.shape[0] if classes else 1)
+    if tuple(gamma.shape) != (C,) or rstd.numel() != rows:
         raise _lib.TeError(f"alrp_layernorm: G {tuple(G.shape)} needs gamma [{C}] and one rstd per row, got "
                            f"{tuple(gamma.shape)} and {tuple(rstd.shape)}")
     out = _alrp_out(out, G, "alrp_layernorm")
+    size = (G.shape[0], rows, C) if classes else (rows, C)
     with _on_device(G) as lib, _timed("alrp_layernorm", 0.0, 8.0 * G.numel()):
-        _lib.check(getattr(lib, name)(_ptr(G), _ptr(gamma), _ptr(rstd), _ptr(out), G.numel() // C, C, _stream(G)), name)
+        _lib.check(getattr(lib, name)(_ptr(G), _ptr(gamma), _ptr(rstd), _ptr(out), *size, _stream(G)), name)
     return out
 
 
 def alrp_token_relevance(x0: Tensor, G: Tensor, skip_first: bool = False) -> Tensor:
-    """x0, G [B,N,C] -> fp32 [B, N - skip_first]: sum_c x0 G per token in fp64, rounded once; skip_first drops token 0."""
-    (x0, name), G = _alrp_operand(x0, "token_relevance"), _c(G)
-    if x0.dim() != 3 or x0.shape != G.shape:
-        raise _lib.TeError(f"alrp_token_relevance: x0 and G must both be [B,N,C], got {tuple(x0.shape)} and {tuple(G.shape)}")
+    """x0, G [B,N,C] -> fp32 [B, N - skip_first]: sum_c x0 G per token in fp64, rounded once; skip_first drops token 0.
+    G [K,B,N,C]: K classes on one x0 (te_alrpk_token_relevance_*) -> fp32 [B, K, N - skip_first], batch-major; [:, k] has the
+    bits of this call on (x0, G[k])."""
+    classes = _alrp_classes(G, x0)
+    (x0, name), G = _alrp_operand(x0, "token_relevance", classes), _c(G)
+    if x0.dim() != 3 or x0.shape != (G.shape[1:] if classes else G.shape):
+        raise _lib.TeError(f"alrp_token_relevance: x0 and G must both be [B,N,C] (G: or [K,B,N,C]), got {tuple(x0.shape)} and "
+                           f"{tuple(G.shape)}")
     B, N, C = x0.shape
     skip = int(bool(skip_first))
-    out = torch.empty((B, N - skip), dtype=torch.float32, device=x0.device)
-    with _on_device(x0) as lib, _timed("alrp_token_relevance", 0.0, (4.0 + x0.element_size()) * x0.numel()):
-        _lib.check(getattr(lib, name)(_ptr(x0), _ptr(G), _ptr(out), B, N, C, skip, _stream(x0)), name)
+    K = (G.shape[0],) if classes else ()
+    out = torch.empty((B, *K, N - skip), dtype=torch.float32, device=x0.device)
+    with _on_device(x0) as lib, _timed("alrp_token_relevance", 0.0, 4.0 * G.numel() + x0.element_size() * x0.numel()):
+        _lib.check(getattr(lib, name)(_ptr(x0), _ptr(G), _ptr(out), *K, B, N, C, skip, _stream(x0)), name)
     return out
 
 
@@ -2793,29 +2815,37 @@ def alrp_linear(G: Tensor, W: Tensor, cache: Optional[dict] = None, Y: Optional[
     shape (gemm_x6_supported; X6_GEMM = "off" switches it off), the stock fp32 GEMM elsewhere -- the two routes of the
     package's own input-gradient product (producers._Linear.backward).
     bf16 W, with the layer's cached bf16 output Y and eps: damp(G, Y) W in one call -- te_attnlrp_linear_bf16 where
-    alrp_linear_bf16_route says 'bf16', else the fp32 route above on exact fp32 copies of Y and W.
+    alrp_linear_bf16_route says 'bf16', else the fp32 route above on exact fp32 copies of Y and W.  G [K, *Y.shape] (a class
+    axis): K launches on the slices G[k] with the same Y, W and workspace, into the slices of one [K, ..., in] result.
     Whatever USE_FUSED_PRODUCERS says."""
     G = _prep(G)
     out_f, in_f = W.shape
     T = G.numel() // out_f
     if _is_bf16(W):
-        if not _is_bf16(Y) or Y.shape != G.shape:
+        classes = Y is not None and G.dim() == Y.dim() + 1
+        slices = list(G) if classes else [G]
+        if not _is_bf16(Y) or Y.shape != slices[0].shape:
             raise _lib.TeError("alrp_linear: a bf16 W needs the layer's cached bf16 output Y, of G's shape "
                                f"(got {None if Y is None else (Y.dtype, tuple(Y.shape))} for G {tuple(G.shape)})")
+        T = slices[0].numel() // out_f
         if alrp_linear_bf16_route(T, in_f, out_f) != "bf16":
+            if classes:      # per slice, like the kernel route: a stock product's order may depend on the number of rows
+                return torch.stack([alrp_linear(g, W, cache, Y=Y, eps=eps) for g in slices])
             return alrp_linear(alrp_damp(G, Y.float(), eps), W.detach().float())
         W2 = alrp_weight_t(W, cache) if ALRP_WEIGHT_T else _c16(W.detach())
-        G2 = G.reshape(T, out_f)                 # G and Y: rows at a uniform stride are read in place
-        if G2.stride(1) != 1 or (T > 1 and G2.stride(0) < out_f):
-            G2 = G2.contiguous()
-        g_ld = G2.stride(0) if T > 1 else out_f
         Y2, y_ld = _rows(Y, out_f)
-        out = torch.empty((T, in_f), dtype=torch.float32, device=G.device)
-        with _on_device(G2) as lib, _timed("alrp_linear_bf16", 6.0 * T * in_f * out_f,
-                                           6.0 * T * out_f + 12.0 * T * out_f + 2.0 * in_f * out_f + 4.0 * T * in_f):
-            ws = _ws(lib.te_attnlrp_linear_bf16_workspace_bytes(T, in_f, out_f), G2)
-            _lib.check(lib.te_attnlrp_linear_bf16(_ptr(G2), g_ld, _ptr(Y2), y_ld, _ptr(W2), int(ALRP_WEIGHT_T), _ptr(out), T, in_f, out_f,
-                                               float(eps), _ptr(ws), ws.numel(), _stream(G2)), "te_attnlrp_linear_bf16")
+        out = torch.empty((len(slices), T, in_f), dtype=torch.float32, device=G.device)
+        with _on_device(G) as lib:
+            ws = _ws(lib.te_attnlrp_linear_bf16_workspace_bytes(T, in_f, out_f), G)
+            for g, o in zip(slices, out):
+                G2 = g.reshape(T, out_f)         # G and Y: rows at a uniform stride are read in place
+                if G2.stride(1) != 1 or (T > 1 and G2.stride(0) < out_f):
+                    G2 = G2.contiguous()
+                g_ld = G2.stride(0) if T > 1 else out_f
+                with _timed("alrp_linear_bf16", 6.0 * T * in_f * out_f,
+                            6.0 * T * out_f + 12.0 * T * out_f + 2.0 * in_f * out_f + 4.0 * T * in_f):
+                    _lib.check(lib.te_attnlrp_linear_bf16(_ptr(G2), g_ld, _ptr(Y2), y_ld, _ptr(W2), int(ALRP_WEIGHT_T), _ptr(o), T, in_f,
+                                                       out_f, float(eps), _ptr(ws), ws.numel(), _stream(G)), "te_attnlrp_linear_bf16")
         return out.reshape(*G.shape[:-1], in_f)
     if Y is not None:
         raise _lib.TeError("alrp_linear: Y is an argument of the bf16 route; with an fp32 W pass damp(G, Y) as G")

@@ -211,9 +211,11 @@ class Linear(_ScratchCache, nn.Linear, RelProp):
         return linear_rule(self, R, alpha)
 
     def attnlrp(self, G, eps):
-        """G_x = damp(G_y, y) W on the cached output y (bias included)."""
+        """G_x = damp(G_y, y) W on the cached output y (bias included).  G [K, *y.shape] (a class axis): fp32, one damp with
+        classes and ONE product over the K T rows; bf16, K calls of the fused damp-and-product on the slices."""
         Y = self.Y.detach()
-        if Y.shape != G.shape:
+        classes = G.dim() == Y.dim() + 1
+        if (G.shape[1:] if classes else G.shape) != Y.shape:
             raise ops._lib.TeError(f"Linear.attnlrp: G {tuple(G.shape)} does not have the shape of the cached output "
                                    f"{tuple(Y.shape)}")
         if ops._is_bf16(self.weight):      # damp and product in one call: the damped G goes to the product as bf16 planes
@@ -392,10 +394,16 @@ class IndexSelect(RelProp):
         return ops.index_select_relprop(R, self.X, host)
 
     def attnlrp(self, G, eps):
-        """Plain gradient of the class-token select: G [B,C] of the selected token -> [B,N,C], zero elsewhere."""
+        """Plain gradient of the class-token select: G [B,C] of the selected token -> [B,N,C], zero elsewhere.  G [K,B,C] (a class
+        axis: three dimensions, the second the batch) -> [K,B,N,C]."""
         idx = self.indices
         if self.dim != 1 or self.X.dim() != 3 or (torch.is_tensor(idx) and idx.numel() != 1):
             raise NotImplementedError("IndexSelect.attnlrp: only dim=1 with a single index")
+        if G.dim() == 3 and G.shape[1] == self.X.shape[0]:
+            out = torch.zeros((G.shape[0], *self.X.shape), dtype=G.dtype, device=G.device)
+            out.index_copy_(2, idx.reshape(1) if torch.is_tensor(idx) else torch.tensor([int(idx)], device=G.device),
+                            G.unsqueeze(2))
+            return out
         out = torch.zeros(self.X.shape, dtype=G.dtype, device=G.device)
         out.index_copy_(1, idx.reshape(1) if torch.is_tensor(idx) else torch.tensor([int(idx)], device=G.device),
                         G.reshape(G.shape[0], 1, -1))

@@ -346,12 +346,14 @@ def make_vit_module(L):
             if self.head_mask is not None:
                 raise ops._lib.TeError("Attention.attnlrp: head_mask is not implemented for AttnLRP")
             G_o = self.proj.attnlrp(G, eps)
-            B, N, C = G_o.shape
+            C = G_o.shape[-1]
             qkv = self.qkv.Y.detach()
-            d_qkv = torch.empty_like(qkv, dtype=torch.float32)      # (G is fp32 on a bf16 model too)
+            classes = G_o.dim() == qkv.dim() + 1      # [K,B,N,C]: the rule per class into the slices of a [K,B,N,3C] gradient
+            d_qkv = torch.empty(G_o.shape[:-1] + (3 * C,), dtype=torch.float32, device=G_o.device)      # (fp32 on a bf16 model too)
             third = lambda t, i: t[..., i * C:(i + 1) * C]      # noqa: E731
-            R_ours.attention_attnlrp(G_o, third(qkv, 0), third(qkv, 1), third(qkv, 2), self.get_attn().detach(),
-                                     self.num_heads, self.scale, third(d_qkv, 0), third(d_qkv, 1), third(d_qkv, 2))
+            for g_o, d in (zip(G_o, d_qkv) if classes else ((G_o, d_qkv),)):
+                R_ours.attention_attnlrp(g_o, third(qkv, 0), third(qkv, 1), third(qkv, 2), self.get_attn().detach(),
+                                         self.num_heads, self.scale, third(d, 0), third(d, 1), third(d, 2))
             return self.qkv.attnlrp(ops.alrp_scale3(d_qkv), eps)
 
     class Block(nn.Module):
@@ -571,16 +573,21 @@ def make_vit_module(L):
             """(extension) AttnLRP (te_relprop.h, section "AttnLRP"): ``seed`` [B, num_classes] (the one-hot of the class) ->
             fp32 [B, N-1], the relevance of the patch tokens.  One chain over the caches of the last forward pass; no
             backward pass.  The position-embedding Add is a parameter Add: plain.  method="full": the same chain, then the
-            eps-rule through the patch embedding and input x G per pixel ("AttnLRP, pixel level") -> fp32 [B,H,W]."""
+            eps-rule through the patch embedding and input x G per pixel ("AttnLRP, pixel level") -> fp32 [B,H,W].
+            ``seed`` [K, B, num_classes] (te_relprop.h, "AttnLRP, a class axis"): K seeds through one chain, every cached operand
+            read once -> fp32 [B, K, N-1] / [B, K, H, W]; [:, k] has the bits of the call on seed[k]."""
             if method not in ("tokens", "full"):
                 raise ValueError(f"attnlrp: method must be 'tokens' or 'full', got {method!r}")
             G = self.head.attnlrp(seed, eps)
             G = self.norm.attnlrp(self.pool.attnlrp(G, eps), eps)
             for blk in reversed(self.blocks):
                 G = blk.attnlrp(G, eps)
+            x0 = self.add.X[0]
             if method == "full":
-                return self.patch_embed.attnlrp(G, self.add.X[0], eps)
-            return ops.alrp_token_relevance(self.add.X[0], G, skip_first=True)
+                if G.dim() == x0.dim() + 1:
+                    return torch.stack([self.patch_embed.attnlrp(g, x0, eps) for g in G], 1)
+                return self.patch_embed.attnlrp(G, x0, eps)
+            return ops.alrp_token_relevance(x0, G, skip_first=True)
 
     def vit_base_patch16_224(pretrained=False, **kwargs):
         model = VisionTransformer(patch_size=16, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4, qkv_bias=True,
