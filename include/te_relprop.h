@@ -1235,6 +1235,70 @@ int te_alrpk_token_relevance_f32(const float* x0, const float* G, float* out, in
 int te_alrpk_token_relevance_bf16(const te_bf16_t* x0, const float* G, float* out, int64_t K, int64_t B, int64_t N, int64_t C,
                                   int skip_first, te_stream_t stream);
 
+/* ---- gradient baselines (Input x Gradient: Shrikumar et al., 2016; SmoothGrad: Smilkov et al., 2017; Integrated Gradients:
+ * Sundararajan et al., ICML 2017) -- csrc/te_gradients.hip -----------------------------------------------------------------
+ * THE REFERENCE TREE HAS NO SUCH METHODS: what follows is this project's definition, restated in numpy / torch by
+ * gradients.py.  Parity with captum is not claimed.  The methods are a loop around the model's own forward and backward pass;
+ * the entries below are what surrounds the loop: the path or noise copies of a batch, written in the model's dtype, and the
+ * reduction of the B S input gradients to B maps.  No entry synchronises, reads back or issues a memset node: a HIP graph
+ * captures every call.  There are no atomics: every output of sample b is the same bit pattern alone, in any batch and in any
+ * chunking (s0, n_s) / (d0, n_d) of the copies.
+ *
+ * Path inputs.  x, base [B,n] fp32, n = C H W: the input the model saw, upcast, and the baseline.  alphas [S] fp32, on the
+ *   device.  out [B,n_s,n], fp32 or bf16: row b n_s + j is node s0 + j of sample b,
+ *       out = round((double)base + (double)alphas[s0 + j] * ((double)x - (double)base)):
+ *   one fp64 subtraction, one fp64 multiplication and one fp64 addition (never an FMA), ONE rounding to fp32; _bf16 rounds that
+ *   fp32 once more, to nearest even.  Every step is IEEE: numpy's float64 expression followed by astype(float32) gives the same
+ *   bits.  alpha = 0 gives base; alpha = 1 gives x wherever x - base is exact in fp64 (exponents less than 2^29 apart).  A
+ *   thread owns four consecutive elements, reads x and base once and walks j.
+ * Gauss inputs.  x [B,n] fp32, out [B,n_d,n], fp32 or bf16: row b n_d + j is draw d = d0 + j of the sample with the global
+ *   64-bit id id0 + b (wrapping), out = round((double)x + sigma * z): one fp64 multiplication, one fp64 addition, ONE rounding
+ *   to fp32 (_bf16: once more, to nearest even).  The four elements 4g .. 4g + 3 take the words w0 .. w3 of Philox4x32-10
+ *   (the generator of "robustness and complexity") with the counter (0x40000000 | g, d, low32(id), high32(id)) and the key
+ *   (low32(seed), high32(seed)): bit 30 of the first counter word keeps this stream apart from the noise stream (first word
+ *   below 2^29) and from the subset stream (bit 31).  Box-Muller in fp64, one pair of words per pair of normals:
+ *       u1 = (w0 + 0.5) 2^-32, u2 = (w1 + 0.5) 2^-32 (exact, in (0, 1)); r = sqrt(-2 ln u1); t = 6.283185307179586 u2;
+ *       z0 = r cos t, z1 = r sin t for the elements 4g, 4g + 1; the same from (w2, w3) for 4g + 2, 4g + 3.
+ *   ln, sqrt, cos and sin are the device library's fp64 functions (a few fp64 ulp): a restatement in another libm agrees within
+ *   one step of the rounded fp32 (bf16) result, and device results agree with device results bit for bit.  sigma == 0 gives x
+ *   exactly (|z| < 6.8).  A sample's copies depend on (element, draw, id, seed, sigma) alone.
+ * Accumulate.  g [B,n_s,n] fp32 or bf16: the gradients of the copies s0 .. s0 + n_s - 1.  w [S] fp64, on the device, with
+ *   S >= s0 + n_s (the caller's promise: the entry does not know S).
+ *   acc [B,n] fp64, zeroed by the caller before the first chunk:  for j = 0 .. n_s - 1 in order
+ *       acc[b][i] = acc[b][i] + w[s0 + j] * t,   t = (double)g, or (double)g * (double)g (exact) when square != 0:
+ *   one fp64 multiplication and one fp64 addition per step, never an FMA.  The order is fixed by (b, i, s) alone, so any
+ *   chunking of S gives the same bits.
+ * Finish.  acc [B,C,HW] fp64; m [B,C,HW] fp32 or NULL (then the terms are acc's); out [B,HW] fp32; sums [B] fp64 or NULL.
+ *   Per pixel, with the terms t_c = (double)m * acc (one fp64 multiplication) for c = 0 .. C - 1 in order, from +0.0:
+ *       TE_GRAD_SUM      v = sum_c t_c            TE_GRAD_ABS_SUM  v = sum_c |t_c|            TE_GRAD_MAX_ABS  v = max_c |t_c|
+ *   (a NaN term makes v NaN in every mode).  out = v rounded once to fp32.  sums[b] = sum over the pixels of v in fp64: one
+ *   workgroup of 1024 per sample, thread t adds the pixel pairs t, t + 1024, ... in order, then the 64 lanes of a wave and the
+ *   16 waves meet in te_block_sum's fixed order -- an order fixed by HW alone.  It is the completeness side of Integrated
+ *   Gradients: sum of the map against f(x) - f(base).
+ * Alignment: pointers on their element's boundary (fp32 4 bytes, bf16 2, fp64 8), TE_ERR_UNSUPPORTED otherwise.  16-byte
+ *   accesses (8-byte for four bf16) where n % 4 == 0 (finish: HW % 2 == 0) and every pointer lies on the boundary of its
+ *   access, single elements elsewhere; the values and their order are the same either way.
+ * Refused on the host before any HIP call.  TE_ERR_INVALID_ARG: null pointers (all but m and sums), sizes <= 0, s0 < 0,
+ *   s0 + n_s > S (path inputs), d0 < 0, d0 + n_d > 2^32, sigma negative, NaN or infinite, an unknown `reduce`.  TE_ERR_UNSUPPORTED: a pointer
+ *   off its element's boundary, B > 65535, n, C or HW > 2^31 - 1, n_s or n_d > 2^31 - 1. */
+#define TE_GRAD_SUM 0
+#define TE_GRAD_ABS_SUM 1
+#define TE_GRAD_MAX_ABS 2
+int te_path_inputs_f32(const float* x, const float* base, const float* alphas, float* out, int64_t B, int64_t n, int64_t S,
+                       int64_t s0, int64_t n_s, te_stream_t stream);
+int te_path_inputs_bf16(const float* x, const float* base, const float* alphas, te_bf16_t* out, int64_t B, int64_t n, int64_t S,
+                        int64_t s0, int64_t n_s, te_stream_t stream);
+int te_gauss_inputs_f32(const float* x, float* out, int64_t B, int64_t n, int64_t d0, int64_t n_d, double sigma, int64_t seed,
+                        int64_t id0, te_stream_t stream);
+int te_gauss_inputs_bf16(const float* x, te_bf16_t* out, int64_t B, int64_t n, int64_t d0, int64_t n_d, double sigma,
+                         int64_t seed, int64_t id0, te_stream_t stream);
+int te_grad_accumulate_f32(const float* g, const double* w, double* acc, int64_t B, int64_t n, int64_t n_s, int64_t s0,
+                           int square, te_stream_t stream);
+int te_grad_accumulate_bf16(const te_bf16_t* g, const double* w, double* acc, int64_t B, int64_t n, int64_t n_s, int64_t s0,
+                            int square, te_stream_t stream);
+int te_grad_finish_f64(const double* acc, const float* m, float* out, double* sums, int64_t B, int64_t C, int64_t HW,
+                       int reduce, te_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ directory name carries a hyphen).  Layout:
   localisation.py                              pointing game, energy-based pointing game, relevance rank accuracy per (image, class) pair
   robustness.py                                max- / average-sensitivity, local Lipschitz estimate (Philox noise), Gini, entropy, effective complexity
   faithfulness.py                              infidelity and faithfulness correlation: random patch subsets (Philox), perturbation . attribution in fp64
+  gradients.py                                 Input x Gradient, SmoothGrad, Integrated Gradients: path / noise copies, fp64 gradient sums
   tuning/                           PyTorch TunableOp selection of the stock fp32 GEMMs of forward + backward
 """
 from . import _lib, ops, rules, rules_lrp  # noqa: F401

@@ -26,7 +26,7 @@ OBJ_DIR = os.path.join(PKG_DIR, "build")
 
 SOURCES = ["te_api.hip", "te_elementwise.hip", "te_linear.hip", "te_linear_x6.hip", "te_bf16.hip", "te_f64.hip", "te_attn.hip", "te_attn_mfma.hip", "te_attn_rules.hip", "te_attn_kb.hip", "te_attn_rc.hip", "te_attn_fwd6.hip", "te_attn_fwd6l.hip", "te_attn_bwd6l.hip", "te_attn_long.hip", "te_attn_bf16.hip", "te_norm_act.hip",
            "te_rollout.hip", "te_heatmap.hip", "te_conv.hip", "te_conv_bf16.hip", "te_perturb.hip", "te_segmetrics.hip", "te_rationale.hip", "te_headmask.hip",
-           "te_classes.hip", "te_mapsim.hip", "te_curves.hip", "te_localise.hip", "te_robust.hip", "te_faithful.hip", "te_attnlrp.hip", "te_attnlrp_patch.hip"]
+           "te_classes.hip", "te_mapsim.hip", "te_curves.hip", "te_localise.hip", "te_robust.hip", "te_faithful.hip", "te_attnlrp.hip", "te_attnlrp_patch.hip", "te_gradients.hip"]
 
 CXXFLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",

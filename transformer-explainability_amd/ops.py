@@ -2026,6 +2026,157 @@ def perturbation_dot(x: Tensor, y: Tensor, w: Tensor) -> Tensor:
     return out
 
 
+# ---------------------------------------------------------------------------------------- gradient baselines (gradients.py)
+# What surrounds the forward / backward loop of Input x Gradient, SmoothGrad and Integrated Gradients (include/te_relprop.h,
+# "gradient baselines"; csrc/te_gradients.hip).  The dtype of an entry is chosen from the tensor it writes or reads; on CPU
+# tensors every binding runs the restatement of gradients.py.
+GRAD_REDUCE = {"sum": _lib.TE_GRAD_SUM, "abs_sum": _lib.TE_GRAD_ABS_SUM, "max_abs": _lib.TE_GRAD_MAX_ABS}
+_COPY_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def _grad_tensor(what: str, name: str, t, dtypes, like: Optional[Tensor] = None) -> Tensor:
+    """A check that needs no device: a tensor of one of ``dtypes``, on the device of ``like`` (CPU or GPU alike)."""
+    if not torch.is_tensor(t):
+        raise _lib.TeError(f"{what}: {name} must be a tensor")
+    if t.dtype not in dtypes:
+        raise _lib.TeError(f"{what} takes {' or '.join(str(d) for d in dtypes)} for {name}, got {t.dtype}")
+    if like is not None and t.device != like.device:
+        raise _lib.TeError(f"{what}: {name} is on {t.device}, the other tensors on {like.device}")
+    return t
+
+
+def _copies_out(what: str, x: Tensor, n_copies: int, out_dtype, out: Optional[Tensor]) -> Tensor:
+    """The dense [B,n_copies,...] output of a kernel that writes copies of x [B,...]: ``out`` itself (its dtype decides the
+    entry), or a new tensor in ``out_dtype``."""
+    if out is None:
+        if out_dtype not in _COPY_DTYPES:
+            raise _lib.TeError(f"{what}: out_dtype must be float32 or bfloat16, got {out_dtype}")
+        if n_copies < 1:
+            raise _lib.TeError(f"{what}: at least one copy per sample, got {n_copies}")
+        return torch.empty((x.shape[0], n_copies) + tuple(x.shape[1:]), dtype=out_dtype, device=x.device)
+    out = _grad_tensor(what, "out", out, _COPY_DTYPES, x)
+    if out.dim() != x.dim() + 1 or out.shape[0] != x.shape[0] or out.shape[2:] != x.shape[1:] or out.numel() == 0 or \
+            not out.is_contiguous():
+        raise _lib.TeError(f"{what}: out must be a dense [B,copies,...] of x {tuple(x.shape)}, got {tuple(out.shape)}")
+    return out
+
+
+def path_inputs(x: Tensor, base: Tensor, alphas: Tensor, s0: int = 0, n_s: Optional[int] = None,
+                out_dtype: torch.dtype = torch.float32, out: Optional[Tensor] = None) -> Tensor:
+    """The copies of a straight path from ``base`` to ``x``, one launch: x and base [B,...] fp32, alphas [S] fp32 ->
+    [B,n_s,...] in ``out_dtype`` (or into ``out``, a dense [B,n_s,...] fp32 or bf16 tensor).  Copy j of sample b is
+    base + alphas[s0 + j] (x - base), formed in fp64 and rounded once to fp32 (bfloat16: once more, to nearest even)
+    (include/te_relprop.h, "gradient baselines"; ``gradients.reference_path_inputs`` gives the same bits)."""
+    what = "path_inputs"
+    x = _grad_tensor(what, "x", x, (torch.float32,))
+    base = _grad_tensor(what, "base", base, (torch.float32,), x)
+    alphas = _grad_tensor(what, "alphas", alphas, (torch.float32,), x)
+    if x.dim() < 2 or x.numel() == 0 or base.shape != x.shape or alphas.dim() != 1 or alphas.numel() == 0:
+        raise _lib.TeError(f"{what}: x and base must be [B,...] alike and not empty and alphas [S], got {tuple(x.shape)}, "
+                           f"{tuple(base.shape)} and {tuple(alphas.shape)}")
+    S, s0 = alphas.numel(), int(s0)
+    n_s = (out.shape[1] if torch.is_tensor(out) and out.dim() > 1 else S - s0) if n_s is None else int(n_s)
+    if s0 < 0 or n_s < 1 or s0 + n_s > S:
+        raise _lib.TeError(f"{what}: nodes {s0} .. {s0 + n_s - 1} are not nodes of the {S} alphas")
+    out = _copies_out(what, x, n_s, out_dtype, out)
+    if out.shape[1] != n_s:
+        raise _lib.TeError(f"{what}: out {tuple(out.shape)} does not hold {n_s} copies per sample")
+    if not x.is_cuda:
+        from .gradients import reference_path_inputs
+        return out.copy_(reference_path_inputs(x, base, alphas, s0, n_s, out.dtype))
+    x, base, alphas = _dense(x), _dense(base), _dense(alphas)
+    name = "te_path_inputs_f32" if out.dtype == torch.float32 else "te_path_inputs_bf16"
+    with _on_device(x) as lib:
+        _lib.check(getattr(lib, name)(_ptr(x), _ptr(base), _ptr(alphas), _ptr(out), x.shape[0], x[0].numel(), S, s0, n_s,
+                                      _stream(x)), name)
+    return out
+
+
+def gauss_inputs(x: Tensor, n_draws: int, sigma: float, seed: int, id0: int = 0, d0: int = 0,
+                 out_dtype: torch.dtype = torch.float32, out: Optional[Tensor] = None) -> Tensor:
+    """SmoothGrad's noisy copies, one launch: x [B,...] fp32 -> [B,n_draws,...] in ``out_dtype`` (or into ``out``, a dense
+    [B,n_draws,...] fp32 or bf16 tensor, whose second dimension then is n_draws).  Copy j of sample b is draw d0 + j of the
+    sample with the global id id0 + b: x + sigma z in fp64, rounded once, z standard normal by Box-Muller from Philox4x32-10
+    keyed by ``seed`` (include/te_relprop.h, "gradient baselines"; ``gradients.reference_gauss_inputs`` agrees within one
+    step of the result's format).  The bits of a sample's copies do not depend on the batch or on the chunk (d0, n_draws)."""
+    what = "gauss_inputs"
+    x = _grad_tensor(what, "x", x, (torch.float32,))
+    if x.dim() < 2 or x.numel() == 0:
+        raise _lib.TeError(f"{what}: x must be [B,...] and not empty, got {tuple(x.shape)}")
+    n_draws = int(n_draws)
+    out = _copies_out(what, x, n_draws, out_dtype, out)
+    if out.shape[1] != n_draws:
+        raise _lib.TeError(f"{what}: out {tuple(out.shape)} does not hold {n_draws} copies per sample")
+    sigma = _finite_not_negative(what, "sigma", sigma)
+    seed, id0, d0 = _philox_args(what, seed, id0, d0, n_draws)
+    if not x.is_cuda:
+        from .gradients import reference_gauss_inputs
+        return out.copy_(reference_gauss_inputs(x, n_draws, sigma, seed, id0, d0, out.dtype))
+    x = _dense(x)
+    name = "te_gauss_inputs_f32" if out.dtype == torch.float32 else "te_gauss_inputs_bf16"
+    with _on_device(x) as lib:
+        _lib.check(getattr(lib, name)(_ptr(x), _ptr(out), x.shape[0], x[0].numel(), d0, n_draws, sigma, seed, id0,
+                                      _stream(x)), name)
+    return out
+
+
+def grad_accumulate(g: Tensor, w: Tensor, acc: Tensor, s0: int = 0, square: bool = False) -> Tensor:
+    """acc[b] += sum_j w[s0 + j] t(g[b, j]) in place, j ascending, one fp64 multiply and one fp64 add per step: g [B,n_s,...]
+    fp32 or bf16 (the input gradients of a pass of copies), w fp64 [S], acc fp64 [B,...] dense, zeroed by the caller;
+    t = g, or g g with ``square``.  The bits do not depend on how S is cut into passes
+    (``gradients.reference_accumulate`` gives the same bits).  Returns acc."""
+    what = "grad_accumulate"
+    g = _grad_tensor(what, "g", g, _COPY_DTYPES)
+    w = _grad_tensor(what, "w", w, (torch.float64,), g)
+    acc = _grad_tensor(what, "acc", acc, (torch.float64,), g)
+    if g.dim() < 3 or g.numel() == 0 or acc.dim() < 2 or acc.shape[0] != g.shape[0] or acc[0].numel() != g[0, 0].numel() or \
+            w.dim() != 1 or not acc.is_contiguous():
+        raise _lib.TeError(f"{what}: g must be [B,n_s,...], acc a dense [B,...] with as many values per sample and w [S], got "
+                           f"{tuple(g.shape)}, {tuple(acc.shape)} and {tuple(w.shape)}")
+    B, n_s, s0 = g.shape[0], g.shape[1], int(s0)
+    if s0 < 0 or s0 + n_s > w.numel():
+        raise _lib.TeError(f"{what}: copies {s0} .. {s0 + n_s - 1} are not among the {w.numel()} weights")
+    if not g.is_cuda:
+        from .gradients import reference_accumulate
+        return reference_accumulate(g, w, acc, s0, square)
+    g, w = _dense(g), _dense(w)
+    name = "te_grad_accumulate_f32" if g.dtype == torch.float32 else "te_grad_accumulate_bf16"
+    with _on_device(g) as lib:
+        _lib.check(getattr(lib, name)(_ptr(g), _ptr(w), _ptr(acc), B, acc[0].numel(), n_s, s0, 1 if square else 0,
+                                      _stream(g)), name)
+    return acc
+
+
+def grad_finish(acc: Tensor, m: Optional[Tensor] = None, reduce: str = "sum", with_sums: bool = True):
+    """acc fp64 [B,C,...] (``grad_accumulate``), m fp32 shaped like acc or None -> (map fp32 [B,...], sums fp64 [B] or None):
+    per pixel v = the ``reduce`` ("sum", "abs_sum", "max_abs") over the channels, in order, of the fp64 terms m acc (acc
+    itself without m); the map is v rounded once, sums its per-sample total in fp64 in a fixed order, one launch, no
+    synchronisation (``gradients.reference_finish``)."""
+    what = "grad_finish"
+    if reduce not in GRAD_REDUCE:
+        raise _lib.TeError(f"{what}: reduce must be one of {tuple(GRAD_REDUCE)}, got {reduce!r}")
+    acc = _grad_tensor(what, "acc", acc, (torch.float64,))
+    if acc.dim() < 3 or acc.numel() == 0:
+        raise _lib.TeError(f"{what}: acc must be [B,C,...] and not empty, got {tuple(acc.shape)}")
+    if m is not None:
+        m = _grad_tensor(what, "m", m, (torch.float32,), acc)
+        if m.shape != acc.shape:
+            raise _lib.TeError(f"{what}: m {tuple(m.shape)} is not shaped like acc {tuple(acc.shape)}")
+    if not acc.is_cuda:
+        from .gradients import reference_finish
+        out, sums = reference_finish(acc, m, reduce)
+        return out, (sums if with_sums else None)
+    acc = _dense(acc)
+    m = None if m is None else _dense(m)
+    B, C = acc.shape[0], acc.shape[1]
+    out = torch.empty((B,) + tuple(acc.shape[2:]), dtype=torch.float32, device=acc.device)
+    sums = torch.empty((B,), dtype=torch.float64, device=acc.device) if with_sums else None
+    with _on_device(acc) as lib:
+        _lib.check(lib.te_grad_finish_f64(_ptr(acc), _ptr(m), _ptr(out), _ptr(sums), B, C, acc[0, 0].numel(), GRAD_REDUCE[reduce],
+                                          _stream(acc)), "te_grad_finish_f64")
+    return out, sums
+
+
 # ---------------------------------------------------------------------------------------- bf16 operands
 # A bf16 model's rules: the reference's algorithm evaluated in fp32 on the model's own bf16 tensors (read exactly: bf16 ->
 # fp32 is exact).  Relevance, safe_divide, per-sample sums and the rollout stay fp32; Linear's Z is X+ W+^T + X- W-^T from
